@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — candidate MIPs scored / second on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config practice62|regions5k|exome|exome_snp] [--regions R]
+    python bench.py --gpus N --steps K --warmup W [--config practice62|regions5k|exome|exome_snp] [--regions R] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs if --dump-outputs is given, and prints its line (`value`,
+`ms_per_step`, the per-kernel times and roofline of those same steps).  Everything that takes runs of its own - the in-run parity gate, the
+HBM traffic passes, `exome_strong` / `scale_base`, the `extra` lines and the CPU baseline - runs only with --full (each still switched off by
+its --no-* option).
+
+--dump-outputs DIR  what a caller of the timed path receives after the last timed step (mipgen_accel_download_survivors; with N > 1 ranks
+                    the survivors rank 0 gathered from every rank), as float64 arrays: DIR/emitted.npy (emitted candidates per region of
+                    rank 0), DIR/survivor_{cand_index,score,record_lo,record_hi}.npy (the 64-bit record as two exact 32-bit halves).  Above
+                    64 MB in all, a fixed seeded sample of the survivor rows is written and DIR/survivor_rows.npy names them.
 
 A "step" is one pass of the hot path over the resident batch, the way a -silent_mode design runs it (mipgen_accel_score_condense_all):
 for every region the dense candidate grid is constructed (integer records of design_mip), scored (libsvm RBF-SVR or logistic), and the
@@ -15,10 +25,10 @@ Workloads (mipgen_amd/workloads.py; no real genome / BED / trained model exists 
                         with the logistic score) or --method svr
   exome / exome_snp     configs[3] / [4] shape: --regions R of the 200,000 exon-like intervals, capture 150-170 / 120-250, SVR
 
-N = 1 (default): practice62 / SVR (configs[1], the config the 1-GPU metric is quoted on); the metric's own multi-GPU config - ALL 200,000 exons of
+N = 1 (default): practice62 / SVR (configs[1], the config the 1-GPU metric is quoted on); with --full the metric's own multi-GPU config - ALL 200,000 exons of
 configs[3] - is timed in the same run on this one GPU (`exome_strong` = `scale_base`; its value and roofline also inside `config.exome_full` /
 `roofline.exome_full`, where the driver's record keeps them); `extra` carries the round-5 shard of 65,536 exons, a sustained (>= 2 s) run of the
-headline, the nSV sweep, the logistic scorer, the mixed-mode list re-scorer and the k-mer counter.  Before anything is timed an in-run PARITY GATE scores regions of the bench batch and
+headline, the nSV sweep, the logistic scorer, the mixed-mode list re-scorer and the k-mer counter.  With --full, before anything is timed an in-run PARITY GATE scores regions of the bench batch and
 compares records / scores / replay / condensed survivors with the oracle (the checker only: nothing the oracle computes is timed or reported
 as a rate) - SURVEY.md section 8d "correctness gate run with every measurement".
 
@@ -30,7 +40,7 @@ with ONE gather of the condensed survivors to rank 0 (RCCL over xGMI), where the
 
 The scaling curve (driver: `bench.py --gpus N` for N = 1, 2, 4, 8) is ONE workload family in `value`: the configs[1] headline batch, weak-scaled
 (`scale_family` names it in every line), so value(N) / (N value(1)) is a like-for-like efficiency.  The metric's own multi-GPU config (configs[3],
-the exome) rides along in every line as `exome_strong`: all 200,000 exons cut N ways, one timed pass with its gather (at N = 1 the same
+the exome) rides along in every --full line as `exome_strong`: all 200,000 exons cut N ways, one timed pass with its gather (at N = 1 the same
 object is also printed as `scale_base`); divide exome_strong.value of an N-rank line by the one of the N = 1 line - never by `value`.
 Every line names `rccl_ranks` (the world size torch.distributed reports after init_process_group; 1 without a process group) and the dense
 candidates of every rank.
@@ -39,7 +49,7 @@ candidates of every rank.
                     exome_snp): tiles whose positions have all stopped are not scored.  `value` then counts the candidates that WERE scored
                     (`config.dense_candidates_covered_per_s` is the covered rate); the headline config (nine sizes: one run) is not affected.
 --measure-traffic   HBM bytes of the dominant kernel measured in THIS run: two child `rocprofv3 --pmc` passes (FETCH_SIZE, WRITE_SIZE - they do
-                    not share a pass) of the same workload, started before this process touches the GPU (the default N = 1 line does this by
+                    not share a pass) of the same workload, started before this process touches the GPU (the default N = 1 --full line does this by
                     itself: ~40 s; --no-measure-traffic switches it off); `roofline.traffic` then comes from
                     them (FETCH_SIZE doubled: the gfx950 correction of MI355X_MICROARCH.md, HBM section) instead of from profiles/.
 
@@ -48,11 +58,14 @@ Prints ONE JSON line on rank 0.
 from __future__ import annotations
 
 import argparse
+import atexit
 import glob
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -99,7 +112,7 @@ def parse_args():
     ap.add_argument("--scale-base-regions", type=int, default=200000, help="exons of `exome_strong` / `scale_base` (0 = skip): ALL of BASELINE configs[3] by default - "
                     "one timed pass on the one GPU at N = 1, cut N ways at --gpus N")
     ap.add_argument("--measure-traffic", action="store_true", help="measure the dominant kernel's HBM bytes in this run (child rocprofv3 --pmc passes); the default "
-                    "N = 1 run (practice62, no --no-extras) does so by itself")
+                    "N = 1 --full run (practice62, no --no-extras) does so by itself")
     ap.add_argument("--no-measure-traffic", action="store_true", help="never start the child rocprofv3 passes (the traffic then comes from profiles/)")
     ap.add_argument("--dynamic-skip", action="store_true", help="mipgen.cpp:430 between the capture-size runs of the dense SVR scorer (regions of more than nine "
                     "capture sizes): tiles whose positions have all stopped are not scored; `value` then counts the candidates that WERE scored")
@@ -108,6 +121,10 @@ def parse_args():
     ap.add_argument("--share-gpus", action="store_true", help="tests only: ranks beyond the visible devices share them (rank r on GPU r mod devices; gloo only)")
     ap.add_argument("--force-dist", action="store_true", help="tests only: take the N > 1 code path (process group, per-step gather) with a world of ONE rank - "
                     "the RCCL calls of the step on a one-GPU box; needs RANK / WORLD_SIZE / MASTER_* in the environment (torch.distributed.run --nproc-per-node 1)")
+    ap.add_argument("--full", action="store_true", help="also run what takes runs of its own: the parity gate, the traffic passes, exome_strong, the extras and "
+                    "the CPU baseline (each still switched off by its --no-* option); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (emitted counts, condensed survivors) as "
+                    "float64 .npy files under DIR (at most 64 MB: a fixed seeded sample of the survivor rows beyond that)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", str(a.gpus)))
     if a.config is None:
@@ -345,8 +362,6 @@ def cpu_baseline(args, model_path: str, n_sv: int) -> dict:
              (emitted candidates of its region / its tile_regions time), every process timed while all the others run.  tile_regions time =
              from the reference's own "[mipgen] bwa copy number analysis finished" line (mipgen.cpp:349) to exit: enumeration + scoring +
              selection, WITHOUT the input stage and the FASTQ / stand-in bwa (awk) I/O, which the GPU figure does not cover either."""
-    import shutil
-    import tempfile
     from concurrent.futures import ThreadPoolExecutor
     from mipgen_amd import capi, synth, workloads
     from oracle import run_reference as rr
@@ -447,8 +462,6 @@ def measure_traffic(args, kernel: str):
     Counter unit: KiB.  FETCH_SIZE is doubled (MI355X_MICROARCH.md, HBM: gfx950 tallies 128-byte requests of coalesced reads at 64 bytes; the raw
     value is kept beside it), WRITE_SIZE is taken as it reads.  Returns None when rocprofv3 is missing or a pass fails."""
     import csv
-    import shutil
-    import tempfile
     exe = shutil.which("rocprofv3")
     if not exe:
         return None
@@ -493,6 +506,26 @@ def measure_traffic(args, kernel: str):
             "launches_averaged": min(got["FETCH_SIZE"][1], got["WRITE_SIZE"][1]), "kernel": kernel, "child_command": " ".join(base[1:]),
             "how": "child `rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of this workload (--steps 2 --warmup 1), mean per launch, "
                    "summed over the device; counter unit KiB; FETCH_SIZE x 2 = the gfx950 correction (MI355X_MICROARCH.md, HBM section)"}
+
+
+def dump_outputs(out_dir: str, emitted, surv, cap_bytes: int = 64 << 20, seed: int = 20140101) -> None:
+    """--dump-outputs: the emitted counts and the condensed survivors as float64 .npy files (every value exact: counts and candidate indices stay
+    below 2^53, the 64-bit record is split into two 32-bit halves).  Above cap_bytes in all, a sample of the survivor rows drawn with a fixed seed
+    from their count alone (so two builds given the same arguments pick the same rows) is written, and survivor_rows.npy names the rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {"survivor_cand_index": surv["cand_index"], "survivor_score": surv["score"],
+            "survivor_record_lo": surv["record"] & np.uint64(0xFFFFFFFF), "survivor_record_hi": surv["record"] >> np.uint64(32)}
+    n = surv.shape[0]
+    max_rows = (cap_bytes - 8 * emitted.shape[0] - 4096) // (8 * (len(cols) + 1))      # 4 KiB for the .npy headers; +1: survivor_rows
+    arrays = {"emitted": emitted}
+    if n > max_rows:
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=max_rows, replace=False))
+        cols = {k: v[rows] for k, v in cols.items()}
+        arrays["survivor_rows"] = rows
+    arrays.update(cols)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def newest_profile(pattern: str):
@@ -631,7 +664,7 @@ def main() -> None:
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
     traffic_run = None
-    default_line = args.gpus == 1 and args.config == "practice62" and not args.no_extras and not args.method and not args.regions
+    default_line = args.full and args.gpus == 1 and args.config == "practice62" and not args.no_extras and not args.method and not args.regions
     if (args.measure_traffic or default_line) and not args.no_measure_traffic and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # child rocprofv3 passes, before this process initialises the GPU
         traffic_run = measure_traffic(args, "k_svr_dense" if (args.method or CONFIGS[args.config][1]) == "svr" else "k_logistic_dense")
@@ -661,7 +694,10 @@ def main() -> None:
             dist.init_process_group(backend="gloo")
 
     P, method, model_genome, build, desc, global_dense = assemble(args, rank, world)
-    cache = os.path.join(ROOT, "gpurun_out", "bench_cache") + ("" if rank == 0 else f"_r{rank}")
+    # the synthetic SVR models are generated per run (under half a second for the headline's) in a directory of this process: the checkout may be
+    # read-only for the user who runs the benchmark
+    cache = tempfile.mkdtemp(prefix="mipgen_bench_")
+    atexit.register(shutil.rmtree, cache, True)
     stream = torch.cuda.current_stream().cuda_stream
     acc = capi.Accel(P, device=local_rank, stream=stream)
     m = capi.SCORE_SVR if method == "svr" else capi.SCORE_LOGISTIC
@@ -688,7 +724,7 @@ def main() -> None:
 
     # correctness gate of this measurement: rank 0 checks its batch against the oracle before anything is timed
     gate = None
-    if rank == 0 and not args.no_parity_gate:
+    if rank == 0 and args.full and not args.no_parity_gate:
         gate = parity_gate(acc, P, regions, grids, method, model_path, local_rank, stream)
     for _ in range(args.warmup):
         step()
@@ -728,7 +764,7 @@ def main() -> None:
         rccl_ranks = 1
     # the metric's own multi-GPU config beside the headline family, at every N: all 200,000 exons of configs[3] cut `world` ways (collective calls: every rank)
     exome_strong = None
-    if args.scale_base_regions > 0 and args.config == "practice62" and method == "svr" and not args.no_extras and not args.regions:
+    if args.full and args.scale_base_regions > 0 and args.config == "practice62" and method == "svr" and not args.no_extras and not args.regions:
         exome_strong = exome_line(args, local_rank, stream, model_path, n_regions=args.scale_base_regions, rank=rank, world=world, distributed=distributed, xdev=xdev)
 
     if rank == 0:
@@ -738,6 +774,9 @@ def main() -> None:
             survivors_gathered = sum(gather.sizes) // 24
             head = gather.recv[0][:gather.sizes[0]].cpu().numpy().view(capi.SURVIVOR_DTYPE)
             assert np.array_equal(head["cand_index"], surv["cand_index"]), "rank 0's own slice of the gather differs from its survivors"
+        if args.dump_outputs:
+            got = surv if not distributed else np.concatenate([gather.recv[r][:gather.sizes[r]].cpu().numpy().view(capi.SURVIVOR_DTYPE) for r in range(world)])
+            dump_outputs(args.dump_outputs, emitted, got)
         # with --dynamic-skip only the candidates that were scored count: the skipped candidates of EVERY rank are left out
         value = (total_cand - sum(skipped_per_rank)) * args.steps / dt
         k_ms = float(np.mean(kernel_ms))
@@ -842,7 +881,7 @@ def main() -> None:
             except Exception:
                 pass
         # ---- extras (N = 1, default workload): throughput vs nSV, and the logistic scorer on the same batch -------------------------
-        if not args.no_extras and not distributed and args.config == "practice62" and method == "svr":
+        if args.full and not args.no_extras and not distributed and args.config == "practice62" and method == "svr":
             extra = []
             if exome_strong:
                 # the N = 1 point of the exome's strong-scaling curve under its round-4 name as well
@@ -955,7 +994,7 @@ def main() -> None:
                                        "algorithmic_bytes_per_launch": gsz}})
             out["extra"] = extra
             acc.load_model_file(model_path)
-        if not args.no_cpu_baseline and not distributed:
+        if args.full and not args.no_cpu_baseline and not distributed:
             mp = model_path or workloads.svr_model_path(cache, model_genome, args.nsv, rho=MODEL_RHO)
             try:
                 out["cpu_baseline"] = cpu_baseline(args, mp, args.nsv)

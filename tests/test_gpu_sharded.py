@@ -105,7 +105,7 @@ def test_bench_two_ranks_child_process():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two visible GPUs")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale-base-regions", "2048", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale-base-regions", "2048", "--no-cpu-baseline", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -137,7 +137,7 @@ def test_bench_two_ranks_logic_through_gloo_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpus", "--steps", "2", "--warmup", "1",
-                        "--scale-base-regions", "2048", "--exome-regions", "0", "--sustain-seconds", "0", "--no-cpu-baseline"],
+                        "--scale-base-regions", "2048", "--exome-regions", "0", "--sustain-seconds", "0", "--no-cpu-baseline", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -166,7 +166,7 @@ def test_bench_scale_base_line_is_the_sharded_workload():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "exome", "--regions", "2048", "--scaling", "strong",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["scaling"] == "strong"
@@ -284,14 +284,14 @@ def test_bench_and_mp_design_take_their_rccl_code_path_with_one_rank(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=root)
     launch = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1"]
     p = subprocess.run(launch + ["--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                                 "--no-extras", "--no-measure-traffic"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env=env)
+                                 "--no-extras", "--no-measure-traffic", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert line["rccl_ranks"] == 1 and line["backend"] == "nccl" and line["parity_checked"] is True
     assert line["config"]["survivors_gathered_per_step"] == line["config"]["survivors_rank0"] > 0        # the gather ran, on device memory
     # the exome beside the headline family (`exome_strong`: shards, gather straight from HBM, max over ranks) takes its RCCL path too
     p = subprocess.run(launch + ["--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-                                 "--no-measure-traffic", "--no-parity-gate", "--scale-base-regions", "1024", "--exome-regions", "0", "--sustain-seconds", "0"],
+                                 "--no-measure-traffic", "--no-parity-gate", "--scale-base-regions", "1024", "--exome-regions", "0", "--sustain-seconds", "0", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])

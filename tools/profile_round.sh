@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/profile_round.sh TAG — the measurements behind DESIGN.md / bench.py's roofline object, on the MI355X box.  Everything is taken from
 # the DRIVER's own command line (`bench.py --steps 20 --warmup 5`), so that profiles/ and BENCH_rNN.json can be recomputed from each other:
-#   1. bench.py --steps 20 --warmup 5 --measure-traffic   -> gpurun_out/TAG_bench.json   (roofline.traffic measured in that run)
+#   1. bench.py --steps 20 --warmup 5 --full --measure-traffic   -> TAG_bench.json in the output directory   (roofline.traffic measured in that run)
 #   2. rocprofv3 --kernel-trace --stats of the same command (25 launches of every kernel; no parity gate / extras / CPU baseline in the
 #      profiled process) -> gpurun_out/TAG_kernel_stats.csv (rocprofv3's own summary) and TAG_kernel_summary.json: per kernel the number of
 #      calls, average, median, minimum and the average WITHOUT the first (cold) call, from the kernel trace itself
@@ -15,7 +15,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python3 "$R/bench.py" --steps 20 --warmup 5 --measure-traffic > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+python3 "$R/bench.py" --steps 20 --warmup 5 --full --measure-traffic > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 tail -c 400 "$OUT/${TAG}_bench.json"; echo
 rm -rf "$OUT/prof_$TAG"
 B="--steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-parity-gate --no-measure-traffic"
