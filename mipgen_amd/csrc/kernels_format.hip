@@ -16,6 +16,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "fmt_g6.h"
+#include "mip_record.h"
 
 struct FmtRegion {                    // per region of the window: what print_details reads from Featurev5
     int32_t chr_off, chr_len;         // into the string pool
@@ -53,14 +54,6 @@ __device__ __forceinline__ int nint(int64_t v) { return v < 0 ? 1 + ndigits((uin
 __device__ __forceinline__ char comp_letter(char c)
 {
     switch (c) { case 'A': return 'T'; case 'T': return 'A'; case 'G': return 'C'; case 'C': return 'G'; default: return c; }   // MinusSVMipv4.cpp:6-29
-}
-
-// copy number as the reference prints it: the table's value, not the record's saturating field
-__device__ __forceinline__ int true_copy(const DevParams* P, const DevRegion& R, const int32_t* copy, int start, int len, uint32_t rec_field)
-{
-    if (rec_field != 65535u || R.copy_off < 0) return (int)rec_field;
-    const int slot = P->len_slot[len], ri = start - R.seq_start;
-    return (slot >= 0 && ri >= 0 && ri < R.seq_len) ? copy[R.copy_off + (int64_t)slot * R.seq_len + ri] : 0;
 }
 
 struct Geometry { int ext_start, ext_stop, lig_start, lig_stop, scan_stop; };
@@ -136,7 +129,7 @@ __device__ __forceinline__ int record_length(const Cand& c, const DevParams* P, 
     const Geometry G = geometry(c);
     char tmp[24];
     const int ls = fmt_g6(score, tmp, d_pow10);
-    const int ec = true_copy(P, R, copy, G.ext_start, c.e, MIPGEN_REC_EXT_COPY(rec)), lc = true_copy(P, R, copy, G.lig_start, c.l, MIPGEN_REC_LIG_COPY(rec));
+    const int ec = true_arm_copy(P, R, copy, G.ext_start, c.e, MIPGEN_REC_EXT_COPY(rec)), lc = true_arm_copy(P, R, copy, G.lig_start, c.l, MIPGEN_REC_LIG_COPY(rec));
     const int le = seq_len_clipped(R, G.ext_start, c.e), ll = seq_len_clipped(R, G.lig_start, c.l), li = seq_len_clipped(R, c.p, c.ss);
     int n = 0;
     n += F.chr_len + 1 + nint(c.s == 0 ? G.ext_start : G.lig_start) + 1 + nint(c.s == 0 ? G.lig_stop : G.ext_stop) + 1 + nint(c.e) + 1 + nint(c.l) + 1 + 1;   // key
@@ -151,7 +144,7 @@ __device__ __forceinline__ int write_record(char* out, const Cand& c, const DevP
 {
     const Geometry G = geometry(c);
     const bool minus = c.s != 0;
-    const int ec = true_copy(P, R, copy, G.ext_start, c.e, MIPGEN_REC_EXT_COPY(rec)), lc = true_copy(P, R, copy, G.lig_start, c.l, MIPGEN_REC_LIG_COPY(rec));
+    const int ec = true_arm_copy(P, R, copy, G.ext_start, c.e, MIPGEN_REC_EXT_COPY(rec)), lc = true_arm_copy(P, R, copy, G.lig_start, c.l, MIPGEN_REC_LIG_COPY(rec));
     const uint32_t f = MIPGEN_REC_FLAGS(rec);
     int n = 0;
     auto chr = [&]() { for (int i = 0; i < F.chr_len; i++) out[n++] = pool[F.chr_off + i]; };

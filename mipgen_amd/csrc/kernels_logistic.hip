@@ -17,6 +17,7 @@
 #include "device_utils.h"
 
 #include "logistic_device.h"
+#include "mip_record.h"
 
 // grid = number of tiles; block = LOG_THREADS; dynamic LDS = lds_bytes(span_max)
 #define LOG_RINV 512
@@ -98,53 +99,28 @@ __global__ __launch_bounds__(LOG_THREADS) void k_records_logistic(
         const int ss = C - e - l;
         const int p = p_first + (int)pl;
 
-        // bounds skips, mipgen.cpp:443-444
-        bool valid = !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) && ss > 0;
+        const bool valid = !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) && ss > 0;   // :443-444
         uint64_t rec = 0;
         double score = 0.0;
         if (valid) {
-            // geometry: PlusSVMipv4.cpp:9-12 / MinusSVMipv4.cpp:32-35
-            const int ext_start = minus ? p + ss : p - e;
-            const int lig_start = minus ? p - l : p + ss;
+            const ArmStarts st = arm_starts(p, ss, e, l, minus);
+            const int ext_start = st.ext, lig_start = st.lig;
             const int be = ext_start - lo, bl = lig_start - lo, bi = p - lo;    // tile-local
             const uint64_t e0 = W0[be + e] - W0[be], l0 = W0[bl + l] - W0[bl];
             const uint64_t e1 = W1[be + e] - W1[be], l1 = W1[bl + l] - W1[bl];
             const bool guard = (f16(e0, 3) + f16(l0, 3)) != 0;                  // SVMipv4.cpp:63,116
-
-            // copies, mipgen.cpp:612-613 (absent key -> 0)
-            int ext_copy = 1, lig_copy = 1;
-            if (R.copy_off >= 0) {
-                const int se = P->len_slot[e], sl = P->len_slot[l];
-                const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-                ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-                lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-            }
-            // mapping flag, mipgen.cpp:615-625
-            bool mapping = false;
-            if (R.unmap_off >= 0 && P->check_copy_number) {
-                const int ms = (minus ? lig_start : ext_start) - R.seq_start;
-                if (ms >= 0 && ms < R.seq_len) mapping = unmap[R.unmap_off + (int64_t)(R.k0 + (int)ki) * R.seq_len + ms] != 0;
-            }
+            const int ext_copy = oligo_copy(P, R, copy, ext_start, e), lig_copy = oligo_copy(P, R, copy, lig_start, l);
+            const bool mapping = unmapped(P, R, unmap, R.k0 + (int)ki, minus, ext_start, lig_start);
             const uint32_t masked_n = f16(e1, 0) + f16(l1, 0);
-            uint32_t flags = MIPGEN_FLAG_VALID | (guard ? MIPGEN_FLAG_GUARD : 0u);
-            uint32_t snp_count = 0;
-            if (mapping) {
-                flags |= MIPGEN_FLAG_MAPPING;                   // early return: masking/SNP fields stay at their defaults
-            } else {
-                if ((double)masked_n / (double)(l + e) > thr) flags |= MIPGEN_FLAG_MASKING;     // :610,626
-                snp_count = f16(e1, 1) + f16(l1, 1);
-                const uint32_t snp_bad = f16(e1, 2) + f16(l1, 2), snp_ok = f16(e1, 3) + f16(l1, 3);
-                if (snp_bad != 0 || snp_count > 1) flags |= MIPGEN_FLAG_SNP;                    // :690-693,759-760
-                if (snp_ok != 0) flags |= MIPGEN_FLAG_HAS_SNP_MIP;
-            }
+            int snp_count;
+            const uint32_t flags = record_flags(mapping, (int)masked_n, l + e, thr, (int)(f16(e1, 1) + f16(l1, 1)), (int)(f16(e1, 2) + f16(l1, 2)),
+                                                (int)(f16(e1, 3) + f16(l1, 3)), guard, snp_count);
             // ligation junction = first two bases of the oriented ligation arm
             int j0, j1;
             if (!minus) { j0 = sb[bl] & BASE_CODE_MASK; j1 = sb[bl + 1] & BASE_CODE_MASK; }
             else { j0 = comp_code(sb[bl + l - 1] & BASE_CODE_MASK); j1 = comp_code(sb[bl + l - 2] & BASE_CODE_MASK); }
-            const uint32_t jc = (j0 < 4 && j1 < 4) ? (uint32_t)(4 * j0 + j1) : 255u;
-            const uint32_t ec = (uint32_t)min(max(ext_copy, 0), 65535), lc = (uint32_t)min(max(lig_copy, 0), 65535);
-            rec = (uint64_t)ec | ((uint64_t)lc << 16) | ((uint64_t)min(masked_n, 255u) << 32) |
-                  ((uint64_t)min(snp_count, 255u) << 40) | ((uint64_t)flags << 48) | ((uint64_t)jc << 56);
+            const uint32_t jc = junction_code(j0, j1);
+            rec = pack_record(ext_copy, lig_copy, (int)masked_n, snp_count, flags, jc);
 
             if (SCORE) {
                 if (guard) score = -1000.0;

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include "common.h"
 #include "device_utils.h"
+#include "mip_record.h"
 #include "logistic_device.h"
 #include "pow_base_cr.h"
 
@@ -83,8 +84,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
     const int p = c.scan_start, C = c.capture_size, e = c.ext_len, l = c.lig_len;
     const bool minus = c.strand != 0;
     const int ss = C - e - l;
-    const bool valid = !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) &&
-                       ss > 0 && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
+    const bool valid = constructed(R, p, C, e, l) && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
     if (!valid) {
         if (tid == 0) {
             if (scores) scores[blockIdx.x] = 0.0;
@@ -94,8 +94,8 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
         if (ints_out && tid == 0) { mipgen_candidate_ints z = {}; ints_out[blockIdx.x] = z; }
         return;
     }
-    const int ext_start = minus ? p + ss : p - e;
-    const int lig_start = minus ? p - l : p + ss;
+    const ArmStarts st = arm_starts(p, ss, e, l, minus);
+    const int ext_start = st.ext, lig_start = st.lig;
     auto base_at = [&](int pos) -> uint8_t {
         int ri = pos - R.seq_start;
         return (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
@@ -129,28 +129,11 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
                 bad += (code == BASE_N || code == BASE_DASH);
             }
         }
-        int ext_copy = 1, lig_copy = 1;
-        if (R.copy_off >= 0) {
-            const int se = P->len_slot[e], sl = P->len_slot[l];
-            const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-            ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-            lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-        }
-        bool mapping = false;
+        const int ext_copy = oligo_copy(P, R, copy, ext_start, e), lig_copy = oligo_copy(P, R, copy, lig_start, l);
         const int k = (P->max_capture - C) / P->inc;
-        if (R.unmap_off >= 0 && P->check_copy_number && k >= 0 && k < P->n_sizes_all) {
-            const int ms = (minus ? lig_start : ext_start) - R.seq_start;
-            if (ms >= 0 && ms < R.seq_len) mapping = unmap[R.unmap_off + (int64_t)k * R.seq_len + ms] != 0;
-        }
-        uint32_t flags = MIPGEN_FLAG_VALID | (bad ? MIPGEN_FLAG_GUARD : 0u);
-        int snp_count = 0;
-        if (mapping) flags |= MIPGEN_FLAG_MAPPING;
-        else {
-            if ((double)masked_n / (double)(l + e) > P->masked_arm_threshold) flags |= MIPGEN_FLAG_MASKING;
-            snp_count = snp_any;
-            if (snp_bad != 0 || snp_count > 1) flags |= MIPGEN_FLAG_SNP;
-            if (snp_ok != 0) flags |= MIPGEN_FLAG_HAS_SNP_MIP;
-        }
+        const bool mapping = k >= 0 && k < P->n_sizes_all && unmapped(P, R, unmap, k, minus, ext_start, lig_start);
+        int snp_count;
+        const uint32_t flags = record_flags(mapping, masked_n, l + e, P->masked_arm_threshold, snp_any, snp_bad, snp_ok, bad != 0, snp_count);
         s_info[0] = ext_copy; s_info[1] = lig_copy; s_info[2] = masked_n; s_info[3] = snp_count; s_info[4] = (int)flags;
         s_info[5] = bad;
     }
@@ -158,7 +141,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
     const int ext_copy = s_info[0], lig_copy = s_info[1];
     const bool guard = s_info[5] != 0;
     const int j0 = s_lig[0], j1 = s_lig[1];
-    const int jc = (j0 < 4 && j1 < 4) ? 4 * j0 + j1 : 255;
+    const int jc = (int)junction_code(j0, j1);
 
     // mer counts: one lane per mer.  The oriented insert passes through LDS in pieces of MAX_INSERT bases (+ two of look-ahead for the 2- / 3-mers
     // that start in a piece): one piece for every realistic capture size, no limit on the others; the class-switch walk (SVMipv4.cpp:118-142) of the
@@ -229,9 +212,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
             ints_out[blockIdx.x] = o;
         }
         if (records) {
-            const uint32_t ec = (uint32_t)min(max(ext_copy, 0), 65535), lc = (uint32_t)min(max(lig_copy, 0), 65535);
-            records[blockIdx.x] = (uint64_t)ec | ((uint64_t)lc << 16) | ((uint64_t)min(s_info[2], 255) << 32) |
-                                  ((uint64_t)min(s_info[3], 255) << 40) | ((uint64_t)(uint32_t)s_info[4] << 48) | ((uint64_t)(uint32_t)jc << 56);
+            records[blockIdx.x] = pack_record(ext_copy, lig_copy, s_info[2], s_info[3], (uint32_t)s_info[4], (uint32_t)jc);
         }
         if (method == MIPGEN_SCORE_LOGISTIC) {
             if (guard) logistic = -1000.0;
@@ -335,16 +316,15 @@ __global__ __launch_bounds__(FB_WAVES * 64) void k_features_batch(
     const int p = c.scan_start, C = c.capture_size, e = c.ext_len, l = c.lig_len;
     const bool minus = c.strand != 0;
     const int ss = C - e - l;
-    const bool valid = !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) &&
-                       ss > 0 && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
+    const bool valid = constructed(R, p, C, e, l) && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
     double* fo = features + (int64_t)ci * MIPGEN_N_FEATURES;
     if (!valid) {
         if (lane == 0) records[ci] = 0;
         for (int j = lane; j < MIPGEN_N_FEATURES; j += 64) fo[j] = 0.0;
         return;
     }
-    const int ext_start = minus ? p + ss : p - e;
-    const int lig_start = minus ? p - l : p + ss;
+    const ArmStarts st = arm_starts(p, ss, e, l, minus);
+    const int ext_start = st.ext, lig_start = st.lig;
     auto base_at = [&](int pos) -> uint8_t {
         const int ri = pos - R.seq_start;
         return (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
@@ -362,39 +342,18 @@ __global__ __launch_bounds__(FB_WAVES * 64) void k_features_batch(
     const int masked_n = cnt2((raw_e & BASE_MASKED_BIT) != 0, (raw_l & BASE_MASKED_BIT) != 0);
     const int snp_any = cnt2(snp_e != 0, snp_l != 0), snp_bad = cnt2(snp_e == 2, snp_l == 2), snp_ok = cnt2(snp_e == 1, snp_l == 1);
     const int bad = cnt2(code_e == BASE_N || code_e == BASE_DASH, code_l == BASE_N || code_l == BASE_DASH);
-    int ext_copy = 1, lig_copy = 1;
-    if (R.copy_off >= 0) {
-        const int se = P->len_slot[e], sl = P->len_slot[l];
-        const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-        ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-        lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-    }
-    bool mapping = false;
-    {
-        const int k = (P->max_capture - C) / P->inc;
-        if (R.unmap_off >= 0 && P->check_copy_number && k >= 0 && k < P->n_sizes_all) {
-            const int ms = (minus ? lig_start : ext_start) - R.seq_start;
-            if (ms >= 0 && ms < R.seq_len) mapping = unmap[R.unmap_off + (int64_t)k * R.seq_len + ms] != 0;
-        }
-    }
-    uint32_t flags = MIPGEN_FLAG_VALID | (bad ? MIPGEN_FLAG_GUARD : 0u);
-    int snp_count = 0;
-    if (mapping) flags |= MIPGEN_FLAG_MAPPING;
-    else {
-        if ((double)masked_n / (double)(l + e) > P->masked_arm_threshold) flags |= MIPGEN_FLAG_MASKING;
-        snp_count = snp_any;
-        if (snp_bad != 0 || snp_count > 1) flags |= MIPGEN_FLAG_SNP;
-        if (snp_ok != 0) flags |= MIPGEN_FLAG_HAS_SNP_MIP;
-    }
+    const int ext_copy = oligo_copy(P, R, copy, ext_start, e), lig_copy = oligo_copy(P, R, copy, lig_start, l);
+    const int k = (P->max_capture - C) / P->inc;
+    const bool mapping = k >= 0 && k < P->n_sizes_all && unmapped(P, R, unmap, k, minus, ext_start, lig_start);
+    int snp_count;
+    const uint32_t flags = record_flags(mapping, masked_n, l + e, P->masked_arm_threshold, snp_any, snp_bad, snp_ok, bad != 0, snp_count);
     const bool guard = bad != 0;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int j0 = s_lig[0], j1 = s_lig[1];
-    const int jc = (j0 < 4 && j1 < 4) ? 4 * j0 + j1 : 255;
+    const int jc = (int)junction_code(j0, j1);
     if (lane == 0) {
-        const uint32_t ec = (uint32_t)min(max(ext_copy, 0), 65535), lc = (uint32_t)min(max(lig_copy, 0), 65535);
-        records[ci] = (uint64_t)ec | ((uint64_t)lc << 16) | ((uint64_t)min(masked_n, 255) << 32) | ((uint64_t)min(snp_count, 255) << 40) |
-                      ((uint64_t)flags << 48) | ((uint64_t)(uint32_t)jc << 56);
+        records[ci] = pack_record(ext_copy, lig_copy, masked_n, snp_count, flags, (uint32_t)jc);
     }
     // mer histogram: a lane per window start; windows touching a non-ACGT code count nowhere (count_mer compares codes 0..3).  The oriented insert
     // passes through LDS in pieces of MAX_INSERT bases + two of look-ahead (one piece for every realistic capture size)

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include "common.h"
 #include "device_utils.h"
+#include "mip_record.h"
 
 #define REPLAY_WAVES 4
 
@@ -46,6 +47,160 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t x, int l)
 }
 __device__ __forceinline__ int top_bit(uint64_t m) { return 63 - __builtin_clzll(m); }      // m != 0
 
+// the take rules of condense_mips, the else-if chain of :1695-1737 as predicates (bitwise: no divergent branches).  A NaN score takes by none of
+// the score rules: neither sc < lower nor sc > lower holds.  Only the last rule leaves chosen_* alone, and only it can stop the fold (:1736).
+__device__ __forceinline__ bool condense_take(bool held, double cur_masked, int cur_copy, double sc, int snp, double thr, int target_copy, double lower,
+                                              double upper, double best_score, int best_snp, double chosen_masked, int chosen_copy,
+                                              bool& update_chosen, bool& stops)
+{
+    const bool rA = !held;                                                                            // :1695
+    const bool rB = (cur_masked > thr) & (cur_masked < chosen_masked);                                // :1701
+    const bool rC = (cur_copy > target_copy) & (cur_copy < chosen_copy);                              // :1709
+    const bool rD = cur_copy <= target_copy;
+    const bool above = sc > best_score;
+    const bool rE = (sc < lower) & above;                                                             // :1717
+    const bool hi_sc = sc > lower;
+    const bool rF = snp < best_snp;                                                                   // :1725
+    const bool rG = (snp == best_snp) & above;                                                        // :1731
+    const bool early = rA | rB | rC;
+    const bool last_rule = !early & rD & !rE & hi_sc & !rF & rG;
+    update_chosen = !last_rule;
+    stops = last_rule & (sc > upper);
+    return early | (rD & (rE | (hi_sc & (rF | rG))));
+}
+
+// the state of the condense fold at one scan position: chosen_* per position, best_* per strand (:1677-1680)
+struct Fold {
+    int64_t best_idx;
+    double best_score;
+    uint64_t best_rec;
+    int best_snp;
+    bool stop;
+    int chosen_copy;
+    double chosen_masked;
+};
+
+__device__ __forceinline__ void fold_strand_start(Fold& F) { F.best_idx = -1; F.best_score = 0.0; F.best_rec = 0; F.best_snp = 0; F.stop = false; }
+
+// Folds one row (strand s, size index ki) over the lanes of em, the wave-uniform mask of its emitted candidates: r / sc are the lane's record and
+// score (anything on the other lanes), e / l its arm pair, row_idx0 the dense-grid index of the row's pair 0.  All lanes evaluate the take rules
+// against the current state at once; the first taker in fold order (highest pair index first) is applied (v_readlane), the lanes after it are
+// re-evaluated against the new state.
+__device__ __forceinline__ void condense_row(Fold& F, uint64_t em, uint64_t r, double sc, int e, int l, int ki, int s, int64_t row_idx0, int pi,
+                                             const DevParams* P, const DevRegion& R, const int32_t* copy)
+{
+    const int target_copy = P->target_arm_copy;
+    const double thr = P->masked_arm_threshold;
+    int ext_copy = (int)MIPGEN_REC_EXT_COPY(r), lig_copy = (int)MIPGEN_REC_LIG_COPY(r);
+    // Quick reject, exact: once a candidate is held, every rule of condense_take but the first needs a higher score, fewer SNPs, a copy number
+    // above the target or masked bases (with a negative threshold even an arm without them counts)
+    if (F.best_idx >= 0 && !(em & __ballot(sc > F.best_score || ext_copy > target_copy || lig_copy > target_copy || thr < 0.0 ||
+                                           MIPGEN_REC_MASKED_N(r) != 0 || (int)MIPGEN_REC_SNP_COUNT(r) < F.best_snp))) return;
+    // the record's 16-bit copy fields saturate; the reference compares bwa's unbounded counts (true_arm_copy)
+    const uint64_t sat_mask = R.copy_off >= 0 ? em & __ballot(ext_copy == 65535 || lig_copy == 65535) : 0;
+    if (sat_mask && __builtin_amdgcn_inverse_ballot_w64(sat_mask)) {      // (the uniform test first: no exec-mask bookkeeping in the common case)
+        const int C = P->max_capture - (R.k0 + ki) * P->inc;
+        const ArmStarts st = arm_starts(R.first_pos + pi, C - e - l, e, l, s != 0);
+        ext_copy = true_arm_copy(P, R, copy, st.ext, e, (uint32_t)ext_copy);
+        lig_copy = true_arm_copy(P, R, copy, st.lig, l, (uint32_t)lig_copy);
+    }
+    const bool ok = !((int64_t)ext_copy * lig_copy > P->max_arm_copy_product) && !(MIPGEN_REC_FLAGS(r) & MIPGEN_FLAG_MAPPING);   // :1689-1690
+    const int cur_copy = ext_copy > lig_copy ? ext_copy : lig_copy;
+    double cur_masked = 0.0;                                   // (the division only where an emitted candidate has masked bases: 0 / x is exactly 0)
+    if (em & __ballot(MIPGEN_REC_MASKED_N(r) != 0)) cur_masked = (double)MIPGEN_REC_MASKED_N(r) / (double)(l + e);
+    const int snp = (int)MIPGEN_REC_SNP_COUNT(r);
+    uint64_t pending = em & __ballot(ok);
+    while (pending) {
+        bool update_chosen, stops;
+        const bool take = condense_take(F.best_idx >= 0, cur_masked, cur_copy, sc, snp, thr, target_copy, P->lower, P->upper, F.best_score, F.best_snp,
+                                        F.chosen_masked, F.chosen_copy, update_chosen, stops);
+        const uint64_t tmask = __ballot(take) & pending;
+        if (!tmask) break;
+        const int f = top_bit(tmask);
+        F.best_idx = row_idx0 + f;
+        F.best_score = readlane_d(sc, f);
+        F.best_rec = readlane_u64(r, f);
+        F.best_snp = (int)MIPGEN_REC_SNP_COUNT(F.best_rec);
+        if (__builtin_amdgcn_readlane((int)update_chosen, f)) {
+            F.chosen_masked = readlane_d(cur_masked, f);
+            F.chosen_copy = __builtin_amdgcn_readlane(cur_copy, f);
+        }
+        if (__builtin_amdgcn_readlane((int)stops, f)) { F.stop = true; break; }
+        pending &= (1ull << f) - 1;
+    }
+}
+
+__device__ __forceinline__ void write_survivor(mipgen_survivor* survivors, int gp, int s, const Fold& F, int64_t cand_base)
+{
+    if ((threadIdx.x & 63) == 0) {
+        mipgen_survivor out;
+        out.cand_index = F.best_idx < 0 ? -1 : F.best_idx + cand_base; out.score = F.best_score; out.record = F.best_rec;
+        survivors[2 * (int64_t)gp + s] = out;
+    }
+}
+
+// The arm-sum lists of a row of at most 64 pairs as lane masks: my pair is lane a (in: a < n_pairs), gend one past the last pair of its list
+struct Lists {
+    uint64_t ends;          // the last pair of every list
+    uint64_t min_sum;       // pairs of the list :434 never switches off
+    uint64_t below, above;  // the pairs of my list before / after mine
+};
+
+__device__ __forceinline__ Lists row_lists(bool in, int e, int l, int gend, int key_min_sum)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t lane_bit = 1ull << lane, below_me = lane_bit - 1;
+    Lists L;
+    L.ends = __ballot(in && lane + 1 == gend);
+    L.min_sum = __ballot(in && e + l == key_min_sum);
+    const uint64_t ends_below = L.ends & below_me;
+    const int lo = ends_below ? top_bit(ends_below) + 1 : 0;
+    const uint64_t seg = in ? ((gend >= 64 ? ~0ull : (1ull << gend) - 1) & ~((1ull << lo) - 1)) : 0;
+    L.below = seg & below_me; L.above = seg & ~below_me & ~lane_bit;
+    return L;
+}
+
+// One row of the replay, mipgen.cpp:430-434,494-497, all lists of the row at once (see k_replay_condense_narrow): the lanes it emits.  pbs is
+// previous_best_score, carried through the lists and rows.
+__device__ __forceinline__ uint64_t replay_row(double& pbs, double plus, double minus, bool valid, bool heuristic, double upper, const Lists& L)
+{
+    const uint64_t vmask = __ballot(valid);
+    bool mine = valid;
+    // :494 compares a score with the TRUNCATED score of the pair before it: while every constructed pair of the row scores in [0, 1) - any
+    // logistic row without a guard value or a NaN - all those integers are 0 and the test (plus < 0 && minus < 0) fails on every lane: one
+    // ballot instead of the shuffles (exact: any other row takes the general path)
+    if (heuristic && vmask && __ballot(valid && !(plus >= 0.0 && plus < 1.0 && minus >= 0.0 && minus < 1.0))) {
+        // the pair before me in my list that was constructed: its truncated scores are what :494 compares against
+        const uint64_t below = vmask & L.below;
+        const int src = below ? top_bit(below) : (int)(threadIdx.x & 63);
+        const double pp = __shfl(plus, src, 64), pm = __shfl(minus, src, 64);
+        const int ip = below ? to_int_x86(pp) : 0, im = below ? to_int_x86(pm) : 0;
+        const bool cond = valid && plus < (double)ip && minus < (double)im;                       // :494
+        const uint64_t cmask = __ballot(cond);
+        mine = valid && !(cmask & L.below);                                  // the first hit of a list is still constructed, nothing behind it
+    }
+    uint64_t emit_all = __ballot(mine);
+    if (emit_all) {
+        const double pb = (minus > plus) ? minus : plus;                     // :495 if I am the last pair constructed in my list
+        const bool last_of_list = mine && !(emit_all & L.above);
+        if (!__ballot(last_of_list && pb > upper)) {
+            pbs = readlane_d(pb, top_bit(emit_all));                         // no list of this row can switch a later one off
+        } else {
+            uint64_t ends = L.ends;
+            int a0 = 0;
+            while (ends) {                                                   // the chain through previous_best_score, list by list
+                const int a1 = __builtin_ctzll(ends) + 1;
+                ends &= ends - 1;
+                const uint64_t sg = (a1 >= 64 ? ~0ull : (1ull << a1) - 1) & ~((1ull << a0) - 1);
+                if (pbs > upper && !((L.min_sum >> a0) & 1)) emit_all &= ~sg;                      // :434
+                else if (emit_all & sg) pbs = readlane_d(pb, top_bit(emit_all & sg));
+                a0 = a1;
+            }
+        }
+    }
+    return emit_all;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense(
@@ -65,7 +220,7 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense(
     const int A = P->n_pairs, nK = R.n_sizes;
     const int64_t per_pos = (int64_t)nK * A * 2;
     const int64_t base = R.out_off + (int64_t)pi * per_pos;
-    const double upper = P->upper, lower = P->lower;
+    const double upper = P->upper;
     const bool heuristic = P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic;
     const int min_sum = P->key_min_sum;
     const uint64_t lane_bit = 1ull << lane, below_me = lane_bit - 1;
@@ -133,78 +288,24 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense(
     __builtin_amdgcn_wave_barrier();
 
     // ---- condense, mipgen.cpp:1670-1746 -------------------------------------------------------------------
-    const int target_copy = P->target_arm_copy;
-    const int64_t max_product = P->max_arm_copy_product;
-    const double thr = P->masked_arm_threshold;
-    int chosen_copy = 0;
-    double chosen_masked = 0.0;                                                      // per position, not per strand (:1677-1680)
+    Fold F;
+    F.chosen_copy = 0; F.chosen_masked = 0.0;
     for (int s = 0; s < 2; s++) {
-        int64_t best_idx = -1;
-        double best_score = 0.0;
-        uint64_t best_rec = 0;
-        int best_snp = 0;
-        bool stop = false;
-        for (int ki = nK - 1; ki >= 0 && !stop; ki--) {                              // newest first (push_front, :475,489)
-            for (int c = n_chunks - 1; c >= 0 && !stop; c--) {
+        fold_strand_start(F);
+        for (int ki = nK - 1; ki >= 0 && !F.stop; ki--) {                            // newest first (push_front, :475,489)
+            for (int c = n_chunks - 1; c >= 0 && !F.stop; c--) {
                 const uint64_t em = emask[ki * n_chunks + c];
                 if (!em) continue;
                 const int a = c * 64 + lane;
                 const bool mine = (em & lane_bit) != 0;
-                const int64_t idx = base + ((int64_t)ki * 2 + s) * A + a;
-                const uint64_t r = mine ? records[idx] : 0;
-                const double sc = mine ? scores[idx] : 0.0;
-                int ext_copy = (int)MIPGEN_REC_EXT_COPY(r), lig_copy = (int)MIPGEN_REC_LIG_COPY(r);
+                const int64_t row_idx0 = base + ((int64_t)ki * 2 + s) * A + c * 64;
+                const uint64_t r = mine ? records[row_idx0 + lane] : 0;
+                const double sc = mine ? scores[row_idx0 + lane] : 0.0;
                 const int e = mine ? P->arm_ext[a] : 1, l = mine ? P->arm_lig[a] : 1;
-                if (mine && (ext_copy == 65535 || lig_copy == 65535) && R.copy_off >= 0) {
-                    // the record's 16-bit fields saturate; the reference compares bwa's unbounded X0 counts (mipgen.cpp:586-587,1692,1709):
-                    // fetch the true values from the copy table
-                    const int C = P->max_capture - (R.k0 + ki) * P->inc, p = R.first_pos + pi, ss = C - e - l;
-                    const int ext_start = s ? p + ss : p - e, lig_start = s ? p - l : p + ss;
-                    const int se = P->len_slot[e], sl = P->len_slot[l];
-                    const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-                    ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-                    lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-                }
-                const bool ok = mine && !((int64_t)ext_copy * lig_copy > max_product) && !(MIPGEN_REC_FLAGS(r) & MIPGEN_FLAG_MAPPING);   // :1689-1690
-                const int cur_copy = ext_copy > lig_copy ? ext_copy : lig_copy;
-                const double cur_masked = (double)MIPGEN_REC_MASKED_N(r) / (double)(l + e);
-                const int snp = (int)MIPGEN_REC_SNP_COUNT(r);
-                uint64_t pending = __ballot(ok);
-                while (pending) {
-                    // every pending lane evaluates the take rules against the current state; the first taker in fold order (highest pair
-                    // index first) is applied, the lanes after it are re-evaluated
-                    bool take = false, update_chosen = true, stops = false;
-                    if (best_idx < 0) take = true;                                                                    // :1695
-                    else if (cur_masked > thr && cur_masked < chosen_masked) take = true;                             // :1701
-                    else if (cur_copy > target_copy && cur_copy < chosen_copy) take = true;                           // :1709
-                    else if (cur_copy <= target_copy) {
-                        if (sc < lower && sc > best_score) take = true;                                               // :1717
-                        else if (sc > lower) {
-                            if (snp < best_snp) take = true;                                                          // :1725
-                            else if (snp == best_snp && sc > best_score) { take = true; update_chosen = false; stops = sc > upper; }   // :1731-1737
-                        }
-                    }
-                    const uint64_t tmask = __ballot(take) & pending;
-                    if (!tmask) break;
-                    const int f = top_bit(tmask);
-                    best_idx = base + ((int64_t)ki * 2 + s) * A + (c * 64 + f);
-                    best_score = readlane_d(sc, f);
-                    best_rec = readlane_u64(r, f);
-                    best_snp = (int)MIPGEN_REC_SNP_COUNT(best_rec);
-                    if (__builtin_amdgcn_readlane((int)update_chosen, f)) {
-                        chosen_masked = readlane_d(cur_masked, f);
-                        chosen_copy = __builtin_amdgcn_readlane(cur_copy, f);
-                    }
-                    if (__builtin_amdgcn_readlane((int)stops, f)) { stop = true; break; }
-                    pending &= (1ull << f) - 1;
-                }
+                condense_row(F, em, r, sc, e, l, ki, s, row_idx0, pi, P, R, copy);
             }
         }
-        if (lane == 0) {
-            mipgen_survivor out;
-            out.cand_index = best_idx < 0 ? -1 : best_idx + cand_base; out.score = best_score; out.record = best_rec;
-            survivors[2 * (int64_t)gp + s] = out;
-        }
+        write_survivor(survivors, gp, s, F, cand_base);
     }
 }
 
@@ -237,19 +338,14 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_narrow(
     const int A = P->n_pairs, nK = R.n_sizes;
     const int64_t per_pos = (int64_t)nK * A * 2;
     const int64_t base = R.out_off + (int64_t)pi * per_pos;
-    const double upper = P->upper, lower = P->lower;
+    const double upper = P->upper;
     const bool heuristic = P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic;
-    const uint64_t lane_bit = 1ull << lane, below_me = lane_bit - 1;
+    const uint64_t lane_bit = 1ull << lane;
 
     // my pair, and the lanes of my arm-sum list
     const bool in = lane < A;
-    const int e = in ? P->arm_ext[lane] : 1, l = in ? P->arm_lig[lane] : 1, gend = in ? P->group_end[lane] : 0;
-    const uint64_t list_ends = __ballot(in && lane + 1 == gend);           // the last pair of every list
-    const uint64_t min_lists = __ballot(in && e + l == P->key_min_sum);        // pairs of the list :434 never switches off
-    const uint64_t ends_below = list_ends & below_me;
-    const int lo = ends_below ? top_bit(ends_below) + 1 : 0;
-    const uint64_t seg = in ? ((gend >= 64 ? ~0ull : (1ull << gend) - 1) & ~((1ull << lo) - 1)) : 0;
-    const uint64_t seg_below = seg & below_me, seg_above = seg & ~below_me & ~lane_bit;
+    const int e = in ? P->arm_ext[lane] : 1, l = in ? P->arm_lig[lane] : 1;
+    const Lists L = row_lists(in, e, l, in ? P->group_end[lane] : 0, P->key_min_sum);
     // :443-444, the bounds skips, from the geometry alone: a pair is constructed at scan start p and capture size C iff p > max(e, l),
     // p + C - 1 - min(e, l) <= seq_stop and the scan target is not empty (C > e + l) - exactly the VALID bit of the candidate's record
     // (kernels_logistic_dense.hip, kernels_logistic.hip: `ss > 0`; mipgen_accel_create refuses parameter sets with min_capture <= max arm sum, the
@@ -305,44 +401,12 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_narrow(
             if (ki >= nK) break;
             uint64_t emit_all = 0;
             if (!(pbs > upper)) {                                            // :430
-                const double plus = bp[q], minus = bm[q];
                 const bool valid = ok_lo && (unsigned)(c_top - ki * c_inc) <= (unsigned)c_span;  // :443-444 (false outside the row)
-                const uint64_t vmask = __ballot(valid);
-                bool mine = valid;
-                // (rows whose constructed pairs all score in [0, 1) cannot trigger :494 - every truncated score is 0: see k_replay_condense_carry)
-                if (heuristic && vmask && __ballot(valid && !(plus >= 0.0 && plus < 1.0 && minus >= 0.0 && minus < 1.0))) {
-                    // the pair before me in my list that was constructed: its truncated scores are what :494 compares against
-                    const uint64_t below = vmask & seg_below;
-                    const int src = below ? top_bit(below) : lane;
-                    const double pp = __shfl(plus, src, 64), pm = __shfl(minus, src, 64);
-                    const int ip = below ? to_int_x86(pp) : 0, im = below ? to_int_x86(pm) : 0;
-                    const bool cond = valid && plus < (double)ip && minus < (double)im;           // :494
-                    const uint64_t cmask = __ballot(cond);
-                    mine = valid && !(cmask & seg_below);                    // the first hit of a list is still constructed, nothing behind it
-                }
-                emit_all = __ballot(mine);
-                if (emit_all) {
-                    const double pb = (minus > plus) ? minus : plus;         // :495 if I am the last pair constructed in my list
-                    const bool last_of_list = mine && !(emit_all & seg_above);
-                    if (!__ballot(last_of_list && pb > upper)) {
-                        pbs = readlane_d(pb, top_bit(emit_all));             // no list of this row can switch a later one off
-                    } else {
-                        uint64_t ends = list_ends;
-                        int a0 = 0;
-                        while (ends) {                                       // the chain through previous_best_score, list by list
-                            const int a1 = __builtin_ctzll(ends) + 1;
-                            ends &= ends - 1;
-                            const uint64_t sg = (a1 >= 64 ? ~0ull : (1ull << a1) - 1) & ~((1ull << a0) - 1);
-                            if (pbs > upper && !((min_lists >> a0) & 1)) emit_all &= ~sg;          // :434
-                            else if (emit_all & sg) pbs = readlane_d(pb, top_bit(emit_all & sg));
-                            a0 = a1;
-                        }
-                    }
-                    n_emitted += 2ull * (unsigned)__builtin_popcountll(emit_all);
-                    if (emitted && (emit_all & lane_bit)) {
-                        const int64_t idx = base + ((int64_t)ki * 2) * A + lane;
-                        emitted[idx] = 1; emitted[idx + A] = 1;
-                    }
+                emit_all = replay_row(pbs, bp[q], bm[q], valid, heuristic, upper, L);
+                n_emitted += 2ull * (unsigned)__builtin_popcountll(emit_all);
+                if (emitted && (emit_all & lane_bit)) {
+                    const int64_t idx = base + ((int64_t)ki * 2) * A + lane;
+                    emitted[idx] = 1; emitted[idx + A] = 1;
                 }
             }
             if (lane == 0) emask[ki] = emit_all;
@@ -353,21 +417,12 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_narrow(
     __builtin_amdgcn_wave_barrier();
 
     // ---- condense, mipgen.cpp:1670-1746 -------------------------------------------------------------------
-    const int target_copy = P->target_arm_copy;
-    const int64_t max_product = P->max_arm_copy_product;
-    const double thr = P->masked_arm_threshold;
-    const bool masked_any_counts = thr < 0.0;                                        // then even an arm without masked bases is "above the threshold" (:1701)
-    const double arm_sum = (double)(l + e);
-    int chosen_copy = 0;
-    double chosen_masked = 0.0;                                                      // per position, not per strand (:1677-1680)
+    Fold F;
+    F.chosen_copy = 0; F.chosen_masked = 0.0;
     const int k_top = ((nK - 1) / REPLAY_ROWS) * REPLAY_ROWS;
     for (int s = 0; s < 2; s++) {
-        int64_t best_idx = -1;
-        double best_score = 0.0;
-        uint64_t best_rec = 0;
-        int best_snp = 0;
-        bool stop = false;
-        for (int k0 = k_top; k0 >= 0 && !stop; k0 -= REPLAY_ROWS) {                  // newest first (push_front, :475,489)
+        fold_strand_start(F);
+        for (int k0 = k_top; k0 >= 0 && !F.stop; k0 -= REPLAY_ROWS) {                  // newest first (push_front, :475,489)
             uint64_t em[REPLAY_ROWS], br[REPLAY_ROWS];
             double bs[REPLAY_ROWS];
             if constexpr (WIDE) {
@@ -403,71 +458,12 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_narrow(
             }
 #pragma unroll
             for (int q = REPLAY_ROWS - 1; q >= 0; q--) {
-                if (stop || !em[q]) continue;
+                if (F.stop || !em[q]) continue;
                 const int ki = k0 + q;
-                const bool mine = (em[q] & lane_bit) != 0;
-                const uint64_t r = br[q];
-                const double sc = bs[q];
-                int ext_copy = (int)MIPGEN_REC_EXT_COPY(r), lig_copy = (int)MIPGEN_REC_LIG_COPY(r);
-                // Quick reject, exact: once a candidate is held (:1695 no longer applies) every other rule needs a higher score (:1717,1731),
-                // fewer SNPs (:1725), a copy number above the target (:1709) or masked bases (:1701) - most rows have none of these
-                if (best_idx >= 0 && !(em[q] & __ballot(sc > best_score || ext_copy > target_copy || lig_copy > target_copy || masked_any_counts ||
-                                                        MIPGEN_REC_MASKED_N(r) != 0 || (int)MIPGEN_REC_SNP_COUNT(r) < best_snp))) continue;
-                const bool saturated = mine && (ext_copy == 65535 || lig_copy == 65535) && R.copy_off >= 0;
-                if (__ballot(saturated) && saturated) {                    // (the uniform test first: no exec-mask bookkeeping in the common case)
-                    // the record's 16-bit fields saturate; the reference compares bwa's unbounded X0 counts (mipgen.cpp:586-587,1692,1709):
-                    // fetch the true values from the copy table
-                    const int C = P->max_capture - (R.k0 + ki) * P->inc, p = R.first_pos + pi, ss = C - e - l;
-                    const int ext_start = s ? p + ss : p - e, lig_start = s ? p - l : p + ss;
-                    const int se = P->len_slot[e], sl = P->len_slot[l];
-                    const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-                    ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-                    lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-                }
-                const bool ok = mine && !((int64_t)ext_copy * lig_copy > max_product) && !(MIPGEN_REC_FLAGS(r) & MIPGEN_FLAG_MAPPING);   // :1689-1690
-                const int cur_copy = ext_copy > lig_copy ? ext_copy : lig_copy;
-                double cur_masked = 0.0;                                   // (the division only where an emitted candidate has masked bases: 0 / x is exactly 0)
-                if (em[q] & __ballot(MIPGEN_REC_MASKED_N(r) != 0)) cur_masked = (double)MIPGEN_REC_MASKED_N(r) / arm_sum;
-                const int snp = (int)MIPGEN_REC_SNP_COUNT(r);
-                uint64_t pending = __ballot(ok);
-                while (pending) {
-                    // every pending lane evaluates the take rules against the current state; the first taker in fold order (highest pair
-                    // index first) is applied, the lanes after it are re-evaluated
-                    // the else-if chain of :1695-1737 as predicates (bitwise: no divergent branches); only the last rule leaves chosen_* alone
-                    const bool rA = best_idx < 0;                                                                     // :1695
-                    const bool rB = (cur_masked > thr) & (cur_masked < chosen_masked);                                // :1701
-                    const bool rC = (cur_copy > target_copy) & (cur_copy < chosen_copy);                              // :1709
-                    const bool rD = cur_copy <= target_copy;
-                    const bool above = sc > best_score;
-                    const bool rE = (sc < lower) & above;                                                             // :1717
-                    const bool hi_sc = sc > lower;
-                    const bool rF = snp < best_snp;                                                                   // :1725
-                    const bool rG = (snp == best_snp) & above;                                                        // :1731-1737
-                    const bool early = rA | rB | rC;
-                    const bool last_rule = !early & rD & !rE & hi_sc & !rF & rG;
-                    const bool take = early | (rD & (rE | (hi_sc & (rF | rG))));
-                    const bool update_chosen = !last_rule, stops = last_rule & (sc > upper);
-                    const uint64_t tmask = __ballot(take) & pending;
-                    if (!tmask) break;
-                    const int f = top_bit(tmask);
-                    best_idx = base + ((int64_t)ki * 2 + s) * A + f;
-                    best_score = readlane_d(sc, f);
-                    best_rec = readlane_u64(r, f);
-                    best_snp = (int)MIPGEN_REC_SNP_COUNT(best_rec);
-                    if (__builtin_amdgcn_readlane((int)update_chosen, f)) {
-                        chosen_masked = readlane_d(cur_masked, f);
-                        chosen_copy = __builtin_amdgcn_readlane(cur_copy, f);
-                    }
-                    if (__builtin_amdgcn_readlane((int)stops, f)) { stop = true; break; }
-                    pending &= (1ull << f) - 1;
-                }
+                condense_row(F, em[q], br[q], bs[q], e, l, ki, s, base + ((int64_t)ki * 2 + s) * A, pi, P, R, copy);
             }
         }
-        if (lane == 0) {
-            mipgen_survivor out;
-            out.cand_index = best_idx < 0 ? -1 : best_idx + cand_base; out.score = best_score; out.record = best_rec;
-            survivors[2 * (int64_t)gp + s] = out;
-        }
+        write_survivor(survivors, gp, s, F, cand_base);
     }
 }
 
@@ -495,23 +491,12 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_carry(
     const int A = P->n_pairs, nK = R.n_sizes;                               // nK <= CR (the launcher checks the parameter set)
     const int64_t per_pos = (int64_t)nK * A * 2;
     const int64_t base = R.out_off + (int64_t)pi * per_pos;
-    const double upper = P->upper, lower = P->lower;
+    const double upper = P->upper;
     const bool heuristic = P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic;
-    const uint64_t lane_bit = 1ull << lane, below_me = lane_bit - 1;
 
     const bool in = lane < A;
-    const int e = in ? P->arm_ext[lane] : 1, l = in ? P->arm_lig[lane] : 1, gend = in ? P->group_end[lane] : 0;
-    const uint64_t list_ends = __ballot(in && lane + 1 == gend);
-    const uint64_t min_lists = __ballot(in && e + l == P->key_min_sum);
-    const uint64_t ends_below = list_ends & below_me;
-    const int lo = ends_below ? top_bit(ends_below) + 1 : 0;
-    const uint64_t seg = in ? ((gend >= 64 ? ~0ull : (1ull << gend) - 1) & ~((1ull << lo) - 1)) : 0;
-    const uint64_t seg_below = seg & below_me, seg_above = seg & ~below_me & ~lane_bit;
-    const int target_copy = P->target_arm_copy;
-    const int64_t max_product = P->max_arm_copy_product;
-    const double thr = P->masked_arm_threshold;
-    const bool masked_any_counts = thr < 0.0;                                        // then even an arm without masked bases is "above the threshold" (:1701)
-    const double arm_sum = (double)(l + e);
+    const int e = in ? P->arm_ext[lane] : 1, l = in ? P->arm_lig[lane] : 1;
+    const Lists L = row_lists(in, e, l, in ? P->group_end[lane] : 0, P->key_min_sum);
 
     // ---- the position's rows: scores and records of both strands, one round trip ----
     double bp[CR], bm[CR];
@@ -532,45 +517,12 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_carry(
         if (q >= nK) break;
         uint64_t emit_all = 0;
         if (!(pbs > upper)) {                                                // :430
-            const double plus = bp[q], minus = bm[q];
             const bool valid = in && (MIPGEN_REC_FLAGS(rp[q]) & MIPGEN_FLAG_VALID) != 0;         // :443-444
-            const uint64_t vmask = __ballot(valid);
-            bool mine = valid;
-            // :494 compares a score with the TRUNCATED score of the pair before it: while every constructed pair of the row scores in [0, 1) - any
-            // logistic row without a guard value or a NaN - all those integers are 0 and the test (plus < 0 && minus < 0) fails on every lane: one
-            // ballot instead of the shuffles (exact: any other row takes the general path)
-            if (heuristic && vmask && __ballot(valid && !(plus >= 0.0 && plus < 1.0 && minus >= 0.0 && minus < 1.0))) {
-                const uint64_t below = vmask & seg_below;
-                const int src = below ? top_bit(below) : lane;
-                const double pp = __shfl(plus, src, 64), pm = __shfl(minus, src, 64);
-                const int ip = below ? to_int_x86(pp) : 0, im = below ? to_int_x86(pm) : 0;
-                const bool cond = valid && plus < (double)ip && minus < (double)im;               // :494
-                const uint64_t cmask = __ballot(cond);
-                mine = valid && !(cmask & seg_below);
-            }
-            emit_all = __ballot(mine);
-            if (emit_all) {
-                const double pb = (minus > plus) ? minus : plus;             // :495
-                const bool last_of_list = mine && !(emit_all & seg_above);
-                if (!__ballot(last_of_list && pb > upper)) {
-                    pbs = readlane_d(pb, top_bit(emit_all));
-                } else {
-                    uint64_t ends = list_ends;
-                    int a0 = 0;
-                    while (ends) {
-                        const int a1 = __builtin_ctzll(ends) + 1;
-                        ends &= ends - 1;
-                        const uint64_t sg = (a1 >= 64 ? ~0ull : (1ull << a1) - 1) & ~((1ull << a0) - 1);
-                        if (pbs > upper && !((min_lists >> a0) & 1)) emit_all &= ~sg;              // :434
-                        else if (emit_all & sg) pbs = readlane_d(pb, top_bit(emit_all & sg));
-                        a0 = a1;
-                    }
-                }
-                n_emitted += 2ull * (unsigned)__builtin_popcountll(emit_all);
-                if (emitted && __builtin_amdgcn_inverse_ballot_w64(emit_all)) {
-                    const int64_t idx = base + ((int64_t)q * 2) * A + lane;
-                    emitted[idx] = 1; emitted[idx + A] = 1;
-                }
+            emit_all = replay_row(pbs, bp[q], bm[q], valid, heuristic, upper, L);
+            n_emitted += 2ull * (unsigned)__builtin_popcountll(emit_all);
+            if (emitted && __builtin_amdgcn_inverse_ballot_w64(emit_all)) {
+                const int64_t idx = base + ((int64_t)q * 2) * A + lane;
+                emitted[idx] = 1; emitted[idx + A] = 1;
             }
         }
         em[q] = emit_all;
@@ -578,75 +530,16 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_carry(
     if (n_emitted && lane == 0) atomicAdd(&emitted_per_region[ri], n_emitted);
 
     // ---- condense, mipgen.cpp:1670-1746, from the registers ----
-    int chosen_copy = 0;
-    double chosen_masked = 0.0;
+    Fold F;
+    F.chosen_copy = 0; F.chosen_masked = 0.0;
     for (int s = 0; s < 2; s++) {
-        int64_t best_idx = -1;
-        double best_score = 0.0;
-        uint64_t best_rec = 0;
-        int best_snp = 0;
-        bool stop = false;
+        fold_strand_start(F);
 #pragma unroll
         for (int q = CR - 1; q >= 0; q--) {                                  // newest first (push_front, :475,489)
-            if (stop || !em[q]) continue;
-            const int ki = q;
-            const uint64_t r = s ? rm[q] : rp[q];
-            const double sc = s ? bm[q] : bp[q];
-            int ext_copy = (int)MIPGEN_REC_EXT_COPY(r), lig_copy = (int)MIPGEN_REC_LIG_COPY(r);
-            // quick reject, exact (see k_replay_condense_narrow)
-            // (the emitted lanes gate every ballot as a uniform mask: no per-lane copy of it)
-            if (best_idx >= 0 && !(em[q] & __ballot(sc > best_score || ext_copy > target_copy || lig_copy > target_copy || masked_any_counts ||
-                                                    MIPGEN_REC_MASKED_N(r) != 0 || (int)MIPGEN_REC_SNP_COUNT(r) < best_snp))) continue;
-            const uint64_t sat_mask = R.copy_off >= 0 ? em[q] & __ballot(ext_copy == 65535 || lig_copy == 65535) : 0;
-            if (sat_mask && __builtin_amdgcn_inverse_ballot_w64(sat_mask)) {
-                const int C = P->max_capture - (R.k0 + ki) * P->inc, p = R.first_pos + pi, ss = C - e - l;
-                const int ext_start = s ? p + ss : p - e, lig_start = s ? p - l : p + ss;
-                const int se = P->len_slot[e], sl = P->len_slot[l];
-                const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-                ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-                lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-            }
-            const bool ok = !((int64_t)ext_copy * lig_copy > max_product) && !(MIPGEN_REC_FLAGS(r) & MIPGEN_FLAG_MAPPING);   // :1689-1690 (of an emitted lane: the mask below)
-            const int cur_copy = ext_copy > lig_copy ? ext_copy : lig_copy;
-            // (the division only where an emitted candidate has masked bases at all: 0 / x is exactly 0)
-            double cur_masked = 0.0;
-            if (em[q] & __ballot(MIPGEN_REC_MASKED_N(r) != 0)) cur_masked = (double)MIPGEN_REC_MASKED_N(r) / arm_sum;
-            const int snp = (int)MIPGEN_REC_SNP_COUNT(r);
-            uint64_t pending = em[q] & __ballot(ok);
-            while (pending) {
-                const bool rA = best_idx < 0;                                                                     // :1695
-                const bool rB = (cur_masked > thr) & (cur_masked < chosen_masked);                                // :1701
-                const bool rC = (cur_copy > target_copy) & (cur_copy < chosen_copy);                              // :1709
-                const bool rD = cur_copy <= target_copy;
-                const bool above = sc > best_score;
-                const bool rE = (sc < lower) & above;                                                             // :1717
-                const bool hi_sc = sc > lower;
-                const bool rF = snp < best_snp;                                                                   // :1725
-                const bool rG = (snp == best_snp) & above;                                                        // :1731-1737
-                const bool early = rA | rB | rC;
-                const bool last_rule = !early & rD & !rE & hi_sc & !rF & rG;
-                const bool take = early | (rD & (rE | (hi_sc & (rF | rG))));
-                const bool update_chosen = !last_rule, stops = last_rule & (sc > upper);
-                const uint64_t tmask = __ballot(take) & pending;
-                if (!tmask) break;
-                const int f = top_bit(tmask);
-                best_idx = base + ((int64_t)ki * 2 + s) * A + f;
-                best_score = readlane_d(sc, f);
-                best_rec = readlane_u64(r, f);
-                best_snp = (int)MIPGEN_REC_SNP_COUNT(best_rec);
-                if (__builtin_amdgcn_readlane((int)update_chosen, f)) {
-                    chosen_masked = readlane_d(cur_masked, f);
-                    chosen_copy = __builtin_amdgcn_readlane(cur_copy, f);
-                }
-                if (__builtin_amdgcn_readlane((int)stops, f)) { stop = true; break; }
-                pending &= (1ull << f) - 1;
-            }
+            if (F.stop || !em[q]) continue;
+            condense_row(F, em[q], s ? rm[q] : rp[q], s ? bm[q] : bp[q], e, l, q, s, base + ((int64_t)q * 2 + s) * A, pi, P, R, copy);
         }
-        if (lane == 0) {
-            mipgen_survivor out;
-            out.cand_index = best_idx < 0 ? -1 : best_idx + cand_base; out.score = best_score; out.record = best_rec;
-            survivors[2 * (int64_t)gp + s] = out;
-        }
+        write_survivor(survivors, gp, s, F, cand_base);
     }
 }
 
@@ -724,15 +617,9 @@ __global__ __launch_bounds__(256) void k_collapse(int n_tiles, const CollapseTil
             const int a = rel % A, ki = rel / (2 * A);
             const int e = P->arm_ext[a], l = P->arm_lig[a];
             const int C = P->max_capture - (R.k0 + ki) * P->inc, ss = C - e - l;
-            int ext_copy = (int)MIPGEN_REC_EXT_COPY(m.record), lig_copy = (int)MIPGEN_REC_LIG_COPY(m.record);
-            if ((ext_copy == 65535 || lig_copy == 65535) && R.copy_off >= 0) {  // saturated record fields: the true counts (see k_replay_condense)
-                const int p = R.first_pos + pi;
-                const int ext_start = s ? p + ss : p - e, lig_start = s ? p - l : p + ss;
-                const int se = P->len_slot[e], sl = P->len_slot[l];
-                const int ie = ext_start - R.seq_start, il = lig_start - R.seq_start;
-                ext_copy = (se >= 0 && ie >= 0 && ie < R.seq_len) ? copy[R.copy_off + (int64_t)se * R.seq_len + ie] : 0;
-                lig_copy = (sl >= 0 && il >= 0 && il < R.seq_len) ? copy[R.copy_off + (int64_t)sl * R.seq_len + il] : 0;
-            }
+            const ArmStarts st = arm_starts(R.first_pos + pi, ss, e, l, s != 0);
+            const int ext_copy = true_arm_copy(P, R, copy, st.ext, e, MIPGEN_REC_EXT_COPY(m.record));
+            const int lig_copy = true_arm_copy(P, R, copy, st.lig, l, MIPGEN_REC_LIG_COPY(m.record));
             const bool keep = !((int64_t)ext_copy * lig_copy > max_product || ext_copy > target || lig_copy > target)          // :1628
                               && !((double)MIPGEN_REC_MASKED_N(m.record) / (double)(l + e) > thr);                          // :1629
             if (keep) end = pi + ss - 1;

@@ -1,0 +1,72 @@
+// mip_record.h — the integer record of design_mip and the bounds skips, as the device kernels restate them: one definition each.
+//
+// The record layout is the one the MIPGEN_REC_* accessors of include/mipgen_accel.h read; every builder packs it with pack_record, and every
+// kernel that looks an oligo's copy number up, tests the mapping flag or places a candidate's arms does so through the functions below.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "common.h"
+
+struct ArmStarts { int ext, lig; };
+
+// arm starts of the candidate at scan start p with scan size ss: PlusSVMipv4.cpp:9-12 / MinusSVMipv4.cpp:32-35
+__device__ __forceinline__ ArmStarts arm_starts(int p, int ss, int e, int l, bool minus)
+{
+    return minus ? ArmStarts{p + ss, p - l} : ArmStarts{p - e, p + ss};
+}
+
+// the bounds skips of mipgen.cpp:443-444, and a non-empty scan target: the candidate is constructed (MIPGEN_FLAG_VALID)
+__device__ __forceinline__ bool constructed(const DevRegion& R, int p, int C, int e, int l)
+{
+    const int ss = C - e - l;
+    return !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) && ss > 0;
+}
+
+// copy number of the oligo [start, start + len), mipgen.cpp:612-613: absent key -> 0, no table -> 1
+__device__ __forceinline__ int oligo_copy(const DevParams* P, const DevRegion& R, const int32_t* copy, int start, int len)
+{
+    if (R.copy_off < 0) return 1;
+    const int slot = P->len_slot[len], ri = start - R.seq_start;
+    return (slot >= 0 && ri >= 0 && ri < R.seq_len) ? copy[R.copy_off + (int64_t)slot * R.seq_len + ri] : 0;
+}
+
+// an arm's copy number from its record field: a 16-bit field saturates at 65535, where the reference keeps bwa's unbounded X0 count
+// (mipgen.cpp:586-587): the true value comes from the copy table
+__device__ __forceinline__ int true_arm_copy(const DevParams* P, const DevRegion& R, const int32_t* copy, int start, int len, uint32_t rec_field)
+{
+    if (rec_field != 65535u || R.copy_off < 0) return (int)rec_field;
+    return oligo_copy(P, R, copy, start, len);
+}
+
+// mapping flag, mipgen.cpp:615-625: the unmappable-position table of capture size index k at the MIP's upstream arm
+__device__ __forceinline__ bool unmapped(const DevParams* P, const DevRegion& R, const uint8_t* unmap, int k, bool minus, int ext_start, int lig_start)
+{
+    if (R.unmap_off < 0 || !P->check_copy_number) return false;
+    const int ms = (minus ? lig_start : ext_start) - R.seq_start;
+    return ms >= 0 && ms < R.seq_len && unmap[R.unmap_off + (int64_t)k * R.seq_len + ms] != 0;
+}
+
+// the record's flags, mipgen.cpp:610,626,690-693,759-760; snp_count is 0 where the mapping flag returns early (the masking and SNP fields keep
+// their defaults)
+__device__ __forceinline__ uint32_t record_flags(bool mapping, int masked_n, int arm_sum, double thr, int snp_any, int snp_bad, int snp_ok, bool guard,
+                                                 int& snp_count)
+{
+    uint32_t flags = MIPGEN_FLAG_VALID | (guard ? MIPGEN_FLAG_GUARD : 0u);
+    snp_count = 0;
+    if (mapping) return flags | MIPGEN_FLAG_MAPPING;
+    if ((double)masked_n / (double)arm_sum > thr) flags |= MIPGEN_FLAG_MASKING;
+    snp_count = snp_any;
+    if (snp_bad != 0 || snp_count > 1) flags |= MIPGEN_FLAG_SNP;
+    if (snp_ok != 0) flags |= MIPGEN_FLAG_HAS_SNP_MIP;
+    return flags;
+}
+
+// ligation junction = the first two bases of the oriented ligation arm, 4 * code + code (A < C < G < T); 255 if either is not ACGT
+__device__ __forceinline__ uint32_t junction_code(int j0, int j1) { return (j0 < 4 && j1 < 4) ? (uint32_t)(4 * j0 + j1) : 255u; }
+
+// the 64-bit record, fields as MIPGEN_REC_*: copy numbers saturate at 65535, the masked-base and SNP counts at 255
+__device__ __forceinline__ uint64_t pack_record(int ext_copy, int lig_copy, int masked_n, int snp_count, uint32_t flags, uint32_t jc)
+{
+    const uint32_t ec = (uint32_t)min(max(ext_copy, 0), 65535), lc = (uint32_t)min(max(lig_copy, 0), 65535);
+    return (uint64_t)ec | ((uint64_t)lc << 16) | ((uint64_t)min(masked_n, 255) << 32) | ((uint64_t)min(snp_count, 255) << 40) |
+           ((uint64_t)flags << 48) | ((uint64_t)jc << 56);
+}
