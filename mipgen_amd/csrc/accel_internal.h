@@ -36,10 +36,10 @@ hipError_t mipgen_launch_svr_dense(hipStream_t, int n_tiles, int n_tiles_few, si
 hipError_t mipgen_launch_candidates(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t*,
                                     const int32_t*, const uint8_t*, const HostConsts*, const double* model, int n_sv, double gamma,
                                     double rho, int method, double*, uint64_t*, double*, mipgen_candidate_ints*, int literal, const unsigned int* n_dev);
-hipError_t mipgen_launch_print_boundary_scan(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const double* scores, const uint64_t* records, int64_t n,
-                                             double tol_rel, double tol_abs, mipgen_candidate* out, int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu);
-hipError_t mipgen_launch_print_boundary_scan_list(hipStream_t, const mipgen_candidate* cands, const double* scores, const uint64_t* records, int n, double tol_rel,
-                                                  double tol_abs, mipgen_candidate* out, int64_t* out_idx, unsigned int* count, unsigned int cap);
+hipError_t mipgen_launch_print_boundary_scan(hipStream_t, const DevParams*, const DevRegion*, const RescoreSrc*, double tol_rel, double tol_abs, mipgen_candidate* out,
+                                             int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu);
+hipError_t mipgen_launch_scatter_scores(hipStream_t, const double* src, const int64_t* idx, int64_t cap, const unsigned int* n_dev, double* dst, mipgen_survivor* dst_surv,
+                                        unsigned int* over);
 hipError_t mipgen_launch_svr_run_state(hipStream_t s, int64_t n_pos, const DevParams* P, const DevRegion* regions, const int32_t* pos_region, const int32_t* pos_local,
                                        const uint32_t* run_bounds, int max_levels, int level, double margin, const double* scores, const uint64_t* records, double* pbs,
                                        uint8_t* state);
@@ -48,14 +48,9 @@ hipError_t mipgen_launch_svr_tile_compact(hipStream_t s, int n_tiles, const SvrT
                                           const DevRegion* regions, double* scores, unsigned long long* skipped);
 hipError_t mipgen_launch_dense_candidates(hipStream_t, const DevParams* P, const DevRegion* regions, int r0, int r1, int64_t c0, int n, mipgen_candidate* out);
 hipError_t mipgen_launch_dense_list_fix(hipStream_t, int n, const uint64_t* records, double rho, double s_guard, double* scores);
-hipError_t mipgen_launch_scatter_scores(hipStream_t, const double* src, const int64_t* idx, int cap, const unsigned int* n_dev, double* scores, unsigned int* over);
-hipError_t mipgen_launch_print_boundary_scan_surv(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const mipgen_survivor* surv, int64_t n, int64_t cand0,
-                                                  double tol_rel, double tol_abs, mipgen_candidate* out, int64_t* out_idx, unsigned int* count, unsigned int cap);
-hipError_t mipgen_launch_scatter_surv_scores(hipStream_t, const double* src, const int64_t* idx, int cap, const unsigned int* n_dev, mipgen_survivor* surv, unsigned int* over);
 hipError_t mipgen_launch_surv_keep(hipStream_t, const mipgen_survivor* surv, int64_t n, int64_t* keep, double* svr);
 hipError_t mipgen_launch_surv_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const mipgen_survivor* surv, int64_t n, int64_t cand0,
                                          const int64_t* offs, mipgen_candidate* out, int64_t* out_idx);
-hipError_t mipgen_launch_scatter_f64(hipStream_t, const double* src, const int64_t* idx, int64_t n, double* dst);
 hipError_t mipgen_launch_long_range(hipStream_t, int n, const char* seqs, const int64_t* offs, const int32_t* lens, const int32_t* denoms,
                                     const LrcMers*, double* out);
 hipError_t mipgen_launch_replay_condense(hipStream_t, int n_regions, int total_pos, const DevParams*, int n_pairs, int n_sizes_max, const DevRegion*,
@@ -259,7 +254,7 @@ struct mipgen_accel {
     DevBuf<int64_t> region_pos0, region_base0;
     DevBuf<CollapseTile> col_tiles;
     DevBuf<int32_t> collapsed;
-    // scores on a rounding boundary of the 6 printed digits are re-scored in the reference's operation order (fix_print_boundaries)
+    // scores on a rounding boundary of the 6 printed digits are re-scored in the reference's operation order (rescore)
     bool print_exact = true;
     double sum_abs_coef = 0.0;
     DevBuf<mipgen_candidate> pb_cands;
@@ -270,7 +265,7 @@ struct mipgen_accel {
     DevBuf<double> pb_scores;
     DevBuf<unsigned int> pb_count;
     // logistic candidates whose b^x lies in [2^53, 2^54) - their score turns on the last bit of the reference's pow (kernels_logistic_dense.hip) - listed by the
-    // dense kernel and re-scored in the reference's term order with the correctly rounded power before anything is replayed (rescore_saturated)
+    // dense kernel and re-scored in the reference's term order with the correctly rounded power before anything is replayed (rescore)
     DevBuf<int64_t> sat_idx;
     DevBuf<unsigned int> sat_count;
     DevBuf<mipgen_candidate> sat_cands;

@@ -13,48 +13,84 @@ int mipgen_pb_check(mipgen_accel* h)
                                 "(mipgen_accel_set_print_exact(h, 0) waives the guarantee)", v);
 }
 
-// SVR scores within the dense / list kernels' error of a midpoint between two 6-significant-digit numbers (what the front end prints,
-// mipgen.cpp:774) are re-scored by k_candidates in the reference's own operation order and overwritten, so that the printed digit is the
-// reference's (its error against the reference's double is ~1e-16 relative: the libm exponential).  No host round trip: the list length
-// stays on the device, the re-scoring grid is the list's capacity.  list = nullptr: the dense results of regions [r0, r1).
-// Logistic scores (method = MIPGEN_SCORE_LOGISTIC; round 5) take the same route: the dense kernel regroups the 69 terms by window (error ~1e-14 on the
-// exponent), the re-score evaluates them in the reference's order with every operation rounded on its own (logistic_exponent_exact).
-static int fix_print_boundaries(mipgen_accel* h, int r0, int r1, const mipgen_candidate* list, double* scores, const uint64_t* records, int64_t n, int method = MIPGEN_SCORE_SVR)
+// Re-score lists side by side: capacity and print-exact tolerance of every route.  The re-scoring grid is the list's capacity (the length stays
+// on the device: no host round trip).  SVR: a dense / list score differs from the reference's double by ~1e-12.  Logistic (round 5): the dense
+// kernel regroups the 69 terms by window (error ~1e-14 on the exponent); its scores sit within 1e-11 of a midpoint with probability <= 2e-5 -
+// a short list keeps the launch cheap beside the 0.1-ms kernels of small logistic batches.  Saturated logistic scores: 0.014 % of a (CCG)n
+// region's candidates sit in the tie binade.
+struct RescoreLimits { unsigned int cap; double tol_rel, tol_abs; };
+static RescoreLimits rescore_limits(const mipgen_accel* h, int kind, int method, int64_t n)
 {
-    if (!h->print_exact || n <= 0 || (method == MIPGEN_SCORE_SVR && h->n_sv <= 0)) return MIPGEN_OK;
-    // (the re-scoring grid is the list's capacity: logistic scores sit within 1e-11 of a midpoint with probability <= 2e-5 - a short list keeps the
-    // launch cheap beside the 0.1-ms kernels of small logistic batches)
-    const unsigned int cap = method == MIPGEN_SCORE_SVR ? (unsigned int)std::min<int64_t>(n / 1024 + 4096, (int64_t)1 << 24)
-                                                        : (unsigned int)std::min<int64_t>(n / 8192 + 256, (int64_t)1 << 22);
-    if (h->pb_cands.reserve(cap) || h->pb_idx.reserve(cap) || h->pb_scores.reserve(cap) || h->pb_count.reserve(1)) return MIPGEN_E_NOMEM;
-    const double tol_rel = method == MIPGEN_SCORE_SVR ? 1e-10 : 1e-11, tol_abs = method == MIPGEN_SCORE_SVR ? 1e-13 * std::max(1.0, h->sum_abs_coef) : 1e-300;
-    HIP_TRY(hipMemsetAsync(h->pb_count.p, 0, sizeof(unsigned int), h->stream));
-    if (list) HIP_TRY(mipgen_launch_print_boundary_scan_list(h->stream, list, scores, records, (int)n, tol_rel, tol_abs, h->pb_cands.p, h->pb_idx.p, h->pb_count.p, cap));
-    else HIP_TRY(mipgen_launch_print_boundary_scan(h->stream, h->dp, h->regions.p, r0, r1, scores, records, n, tol_rel, tol_abs, h->pb_cands.p, h->pb_idx.p, h->pb_count.p, cap, h->n_cu));
-    HIP_TRY(mipgen_launch_candidates(h->stream, (int)cap, h->dp, h->regions.p, h->pb_cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
-                                     h->gamma, h->rho, method, h->pb_scores.p, nullptr, nullptr, nullptr, 1, h->pb_count.p));
-    HIP_TRY(mipgen_launch_scatter_scores(h->stream, h->pb_scores.p, h->pb_idx.p, (int)cap, h->pb_count.p, scores, h->pb_over));
+    const bool svr = method == MIPGEN_SCORE_SVR;
+    int64_t cap;
+    if (kind == RESCORE_SATURATED) cap = std::min<int64_t>(n / 4096 + 4096, (int64_t)1 << 20);
+    else if (kind == RESCORE_SURV) cap = svr ? std::min<int64_t>(n / 256 + 1024, (int64_t)1 << 22) : std::min<int64_t>(n / 4096 + 64, (int64_t)1 << 20);
+    else cap = svr ? std::min<int64_t>(n / 1024 + 4096, (int64_t)1 << 24) : std::min<int64_t>(n / 8192 + 256, (int64_t)1 << 22);   // dense grid, candidate list
+    return {(unsigned int)cap, svr ? 1e-10 : 1e-11, svr ? 1e-13 * std::max(1.0, h->sum_abs_coef) : 1e-300};
+}
+
+// List -> re-score -> scatter back: every route that recomputes selected scores after the fast kernels.
+//  * Print-exact (RESCORE_DENSE / LIST / SURV): k_print_boundary_scan lists the scores within the kernels' error of a midpoint between two
+//    6-significant-digit numbers (what the front end prints, mipgen.cpp:774), so that the printed digit is the reference's (the re-score's
+//    error against the reference's double is ~1e-16 relative: the libm exponential).  Silent designs test the condensed survivors of a window
+//    only: nothing else is printed.  A list that overflows is reported by mipgen_pb_check.
+//  * RESCORE_SATURATED: the logistic candidates whose b^x lies in [2^53, 2^54) - their score turns on the last bit of the reference's pow - as
+//    the dense kernel listed them, before the replay, the condense fold and the collapse compare anything.  (A list that overflows leaves its
+//    surplus with the dense kernel's value: there is no guarantee to break - the reference's own double is a coin there - and no region short
+//    of a megabase of (CCG)n fills it.)
+// k_candidates re-scores the list in the reference's own operation order (literal; logistic: logistic_exponent_exact, pow_base_cr), its grid the
+// list's capacity; k_scatter_scores writes the values back where they came from.
+static int rescore(mipgen_accel* h, const RescoreSrc& src, int method)
+{
+    const bool sat = src.kind == RESCORE_SATURATED;
+    if (!sat && (!h->print_exact || src.n <= 0 || (method == MIPGEN_SCORE_SVR && h->n_sv <= 0))) return MIPGEN_OK;
+    const RescoreLimits lim = rescore_limits(h, src.kind, method, src.n);
+    DevBuf<mipgen_candidate>& cands = sat ? h->sat_cands : h->pb_cands;
+    DevBuf<int64_t>& idx = sat ? h->sat_idx : h->pb_idx;
+    DevBuf<double>& vals = sat ? h->sat_scores : h->pb_scores;
+    DevBuf<unsigned int>& count = sat ? h->sat_count : h->pb_count;
+    if (cands.reserve(lim.cap) || idx.reserve(lim.cap) || vals.reserve(lim.cap) || count.reserve(1)) return MIPGEN_E_NOMEM;
+    if (sat) HIP_TRY(mipgen_launch_index_candidates(h->stream, h->dp, h->regions.p, src.r0, src.r1, idx.p, count.p, lim.cap, cands.p));
+    else {
+        HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned int), h->stream));
+        HIP_TRY(mipgen_launch_print_boundary_scan(h->stream, h->dp, h->regions.p, &src, lim.tol_rel, lim.tol_abs, cands.p, idx.p, count.p, lim.cap, h->n_cu));
+    }
+    HIP_TRY(mipgen_launch_candidates(h->stream, (int)lim.cap, h->dp, h->regions.p, cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
+                                     h->gamma, h->rho, method, vals.p, nullptr, nullptr, nullptr, 1, count.p));
+    HIP_TRY(mipgen_launch_scatter_scores(h->stream, vals.p, idx.p, lim.cap, count.p, src.scores, src.surv, sat ? nullptr : h->pb_over));
     return MIPGEN_OK;
 }
 
-// the silent path (mipgen_accel_score_condense_all): only the condensed survivors of the window are ever printed, so only they are tested
-// and re-scored (2 per scan position instead of the whole dense grid); the value goes into the survivor's score field
-static int fix_print_boundaries_survivors(mipgen_accel* h, int w, int method = MIPGEN_SCORE_SVR)
+// the silent path (mipgen_accel_score_condense_*): the survivors of window w, 2 per scan position, instead of the whole dense grid
+static int fix_survivor_print_boundaries(mipgen_accel* h, int w, int method)
 {
     const Window& W = h->windows[(size_t)w];
-    const int64_t n = 2 * W.n_pos;
-    if (!h->print_exact || n <= 0 || (method == MIPGEN_SCORE_SVR && h->n_sv <= 0)) return MIPGEN_OK;
-    const unsigned int cap = method == MIPGEN_SCORE_SVR ? (unsigned int)std::min<int64_t>(n / 256 + 1024, (int64_t)1 << 22)
-                                                        : (unsigned int)std::min<int64_t>(n / 4096 + 64, (int64_t)1 << 20);
-    if (h->pb_cands.reserve(cap) || h->pb_idx.reserve(cap) || h->pb_scores.reserve(cap) || h->pb_count.reserve(1)) return MIPGEN_E_NOMEM;
-    const double tol_rel = method == MIPGEN_SCORE_SVR ? 1e-10 : 1e-11, tol_abs = method == MIPGEN_SCORE_SVR ? 1e-13 * std::max(1.0, h->sum_abs_coef) : 1e-300;
-    mipgen_survivor* surv = h->survivors.p + 2 * W.pos0;
-    HIP_TRY(hipMemsetAsync(h->pb_count.p, 0, sizeof(unsigned int), h->stream));
-    HIP_TRY(mipgen_launch_print_boundary_scan_surv(h->stream, h->dp, h->regions.p, W.r0, W.r1, surv, n, W.cand0, tol_rel, tol_abs, h->pb_cands.p, h->pb_idx.p, h->pb_count.p, cap));
-    HIP_TRY(mipgen_launch_candidates(h->stream, (int)cap, h->dp, h->regions.p, h->pb_cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
-                                     h->gamma, h->rho, method, h->pb_scores.p, nullptr, nullptr, nullptr, 1, h->pb_count.p));
-    HIP_TRY(mipgen_launch_scatter_surv_scores(h->stream, h->pb_scores.p, h->pb_idx.p, (int)cap, h->pb_count.p, surv, h->pb_over));
-    return MIPGEN_OK;
+    return rescore(h, {RESCORE_SURV, 2 * W.n_pos, nullptr, nullptr, nullptr, h->survivors.p + 2 * W.pos0, W.r0, W.r1, W.cand0}, method);
+}
+
+// The list scorer: the candidates cand_in[0, n) -> cand_scores, cand_records (+ cand_feats / cand_ints where asked).  Long SVR lists (a mixed
+// design re-scores every condensed survivor) go through k_features_batch (a wavefront per candidate) and the FP64 matrix cores (k_svr_gemm: all
+// candidate x support-vector distances instead of one model walk per candidate), then the print-exact re-score; the others through k_candidates.
+// le (optional): three events around the two stages of a matrix-core list, created here when timing is on.
+static int score_list(mipgen_accel* h, int n, int method, bool want_scores, bool features, bool ints, hipEvent_t* le)
+{
+    const bool batched = method == MIPGEN_SCORE_SVR && n >= 256 && want_scores;
+    if (batched && h->cand_feats.reserve((size_t)n * MIPGEN_N_FEATURES)) return MIPGEN_E_NOMEM;
+    const bool time_list = le && batched && !ints && h->timing;
+    if (time_list) { for (int k = 0; k < 3; k++) HIP_TRY(hipEventCreate(&le[k])); HIP_TRY(hipEventRecord(le[0], h->stream)); }
+    if (batched && !ints)
+        HIP_TRY(mipgen_launch_features_batch(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->cand_records.p,
+                                             h->cand_feats.p));
+    else
+        HIP_TRY(mipgen_launch_candidates(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts,
+                                         h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p, h->cand_records.p,
+                                         (features || batched) ? h->cand_feats.p : nullptr, ints ? h->cand_ints.p : nullptr, 0, nullptr));
+    if (time_list) HIP_TRY(hipEventRecord(le[1], h->stream));
+    if (batched) HIP_TRY(mipgen_launch_svr_gemm(h->stream, n, h->cand_feats.p, h->cand_records.p, h->model_t.p, h->sv_norm.p, h->sv_coef.p, h->sv_center.p, h->n_sv_pad,
+                                            h->gamma, h->rho, h->cand_scores.p));
+    if (time_list) HIP_TRY(hipEventRecord(le[2], h->stream));
+    if (!batched) return MIPGEN_OK;
+    return rescore(h, {RESCORE_LIST, n, h->cand_scores.p, h->cand_records.p, h->cand_in.p, nullptr, 0, 0, 0}, MIPGEN_SCORE_SVR);
 }
 
 // The dense grid of a window through the LIST scorer: the route of SVR parameter sets outside the tiled kernel's limits (scan size < 3,
@@ -91,8 +127,8 @@ static int score_window_impl(mipgen_accel* h, int w, int32_t method, bool fix_de
     if (method == MIPGEN_SCORE_LOGISTIC) {
         // the logistic kernels list the candidates whose score turns on the last bit of the reference's pow (b^x in [2^53, 2^54): GC-rich
         // microsatellites get there, nothing else)
-        sat_cap = (unsigned int)std::min<int64_t>(W.n_cand / 4096 + 4096, (int64_t)1 << 20);      // (0.014 % of a (CCG)n region's candidates sit in the tie binade; the re-score grid is the capacity)
-        if (h->sat_idx.reserve(sat_cap) || h->sat_count.reserve(1) || h->sat_cands.reserve(sat_cap) || h->sat_scores.reserve(sat_cap)) return MIPGEN_E_NOMEM;
+        sat_cap = rescore_limits(h, RESCORE_SATURATED, method, W.n_cand).cap;
+        if (h->sat_idx.reserve(sat_cap) || h->sat_count.reserve(1)) return MIPGEN_E_NOMEM;
         HIP_TRY(hipMemsetAsync(h->sat_count.p, 0, sizeof(unsigned int), h->stream));
     }
     if (method == MIPGEN_SCORE_LOGISTIC && h->ld_lds > 0)
@@ -104,21 +140,9 @@ static int score_window_impl(mipgen_accel* h, int w, int32_t method, bool fix_de
                                                h->log_tiles.p + W.log_tile0, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->scores.p, h->records.p,
                                                sat_cap ? h->sat_idx.p : nullptr, sat_cap ? h->sat_count.p : nullptr, sat_cap));
     if (ev) HIP_TRY(hipEventRecord(ev[1], h->stream));
-    if (sat_cap) {
-        // the listed candidates in the reference's own term order with the correctly rounded power (k_candidates: logistic_exponent_exact, pow_base_cr) - before
-        // the replay, the condense fold and the collapse compare anything.  (A list that overflows leaves its surplus with the dense kernel's value: there is no
-        // guarantee to break - the reference's own double is a coin there - and no region short of a megabase of (CCG)n fills it.)
-        HIP_TRY(mipgen_launch_index_candidates(h->stream, h->dp, h->regions.p, W.r0, W.r1, h->sat_idx.p, h->sat_count.p, sat_cap, h->sat_cands.p));
-        HIP_TRY(mipgen_launch_candidates(h->stream, (int)sat_cap, h->dp, h->regions.p, h->sat_cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
-                                         h->gamma, h->rho, MIPGEN_SCORE_LOGISTIC, h->sat_scores.p, nullptr, nullptr, nullptr, 1, h->sat_count.p));
-        HIP_TRY(mipgen_launch_scatter_scores(h->stream, h->sat_scores.p, h->sat_idx.p, (int)sat_cap, h->sat_count.p, h->scores.p, nullptr));
-    }
-    // logistic scores that sit on a rounding midpoint of the six printed digits: re-scored in the reference's term order (dense windows of non-silent
-    // designs; the silent path tests its survivors only)
-    if (method == MIPGEN_SCORE_LOGISTIC && fix_dense) { if (int rc = fix_print_boundaries(h, W.r0, W.r1, nullptr, h->scores.p, h->records.p, W.n_cand, MIPGEN_SCORE_LOGISTIC)) return rc; }
+    if (sat_cap) { if (int rc = rescore(h, {RESCORE_SATURATED, W.n_cand, h->scores.p, nullptr, nullptr, nullptr, W.r0, W.r1, 0}, method)) return rc; }
     if (svr_via_list) {
         if (int rc = svr_window_via_list(h, W)) return rc;
-        if (fix_dense) { if (int rc = fix_print_boundaries(h, W.r0, W.r1, nullptr, h->scores.p, h->records.p, W.n_cand)) return rc; }
     } else if (method == MIPGEN_SCORE_SVR) {
         const double gamma_l2e = h->gamma * 1.4426950408889634074;
         int split = h->sv_split > 0 ? h->sv_split : mipgen_pick_sv_split(W.n_svr_tiles, h->n_sv, h->n_cu);
@@ -167,8 +191,9 @@ static int score_window_impl(mipgen_accel* h, int w, int32_t method, bool fix_de
         HIP_TRY(mipgen_launch_svr_dense(h->stream, W.n_svr_tiles - W.n_svr_few, W.n_svr_few, h->svr_lds, h->dp, &h->geom, &h->geom_few, h->regions.p,
                                         h->svr_tiles.p + W.svr_tile0, h->bases.p, h->copy.p, (const double*)h->dconsts /* log10_tab is the first member */,
                                         h->model.p, h->n_sv, gamma_l2e, h->rho, h->s_guard, h->records.p, h->scores.p, W.n_cand, split, h->partials.p));
-        if (fix_dense) { if (int rc = fix_print_boundaries(h, W.r0, W.r1, nullptr, h->scores.p, h->records.p, W.n_cand)) return rc; }
     }
+    // scores that sit on a rounding midpoint of the six printed digits (dense windows of non-silent designs; the silent path tests its survivors only)
+    if (fix_dense) { if (int rc = rescore(h, {RESCORE_DENSE, W.n_cand, h->scores.p, h->records.p, nullptr, nullptr, W.r0, W.r1, 0}, method)) return rc; }
     if (ev) { HIP_TRY(hipEventRecord(ev[2], h->stream)); h->ev_used[(size_t)w] |= 1; }
     h->cur_window = w; h->scored = true; h->replayed = false;
     if ((size_t)w < h->win_state.size()) h->win_state[(size_t)w] = 0;          // its survivors / collapse results are of older scores now
@@ -237,7 +262,7 @@ int mipgen_accel_score_condense_window(mipgen_accel* h, int32_t w, int32_t metho
     std::fill(h->ev_used.begin(), h->ev_used.end(), 0);
     if (int rc = score_window_impl(h, w, method, false)) return rc;
     if (int rc = replay_window_impl(h, false)) return rc;
-    return fix_print_boundaries_survivors(h, w, method);
+    return fix_survivor_print_boundaries(h, w, method);
 }
 
 int mipgen_accel_score_condense_all(mipgen_accel* h, int32_t method)
@@ -248,7 +273,7 @@ int mipgen_accel_score_condense_all(mipgen_accel* h, int32_t method)
     for (int w = 0; w < (int)h->windows.size(); w++) {
         if (int rc = score_window_impl(h, w, method, false)) return rc;
         if (int rc = replay_window_impl(h, false)) return rc;
-        if (int rc = fix_print_boundaries_survivors(h, w, method)) return rc;
+        if (int rc = fix_survivor_print_boundaries(h, w, method)) return rc;
         if (int rc = collapse_window_impl(h)) return rc;
     }
     return MIPGEN_OK;
@@ -343,33 +368,15 @@ int mipgen_accel_score_candidates(mipgen_accel* h, const mipgen_candidate* cands
         (features && h->cand_feats.reserve((size_t)n * MIPGEN_N_FEATURES)) || (ints && h->cand_ints.reserve((size_t)n)))
         return MIPGEN_E_NOMEM;
     HIP_TRY(hipMemcpyAsync(h->cand_in.p, cands, (size_t)n * sizeof(mipgen_candidate), hipMemcpyHostToDevice, h->stream));
-    // long SVR lists (a mixed design re-scores every condensed survivor): features + records by k_features_batch (a wavefront per candidate),
-    // then all candidate x support-vector distances through the FP64 matrix cores (k_svr_gemm) instead of one model walk per candidate
-    const bool batched = method == MIPGEN_SCORE_SVR && n >= 256 && scores;
-    if (batched && h->cand_feats.reserve((size_t)n * MIPGEN_N_FEATURES)) return MIPGEN_E_NOMEM;
     hipEvent_t le[3] = {nullptr, nullptr, nullptr};
-    const bool time_list = batched && !ints && h->timing;
-    if (time_list) { for (hipEvent_t& e : le) HIP_TRY(hipEventCreate(&e)); HIP_TRY(hipEventRecord(le[0], h->stream)); }
-    if (batched && !ints)
-        // lists: one wavefront per candidate for the features + records, then the matrix-core scorer
-        HIP_TRY(mipgen_launch_features_batch(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->cand_records.p,
-                                             h->cand_feats.p));
-    else
-        HIP_TRY(mipgen_launch_candidates(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts,
-                                         h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p, h->cand_records.p,
-                                         (features || batched) ? h->cand_feats.p : nullptr, ints ? h->cand_ints.p : nullptr, 0, nullptr));
-    if (time_list) HIP_TRY(hipEventRecord(le[1], h->stream));
-    if (batched) HIP_TRY(mipgen_launch_svr_gemm(h->stream, n, h->cand_feats.p, h->cand_records.p, h->model_t.p, h->sv_norm.p, h->sv_coef.p, h->sv_center.p, h->n_sv_pad,
-                                            h->gamma, h->rho, h->cand_scores.p));
-    if (time_list) HIP_TRY(hipEventRecord(le[2], h->stream));
-    if (batched) { if (int rc = fix_print_boundaries(h, 0, 0, h->cand_in.p, h->cand_scores.p, h->cand_records.p, n)) return rc; }
+    if (int rc = score_list(h, n, method, scores != nullptr, features != nullptr, ints != nullptr, le)) return rc;
     if (scores) HIP_TRY(hipMemcpyAsync(scores, h->cand_scores.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (records) HIP_TRY(hipMemcpyAsync(records, h->cand_records.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     if (features) HIP_TRY(hipMemcpyAsync(features, h->cand_feats.p, (size_t)n * MIPGEN_N_FEATURES * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (ints) HIP_TRY(hipMemcpyAsync(ints, h->cand_ints.p, (size_t)n * sizeof(mipgen_candidate_ints), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (int rc_pb = mipgen_pb_check(h)) return rc_pb;
-    if (time_list) {
+    if (le[0]) {
         float a = 0.f, b = 0.f;
         if (hipEventElapsedTime(&a, le[0], le[1]) == hipSuccess && hipEventElapsedTime(&b, le[1], le[2]) == hipSuccess) { h->list_feat_ms = a; h->list_svr_ms = b; }
         for (hipEvent_t e : le) (void)hipEventDestroy(e);
@@ -623,19 +630,8 @@ int mipgen_accel_rescore_survivors(mipgen_accel* h)
         if (m > 0) {
             if (m > INT32_MAX) return fail(MIPGEN_E_INVALID, "too many survivors in one window for the list scorer");
             if (h->cand_scores.reserve((size_t)m) || h->cand_records.reserve((size_t)m)) return MIPGEN_E_NOMEM;
-            const bool batched = m >= 256;                                   // as mipgen_accel_score_candidates decides
-            if (batched) {
-                if (h->cand_feats.reserve((size_t)m * MIPGEN_N_FEATURES)) return MIPGEN_E_NOMEM;
-                HIP_TRY(mipgen_launch_features_batch(h->stream, (int)m, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->cand_records.p,
-                                                     h->cand_feats.p));
-                HIP_TRY(mipgen_launch_svr_gemm(h->stream, (int)m, h->cand_feats.p, h->cand_records.p, h->model_t.p, h->sv_norm.p, h->sv_coef.p, h->sv_center.p, h->n_sv_pad,
-                                               h->gamma, h->rho, h->cand_scores.p));
-                if (int rc = fix_print_boundaries(h, 0, 0, h->cand_in.p, h->cand_scores.p, h->cand_records.p, m)) return rc;
-            } else {
-                HIP_TRY(mipgen_launch_candidates(h->stream, (int)m, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts,
-                                                 h->model.p, h->n_sv, h->gamma, h->rho, MIPGEN_SCORE_SVR, h->cand_scores.p, h->cand_records.p, nullptr, nullptr, 0, nullptr));
-            }
-            HIP_TRY(mipgen_launch_scatter_f64(h->stream, h->cand_scores.p, h->rs_idx.p, m, svr));
+            if (int rc = score_list(h, (int)m, MIPGEN_SCORE_SVR, true, false, false, nullptr)) return rc;
+            HIP_TRY(mipgen_launch_scatter_scores(h->stream, h->cand_scores.p, h->rs_idx.p, m, nullptr, svr, nullptr, nullptr));
         }
     }
     if ((size_t)w < h->win_state.size()) h->win_state[(size_t)w] |= 4;

@@ -109,6 +109,20 @@ struct SvrTile {
                            // scores fit the LDS staging area of the kernel's epilogue (whole-row stores), as the host has checked
 };
 
+// the entries of a re-score list (accel_score.hip: rescore): what k_print_boundary_scan tests - or, for RESCORE_SATURATED, the dense indices
+// the logistic scoring kernels listed themselves - and where k_scatter_scores writes the re-scored values back
+enum { RESCORE_DENSE, RESCORE_LIST, RESCORE_SURV, RESCORE_SATURATED };
+struct RescoreSrc {
+    int kind;
+    int64_t n;                        // entries (SATURATED: the window's candidates)
+    double* scores;                   // DENSE / LIST: entry i's score; SATURATED: the window's scores
+    const uint64_t* records;          // DENSE / LIST: entry i's record
+    const mipgen_candidate* cands;    // LIST: entry i's candidate
+    mipgen_survivor* surv;            // SURV: entry i (score, record, batch-wide dense index)
+    int r0, r1;                       // DENSE / SURV / SATURATED: the window's regions (its dense indices are window-relative, as DevRegion::out_off)
+    int64_t cand0;                    // SURV: the window's first candidate
+};
+
 // static thread geometry of the dense SVR kernel for a parameter set (computed on the host once)
 struct SvrGeom {
     int32_t nchunk;        // per-thread chunks of the arm-pair list

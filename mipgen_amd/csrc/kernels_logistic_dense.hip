@@ -371,7 +371,7 @@ __global__ __launch_bounds__(LD_THREADS, 2) void k_logistic_dense(
                 if (ti >= (20 << 8) && !odd && special == 0) score = y / d;
                 // ... except where b^x reaches [2^53, 2^54): there 1 + y is a tie the reference rounds to even on the LAST bit of its pow, and its score -
                 // 1.0, or one / two ulps below - is a coin this kernel's y (1e-13 off) cannot call.  Those candidates are listed and re-scored in the
-                // reference's term order with the correctly rounded power (accel_score.hip: rescore_saturated; pow_base_cr.h) before anything is replayed.
+                // reference's term order with the correctly rounded power (accel_score.hip: rescore; pow_base_cr.h) before anything is replayed.
                 const bool coin = valid && special == 0 && !odd && ti >= 53 * 256 - 1 && ti <= 54 * 256;
                 if (__ballot(coin) && coin && sat_count) { const unsigned int at = atomicAdd(sat_count, 1u); if (at < sat_cap) sat_idx[at] = out_row + a; }
             }

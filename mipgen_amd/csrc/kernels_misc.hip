@@ -240,7 +240,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
     if (literal) {
         // the reference's own operation order (svm.cpp:329-368 k_function: d = x - y, sum += d * d in index order; :2511-2515 svm_predict_values:
         // sum += coef * k in support-vector order, then - rho), every operation rounded on its own (g++ on x86-64 does not contract to FMA):
-        // what mipgen_accel prints for the scores that sit on a rounding boundary of the 6 printed digits (accel_score.hip: fix_print_boundaries).
+        // what mipgen_accel prints for the scores that sit on a rounding boundary of the 6 printed digits (accel_score.hip: rescore).
         // Plain operators under `fp contract(off)`: HIP's __dmul_rn / __dadd_rn are plain operators compiled under contract(fast) - inlined, hipcc
         // fuses them into FMAs whatever the caller says.
 #pragma clang fp contract(off)
@@ -420,6 +420,25 @@ __global__ __launch_bounds__(FB_WAVES * 64) void k_features_batch(
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Dense index -> candidate: the one decode of every kernel below that turns a window-relative dense index (DevRegion::out_off is
+// window-relative too; layout [position][capture size][strand][arm pair], mipgen_accel.h) into its candidate.  The region is the last of
+// [r0, r1) with out_off <= idx: an empty region shares the offset of its successor and comes before it.  False where the index lies past
+// the region's scan positions.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool dense_candidate(const DevParams* P, const DevRegion* regions, int r0, int r1, int64_t idx, mipgen_candidate& c)
+{
+    int lo = r0, hi = r1 - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (regions[mid].out_off <= idx) lo = mid; else hi = mid - 1; }
+    const DevRegion& R = regions[lo];
+    const int A = P->n_pairs;
+    const int64_t local = idx - R.out_off, row = local / A, rest = row >> 1;
+    const int a = (int)(local % A), ki = (int)(rest % R.n_sizes), pi = (int)(rest / R.n_sizes);
+    c.region = lo; c.scan_start = R.first_pos + pi; c.capture_size = P->max_capture - (R.k0 + ki) * P->inc;
+    c.ext_len = P->arm_ext[a]; c.lig_len = P->arm_lig[a]; c.strand = (int)(row & 1);
+    return pi < R.n_pos;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // The slow SVR route of the dense grid (parameter sets the tiled kernel of kernels_svr.hip cannot take: scan sizes below 3, more than
 // 240 arm pairs, a tile beyond 160 KiB of LDS - the reference accepts any -arm_lengths / -capture_increment / range, mipgen.cpp:222-261,
 // 427-444): the candidates of a chunk of the window's dense index range are written out as a LIST (k_dense_candidates) and go through the
@@ -431,23 +450,8 @@ __global__ __launch_bounds__(256) void k_dense_candidates(const DevParams* __res
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int64_t idx = c0 + i;                                    // window-relative dense index (DevRegion::out_off is window-relative too)
-    int lo = r0, hi = r1;                                          // the last region with out_off <= idx: empty regions share the offset of the
-    while (hi - lo > 1) {                                          // next non-empty one and come before it
-        const int mid = (lo + hi) >> 1;
-        if (regions[mid].out_off <= idx) lo = mid; else hi = mid;
-    }
-    const DevRegion& R = regions[lo];
-    const int64_t rel = idx - R.out_off;
-    const int A = P->n_pairs;
-    const int a = (int)(rel % A);
-    const int64_t row = rel / A;
-    const int strand = (int)(row & 1);
-    const int64_t rest = row >> 1;
-    const int k = (int)(rest % R.n_sizes), pi = (int)(rest / R.n_sizes);
     mipgen_candidate c;
-    c.region = lo; c.scan_start = R.first_pos + pi; c.capture_size = P->max_capture - (R.k0 + k) * P->inc;
-    c.ext_len = P->arm_ext[a]; c.lig_len = P->arm_lig[a]; c.strand = strand;
+    dense_candidate(P, regions, r0, r1, c0 + i, c);
     out[i] = c;
 }
 __global__ __launch_bounds__(256) void k_dense_list_fix(int n, const uint64_t* __restrict__ records, double rho, double s_guard, double* __restrict__ scores)
@@ -455,10 +459,7 @@ __global__ __launch_bounds__(256) void k_dense_list_fix(int n, const uint64_t* _
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t rec = records[i];
-    const uint32_t flags = MIPGEN_REC_FLAGS(rec);
-    if (!(flags & MIPGEN_FLAG_VALID)) scores[i] = 0.0;
-    else if (flags & MIPGEN_FLAG_GUARD) scores[i] = s_guard;           // all-zero feature vector (SVMipv4.cpp:63-68)
-    else if (MIPGEN_REC_EXT_COPY(rec) == 0 || MIPGEN_REC_LIG_COPY(rec) == 0) scores[i] = -rho;   // log10(0) = -inf: every kernel value is 0
+    if (score_is_constant(rec)) scores[i] = record_score(rec, 0.0, rho, s_guard);
 }
 extern "C" hipError_t mipgen_launch_dense_candidates(hipStream_t stream, const DevParams* P, const DevRegion* regions, int r0, int r1, int64_t c0, int n,
                                                      mipgen_candidate* out)
@@ -499,8 +500,9 @@ extern "C" hipError_t mipgen_launch_candidates(
 // Scores on a rounding boundary of the printed digits.  The front end prints scores with 6 significant digits (mipgen.cpp:774: default
 // ostream precision); a dense SVR score differs from the reference's double by ~1e-12 (another summation order, table factors), so a
 // score within that distance of a midpoint between two 6-digit numbers could print another last digit.  k_print_boundary_scan lists the
-// dense-grid candidates of a window whose score lies within tol of such a midpoint (guard / zero-copy candidates carry exact constants and
-// are skipped); they are re-scored by k_candidates in the reference's own operation order and written back (k_scatter_scores).
+// entries whose score lies within tol of such a midpoint (scores the record fixes carry exact constants and are skipped) - entries of a
+// window's dense grid, of a candidate list or of a window's condensed survivors (RescoreSrc); they are re-scored by k_candidates in the
+// reference's own operation order and written back (k_scatter_scores).
 // ---------------------------------------------------------------------------------------------------------
 
 // distance of |s| to the nearest midpoint between two 6-significant-digit decimal numbers (what "%g" / the default ostream precision prints,
@@ -528,57 +530,82 @@ __device__ __forceinline__ bool near_print_midpoint(double s, double tol_rel, do
     return fabs(frac - 0.5) * unit <= tol_rel * a + tol_abs;
 }
 
-__global__ __launch_bounds__(256) void k_print_boundary_scan(const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, int r0, int r1,
-                                                             const double* __restrict__ scores, const uint64_t* __restrict__ records, int64_t n,
+// out_idx[k]: entry i of the source (a dense index, a list position, a survivor slot).  The midpoint test comes first: only entries near a
+// midpoint read their record.  The dense-grid scan runs over every candidate of a non-silent window: grid-stride, its grid capped by the
+// launch; the list and survivor scans take one entry per thread (a loop there more than doubles their VGPRs).
+template <int KIND>
+__global__ __launch_bounds__(256) void k_print_boundary_scan(const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, int r0, int r1, int64_t n,
+                                                             const double* __restrict__ scores, const uint64_t* __restrict__ records,
+                                                             const mipgen_candidate* __restrict__ cands, const mipgen_survivor* __restrict__ surv, int64_t cand0,
                                                              double tol_rel, double tol_abs, mipgen_candidate* __restrict__ out, int64_t* __restrict__ out_idx,
                                                              unsigned int* __restrict__ count, unsigned int cap)
 {
-    const int A = P->n_pairs;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
-        if (!near_print_midpoint(scores[idx], tol_rel, tol_abs)) continue;
-        const uint64_t rec = records[idx];
-        const uint32_t flags = MIPGEN_REC_FLAGS(rec);
-        if (!(flags & MIPGEN_FLAG_VALID) || (flags & MIPGEN_FLAG_GUARD) || MIPGEN_REC_EXT_COPY(rec) == 0 || MIPGEN_REC_LIG_COPY(rec) == 0) continue;
-        int lo = r0, hi = r1 - 1;                                           // the region of the candidate: the last one that starts at or before idx
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (regions[mid].out_off <= idx) lo = mid; else hi = mid - 1; }
-        const DevRegion& R = regions[lo];
-        const int64_t local = idx - R.out_off;
-        const int a_i = (int)(local % A);
-        const int64_t row = local / A;
-        const int strand = (int)(row & 1);
-        const int64_t rest = row >> 1;
-        const int ki = (int)(rest % R.n_sizes);
-        const int pi = (int)(rest / R.n_sizes);
-        if (pi >= R.n_pos) continue;                                        // (empty regions share an offset with their successor)
-        const unsigned int at = atomicAdd(count, 1u);
-        if (at < cap) {
-            mipgen_candidate c;
-            c.region = lo; c.scan_start = R.first_pos + pi; c.capture_size = P->max_capture - (R.k0 + ki) * P->inc;
-            c.ext_len = P->arm_ext[a_i]; c.lig_len = P->arm_lig[a_i]; c.strand = strand;
-            out[at] = c; out_idx[at] = idx;
+    auto scan = [&](int64_t i) {
+        uint64_t rec;
+        int64_t idx = i;                                                    // the window-relative dense index of a DENSE / SURV entry
+        if constexpr (KIND == RESCORE_SURV) {
+            const mipgen_survivor sv = surv[i];
+            if (sv.cand_index < 0 || !near_print_midpoint(sv.score, tol_rel, tol_abs)) return;
+            rec = sv.record; idx = sv.cand_index - cand0;
+        } else {
+            if (!near_print_midpoint(scores[i], tol_rel, tol_abs)) return;
+            rec = records[i];
         }
-    }
+        if (score_is_constant(rec)) return;
+        mipgen_candidate c;
+        if constexpr (KIND != RESCORE_LIST) { if (!dense_candidate(P, regions, r0, r1, idx, c)) return; }
+        const unsigned int at = atomicAdd(count, 1u);
+        if (at >= cap) return;
+        if constexpr (KIND == RESCORE_LIST) out[at] = cands[i]; else out[at] = c;
+        out_idx[at] = i;
+    };
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (KIND == RESCORE_DENSE) { for (int64_t i = i0; i < n; i += (int64_t)gridDim.x * blockDim.x) scan(i); }
+    else if (i0 < n) scan(i0);
 }
 
-// dense indices of a window -> candidates (the decode of k_print_boundary_scan for a ready-made index list: the saturated logistic candidates the dense kernel listed)
+// dense indices of a window -> candidates: the saturated logistic candidates the dense kernel listed
 __global__ __launch_bounds__(256) void k_index_candidates(const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, int r0, int r1, const int64_t* __restrict__ idx_list,
                                                           const unsigned int* __restrict__ count, unsigned int cap, mipgen_candidate* __restrict__ out)
 {
     const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cap || i >= *count) return;
-    const int64_t idx = idx_list[i];
-    const int A = P->n_pairs;
-    int lo = r0, hi = r1 - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (regions[mid].out_off <= idx) lo = mid; else hi = mid - 1; }
-    const DevRegion& R = regions[lo];
-    const int64_t local = idx - R.out_off;
-    const int a_i = (int)(local % A);
-    const int64_t row = local / A;
-    const int64_t rest = row >> 1;
     mipgen_candidate c;
-    c.region = lo; c.scan_start = R.first_pos + (int)(rest / R.n_sizes); c.capture_size = P->max_capture - (R.k0 + (int)(rest % R.n_sizes)) * P->inc;
-    c.ext_len = P->arm_ext[a_i]; c.lig_len = P->arm_lig[a_i]; c.strand = (int)(row & 1);
+    dense_candidate(P, regions, r0, r1, idx_list[i], c);
     out[i] = c;
+}
+
+// re-scored values back where they came from: entry i of the list -> dst[idx[i]] (a score array or the score field of a survivor).  n_dev: the
+// list length on the device (null: cap); `over` (host-mapped word, may be null): set when the scan listed more entries than the list holds -
+// the surplus was not re-scored, the caller reports it
+__device__ __forceinline__ double& score_at(double* d, int64_t i) { return d[i]; }
+__device__ __forceinline__ double& score_at(mipgen_survivor* d, int64_t i) { return d[i].score; }
+template <typename T>
+__global__ __launch_bounds__(256) void k_scatter_scores(const double* __restrict__ src, const int64_t* __restrict__ idx, int64_t cap, const unsigned int* __restrict__ n_dev,
+                                                        T* __restrict__ dst, unsigned int* __restrict__ over)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = n_dev ? (int64_t)*n_dev : cap;
+    if (i < cap && i < n) score_at(dst, idx[i]) = src[i];
+    if (i == 0 && over && n > cap) *over = (unsigned int)(n - cap);
+}
+
+extern "C" hipError_t mipgen_launch_print_boundary_scan(hipStream_t stream, const DevParams* P, const DevRegion* regions, const RescoreSrc* s, double tol_rel,
+                                                        double tol_abs, mipgen_candidate* out, int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu)
+{
+    if (s->n <= 0 || (s->kind != RESCORE_LIST && s->r1 <= s->r0)) return hipSuccess;
+    const int64_t want = (s->n + 255) / 256;
+    const unsigned grid = (unsigned)(s->kind == RESCORE_DENSE ? std::min<int64_t>(want, (int64_t)std::max(n_cu, 1) * 16) : want);
+#define SCAN(K) hipLaunchKernelGGL(k_print_boundary_scan<K>, dim3(grid), dim3(256), 0, stream, P, regions, s->r0, s->r1, s->n, s->scores, s->records, s->cands, \
+                                   s->surv, s->cand0, tol_rel, tol_abs, out, out_idx, count, cap)
+    switch (s->kind) {
+        case RESCORE_DENSE: SCAN(RESCORE_DENSE); break;
+        case RESCORE_LIST: SCAN(RESCORE_LIST); break;
+        case RESCORE_SURV: SCAN(RESCORE_SURV); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef SCAN
+    return hipGetLastError();
 }
 extern "C" hipError_t mipgen_launch_index_candidates(hipStream_t stream, const DevParams* P, const DevRegion* regions, int r0, int r1, const int64_t* idx, const unsigned int* count,
                                                      unsigned int cap, mipgen_candidate* out)
@@ -587,82 +614,15 @@ extern "C" hipError_t mipgen_launch_index_candidates(hipStream_t stream, const D
     hipLaunchKernelGGL(k_index_candidates, dim3((cap + 255) / 256), dim3(256), 0, stream, P, regions, r0, r1, idx, count, cap, out);
     return hipGetLastError();
 }
-
-// `over` (host-mapped word, may be null): set when the scan listed more entries than the list holds - the surplus was not re-scored, the caller reports it
-__global__ __launch_bounds__(256) void k_scatter_scores(const double* __restrict__ src, const int64_t* __restrict__ idx, int cap, const unsigned int* __restrict__ n_dev,
-                                                        double* __restrict__ scores, unsigned int* __restrict__ over)
+// one of dst / dst_surv
+extern "C" hipError_t mipgen_launch_scatter_scores(hipStream_t stream, const double* src, const int64_t* idx, int64_t cap, const unsigned int* n_dev, double* dst,
+                                                   mipgen_survivor* dst_surv, unsigned int* over)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap && (unsigned int)i < *n_dev) scores[idx[i]] = src[i];
-    if (i == 0 && over && *n_dev > (unsigned int)cap) *over = *n_dev - (unsigned int)cap;
-}
-
-// the same test over a candidate LIST (mixed designs: the survivors re-scored by the matrix-core scorer): entry i of the list
-__global__ __launch_bounds__(256) void k_print_boundary_scan_list(const mipgen_candidate* __restrict__ cands, const double* __restrict__ scores,
-                                                                  const uint64_t* __restrict__ records, int n, double tol_rel, double tol_abs,
-                                                                  mipgen_candidate* __restrict__ out, int64_t* __restrict__ out_idx,
-                                                                  unsigned int* __restrict__ count, unsigned int cap)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (!near_print_midpoint(scores[i], tol_rel, tol_abs)) return;
-    const uint64_t rec = records[i];
-    const uint32_t flags = MIPGEN_REC_FLAGS(rec);
-    if (!(flags & MIPGEN_FLAG_VALID) || (flags & MIPGEN_FLAG_GUARD) || MIPGEN_REC_EXT_COPY(rec) == 0 || MIPGEN_REC_LIG_COPY(rec) == 0) return;
-    const unsigned int at = atomicAdd(count, 1u);
-    if (at < cap) { out[at] = cands[i]; out_idx[at] = i; }
-}
-
-extern "C" hipError_t mipgen_launch_print_boundary_scan(hipStream_t stream, const DevParams* P, const DevRegion* regions, int r0, int r1, const double* scores,
-                                                        const uint64_t* records, int64_t n, double tol_rel, double tol_abs, mipgen_candidate* out,
-                                                        int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu)
-{
-    if (n <= 0 || r1 <= r0) return hipSuccess;
-    const int64_t want = (n + 255) / 256;
-    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)std::max(n_cu, 1) * 16);
-    hipLaunchKernelGGL(k_print_boundary_scan, dim3(grid), dim3(256), 0, stream, P, regions, r0, r1, scores, records, n, tol_rel, tol_abs, out, out_idx, count, cap);
+    if (cap <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((cap + 255) / 256));
+    if (dst_surv) hipLaunchKernelGGL(k_scatter_scores<mipgen_survivor>, grid, dim3(256), 0, stream, src, idx, cap, n_dev, dst_surv, over);
+    else hipLaunchKernelGGL(k_scatter_scores<double>, grid, dim3(256), 0, stream, src, idx, cap, n_dev, dst, over);
     return hipGetLastError();
-}
-
-// the same test over the condensed survivors of a window (silent designs print nothing else): entry i of the survivor array; the re-scored
-// value goes back into the survivor's score field
-__global__ __launch_bounds__(256) void k_print_boundary_scan_surv(const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, int r0, int r1,
-                                                                  const mipgen_survivor* __restrict__ surv, int64_t n, int64_t cand0, double tol_rel, double tol_abs,
-                                                                  mipgen_candidate* __restrict__ out, int64_t* __restrict__ out_idx,
-                                                                  unsigned int* __restrict__ count, unsigned int cap)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const mipgen_survivor sv = surv[i];
-    if (sv.cand_index < 0 || !near_print_midpoint(sv.score, tol_rel, tol_abs)) return;
-    const uint32_t flags = MIPGEN_REC_FLAGS(sv.record);
-    if (!(flags & MIPGEN_FLAG_VALID) || (flags & MIPGEN_FLAG_GUARD) || MIPGEN_REC_EXT_COPY(sv.record) == 0 || MIPGEN_REC_LIG_COPY(sv.record) == 0) return;
-    const int64_t idx = sv.cand_index - cand0;                             // window-relative, like DevRegion::out_off
-    const int A = P->n_pairs;
-    int lo = r0, hi = r1 - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (regions[mid].out_off <= idx) lo = mid; else hi = mid - 1; }
-    const DevRegion& R = regions[lo];
-    const int64_t local = idx - R.out_off;
-    const int a_i = (int)(local % A);
-    const int64_t row = local / A;
-    const int64_t rest = row >> 1;
-    const int ki = (int)(rest % R.n_sizes), pi = (int)(rest / R.n_sizes);
-    if (pi >= R.n_pos) return;
-    const unsigned int at = atomicAdd(count, 1u);
-    if (at < cap) {
-        mipgen_candidate c;
-        c.region = lo; c.scan_start = R.first_pos + pi; c.capture_size = P->max_capture - (R.k0 + ki) * P->inc;
-        c.ext_len = P->arm_ext[a_i]; c.lig_len = P->arm_lig[a_i]; c.strand = (int)(row & 1);
-        out[at] = c; out_idx[at] = i;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_scatter_surv_scores(const double* __restrict__ src, const int64_t* __restrict__ idx, int cap, const unsigned int* __restrict__ n_dev,
-                                                             mipgen_survivor* __restrict__ surv, unsigned int* __restrict__ over)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap && (unsigned int)i < *n_dev) surv[idx[i]].score = src[i];
-    if (i == 0 && over && *n_dev > (unsigned int)cap) *over = *n_dev - (unsigned int)cap;
 }
 
 // ---- every condensed survivor of a window as a candidate list, in slot order (mixed designs: the pick stage re-scores survivors with the SVR,
@@ -682,26 +642,10 @@ __global__ __launch_bounds__(256) void k_surv_candidates(const DevParams* __rest
     if (i >= n) return;
     const mipgen_survivor sv = surv[i];
     if (sv.cand_index < 0) return;
-    const int64_t idx = sv.cand_index - cand0;                             // window-relative, like DevRegion::out_off
-    const int A = P->n_pairs;
-    int lo = r0, hi = r1 - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (regions[mid].out_off <= idx) lo = mid; else hi = mid - 1; }
-    const DevRegion& R = regions[lo];
-    const int64_t local = idx - R.out_off;
-    const int a_i = (int)(local % A);
-    const int64_t row = local / A;
-    const int64_t rest = row >> 1;
-    const int ki = (int)(rest % R.n_sizes), pi = (int)(rest / R.n_sizes);
     mipgen_candidate c;
-    c.region = lo; c.scan_start = R.first_pos + pi; c.capture_size = P->max_capture - (R.k0 + ki) * P->inc;
-    c.ext_len = P->arm_ext[a_i]; c.lig_len = P->arm_lig[a_i]; c.strand = (int)(row & 1);
+    dense_candidate(P, regions, r0, r1, sv.cand_index - cand0, c);         // (cand_index is batch-wide)
     const int64_t at = offs[i];
     out[at] = c; out_idx[at] = i;
-}
-__global__ __launch_bounds__(256) void k_scatter_f64(const double* __restrict__ src, const int64_t* __restrict__ idx, int64_t n, double* __restrict__ dst)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[idx[i]] = src[i];
 }
 extern "C" hipError_t mipgen_launch_surv_keep(hipStream_t stream, const mipgen_survivor* surv, int64_t n, int64_t* keep, double* svr)
 {
@@ -713,41 +657,6 @@ extern "C" hipError_t mipgen_launch_surv_candidates(hipStream_t stream, const De
 {
     if (n <= 0 || r1 <= r0) return hipSuccess;
     hipLaunchKernelGGL(k_surv_candidates, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P, regions, r0, r1, surv, n, cand0, offs, out, out_idx);
-    return hipGetLastError();
-}
-extern "C" hipError_t mipgen_launch_scatter_f64(hipStream_t stream, const double* src, const int64_t* idx, int64_t n, double* dst)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scatter_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, idx, n, dst);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t mipgen_launch_print_boundary_scan_surv(hipStream_t stream, const DevParams* P, const DevRegion* regions, int r0, int r1, const mipgen_survivor* surv,
-                                                             int64_t n, int64_t cand0, double tol_rel, double tol_abs, mipgen_candidate* out, int64_t* out_idx,
-                                                             unsigned int* count, unsigned int cap)
-{
-    if (n <= 0 || r1 <= r0) return hipSuccess;
-    hipLaunchKernelGGL(k_print_boundary_scan_surv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P, regions, r0, r1, surv, n, cand0, tol_rel, tol_abs, out, out_idx, count, cap);
-    return hipGetLastError();
-}
-extern "C" hipError_t mipgen_launch_scatter_surv_scores(hipStream_t stream, const double* src, const int64_t* idx, int cap, const unsigned int* n_dev, mipgen_survivor* surv, unsigned int* over)
-{
-    if (cap <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scatter_surv_scores, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, stream, src, idx, cap, n_dev, surv, over);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t mipgen_launch_print_boundary_scan_list(hipStream_t stream, const mipgen_candidate* cands, const double* scores, const uint64_t* records, int n,
-                                                             double tol_rel, double tol_abs, mipgen_candidate* out, int64_t* out_idx, unsigned int* count, unsigned int cap)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_print_boundary_scan_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cands, scores, records, n, tol_rel, tol_abs, out, out_idx, count, cap);
-    return hipGetLastError();
-}
-extern "C" hipError_t mipgen_launch_scatter_scores(hipStream_t stream, const double* src, const int64_t* idx, int cap, const unsigned int* n_dev, double* scores, unsigned int* over)
-{
-    if (cap <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scatter_scores, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, stream, src, idx, cap, n_dev, scores, over);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // mip_record.h — the integer record of design_mip and the bounds skips, as the device kernels restate them: one definition each.
 //
 // The record layout is the one the MIPGEN_REC_* accessors of include/mipgen_accel.h read; every builder packs it with pack_record, and every
-// kernel that looks an oligo's copy number up, tests the mapping flag or places a candidate's arms does so through the functions below.
+// kernel that looks an oligo's copy number up, tests the mapping flag, places a candidate's arms or applies the record's constant SVR scores
+// does so through the functions below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -69,4 +70,22 @@ __device__ __forceinline__ uint64_t pack_record(int ext_copy, int lig_copy, int 
     const uint32_t ec = (uint32_t)min(max(ext_copy, 0), 65535), lc = (uint32_t)min(max(lig_copy, 0), 65535);
     return (uint64_t)ec | ((uint64_t)lc << 16) | ((uint64_t)min(masked_n, 255) << 32) | ((uint64_t)min(snp_count, 255) << 40) |
            ((uint64_t)flags << 48) | ((uint64_t)jc << 56);
+}
+
+// the record fixes the SVR score: the candidate is not constructed, an arm holds a guard base (the all-zero feature vector, SVMipv4.cpp:63-68)
+// or an arm's copy number is 0 (log10(0) = -inf: every kernel value is 0)
+__device__ __forceinline__ bool score_is_constant(uint64_t rec)
+{
+    const uint32_t flags = MIPGEN_REC_FLAGS(rec);
+    return !(flags & MIPGEN_FLAG_VALID) || (flags & MIPGEN_FLAG_GUARD) || MIPGEN_REC_EXT_COPY(rec) == 0 || MIPGEN_REC_LIG_COPY(rec) == 0;
+}
+
+// ... and the score with those constants applied: 0, s_guard (the model at the all-zero vector), -rho; s where the record does not fix it
+__device__ __forceinline__ double record_score(uint64_t rec, double s, double rho, double s_guard)
+{
+    const uint32_t flags = MIPGEN_REC_FLAGS(rec);
+    if (!(flags & MIPGEN_FLAG_VALID)) return 0.0;
+    if (flags & MIPGEN_FLAG_GUARD) return s_guard;
+    if (MIPGEN_REC_EXT_COPY(rec) == 0 || MIPGEN_REC_LIG_COPY(rec) == 0) return -rho;
+    return s;
 }
