@@ -444,6 +444,27 @@ int mipgen_accel_skip_state(mipgen_accel* h, uint8_t* state, double* previous_be
  * 1..8 forced.  Results do not depend on it. */
 int mipgen_accel_set_logistic_subruns(mipgen_accel* h, int32_t n);
 
+/* ---- training (svm.cpp:2095 svm_train, epsilon-SVR with an RBF kernel) ------------------------------ */
+/* libsvm's svm-train -s 3 -t 2 -h 1 on the device: the same model file, byte for byte (svm_save_model, svm.cpp:2644-2757).  The whole n x n float
+ * kernel matrix stays resident in HBM, so n is limited to MIPGEN_SVR_TRAIN_MAX_ROWS (64 GiB of matrix); a larger n is MIPGEN_E_NOMEM before anything
+ * is allocated. */
+#define MIPGEN_SVR_TRAIN_MAX_ROWS 131072
+typedef struct mipgen_svr_train_params {
+    double gamma, cost, epsilon_p, eps;   /* -g, -c, -p, -e: gamma >= 0, cost > 0, epsilon_p >= 0, eps > 0 (svm_check_parameter, svm.cpp:3026) */
+    int32_t shrinking, reserved;          /* shrinking must be 1 (-h 1) */
+} mipgen_svr_train_params;
+typedef struct mipgen_svr_train_info {
+    int64_t iterations;                   /* the solver's #iter */
+    int32_t n_sv, n_bsv;                  /* nSV, nBSV as svm_train_one counts them (svm.cpp:1677-1694) */
+    double rho, obj;
+    int32_t n_shrink, n_reconstruct;      /* do_shrinking calls; reconstruct_gradient calls that rebuilt an inactive gradient */
+    double gram_ms, solve_ms;             /* HIP-event time of the kernel-matrix build; wall time of the solver loop */
+} mipgen_svr_train_info;
+/* x: row-major [n][192] features (absent libsvm indices = 0), y: n targets; all finite.  Trains, writes model_path as svm_save_model would, then
+ * installs it through mipgen_accel_load_model_file.  Invalid arguments are MIPGEN_E_INVALID and leave the handle's model as it was.  info may be NULL. */
+int mipgen_accel_train_svr(mipgen_accel* h, int32_t n, const double* x, const double* y, const mipgen_svr_train_params* p, const char* model_path,
+                           mipgen_svr_train_info* info);
+
 /* ---- instrumentation ------------------------------------------------------------------------------ */
 /* HIP-event time (ms) of the kernels of the last scoring call (summed over its windows), measured on the handle's stream;
  * negative if unavailable.  which: 0 = dense SVR kernel, 1 = records + scoring kernels, 2 = records / logistic kernel,

@@ -122,6 +122,16 @@ def arm_pairs_of(p: Params) -> List[Tuple[int, int]]:
 COPY_RESIDENT = "resident"
 
 
+class SvrTrainParams(C.Structure):     # mipgen_svr_train_params
+    _fields_ = [("gamma", C.c_double), ("cost", C.c_double), ("epsilon_p", C.c_double), ("eps", C.c_double),
+                ("shrinking", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SvrTrainInfo(C.Structure):       # mipgen_svr_train_info
+    _fields_ = [("iterations", C.c_int64), ("n_sv", C.c_int32), ("n_bsv", C.c_int32), ("rho", C.c_double), ("obj", C.c_double),
+                ("n_shrink", C.c_int32), ("n_reconstruct", C.c_int32), ("gram_ms", C.c_double), ("solve_ms", C.c_double)]
+
+
 class BigCopy(C.Structure):
     _fields_ = [("region", C.c_int32), ("length", C.c_int32), ("start", C.c_int32), ("copies", C.c_int32)]
 
@@ -282,6 +292,8 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_load_model_file.argtypes = [vp, C.c_char_p]
     lib.mipgen_accel_set_model.argtypes = [vp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.mipgen_accel_model_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.mipgen_accel_train_svr.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(SvrTrainParams), C.c_char_p,
+                                           C.POINTER(SvrTrainInfo)]
     lib.mipgen_accel_upload_regions.argtypes = [vp, C.POINTER(Region), C.c_int32, C.POINTER(Grid)]
     lib.mipgen_accel_batch_candidates.argtypes = [vp]
     lib.mipgen_accel_batch_candidates.restype = C.c_int64
@@ -343,7 +355,7 @@ def load_library(path: Optional[str] = None):
                  "long_range_content", "replay_condense", "download_replay", "set_timing", "set_window_candidates",
                  "window_info", "score_window", "score_condense_all", "score_condense_window", "download_survivors", "survivors_device_ptr",
                  "set_sv_split", "set_print_exact", "set_logistic_subruns", "long_range_content_batch", "collapse", "region_bases", "download_collapsed", "count_oligo_copies", "count_oligo_copies_resident", "window_uniqueness", "window_uniqueness_begin", "window_flags_region", "window_uniqueness_end",
-                 "format_all_mips", "download_text", "set_dynamic_skip", "skipped_candidates", "skip_state"):
+                 "format_all_mips", "download_text", "set_dynamic_skip", "skipped_candidates", "skip_state", "train_svr"):
         getattr(lib, "mipgen_accel_" + name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -364,6 +376,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_count_oligo_copies_resident", "mipgen_accel_window_uniqueness", "mipgen_accel_window_uniqueness_begin", "mipgen_accel_window_flags_region",
     "mipgen_accel_window_uniqueness_end", "mipgen_accel_set_dynamic_skip", "mipgen_accel_skipped_candidates", "mipgen_accel_skip_state", "mipgen_accel_set_print_exact", "mipgen_accel_set_logistic_subruns",
     "mipgen_accel_rescore_survivors", "mipgen_accel_download_survivor_scores", "mipgen_accel_window_views", "mipgen_accel_synchronize",
+    "mipgen_accel_train_svr",
 ]
 
 
@@ -410,6 +423,20 @@ class Accel:
         n, g, r = C.c_int32(), C.c_double(), C.c_double()
         self._check(self.lib.mipgen_accel_model_info(self.h, C.byref(n), C.byref(g), C.byref(r)))
         return n.value, g.value, r.value
+
+    def train_svr(self, x: np.ndarray, y: np.ndarray, gamma: float, cost: float, epsilon_p: float, eps: float = 1e-3,
+                  model_path: str = "mipgen_svr.model", shrinking: int = 1) -> dict:
+        """libsvm's svm-train -s 3 -t 2 on the device (x: [n][192] features, y: n targets); writes model_path byte for byte as libsvm
+        would and makes it this handle's model.  Returns mipgen_svr_train_info as a dict."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != N_FEATURES or y.shape != (x.shape[0],):
+            raise ValueError(f"x must be [n][{N_FEATURES}] and y [n]; got {x.shape} and {y.shape}")
+        p = SvrTrainParams(gamma, cost, epsilon_p, eps, shrinking, 0)
+        info = SvrTrainInfo()
+        self._check(self.lib.mipgen_accel_train_svr(self.h, x.shape[0], x.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    y.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), model_path.encode(), C.byref(info)))
+        return {name: getattr(info, name) for name, _ in SvrTrainInfo._fields_}
 
     # regions
     def upload(self, regions: Sequence[RegionData]) -> List[Grid]:
