@@ -34,7 +34,7 @@ int mipgen_accel_create(const mipgen_params* params, int device, void* stream, m
     mipgen_accel* h = new mipgen_accel();
     // the buffers that reach gigabytes share the handle's pool
     h->copy.pool = h->scores.pool = h->partials.pool = h->records.pool = h->emitted.pool = h->survivors.pool = h->collapsed.pool = h->pos_region.pool =
-        h->pos_local.pool = h->bases.pool = h->letters.pool = h->unmap.pool = h->fmt_pool.pool = h->fmt_text.pool = h->fmt_temp.pool = &h->pool;
+        h->pos_local.pool = h->bases.pool = h->letters.pool = h->unmap.pool = h->fmt_pool.pool = h->fmt_text.pool = h->scan_temp.pool = &h->pool;
     h->device = device;
     h->params = *params;
     DevParams& D = h->hp;
@@ -145,13 +145,12 @@ void mipgen_accel_destroy(mipgen_accel* h)
     h->model.release(); h->model_t.release(); h->sv_norm.release(); h->sv_coef.release(); h->sv_center.release(); h->regions.release(); h->bases.release(); h->unmap.release(); h->copy.release();
     h->log_tiles.release(); h->svr_tiles.release(); h->ld_tiles.release(); h->scores.release(); h->records.release();
     h->emitted.release(); h->survivors.release(); h->emitted_per_region.release(); h->pos_region.release(); h->pos_local.release();
-    h->letters.release(); h->fmt_regions.release(); h->fmt_pool.release(); h->fmt_text.release(); h->fmt_temp.release();
+    h->letters.release(); h->fmt_regions.release(); h->fmt_pool.release(); h->fmt_text.release(); h->scan_temp.release();
     h->fmt_a.release(); h->fmt_b.release(); h->fmt_c.release(); h->fmt_d.release();
     h->region_pos0.release(); h->region_base0.release(); h->col_tiles.release(); h->collapsed.release();
     h->cand_in.release(); h->cand_scores.release(); h->cand_feats.release(); h->cand_records.release(); h->cand_ints.release();
     h->win_img.release();
-    h->pb_cands.release(); h->pb_idx.release(); h->pb_scores.release(); h->pb_count.release(); h->surv_svr.release(); h->rs_keep.release(); h->rs_offs.release(); h->rs_idx.release();
-    h->sat_idx.release(); h->sat_count.release(); h->sat_cands.release(); h->sat_scores.release();
+    h->pb.release(); h->sat.release(); h->surv_svr.release(); h->rs_keep.release(); h->rs_offs.release(); h->rs_idx.release();
     h->svr_tiles_lvl.release(); h->svr_tiles_kept.release(); h->run_bounds.release(); h->run_pbs.release(); h->run_state.release(); h->run_keep.release();
     h->run_offs.release(); h->skip_count.release();
     h->lrc_seq.release(); h->lrc_out.release(); h->lrc_offs.release(); h->lrc_lens.release(); h->lrc_denoms.release(); h->partials.release();
@@ -364,7 +363,7 @@ int mipgen_accel_upload_regions(mipgen_accel* h, const mipgen_region* regions, i
     const mipgen_params& P = h->params;
     const DevParams& D = h->hp;
     h->cur_window = -1;
-    h->windows.clear();
+    h->windows.clear(); h->win_state.clear();
     h->hregions.assign((size_t)n, DevRegion());
     h->grids.assign((size_t)n, mipgen_grid());
     int64_t seq_total = 0, copy_total = 0, unmap_total = 0, cand_total = 0, pos_total = 0, cand_max = 0;
@@ -459,6 +458,7 @@ int mipgen_accel_upload_regions(mipgen_accel* h, const mipgen_region* regions, i
             w.n_cand += g.count; w.n_pos += g.n_pos; w.r1 = i + 1;
         }
         h->windows.push_back(w);                                   // an empty batch is one empty window
+        h->win_state.assign(h->windows.size(), 0);
     }
     int64_t win_cand_max = 0;
     for (const Window& w : h->windows) win_cand_max = std::max(win_cand_max, w.n_cand);
@@ -542,7 +542,6 @@ int mipgen_accel_upload_regions(mipgen_accel* h, const mipgen_region* regions, i
     HIP_TRY(hipStreamSynchronize(h->stream));             // host staging vectors die here
     DIAG_LAP("buffers + copies");
     h->n_regions = n; h->n_cand = cand_total; h->total_pos = pos_total;
-    h->scored = false; h->replayed = false; h->win_state.assign(h->windows.size(), 0); h->fmt_bytes = -1;
     h->ev_used.assign(h->windows.size(), 0);
 #ifdef MIPGEN_DIAG
     fprintf(stderr, "[mipgen_accel] batch: %d regions, %lld candidates in %zu window(s)\n", n, (long long)cand_total, h->windows.size());

@@ -1,9 +1,8 @@
-// accel_internal.h — what the host-side translation units of libmipgen_accel.so share: the kernel launchers' prototypes, the error convention,
+// accel_internal.h — what the host-side translation units of libmipgen_accel.so share (the kernel launchers are in kernels.h): the error convention,
 // device buffers, the handle (struct mipgen_accel) and the helpers that cross files.  accel.hip: lifecycle, model, region batch; accel_tiles.hip:
 // tile lists of the scoring kernels; accel_score.hip: scoring / replay / collapse / record text / downloads; accel_kmer.hip: section 8f-3.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <functional>
 
 #include <algorithm>
 #include <chrono>
@@ -16,76 +15,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "kernels.h"
 #include "logistic_device.h"
-
-// ---- kernel launchers (other translation units) -------------------------------------------------------
-struct LrcMers { int8_t k[MIPGEN_N_LRC]; int8_t code[MIPGEN_N_LRC]; int8_t rc[MIPGEN_N_LRC]; };
-struct TileDims;
-extern "C" {
-size_t mipgen_logistic_lds_bytes(int span);
-hipError_t mipgen_launch_records_logistic(hipStream_t, int score, int n_tiles, int span_max, const DevParams*, const DevRegion*,
-                                          const LogTile*, const uint8_t*, const int32_t*, const uint8_t*, const HostConsts*,
-                                          double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
-size_t mipgen_svr_lds_bytes_tile(int np, int kc_ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads);
-int mipgen_svr_scores_fit_lds(int np, int kc, int n_pairs, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads);
-hipError_t mipgen_launch_svr_dense(hipStream_t, int n_tiles, int n_tiles_few, size_t lds_bytes, const DevParams*, const SvrGeom*, const SvrGeom* geom_few,
-                                   const DevRegion*, const SvrTile*, const uint8_t*, const int32_t*, const double* log10_tab,
-                                   const double* model, int n_sv, double gamma_l2e, double rho, double s_guard,
-                                   const uint64_t* records, double* scores, int64_t n_cand, int n_split, double* partials);
-hipError_t mipgen_launch_candidates(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t*,
-                                    const int32_t*, const uint8_t*, const HostConsts*, const double* model, int n_sv, double gamma,
-                                    double rho, int method, double*, uint64_t*, double*, mipgen_candidate_ints*, int literal, const unsigned int* n_dev);
-hipError_t mipgen_launch_print_boundary_scan(hipStream_t, const DevParams*, const DevRegion*, const RescoreSrc*, double tol_rel, double tol_abs, mipgen_candidate* out,
-                                             int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu);
-hipError_t mipgen_launch_scatter_scores(hipStream_t, const double* src, const int64_t* idx, int64_t cap, const unsigned int* n_dev, double* dst, mipgen_survivor* dst_surv,
-                                        unsigned int* over);
-hipError_t mipgen_launch_svr_run_state(hipStream_t s, int64_t n_pos, const DevParams* P, const DevRegion* regions, const int32_t* pos_region, const int32_t* pos_local,
-                                       const uint32_t* run_bounds, int max_levels, int level, double margin, const double* scores, const uint64_t* records, double* pbs,
-                                       uint8_t* state);
-hipError_t mipgen_launch_svr_tile_keep(hipStream_t s, int n_tiles, const SvrTile* tiles, const int64_t* region_pos0, int64_t win_pos0, const uint8_t* state, int64_t* keep);
-hipError_t mipgen_launch_svr_tile_compact(hipStream_t s, int n_tiles, const SvrTile* tiles, const int64_t* keep, const int64_t* offs, SvrTile* out, const DevParams* P,
-                                          const DevRegion* regions, double* scores, unsigned long long* skipped);
-hipError_t mipgen_launch_dense_candidates(hipStream_t, const DevParams* P, const DevRegion* regions, int r0, int r1, int64_t c0, int n, mipgen_candidate* out);
-hipError_t mipgen_launch_dense_list_fix(hipStream_t, int n, const uint64_t* records, double rho, double s_guard, double* scores);
-hipError_t mipgen_launch_surv_keep(hipStream_t, const mipgen_survivor* surv, int64_t n, int64_t* keep, double* svr);
-hipError_t mipgen_launch_surv_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const mipgen_survivor* surv, int64_t n, int64_t cand0,
-                                         const int64_t* offs, mipgen_candidate* out, int64_t* out_idx);
-hipError_t mipgen_launch_long_range(hipStream_t, int n, const char* seqs, const int64_t* offs, const int32_t* lens, const int32_t* denoms,
-                                    const LrcMers*, double* out);
-hipError_t mipgen_launch_replay_condense(hipStream_t, int n_regions, int total_pos, const DevParams*, int n_pairs, int n_sizes_max, const DevRegion*,
-                                         const int32_t* pos_region, const int32_t* pos_local, const double* scores,
-                                         const uint64_t* records, const int32_t* copy, int64_t cand_base, uint8_t* emitted,
-                                         mipgen_survivor* survivors, unsigned long long* emitted_per_region);
-size_t mipgen_logistic_dense_lds_bytes(int np_all, int np, int ssr, int ssmax, int Lmax, int n_up, int n_dn);
-hipError_t mipgen_launch_logistic_dense(hipStream_t, int n_tiles, size_t lds_bytes, const DevParams*, const DevRegion*, const SvrTile*, const uint8_t*,
-                                        const int32_t*, const uint8_t*, const HostConsts*, double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
-hipError_t mipgen_launch_index_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const int64_t* idx, const unsigned int* count, unsigned int cap,
-                                          mipgen_candidate* out);
-struct FmtRegion { int32_t chr_off, chr_len, label_off, label_len, feature_start, feature_stop; int64_t rb0; };
-struct FmtConst { char middle[96]; int32_t middle_len; int32_t n_regions; int64_t first_index; };
-hipError_t mipgen_launch_fmt_count(hipStream_t, int64_t n_rb, int r0, const FmtConst*, const FmtRegion*, const DevParams*, const DevRegion*, const uint8_t* emitted, int64_t* cnt);
-hipError_t mipgen_launch_fmt_records(hipStream_t, int write, int64_t n_rb, int r0, const FmtConst*, const FmtRegion*, const char* pool, const DevParams*, const DevRegion*,
-                                     const char* letters, const int32_t* copy, const double* scores, const uint64_t* records, const uint8_t* emitted,
-                                     const int64_t* rank0, const int64_t* off, int64_t* len_out, char* text);
-hipError_t mipgen_scan_i64(hipStream_t, void* temp, size_t* temp_bytes, const int64_t* in, int64_t* out, int64_t n);
-struct KmerParams { int32_t n_k; int32_t k[MIPGEN_MAX_OLIGO]; int32_t kmax; int32_t filter_bits; uint64_t cap_mask; };   // as in kernels_kmer.hip
-hipError_t mipgen_launch_features_batch(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t* bases, const int32_t* copy,
-                                        const uint8_t* unmap, const HostConsts*, uint64_t* records, double* features);
-hipError_t mipgen_launch_svr_gemm(hipStream_t, int n, const double* feats, const uint64_t* records, const double* model_t, const double* sv_norm,
-                                  const double* sv_coef, const double* center, int n_sv_pad, double gamma, double rho, double* scores);
-hipError_t mipgen_launch_kmer_insert(hipStream_t, const char* seq, int64_t len, const KmerParams*, uint64_t* keys, uint32_t* filter);
-hipError_t mipgen_launch_kmer_fold(hipStream_t, const uint32_t* filter, int filter_bits, uint32_t* folded);
-hipError_t mipgen_launch_kmer_count(hipStream_t, const char* genome, int64_t len, const KmerParams*, const uint64_t* keys, const uint32_t* filter,
-                                    const uint32_t* folded, unsigned int* counts, int n_cu);
-hipError_t mipgen_launch_fill_pos_map(hipStream_t, const int64_t* region_pos0, int n_regions, int64_t total, int32_t* pos_region, int32_t* pos_local);
-hipError_t mipgen_launch_kmer_lookup(hipStream_t, const char* seq, int64_t len, const KmerParams*, const uint64_t* keys, const unsigned int* counts, int32_t* out);
-hipError_t mipgen_launch_kmer_place(hipStream_t, const int32_t* src, int64_t len, const KmerParams*, const int64_t* roff, int n_regions, int32_t* dst, void* big,
-                                    unsigned int* n_big, unsigned int big_cap);
-hipError_t mipgen_launch_collapse(hipStream_t, int n_tiles, const CollapseTile* tiles, const DevParams*, const DevRegion*, const int64_t* region_pos0,
-                                  const int64_t* region_base0, const mipgen_survivor* survivors, const int32_t* copy, int64_t cand_base, int32_t* collapsed,
-                                  int max_scan_all);
-}
 
 // ---- errors ----------------------------------------------------------------------------------------------
 // (one buffer per calling thread, shared by the translation units of the library: accel.hip defines it)
@@ -190,6 +121,22 @@ struct PinnedPair {
     ~PinnedPair() { for (int b = 0; b < 2; b++) { if (done[b]) { if (busy[b]) (void)hipEventSynchronize(done[b]); (void)hipEventDestroy(done[b]); } if (buf[b]) (void)hipHostFree(buf[b]); } }
 };
 
+// What of a result window is current (mipgen_accel::win_state, one byte per window).  The result arrays, the emitted mask and the record text
+// hold one window at a time (cur_window); survivors, collapsed entries and survivor SVR scores are batch-wide and keep every window's slice.
+enum : uint8_t {
+    WIN_SURVIVORS = 1,               // survivors / emitted counts are of the scores the window got last (replay + condense ran on them)
+    WIN_MASK = 2,                    // ... and that replay kept the per-candidate emitted mask
+    WIN_COLLAPSED = 4,               // the collapsed entries are of those survivors
+    WIN_SURV_SVR = 8,                // surv_svr holds the SVR scores of those survivors
+    WIN_TEXT = 16,                   // fmt_text / fmt_bytes are the all_mips records of those scores
+};
+
+// scores picked out of the fast kernels' results for a second computation: the candidates, where each came from, the new values, how many
+struct RescoreList {
+    DevBuf<mipgen_candidate> cands; DevBuf<int64_t> idx; DevBuf<double> vals; DevBuf<unsigned int> count;
+    void release() { cands.release(); idx.release(); vals.release(); count.release(); }
+};
+
 struct mipgen_accel {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -223,9 +170,9 @@ struct mipgen_accel {
     DevBuf<char> letters;                     // the region strings as given (record formatting prints them; `bases` keeps only classes)
     // device-side all_mips formatting (section 8f-4)
     DevBuf<FmtRegion> fmt_regions;
-    DevBuf<char> fmt_pool, fmt_text, fmt_temp;
+    DevBuf<char> fmt_pool, fmt_text, scan_temp;   // (scan_temp: scratch of device_scan_i64, whoever scans)
     DevBuf<int64_t> fmt_a, fmt_b, fmt_c, fmt_d;
-    int64_t fmt_bytes = -1;
+    int64_t fmt_bytes = 0;                    // bytes in fmt_text (current while a window has WIN_TEXT)
     DevPool pool;                             // large buffers the handle let go of (see DevPool)
     DevBuf<int32_t> copy;
     std::vector<int32_t> resident_lens;      // seq_len of the regions whose copy tables mipgen_accel_count_oligo_copies_resident left in `copy`
@@ -240,10 +187,10 @@ struct mipgen_accel {
     int64_t window_cap = 0;          // max candidates per window; 0 = as many as fit in free device memory
     std::vector<int32_t> window_breaks;   // batch indices at which a window must start (mipgen_accel_set_window_breaks), ascending
     std::vector<Window> windows;
-    int cur_window = -1;
+    int cur_window = -1;             // the window whose scores / records are in the result arrays (-1: none scored since the upload)
+    std::vector<uint8_t> win_state;  // WIN_* per window, sized with `windows`
     DevBuf<double> scores, partials;
     DevBuf<uint64_t> records;
-    bool scored = false;
     // replay
     DevBuf<uint8_t> emitted;
     DevBuf<mipgen_survivor> survivors;
@@ -257,19 +204,13 @@ struct mipgen_accel {
     // scores on a rounding boundary of the 6 printed digits are re-scored in the reference's operation order (rescore)
     bool print_exact = true;
     double sum_abs_coef = 0.0;
-    DevBuf<mipgen_candidate> pb_cands;
+    RescoreList pb;
     // mixed designs: SVR score of every condensed survivor of the batch (mipgen_accel_rescore_survivors), slot for slot beside `survivors`
     DevBuf<double> surv_svr;
     DevBuf<int64_t> rs_keep, rs_offs, rs_idx;
-    DevBuf<int64_t> pb_idx;
-    DevBuf<double> pb_scores;
-    DevBuf<unsigned int> pb_count;
     // logistic candidates whose b^x lies in [2^53, 2^54) - their score turns on the last bit of the reference's pow (kernels_logistic_dense.hip) - listed by the
     // dense kernel and re-scored in the reference's term order with the correctly rounded power before anything is replayed (rescore)
-    DevBuf<int64_t> sat_idx;
-    DevBuf<unsigned int> sat_count;
-    DevBuf<mipgen_candidate> sat_cands;
-    DevBuf<double> sat_scores;
+    RescoreList sat;
     // flag image of the last mipgen_accel_window_uniqueness_begin: uint8 [win_sizes][win_total], region r at column win_roff[r]
     DevBuf<uint8_t> win_img;
     std::vector<int64_t> win_roff;
@@ -288,14 +229,11 @@ struct mipgen_accel {
     unsigned long long skipped_total = 0;
     bool skip_count_valid = false;
     unsigned int* pb_over = nullptr;         // host-mapped word: entries a re-score list could not hold (checked at the next download: pb_check)
-    std::vector<uint8_t> win_state;          // per result window: bit 0 = survivors / emitted counts are of the scores it holds now (replayed), bit 1 = collapsed,
-                                             // bit 2 = surv_svr holds the SVR scores of its current survivors
     DevBuf<double> model_t, sv_norm, sv_coef, sv_center;   // the model centred and transposed for the survivor-list scorer (kernels_svr_gemm.hip)
     int n_sv_pad = 0;
     double kmer_count_ms = -1.0;             // genome pass of the last mipgen_accel_count_oligo_copies
     double list_feat_ms = -1.0, list_svr_ms = -1.0;   // k_features_batch / k_svr_gemm of the last list call (timing enabled)
     int64_t kmer_genome_bytes = 0;
-    bool replayed = false, mask_valid = false;
     // sparse scratch
     DevBuf<mipgen_candidate> cand_in;
     DevBuf<double> cand_scores, cand_feats;
@@ -336,6 +274,9 @@ static inline void grid_of(const mipgen_params& P, const DevParams& D, const mip
     g->count = (int64_t)g->n_pos * g->n_sizes * P.n_arm_pairs * 2;
     g->offset = 0;
 }
+
+static inline bool win_has(const mipgen_accel* h, int w, uint8_t bits) { return w >= 0 && (h->win_state[(size_t)w] & bits) == bits; }   // (w = cur_window may be -1)
+static inline void win_set(mipgen_accel* h, int w, uint8_t bits) { h->win_state[(size_t)w] |= bits; }
 
 static inline uint8_t base_code(char c)
 {

@@ -1,6 +1,7 @@
 // accel_kmer.hip — SURVEY.md section 8f-3 behind the C ABI: arm-oligo copy numbers by exact k-mer counting and capture-window uniqueness
 // (kernels_kmer.hip, kernels_window.hip), the opt-in replacement of the reference's bwa round trips (mipgen.cpp:558-596, 796-873).
 #include "accel_internal.h"
+#include <functional>
 
 extern "C" {
 
@@ -174,18 +175,7 @@ int mipgen_accel_count_oligo_copies_resident(mipgen_accel* h, int32_t n_chrom, c
     return MIPGEN_OK;
 }
 
-
 // ---- section 8f-3, second half: uniqueness of whole capture windows (kernels_window.hip) ---------------------------------------------------
-extern "C" hipError_t mipgen_launch_window_spans(hipStream_t st, const char* q, const int64_t* roff, int n_regions, uint16_t* dist_bad, uint16_t* dist_end, uint16_t* dist_start);
-extern "C" hipError_t mipgen_launch_seed_index(hipStream_t st, const char* q, int64_t total, int k, const uint64_t* keys, uint64_t cap_mask, unsigned int* rmult,
-                                               unsigned int* rstart, unsigned int* rfill, uint32_t* rlist, unsigned int* alloc, int phase);
-extern "C" hipError_t mipgen_launch_window_verify(hipStream_t st, const char* G, int64_t glen, const char* q, int64_t total, const int32_t* sizes, int n_sizes, int k,
-                                                  const uint64_t* keys, uint64_t cap_mask, const unsigned int* counts, const uint32_t* filter, int filter_bits,
-                                                  const unsigned int* rmult, const unsigned int* rstart, const uint32_t* rlist, const uint16_t* dist_start, unsigned int* ctr);
-extern "C" hipError_t mipgen_launch_window_flags(hipStream_t st, const char* q, int64_t total, const int32_t* sizes, int n_sizes, int k, const uint64_t* keys,
-                                                 uint64_t cap_mask, const unsigned int* counts, const uint16_t* dist_bad, const uint16_t* dist_end, const unsigned int* ctr,
-                                                 uint8_t* unmap, const int64_t* roff, int n_regions, const int32_t* bounds, uint8_t* any);
-
 // bounds == nullptr: the full flag image goes to unmap_out (mipgen_accel_window_uniqueness).  bounds != nullptr: the flags are restricted to the
 // window starts the reference looks up on the device, the image stays in the handle (h->win_img) and any_out gets one byte per region
 // (mipgen_accel_window_uniqueness_begin)

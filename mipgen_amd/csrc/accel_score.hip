@@ -45,19 +45,26 @@ static int rescore(mipgen_accel* h, const RescoreSrc& src, int method)
     const bool sat = src.kind == RESCORE_SATURATED;
     if (!sat && (!h->print_exact || src.n <= 0 || (method == MIPGEN_SCORE_SVR && h->n_sv <= 0))) return MIPGEN_OK;
     const RescoreLimits lim = rescore_limits(h, src.kind, method, src.n);
-    DevBuf<mipgen_candidate>& cands = sat ? h->sat_cands : h->pb_cands;
-    DevBuf<int64_t>& idx = sat ? h->sat_idx : h->pb_idx;
-    DevBuf<double>& vals = sat ? h->sat_scores : h->pb_scores;
-    DevBuf<unsigned int>& count = sat ? h->sat_count : h->pb_count;
-    if (cands.reserve(lim.cap) || idx.reserve(lim.cap) || vals.reserve(lim.cap) || count.reserve(1)) return MIPGEN_E_NOMEM;
-    if (sat) HIP_TRY(mipgen_launch_index_candidates(h->stream, h->dp, h->regions.p, src.r0, src.r1, idx.p, count.p, lim.cap, cands.p));
+    RescoreList& L = sat ? h->sat : h->pb;
+    if (L.cands.reserve(lim.cap) || L.idx.reserve(lim.cap) || L.vals.reserve(lim.cap) || L.count.reserve(1)) return MIPGEN_E_NOMEM;
+    if (sat) HIP_TRY(mipgen_launch_index_candidates(h->stream, h->dp, h->regions.p, src.r0, src.r1, L.idx.p, L.count.p, lim.cap, L.cands.p));
     else {
-        HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned int), h->stream));
-        HIP_TRY(mipgen_launch_print_boundary_scan(h->stream, h->dp, h->regions.p, &src, lim.tol_rel, lim.tol_abs, cands.p, idx.p, count.p, lim.cap, h->n_cu));
+        HIP_TRY(hipMemsetAsync(L.count.p, 0, sizeof(unsigned int), h->stream));
+        HIP_TRY(mipgen_launch_print_boundary_scan(h->stream, h->dp, h->regions.p, &src, lim.tol_rel, lim.tol_abs, L.cands.p, L.idx.p, L.count.p, lim.cap, h->n_cu));
     }
-    HIP_TRY(mipgen_launch_candidates(h->stream, (int)lim.cap, h->dp, h->regions.p, cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
-                                     h->gamma, h->rho, method, vals.p, nullptr, nullptr, nullptr, 1, count.p));
-    HIP_TRY(mipgen_launch_scatter_scores(h->stream, vals.p, idx.p, lim.cap, count.p, src.scores, src.surv, sat ? nullptr : h->pb_over));
+    HIP_TRY(mipgen_launch_candidates(h->stream, (int)lim.cap, h->dp, h->regions.p, L.cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
+                                     h->gamma, h->rho, method, L.vals.p, nullptr, nullptr, nullptr, 1, L.count.p));
+    HIP_TRY(mipgen_launch_scatter_scores(h->stream, L.vals.p, L.idx.p, lim.cap, L.count.p, src.scores, src.surv, sat ? nullptr : h->pb_over));
+    return MIPGEN_OK;
+}
+
+// exclusive prefix sums of in[0, n) on the handle's stream (callers pass one element more than they count: the last output is the total)
+static int device_scan_i64(mipgen_accel* h, const int64_t* in, int64_t* out, int64_t n)
+{
+    size_t temp_bytes = 0;
+    HIP_TRY(mipgen_scan_i64(h->stream, nullptr, &temp_bytes, in, out, n));
+    if (h->scan_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
+    HIP_TRY(mipgen_scan_i64(h->stream, h->scan_temp.p, &temp_bytes, in, out, n));
     return MIPGEN_OK;
 }
 
@@ -128,17 +135,17 @@ static int score_window_impl(mipgen_accel* h, int w, int32_t method, bool fix_de
         // the logistic kernels list the candidates whose score turns on the last bit of the reference's pow (b^x in [2^53, 2^54): GC-rich
         // microsatellites get there, nothing else)
         sat_cap = rescore_limits(h, RESCORE_SATURATED, method, W.n_cand).cap;
-        if (h->sat_idx.reserve(sat_cap) || h->sat_count.reserve(1)) return MIPGEN_E_NOMEM;
-        HIP_TRY(hipMemsetAsync(h->sat_count.p, 0, sizeof(unsigned int), h->stream));
+        if (h->sat.idx.reserve(sat_cap) || h->sat.count.reserve(1)) return MIPGEN_E_NOMEM;
+        HIP_TRY(hipMemsetAsync(h->sat.count.p, 0, sizeof(unsigned int), h->stream));
     }
     if (method == MIPGEN_SCORE_LOGISTIC && h->ld_lds > 0)
         // records + logistic scores from per-window tables (kernels_logistic_dense.hip)
         HIP_TRY(mipgen_launch_logistic_dense(h->stream, W.n_ld_tiles, h->ld_lds, h->dp, h->regions.p, h->ld_tiles.p + W.ld_tile0, h->bases.p, h->copy.p,
-                                             h->unmap.p, h->dconsts, h->scores.p, h->records.p, h->sat_idx.p, h->sat_count.p, sat_cap));
+                                             h->unmap.p, h->dconsts, h->scores.p, h->records.p, h->sat.idx.p, h->sat.count.p, sat_cap));
     else
         HIP_TRY(mipgen_launch_records_logistic(h->stream, method == MIPGEN_SCORE_LOGISTIC, W.n_log_tiles, h->log_span_max, h->dp, h->regions.p,
                                                h->log_tiles.p + W.log_tile0, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->scores.p, h->records.p,
-                                               sat_cap ? h->sat_idx.p : nullptr, sat_cap ? h->sat_count.p : nullptr, sat_cap));
+                                               sat_cap ? h->sat.idx.p : nullptr, sat_cap ? h->sat.count.p : nullptr, sat_cap));
     if (ev) HIP_TRY(hipEventRecord(ev[1], h->stream));
     if (sat_cap) { if (int rc = rescore(h, {RESCORE_SATURATED, W.n_cand, h->scores.p, nullptr, nullptr, nullptr, W.r0, W.r1, 0}, method)) return rc; }
     if (svr_via_list) {
@@ -171,10 +178,7 @@ static int score_window_impl(mipgen_accel* h, int w, int32_t method, bool fix_de
                     HIP_TRY(mipgen_launch_svr_run_state(h->stream, W.n_pos, h->dp, h->regions.p, h->pos_region.p + W.pos0, h->pos_local.p + W.pos0, h->run_bounds.p,
                                                         h->svr_levels, l - 1, margin, h->scores.p, h->records.p, h->run_pbs.p, h->run_state.p));
                     HIP_TRY(mipgen_launch_svr_tile_keep(h->stream, nt, tl, h->region_pos0.p, W.pos0, h->run_state.p, h->run_keep.p));
-                    size_t temp_bytes = 0;
-                    HIP_TRY(mipgen_scan_i64(h->stream, nullptr, &temp_bytes, h->run_keep.p, h->run_offs.p, (int64_t)nt + 1));
-                    if (h->fmt_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
-                    HIP_TRY(mipgen_scan_i64(h->stream, h->fmt_temp.p, &temp_bytes, h->run_keep.p, h->run_offs.p, (int64_t)nt + 1));
+                    if (int rc = device_scan_i64(h, h->run_keep.p, h->run_offs.p, (int64_t)nt + 1)) return rc;
                     HIP_TRY(mipgen_launch_svr_tile_compact(h->stream, nt, tl, h->run_keep.p, h->run_offs.p, h->svr_tiles_kept.p, h->dp, h->regions.p, h->scores.p,
                                                            h->skip_count.p));
                     int64_t kept = 0;
@@ -195,8 +199,8 @@ static int score_window_impl(mipgen_accel* h, int w, int32_t method, bool fix_de
     // scores that sit on a rounding midpoint of the six printed digits (dense windows of non-silent designs; the silent path tests its survivors only)
     if (fix_dense) { if (int rc = rescore(h, {RESCORE_DENSE, W.n_cand, h->scores.p, h->records.p, nullptr, nullptr, W.r0, W.r1, 0}, method)) return rc; }
     if (ev) { HIP_TRY(hipEventRecord(ev[2], h->stream)); h->ev_used[(size_t)w] |= 1; }
-    h->cur_window = w; h->scored = true; h->replayed = false;
-    if ((size_t)w < h->win_state.size()) h->win_state[(size_t)w] = 0;          // its survivors / collapse results are of older scores now
+    if (h->cur_window >= 0) h->win_state[(size_t)h->cur_window] &= (uint8_t)~(WIN_MASK | WIN_TEXT);   // the mask and the text went with the result arrays
+    h->win_state[(size_t)w] = 0; h->cur_window = w;                            // its survivors / collapse results are of older scores now
     return MIPGEN_OK;
 }
 
@@ -212,10 +216,9 @@ static int replay_window_impl(mipgen_accel* h, bool want_mask)
     HIP_TRY(mipgen_launch_replay_condense(h->stream, h->n_regions, (int)W.n_pos, h->dp, h->hp.n_pairs, h->hp.n_sizes_all, h->regions.p, h->pos_region.p + W.pos0,
                                           h->pos_local.p + W.pos0, h->scores.p, h->records.p, h->copy.p, W.cand0, want_mask ? h->emitted.p : nullptr,
                                           h->survivors.p + 2 * W.pos0, h->emitted_per_region.p));
-    h->mask_valid = want_mask;
     if (h->timing && h->ev.size() >= 4 * ((size_t)w + 1)) { HIP_TRY(hipEventRecord(h->ev[4 * (size_t)w + 3], h->stream)); h->ev_used[(size_t)w] |= 2; }
-    h->replayed = true;
-    if ((size_t)w < h->win_state.size()) h->win_state[(size_t)w] = 1;
+    // collapse results and survivor SVR scores were of the survivors before; record text is of the same scores
+    h->win_state[(size_t)w] = (uint8_t)((h->win_state[(size_t)w] & WIN_TEXT) | WIN_SURVIVORS | (want_mask ? WIN_MASK : 0));
     return MIPGEN_OK;
 }
 
@@ -224,7 +227,7 @@ static int collapse_window_impl(mipgen_accel* h)
     const Window& W = h->windows[(size_t)h->cur_window];
     HIP_TRY(mipgen_launch_collapse(h->stream, W.n_col_tiles, h->col_tiles.p + W.col_tile0, h->dp, h->regions.p, h->region_pos0.p, h->region_base0.p,
                                    h->survivors.p, h->copy.p, W.cand0, h->collapsed.p, h->hp.max_capture - h->hp.min_sum));
-    if ((size_t)h->cur_window < h->win_state.size()) h->win_state[(size_t)h->cur_window] |= 2;
+    win_set(h, h->cur_window, WIN_COLLAPSED);
     return MIPGEN_OK;
 }
 
@@ -237,12 +240,19 @@ static int check_scoring_args(mipgen_accel* h, int32_t method)
     return MIPGEN_OK;
 }
 
-int mipgen_accel_score_window(mipgen_accel* h, int32_t w, int32_t method)
+// what a scoring call starts with: the checks above, the window index, the device, a fresh timing record
+static int begin_scoring_call(mipgen_accel* h, int32_t method, int32_t w)
 {
     if (int rc = check_scoring_args(h, method)) return rc;
     if (w < 0 || w >= (int32_t)h->windows.size()) return fail(MIPGEN_E_INVALID, "window %d out of range (%zu windows)", w, h->windows.size());
     HIP_TRY(hipSetDevice(h->device));
     std::fill(h->ev_used.begin(), h->ev_used.end(), 0);
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_score_window(mipgen_accel* h, int32_t w, int32_t method)
+{
+    if (int rc = begin_scoring_call(h, method, w)) return rc;
     return score_window_impl(h, w, method);
 }
 
@@ -256,10 +266,7 @@ int mipgen_accel_score_resident(mipgen_accel* h, int32_t method)
 
 int mipgen_accel_score_condense_window(mipgen_accel* h, int32_t w, int32_t method)
 {
-    if (int rc = check_scoring_args(h, method)) return rc;
-    if (w < 0 || w >= (int32_t)h->windows.size()) return fail(MIPGEN_E_INVALID, "window %d out of range (%zu windows)", w, h->windows.size());
-    HIP_TRY(hipSetDevice(h->device));
-    std::fill(h->ev_used.begin(), h->ev_used.end(), 0);
+    if (int rc = begin_scoring_call(h, method, w)) return rc;
     if (int rc = score_window_impl(h, w, method, false)) return rc;
     if (int rc = replay_window_impl(h, false)) return rc;
     return fix_survivor_print_boundaries(h, w, method);
@@ -267,9 +274,7 @@ int mipgen_accel_score_condense_window(mipgen_accel* h, int32_t w, int32_t metho
 
 int mipgen_accel_score_condense_all(mipgen_accel* h, int32_t method)
 {
-    if (int rc = check_scoring_args(h, method)) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    std::fill(h->ev_used.begin(), h->ev_used.end(), 0);
+    if (int rc = begin_scoring_call(h, method, 0)) return rc;             // (a resident batch has a window 0)
     for (int w = 0; w < (int)h->windows.size(); w++) {
         if (int rc = score_window_impl(h, w, method, false)) return rc;
         if (int rc = replay_window_impl(h, false)) return rc;
@@ -324,7 +329,7 @@ int mipgen_accel_result_device_ptrs(const mipgen_accel* h, void** scores_dev, vo
 int mipgen_accel_download_results(mipgen_accel* h, double* scores, uint64_t* records, int64_t first, int64_t count)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->scored || h->cur_window < 0) return fail(MIPGEN_E_STATE, "nothing scored yet");
+    if (h->cur_window < 0) return fail(MIPGEN_E_STATE, "nothing scored yet");
     const Window& W = h->windows[(size_t)h->cur_window];
     if (first < W.cand0 || count < 0 || first + count > W.cand0 + W.n_cand)
         return fail(MIPGEN_E_INVALID, "range [%lld,+%lld) outside the scored window [%lld,+%lld)", (long long)first, (long long)count, (long long)W.cand0, (long long)W.n_cand);
@@ -334,8 +339,7 @@ int mipgen_accel_download_results(mipgen_accel* h, double* scores, uint64_t* rec
     if (scores) HIP_TRY(hipMemcpyAsync(scores, h->scores.p + off, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (records) HIP_TRY(hipMemcpyAsync(records, h->records.p + off, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc_pb = mipgen_pb_check(h)) return rc_pb;
-    return MIPGEN_OK;
+    return mipgen_pb_check(h);
 }
 
 int mipgen_accel_score_regions(mipgen_accel* h, const mipgen_region* regions, int32_t n, int32_t method, mipgen_grid* grids_out,
@@ -438,7 +442,7 @@ int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, i
 int mipgen_accel_replay_condense(mipgen_accel* h)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->scored || h->cur_window < 0) return fail(MIPGEN_E_STATE, "replay requested before scoring");
+    if (h->cur_window < 0) return fail(MIPGEN_E_STATE, "replay requested before scoring");
     HIP_TRY(hipSetDevice(h->device));
     return replay_window_impl(h, true);
 }
@@ -447,11 +451,9 @@ int mipgen_accel_download_replay(mipgen_accel* h, int64_t* emitted_per_region, m
                                  uint8_t* emitted_mask, int64_t mask_capacity)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->replayed || h->cur_window < 0) return fail(MIPGEN_E_STATE, "mipgen_accel_replay_condense has not run on these scores");
+    if (!win_has(h, h->cur_window, WIN_SURVIVORS)) return fail(MIPGEN_E_STATE, "mipgen_accel_replay_condense has not run on these scores");
     const Window& W = h->windows[(size_t)h->cur_window];
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc_pb = mipgen_pb_check(h)) return rc_pb;
+    if (int rc = mipgen_accel_synchronize(h)) return rc;             // (device, stream, mipgen_pb_check)
     if (emitted_per_region && W.r1 > W.r0)
         HIP_TRY(hipMemcpy(emitted_per_region, h->emitted_per_region.p + W.r0, (size_t)(W.r1 - W.r0) * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (survivors) {
@@ -459,7 +461,7 @@ int mipgen_accel_download_replay(mipgen_accel* h, int64_t* emitted_per_region, m
         if (W.n_pos) HIP_TRY(hipMemcpy(survivors, h->survivors.p + 2 * W.pos0, (size_t)(2 * W.n_pos) * sizeof(mipgen_survivor), hipMemcpyDeviceToHost));
     }
     if (emitted_mask) {
-        if (!h->mask_valid) return fail(MIPGEN_E_STATE, "the emitted mask is only kept by mipgen_accel_replay_condense, not by mipgen_accel_score_condense_all");
+        if (!win_has(h, h->cur_window, WIN_MASK)) return fail(MIPGEN_E_STATE, "the emitted mask is only kept by mipgen_accel_replay_condense, not by mipgen_accel_score_condense_all");
         if (mask_capacity < W.n_cand) return fail(MIPGEN_E_INVALID, "mask capacity too small");
         if (W.n_cand) HIP_TRY(hipMemcpy(emitted_mask, h->emitted.p, (size_t)W.n_cand, hipMemcpyDeviceToHost));
     }
@@ -469,10 +471,9 @@ int mipgen_accel_download_replay(mipgen_accel* h, int64_t* emitted_per_region, m
 int mipgen_accel_collapse(mipgen_accel* h)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->replayed || h->cur_window < 0) return fail(MIPGEN_E_STATE, "collapse requested before replay + condense");
+    if (!win_has(h, h->cur_window, WIN_SURVIVORS)) return fail(MIPGEN_E_STATE, "collapse requested before replay + condense");
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = collapse_window_impl(h)) return rc;
-    return MIPGEN_OK;
+    return collapse_window_impl(h);
 }
 
 int mipgen_accel_region_bases(const mipgen_accel* h, int32_t region, int64_t* first_entry, int32_t* n_bases)
@@ -488,7 +489,7 @@ int mipgen_accel_download_collapsed(mipgen_accel* h, int32_t window, int32_t* be
     if (!h || !best_scan_index) return fail(MIPGEN_E_INVALID, "bad arguments");
     // validity is per result window: every window asked for must have been collapsed since it was last scored
     for (size_t w = 0; w < h->win_state.size(); w++)
-        if ((window < 0 || (size_t)window == w) && !(h->win_state[w] & 2))
+        if ((window < 0 || (size_t)window == w) && !win_has(h, (int)w, WIN_COLLAPSED))
             return fail(MIPGEN_E_STATE, "mipgen_accel_collapse / mipgen_accel_score_condense_all has not run on the current scores of window %zu", w);
     if (h->win_state.empty()) return fail(MIPGEN_E_STATE, "no resident region batch");
     int64_t first = 0, count = h->h_region_base0.empty() ? 0 : h->h_region_base0.back();
@@ -507,7 +508,7 @@ int mipgen_accel_download_collapsed(mipgen_accel* h, int32_t window, int32_t* be
 int mipgen_accel_format_all_mips(mipgen_accel* h, const mipgen_record_names* names, const char* middle, int64_t first_index, int64_t* n_records, int64_t* n_bytes)
 {
     if (!h || !middle || !n_records || !n_bytes) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (!h->replayed || !h->mask_valid || h->cur_window < 0) return fail(MIPGEN_E_STATE, "format_all_mips needs mipgen_accel_replay_condense on the scored window first");
+    if (!win_has(h, h->cur_window, WIN_SURVIVORS | WIN_MASK)) return fail(MIPGEN_E_STATE, "format_all_mips needs mipgen_accel_replay_condense on the scored window first");
     const Window& W = h->windows[(size_t)h->cur_window];
     const int nr = W.r1 - W.r0;
     if (nr > 0 && !names) return fail(MIPGEN_E_INVALID, "bad arguments");
@@ -530,25 +531,22 @@ int mipgen_accel_format_all_mips(mipgen_accel* h, const mipgen_record_names* nam
         f.rb0 = n_rb;
         n_rb += (int64_t)d.n_pos * d.n_sizes;
     }
-    *n_records = 0; *n_bytes = 0; h->fmt_bytes = 0;
+    *n_records = 0; *n_bytes = 0; h->fmt_bytes = 0; win_set(h, h->cur_window, WIN_TEXT);
     if (n_rb == 0) return MIPGEN_OK;
     if (n_rb + 1 > INT32_MAX) return fail(MIPGEN_E_INVALID, "window too large for record formatting (%lld row blocks)", (long long)n_rb);
     if (h->fmt_regions.reserve(fr.size()) || h->fmt_pool.reserve(std::max<size_t>(pool.size(), 1)) || h->fmt_a.reserve((size_t)n_rb + 1) || h->fmt_b.reserve((size_t)n_rb + 1) ||
         h->fmt_c.reserve((size_t)n_rb + 1) || h->fmt_d.reserve((size_t)n_rb + 1))
         return MIPGEN_E_NOMEM;
-    size_t temp_bytes = 0;
-    HIP_TRY(mipgen_scan_i64(h->stream, nullptr, &temp_bytes, h->fmt_a.p, h->fmt_b.p, n_rb + 1));
-    if (h->fmt_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
     HIP_TRY(hipMemcpyAsync(h->fmt_regions.p, fr.data(), fr.size() * sizeof(FmtRegion), hipMemcpyHostToDevice, h->stream));
     if (!pool.empty()) HIP_TRY(hipMemcpyAsync(h->fmt_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(h->fmt_a.p + n_rb, 0, sizeof(int64_t), h->stream));
     HIP_TRY(hipMemsetAsync(h->fmt_c.p + n_rb, 0, sizeof(int64_t), h->stream));
     // records per row block -> ranks; bytes per row block -> offsets; then the bytes
     HIP_TRY(mipgen_launch_fmt_count(h->stream, n_rb, W.r0, &FC, h->fmt_regions.p, h->dp, h->regions.p, h->emitted.p, h->fmt_a.p));
-    HIP_TRY(mipgen_scan_i64(h->stream, h->fmt_temp.p, &temp_bytes, h->fmt_a.p, h->fmt_b.p, n_rb + 1));
+    if (int rc = device_scan_i64(h, h->fmt_a.p, h->fmt_b.p, n_rb + 1)) return rc;
     HIP_TRY(mipgen_launch_fmt_records(h->stream, 0, n_rb, W.r0, &FC, h->fmt_regions.p, h->fmt_pool.p, h->dp, h->regions.p, h->letters.p, h->copy.p, h->scores.p,
                                       h->records.p, h->emitted.p, h->fmt_b.p, nullptr, h->fmt_c.p, nullptr));
-    HIP_TRY(mipgen_scan_i64(h->stream, h->fmt_temp.p, &temp_bytes, h->fmt_c.p, h->fmt_d.p, n_rb + 1));
+    if (int rc = device_scan_i64(h, h->fmt_c.p, h->fmt_d.p, n_rb + 1)) return rc;
     int64_t totals[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&totals[0], h->fmt_b.p + n_rb, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(&totals[1], h->fmt_d.p + n_rb, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -564,7 +562,7 @@ int mipgen_accel_format_all_mips(mipgen_accel* h, const mipgen_record_names* nam
 int mipgen_accel_download_text(mipgen_accel* h, char* dst, int64_t capacity)
 {
     if (!h || (!dst && capacity > 0)) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (h->fmt_bytes < 0) return fail(MIPGEN_E_STATE, "mipgen_accel_format_all_mips has not run on this window");
+    if (!win_has(h, h->cur_window, WIN_TEXT)) return fail(MIPGEN_E_STATE, "mipgen_accel_format_all_mips has not run on this window");
     if (capacity < h->fmt_bytes) return fail(MIPGEN_E_INVALID, "text capacity %lld < %lld bytes", (long long)capacity, (long long)h->fmt_bytes);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -578,10 +576,8 @@ int mipgen_accel_download_survivors(mipgen_accel* h, int64_t* emitted_per_region
     // batch-wide survivors: every result window must have been replayed + condensed since it was last scored
     if (h->win_state.empty()) return fail(MIPGEN_E_STATE, "mipgen_accel_score_condense_all has not run on this batch");
     for (size_t w = 0; w < h->win_state.size(); w++)
-        if (!(h->win_state[w] & 1)) return fail(MIPGEN_E_STATE, "mipgen_accel_score_condense_all has not run on this batch (window %zu holds no current survivors)", w);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc_pb = mipgen_pb_check(h)) return rc_pb;
+        if (!win_has(h, (int)w, WIN_SURVIVORS)) return fail(MIPGEN_E_STATE, "mipgen_accel_score_condense_all has not run on this batch (window %zu holds no current survivors)", w);
+    if (int rc = mipgen_accel_synchronize(h)) return rc;             // (device, stream, mipgen_pb_check)
     if (emitted_per_region && h->n_regions)
         HIP_TRY(hipMemcpy(emitted_per_region, h->emitted_per_region.p, (size_t)h->n_regions * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (survivors) {
@@ -607,7 +603,7 @@ int mipgen_accel_survivors_device_ptr(const mipgen_accel* h, void** survivors_de
 int mipgen_accel_rescore_survivors(mipgen_accel* h)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->replayed || h->cur_window < 0) return fail(MIPGEN_E_STATE, "mipgen_accel_replay_condense has not run on these scores");
+    if (!win_has(h, h->cur_window, WIN_SURVIVORS)) return fail(MIPGEN_E_STATE, "mipgen_accel_replay_condense has not run on these scores");
     if (h->model.p == nullptr) return fail(MIPGEN_E_MODEL, "SVR scoring requested but no model is loaded");
     const int w = h->cur_window;
     const Window& W = h->windows[(size_t)w];
@@ -619,10 +615,7 @@ int mipgen_accel_rescore_survivors(mipgen_accel* h)
         const mipgen_survivor* surv = h->survivors.p + 2 * W.pos0;
         double* svr = h->surv_svr.p + 2 * W.pos0;
         HIP_TRY(mipgen_launch_surv_keep(h->stream, surv, n, h->rs_keep.p, svr));
-        size_t temp_bytes = 0;
-        HIP_TRY(mipgen_scan_i64(h->stream, nullptr, &temp_bytes, h->rs_keep.p, h->rs_offs.p, n + 1));
-        if (h->fmt_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
-        HIP_TRY(mipgen_scan_i64(h->stream, h->fmt_temp.p, &temp_bytes, h->rs_keep.p, h->rs_offs.p, n + 1));
+        if (int rc = device_scan_i64(h, h->rs_keep.p, h->rs_offs.p, n + 1)) return rc;
         HIP_TRY(mipgen_launch_surv_candidates(h->stream, h->dp, h->regions.p, W.r0, W.r1, surv, n, W.cand0, h->rs_offs.p, h->cand_in.p, h->rs_idx.p));
         int64_t m = 0;
         HIP_TRY(hipMemcpyAsync(&m, h->rs_offs.p + n, sizeof m, hipMemcpyDeviceToHost, h->stream));
@@ -634,19 +627,17 @@ int mipgen_accel_rescore_survivors(mipgen_accel* h)
             HIP_TRY(mipgen_launch_scatter_scores(h->stream, h->cand_scores.p, h->rs_idx.p, m, nullptr, svr, nullptr, nullptr));
         }
     }
-    if ((size_t)w < h->win_state.size()) h->win_state[(size_t)w] |= 4;
+    win_set(h, w, WIN_SURV_SVR);
     return MIPGEN_OK;
 }
 
 int mipgen_accel_download_survivor_scores(mipgen_accel* h, int32_t window, double* svr, int64_t capacity)
 {
     if (!h || !svr || window < 0 || window >= (int32_t)h->windows.size()) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if ((size_t)window >= h->win_state.size() || !(h->win_state[(size_t)window] & 4)) return fail(MIPGEN_E_STATE, "mipgen_accel_rescore_survivors has not run on the current survivors of window %d", window);
+    if (!win_has(h, window, WIN_SURV_SVR)) return fail(MIPGEN_E_STATE, "mipgen_accel_rescore_survivors has not run on the current survivors of window %d", window);
     const Window& W = h->windows[(size_t)window];
     if (capacity < 2 * W.n_pos) return fail(MIPGEN_E_INVALID, "capacity too small");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc_pb = mipgen_pb_check(h)) return rc_pb;
+    if (int rc = mipgen_accel_synchronize(h)) return rc;             // (device, stream, mipgen_pb_check)
     if (W.n_pos) HIP_TRY(hipMemcpy(svr, h->surv_svr.p + 2 * W.pos0, (size_t)(2 * W.n_pos) * sizeof(double), hipMemcpyDeviceToHost));
     return MIPGEN_OK;
 }
@@ -655,15 +646,14 @@ int mipgen_accel_download_survivor_scores(mipgen_accel* h, int32_t window, doubl
 int mipgen_accel_window_views(mipgen_accel* h, int32_t window, mipgen_window_views* out)
 {
     if (!h || !out || window < 0 || window >= (int32_t)h->windows.size()) return fail(MIPGEN_E_INVALID, "bad arguments");
-    const uint8_t st = (size_t)window < h->win_state.size() ? h->win_state[(size_t)window] : 0;
-    if (!(st & 1)) return fail(MIPGEN_E_STATE, "window %d holds no current survivors (replay + condense first)", window);
+    if (!win_has(h, window, WIN_SURVIVORS)) return fail(MIPGEN_E_STATE, "window %d holds no current survivors (replay + condense first)", window);
     const Window& W = h->windows[(size_t)window];
     memset(out, 0, sizeof *out);
     out->emitted = h->emitted_per_region.p + W.r0; out->n_emitted = W.r1 - W.r0;
     out->survivors = h->survivors.p + 2 * W.pos0; out->n_survivors = 2 * W.n_pos;
-    if (st & 2) { out->collapsed = h->collapsed.p + W.base0; out->n_collapsed = W.n_base_entries; }
-    if (st & 4) out->survivor_svr = h->surv_svr.p + 2 * W.pos0;
-    if (window == h->cur_window && h->fmt_bytes > 0) { out->text = h->fmt_text.p; out->n_text_bytes = h->fmt_bytes; }
+    if (win_has(h, window, WIN_COLLAPSED)) { out->collapsed = h->collapsed.p + W.base0; out->n_collapsed = W.n_base_entries; }
+    if (win_has(h, window, WIN_SURV_SVR)) out->survivor_svr = h->surv_svr.p + 2 * W.pos0;
+    if (win_has(h, window, WIN_TEXT) && h->fmt_bytes > 0) { out->text = h->fmt_text.p; out->n_text_bytes = h->fmt_bytes; }
     out->first_candidate = W.cand0;
     return MIPGEN_OK;
 }

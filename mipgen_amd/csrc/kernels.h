@@ -1,0 +1,106 @@
+// kernels.h — the boundary between the kernel files (kernels_*.hip) and the host side of libmipgen_accel.so (accel*.hip): the structs that
+// cross it and every launcher / LDS-sizing function, declared once.  Each kernels_*.hip includes it, so a definition that drifts from its
+// declaration fails to compile instead of linking (the symbols are extern "C").  The SVR trainer keeps its own boundary in svr_train.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "common.h"
+
+struct HostConsts;                   // logistic_device.h: crosses the boundary by pointer only
+struct LrcMers { int8_t k[MIPGEN_N_LRC], code[MIPGEN_N_LRC], rc[MIPGEN_N_LRC]; };   // per mer: length, base-4 code, code of its reverse complement (-1: palindrome)
+struct FmtRegion {                    // per region of the window: what print_details reads from Featurev5
+    int32_t chr_off, chr_len;         // into the string pool
+    int32_t label_off, label_len;
+    int32_t feature_start, feature_stop;   // start_position - 1, stop_position (mipgen.cpp:788-789)
+    int64_t rb0;                      // first row block of the region in the window
+};
+struct FmtConst {
+    char middle[96];                  // universal_middle_mip_seq (mipgen.cpp:199-200)
+    int32_t middle_len;
+    int32_t n_regions;
+    int64_t first_index;              // all_mip_counter before this window
+};
+
+struct KmerParams {
+    int32_t n_k;                       // requested oligo lengths, ascending
+    int32_t k[MIPGEN_MAX_OLIGO];
+    int32_t kmax;
+    int32_t filter_bits;               // log2 of the Bloom bitmap size in bits (>= KMER_LDS_BITS, kmer_common.h)
+    uint64_t cap_mask;                 // partition capacity - 1 (power of two)
+};
+
+extern "C" {
+// kernels_logistic.hip
+size_t mipgen_logistic_lds_bytes(int span);
+hipError_t mipgen_launch_records_logistic(hipStream_t, int score, int n_tiles, int span_max, const DevParams*, const DevRegion*, const LogTile*, const uint8_t*, const int32_t*,
+                                          const uint8_t*, const HostConsts*, double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
+// kernels_logistic_dense.hip
+size_t mipgen_logistic_dense_lds_bytes(int np_all, int np, int ssr, int ssmax, int Lmax, int n_up, int n_dn);
+hipError_t mipgen_launch_logistic_dense(hipStream_t, int n_tiles, size_t lds_bytes, const DevParams*, const DevRegion*, const SvrTile*, const uint8_t*, const int32_t*,
+                                        const uint8_t*, const HostConsts*, double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
+// kernels_svr.hip
+size_t mipgen_svr_lds_bytes_tile(int np, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads);
+int mipgen_svr_scores_fit_lds(int np, int kc, int n_pairs, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads);
+hipError_t mipgen_launch_svr_dense(hipStream_t, int n_tiles, int n_tiles_few, size_t lds_bytes, const DevParams*, const SvrGeom*, const SvrGeom* geom_few, const DevRegion*,
+                                   const SvrTile*, const uint8_t*, const int32_t*, const double* log10_tab, const double* model, int n_sv, double gamma_l2e, double rho,
+                                   double s_guard, const uint64_t* records, double* scores, int64_t n_cand, int n_split, double* partials);
+// kernels_skip.hip
+hipError_t mipgen_launch_svr_run_state(hipStream_t s, int64_t n_pos, const DevParams* P, const DevRegion* regions, const int32_t* pos_region, const int32_t* pos_local,
+                                       const uint32_t* run_bounds, int max_levels, int level, double margin, const double* scores, const uint64_t* records, double* pbs,
+                                       uint8_t* state);
+hipError_t mipgen_launch_svr_tile_keep(hipStream_t s, int n_tiles, const SvrTile* tiles, const int64_t* region_pos0, int64_t win_pos0, const uint8_t* state, int64_t* keep);
+hipError_t mipgen_launch_svr_tile_compact(hipStream_t s, int n_tiles, const SvrTile* tiles, const int64_t* keep, const int64_t* offs, SvrTile* out, const DevParams* P,
+                                          const DevRegion* regions, double* scores, unsigned long long* skipped);
+// kernels_svr_gemm.hip
+hipError_t mipgen_launch_svr_gemm(hipStream_t, int n, const double* feats, const uint64_t* records, const double* model_t, const double* sv_norm, const double* sv_coef,
+                                  const double* center, int n_sv_pad, double gamma, double rho, double* scores);
+// kernels_misc.hip
+hipError_t mipgen_launch_dense_candidates(hipStream_t, const DevParams* P, const DevRegion* regions, int r0, int r1, int64_t c0, int n, mipgen_candidate* out);
+hipError_t mipgen_launch_dense_list_fix(hipStream_t, int n, const uint64_t* records, double rho, double s_guard, double* scores);
+hipError_t mipgen_launch_features_batch(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t* bases, const int32_t* copy,
+                                        const uint8_t* unmap, const HostConsts*, uint64_t* records, double* features);
+hipError_t mipgen_launch_candidates(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t*, const int32_t*, const uint8_t*,
+                                    const HostConsts*, const double* model, int n_sv, double gamma, double rho, int method, double*, uint64_t*, double*, mipgen_candidate_ints*,
+                                    int literal, const unsigned int* n_dev);
+hipError_t mipgen_launch_print_boundary_scan(hipStream_t, const DevParams*, const DevRegion*, const RescoreSrc*, double tol_rel, double tol_abs, mipgen_candidate* out,
+                                             int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu);
+hipError_t mipgen_launch_index_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const int64_t* idx, const unsigned int* count, unsigned int cap,
+                                          mipgen_candidate* out);
+hipError_t mipgen_launch_scatter_scores(hipStream_t, const double* src, const int64_t* idx, int64_t cap, const unsigned int* n_dev, double* dst, mipgen_survivor* dst_surv,
+                                        unsigned int* over);
+hipError_t mipgen_launch_surv_keep(hipStream_t, const mipgen_survivor* surv, int64_t n, int64_t* keep, double* svr);
+hipError_t mipgen_launch_surv_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const mipgen_survivor* surv, int64_t n, int64_t cand0,
+                                         const int64_t* offs, mipgen_candidate* out, int64_t* out_idx);
+hipError_t mipgen_launch_long_range(hipStream_t, int n, const char* seqs, const int64_t* offs, const int32_t* lens, const int32_t* denoms, const LrcMers*, double* out);
+// kernels_replay.hip
+hipError_t mipgen_launch_replay_condense(hipStream_t, int n_regions, int total_pos, const DevParams*, int n_pairs, int n_sizes_max, const DevRegion*, const int32_t* pos_region,
+                                         const int32_t* pos_local, const double* scores, const uint64_t* records, const int32_t* copy, int64_t cand_base, uint8_t* emitted,
+                                         mipgen_survivor* survivors, unsigned long long* emitted_per_region);
+hipError_t mipgen_launch_collapse(hipStream_t, int n_tiles, const CollapseTile* tiles, const DevParams*, const DevRegion*, const int64_t* region_pos0,
+                                  const int64_t* region_base0, const mipgen_survivor* survivors, const int32_t* copy, int64_t cand_base, int32_t* collapsed, int max_scan_all);
+hipError_t mipgen_launch_fill_pos_map(hipStream_t, const int64_t* region_pos0, int n_regions, int64_t total, int32_t* pos_region, int32_t* pos_local);
+// kernels_format.hip
+hipError_t mipgen_launch_fmt_count(hipStream_t, int64_t n_rb, int r0, const FmtConst*, const FmtRegion*, const DevParams*, const DevRegion*, const uint8_t* emitted,
+                                   int64_t* cnt);
+hipError_t mipgen_launch_fmt_records(hipStream_t, int write, int64_t n_rb, int r0, const FmtConst*, const FmtRegion*, const char* pool, const DevParams*, const DevRegion*,
+                                     const char* letters, const int32_t* copy, const double* scores, const uint64_t* records, const uint8_t* emitted, const int64_t* rank0,
+                                     const int64_t* off, int64_t* len_out, char* text);
+hipError_t mipgen_scan_i64(hipStream_t, void* temp, size_t* temp_bytes, const int64_t* in, int64_t* out, int64_t n);   // exclusive sum; temp == nullptr: size query
+// kernels_kmer.hip
+hipError_t mipgen_launch_kmer_insert(hipStream_t, const char* seq, int64_t len, const KmerParams*, uint64_t* keys, uint32_t* filter);
+hipError_t mipgen_launch_kmer_fold(hipStream_t, const uint32_t* filter, int filter_bits, uint32_t* folded);
+hipError_t mipgen_launch_kmer_count(hipStream_t, const char* genome, int64_t len, const KmerParams*, const uint64_t* keys, const uint32_t* filter, const uint32_t* folded,
+                                    unsigned int* counts, int n_cu);
+hipError_t mipgen_launch_kmer_lookup(hipStream_t, const char* seq, int64_t len, const KmerParams*, const uint64_t* keys, const unsigned int* counts, int32_t* out);
+hipError_t mipgen_launch_kmer_place(hipStream_t, const int32_t* src, int64_t len, const KmerParams*, const int64_t* roff, int n_regions, int32_t* dst, void* big,
+                                    unsigned int* n_big, unsigned int big_cap);
+// kernels_window.hip
+hipError_t mipgen_launch_window_spans(hipStream_t st, const char* q, const int64_t* roff, int n_regions, uint16_t* dist_bad, uint16_t* dist_end, uint16_t* dist_start);
+hipError_t mipgen_launch_seed_index(hipStream_t st, const char* q, int64_t total, int k, const uint64_t* keys, uint64_t cap_mask, unsigned int* rmult, unsigned int* rstart,
+                                    unsigned int* rfill, uint32_t* rlist, unsigned int* alloc, int phase);
+hipError_t mipgen_launch_window_verify(hipStream_t st, const char* G, int64_t glen, const char* q, int64_t total, const int32_t* sizes, int n_sizes, int k,
+                                       const uint64_t* keys, uint64_t cap_mask, const unsigned int* counts, const uint32_t* filter, int filter_bits, const unsigned int* rmult,
+                                       const unsigned int* rstart, const uint32_t* rlist, const uint16_t* dist_start, unsigned int* ctr);
+hipError_t mipgen_launch_window_flags(hipStream_t st, const char* q, int64_t total, const int32_t* sizes, int n_sizes, int k, const uint64_t* keys, uint64_t cap_mask,
+                                      const unsigned int* counts, const uint16_t* dist_bad, const uint16_t* dist_end, const unsigned int* ctr, uint8_t* unmap,
+                                      const int64_t* roff, int n_regions, const int32_t* bounds, uint8_t* any);
+}

@@ -13,23 +13,10 @@
 // Numbers are printed as the C library prints them: fmt_g6.h is printf("%g") to the last digit (checked against glibc on 1.5e7 values).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 #include "fmt_g6.h"
 #include "mip_record.h"
-
-struct FmtRegion {                    // per region of the window: what print_details reads from Featurev5
-    int32_t chr_off, chr_len;         // into the string pool
-    int32_t label_off, label_len;
-    int32_t feature_start, feature_stop;   // start_position - 1, stop_position (mipgen.cpp:788-789)
-    int64_t rb0;                      // first row block of the region in the window
-};
-struct FmtConst {
-    char middle[96];                  // universal_middle_mip_seq (mipgen.cpp:199-200)
-    int32_t middle_len;
-    int32_t n_regions;
-    int64_t first_index;              // all_mip_counter before this window
-};
 
 __device__ const Pow10DD d_pow10[] = POW10_DD_TABLE;
 

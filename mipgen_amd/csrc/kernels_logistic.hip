@@ -13,7 +13,7 @@
 // lanes own consecutive dense-grid indices, so the 8-byte score and 8-byte record stores of a wave are two
 // contiguous 512-byte segments (coalesced, the only compulsory HBM traffic of this kernel: 16 B/candidate).
 #include <hip/hip_runtime.h>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 
 #include "logistic_device.h"

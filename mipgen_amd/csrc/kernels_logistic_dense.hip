@@ -14,7 +14,7 @@
 // (position, capture size) row at a time with its lanes on the arm pairs: a candidate is ~20 LDS reads, a dozen FMAs, one exp2, one
 // division, and the two 8-byte stores of a row are contiguous.
 #include <hip/hip_runtime.h>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 #include "logistic_device.h"
 #include "logistic_groups.h"

@@ -9,7 +9,7 @@
 // It doubles as an on-device cross-check of the window-separable dense kernel (kernels_svr.hip).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 #include "mip_record.h"
 #include "logistic_device.h"
@@ -663,12 +663,6 @@ extern "C" hipError_t mipgen_launch_surv_candidates(hipStream_t stream, const De
 // ---------------------------------------------------------------------------------------------------------
 // Featurev5::get_long_range_content (/root/reference/Featurev5.cpp:18-56; mers mipgen.cpp:32)
 // ---------------------------------------------------------------------------------------------------------
-struct LrcMers {
-    int8_t k[MIPGEN_N_LRC];        // mer length
-    int8_t code[MIPGEN_N_LRC];     // base-4 code of the mer
-    int8_t rc[MIPGEN_N_LRC];       // base-4 code of its reverse complement, -1 if palindromic
-};
-
 // one workgroup per region: LDS histogram of the 1/2/3-mers of its extended sequence, then the 44 frequencies
 __global__ __launch_bounds__(256) void k_long_range(const char* __restrict__ seqs, const int64_t* __restrict__ offs, const int32_t* __restrict__ lens,
                                                     const int32_t* __restrict__ denoms, LrcMers M, double* __restrict__ out_all)

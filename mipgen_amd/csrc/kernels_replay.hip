@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <algorithm>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 #include "mip_record.h"
 

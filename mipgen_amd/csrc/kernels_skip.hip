@@ -15,7 +15,7 @@
 //   k_svr_tile_keep   per tile of the next run: 1 unless all of its positions have stopped
 //   k_svr_tile_compact  kept tiles -> a dense tile list in their old (longest first) order; skipped tiles fill their score rows with NaN
 #include <hip/hip_runtime.h>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 
 // run_bounds[region * max_levels + level] = first size index of the run | sizes of the run << 16 (0 = the region has no such run)

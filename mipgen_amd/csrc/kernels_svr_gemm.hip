@@ -15,7 +15,7 @@
 // Layout of v_mfma_f64_16x16x4f64 (probed on gfx950): A[i][k] in lane 16 k + i, B[k][j] in lane 16 k + j, D[i][j] in lane
 // 16 (i mod 4) + j, register i / 4.
 #include <hip/hip_runtime.h>
-#include "common.h"
+#include "kernels.h"
 #include "device_utils.h"
 #include "exp2_coef.h"
 

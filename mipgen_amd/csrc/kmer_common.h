@@ -4,18 +4,10 @@
 #include <stdint.h>
 #include <type_traits>
 #include <algorithm>
-#include "common.h"
+#include "kernels.h"                   // KmerParams, and the launchers the two files define
 
 #define KMER_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define KMER_MAX_K 31
-
-struct KmerParams {
-    int32_t n_k;                       // requested oligo lengths, ascending
-    int32_t k[MIPGEN_MAX_OLIGO];
-    int32_t kmax;
-    int32_t filter_bits;               // log2 of the Bloom bitmap size in bits (>= KMER_LDS_BITS)
-    uint64_t cap_mask;                 // partition capacity - 1 (power of two)
-};
 
 #define KMER_LDS_BITS 18               // the LDS fold of the filter: 2^18 bits = 32 KB
 #define KMER_THREADS 512                // threads of a genome-pass workgroup, 16 consecutive window starts each
