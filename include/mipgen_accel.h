@@ -465,6 +465,30 @@ typedef struct mipgen_svr_train_info {
 int mipgen_accel_train_svr(mipgen_accel* h, int32_t n, const double* x, const double* y, const mipgen_svr_train_params* p, const char* model_path,
                            mipgen_svr_train_info* info);
 
+/* ---- model selection (svm.cpp:2342 svm_cross_validation; svm-train -v n, and a grid of parameter sets around it) --------- */
+/* New entry points only: the ABI number does not change.  Every (parameter set, fold) is one problem of a batch that the device solves at once, one
+ * workgroup per problem, over ONE kernel matrix per distinct gamma (a fold's matrix is a gather of it); every fold model is the one svm_train gives
+ * svm_cross_validation, byte for byte when saved, and target is svm_predict's value within 1e-5. */
+typedef struct mipgen_svr_cv_point  { double gamma, cost, epsilon_p; } mipgen_svr_cv_point;
+typedef struct mipgen_svr_cv_result {
+    double mse, r2;                       /* svm-train's "Cross Validation Mean squared error" / "Squared correlation coefficient", over target and y */
+    int64_t iterations;                   /* #iter summed over the folds */
+    int32_t n_sv_total, reserved;         /* nSV summed over the folds */
+} mipgen_svr_cv_result;
+/* host only, no device needed: libsvm's fold assignment for a regression problem (svm.cpp:2408-2415) from glibc's rand() stream as srand(seed)
+ * leaves it (seed 1 = what svm-train, which never seeds, gets; the library keeps its own copy of the generator and never calls rand()).
+ * perm[n], fold_start[nr_fold + 1]: fold i holds out rows perm[fold_start[i] .. fold_start[i + 1]).  nr_fold > n is clipped to n as libsvm does;
+ * nr_fold_used (may be NULL) receives the count in use. */
+int mipgen_accel_svr_cv_folds(int32_t n, int32_t nr_fold, uint32_t seed, int32_t* perm, int32_t* fold_start, int32_t* nr_fold_used);
+/* n_points parameter sets x nr_fold folds in one call; x, y, eps as mipgen_accel_train_svr takes them (same checks, same messages), nr_fold >= 2,
+ * n_points >= 1, n >= 2.  target: [n_points][n] held-out predictions in original row order (may be NULL); results: [n_points];
+ * fold_model_prefix (may be NULL): writes "<prefix>.<point>.<fold>.model" as svm_save_model would.  The handle's model is untouched.
+ * Points are processed gamma by gamma, one n x n float matrix resident at a time (n <= MIPGEN_SVR_TRAIN_MAX_ROWS); MIPGEN_E_NOMEM before any
+ * allocation when the matrix plus the solver state of the largest gamma group's points x folds problems does not fit the device's free memory. */
+int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x, const double* y, int32_t nr_fold, uint32_t seed, double eps,
+                                    int32_t n_points, const mipgen_svr_cv_point* points, double* target, mipgen_svr_cv_result* results,
+                                    const char* fold_model_prefix);
+
 /* ---- instrumentation ------------------------------------------------------------------------------ */
 /* HIP-event time (ms) of the kernels of the last scoring call (summed over its windows), measured on the handle's stream;
  * negative if unavailable.  which: 0 = dense SVR kernel, 1 = records + scoring kernels, 2 = records / logistic kernel,

@@ -132,6 +132,14 @@ class SvrTrainInfo(C.Structure):       # mipgen_svr_train_info
                 ("n_shrink", C.c_int32), ("n_reconstruct", C.c_int32), ("gram_ms", C.c_double), ("solve_ms", C.c_double)]
 
 
+class SvrCvPoint(C.Structure):         # mipgen_svr_cv_point
+    _fields_ = [("gamma", C.c_double), ("cost", C.c_double), ("epsilon_p", C.c_double)]
+
+
+class SvrCvResult(C.Structure):        # mipgen_svr_cv_result
+    _fields_ = [("mse", C.c_double), ("r2", C.c_double), ("iterations", C.c_int64), ("n_sv_total", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BigCopy(C.Structure):
     _fields_ = [("region", C.c_int32), ("length", C.c_int32), ("start", C.c_int32), ("copies", C.c_int32)]
 
@@ -294,6 +302,9 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_model_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.mipgen_accel_train_svr.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(SvrTrainParams), C.c_char_p,
                                            C.POINTER(SvrTrainInfo)]
+    lib.mipgen_accel_svr_cv_folds.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mipgen_accel_cross_validate_svr.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_uint32, C.c_double,
+                                                    C.c_int32, C.POINTER(SvrCvPoint), C.POINTER(C.c_double), C.POINTER(SvrCvResult), C.c_char_p]
     lib.mipgen_accel_upload_regions.argtypes = [vp, C.POINTER(Region), C.c_int32, C.POINTER(Grid)]
     lib.mipgen_accel_batch_candidates.argtypes = [vp]
     lib.mipgen_accel_batch_candidates.restype = C.c_int64
@@ -355,7 +366,8 @@ def load_library(path: Optional[str] = None):
                  "long_range_content", "replay_condense", "download_replay", "set_timing", "set_window_candidates",
                  "window_info", "score_window", "score_condense_all", "score_condense_window", "download_survivors", "survivors_device_ptr",
                  "set_sv_split", "set_print_exact", "set_logistic_subruns", "long_range_content_batch", "collapse", "region_bases", "download_collapsed", "count_oligo_copies", "count_oligo_copies_resident", "window_uniqueness", "window_uniqueness_begin", "window_flags_region", "window_uniqueness_end",
-                 "format_all_mips", "download_text", "set_dynamic_skip", "skipped_candidates", "skip_state", "train_svr"):
+                 "format_all_mips", "download_text", "set_dynamic_skip", "skipped_candidates", "skip_state", "train_svr",
+                 "svr_cv_folds", "cross_validate_svr"):
         getattr(lib, "mipgen_accel_" + name).restype = C.c_int
     if path is None:
         _lib = lib
@@ -376,8 +388,23 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_count_oligo_copies_resident", "mipgen_accel_window_uniqueness", "mipgen_accel_window_uniqueness_begin", "mipgen_accel_window_flags_region",
     "mipgen_accel_window_uniqueness_end", "mipgen_accel_set_dynamic_skip", "mipgen_accel_skipped_candidates", "mipgen_accel_skip_state", "mipgen_accel_set_print_exact", "mipgen_accel_set_logistic_subruns",
     "mipgen_accel_rescore_survivors", "mipgen_accel_download_survivor_scores", "mipgen_accel_window_views", "mipgen_accel_synchronize",
-    "mipgen_accel_train_svr",
+    "mipgen_accel_train_svr", "mipgen_accel_svr_cv_folds", "mipgen_accel_cross_validate_svr",
 ]
+
+
+def svr_cv_folds(n: int, nr_fold: int, seed: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """libsvm's cross-validation fold assignment of n regression rows (host only): (perm, fold_start); fold i holds out rows
+    perm[fold_start[i]:fold_start[i + 1]].  nr_fold > n is clipped to n (len(fold_start) - 1 folds are in use); seed 1 is svm-train's stream."""
+    lib = load_library()
+    perm = np.empty(max(n, 1), dtype=np.int32)
+    start = np.empty(max(nr_fold, 0) + 1, dtype=np.int32)
+    used = C.c_int32()
+    i32p = C.POINTER(C.c_int32)
+    rc = lib.mipgen_accel_svr_cv_folds(n, nr_fold, seed, perm.ctypes.data_as(i32p), start.ctypes.data_as(i32p), C.byref(used))
+    if rc != 0:
+        msg = lib.mipgen_accel_last_error()
+        raise AccelError(f"mipgen_accel error {rc}: {msg.decode() if msg else ''}")
+    return perm[:n], start[:used.value + 1]
 
 
 class Accel:
@@ -437,6 +464,24 @@ class Accel:
         self._check(self.lib.mipgen_accel_train_svr(self.h, x.shape[0], x.ctypes.data_as(C.POINTER(C.c_double)),
                                                     y.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), model_path.encode(), C.byref(info)))
         return {name: getattr(info, name) for name, _ in SvrTrainInfo._fields_}
+
+    def cross_validate_svr(self, x: np.ndarray, y: np.ndarray, points, nr_fold: int = 5, seed: int = 1, eps: float = 1e-3,
+                           fold_model_prefix: Optional[str] = None) -> Tuple[np.ndarray, List[dict]]:
+        """libsvm's svm_cross_validation for every (gamma, cost, epsilon_p) of `points` in one call, all points x folds solved as one batch on
+        the device.  Returns (target [n_points][n]: the held-out predictions in row order, one mipgen_svr_cv_result dict per point).  With
+        fold_model_prefix every fold model is written to "<prefix>.<point>.<fold>.model".  The handle's model is not touched."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != N_FEATURES or y.shape != (x.shape[0],):
+            raise ValueError(f"x must be [n][{N_FEATURES}] and y [n]; got {x.shape} and {y.shape}")
+        pts = (SvrCvPoint * max(len(points), 1))(*[SvrCvPoint(float(g), float(c), float(p)) for g, c, p in points])
+        res = (SvrCvResult * max(len(points), 1))()
+        target = np.empty((len(points), x.shape[0]), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.mipgen_accel_cross_validate_svr(self.h, x.shape[0], x.ctypes.data_as(dp), y.ctypes.data_as(dp), nr_fold, seed, eps,
+                                                             len(points), pts, target.ctypes.data_as(dp), res,
+                                                             fold_model_prefix.encode() if fold_model_prefix is not None else None))
+        return target, [{name: getattr(r, name) for name, _ in SvrCvResult._fields_} for r in res[:len(points)]]
 
     # regions
     def upload(self, regions: Sequence[RegionData]) -> List[Grid]:

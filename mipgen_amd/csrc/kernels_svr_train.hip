@@ -13,6 +13,12 @@
 //            (svm.cpp:697-700) and the G_bar update (svm.cpp:702-730) elementwise.  A launch stops at the next shrinking point, on optimality or at
 //            max_iter; the host reads SvtCtl and runs do_shrinking (k_svt_shrink_stats + k_svt_shrink) or reconstruct_gradient
 //            (k_svt_free_list + k_svt_reconstruct) between launches.
+//   Batch    every solver kernel works on a list of problems (SvtProb, svr_train.h), one workgroup - or one row of workgroups - per problem: a problem
+//            is n rows of the shared matrix picked by its row map, so sub-problem row k reads K row rows[k] at the columns rows[..] and QD[rows[k]].
+//            The kernel value of two rows depends on the two rows only, not on their positions (the sum xsq[a] + xsq[b] and the products of dot
+//            commute, dot walks ascending feature indices whichever row comes first), so the gathered sub-matrix IS the matrix libsvm builds for the
+//            sub-problem, and one Gram build per gamma serves every fold, every C and every p.  Training on all rows is the identity map.
+//   Predict  k_svt_predict: svm_predict (svm.cpp:2547-2562) of a fold's model on its held-out rows, k_function's double RBF (svm.cpp:329-368).
 // Every function here computes under `fp contract(off)`: a product fused into the sum that consumes it is not libsvm's arithmetic.
 #include "svr_train.h"
 #include "pow_base_cr.h"
@@ -97,11 +103,12 @@ __device__ __forceinline__ int svt_y(int v, int n) { return v < n ? 1 : -1; }
 __device__ __forceinline__ int svt_row(int v, int n) { return v < n ? v : v - n; }
 
 // Solve's set-up (svm.cpp:522-559) for alpha = 0: every variable at its lower bound, G = p, G_bar = 0, active_set = identity
-__global__ void k_svt_init(int L, const double* __restrict__ lin, int32_t* perm, double* G, double* Gbar, double* alpha, int8_t* st)
+__global__ void k_svt_init(const SvtProb* __restrict__ probs, const int32_t* __restrict__ list)
 {
+    const SvtProb& P = probs[list[blockIdx.y]];
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= L) return;
-    perm[k] = k; G[k] = lin[k]; Gbar[k] = 0.0; alpha[k] = 0.0; st[k] = SVT_LOWER;
+    if (k >= 2 * P.n) return;
+    P.perm[k] = k; P.G[k] = P.lin[k]; P.Gbar[k] = 0.0; P.alpha[k] = 0.0; P.st[k] = SVT_LOWER;
 }
 
 // (value, position) pairs: the larger value wins, equal values go to the larger position - the sequential `>=` scan's result (`<=` for minima:
@@ -145,10 +152,21 @@ __device__ __forceinline__ void svt_up_candidate(int k, int yk, double Gk, int s
 
 // The iteration loop (svm.cpp:567-732) from one select_working_set to the next exit point.  LDS: the two K rows are staged when they fit.
 template <bool LDS>
-__global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float* __restrict__ K, const double* __restrict__ qd, const double* __restrict__ lin,
-                                                            int32_t* __restrict__ perm, double* __restrict__ G, double* __restrict__ Gbar,
-                                                            double* __restrict__ alpha, int8_t* __restrict__ st, SvtCtl* ctl, double C, double eps)
+__global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(const SvtProb* __restrict__ probs, const int32_t* __restrict__ list)
 {
+    const SvtProb& P = probs[list[blockIdx.x]];
+    const int n = P.n;
+    const size_t ldk = (size_t)P.ldk;
+    const int32_t* __restrict__ rmap = P.rows;
+    const float* __restrict__ K = P.K;
+    const double* __restrict__ qd = P.qd;
+    int32_t* __restrict__ perm = P.perm;
+    double* __restrict__ G = P.G;
+    double* __restrict__ Gbar = P.Gbar;
+    double* __restrict__ alpha = P.alpha;
+    int8_t* __restrict__ st = P.st;
+    SvtCtl* ctl = P.ctl;
+    const double C = P.C, eps = P.eps;
     __shared__ float rows[2][LDS ? SVT_LDS_ROW : 1];
     __shared__ SvtRed red;
     __shared__ double s_da[2];
@@ -172,16 +190,16 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
         const float* Ki = K;
         if (i >= 0) {
             vi = perm[i]; yi = svt_y(vi, n); ri = svt_row(vi, n);
-            Ki = K + (size_t)ri * n;
+            Ki = K + (size_t)rmap[ri] * ldk;
             if (LDS) {
-                for (int c = t; c < n; c += SVT_THREADS) rows[0][c] = Ki[c];
+                for (int c = t; c < n; c += SVT_THREADS) rows[0][c] = Ki[rmap[c]];
                 __syncthreads();
             }
         }
         // second loop (svm.cpp:828-878): Gmax2 and the argmin of obj_diff
         double omin = HUGE_VAL, gmax2 = -HUGE_VAL;
         int jidx = -1;
-        const double QDi = i >= 0 ? qd[ri] : 0.0;
+        const double QDi = i >= 0 ? qd[rmap[ri]] : 0.0;
         for (int j = t; j < A; j += SVT_THREADS) {
             const int vj = perm[j], yj = svt_y(vj, n), sj = st[j];
             const double Gj = G[j];
@@ -191,8 +209,8 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
                     if (Gj >= gmax2) gmax2 = Gj;
                     if (grad_diff > 0) {
                         const int rj = svt_row(vj, n);
-                        const float q = (float)yi * (float)yj * (LDS ? rows[0][rj] : Ki[rj]);
-                        const double quad_coef = qd[ri] + qd[rj] - 2.0 * yi * q;
+                        const float q = (float)yi * (float)yj * (LDS ? rows[0][rj] : Ki[rmap[rj]]);
+                        const double quad_coef = QDi + qd[rmap[rj]] - 2.0 * yi * q;
                         const double obj_diff = quad_coef > 0 ? -(grad_diff * grad_diff) / quad_coef : -(grad_diff * grad_diff) / SVT_TAU;
                         if (better_min(omin, jidx, obj_diff, j)) { omin = obj_diff; jidx = j; }
                     }
@@ -202,8 +220,8 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
                 if (-Gj >= gmax2) gmax2 = -Gj;
                 if (grad_diff > 0) {
                     const int rj = svt_row(vj, n);
-                    const float q = (float)yi * (float)yj * (LDS ? rows[0][rj] : Ki[rj]);
-                    const double quad_coef = qd[ri] + qd[rj] + 2.0 * yi * q;
+                    const float q = (float)yi * (float)yj * (LDS ? rows[0][rj] : Ki[rmap[rj]]);
+                    const double quad_coef = QDi + qd[rmap[rj]] + 2.0 * yi * q;
                     const double obj_diff = quad_coef > 0 ? -(grad_diff * grad_diff) / quad_coef : -(grad_diff * grad_diff) / SVT_TAU;
                     if (better_min(omin, jidx, obj_diff, j)) { omin = obj_diff; jidx = j; }
                 }
@@ -217,8 +235,8 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
 
         // the two-variable update (svm.cpp:596-690) and the bound bookkeeping (svm.cpp:704-708), one lane
         if (t == 0) {
-            const float Qij = (float)yi * (float)yj * Ki[rj];
-            const double QDj = qd[rj], C_i = C, C_j = C;
+            const float Qij = (float)yi * (float)yj * Ki[rmap[rj]];
+            const double QDj = qd[rmap[rj]], C_i = C, C_j = C;
             const double old_alpha_i = alpha[i], old_alpha_j = alpha[j];
             double ai = old_alpha_i, aj = old_alpha_j;
             const double Gi = G[i], Gj = G[j];
@@ -254,8 +272,8 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
             s_gb[0] = ui != (si == SVT_UPPER) ? (ui ? -1 : 1) : 0;
             s_gb[1] = uj != (sj == SVT_UPPER) ? (uj ? -1 : 1) : 0;
         }
-        const float* Kj = K + (size_t)rj * n;
-        if (LDS) for (int c = t; c < n; c += SVT_THREADS) rows[1][c] = Kj[c];
+        const float* Kj = K + (size_t)rmap[rj] * ldk;
+        if (LDS) for (int c = t; c < n; c += SVT_THREADS) rows[1][c] = Kj[rmap[c]];
         __syncthreads();
         const double dai = s_da[0], daj = s_da[1];
         const int gbi = s_gb[0], gbj = s_gb[1];
@@ -267,8 +285,8 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
         const int top = (gbi | gbj) ? L : A;
         for (int k = t; k < top; k += SVT_THREADS) {
             const int vk = perm[k], yk = svt_y(vk, n), rk = svt_row(vk, n);
-            const float qi = (float)yi * (float)yk * (LDS ? rows[0][rk] : Ki[rk]);
-            const float qj = (float)yj * (float)yk * (LDS ? rows[1][rk] : Kj[rk]);
+            const float qi = (float)yi * (float)yk * (LDS ? rows[0][rk] : Ki[rmap[rk]]);
+            const float qj = (float)yj * (float)yk * (LDS ? rows[1][rk] : Kj[rmap[rk]]);
             if (k < A) {
                 const double g = G[k] + (qi * dai + qj * daj);
                 G[k] = g;
@@ -291,9 +309,14 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_iterate(int n, const float*
 }
 
 // ---- do_shrinking (svm.cpp:908-967) ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SVT_THREADS) void k_svt_shrink_stats(int n, const int32_t* __restrict__ perm, const double* __restrict__ G,
-                                                                  const int8_t* __restrict__ st, SvtCtl* ctl)
+__global__ __launch_bounds__(SVT_THREADS) void k_svt_shrink_stats(const SvtProb* __restrict__ probs, const int32_t* __restrict__ list)
 {
+    const SvtProb& P = probs[list[blockIdx.x]];
+    const int n = P.n;
+    const int32_t* __restrict__ perm = P.perm;
+    const double* __restrict__ G = P.G;
+    const int8_t* __restrict__ st = P.st;
+    SvtCtl* ctl = P.ctl;
     __shared__ SvtRed red;
     const int A = ctl->active;
     double g1 = -HUGE_VAL, g2 = -HUGE_VAL;
@@ -341,9 +364,15 @@ __device__ __forceinline__ int svt_scan(int v, int* buf, int* total)
 // libsvm's two-pointer compaction swaps the k-th shrunk position from the bottom with the k-th kept position from the top while the first lies
 // below the second: below the new active size (the number kept) the shrunk ones, ascending, meet the kept ones above it, descending.  Both
 // pointers only ever test positions nothing has moved yet, so every be_shrunk here sees the state do_shrinking starts from.
-__global__ __launch_bounds__(SVT_THREADS) void k_svt_shrink(int n, int32_t* perm, double* G, double* Gbar, double* alpha, int8_t* st, SvtCtl* ctl,
-                                                            int8_t* flag, int32_t* lo, int32_t* hi)
+__global__ __launch_bounds__(SVT_THREADS) void k_svt_shrink(const SvtProb* __restrict__ probs, const int32_t* __restrict__ list)
 {
+    const SvtProb& P = probs[list[blockIdx.x]];
+    const int n = P.n;
+    int32_t* perm = P.perm;
+    double *G = P.G, *Gbar = P.Gbar, *alpha = P.alpha;
+    int8_t *st = P.st, *flag = P.flag;
+    int32_t *lo = P.lo, *hi = P.hi;
+    SvtCtl* ctl = P.ctl;
     __shared__ int buf[SVT_THREADS];
     __shared__ int s_m;
     const int t = threadIdx.x, A = ctl->active;
@@ -384,9 +413,15 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_shrink(int n, int32_t* perm
 // ---- reconstruct_gradient (svm.cpp:465-505) ----------------------------------------------------------------------------------------------------
 // The free positions of the active set in ascending order: both of libsvm's loop orders add alpha[j] * Q[i][j] to an inactive G[i] over them in
 // this order.
-__global__ __launch_bounds__(SVT_THREADS) void k_svt_free_list(int n, const int32_t* __restrict__ perm, const double* __restrict__ alpha,
-                                                               const int8_t* __restrict__ st, SvtCtl* ctl, int32_t* fperm, double* falpha)
+__global__ __launch_bounds__(SVT_THREADS) void k_svt_free_list(const SvtProb* __restrict__ probs, const int32_t* __restrict__ list)
 {
+    const SvtProb& P = probs[list[blockIdx.x]];
+    const int32_t* __restrict__ perm = P.perm;
+    const double* __restrict__ alpha = P.alpha;
+    const int8_t* __restrict__ st = P.st;
+    SvtCtl* ctl = P.ctl;
+    int32_t* fperm = P.fperm;
+    double* falpha = P.falpha;
     __shared__ int buf[SVT_THREADS];
     const int t = threadIdx.x, A = ctl->active;
     const int chunk = (A + SVT_THREADS - 1) / SVT_THREADS, c0 = min(A, t * chunk), c1 = min(A, c0 + chunk);
@@ -400,20 +435,72 @@ __global__ __launch_bounds__(SVT_THREADS) void k_svt_free_list(int n, const int3
 }
 
 // one thread per inactive position: G = G_bar + p, then + alpha[j] * Q[i][j] over the free list (K symmetric: row of j, column of i)
-__global__ __launch_bounds__(256) void k_svt_reconstruct(int n, int active, int n_free, const float* __restrict__ K, const double* __restrict__ lin,
-                                                         const int32_t* __restrict__ perm, const double* __restrict__ Gbar, const int32_t* __restrict__ fperm,
-                                                         const double* __restrict__ falpha, double* __restrict__ G)
+__global__ __launch_bounds__(256) void k_svt_reconstruct(const SvtProb* __restrict__ probs, const int32_t* __restrict__ list)
 {
+    const SvtProb& P = probs[list[blockIdx.y]];
+    const int n = P.n, active = P.ctl->active, n_free = P.ctl->n_free;
+    const size_t ldk = (size_t)P.ldk;
+    const int32_t* __restrict__ rmap = P.rows;
+    const float* __restrict__ K = P.K;
+    const double* __restrict__ lin = P.lin;
+    const int32_t* __restrict__ perm = P.perm;
+    const double* __restrict__ Gbar = P.Gbar;
+    const int32_t* __restrict__ fperm = P.fperm;
+    const double* __restrict__ falpha = P.falpha;
+    double* __restrict__ G = P.G;
     const int k = active + blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= 2 * n) return;
-    const int vk = perm[k], yk = svt_y(vk, n), rk = svt_row(vk, n);
+    const int vk = perm[k], yk = svt_y(vk, n), ck = rmap[svt_row(vk, n)];
     double g = Gbar[k] + lin[vk];
     for (int f = 0; f < n_free; f++) {
         const int vf = fperm[f];
-        const float q = (float)yk * (float)svt_y(vf, n) * K[(size_t)svt_row(vf, n) * n + rk];
+        const float q = (float)yk * (float)svt_y(vf, n) * K[(size_t)rmap[svt_row(vf, n)] * ldk + ck];
         g += falpha[f] * q;
     }
     G[k] = g;
+}
+
+// ---- svm_predict on held-out rows (cross-validation, svm.cpp:2453) ------------------------------------------------------------------------------
+// sum over the model's support vectors, in its order, of coef * exp(-gamma * |x - sv|^2), minus rho - all in double (k_function keeps no float).
+// |x - sv|^2 over the 192 dense features in ascending order is k_function's walk over the union of the two rows' indices: a feature absent from both
+// adds +0.  One workgroup per 16 held-out rows of one problem; the support vectors pass through LDS 16 at a time, thread (ra, rb) computes one term,
+// and 16 threads add each row's terms in the model's order.  exp is svt_exp_cr: glibc's differs from it by at most an ulp.
+__global__ __launch_bounds__(256) void k_svt_predict(const double* __restrict__ x, const SvtPred* __restrict__ preds)
+{
+    const SvtPred& Q = preds[blockIdx.y];
+    const int h0 = blockIdx.x * SVT_TILE, t = threadIdx.x;
+    if (h0 >= Q.n_held) return;
+    __shared__ double sa[SVT_TILE][SVT_NF + 1], sb[SVT_TILE][SVT_NF + 1];
+    __shared__ double term[SVT_TILE][SVT_TILE + 1];
+    const int n_sv = Q.n_sv, n_held = Q.n_held;
+    const double gamma = Q.gamma;
+    for (int e = t; e < SVT_TILE * SVT_NF; e += 256) {
+        const int r = e / SVT_NF, f = e % SVT_NF;
+        sa[r][f] = h0 + r < n_held ? x[(size_t)Q.held[h0 + r] * SVT_NF + f] : 0.0;
+    }
+    const int ra = t / SVT_TILE, rb = t % SVT_TILE;
+    double acc = 0;
+    for (int s0 = 0; s0 < n_sv; s0 += SVT_TILE) {
+        __syncthreads();                                        // sa is staged; the previous tile's readers are done with sb and term
+        for (int e = t; e < SVT_TILE * SVT_NF; e += 256) {
+            const int r = e / SVT_NF, f = e % SVT_NF;
+            sb[r][f] = s0 + r < n_sv ? x[(size_t)Q.sv_rows[s0 + r] * SVT_NF + f] : 0.0;
+        }
+        __syncthreads();
+        double v = 0;
+        if (s0 + rb < n_sv) {
+            double sum = 0;
+            for (int f = 0; f < SVT_NF; f++) { const double d = sa[ra][f] - sb[rb][f]; sum += d * d; }
+            v = Q.coef[s0 + rb] * svt_exp_cr(-gamma * sum);
+        }
+        term[ra][rb] = v;
+        __syncthreads();
+        if (rb == 0) {
+            const int m = min(SVT_TILE, n_sv - s0);
+            for (int k = 0; k < m; k++) acc += term[ra][k];
+        }
+    }
+    if (rb == 0 && h0 + ra < n_held) Q.out[Q.held[h0 + ra]] = acc - Q.rho;
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------------
@@ -425,45 +512,49 @@ extern "C" hipError_t mipgen_svt_launch_gram(hipStream_t s, int n, double gamma,
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_svt_launch_init(hipStream_t s, int n, const double* lin, int32_t* perm, double* G, double* Gbar, double* alpha, int8_t* st)
+extern "C" hipError_t mipgen_svt_launch_init(hipStream_t s, const SvtProb* probs, const int32_t* list, int count, int max_n)
 {
-    hipLaunchKernelGGL(k_svt_init, dim3((2 * n + 255) / 256), dim3(256), 0, s, 2 * n, lin, perm, G, Gbar, alpha, st);
+    hipLaunchKernelGGL(k_svt_init, dim3((2 * max_n + 255) / 256, count), dim3(256), 0, s, probs, list);
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_svt_launch_iterate(hipStream_t s, int n, const float* K, const double* qd, const double* lin, int32_t* perm, double* G,
-                                                double* Gbar, double* alpha, int8_t* st, SvtCtl* ctl, double C, double eps)
+// the two K rows go through LDS when every problem of the list has rows that fit (the staging changes no value)
+extern "C" hipError_t mipgen_svt_launch_iterate(hipStream_t s, const SvtProb* probs, const int32_t* list, int count, int max_n)
 {
-    if (n <= SVT_LDS_ROW) hipLaunchKernelGGL(k_svt_iterate<true>, dim3(1), dim3(SVT_THREADS), 0, s, n, K, qd, lin, perm, G, Gbar, alpha, st, ctl, C, eps);
-    else hipLaunchKernelGGL(k_svt_iterate<false>, dim3(1), dim3(SVT_THREADS), 0, s, n, K, qd, lin, perm, G, Gbar, alpha, st, ctl, C, eps);
+    if (max_n <= SVT_LDS_ROW) hipLaunchKernelGGL(k_svt_iterate<true>, dim3(count), dim3(SVT_THREADS), 0, s, probs, list);
+    else hipLaunchKernelGGL(k_svt_iterate<false>, dim3(count), dim3(SVT_THREADS), 0, s, probs, list);
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_svt_launch_shrink_stats(hipStream_t s, int n, const int32_t* perm, const double* G, const int8_t* st, SvtCtl* ctl)
+extern "C" hipError_t mipgen_svt_launch_shrink_stats(hipStream_t s, const SvtProb* probs, const int32_t* list, int count)
 {
-    hipLaunchKernelGGL(k_svt_shrink_stats, dim3(1), dim3(SVT_THREADS), 0, s, n, perm, G, st, ctl);
+    hipLaunchKernelGGL(k_svt_shrink_stats, dim3(count), dim3(SVT_THREADS), 0, s, probs, list);
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_svt_launch_shrink(hipStream_t s, int n, int32_t* perm, double* G, double* Gbar, double* alpha, int8_t* st, SvtCtl* ctl,
-                                               int8_t* flag, int32_t* lo, int32_t* hi)
+extern "C" hipError_t mipgen_svt_launch_shrink(hipStream_t s, const SvtProb* probs, const int32_t* list, int count)
 {
-    hipLaunchKernelGGL(k_svt_shrink, dim3(1), dim3(SVT_THREADS), 0, s, n, perm, G, Gbar, alpha, st, ctl, flag, lo, hi);
+    hipLaunchKernelGGL(k_svt_shrink, dim3(count), dim3(SVT_THREADS), 0, s, probs, list);
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_svt_launch_free_list(hipStream_t s, int n, const int32_t* perm, const double* alpha, const int8_t* st, SvtCtl* ctl,
-                                                  int32_t* fperm, double* falpha)
+extern "C" hipError_t mipgen_svt_launch_free_list(hipStream_t s, const SvtProb* probs, const int32_t* list, int count)
 {
-    hipLaunchKernelGGL(k_svt_free_list, dim3(1), dim3(SVT_THREADS), 0, s, n, perm, alpha, st, ctl, fperm, falpha);
+    hipLaunchKernelGGL(k_svt_free_list, dim3(count), dim3(SVT_THREADS), 0, s, probs, list);
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_svt_launch_reconstruct(hipStream_t s, int n, int active, int n_free, const float* K, const double* lin, const int32_t* perm,
-                                                    const double* Gbar, const int32_t* fperm, const double* falpha, double* G)
+// max_inactive: the largest 2n - active_size of the list's problems (each reads its own from its control block)
+extern "C" hipError_t mipgen_svt_launch_reconstruct(hipStream_t s, const SvtProb* probs, const int32_t* list, int count, int max_inactive)
 {
-    const int m = 2 * n - active;
-    if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_svt_reconstruct, dim3((m + 255) / 256), dim3(256), 0, s, n, active, n_free, K, lin, perm, Gbar, fperm, falpha, G);
+    if (max_inactive <= 0 || count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_svt_reconstruct, dim3((max_inactive + 255) / 256, count), dim3(256), 0, s, probs, list);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t mipgen_svt_launch_predict(hipStream_t s, const double* x, const SvtPred* preds, int count, int max_held)
+{
+    if (max_held <= 0 || count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_svt_predict, dim3((max_held + SVT_TILE - 1) / SVT_TILE, count), dim3(256), 0, s, x, preds);
     return hipGetLastError();
 }

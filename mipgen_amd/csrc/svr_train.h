@@ -1,5 +1,5 @@
 // svr_train.h — what kernels_svr_train.hip (device side of libsvm's epsilon-SVR trainer) and accel_train.hip (its host driver) share:
-// the control block the solver keeps in device memory and the kernel launchers.
+// the control block the solver keeps in device memory, the descriptor of one solve of a batch and the kernel launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,7 +13,7 @@
 #define SVT_EXIT_DONE 3              // ... and optimal again over all 2l variables (svm.cpp:586-587)
 #define SVT_EXIT_MAXITER 4           // iter reached max_iter (svm.cpp:567, 734)
 
-#define SVT_THREADS 1024             // the one workgroup of the iteration loop
+#define SVT_THREADS 1024             // the one workgroup of a problem's iteration loop
 #define SVT_LDS_ROW 7168             // K rows of up to this many floats are staged through LDS (two of them: 56 KiB)
 
 // Solver state besides the per-position arrays; thread 0 of the one-workgroup kernels writes it, the host reads it between launches.
@@ -28,16 +28,44 @@ struct SvtCtl {
     double gmax1, gmax2;             // do_shrinking's maximal violating pair values
 };
 
+// One solve of a batch: a sub-problem of n rows of the shared ldk x ldk matrix K (sub-problem row k is original row rows[k]; a training run on all
+// rows is the batch of one with the identity map), its C and eps and its own slices of the solver's arrays.  A cross-validation's folds and a grid's
+// points are such sub-problems over the ONE matrix of their gamma.
+struct SvtProb {
+    int32_t n, ldk;
+    const int32_t* rows;             // [n]
+    const float* K;                  // [ldk][ldk], original row order
+    const double* qd;                // [ldk]
+    const double* lin;               // [2n] linear term
+    int32_t* perm;                   // [2n] active_set
+    double *G, *Gbar, *alpha;        // [2n]
+    int8_t* st;                      // [2n] alpha_status
+    SvtCtl* ctl;
+    int8_t* flag;                    // [2n] do_shrinking: be_shrunk
+    int32_t *lo, *hi;                // [2n] do_shrinking: the positions its swaps pair
+    int32_t* fperm;                  // [2n] reconstruct_gradient: the free positions' variables ...
+    double* falpha;                  // [2n] ... and their alpha
+    double C, eps;
+};
+
+// One (problem, held-out rows) prediction of a cross-validation: svm_predict of the fold's model on the rows it was not trained on.
+struct SvtPred {
+    int32_t n_sv, n_held;
+    const int32_t* sv_rows;          // [n_sv] original rows of the support vectors, in the model's order (ascending sub-problem row)
+    const double* coef;              // [n_sv]
+    const int32_t* held;             // [n_held] original rows to predict
+    double* out;                     // [ldk] the point's target, indexed by original row
+    double gamma, rho;
+};
+
+// Every launcher takes the device array of descriptors and a device list of `count` indices into it: workgroup b works on probs[list[b]].
 extern "C" {
 hipError_t mipgen_svt_launch_gram(hipStream_t, int n, double gamma, const double* x, double* xsq, double* qd, float* K);
-hipError_t mipgen_svt_launch_init(hipStream_t, int n, const double* lin, int32_t* perm, double* G, double* Gbar, double* alpha, int8_t* st);
-hipError_t mipgen_svt_launch_iterate(hipStream_t, int n, const float* K, const double* qd, const double* lin, int32_t* perm, double* G, double* Gbar,
-                                     double* alpha, int8_t* st, SvtCtl* ctl, double C, double eps);
-hipError_t mipgen_svt_launch_shrink_stats(hipStream_t, int n, const int32_t* perm, const double* G, const int8_t* st, SvtCtl* ctl);
-hipError_t mipgen_svt_launch_shrink(hipStream_t, int n, int32_t* perm, double* G, double* Gbar, double* alpha, int8_t* st, SvtCtl* ctl,
-                                    int8_t* flag, int32_t* lo, int32_t* hi);
-hipError_t mipgen_svt_launch_free_list(hipStream_t, int n, const int32_t* perm, const double* alpha, const int8_t* st, SvtCtl* ctl,
-                                       int32_t* fperm, double* falpha);
-hipError_t mipgen_svt_launch_reconstruct(hipStream_t, int n, int active, int n_free, const float* K, const double* lin, const int32_t* perm,
-                                         const double* Gbar, const int32_t* fperm, const double* falpha, double* G);
+hipError_t mipgen_svt_launch_init(hipStream_t, const SvtProb* probs, const int32_t* list, int count, int max_n);
+hipError_t mipgen_svt_launch_iterate(hipStream_t, const SvtProb* probs, const int32_t* list, int count, int max_n);
+hipError_t mipgen_svt_launch_shrink_stats(hipStream_t, const SvtProb* probs, const int32_t* list, int count);
+hipError_t mipgen_svt_launch_shrink(hipStream_t, const SvtProb* probs, const int32_t* list, int count);
+hipError_t mipgen_svt_launch_free_list(hipStream_t, const SvtProb* probs, const int32_t* list, int count);
+hipError_t mipgen_svt_launch_reconstruct(hipStream_t, const SvtProb* probs, const int32_t* list, int count, int max_inactive);
+hipError_t mipgen_svt_launch_predict(hipStream_t, const double* x, const SvtPred* preds, int count, int max_held);
 }

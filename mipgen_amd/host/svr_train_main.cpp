@@ -6,17 +6,11 @@
 // Defaults are svm-train's: C 1, p 0.1, eps 1e-3, gamma 1 / (largest feature index in the file); -m is accepted and ignored (the kernel matrix is
 // resident).  The training file is libsvm's sparse text format, "label index:value ...", indices 1..192 strictly ascending, absent ones 0.  Everything
 // is parsed and checked before the device is touched; any error ends with a message and exit status 1.
-#include <cerrno>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/mipgen_accel.h"
+#include "svr_problem.hpp"
 
-static const int NF = 192;
+static const char* PROG = "mipgen_svr_train";
 
 static int usage(const char* msg)
 {
@@ -36,77 +30,6 @@ static int usage(const char* msg)
     return 1;
 }
 
-static bool parse_double(const char* s, double* out)
-{
-    char* end = nullptr;
-    errno = 0;
-    const double v = strtod(s, &end);
-    if (end == s || *end != '\0') return false;
-    *out = v;
-    return true;
-}
-
-static bool parse_int(const char* s, long* out)
-{
-    char* end = nullptr;
-    errno = 0;
-    const long v = strtol(s, &end, 10);
-    if (end == s || *end != '\0' || errno != 0) return false;
-    *out = v;
-    return true;
-}
-
-// svm-train's read_problem (its grammar: label, then index:value pairs with strictly ascending indices), restricted to indices 1..192 and finite values
-static int read_problem(const char* path, std::vector<double>& x, std::vector<double>& y, int* max_index)
-{
-    FILE* fp = fopen(path, "r");
-    if (!fp) { fprintf(stderr, "mipgen_svr_train: can't open input file %s\n", path); return 1; }
-    char* line = nullptr;
-    size_t cap = 0;
-    long lineno = 0;
-    *max_index = 0;
-    int rc = 0;
-    while (getline(&line, &cap, fp) >= 0) {
-        lineno++;
-        char* save = nullptr;
-        char* label = strtok_r(line, " \t\n", &save);
-        double yv;
-        if (!label || !parse_double(label, &yv) || !std::isfinite(yv)) {
-            fprintf(stderr, "mipgen_svr_train: wrong input format at line %ld (%s)\n", lineno, label ? "label is not a finite number" : "empty line");
-            rc = 1; break;
-        }
-        y.push_back(yv);
-        x.resize(x.size() + NF, 0.0);
-        double* row = x.data() + x.size() - NF;
-        long last = 0;
-        for (;;) {
-            char* idx = strtok_r(nullptr, ":", &save);
-            char* val = strtok_r(nullptr, " \t", &save);
-            if (!val) {
-                if (idx && strspn(idx, " \t\r\n") != strlen(idx)) { fprintf(stderr, "mipgen_svr_train: wrong input format at line %ld (index without value)\n", lineno); rc = 1; }
-                break;
-            }
-            long j;
-            double v;
-            if (!parse_int(idx, &j)) { fprintf(stderr, "mipgen_svr_train: wrong input format at line %ld (bad index '%s')\n", lineno, idx); rc = 1; break; }
-            if (j <= last) { fprintf(stderr, "mipgen_svr_train: wrong input format at line %ld (index %ld not above %ld: indices must ascend)\n", lineno, j, last); rc = 1; break; }
-            if (j > NF) { fprintf(stderr, "mipgen_svr_train: wrong input format at line %ld (index %ld above %d)\n", lineno, j, NF); rc = 1; break; }
-            const size_t vl = strlen(val);
-            if (vl && val[vl - 1] == '\n') val[vl - 1] = '\0';
-            if (!parse_double(val, &v)) { fprintf(stderr, "mipgen_svr_train: wrong input format at line %ld (bad value '%s')\n", lineno, val); rc = 1; break; }
-            if (!std::isfinite(v)) { fprintf(stderr, "mipgen_svr_train: line %ld: feature %ld is not finite\n", lineno, j); rc = 1; break; }
-            row[j - 1] = v;
-            last = j;
-            if (j > *max_index) *max_index = (int)j;
-        }
-        if (rc) break;
-    }
-    free(line);
-    fclose(fp);
-    if (!rc && y.empty()) { fprintf(stderr, "mipgen_svr_train: %s holds no training rows\n", path); rc = 1; }
-    return rc;
-}
-
 int main(int argc, char** argv)
 {
     double gamma = 0, cost = 1, p = 0.1, eps = 1e-3;
@@ -122,14 +45,14 @@ int main(int argc, char** argv)
         long iv;
         double dv;
         switch (o) {
-        case 's': if (!parse_int(a, &iv) || iv != 3) return usage("only -s 3 (epsilon-SVR) is supported"); break;
-        case 't': if (!parse_int(a, &iv) || iv != 2) return usage("only -t 2 (RBF kernel) is supported"); break;
-        case 'h': if (!parse_int(a, &iv) || iv != 1) return usage("only -h 1 (shrinking) is supported"); break;
-        case 'g': if (!parse_double(a, &gamma)) return usage("bad value for -g"); break;
-        case 'c': if (!parse_double(a, &cost)) return usage("bad value for -c"); break;
-        case 'p': if (!parse_double(a, &p)) return usage("bad value for -p"); break;
-        case 'e': if (!parse_double(a, &eps)) return usage("bad value for -e"); break;
-        case 'm': if (!parse_double(a, &dv)) return usage("bad value for -m"); break;
+        case 's': if (!svr_parse_int(a, &iv) || iv != 3) return usage("only -s 3 (epsilon-SVR) is supported"); break;
+        case 't': if (!svr_parse_int(a, &iv) || iv != 2) return usage("only -t 2 (RBF kernel) is supported"); break;
+        case 'h': if (!svr_parse_int(a, &iv) || iv != 1) return usage("only -h 1 (shrinking) is supported"); break;
+        case 'g': if (!svr_parse_double(a, &gamma)) return usage("bad value for -g"); break;
+        case 'c': if (!svr_parse_double(a, &cost)) return usage("bad value for -c"); break;
+        case 'p': if (!svr_parse_double(a, &p)) return usage("bad value for -p"); break;
+        case 'e': if (!svr_parse_double(a, &eps)) return usage("bad value for -e"); break;
+        case 'm': if (!svr_parse_double(a, &dv)) return usage("bad value for -m"); break;
         default: return usage((std::string("unknown option: -") + o).c_str());
         }
     }
@@ -150,19 +73,11 @@ int main(int argc, char** argv)
 
     std::vector<double> x, y;
     int max_index = 0;
-    if (read_problem(train_path, x, y, &max_index)) return 1;
+    if (svr_read_problem(PROG, train_path, x, y, &max_index)) return 1;
     if (gamma == 0 && max_index > 0) gamma = 1.0 / max_index;      // svm-train's default
 
-    mipgen_params P;
-    memset(&P, 0, sizeof P);
-    P.abi_version = MIPGEN_ACCEL_ABI_VERSION;
-    P.score_method = MIPGEN_SCORE_SVR;
-    P.min_capture_size = P.max_capture_size = 162;
-    P.capture_increment = 1;
-    P.n_arm_pairs = 1;
-    P.arm_ext[0] = 16; P.arm_lig[0] = 24;
     mipgen_accel* h = nullptr;
-    if (mipgen_accel_create(&P, 0, nullptr, &h) != MIPGEN_OK) { fprintf(stderr, "mipgen_svr_train: %s\n", mipgen_accel_last_error()); return 1; }
+    if (svr_tool_handle(&h) != MIPGEN_OK) { fprintf(stderr, "mipgen_svr_train: %s\n", mipgen_accel_last_error()); return 1; }
     mipgen_svr_train_params tp;
     memset(&tp, 0, sizeof tp);
     tp.gamma = gamma; tp.cost = cost; tp.epsilon_p = p; tp.eps = eps; tp.shrinking = 1;
