@@ -285,6 +285,34 @@ int mipgen_accel_score_regions(mipgen_accel* h, const mipgen_region* regions, in
 int mipgen_accel_score_candidates(mipgen_accel* h, const mipgen_candidate* cands, int32_t n, int32_t method,
                                   double* scores, uint64_t* records, double* features, mipgen_candidate_ints* ints);
 
+/* Probes given by their SEQUENCES instead of coordinates in a resident batch (new entry point only: the ABI number does not change): what a MIP table
+ * (all_mips / collapsed_mips / picked_mips / snp_mips, print_details mipgen.cpp:765-794) holds of a probe is everything the two scorers read, so a
+ * design that exists only as such a file - this front end's, the reference's, one years old - can be featurized (training rows for
+ * mipgen_accel_train_svr) and scored with the model in hand.
+ *   - the sequences are STRAND-ORIENTED, as the reference's objects hold them and its files print them; nothing is reverse-complemented here.
+ *   - bytes are compared as the reference compares characters (std::string::find of "A", "AC", ..., SVMipv4.cpp:31-57; find("N") / find("-"), :63, :116;
+ *     current_base == "G", :123-134): only upper-case A C G T count in a mer, only 'N' in an arm and '-' in mip_seq raise the guard; a lower-case
+ *     letter or any other byte is in no mer, is no guard base and is "neither G/C nor A/T" in the run walk of get_score.
+ *   - guard (N in an arm, '-' anywhere in mip_seq): the all-zero feature vector; logistic score -1000, SVR the model's value at that vector.
+ *   - any insert length (the device stages an insert in pieces); arms of 1..MIPGEN_MAX_OLIGO bases.
+ *   - scores: MIPGEN_SCORE_LOGISTIC in the reference's term order with the correctly rounded power; MIPGEN_SCORE_SVR through the matrix-core list
+ *     scorer for n >= 256 and the per-probe model walk below - the scorers and the choice of mipgen_accel_score_candidates.
+ *   - ints: base counts, run_count, junction, copies, scan_size and flags (MIPGEN_FLAG_VALID, MIPGEN_FLAG_GUARD); masked_n and snp_count are 0 - the
+ *     tables they come from are not part of a probe.
+ * Any output pointer may be NULL.  A NULL sequence, an empty arm, an lrc_index outside [-1, n_lrc) are MIPGEN_E_INVALID, SVR without a model
+ * MIPGEN_E_MODEL, all before anything is allocated.  No resident batch is needed, and the handle's batch, result windows and result arrays are
+ * exactly as they were when the call returns. */
+typedef struct mipgen_probe {
+    const char* ext_seq; const char* lig_seq; const char* ins_seq;   /* oriented, NUL-terminated, upper or lower case as the files hold them */
+    const char* mip_seq;             /* may be NULL: then the '-' guard looks at the two arms only */
+    int32_t ext_copy, lig_copy;      /* unsaturated */
+    int32_t lrc_index;               /* row of the long-range table, or -1 = 44 zeros */
+    int32_t reserved;
+} mipgen_probe;
+int mipgen_accel_score_probes(mipgen_accel* h, const mipgen_probe* probes, int32_t n,
+                              const double* lrc, int32_t n_lrc,   /* [n_lrc][44], e.g. from mipgen_accel_long_range_content_batch */
+                              int32_t method, double* scores, double* features, mipgen_candidate_ints* ints);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -493,7 +521,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
 /* HIP-event time (ms) of the kernels of the last scoring call (summed over its windows), measured on the handle's stream;
  * negative if unavailable.  which: 0 = dense SVR kernel, 1 = records + scoring kernels, 2 = records / logistic kernel,
  * 3 = replay + condense; 4 = genome pass of the last mipgen_accel_count_oligo_copies (always recorded);
- * 5 / 6 = the matrix-core SVR kernel / the feature kernel of the last mipgen_accel_score_candidates call on a list (>= 256 SVR candidates). */
+ * 5 / 6 = the matrix-core SVR kernel / the feature kernel of the last mipgen_accel_score_candidates or mipgen_accel_score_probes call on a list
+ * (>= 256 SVR candidates). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -66,6 +66,11 @@ class CandidateInts(C.Structure):
         "run_count", "junction", "ext_copy", "lig_copy", "masked_n", "snp_count", "flags", "scan_size")]
 
 
+class Probe(C.Structure):            # mipgen_probe: a probe given by its strand-oriented sequences
+    _fields_ = [("ext_seq", C.c_char_p), ("lig_seq", C.c_char_p), ("ins_seq", C.c_char_p), ("mip_seq", C.c_char_p),
+                ("ext_copy", C.c_int32), ("lig_copy", C.c_int32), ("lrc_index", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -315,6 +320,9 @@ def load_library(path: Optional[str] = None):
                                                C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int64]
     lib.mipgen_accel_score_candidates.argtypes = [vp, C.POINTER(Candidate), C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(CandidateInts)]
+    lib.mipgen_accel_score_probes.argtypes = [vp, C.POINTER(Probe), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), C.POINTER(CandidateInts)]
+    lib.mipgen_accel_score_probes.restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
     lib.mipgen_accel_download_replay.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(Survivor), C.c_int64,
@@ -388,7 +396,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_count_oligo_copies_resident", "mipgen_accel_window_uniqueness", "mipgen_accel_window_uniqueness_begin", "mipgen_accel_window_flags_region",
     "mipgen_accel_window_uniqueness_end", "mipgen_accel_set_dynamic_skip", "mipgen_accel_skipped_candidates", "mipgen_accel_skip_state", "mipgen_accel_set_print_exact", "mipgen_accel_set_logistic_subruns",
     "mipgen_accel_rescore_survivors", "mipgen_accel_download_survivor_scores", "mipgen_accel_window_views", "mipgen_accel_synchronize",
-    "mipgen_accel_train_svr", "mipgen_accel_svr_cv_folds", "mipgen_accel_cross_validate_svr",
+    "mipgen_accel_train_svr", "mipgen_accel_svr_cv_folds", "mipgen_accel_cross_validate_svr", "mipgen_accel_score_probes",
 ]
 
 
@@ -753,6 +761,29 @@ class Accel:
             feats.ctypes.data_as(C.POINTER(C.c_double)) if feats is not None else None,
             ints if ints is not None else None))
         return scores, records, feats, ints
+
+    def score_probes(self, probes: Sequence[tuple], method: int, lrc: Optional[np.ndarray] = None, want_scores: bool = True,
+                     want_features: bool = False, want_ints: bool = False):
+        """mipgen_accel_score_probes: probes given by their strand-oriented sequences, no resident batch needed.  probes: tuples
+        (ext_seq, lig_seq, ins_seq, mip_seq or None, ext_copy, lig_copy, lrc_index) with bytes sequences; lrc: [n_lrc][44] long-range rows.
+        Returns (scores, features, ints), None for what was not asked."""
+        n = len(probes)
+        arr = (Probe * max(n, 1))()
+        for i, q in enumerate(probes):
+            arr[i] = Probe(q[0], q[1], q[2], q[3], q[4], q[5], q[6], 0)
+        n_lrc = 0
+        if lrc is not None:
+            lrc = np.ascontiguousarray(lrc, dtype=np.float64).reshape(-1, N_LRC)
+            n_lrc = lrc.shape[0]
+        scores = np.empty(n, dtype=np.float64) if want_scores else None
+        feats = np.empty((n, N_FEATURES), dtype=np.float64) if want_features else None
+        ints = (CandidateInts * max(n, 1))() if want_ints else None
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.mipgen_accel_score_probes(
+            self.h, arr, n, lrc.ctypes.data_as(dp) if n_lrc else None, n_lrc, method,
+            scores.ctypes.data_as(dp) if scores is not None else None,
+            feats.ctypes.data_as(dp) if feats is not None else None, ints))
+        return scores, feats, ints
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

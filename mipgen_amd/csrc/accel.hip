@@ -153,6 +153,7 @@ void mipgen_accel_destroy(mipgen_accel* h)
     h->pb.release(); h->sat.release(); h->surv_svr.release(); h->rs_keep.release(); h->rs_offs.release(); h->rs_idx.release();
     h->svr_tiles_lvl.release(); h->svr_tiles_kept.release(); h->run_bounds.release(); h->run_pbs.release(); h->run_state.release(); h->run_keep.release();
     h->run_offs.release(); h->skip_count.release();
+    h->probe_recs.release(); h->probe_bytes.release(); h->probe_lrc.release(); h->probe_order.release();
     h->lrc_seq.release(); h->lrc_out.release(); h->lrc_offs.release(); h->lrc_lens.release(); h->lrc_denoms.release(); h->partials.release();
     h->pool.clear();
     if (h->dp) (void)hipFree(h->dp);

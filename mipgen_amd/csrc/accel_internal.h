@@ -232,13 +232,18 @@ struct mipgen_accel {
     DevBuf<double> model_t, sv_norm, sv_coef, sv_center;   // the model centred and transposed for the survivor-list scorer (kernels_svr_gemm.hip)
     int n_sv_pad = 0;
     double kmer_count_ms = -1.0;             // genome pass of the last mipgen_accel_count_oligo_copies
-    double list_feat_ms = -1.0, list_svr_ms = -1.0;   // k_features_batch / k_svr_gemm of the last list call (timing enabled)
+    double list_feat_ms = -1.0, list_svr_ms = -1.0;   // k_features_batch (k_probe_features) / k_svr_gemm of the last list call (timing enabled)
     int64_t kmer_genome_bytes = 0;
     // sparse scratch
     DevBuf<mipgen_candidate> cand_in;
     DevBuf<double> cand_scores, cand_feats;
     DevBuf<uint64_t> cand_records;
     DevBuf<mipgen_candidate_ints> cand_ints;
+    // probes given by sequence (mipgen_accel_score_probes): descriptors, packed bytes, long-range rows, launch order
+    DevBuf<ProbeRec> probe_recs;
+    DevBuf<uint8_t> probe_bytes;
+    DevBuf<double> probe_lrc;
+    DevBuf<int32_t> probe_order;
     DevBuf<char> lrc_seq;
     DevBuf<double> lrc_out;
     DevBuf<int64_t> lrc_offs;

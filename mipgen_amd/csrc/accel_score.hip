@@ -40,18 +40,25 @@ static RescoreLimits rescore_limits(const mipgen_accel* h, int kind, int method,
 //    of a megabase of (CCG)n fills it.)
 // k_candidates re-scores the list in the reference's own operation order (literal; logistic: logistic_exponent_exact, pow_base_cr), its grid the
 // list's capacity; k_scatter_scores writes the values back where they came from.
-static int rescore(mipgen_accel* h, const RescoreSrc& src, int method)
+// ps: the entries are probes given by sequence (RESCORE_PROBES) - the list keeps their positions only and k_candidates reads the probes through them.
+static int rescore(mipgen_accel* h, const RescoreSrc& src, int method, const ProbeSrc* ps = nullptr)
 {
     const bool sat = src.kind == RESCORE_SATURATED;
     if (!sat && (!h->print_exact || src.n <= 0 || (method == MIPGEN_SCORE_SVR && h->n_sv <= 0))) return MIPGEN_OK;
     const RescoreLimits lim = rescore_limits(h, src.kind, method, src.n);
     RescoreList& L = sat ? h->sat : h->pb;
-    if (L.cands.reserve(lim.cap) || L.idx.reserve(lim.cap) || L.vals.reserve(lim.cap) || L.count.reserve(1)) return MIPGEN_E_NOMEM;
+    if ((!ps && L.cands.reserve(lim.cap)) || L.idx.reserve(lim.cap) || L.vals.reserve(lim.cap) || L.count.reserve(1)) return MIPGEN_E_NOMEM;
     if (sat) HIP_TRY(mipgen_launch_index_candidates(h->stream, h->dp, h->regions.p, src.r0, src.r1, L.idx.p, L.count.p, lim.cap, L.cands.p));
     else {
         HIP_TRY(hipMemsetAsync(L.count.p, 0, sizeof(unsigned int), h->stream));
         HIP_TRY(mipgen_launch_print_boundary_scan(h->stream, h->dp, h->regions.p, &src, lim.tol_rel, lim.tol_abs, L.cands.p, L.idx.p, L.count.p, lim.cap, h->n_cu));
     }
+    if (ps) {
+        ProbeSrc listed = *ps;
+        listed.sel = L.idx.p; listed.order = nullptr;
+        HIP_TRY(mipgen_launch_candidates_probes(h->stream, (int)lim.cap, &listed, h->dconsts, h->model.p, h->n_sv, h->gamma, h->rho, method, L.vals.p, nullptr, nullptr,
+                                                nullptr, 1, L.count.p));
+    } else
     HIP_TRY(mipgen_launch_candidates(h->stream, (int)lim.cap, h->dp, h->regions.p, L.cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
                                      h->gamma, h->rho, method, L.vals.p, nullptr, nullptr, nullptr, 1, L.count.p));
     HIP_TRY(mipgen_launch_scatter_scores(h->stream, L.vals.p, L.idx.p, lim.cap, L.count.p, src.scores, src.surv, sat ? nullptr : h->pb_over));
@@ -75,19 +82,31 @@ static int fix_survivor_print_boundaries(mipgen_accel* h, int w, int method)
     return rescore(h, {RESCORE_SURV, 2 * W.n_pos, nullptr, nullptr, nullptr, h->survivors.p + 2 * W.pos0, W.r0, W.r1, W.cand0}, method);
 }
 
+// The route choice of the list scorer, held once: SVR scores of a list of 256 and more go through the feature kernel and the matrix cores ...
+static bool list_is_batched(int n, int method, bool want_scores) { return method == MIPGEN_SCORE_SVR && n >= 256 && want_scores; }
+// ... and the wavefront-per-entry feature kernel (k_features_batch / k_probe_features) runs unless the integer features are asked for too
+static bool list_runs_feature_kernel(int n, int method, bool want_scores, bool ints) { return list_is_batched(n, method, want_scores) && !ints; }
+
 // The list scorer: the candidates cand_in[0, n) -> cand_scores, cand_records (+ cand_feats / cand_ints where asked).  Long SVR lists (a mixed
 // design re-scores every condensed survivor) go through k_features_batch (a wavefront per candidate) and the FP64 matrix cores (k_svr_gemm: all
 // candidate x support-vector distances instead of one model walk per candidate), then the print-exact re-score; the others through k_candidates.
 // le (optional): three events around the two stages of a matrix-core list, created here when timing is on.
-static int score_list(mipgen_accel* h, int n, int method, bool want_scores, bool features, bool ints, hipEvent_t* le)
+// ps (optional): the list is made of probes given by sequence (mipgen_accel_score_probes) instead of cand_in - the same choice of route, the same
+// scorers: k_probe_features in k_features_batch's place, k_candidates reading the probes' bytes instead of the resident batch.
+static int score_list(mipgen_accel* h, int n, int method, bool want_scores, bool features, bool ints, hipEvent_t* le, const ProbeSrc* ps = nullptr)
 {
-    const bool batched = method == MIPGEN_SCORE_SVR && n >= 256 && want_scores;
+    const bool batched = list_is_batched(n, method, want_scores);
     if (batched && h->cand_feats.reserve((size_t)n * MIPGEN_N_FEATURES)) return MIPGEN_E_NOMEM;
     const bool time_list = le && batched && !ints && h->timing;
     if (time_list) { for (int k = 0; k < 3; k++) HIP_TRY(hipEventCreate(&le[k])); HIP_TRY(hipEventRecord(le[0], h->stream)); }
-    if (batched && !ints)
+    if (list_runs_feature_kernel(n, method, want_scores, ints) && ps)
+        HIP_TRY(mipgen_launch_probe_features(h->stream, n, ps, h->dconsts, h->cand_records.p, h->cand_feats.p));
+    else if (list_runs_feature_kernel(n, method, want_scores, ints))
         HIP_TRY(mipgen_launch_features_batch(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->cand_records.p,
                                              h->cand_feats.p));
+    else if (ps)
+        HIP_TRY(mipgen_launch_candidates_probes(h->stream, n, ps, h->dconsts, h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p,
+                                                h->cand_records.p, (features || batched) ? h->cand_feats.p : nullptr, ints ? h->cand_ints.p : nullptr, 0, nullptr));
     else
         HIP_TRY(mipgen_launch_candidates(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts,
                                          h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p, h->cand_records.p,
@@ -97,6 +116,7 @@ static int score_list(mipgen_accel* h, int n, int method, bool want_scores, bool
                                             h->gamma, h->rho, h->cand_scores.p));
     if (time_list) HIP_TRY(hipEventRecord(le[2], h->stream));
     if (!batched) return MIPGEN_OK;
+    if (ps) return rescore(h, {RESCORE_PROBES, n, h->cand_scores.p, h->cand_records.p, nullptr, nullptr, 0, 0, 0}, MIPGEN_SCORE_SVR, ps);
     return rescore(h, {RESCORE_LIST, n, h->cand_scores.p, h->cand_records.p, h->cand_in.p, nullptr, 0, 0, 0}, MIPGEN_SCORE_SVR);
 }
 
@@ -386,6 +406,91 @@ int mipgen_accel_score_candidates(mipgen_accel* h, const mipgen_candidate* cands
         for (hipEvent_t e : le) (void)hipEventDestroy(e);
     }
     return MIPGEN_OK;
+}
+
+// Probes given by their sequences (ABI 6, new entry point only): the strand-oriented extension arm, ligation arm and insert of each probe as a MIP
+// table holds them (print_details, mipgen.cpp:765-794), its copy numbers and a row of long-range content - everything SVMipv4::get_parameters and
+// get_score read - so that a design that exists only as a file can be featurized and scored.  No resident batch is needed and none is touched: the
+// list goes through score_list (k_probe_features / k_candidates over the probes' bytes, then the scorers of mipgen_accel_score_candidates), in the
+// handle's list scratch; win_state, cur_window, the result arrays and the resident batch stay as they were.
+int mipgen_accel_score_probes(mipgen_accel* h, const mipgen_probe* probes, int32_t n, const double* lrc, int32_t n_lrc, int32_t method, double* scores,
+                              double* features, mipgen_candidate_ints* ints)
+{
+    if (!h || n < 0 || (n > 0 && !probes) || n_lrc < 0 || (n_lrc > 0 && !lrc)) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (method != MIPGEN_SCORE_LOGISTIC && method != MIPGEN_SCORE_SVR) return fail(MIPGEN_E_INVALID, "method must be logistic or svr");
+    if (method == MIPGEN_SCORE_SVR && h->model.p == nullptr) return fail(MIPGEN_E_MODEL, "SVR scoring requested but no model is loaded");
+    if (n == 0) return MIPGEN_OK;
+    // everything is checked before anything is allocated
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) {
+        const mipgen_probe& q = probes[i];
+        if (!q.ext_seq || !q.lig_seq || !q.ins_seq) return fail(MIPGEN_E_INVALID, "probe %d: %s sequence is NULL", i, !q.ext_seq ? "extension arm" : !q.lig_seq ? "ligation arm" : "insert");
+        const size_t e = strlen(q.ext_seq), l = strlen(q.lig_seq), s = strlen(q.ins_seq);
+        if (e < MIPGEN_MIN_OLIGO || l < MIPGEN_MIN_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: empty %s arm", i, e < MIPGEN_MIN_OLIGO ? "extension" : "ligation");
+        if (e > MIPGEN_MAX_OLIGO || l > MIPGEN_MAX_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: arm of %zu bases (at most %d)", i, std::max(e, l), MIPGEN_MAX_OLIGO);
+        if (s > (size_t)INT32_MAX) return fail(MIPGEN_E_INVALID, "probe %d: insert too long", i);
+        if (q.lrc_index < -1 || q.lrc_index >= n_lrc) return fail(MIPGEN_E_INVALID, "probe %d: long-range row %d out of range (%d rows)", i, q.lrc_index, n_lrc);
+        total += (int64_t)(e + l + s);
+    }
+    std::vector<ProbeRec> recs((size_t)n);
+    std::vector<uint8_t> packed((size_t)std::max<int64_t>(total, 1));
+    int64_t at = 0;
+    for (int i = 0; i < n; i++) {
+        const mipgen_probe& q = probes[i];
+        ProbeRec& r = recs[(size_t)i];
+        r.ext_len = (int32_t)strlen(q.ext_seq); r.lig_len = (int32_t)strlen(q.lig_seq); r.ins_len = (int32_t)strlen(q.ins_seq);
+        r.ext_off = at; memcpy(&packed[(size_t)at], q.ext_seq, (size_t)r.ext_len); at += r.ext_len;
+        r.lig_off = at; memcpy(&packed[(size_t)at], q.lig_seq, (size_t)r.lig_len); at += r.lig_len;
+        r.ins_off = at; memcpy(&packed[(size_t)at], q.ins_seq, (size_t)r.ins_len); at += r.ins_len;
+        r.ext_copy = q.ext_copy; r.lig_copy = q.lig_copy; r.lrc_index = q.lrc_index;
+        r.guard = q.mip_seq && strchr(q.mip_seq, '-') != nullptr;     // mip_seq.find("-"), SVMipv4.cpp:63,116 (the arms' own bytes are tested on the device)
+        r.pad = 0;
+    }
+    // launch order of the wavefront-per-probe kernel: falling insert length in classes of 64 bases (a counting sort; the last class holds the rest)
+    std::vector<int32_t> order;
+    if (list_runs_feature_kernel(n, method, scores != nullptr, ints != nullptr)) {          // (score_list's own choice: the order is k_probe_features')
+        const int NB = 64;
+        auto bucket = [](int32_t len) { return NB - 1 - std::min(len >> 6, NB - 1); };
+        int64_t first[NB + 1] = {0};
+        for (int i = 0; i < n; i++) first[bucket(recs[(size_t)i].ins_len) + 1]++;
+        for (int b = 0; b < NB; b++) first[b + 1] += first[b];
+        order.resize((size_t)n);
+        for (int i = 0; i < n; i++) order[(size_t)first[bucket(recs[(size_t)i].ins_len)]++] = i;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    // a print-exact overflow an earlier asynchronous call left for ITS download stays with that call
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    struct KeepOver { unsigned int* p; unsigned int v; ~KeepOver() { if (p) *p = v; } } keep_over{h->pb_over, h->pb_over ? *h->pb_over : 0u};
+    if (h->pb_over) *h->pb_over = 0u;
+    if (h->probe_recs.reserve((size_t)n) || h->probe_bytes.reserve(packed.size()) || (n_lrc > 0 && h->probe_lrc.reserve((size_t)n_lrc * MIPGEN_N_LRC)) ||
+        (!order.empty() && h->probe_order.reserve((size_t)n)) || h->cand_scores.reserve((size_t)n) || h->cand_records.reserve((size_t)n) ||
+        (features && h->cand_feats.reserve((size_t)n * MIPGEN_N_FEATURES)) || (ints && h->cand_ints.reserve((size_t)n)))
+        return MIPGEN_E_NOMEM;
+    // the copies below read recs / packed / order: whichever way the call ends, the stream is idle before they go (declared after them: runs first)
+    struct IdleOnExit { hipStream_t s; ~IdleOnExit() { (void)hipStreamSynchronize(s); } } idle_on_exit{h->stream};
+    HIP_TRY(hipMemcpyAsync(h->probe_recs.p, recs.data(), (size_t)n * sizeof(ProbeRec), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->probe_bytes.p, packed.data(), packed.size(), hipMemcpyHostToDevice, h->stream));
+    if (n_lrc > 0) HIP_TRY(hipMemcpyAsync(h->probe_lrc.p, lrc, (size_t)n_lrc * MIPGEN_N_LRC * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!order.empty()) HIP_TRY(hipMemcpyAsync(h->probe_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    const ProbeSrc ps = {h->probe_recs.p, h->probe_bytes.p, h->probe_lrc.p, nullptr, order.empty() ? nullptr : h->probe_order.p};
+    hipEvent_t le[3] = {nullptr, nullptr, nullptr};
+    int rc = score_list(h, n, method, scores != nullptr, features != nullptr, ints != nullptr, le, &ps);
+    if (rc == MIPGEN_OK) {
+        // (the host vectors above live until the synchronisation below)
+        hipError_t e_ = hipSuccess;
+        if (scores) e_ = hipMemcpyAsync(scores, h->cand_scores.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        if (e_ == hipSuccess && features) e_ = hipMemcpyAsync(features, h->cand_feats.p, (size_t)n * MIPGEN_N_FEATURES * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        if (e_ == hipSuccess && ints) e_ = hipMemcpyAsync(ints, h->cand_ints.p, (size_t)n * sizeof(mipgen_candidate_ints), hipMemcpyDeviceToHost, h->stream);
+        if (e_ == hipSuccess) e_ = hipStreamSynchronize(h->stream);
+        if (e_ != hipSuccess) rc = fail(MIPGEN_E_HIP, "mipgen_accel_score_probes: %s", hipGetErrorString(e_));
+    } else (void)hipStreamSynchronize(h->stream);
+    if (rc == MIPGEN_OK) rc = mipgen_pb_check(h);
+    if (le[0]) {
+        float a = 0.f, b = 0.f;
+        if (rc == MIPGEN_OK && hipEventElapsedTime(&a, le[0], le[1]) == hipSuccess && hipEventElapsedTime(&b, le[1], le[2]) == hipSuccess) { h->list_feat_ms = a; h->list_svr_ms = b; }
+        for (hipEvent_t e : le) if (e) (void)hipEventDestroy(e);
+    }
+    return rc;
 }
 
 static void lrc_mers(LrcMers& M)

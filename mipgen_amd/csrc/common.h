@@ -111,7 +111,7 @@ struct SvrTile {
 
 // the entries of a re-score list (accel_score.hip: rescore): what k_print_boundary_scan tests - or, for RESCORE_SATURATED, the dense indices
 // the logistic scoring kernels listed themselves - and where k_scatter_scores writes the re-scored values back
-enum { RESCORE_DENSE, RESCORE_LIST, RESCORE_SURV, RESCORE_SATURATED };
+enum { RESCORE_DENSE, RESCORE_LIST, RESCORE_SURV, RESCORE_SATURATED, RESCORE_PROBES };   // PROBES: a LIST whose entries are probes given by sequence (no candidate to copy: the list keeps positions only)
 struct RescoreSrc {
     int kind;
     int64_t n;                        // entries (SATURATED: the window's candidates)
@@ -121,6 +121,26 @@ struct RescoreSrc {
     mipgen_survivor* surv;            // SURV: entry i (score, record, batch-wide dense index)
     int r0, r1;                       // DENSE / SURV / SATURATED: the window's regions (its dense indices are window-relative, as DevRegion::out_off)
     int64_t cand0;                    // SURV: the window's first candidate
+};
+
+// A probe given by its SEQUENCES (mipgen_accel_score_probes): strand-oriented extension arm, ligation arm and insert as the bytes of a MIP table
+// hold them, packed into one byte array; what a coordinate-addressed candidate takes from the resident batch's tables comes with the probe.
+struct ProbeRec {
+    int64_t ext_off, lig_off, ins_off;   // into ProbeSrc::bytes
+    int32_t ext_len, lig_len, ins_len;
+    int32_t ext_copy, lig_copy;          // unsaturated
+    int32_t lrc_index;                   // row of ProbeSrc::lrc, -1 = 44 zeros
+    int32_t guard;                       // != 0: '-' in the MIP sequence outside the arms (SVMipv4.cpp:63,116); N / '-' inside an arm is found from the bytes
+    int32_t pad;
+};
+// the probe list of a launch, by value.  sel (optional): the launch's entry b is probe sel[b] and writes result b (the re-score of listed positions);
+// order (optional, k_probe_features): wavefront w takes probe order[w] (longest inserts first) and writes at the probe's own index
+struct ProbeSrc {
+    const ProbeRec* probes;
+    const uint8_t* bytes;
+    const double* lrc;                   // [n_lrc][44]
+    const int64_t* sel;
+    const int32_t* order;
 };
 
 // static thread geometry of the dense SVR kernel for a parameter set (computed on the host once)

@@ -61,6 +61,11 @@ hipError_t mipgen_launch_features_batch(hipStream_t, int n, const DevParams*, co
 hipError_t mipgen_launch_candidates(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t*, const int32_t*, const uint8_t*,
                                     const HostConsts*, const double* model, int n_sv, double gamma, double rho, int method, double*, uint64_t*, double*, mipgen_candidate_ints*,
                                     int literal, const unsigned int* n_dev);
+// the same kernel over probes given by sequence (no resident batch)
+hipError_t mipgen_launch_candidates_probes(hipStream_t, int n, const ProbeSrc*, const HostConsts*, const double* model, int n_sv, double gamma, double rho, int method,
+                                           double*, uint64_t*, double*, mipgen_candidate_ints*, int literal, const unsigned int* n_dev);
+// kernels_probe.hip
+hipError_t mipgen_launch_probe_features(hipStream_t, int n, const ProbeSrc*, const HostConsts*, uint64_t* records, double* features);
 hipError_t mipgen_launch_print_boundary_scan(hipStream_t, const DevParams*, const DevRegion*, const RescoreSrc*, double tol_rel, double tol_abs, mipgen_candidate* out,
                                              int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu);
 hipError_t mipgen_launch_index_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const int64_t* idx, const unsigned int* count, unsigned int cap,

@@ -7,16 +7,20 @@
 //   * lanes then own support vectors: each walks the 192 dimensions in index order (svm.cpp:329-368), takes
 //     exp(-gamma*d2) and the partial sums coef*k are reduced with wavefront shuffles (svm.cpp:2511-2515).
 // It doubles as an on-device cross-check of the window-separable dense kernel (kernels_svr.hip).
+// Two sources of a candidate's sequences, one kernel (template parameter PROBE): coordinates in the resident region batch (strand orientation,
+// record fields and copy numbers from the batch's tables), or a probe given by its oriented sequences (ProbeSrc, mipgen_accel_score_probes: the
+// bytes of a MIP table, copies and long-range row come with the probe).  Everything behind the staged sequences - mer counts, features, integer
+// features, the logistic score, the SVR walks - is the same code.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "kernels.h"
 #include "device_utils.h"
 #include "mip_record.h"
 #include "logistic_device.h"
+#include "mip_features.h"
 #include "pow_base_cr.h"
 
 #define CAND_THREADS 256
-#define MAX_INSERT 1024
 
 namespace {
 
@@ -62,9 +66,10 @@ __device__ void run_count_piece(const uint8_t* s, int n, int& last, int& run)
 
 }  // namespace
 
+template <bool PROBE>
 __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
     const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, const mipgen_candidate* __restrict__ cands,
-    const uint8_t* __restrict__ bases, const int32_t* __restrict__ copy, const uint8_t* __restrict__ unmap,
+    const uint8_t* __restrict__ bases, const int32_t* __restrict__ copy, const uint8_t* __restrict__ unmap, const ProbeSrc S,
     const HostConsts* __restrict__ HC, const double* __restrict__ model, int n_sv, double gamma, double rho, int method,
     double* __restrict__ scores, uint64_t* __restrict__ records, double* __restrict__ features,
     mipgen_candidate_ints* __restrict__ ints_out, int literal, const unsigned int* __restrict__ n_dev)
@@ -79,11 +84,37 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
     __shared__ int s_info[16];
 
     const int tid = threadIdx.x;
+    const int64_t oi = blockIdx.x;                        // where this workgroup's results go
+    int p = 0, e, l, ss;
+    bool minus = false;
+    const DevRegion* Rp = nullptr;
+    const double* lrc;
+    ProbeRec pr = {};
+    if constexpr (PROBE) {
+        pr = S.probes[S.sel ? S.sel[blockIdx.x] : (int64_t)blockIdx.x];
+        e = pr.ext_len; l = pr.lig_len; ss = pr.ins_len;
+        lrc = pr.lrc_index >= 0 ? S.lrc + (int64_t)pr.lrc_index * MIPGEN_N_LRC : nullptr;
+        // the oriented arms as the file holds them: no strand, no masked / SNP bits, no table to look a copy number up in
+        for (int i = tid; i < e; i += CAND_THREADS) s_ext[i] = ascii_base_code(S.bytes[pr.ext_off + i]);
+        for (int i = tid; i < l; i += CAND_THREADS) s_lig[i] = ascii_base_code(S.bytes[pr.lig_off + i]);
+        if (tid == 0 && l < 2) s_lig[1] = BASE_OTHER;     // a one-base arm has no junction dimer (lig_probe_sequence.substr(0, 2), SVMipv4.cpp:103)
+        __syncthreads();
+        if (tid == 0) {
+            int bad = pr.guard != 0;
+            for (int i = 0; i < e; i++) bad += (s_ext[i] == BASE_N || s_ext[i] == BASE_DASH);
+            for (int i = 0; i < l; i++) bad += (s_lig[i] == BASE_N || s_lig[i] == BASE_DASH);
+            s_info[0] = pr.ext_copy; s_info[1] = pr.lig_copy; s_info[2] = 0; s_info[3] = 0;
+            s_info[4] = (int)(MIPGEN_FLAG_VALID | (bad ? MIPGEN_FLAG_GUARD : 0u));
+            s_info[5] = bad;
+        }
+    } else {
     const mipgen_candidate c = cands[blockIdx.x];
     const DevRegion& R = regions[c.region];
-    const int p = c.scan_start, C = c.capture_size, e = c.ext_len, l = c.lig_len;
-    const bool minus = c.strand != 0;
-    const int ss = C - e - l;
+    Rp = &R; lrc = R.lrc;
+    const int C = c.capture_size;
+    p = c.scan_start; e = c.ext_len; l = c.lig_len;
+    minus = c.strand != 0;
+    ss = C - e - l;
     const bool valid = constructed(R, p, C, e, l) && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
     if (!valid) {
         if (tid == 0) {
@@ -137,6 +168,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
         s_info[0] = ext_copy; s_info[1] = lig_copy; s_info[2] = masked_n; s_info[3] = snp_count; s_info[4] = (int)flags;
         s_info[5] = bad;
     }
+    }
     __syncthreads();
     const int ext_copy = s_info[0], lig_copy = s_info[1];
     const bool guard = s_info[5] != 0;
@@ -152,8 +184,13 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
         const int len = min(MAX_INSERT, ss - c0), lenx = min(len + 2, ss - c0);
         if (c0) __syncthreads();
         for (int i = tid; i < lenx; i += CAND_THREADS) {
-            const int b = base_at(minus ? p + ss - 1 - (c0 + i) : p + c0 + i) & BASE_CODE_MASK;
-            s_ins[i] = (uint8_t)(minus ? comp_code(b) : b);
+            if constexpr (PROBE) s_ins[i] = ascii_base_code(S.bytes[pr.ins_off + c0 + i]);
+            else {
+                const DevRegion& R = *Rp;
+                const int ri = (minus ? p + ss - 1 - (c0 + i) : p + c0 + i) - R.seq_start;
+                const int b = ((ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER) & BASE_CODE_MASK;
+                s_ins[i] = (uint8_t)(minus ? comp_code(b) : b);
+            }
         }
         __syncthreads();
         if (tid < 84) { int k, x, y, z; ins_mer(tid, k, x, y, z); ins_count += count_mer(s_ins, len, lenx, k, x, y, z); }
@@ -166,32 +203,10 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
 
     // 192 features, SVMipv4.cpp:72-112
     if (tid < MIPGEN_N_FEATURES) {
-        double v;
         const int f = tid;
-        if (guard) v = 0.0;
-        else if (f < F_LRC) {                         // ext block
-            if (f == F_EXT_LEN) v = (double)e;
-            else if (f == F_EXT_GC) v = ((double)s_cnt[84 + 10] + (double)s_cnt[84 + 5]) / (double)(uint64_t)((uint64_t)e - 1 + 1);
-            else { int idx = f < F_EXT_GC ? f : f - 1; int k = (idx % 5) ? 2 : 1; v = (double)s_cnt[84 + idx] / ((double)(uint64_t)((uint64_t)e - k) + 1.); }
-        } else if (f < F_INS) v = R.lrc[f - F_LRC];
-        else if (f < F_LIG) {                         // insert block
-            const int g = f - F_INS;
-            if (f == F_INS_LEN) v = (double)ss;
-            else if (f == F_INS_GC) v = ((double)s_cnt[42] + (double)s_cnt[21]) / ((double)(uint64_t)((uint64_t)ss - 1) + 1.);
-            else {
-                int idx = g < 63 ? g : g - 1;
-                int r = idx % 21; int k = r == 0 ? 1 : (((r - 1) % 5) == 0 ? 2 : 3);
-                v = (double)s_cnt[idx] / ((double)(uint64_t)((uint64_t)ss - k) + 1.);
-            }
-        } else if (f < F_JUNC) {                      // lig block
-            const int g = f - F_LIG;
-            if (f == F_LIG_LEN) v = (double)l;
-            else if (f == F_LIG_GC) v = ((double)s_cnt[104 + 10] + (double)s_cnt[104 + 5]) / ((double)(uint64_t)((uint64_t)l - 1) + 1.);
-            else { int idx = g < 15 ? g : g - 1; int k = (idx % 5) ? 2 : 1; v = (double)s_cnt[104 + idx] / ((double)(uint64_t)((uint64_t)l - k) + 1.); }
-        } else if (f < F_LEC) v = (jc == f - F_JUNC) ? 1.0 : 0.0;
-        else v = log_copy_dev(HC, f == F_LEC ? ext_copy : lig_copy);
+        const double v = mip_feature(f, s_cnt, e, l, ss, lrc, jc, ext_copy, lig_copy, guard, HC);
         s_x[f] = v;
-        if (features) features[(int64_t)blockIdx.x * MIPGEN_N_FEATURES + f] = v;
+        if (features) features[oi * MIPGEN_N_FEATURES + f] = v;
     }
     __syncthreads();
 
@@ -209,10 +224,10 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
             o.ins_a = tA; o.ins_c = tC; o.ins_g = tG; o.ins_t = tT;
             o.run_count = run; o.junction = jc; o.ext_copy = ext_copy; o.lig_copy = lig_copy;
             o.masked_n = s_info[2]; o.snp_count = s_info[3]; o.flags = s_info[4]; o.scan_size = ss;
-            ints_out[blockIdx.x] = o;
+            ints_out[oi] = o;
         }
         if (records) {
-            records[blockIdx.x] = pack_record(ext_copy, lig_copy, s_info[2], s_info[3], (uint32_t)s_info[4], (uint32_t)jc);
+            records[oi] = pack_record(ext_copy, lig_copy, s_info[2], s_info[3], (uint32_t)s_info[4], (uint32_t)jc);
         }
         if (method == MIPGEN_SCORE_LOGISTIC) {
             if (guard) logistic = -1000.0;
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
                 const double y = fabs(ex) < 700.0 ? pow_base_cr(ex) : pow(MIPGEN_LOGISTIC_BASE, ex);
                 logistic = y / (1.0 + y);
             }
-            if (scores) scores[blockIdx.x] = logistic;
+            if (scores) scores[oi] = logistic;
         }
     }
     if (method != MIPGEN_SCORE_SVR || !scores) return;
@@ -266,7 +281,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
             if (tid == 0) { const int m = min(CAND_THREADS, n_sv - base); for (int q = 0; q < m; q++) total = total + s_term[q]; }
             __syncthreads();
         }
-        if (tid == 0) scores[blockIdx.x] = total - rho;
+        if (tid == 0) scores[oi] = total - rho;
         return;
     }
     // SVR: lanes own support vectors; 192-dimension walk in index order, then shuffle reduction
@@ -287,7 +302,7 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
     if (tid == 0) {
         double s = 0.0;
         for (int w = 0; w < CAND_THREADS / WAVE; w++) s += s_red[w];
-        scores[blockIdx.x] = s - rho;
+        scores[oi] = s - rho;
     }
 }
 
@@ -366,57 +381,15 @@ __global__ __launch_bounds__(FB_WAVES * 64) void k_features_batch(
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < len; i += 64) {
-            const int x = s_ins[i];
-            if (x < 4) {
-                atomicAdd(&s_cnt[21 * x], 1);
-                if (i + 1 < lenx) {
-                    const int y = s_ins[i + 1];
-                    if (y < 4) {
-                        atomicAdd(&s_cnt[21 * x + 1 + 5 * y], 1);
-                        if (i + 2 < lenx) { const int z = s_ins[i + 2]; if (z < 4) atomicAdd(&s_cnt[21 * x + 1 + 5 * y + 1 + z], 1); }
-                    }
-                }
-            }
-        }
+        hist_insert_piece(s_ins, len, lenx, s_cnt, lane, 64);
     }
-    if (lane < e) {
-        const int x = s_ext[lane];
-        if (x < 4) { atomicAdd(&s_cnt[84 + 5 * x], 1); if (lane + 1 < e) { const int y = s_ext[lane + 1]; if (y < 4) atomicAdd(&s_cnt[84 + 5 * x + 1 + y], 1); } }
-    }
-    if (lane < l) {
-        const int x = s_lig[lane];
-        if (x < 4) { atomicAdd(&s_cnt[104 + 5 * x], 1); if (lane + 1 < l) { const int y = s_lig[lane + 1]; if (y < 4) atomicAdd(&s_cnt[104 + 5 * x + 1 + y], 1); } }
-    }
+    hist_arm(s_ext, e, s_cnt + 84, lane);
+    hist_arm(s_lig, l, s_cnt + 104, lane);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // 192 features, SVMipv4.cpp:72-112 (the arithmetic of k_candidates, three features per lane)
-    for (int f = lane; f < MIPGEN_N_FEATURES; f += 64) {
-        double v;
-        if (guard) v = 0.0;
-        else if (f < F_LRC) {                         // ext block
-            if (f == F_EXT_LEN) v = (double)e;
-            else if (f == F_EXT_GC) v = ((double)s_cnt[84 + 10] + (double)s_cnt[84 + 5]) / (double)(uint64_t)((uint64_t)e - 1 + 1);
-            else { int idx = f < F_EXT_GC ? f : f - 1; int k = (idx % 5) ? 2 : 1; v = (double)s_cnt[84 + idx] / ((double)(uint64_t)((uint64_t)e - k) + 1.); }
-        } else if (f < F_INS) v = R.lrc[f - F_LRC];
-        else if (f < F_LIG) {                         // insert block
-            const int g = f - F_INS;
-            if (f == F_INS_LEN) v = (double)ss;
-            else if (f == F_INS_GC) v = ((double)s_cnt[42] + (double)s_cnt[21]) / ((double)(uint64_t)((uint64_t)ss - 1) + 1.);
-            else {
-                int idx = g < 63 ? g : g - 1;
-                int r = idx % 21; int k = r == 0 ? 1 : (((r - 1) % 5) == 0 ? 2 : 3);
-                v = (double)s_cnt[idx] / ((double)(uint64_t)((uint64_t)ss - k) + 1.);
-            }
-        } else if (f < F_JUNC) {                      // lig block
-            const int g = f - F_LIG;
-            if (f == F_LIG_LEN) v = (double)l;
-            else if (f == F_LIG_GC) v = ((double)s_cnt[104 + 10] + (double)s_cnt[104 + 5]) / ((double)(uint64_t)((uint64_t)l - 1) + 1.);
-            else { int idx = g < 15 ? g : g - 1; int k = (idx % 5) ? 2 : 1; v = (double)s_cnt[104 + idx] / ((double)(uint64_t)((uint64_t)l - k) + 1.); }
-        } else if (f < F_LEC) v = (jc == f - F_JUNC) ? 1.0 : 0.0;
-        else v = log_copy_dev(HC, f == F_LEC ? ext_copy : lig_copy);
-        fo[f] = v;
-    }
+    for (int f = lane; f < MIPGEN_N_FEATURES; f += 64)
+        fo[f] = mip_feature(f, s_cnt, e, l, ss, R.lrc, jc, ext_copy, lig_copy, guard, HC);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -491,7 +464,16 @@ extern "C" hipError_t mipgen_launch_candidates(
     int method, double* scores, uint64_t* records, double* features, mipgen_candidate_ints* ints, int literal, const unsigned int* n_dev)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_candidates, dim3(n), dim3(CAND_THREADS), 0, stream, P, regions, cands, bases, copy, unmap, HC, model,
+    hipLaunchKernelGGL(k_candidates<false>, dim3(n), dim3(CAND_THREADS), 0, stream, P, regions, cands, bases, copy, unmap, ProbeSrc{}, HC, model,
+                       n_sv, gamma, rho, method, scores, records, features, ints, literal, n_dev);
+    return hipGetLastError();
+}
+extern "C" hipError_t mipgen_launch_candidates_probes(hipStream_t stream, int n, const ProbeSrc* S, const HostConsts* HC, const double* model, int n_sv, double gamma,
+                                                      double rho, int method, double* scores, uint64_t* records, double* features, mipgen_candidate_ints* ints,
+                                                      int literal, const unsigned int* n_dev)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_candidates<true>, dim3(n), dim3(CAND_THREADS), 0, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, *S, HC, model,
                        n_sv, gamma, rho, method, scores, records, features, ints, literal, n_dev);
     return hipGetLastError();
 }
@@ -553,10 +535,10 @@ __global__ __launch_bounds__(256) void k_print_boundary_scan(const DevParams* __
         }
         if (score_is_constant(rec)) return;
         mipgen_candidate c;
-        if constexpr (KIND != RESCORE_LIST) { if (!dense_candidate(P, regions, r0, r1, idx, c)) return; }
+        if constexpr (KIND != RESCORE_LIST && KIND != RESCORE_PROBES) { if (!dense_candidate(P, regions, r0, r1, idx, c)) return; }
         const unsigned int at = atomicAdd(count, 1u);
         if (at >= cap) return;
-        if constexpr (KIND == RESCORE_LIST) out[at] = cands[i]; else out[at] = c;
+        if constexpr (KIND == RESCORE_LIST) out[at] = cands[i]; else if constexpr (KIND != RESCORE_PROBES) out[at] = c;
         out_idx[at] = i;
     };
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -593,7 +575,7 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const double* __restrict
 extern "C" hipError_t mipgen_launch_print_boundary_scan(hipStream_t stream, const DevParams* P, const DevRegion* regions, const RescoreSrc* s, double tol_rel,
                                                         double tol_abs, mipgen_candidate* out, int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu)
 {
-    if (s->n <= 0 || (s->kind != RESCORE_LIST && s->r1 <= s->r0)) return hipSuccess;
+    if (s->n <= 0 || (s->kind != RESCORE_LIST && s->kind != RESCORE_PROBES && s->r1 <= s->r0)) return hipSuccess;
     const int64_t want = (s->n + 255) / 256;
     const unsigned grid = (unsigned)(s->kind == RESCORE_DENSE ? std::min<int64_t>(want, (int64_t)std::max(n_cu, 1) * 16) : want);
 #define SCAN(K) hipLaunchKernelGGL(k_print_boundary_scan<K>, dim3(grid), dim3(256), 0, stream, P, regions, s->r0, s->r1, s->n, s->scores, s->records, s->cands, \
@@ -602,6 +584,7 @@ extern "C" hipError_t mipgen_launch_print_boundary_scan(hipStream_t stream, cons
         case RESCORE_DENSE: SCAN(RESCORE_DENSE); break;
         case RESCORE_LIST: SCAN(RESCORE_LIST); break;
         case RESCORE_SURV: SCAN(RESCORE_SURV); break;
+        case RESCORE_PROBES: SCAN(RESCORE_PROBES); break;
         default: return hipErrorInvalidValue;
     }
 #undef SCAN

@@ -147,7 +147,8 @@ static bool slurp_fasta(const std::string& path, std::vector<std::string>& recor
 
 bool load_sequences_from_genome_dir(const Options& o, std::vector<Region>& regs)
 {
-    std::ofstream fa(o.project_name + ".feature_sequences.fa");
+    std::ofstream fa;
+    if (o.write_feature_fasta) fa.open(o.project_name + ".feature_sequences.fa");
     const std::string dir = o.arg("-genome_dir");
     // The chromosome files are read and joined ahead of the regions that slice them (up to four loads in flight: a 300 Mb genome is 0.5 s of
     // fread + line joining + toupper on one core).  One load per RUN of regions on the same chromosome, as the reference reloads on every change.
@@ -183,7 +184,7 @@ bool load_sequences_from_genome_dir(const Options& o, std::vector<Region>& regs)
         const int len = ce - cs + 1;
         r.seq = chr_seq.substr((size_t)(cs - 1), (size_t)std::max(len, 0));
         r.seq_start = cs; r.seq_stop = ce;
-        fa << ">" << r.chr << ':' << cs << "-" << ce << '\n' << r.seq << '\n';        // flushed when the file closes (200,000 regions: no write per line)
+        if (o.write_feature_fasta) fa << ">" << r.chr << ':' << cs << "-" << ce << '\n' << r.seq << '\n';        // flushed when the file closes (200,000 regions: no write per line)
         if (o.score_method != MIPGEN_SCORE_LOGISTIC) {
             long s0 = (long)r.start_fl - o.max_capture - 1 - 1000;               // :1225 (the reference throws if this is negative)
             if (s0 < 0) s0 = 0;
@@ -222,7 +223,8 @@ bool load_sequences_from_indexed_fasta(const Options& o, std::vector<Region>& re
         }
         return out;
     };
-    std::ofstream fa(o.project_name + ".feature_sequences.fa");
+    std::ofstream fa;
+    if (o.write_feature_fasta) fa.open(o.project_name + ".feature_sequences.fa");
     for (Region& r : regs) {
         auto it = fai.find(r.chr);
         if (it == fai.end()) it = fai.find("chr" + r.chr);                      // mipgen.cpp:1106 adds "chr" when the reference uses it
@@ -231,8 +233,10 @@ bool load_sequences_from_indexed_fasta(const Options& o, std::vector<Region>& re
         r.seq = fetch(it->second, a, b);
         r.seq_start = (int)std::max(a, 1L);
         r.seq_stop = r.seq_start + (int)r.seq.size() - 1;
-        fa << ">" << it->first << ':' << a << "-" << b << std::endl;
-        for (size_t i = 0; i < r.seq.size(); i += 60) fa << r.seq.substr(i, 60) << std::endl;
+        if (o.write_feature_fasta) {
+            fa << ">" << it->first << ':' << a << "-" << b << std::endl;
+            for (size_t i = 0; i < r.seq.size(); i += 60) fa << r.seq.substr(i, 60) << std::endl;
+        }
         if (o.score_method != MIPGEN_SCORE_LOGISTIC) r.long_range_seq = fetch(it->second, a - 1000, b + 1000);
     }
     fclose(fp);

@@ -47,6 +47,7 @@ struct Options {
     int score_method = MIPGEN_SCORE_LOGISTIC;
     std::string middle;                          // universal_middle_mip_seq (mipgen.cpp:199-200)
     std::string regions_to_scan, project_name, bwa_genome_index, file_dir;
+    bool write_feature_fasta = true;             // the sequence loaders leave <project_name>.feature_sequences.fa (mipgen.cpp:1186,1222); mipgen_rescore has no project
     std::vector<std::pair<int, int>> arm_pairs;  // (ext, lig) in enumeration order: arm sum desc, list order (mipgen.cpp:431-442)
     std::set<int> oligo_sizes;
     int max_arm_sum = 0, min_arm_sum = 0;

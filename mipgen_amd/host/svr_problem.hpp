@@ -1,5 +1,5 @@
-// svr_problem.hpp — what the SVR model tools (mipgen_svr_train, mipgen_svr_cv) share: number parsing, the reader of libsvm's sparse training
-// format, and the accelerator handle a tool that only trains needs.  Messages name the program that reads.
+// svr_problem.hpp — what the SVR model tools (mipgen_svr_train, mipgen_svr_cv, mipgen_rescore) share: number parsing, the reader and the writer of
+// libsvm's sparse training format, and the accelerator handle a tool that needs no design parameters takes.  Messages name the program that reads.
 #pragma once
 #include <cerrno>
 #include <cmath>
@@ -81,6 +81,15 @@ static inline int svr_read_problem(const char* prog, const char* path, std::vect
     fclose(fp);
     if (!rc && y.empty()) { fprintf(stderr, "%s: %s holds no training rows\n", prog, path); rc = 1; }
     return rc;
+}
+
+// ... and its writer: one row of that format, the non-zero features only (what libsvm's own tools write and svr_read_problem reads back: absent
+// indices are 0), every value with 17 significant digits so that the doubles survive the text
+static inline void svr_write_row(FILE* fp, double label, const double* row)
+{
+    fprintf(fp, "%.17g", label);
+    for (int j = 0; j < SVR_NF; j++) if (row[j] != 0.0) fprintf(fp, " %d:%.17g", j + 1, row[j]);
+    fputc('\n', fp);
 }
 
 // a handle for training only: the scoring parameters are never used, any valid set will do
