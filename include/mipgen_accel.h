@@ -313,6 +313,38 @@ int mipgen_accel_score_probes(mipgen_accel* h, const mipgen_probe* probes, int32
                               const double* lrc, int32_t n_lrc,   /* [n_lrc][44], e.g. from mipgen_accel_long_range_content_batch */
                               int32_t method, double* scores, double* features, mipgen_candidate_ints* ints);
 
+/* ---- measured counts: reads and unique molecular tags per probe from smMIP read pairs (new entry points only: the ABI number does not change) ----
+ * The capture model: with E = ext_seq, L = lig_seq as a MIP table prints them and tag sizes (ext_tag, lig_tag), the extension read of a
+ * captured molecule is tag + E + target ..., the ligation read is tag + revcomp(L) + ....  A pair is a CANDIDATE of a probe if the S bases behind
+ * the tag of its extension read are the first S bases of E, or those of its ligation read the first S of revcomp(L), exactly (S = the shortest arm
+ * of the table, at most 32); it PASSES if all of E and all of revcomp(L) match with at most max_mismatches substitutions each (any byte of a read
+ * or an arm that is not upper-case A C G T is a mismatch; a read shorter than tag + arm fails).  The pair goes to the passing probe with the
+ * fewest mismatches in total; an exact tie for fewest is ambiguous (no probe; two rows with the same arms always tie), no passing probe is
+ * unassigned.  reads[p] = pairs assigned to probe p; unique_tags[p] = distinct tags among them, a tag being the ext_tag + lig_tag bases packed at 2
+ * bits each; a tag holding a byte that is not A C G T adds to reads, joins no group and is counted in tag_n.  With no tag bases unique_tags = reads.
+ * A pair whose two seed ranges hold more than 1,024 probes together is counted in overflow and assigned to nothing.
+ *   open:   packs the arms and builds the seed tables (ins_seq, mip_seq and the other members of mipgen_probe are not read).  MIPGEN_E_INVALID: NULL
+ *           pointers, n < 1, an empty arm or one beyond MIPGEN_MAX_OLIGO, a shortest arm below 12 bases, negative tag sizes or ext_tag + lig_tag > 16,
+ *           max_mismatches outside 0..2; MIPGEN_E_STATE: a session is open; MIPGEN_E_NOMEM: the tables and buffers against free device memory.
+ *           Every check comes before any allocation.
+ *   feed:   n_pairs read pairs, any number of times: the bytes of read i of a file are bytes[offsets[i] - offsets[0] ... offsets[i + 1] - offsets[0])
+ *           (offsets: n_pairs + 1 ascending entries, so a slice of a larger offset array can be passed with the bytes it starts at).  The call
+ *           returns when the device is done with the arrays.  MIPGEN_E_STATE without an open session.
+ *   finish: reads and unique_tags (n entries each, either may be NULL), the totals (may be NULL), and the session is closed whichever way the call
+ *           ends.  The result does not depend on how the pairs were cut into feed calls.
+ * The handle's resident batch, result windows, result arrays and model are exactly as they were after each of the calls; mipgen_accel_destroy
+ * releases an open session. */
+typedef struct mipgen_read_totals { int64_t pairs, assigned, ambiguous, unassigned, tag_n, overflow; } mipgen_read_totals;
+int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches);
+int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets);
+int mipgen_accel_reads_finish(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals);
+/* Capacity, in keys, of the (probe, tag) key buffer of the sessions opened after the call (0: the default, 2^26 or what free memory allows).  The
+ * buffer is sorted and made duplicate-free whenever it fills and grows only when more than half of it is distinct keys: a small value makes that
+ * happen often (tests); the counts do not depend on it. */
+int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys);
+/* The probe index of every pair of the LAST feed call (capacity >= its n_pairs): >= 0 assigned, -1 unassigned, -2 ambiguous, -3 overflow. */
+int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, int64_t capacity);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -522,7 +554,7 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * negative if unavailable.  which: 0 = dense SVR kernel, 1 = records + scoring kernels, 2 = records / logistic kernel,
  * 3 = replay + condense; 4 = genome pass of the last mipgen_accel_count_oligo_copies (always recorded);
  * 5 / 6 = the matrix-core SVR kernel / the feature kernel of the last mipgen_accel_score_candidates or mipgen_accel_score_probes call on a list
- * (>= 256 SVR candidates). */
+ * (>= 256 SVR candidates); 7 = k_read_assign summed over the feed calls since the last mipgen_accel_reads_open (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

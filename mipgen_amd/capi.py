@@ -71,6 +71,10 @@ class Probe(C.Structure):            # mipgen_probe: a probe given by its strand
                 ("ext_copy", C.c_int32), ("lig_copy", C.c_int32), ("lrc_index", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ReadTotals(C.Structure):       # mipgen_read_totals
+    _fields_ = [(n, C.c_int64) for n in ("pairs", "assigned", "ambiguous", "unassigned", "tag_n", "overflow")]
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -323,6 +327,14 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_score_probes.argtypes = [vp, C.POINTER(Probe), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.POINTER(CandidateInts)]
     lib.mipgen_accel_score_probes.restype = C.c_int
+    i64p_ = C.POINTER(C.c_int64)
+    lib.mipgen_accel_reads_open.argtypes = [vp, C.POINTER(Probe), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.mipgen_accel_reads_feed.argtypes = [vp, C.c_int64, C.c_void_p, i64p_, C.c_void_p, i64p_]
+    lib.mipgen_accel_reads_finish.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals)]
+    lib.mipgen_accel_reads_set_key_buffer.argtypes = [vp, C.c_int64]
+    lib.mipgen_accel_reads_last_assignment.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64]
+    for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment"):
+        getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
     lib.mipgen_accel_download_replay.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(Survivor), C.c_int64,
@@ -397,6 +409,8 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_window_uniqueness_end", "mipgen_accel_set_dynamic_skip", "mipgen_accel_skipped_candidates", "mipgen_accel_skip_state", "mipgen_accel_set_print_exact", "mipgen_accel_set_logistic_subruns",
     "mipgen_accel_rescore_survivors", "mipgen_accel_download_survivor_scores", "mipgen_accel_window_views", "mipgen_accel_synchronize",
     "mipgen_accel_train_svr", "mipgen_accel_svr_cv_folds", "mipgen_accel_cross_validate_svr", "mipgen_accel_score_probes",
+    "mipgen_accel_reads_open", "mipgen_accel_reads_feed", "mipgen_accel_reads_finish", "mipgen_accel_reads_set_key_buffer",
+    "mipgen_accel_reads_last_assignment",
 ]
 
 
@@ -784,6 +798,50 @@ class Accel:
             scores.ctypes.data_as(dp) if scores is not None else None,
             feats.ctypes.data_as(dp) if feats is not None else None, ints))
         return scores, feats, ints
+
+    def count_reads(self, arms: Sequence[tuple], ext_reads: Sequence[bytes], lig_reads: Sequence[bytes], tag_sizes: Tuple[int, int] = (5, 0),
+                    mismatches: int = 0, swap_reads: bool = False, chunks: int = 1, key_buffer: int = 0, want_assignment: bool = False):
+        """mipgen_accel_reads_open / _feed / _finish: reads and unique tags per probe from read pairs.  arms: (ext_seq, lig_seq) bytes per probe as a
+        MIP table prints them; ext_reads / lig_reads: the two reads of every pair (swap_reads: the first list holds the ligation reads); the pairs
+        are fed in `chunks` calls.  Returns (reads, unique_tags, totals dict[, probe index per pair])."""
+        if swap_reads:
+            ext_reads, lig_reads = lig_reads, ext_reads
+        assert len(ext_reads) == len(lig_reads)
+        n, n_pairs = len(arms), len(ext_reads)
+        arr = (Probe * max(n, 1))()
+        for i, q in enumerate(arms):
+            arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
+        i64p = C.POINTER(C.c_int64)
+
+        def pack(rs):
+            off = np.zeros(len(rs) + 1, dtype=np.int64)
+            np.cumsum([len(r) for r in rs], out=off[1:])
+            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
+
+        eb, eo = pack(ext_reads)
+        lb, lo = pack(lig_reads)
+        self._check(self.lib.mipgen_accel_reads_set_key_buffer(self.h, key_buffer))
+        self._check(self.lib.mipgen_accel_reads_open(self.h, arr, n, tag_sizes[0], tag_sizes[1], mismatches))
+        assignment = np.empty(n_pairs, dtype=np.int32)
+        try:
+            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                # (a slice of the offsets with the bytes it starts at: what the entry point takes)
+                self._check(self.lib.mipgen_accel_reads_feed(self.h, b - a, eb[eo[a]:].ctypes.data, eo[a:b + 1].ctypes.data_as(i64p),
+                                                             lb[lo[a]:].ctypes.data, lo[a:b + 1].ctypes.data_as(i64p)))
+                if want_assignment and b > a:
+                    self._check(self.lib.mipgen_accel_reads_last_assignment(self.h, assignment[a:b].ctypes.data_as(C.POINTER(C.c_int32)), b - a))
+        except Exception:
+            self.lib.mipgen_accel_reads_finish(self.h, None, None, None)
+            raise
+        finally:
+            self.lib.mipgen_accel_reads_set_key_buffer(self.h, 0)
+        reads = np.empty(n, dtype=np.int64)
+        unique = np.empty(n, dtype=np.int64)
+        tot = ReadTotals()
+        self._check(self.lib.mipgen_accel_reads_finish(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot)))
+        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
+        return (reads, unique, totals, assignment) if want_assignment else (reads, unique, totals)
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

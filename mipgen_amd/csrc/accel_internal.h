@@ -137,6 +137,8 @@ struct RescoreList {
     void release() { cands.release(); idx.release(); vals.release(); count.release(); }
 };
 
+struct ReadsSession;                  // accel_reads.hip
+
 struct mipgen_accel {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -248,6 +250,10 @@ struct mipgen_accel {
     DevBuf<double> lrc_out;
     DevBuf<int64_t> lrc_offs;
     DevBuf<int32_t> lrc_lens, lrc_denoms;
+    // reads and unique tags per probe (accel_reads.hip): the open session owns its buffers; nothing else of the handle is touched by it
+    ReadsSession* reads = nullptr;
+    int64_t reads_key_cap = 0;       // mipgen_accel_reads_set_key_buffer (0: default)
+    double reads_assign_ms = -1.0;   // k_read_assign over the feed calls of the last session (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;
@@ -310,4 +316,5 @@ int mipgen_pick_sv_split(int n_tiles, int n_sv, int n_cu);       // accel_tiles.
 int mipgen_ensure_events(mipgen_accel* h);
 int mipgen_ensure_tiles(mipgen_accel* h, int32_t method);
 int mipgen_pb_check(mipgen_accel* h);                            // accel_score.hip
+void mipgen_reads_release(mipgen_accel* h);                      // accel_reads.hip: closes an open read-counting session
 }

@@ -1,0 +1,325 @@
+// accel_reads.hip — reads and unique tags per probe from smMIP read pairs behind the C ABI: mipgen_accel_reads_open / _feed / _finish.
+// A session owns every buffer it uses (ReadsSession); of the handle it takes the device and the stream, nothing else.
+#include "accel_internal.h"
+
+struct SeedTableBufs {
+    DevBuf<uint32_t> slots, start;
+    DevBuf<uint64_t> keys;
+    DevBuf<int32_t> probes;
+    SeedTable view{};
+    void release() { slots.release(); start.release(); keys.release(); probes.release(); }
+};
+
+struct ReadsSession {
+    ReadsParams P{};
+    DevBuf<ReadProbe> probes;
+    SeedTableBufs ext_seeds, lig_seeds;
+    DevBuf<uint8_t> ext_bytes, lig_bytes;                   // the pairs of the current feed call
+    DevBuf<int64_t> ext_off, lig_off;
+    DevBuf<int32_t> assign;
+    int64_t last_pairs = 0;
+    DevBuf<unsigned long long> reads, unique;
+    DevBuf<uint64_t> keys, keys_alt;
+    DevBuf<char> sort_temp;
+    DevBuf<ReadsCounters> ctr;
+    int64_t key_cap = 0;                                     // entries of `keys` in use as capacity
+    int64_t key_ub = 0;                                      // no more keys than this are in the buffer (every pair fed since the last sort-unique counted)
+    int end_bit = 64;                                        // key bits that can be set
+    void release()
+    {
+        probes.release(); ext_seeds.release(); lig_seeds.release(); ext_bytes.release(); lig_bytes.release(); ext_off.release(); lig_off.release();
+        assign.release(); reads.release(); unique.release(); keys.release(); keys_alt.release(); sort_temp.release(); ctr.release();
+    }
+};
+
+static const int64_t READS_KEY_CAP_DEFAULT = (int64_t)1 << 26, READS_KEY_CAP_MAX = (int64_t)1 << 30;
+
+// an arm as bit planes (reads_common.h); rc: of its reverse complement
+static void pack_arm(const char* s, int len, bool rc, uint64_t* p0, uint64_t* p1, uint64_t* bad)
+{
+    *p0 = *p1 = *bad = 0;
+    for (int i = 0; i < len; i++) {
+        uint32_t c = reads_base_code((uint8_t)(rc ? s[len - 1 - i] : s[i]));
+        if (rc && c < 4u) c = 3u - c;
+        *p0 |= (uint64_t)(c & 1u) << i; *p1 |= (uint64_t)((c >> 1) & 1u) << i; *bad |= (uint64_t)(c >> 2) << i;
+    }
+}
+
+struct HostSeedTable { std::vector<uint32_t> slots, start; std::vector<uint64_t> keys; std::vector<int32_t> probes; };
+
+// (key, probe) of every probe whose seed holds A C G T only -> distinct keys ascending, the probes of each ascending, the hash in front
+static void build_seed_table(std::vector<std::pair<uint64_t, int32_t>>& kp, HostSeedTable& T)
+{
+    std::sort(kp.begin(), kp.end());
+    T.start.push_back(0);
+    for (size_t i = 0; i < kp.size(); i++) {
+        if (i == 0 || kp[i].first != kp[i - 1].first) { if (i) T.start.push_back((uint32_t)i); T.keys.push_back(kp[i].first); }
+        T.probes.push_back(kp[i].second);
+    }
+    if (!kp.empty()) T.start.push_back((uint32_t)kp.size());
+    size_t n_slots = 16;
+    while (n_slots < 2 * T.keys.size()) n_slots *= 2;
+    T.slots.assign(n_slots, 0u);
+    for (size_t k = 0; k < T.keys.size(); k++) {
+        uint32_t s = reads_hash(T.keys[k]) & (uint32_t)(n_slots - 1);
+        while (T.slots[s]) s = (s + 1) & (uint32_t)(n_slots - 1);
+        T.slots[s] = (uint32_t)k + 1;
+    }
+    if (T.keys.empty()) { T.keys.push_back(0); T.probes.push_back(0); T.start.push_back(0); }      // (never read: every slot is empty)
+}
+
+static int upload_seed_table(mipgen_accel* h, const HostSeedTable& T, SeedTableBufs& B)
+{
+    if (B.slots.reserve(T.slots.size()) || B.start.reserve(T.start.size()) || B.keys.reserve(T.keys.size()) || B.probes.reserve(T.probes.size())) return MIPGEN_E_NOMEM;
+    HIP_TRY(hipMemcpyAsync(B.slots.p, T.slots.data(), T.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(B.start.p, T.start.data(), T.start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(B.keys.p, T.keys.data(), T.keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(B.probes.p, T.probes.data(), T.probes.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    B.view = {B.slots.p, B.keys.p, B.start.p, B.probes.p, (uint32_t)(T.slots.size() - 1)};
+    return MIPGEN_OK;
+}
+
+static int free_device_bytes(size_t* free_b)
+{
+    size_t total_b = 0;
+    HIP_TRY(hipMemGetInfo(free_b, &total_b));
+    return MIPGEN_OK;
+}
+
+// keys[0, n) of the session sorted and made duplicate-free; key_ub becomes their exact number
+static int sort_unique_keys(mipgen_accel* h, ReadsSession* S)
+{
+    unsigned long long n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, &S->ctr.p->n_keys, sizeof n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((int64_t)n > S->key_cap) return fail(MIPGEN_E_STATE, "read counter: %llu keys in a buffer of %lld", n, (long long)S->key_cap);
+    if (n > 0) {
+        size_t temp_bytes = 0;
+        HIP_TRY(mipgen_reads_sort_unique(h->stream, nullptr, &temp_bytes, S->keys.p, S->keys_alt.p, (int64_t)n, S->end_bit, &S->ctr.p->n_keys));
+        if (S->sort_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
+        temp_bytes = S->sort_temp.cap;
+        HIP_TRY(mipgen_reads_sort_unique(h->stream, S->sort_temp.p, &temp_bytes, S->keys.p, S->keys_alt.p, (int64_t)n, S->end_bit, &S->ctr.p->n_keys));
+        HIP_TRY(hipMemcpyAsync(&n, &S->ctr.p->n_keys, sizeof n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    S->key_ub = (int64_t)n;
+    return MIPGEN_OK;
+}
+
+// room for `want` more keys (at least 1): sort-unique what is there, and double the buffer while more than half of it is distinct keys
+static int make_key_room(mipgen_accel* h, ReadsSession* S, int64_t want, int64_t* room)
+{
+    if (S->key_cap - S->key_ub < std::min(want, std::max<int64_t>(S->key_cap / 2, 1))) {
+        if (int rc = sort_unique_keys(h, S)) return rc;
+        while (S->key_cap - S->key_ub < std::max<int64_t>(S->key_cap / 2, 1)) {
+            const int64_t cap = S->key_cap * 2;
+            size_t free_b = 0;
+            if (int rc = free_device_bytes(&free_b)) return rc;
+            if (cap > READS_KEY_CAP_MAX || (size_t)cap * 16 + ((size_t)64 << 20) > free_b)
+                return fail(MIPGEN_E_NOMEM, "read counter: %lld distinct (probe, tag) keys do not fit device memory (%zu MiB free)", (long long)S->key_ub, free_b >> 20);
+            DevBuf<uint64_t> grown;
+            if (grown.reserve((size_t)cap)) return MIPGEN_E_NOMEM;
+            if (S->key_ub) HIP_TRY(hipMemcpyAsync(grown.p, S->keys.p, (size_t)S->key_ub * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            S->keys.release(); S->keys_alt.release();
+            S->keys = grown;
+            if (S->keys_alt.reserve((size_t)cap)) return MIPGEN_E_NOMEM;
+            S->key_cap = cap;
+        }
+    }
+    *room = S->key_cap - S->key_ub;
+    return MIPGEN_OK;
+}
+
+extern "C" {
+
+void mipgen_reads_release(mipgen_accel* h)
+{
+    if (!h->reads) return;
+    (void)hipStreamSynchronize(h->stream);
+    h->reads->release();
+    delete h->reads;
+    h->reads = nullptr;
+}
+
+int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys)
+{
+    if (!h || n_keys < 0 || n_keys > READS_KEY_CAP_MAX) return fail(MIPGEN_E_INVALID, "bad arguments");
+    h->reads_key_cap = n_keys;
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches)
+{
+    if (!h || !probes || n < 1) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (ext_tag < 0 || lig_tag < 0 || ext_tag + lig_tag > READS_MAX_TAG) return fail(MIPGEN_E_INVALID, "tag sizes %d,%d: at most %d tag bases in all", ext_tag, lig_tag, READS_MAX_TAG);
+    if (max_mismatches < 0 || max_mismatches > 2) return fail(MIPGEN_E_INVALID, "max_mismatches %d outside 0..2", max_mismatches);
+    size_t shortest = MIPGEN_MAX_OLIGO;
+    for (int i = 0; i < n; i++) {
+        const mipgen_probe& q = probes[i];
+        if (!q.ext_seq || !q.lig_seq) return fail(MIPGEN_E_INVALID, "probe %d: %s sequence is NULL", i, !q.ext_seq ? "extension arm" : "ligation arm");
+        const size_t e = strlen(q.ext_seq), l = strlen(q.lig_seq);
+        if (e < MIPGEN_MIN_OLIGO || l < MIPGEN_MIN_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: empty %s arm", i, e < MIPGEN_MIN_OLIGO ? "extension" : "ligation");
+        if (e > MIPGEN_MAX_OLIGO || l > MIPGEN_MAX_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: arm of %zu bases (at most %d)", i, std::max(e, l), MIPGEN_MAX_OLIGO);
+        shortest = std::min(shortest, std::min(e, l));
+    }
+    if (shortest < 12) return fail(MIPGEN_E_INVALID, "the shortest arm of the table has %zu bases: a seed of fewer than 12 bases is refused", shortest);
+    if (h->reads) return fail(MIPGEN_E_STATE, "a read-counting session is open: mipgen_accel_reads_finish closes it");
+    const int S = (int)std::min<size_t>(shortest, READS_MAX_SEED);
+
+    // the tables, on the host
+    std::vector<ReadProbe> packed((size_t)n);
+    std::vector<std::pair<uint64_t, int32_t>> ekp, lkp;
+    const uint64_t seed_mask = reads_len_mask(S);
+    for (int i = 0; i < n; i++) {
+        ReadProbe& r = packed[(size_t)i];
+        memset(&r, 0, sizeof r);
+        r.e_len = (int32_t)strlen(probes[i].ext_seq); r.l_len = (int32_t)strlen(probes[i].lig_seq);
+        pack_arm(probes[i].ext_seq, r.e_len, false, &r.e0, &r.e1, &r.ebad);
+        pack_arm(probes[i].lig_seq, r.l_len, true, &r.l0, &r.l1, &r.lbad);
+        if ((r.ebad & seed_mask) == 0) ekp.emplace_back(reads_seed_key(r.e0, r.e1, seed_mask), i);
+        if ((r.lbad & seed_mask) == 0) lkp.emplace_back(reads_seed_key(r.l0, r.l1, seed_mask), i);
+    }
+    HostSeedTable TE, TL;
+    build_seed_table(ekp, TE);
+    build_seed_table(lkp, TL);
+
+    HIP_TRY(hipSetDevice(h->device));
+    // the budget: tables + counters + two key buffers, against free device memory
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    const bool tags = ext_tag + lig_tag > 0;
+    int64_t key_cap = !tags ? 0 : h->reads_key_cap > 0 ? h->reads_key_cap : READS_KEY_CAP_DEFAULT;
+    const size_t fixed = (size_t)n * (sizeof(ReadProbe) + 16 + 2 * 4) + (TE.slots.size() + TL.slots.size()) * 4 + (TE.keys.size() + TL.keys.size()) * 12 + ((size_t)64 << 20);
+    if (tags && h->reads_key_cap <= 0)
+        while (key_cap > 1024 && fixed + (size_t)key_cap * 16 > free_b / 2) key_cap /= 2;      // the default gives way to what is free; half is left for the reads
+    if (fixed + (size_t)key_cap * 16 > free_b)
+        return fail(MIPGEN_E_NOMEM, "read counter: tables of %d probes and %lld keys need %zu MiB of device memory, %zu MiB are free", n, (long long)key_cap,
+                    (fixed + (size_t)key_cap * 16) >> 20, free_b >> 20);
+
+    ReadsSession* S_ = new ReadsSession;
+    h->reads = S_;
+    auto give_up = [&](int rc) { mipgen_reads_release(h); return rc; };
+    S_->P = {ext_tag, lig_tag, max_mismatches, S, seed_mask, n, 0};
+    S_->key_cap = key_cap;
+    int probe_bits = 1;
+    while (probe_bits < 32 && ((int64_t)1 << probe_bits) < n) probe_bits++;
+    S_->end_bit = 32 + probe_bits;
+    if (S_->probes.reserve((size_t)n) || S_->reads.reserve((size_t)n) || S_->unique.reserve((size_t)n) || S_->ctr.reserve(1) ||
+        (key_cap && (S_->keys.reserve((size_t)key_cap) || S_->keys_alt.reserve((size_t)key_cap))))
+        return give_up(MIPGEN_E_NOMEM);
+    int rc = upload_seed_table(h, TE, S_->ext_seeds);
+    if (rc == MIPGEN_OK) rc = upload_seed_table(h, TL, S_->lig_seeds);
+    hipError_t e = hipSuccess;
+    if (rc == MIPGEN_OK) e = hipMemcpyAsync(S_->probes.p, packed.data(), (size_t)n * sizeof(ReadProbe), hipMemcpyHostToDevice, h->stream);
+    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->reads.p, 0, (size_t)n * sizeof(unsigned long long), h->stream);
+    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->unique.p, 0, (size_t)n * sizeof(unsigned long long), h->stream);
+    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->ctr.p, 0, sizeof(ReadsCounters), h->stream);
+    const hipError_t e2 = hipStreamSynchronize(h->stream);                 // (the host tables above live until here)
+    if (rc == MIPGEN_OK && e == hipSuccess) e = e2;
+    if (rc == MIPGEN_OK && e != hipSuccess) rc = fail(MIPGEN_E_HIP, "mipgen_accel_reads_open: %s", hipGetErrorString(e));
+    if (rc != MIPGEN_OK) return give_up(rc);
+    h->reads_assign_ms = 0.0;
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets)
+{
+    if (!h || n_pairs < 0 || (n_pairs > 0 && (!ext_bytes || !ext_offsets || !lig_bytes || !lig_offsets))) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (n_pairs > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld pairs in one call (at most 2^31 - 1)", (long long)n_pairs);
+    ReadsSession* S = h->reads;
+    S->last_pairs = 0;
+    if (n_pairs == 0) return MIPGEN_OK;
+    // the kernel trusts the offsets: they are checked here
+    for (int f = 0; f < 2; f++) {
+        const int64_t* off = f ? lig_offsets : ext_offsets;
+        if (off[0] < 0) return fail(MIPGEN_E_INVALID, "%s offsets: negative", f ? "ligation" : "extension");
+        for (int64_t i = 0; i < n_pairs; i++)
+            if (off[i + 1] < off[i]) return fail(MIPGEN_E_INVALID, "%s offsets: entry %lld below entry %lld", f ? "ligation" : "extension", (long long)(i + 1), (long long)i);
+    }
+    const size_t eb = (size_t)(ext_offsets[n_pairs] - ext_offsets[0]), lb = (size_t)(lig_offsets[n_pairs] - lig_offsets[0]);
+    HIP_TRY(hipSetDevice(h->device));
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    const size_t have = S->ext_bytes.cap + S->lig_bytes.cap + (S->ext_off.cap + S->lig_off.cap) * 8 + S->assign.cap * 4;
+    const size_t need = eb + lb + 2 * (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 4;
+    if (need + need / 8 + ((size_t)64 << 20) > free_b + have)
+        return fail(MIPGEN_E_NOMEM, "read counter: a chunk of %lld pairs needs %zu MiB of device memory, %zu MiB are free (feed fewer pairs per call)", (long long)n_pairs,
+                    need >> 20, (free_b + have) >> 20);
+    // (+ 8: the kernel fetches the bases as aligned 32-bit words, up to 5 bytes beyond the last read)
+    if (S->ext_bytes.reserve(eb + 8) || S->lig_bytes.reserve(lb + 8) || S->ext_off.reserve((size_t)n_pairs + 1) || S->lig_off.reserve((size_t)n_pairs + 1) ||
+        S->assign.reserve((size_t)n_pairs))
+        return MIPGEN_E_NOMEM;
+    struct IdleOnExit { hipStream_t s; ~IdleOnExit() { (void)hipStreamSynchronize(s); } } idle_on_exit{h->stream};      // the caller's arrays are free when the call returns
+    if (eb) HIP_TRY(hipMemcpyAsync(S->ext_bytes.p, ext_bytes, eb, hipMemcpyHostToDevice, h->stream));
+    if (lb) HIP_TRY(hipMemcpyAsync(S->lig_bytes.p, lig_bytes, lb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(S->ext_off.p, ext_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(S->lig_off.p, lig_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    const bool tags = S->P.te + S->P.tl > 0;
+    std::vector<hipEvent_t> ev;
+    int rc = MIPGEN_OK;
+    for (int64_t p0 = 0; p0 < n_pairs && rc == MIPGEN_OK;) {
+        int64_t c = n_pairs - p0;
+        if (tags) { if ((rc = make_key_room(h, S, c, &c))) break; c = std::min(c, n_pairs - p0); }
+        hipEvent_t a = nullptr, b = nullptr;
+        if (h->timing && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ev.push_back(a); ev.push_back(b); (void)hipEventRecord(a, h->stream); }
+        const hipError_t e = mipgen_launch_read_assign(h->stream, &S->P, S->probes.p, &S->ext_seeds.view, &S->lig_seeds.view, p0, c, S->ext_bytes.p, S->ext_off.p, ext_offsets[0],
+                                                       S->lig_bytes.p, S->lig_off.p, lig_offsets[0], S->assign.p, S->reads.p, S->keys.p, S->key_cap, S->ctr.p);
+        if (e != hipSuccess) rc = fail(MIPGEN_E_HIP, "k_read_assign: %s", hipGetErrorString(e));
+        if (b) (void)hipEventRecord(b, h->stream);
+        if (tags) S->key_ub += c;
+        p0 += c;
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (rc == MIPGEN_OK && es != hipSuccess) rc = fail(MIPGEN_E_HIP, "mipgen_accel_reads_feed: %s", hipGetErrorString(es));
+    for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+        float ms = 0.f;
+        if (rc == MIPGEN_OK && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) h->reads_assign_ms += ms;
+    }
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (rc == MIPGEN_OK) S->last_pairs = n_pairs;
+    return rc;
+}
+
+int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, int64_t capacity)
+{
+    if (!h || !probe_index) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (capacity < h->reads->last_pairs) return fail(MIPGEN_E_INVALID, "capacity %lld < %lld pairs", (long long)capacity, (long long)h->reads->last_pairs);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->reads->last_pairs) HIP_TRY(hipMemcpyAsync(probe_index, h->reads->assign.p, (size_t)h->reads->last_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MIPGEN_OK;
+}
+
+static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n = (size_t)S->P.n_probes;
+    const bool tags = S->P.te + S->P.tl > 0;
+    if (tags) {
+        if (int rc = sort_unique_keys(h, S)) return rc;
+        HIP_TRY(mipgen_launch_reads_histogram(h->stream, S->keys.p, S->key_ub, S->unique.p));
+    }
+    ReadsCounters c;
+    HIP_TRY(hipMemcpyAsync(&c, S->ctr.p, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are downloaded in place");
+    if (reads) HIP_TRY(hipMemcpyAsync(reads, S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    if (unique_tags) HIP_TRY(hipMemcpyAsync(unique_tags, tags ? S->unique.p : S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (c.keys_lost) return fail(MIPGEN_E_STATE, "read counter: %llu keys did not fit the key buffer", c.keys_lost);
+    if (totals) *totals = {(int64_t)c.pairs, (int64_t)c.assigned, (int64_t)c.ambiguous, (int64_t)c.unassigned, (int64_t)c.tag_n, (int64_t)c.overflow};
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_finish(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    const int rc = finish_impl(h, h->reads, reads, unique_tags, totals);
+    mipgen_reads_release(h);
+    return rc;
+}
+
+}  // extern "C"

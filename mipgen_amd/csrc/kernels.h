@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "reads_common.h"
 
 struct HostConsts;                   // logistic_device.h: crosses the boundary by pointer only
 struct LrcMers { int8_t k[MIPGEN_N_LRC], code[MIPGEN_N_LRC], rc[MIPGEN_N_LRC]; };   // per mer: length, base-4 code, code of its reverse complement (-1: palindrome)
@@ -108,4 +109,10 @@ hipError_t mipgen_launch_window_verify(hipStream_t st, const char* G, int64_t gl
 hipError_t mipgen_launch_window_flags(hipStream_t st, const char* q, int64_t total, const int32_t* sizes, int n_sizes, int k, const uint64_t* keys, uint64_t cap_mask,
                                       const unsigned int* counts, const uint16_t* dist_bad, const uint16_t* dist_end, const unsigned int* ctr, uint8_t* unmap,
                                       const int64_t* roff, int n_regions, const int32_t* bounds, uint8_t* any);
+// kernels_reads.hip (pairs [pair0, pair0 + n_pairs) of the uploaded chunk; assign is indexed by the pair's position in the chunk)
+hipError_t mipgen_launch_read_assign(hipStream_t, const ReadsParams*, const ReadProbe* probes, const SeedTable* ext_seeds, const SeedTable* lig_seeds, int64_t pair0,
+                                     int64_t n_pairs, const uint8_t* ext_bytes, const int64_t* ext_off, int64_t ext_base, const uint8_t* lig_bytes, const int64_t* lig_off,
+                                     int64_t lig_base, int32_t* assign, unsigned long long* reads, uint64_t* keys, int64_t key_cap, ReadsCounters* ctr);
+hipError_t mipgen_launch_reads_histogram(hipStream_t, const uint64_t* keys, int64_t n, unsigned long long* unique);
+hipError_t mipgen_reads_sort_unique(hipStream_t, void* temp, size_t* temp_bytes, uint64_t* keys, uint64_t* alt, int64_t n, int end_bit, unsigned long long* n_out);
 }

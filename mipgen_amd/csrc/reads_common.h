@@ -1,0 +1,59 @@
+// reads_common.h — what kernels_reads.hip and accel_reads.hip share of the read counter: the packed probe arms, the seed tables, the
+// base code and the hash of a seed key.  The host packs the arms and builds the tables with the same functions the kernel reads them with.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define READS_MAX_SEED 32            // bases of a seed: 2 bits each in a 64-bit key
+#define READS_MAX_CAND 1024          // probes compared per pair (both seed ranges together); a pair above it is counted in `overflow`
+#define READS_MAX_TAG 16             // tag bases of a pair: 2 bits each in the low word of a 64-bit key
+
+#define READS_UNASSIGNED (-1)
+#define READS_AMBIGUOUS (-2)
+#define READS_OVERFLOW (-3)
+
+// An arm of up to 64 bases as three bit planes, base i at bit i: low and high bit of its code (A 0, C 1, G 2, T 3) and "not one of upper-case A C G T".
+// A mismatch count is then one popcount: ((x0 ^ a0) | (x1 ^ a1) | xbad | abad) & length mask.
+struct ReadProbe {                    // 64 bytes: one cache line per probe
+    uint64_t e0, e1, ebad;            // E = ext_probe_sequence
+    uint64_t l0, l1, lbad;            // revcomp(L), L = lig_probe_sequence
+    int32_t e_len, l_len;
+    uint64_t pad;
+};
+
+// key -> range of probe indices: an open-addressing hash of the DISTINCT seed keys (slot = index of the key + 1, 0 = empty; linear probing, load <= 1/2)
+// in front of the sorted keys; probes[start[k], start[k + 1]) are the probes (ascending) whose seed is keys[k]
+struct SeedTable {
+    const uint32_t* slots;
+    const uint64_t* keys;
+    const uint32_t* start;
+    const int32_t* probes;
+    uint32_t mask;                    // slots - 1 (a power of two)
+};
+
+struct ReadsParams {
+    int32_t te, tl;                   // tag bases at the head of the extension / ligation read
+    int32_t m;                        // mismatches allowed per arm
+    int32_t S;                        // seed length
+    uint64_t seed_mask;               // low S bits
+    int32_t n_probes, pad;
+};
+
+struct ReadsCounters { unsigned long long pairs, assigned, ambiguous, unassigned, tag_n, overflow, n_keys, keys_lost; };
+
+__host__ __device__ static inline uint32_t reads_base_code(uint32_t c)     // 0..3, or 4 for every other byte (lower case included)
+{
+    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+}
+
+__host__ __device__ static inline uint64_t reads_len_mask(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
+
+__host__ __device__ static inline uint64_t reads_seed_key(uint64_t p0, uint64_t p1, uint64_t seed_mask) { return (p0 & seed_mask) | ((p1 & seed_mask) << 32); }
+
+__host__ __device__ static inline uint32_t reads_hash(uint64_t k)           // splitmix64's finaliser
+{
+    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27; k *= 0x94d049bb133111ebull;
+    k ^= k >> 31;
+    return (uint32_t)k;
+}

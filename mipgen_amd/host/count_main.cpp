@@ -1,0 +1,220 @@
+// mipgen_count — the "measure" link of design -> measure -> featurize -> cross-validate -> train -> design: reads and unique molecular tags per
+// probe of MIP tables from the FASTQ files of a capture, on the device through mipgen_accel_reads_open / _feed / _finish.  No
+// aligner: a smMIP read pair starts, after its tag, with the probe's own arm sequences.
+//
+//   mipgen_count [-tag_sizes 5,0] [-mismatches 0] [-swap_reads] [-label tags|reads|log10tags] -o counts.tsv [-labels labels.tsv]
+//                -reads ext.fq lig.fq  mip_table [mip_table ...]
+//
+//   -reads     the extension-read file and the ligation-read file (plain FASTQ, four lines per record, pairs in the same order);
+//              -swap_reads: the first file holds the ligation reads
+//   -o         "mip_key <tab> mip_name <tab> reads <tab> unique_tags" under a header line of those words, one row per probe in table order
+//   -labels    "mip_key <tab> value", the file `mipgen_rescore -features ... -labels` reads: unique_tags (tags, the default), reads, or
+//              log10(unique_tags + 1) printed with %.17g (log10tags)
+//   stderr     "mipgen_count: pairs P assigned A ambiguous B unassigned U tag_n T overflow O"
+// Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
+// device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
+// second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+
+#include "mip_table.hpp"
+
+static const char* PROG = "mipgen_count";
+static const int64_t CHUNK_PAIRS = (int64_t)1 << 19;
+
+static int usage(const std::string& msg)
+{
+    if (!msg.empty()) fprintf(stderr, "mipgen_count: %s\n", msg.c_str());
+    fprintf(stderr,
+            "Usage: mipgen_count [options] -o counts.tsv -reads ext.fq lig.fq mip_table [mip_table ...]\n"
+            "-tag_sizes e,l : molecular tag bases at the head of the extension / ligation read (default 5,0; at most 16 in all)\n"
+            "-mismatches n : substitutions allowed per arm, 0..2 (default 0)\n"
+            "-swap_reads : the first file of -reads holds the ligation reads\n"
+            "-o file : mip_key, mip_name, reads, unique_tags per probe\n"
+            "-labels file : mip_key <tab> value for mipgen_rescore -labels; -label tags|reads|log10tags : the value (default tags)\n");
+    return 1;
+}
+
+// one FASTQ file read record by record; an error names file and line
+struct Fastq {
+    std::string path;
+    FILE* fp = nullptr;
+    char* line = nullptr;
+    size_t cap = 0;
+    long lineno = 0;
+    ~Fastq() { if (fp) fclose(fp); free(line); }
+    bool open() { fp = fopen(path.c_str(), "r"); lineno = 0; return fp != nullptr; }
+    // a line without its end-of-line bytes: its length, or -1 at the end of the file
+    ssize_t get()
+    {
+        ssize_t n = getline(&line, &cap, fp);
+        if (n < 0) return -1;
+        lineno++;
+        while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r')) n--;
+        return n;
+    }
+    // 1: a record, its sequence appended to *seq (NULL: checked only); 0: end of file; -1: malformed (message printed)
+    int next(std::string* seq)
+    {
+        ssize_t n = get();
+        if (n < 0) return 0;
+        auto bad = [&](const char* what) { fprintf(stderr, "%s: %s:%ld: malformed FASTQ record (%s)\n", PROG, path.c_str(), lineno, what); return -1; };
+        if (n == 0 || line[0] != '@') return bad("the header line does not start with '@'");
+        if ((n = get()) < 0) { lineno++; return bad("the file ends after a header line"); }
+        const ssize_t len = n;
+        if (seq) seq->append(line, (size_t)len);
+        if ((n = get()) < 0) { lineno++; return bad("the file ends after a sequence line"); }
+        if (n == 0 || line[0] != '+') return bad("the third line of a record does not start with '+'");
+        if ((n = get()) < 0) { lineno++; return bad("the file ends before the quality line"); }
+        if (n != len) return bad("sequence and quality differ in length");
+        return 1;
+    }
+};
+
+struct Chunk {
+    std::string ext, lig;
+    std::vector<int64_t> ext_off, lig_off;
+    int64_t n = 0;
+    bool last = false, failed = false;
+};
+
+int main(int argc, char** argv)
+{
+    int te = 5, tl = 0, mism = 0;
+    bool swap = false;
+    std::string out_path, label_path, label_kind = "tags", reads_a, reads_b;
+    std::vector<std::string> inputs;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a.empty() || a[0] != '-') { inputs.push_back(a); continue; }
+        if (a == "-swap_reads") { swap = true; continue; }
+        if (a == "-reads") {
+            if (i + 2 > argc - 1) return usage("option -reads needs two files");
+            reads_a = argv[++i]; reads_b = argv[++i];
+            continue;
+        }
+        if (i + 1 >= argc) return usage("option " + a + " needs a value");
+        const std::string v = argv[++i];
+        long iv;
+        if (a == "-tag_sizes") {
+            const size_t c = v.find(',');
+            long e, l;
+            if (c == std::string::npos || !svr_parse_int(v.substr(0, c).c_str(), &e) || !svr_parse_int(v.substr(c + 1).c_str(), &l) || e < 0 || l < 0 || e + l > 16)
+                return usage("-tag_sizes takes two sizes e,l of at most 16 bases in all");
+            te = (int)e; tl = (int)l;
+        } else if (a == "-mismatches") { if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 2) return usage("-mismatches must be 0, 1 or 2"); mism = (int)iv; }
+        else if (a == "-label") { if (v != "tags" && v != "reads" && v != "log10tags") return usage("-label must be tags, reads or log10tags"); label_kind = v; }
+        else if (a == "-o") out_path = v;
+        else if (a == "-labels") label_path = v;
+        else return usage("unknown option: " + a);
+    }
+    if (inputs.empty()) return usage("no MIP table");
+    if (out_path.empty()) return usage("no output: -o counts.tsv is missing");
+    if (reads_a.empty() || reads_b.empty()) return usage("no reads: -reads ext.fq lig.fq is missing");
+    for (const std::string* p : {&reads_a, &reads_b})
+        if (p->size() >= 3 && p->compare(p->size() - 3, 3, ".gz") == 0) return usage(*p + ": compressed FASTQ is not read (plain FASTQ only: decompress it first)");
+
+    // ---- everything is read and checked before the device is opened ----
+    std::vector<Table> tables(inputs.size());
+    for (size_t k = 0; k < inputs.size(); k++) if (!read_table(PROG, inputs[k], 0, tables[k])) return 1;
+    std::vector<mipgen_probe> probes;
+    std::vector<const std::vector<std::string>*> rows;
+    size_t shortest = MIPGEN_MAX_OLIGO;
+    for (const Table& t : tables)
+        for (const auto& r : t.rows) {
+            mipgen_probe q;
+            memset(&q, 0, sizeof q);
+            q.ext_seq = r[COL_EXT_SEQ].c_str(); q.lig_seq = r[COL_LIG_SEQ].c_str(); q.ins_seq = r[COL_INS_SEQ].c_str(); q.mip_seq = r[COL_MIP_SEQ].c_str();
+            q.lrc_index = -1;
+            probes.push_back(q); rows.push_back(&r);
+            shortest = std::min(shortest, std::min(r[COL_EXT_SEQ].size(), r[COL_LIG_SEQ].size()));
+        }
+    if (probes.empty()) { fprintf(stderr, "%s: the tables hold no probe\n", PROG); return 1; }
+    if (probes.size() > (size_t)INT32_MAX) { fprintf(stderr, "%s: too many probes\n", PROG); return 1; }
+    if (shortest < 12) { fprintf(stderr, "%s: the shortest arm of the tables has %zu bases: a seed of fewer than 12 bases is refused\n", PROG, shortest); return 1; }
+    Fastq fe, fl;
+    fe.path = swap ? reads_b : reads_a; fl.path = swap ? reads_a : reads_b;
+    for (Fastq* f : {&fe, &fl}) if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; }
+    int64_t n_records = 0;
+    for (;;) {
+        const int a = fe.next(nullptr), b = fl.next(nullptr);
+        if (a < 0 || b < 0) return 1;
+        if (a != b) {
+            fprintf(stderr, "%s: %s holds %s records than %s (%lld pairs read)\n", PROG, fe.path.c_str(), a ? "more" : "fewer", fl.path.c_str(), (long long)n_records);
+            return 1;
+        }
+        if (!a) break;
+        n_records++;
+    }
+    for (Fastq* f : {&fe, &fl}) { fclose(f->fp); f->fp = nullptr; if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; } }
+
+    // ---- the device ----
+    mipgen_accel* h = nullptr;
+    if (svr_tool_handle(&h) != MIPGEN_OK) { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); return 1; }
+    auto die = [&]() { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); mipgen_accel_destroy(h); return 1; };
+    if (mipgen_accel_reads_open(h, probes.data(), (int32_t)probes.size(), te, tl, mism) != MIPGEN_OK) return die();
+
+    // two chunks: the reader thread fills one while the device works on the other
+    Chunk chunks[2];
+    std::mutex mu;
+    std::condition_variable cv;
+    bool full[2] = {false, false}, stop = false;
+    std::thread reader([&]() {
+        for (int k = 0;; k ^= 1) {
+            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !full[k] || stop; }); if (stop) return; }
+            Chunk& c = chunks[k];
+            c.ext.clear(); c.lig.clear(); c.ext_off.assign(1, 0); c.lig_off.assign(1, 0); c.n = 0; c.last = false;
+            while (c.n < CHUNK_PAIRS) {
+                const int a = fe.next(&c.ext), b = fl.next(&c.lig);
+                if (a < 0 || b < 0 || a != b) { c.failed = true; break; }          // (the files changed since they were checked)
+                if (!a) { c.last = true; break; }
+                c.ext_off.push_back((int64_t)c.ext.size()); c.lig_off.push_back((int64_t)c.lig.size());
+                c.n++;
+            }
+            const bool done = c.last || c.failed;
+            { std::lock_guard<std::mutex> lk(mu); full[k] = true; }
+            cv.notify_all();
+            if (done) return;
+        }
+    });
+    int rc = 0;
+    for (int k = 0;; k ^= 1) {
+        { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return full[k]; }); }
+        Chunk& c = chunks[k];
+        if (c.failed) { fprintf(stderr, "%s: the FASTQ files changed while they were read\n", PROG); rc = 1; }
+        else if (c.n > 0 && mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data()) != MIPGEN_OK) {
+            fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); rc = 1;
+        }
+        const bool done = rc != 0 || c.last;
+        { std::lock_guard<std::mutex> lk(mu); full[k] = false; if (done) stop = true; }
+        cv.notify_all();
+        if (done) break;
+    }
+    reader.join();
+    if (rc) { mipgen_accel_destroy(h); return 1; }
+    std::vector<int64_t> reads(probes.size()), unique(probes.size());
+    mipgen_read_totals tot;
+    if (mipgen_accel_reads_finish(h, reads.data(), unique.data(), &tot) != MIPGEN_OK) return die();
+    mipgen_accel_destroy(h);
+
+    FILE* out = fopen(out_path.c_str(), "w");
+    if (!out) { fprintf(stderr, "%s: can't write %s\n", PROG, out_path.c_str()); return 1; }
+    fprintf(out, "mip_key\tmip_name\treads\tunique_tags\n");
+    for (size_t i = 0; i < rows.size(); i++)
+        fprintf(out, "%s\t%s\t%lld\t%lld\n", (*rows[i])[COL_KEY].c_str(), (*rows[i])[COL_NAME].c_str(), (long long)reads[i], (long long)unique[i]);
+    if (fclose(out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, out_path.c_str()); return 1; }
+    if (!label_path.empty()) {
+        FILE* lab = fopen(label_path.c_str(), "w");
+        if (!lab) { fprintf(stderr, "%s: can't write %s\n", PROG, label_path.c_str()); return 1; }
+        for (size_t i = 0; i < rows.size(); i++) {
+            fprintf(lab, "%s\t", (*rows[i])[COL_KEY].c_str());
+            if (label_kind == "log10tags") fprintf(lab, "%.17g\n", log10((double)unique[i] + 1.0));
+            else fprintf(lab, "%lld\n", (long long)(label_kind == "reads" ? reads[i] : unique[i]));
+        }
+        if (fclose(lab) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, label_path.c_str()); return 1; }
+    }
+    fprintf(stderr, "%s: pairs %lld assigned %lld ambiguous %lld unassigned %lld tag_n %lld overflow %lld\n", PROG, (long long)tot.pairs, (long long)tot.assigned,
+            (long long)tot.ambiguous, (long long)tot.unassigned, (long long)tot.tag_n, (long long)tot.overflow);
+    return 0;
+}

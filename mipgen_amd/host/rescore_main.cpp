@@ -18,13 +18,9 @@
 #include <map>
 #include <string>
 
-#include "mipgen_host.hpp"
-#include "svr_problem.hpp"
+#include "mip_table.hpp"
 
 static const char* PROG = "mipgen_rescore";
-enum { COL_KEY = 0, COL_SCORE = 1, COL_CHR = 2, COL_EXT_COPY = 5, COL_EXT_SEQ = 6, COL_LIG_COPY = 9, COL_LIG_SEQ = 10, COL_INS_SEQ = 13, COL_MIP_SEQ = 14,
-       COL_FEAT_START = 15, COL_FEAT_STOP = 16, COL_NAME = 19, N_COLS = 20 };
-
 static int usage(const std::string& msg)
 {
     if (!msg.empty()) fprintf(stderr, "mipgen_rescore: %s\n", msg.c_str());
@@ -37,72 +33,6 @@ static int usage(const std::string& msg)
             "-o file : the tables with the score column re-derived\n"
             "-features file : libsvm training rows, one per probe; -labels table.tsv : mip_key or mip_name <tab> value\n");
     return 1;
-}
-
-struct Table {
-    std::string path, header;
-    std::vector<std::vector<std::string>> rows;
-    std::vector<int32_t> feature;                 // per row: index into `features`
-    std::vector<mipgen::Region> features;         // distinct (chr, feature_start_position, feature_stop_position) in order of appearance
-};
-
-static std::vector<std::string> split_tabs(const std::string& s)
-{
-    std::vector<std::string> f;
-    size_t a = 0;
-    for (;;) {
-        const size_t b = s.find('\t', a);
-        f.push_back(s.substr(a, b == std::string::npos ? std::string::npos : b - a));
-        if (b == std::string::npos) break;
-        a = b + 1;
-    }
-    return f;
-}
-
-static bool read_table(const std::string& path, int flank, Table& t)
-{
-    std::ifstream fh(path);
-    if (!fh.is_open()) { fprintf(stderr, "%s: can't open MIP table %s\n", PROG, path.c_str()); return false; }
-    t.path = path;
-    std::string line;
-    if (!std::getline(fh, line) || line.compare(0, 9, ">mip_key\t") != 0 || split_tabs(line).size() != N_COLS ||
-        split_tabs(line)[COL_SCORE].find("_score") == std::string::npos) {
-        fprintf(stderr, "%s: %s: not a MIP table (the first line is not the \">mip_key ...\" header of %d columns)\n", PROG, path.c_str(), N_COLS);
-        return false;
-    }
-    t.header = line;
-    std::map<std::string, int32_t> seen;
-    long lineno = 1;
-    while (std::getline(fh, line)) {
-        lineno++;
-        if (line.empty()) continue;
-        std::vector<std::string> f = split_tabs(line);
-        auto bad = [&](const char* what) { fprintf(stderr, "%s: %s:%ld: malformed row (%s)\n", PROG, path.c_str(), lineno, what); return false; };
-        if (f.size() != N_COLS) return bad(("expected " + std::to_string((int)N_COLS) + " tab-separated columns, found " + std::to_string(f.size())).c_str());
-        long v;
-        double d;
-        if (!svr_parse_int(f[COL_EXT_COPY].c_str(), &v) || v < INT32_MIN || v > INT32_MAX) return bad("ext_probe_copy is not an integer");
-        if (!svr_parse_int(f[COL_LIG_COPY].c_str(), &v) || v < INT32_MIN || v > INT32_MAX) return bad("lig_probe_copy is not an integer");
-        if (f[COL_EXT_SEQ].empty() || f[COL_EXT_SEQ].size() > MIPGEN_MAX_OLIGO) return bad("ext_probe_sequence is empty or longer than 64 bases");
-        if (f[COL_LIG_SEQ].empty() || f[COL_LIG_SEQ].size() > MIPGEN_MAX_OLIGO) return bad("lig_probe_sequence is empty or longer than 64 bases");
-        if (!svr_parse_double(f[COL_SCORE].c_str(), &d)) return bad("the score is not a number");
-        long fs, fe;
-        if (!svr_parse_int(f[COL_FEAT_START].c_str(), &fs) || !svr_parse_int(f[COL_FEAT_STOP].c_str(), &fe) || fs < 0 || fe < fs || fe > INT32_MAX - 100000)
-            return bad("feature_start_position / feature_stop_position are not a range");
-        if (f[COL_CHR].empty()) return bad("chr is empty");
-        const std::string key = f[COL_CHR] + "\t" + f[COL_FEAT_START] + "\t" + f[COL_FEAT_STOP];
-        auto it = seen.find(key);
-        if (it == seen.end()) {
-            mipgen::Region r;                                                       // the Featurev5 the row was designed for (mipgen.cpp:788-789)
-            r.chr = f[COL_CHR]; r.start = (int)fs + 1; r.stop = (int)fe;
-            r.start_fl = r.start - flank; r.stop_fl = r.stop + flank;
-            it = seen.emplace(key, (int32_t)t.features.size()).first;
-            t.features.push_back(r);
-        }
-        t.feature.push_back(it->second);
-        t.rows.push_back(std::move(f));
-    }
-    return true;
 }
 
 // a score as the reference prints it: `ss << mip->score`, default ostream formatting = six significant digits (mipgen.cpp:774); "-nan" is what its
@@ -164,7 +94,7 @@ int main(int argc, char** argv)
 
     // ---- everything is read and checked before the device is opened ----
     std::vector<Table> tables(inputs.size());
-    for (size_t k = 0; k < inputs.size(); k++) if (!read_table(inputs[k], flank, tables[k])) return 1;
+    for (size_t k = 0; k < inputs.size(); k++) if (!read_table(PROG, inputs[k], flank, tables[k])) return 1;
     std::map<std::string, double> labels;
     if (!label_path.empty()) {
         std::ifstream fh(label_path);
