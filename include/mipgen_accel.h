@@ -345,6 +345,30 @@ int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys);
 /* The probe index of every pair of the LAST feed call (capacity >= its n_pairs): >= 0 assigned, -1 unassigned, -2 ambiguous, -3 overflow. */
 int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, int64_t capacity);
 
+/* ---- the same per SAMPLE of a multiplexed lane (new entry points only: the ABI number does not change) ----
+ * The sample model: n_samples >= 1 barcodes of one length J (1..32), upper-case A C G T only, pairwise distinct.  The index of a pair is
+ * the first J bytes of its index read (bytes beyond J are ignored; a shorter read has no sample).  Distance is the Hamming distance over the J
+ * positions, a byte that is not upper-case A C G T being a mismatch; the sample of a pair is the barcode at the smallest distance <=
+ * barcode_mismatches (0 or 1); two barcodes at that smallest distance: ambiguous; none within it: none.  Row s of the outputs is sample s, row n_samples
+ * is `undetermined` (none + ambiguous).  The probe of a pair and the six totals are what a plain session gives, whatever the sample.
+ * reads[row * n + p]: pairs of that row assigned to probe p; unique_tags[row * n + p]: distinct clean tags among them (the same tag in two samples
+ * is two molecules; = reads with no tag bases); row_pairs[row]: all pairs of the row, assigned to a probe or not.
+ *   open_samples:   everything mipgen_accel_reads_open refuses, and MIPGEN_E_INVALID for NULL / no barcodes, barcodes of unequal length or of more than
+ *                   32 bases, a byte that is not A C G T, a barcode twice, barcode_mismatches outside 0..1, (n_samples + 1) * n > 2^32.  The count matrices
+ *                   (2 x 8 bytes per cell) and the barcode table are part of the MIPGEN_E_NOMEM budget.
+ *   feed_samples:   as feed, with the index read of every pair (its offsets checked like the others).
+ *   finish_samples: reads and unique_tags hold (n_samples + 1) * n entries each, row-major; row_pairs n_samples + 1; every output may be NULL.
+ *   last_samples:   the sample index of every pair of the LAST feed_samples call: >= 0, -1 none, -2 ambiguous (last_assignment gives the probes).
+ * feed / finish of one kind on a session of the other kind: MIPGEN_E_STATE, the session is left as it was and a later correct call works. */
+typedef struct mipgen_sample_totals { int64_t sample_none, sample_ambiguous; } mipgen_sample_totals;
+int mipgen_accel_reads_open_samples(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches,
+                                    const char* const* barcodes, int32_t n_samples, int32_t barcode_mismatches);
+int mipgen_accel_reads_feed_samples(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets,
+                                    const char* index_bytes, const int64_t* index_offsets);
+int mipgen_accel_reads_finish_samples(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
+                                      int64_t* row_pairs);
+int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -554,7 +578,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * negative if unavailable.  which: 0 = dense SVR kernel, 1 = records + scoring kernels, 2 = records / logistic kernel,
  * 3 = replay + condense; 4 = genome pass of the last mipgen_accel_count_oligo_copies (always recorded);
  * 5 / 6 = the matrix-core SVR kernel / the feature kernel of the last mipgen_accel_score_candidates or mipgen_accel_score_probes call on a list
- * (>= 256 SVR candidates); 7 = k_read_assign summed over the feed calls since the last mipgen_accel_reads_open (timing enabled). */
+ * (>= 256 SVR candidates); 7 = k_read_assign summed over the feed calls since the last mipgen_accel_reads_open (timing enabled);
+ * 8 = k_sample_assign summed over the feed calls since the last mipgen_accel_reads_open_samples (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -75,6 +75,10 @@ class ReadTotals(C.Structure):       # mipgen_read_totals
     _fields_ = [(n, C.c_int64) for n in ("pairs", "assigned", "ambiguous", "unassigned", "tag_n", "overflow")]
 
 
+class SampleTotals(C.Structure):     # mipgen_sample_totals
+    _fields_ = [(n, C.c_int64) for n in ("sample_none", "sample_ambiguous")]
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -333,7 +337,11 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_finish.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals)]
     lib.mipgen_accel_reads_set_key_buffer.argtypes = [vp, C.c_int64]
     lib.mipgen_accel_reads_last_assignment.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64]
-    for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment"):
+    lib.mipgen_accel_reads_open_samples.argtypes = [vp, C.POINTER(Probe), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+    lib.mipgen_accel_reads_feed_samples.argtypes = [vp, C.c_int64, C.c_void_p, i64p_, C.c_void_p, i64p_, C.c_void_p, i64p_]
+    lib.mipgen_accel_reads_finish_samples.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals), C.POINTER(SampleTotals), i64p_]
+    lib.mipgen_accel_reads_last_samples.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64]
+    for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -411,6 +419,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_train_svr", "mipgen_accel_svr_cv_folds", "mipgen_accel_cross_validate_svr", "mipgen_accel_score_probes",
     "mipgen_accel_reads_open", "mipgen_accel_reads_feed", "mipgen_accel_reads_finish", "mipgen_accel_reads_set_key_buffer",
     "mipgen_accel_reads_last_assignment",
+    "mipgen_accel_reads_open_samples", "mipgen_accel_reads_feed_samples", "mipgen_accel_reads_finish_samples", "mipgen_accel_reads_last_samples",
 ]
 
 
@@ -842,6 +851,60 @@ class Accel:
         self._check(self.lib.mipgen_accel_reads_finish(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot)))
         totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
         return (reads, unique, totals, assignment) if want_assignment else (reads, unique, totals)
+
+    def count_reads_samples(self, arms: Sequence[tuple], ext_reads: Sequence[bytes], lig_reads: Sequence[bytes], index_reads: Sequence[bytes],
+                            barcodes: Sequence[bytes], barcode_mismatches: int = 0, tag_sizes: Tuple[int, int] = (5, 0), mismatches: int = 0,
+                            swap_reads: bool = False, chunks: int = 1, key_buffer: int = 0, want_assignment: bool = False):
+        """mipgen_accel_reads_open_samples / _feed_samples / _finish_samples: count_reads per sample of a multiplexed lane.  index_reads: the index
+        read of every pair; barcodes: one per sample, of one length.  Returns (reads[rows][n], unique_tags[rows][n], totals dict (the six of
+        count_reads, sample_none, sample_ambiguous), row_pairs[rows][, sample index per pair, probe index per pair]); rows = samples + 1, the last
+        row is `undetermined`."""
+        if swap_reads:
+            ext_reads, lig_reads = lig_reads, ext_reads
+        assert len(ext_reads) == len(lig_reads) == len(index_reads)
+        n, n_pairs, n_samples = len(arms), len(ext_reads), len(barcodes)
+        arr = (Probe * max(n, 1))()
+        for i, q in enumerate(arms):
+            arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
+        bc = (C.c_char_p * max(n_samples, 1))(*barcodes)
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+
+        def pack(rs):
+            off = np.zeros(len(rs) + 1, dtype=np.int64)
+            np.cumsum([len(r) for r in rs], out=off[1:])
+            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
+
+        eb, eo = pack(ext_reads)
+        lb, lo = pack(lig_reads)
+        ib, io = pack(index_reads)
+        self._check(self.lib.mipgen_accel_reads_set_key_buffer(self.h, key_buffer))
+        try:
+            self._check(self.lib.mipgen_accel_reads_open_samples(self.h, arr, n, tag_sizes[0], tag_sizes[1], mismatches, bc, n_samples, barcode_mismatches))
+        finally:
+            self.lib.mipgen_accel_reads_set_key_buffer(self.h, 0)
+        sample = np.empty(n_pairs, dtype=np.int32)
+        probe = np.empty(n_pairs, dtype=np.int32)
+        try:
+            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                self._check(self.lib.mipgen_accel_reads_feed_samples(self.h, b - a, eb[eo[a]:].ctypes.data, eo[a:b + 1].ctypes.data_as(i64p),
+                                                                     lb[lo[a]:].ctypes.data, lo[a:b + 1].ctypes.data_as(i64p),
+                                                                     ib[io[a]:].ctypes.data, io[a:b + 1].ctypes.data_as(i64p)))
+                if want_assignment and b > a:
+                    self._check(self.lib.mipgen_accel_reads_last_samples(self.h, sample[a:b].ctypes.data_as(i32p), b - a))
+                    self._check(self.lib.mipgen_accel_reads_last_assignment(self.h, probe[a:b].ctypes.data_as(i32p), b - a))
+        except Exception:
+            self.lib.mipgen_accel_reads_finish_samples(self.h, None, None, None, None, None)
+            raise
+        reads = np.empty((n_samples + 1, n), dtype=np.int64)
+        unique = np.empty((n_samples + 1, n), dtype=np.int64)
+        row_pairs = np.empty(n_samples + 1, dtype=np.int64)
+        tot, stot = ReadTotals(), SampleTotals()
+        self._check(self.lib.mipgen_accel_reads_finish_samples(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot), C.byref(stot),
+                                                               row_pairs.ctypes.data_as(i64p)))
+        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
+        totals.update({f[0]: int(getattr(stot, f[0])) for f in SampleTotals._fields_})
+        return (reads, unique, totals, row_pairs, sample, probe) if want_assignment else (reads, unique, totals, row_pairs)
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

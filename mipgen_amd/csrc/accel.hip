@@ -578,6 +578,7 @@ double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which)
     if (h && which == 5) return h->list_svr_ms;
     if (h && which == 6) return h->list_feat_ms;
     if (h && which == 7) return h->reads_assign_ms;
+    if (h && which == 8) return h->sample_assign_ms;
     if (!h || !h->timing) return -1.0;
     if (hipSetDevice(h->device) != hipSuccess) return -1.0;
     double total = 0.0;

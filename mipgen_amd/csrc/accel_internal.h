@@ -254,6 +254,7 @@ struct mipgen_accel {
     ReadsSession* reads = nullptr;
     int64_t reads_key_cap = 0;       // mipgen_accel_reads_set_key_buffer (0: default)
     double reads_assign_ms = -1.0;   // k_read_assign over the feed calls of the last session (timing enabled)
+    double sample_assign_ms = -1.0;  // k_sample_assign over the feed calls of the last samples session (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

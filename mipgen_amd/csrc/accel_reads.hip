@@ -1,4 +1,5 @@
-// accel_reads.hip — reads and unique tags per probe from smMIP read pairs behind the C ABI: mipgen_accel_reads_open / _feed / _finish.
+// accel_reads.hip — reads and unique tags per probe from smMIP read pairs behind the C ABI: mipgen_accel_reads_open / _feed / _finish, and
+// per sample of a multiplexed lane: mipgen_accel_reads_open_samples / _feed_samples / _finish_samples / _last_samples.
 // A session owns every buffer it uses (ReadsSession); of the handle it takes the device and the stream, nothing else.
 #include "accel_internal.h"
 
@@ -25,8 +26,19 @@ struct ReadsSession {
     int64_t key_cap = 0;                                     // entries of `keys` in use as capacity
     int64_t key_ub = 0;                                      // no more keys than this are in the buffer (every pair fed since the last sort-unique counted)
     int end_bit = 64;                                        // key bits that can be set
+    // a samples session: rows = n_samples + 1, the count matrices hold rows * n_probes cells
+    bool samples = false;
+    int64_t rows = 1;
+    SampleTable sample_table{};
+    DevBuf<SampleSlot> sample_slots;
+    DevBuf<uint8_t> idx_bytes;
+    DevBuf<int64_t> idx_off;
+    DevBuf<int32_t> row, sample_index;
+    DevBuf<unsigned long long> row_pairs;
+    DevBuf<SampleCounters> sctr;
     void release()
     {
+        sample_slots.release(); idx_bytes.release(); idx_off.release(); row.release(); sample_index.release(); row_pairs.release(); sctr.release();
         probes.release(); ext_seeds.release(); lig_seeds.release(); ext_bytes.release(); lig_bytes.release(); ext_off.release(); lig_off.release();
         assign.release(); reads.release(); unique.release(); keys.release(); keys_alt.release(); sort_temp.release(); ctr.release();
     }
@@ -77,6 +89,50 @@ static int upload_seed_table(mipgen_accel* h, const HostSeedTable& T, SeedTableB
     HIP_TRY(hipMemcpyAsync(B.probes.p, T.probes.data(), T.probes.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     B.view = {B.slots.p, B.keys.p, B.start.p, B.probes.p, (uint32_t)(T.slots.size() - 1)};
     return MIPGEN_OK;
+}
+
+// the barcode hash of a samples session: every barcode, and at d = 1 every one-substitution neighbour of every barcode.  A neighbour
+// that IS another barcode belongs to that barcode (distance 0 wins); one claimed by two barcodes is ambiguous.  (key, kind, sample) sorted: the
+// entries of a key are adjacent, an exact one first.
+static void build_sample_table(const char* const* barcodes, int n_samples, int J, int d, std::vector<SampleSlot>& slots)
+{
+    struct Entry { uint64_t key; uint32_t kind; int32_t sample; };
+    std::vector<Entry> all;
+    all.reserve((size_t)n_samples * (d ? 1 + 3 * (size_t)J : 1));
+    const uint64_t jmask = reads_len_mask(J);
+    for (int s = 0; s < n_samples; s++) {
+        uint64_t p0, p1, bad;
+        pack_arm(barcodes[s], J, false, &p0, &p1, &bad);
+        all.push_back({reads_seed_key(p0, p1, jmask), SAMPLE_SLOT_EXACT, s});
+        if (!d) continue;
+        for (int j = 0; j < J; j++) {
+            const uint64_t bit = 1ull << j;
+            const uint32_t own = (uint32_t)((p0 >> j) & 1u) | ((uint32_t)((p1 >> j) & 1u) << 1);
+            for (uint32_t c = 0; c < 4; c++) {
+                if (c == own) continue;
+                const uint64_t q0 = (p0 & ~bit) | ((c & 1u) ? bit : 0ull), q1 = (p1 & ~bit) | ((c & 2u) ? bit : 0ull);
+                all.push_back({reads_seed_key(q0, q1, jmask), SAMPLE_SLOT_NEIGHBOUR, s});
+            }
+        }
+    }
+    std::sort(all.begin(), all.end(), [](const Entry& a, const Entry& b) { return a.key != b.key ? a.key < b.key : a.kind != b.kind ? a.kind < b.kind : a.sample < b.sample; });
+    std::vector<SampleSlot> distinct;
+    for (size_t i = 0; i < all.size();) {
+        size_t j = i + 1;
+        while (j < all.size() && all[j].key == all[i].key) j++;
+        SampleSlot e{all[i].key, all[i].sample, all[i].kind};
+        if (all[i].kind == SAMPLE_SLOT_NEIGHBOUR && j - i > 1) e.sample = SAMPLE_AMBIGUOUS;
+        distinct.push_back(e);
+        i = j;
+    }
+    size_t n_slots = 16;
+    while (n_slots < 2 * distinct.size()) n_slots *= 2;
+    slots.assign(n_slots, SampleSlot{0, 0, SAMPLE_SLOT_EMPTY});
+    for (const SampleSlot& e : distinct) {
+        uint32_t s = reads_hash(e.key) & (uint32_t)(n_slots - 1);
+        while (slots[s].kind != SAMPLE_SLOT_EMPTY) s = (s + 1) & (uint32_t)(n_slots - 1);
+        slots[s] = e;
+    }
 }
 
 static int free_device_bytes(size_t* free_b)
@@ -149,7 +205,9 @@ int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys)
     return MIPGEN_OK;
 }
 
-int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches)
+// barcodes == nullptr: a plain session
+static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches, const char* const* barcodes,
+                     int32_t n_samples, int32_t barcode_mismatches)
 {
     if (!h || !probes || n < 1) return fail(MIPGEN_E_INVALID, "bad arguments");
     if (ext_tag < 0 || lig_tag < 0 || ext_tag + lig_tag > READS_MAX_TAG) return fail(MIPGEN_E_INVALID, "tag sizes %d,%d: at most %d tag bases in all", ext_tag, lig_tag, READS_MAX_TAG);
@@ -164,6 +222,29 @@ int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t
         shortest = std::min(shortest, std::min(e, l));
     }
     if (shortest < 12) return fail(MIPGEN_E_INVALID, "the shortest arm of the table has %zu bases: a seed of fewer than 12 bases is refused", shortest);
+    int J = 0;
+    const int64_t rows = barcodes ? (int64_t)n_samples + 1 : 1;
+    if (barcodes) {
+        if (barcode_mismatches < 0 || barcode_mismatches > 1) return fail(MIPGEN_E_INVALID, "barcode_mismatches %d outside 0..1", barcode_mismatches);
+        for (int s = 0; s < n_samples; s++) {
+            if (!barcodes[s]) return fail(MIPGEN_E_INVALID, "barcode %d is NULL", s);
+            const size_t len = strlen(barcodes[s]);
+            if (s == 0) {
+                if (len < 1 || len > SAMPLES_MAX_BARCODE) return fail(MIPGEN_E_INVALID, "barcode 0 has %zu bases (1 to %d)", len, SAMPLES_MAX_BARCODE);
+                J = (int)len;
+            } else if ((int)len != J) return fail(MIPGEN_E_INVALID, "barcode %d has %zu bases, barcode 0 has %d: barcodes of unequal length", s, len, J);
+            for (int j = 0; j < J; j++)
+                if (reads_base_code((uint8_t)barcodes[s][j]) > 3u) return fail(MIPGEN_E_INVALID, "barcode %d: byte %d is not one of upper-case A C G T", s, j);
+        }
+        std::vector<std::string> seen;
+        seen.reserve((size_t)n_samples);
+        for (int s = 0; s < n_samples; s++) seen.emplace_back(barcodes[s]);
+        std::sort(seen.begin(), seen.end());
+        for (size_t s = 1; s < seen.size(); s++)
+            if (seen[s] == seen[s - 1]) return fail(MIPGEN_E_INVALID, "barcode %s is there twice", seen[s].c_str());
+        if ((uint64_t)rows * (uint64_t)n > ((uint64_t)1 << 32))
+            return fail(MIPGEN_E_INVALID, "%d samples + undetermined x %d probes: more than 2^32 cells", n_samples, n);
+    }
     if (h->reads) return fail(MIPGEN_E_STATE, "a read-counting session is open: mipgen_accel_reads_finish closes it");
     const int S = (int)std::min<size_t>(shortest, READS_MAX_SEED);
 
@@ -183,6 +264,9 @@ int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t
     HostSeedTable TE, TL;
     build_seed_table(ekp, TE);
     build_seed_table(lkp, TL);
+    std::vector<SampleSlot> sample_slots;
+    if (barcodes) build_sample_table(barcodes, n_samples, J, barcode_mismatches, sample_slots);
+    const size_t cells = (size_t)rows * (size_t)n;
 
     HIP_TRY(hipSetDevice(h->device));
     // the budget: tables + counters + two key buffers, against free device memory
@@ -190,66 +274,86 @@ int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t
     if (int rc = free_device_bytes(&free_b)) return rc;
     const bool tags = ext_tag + lig_tag > 0;
     int64_t key_cap = !tags ? 0 : h->reads_key_cap > 0 ? h->reads_key_cap : READS_KEY_CAP_DEFAULT;
-    const size_t fixed = (size_t)n * (sizeof(ReadProbe) + 16 + 2 * 4) + (TE.slots.size() + TL.slots.size()) * 4 + (TE.keys.size() + TL.keys.size()) * 12 + ((size_t)64 << 20);
+    const size_t fixed = (size_t)n * (sizeof(ReadProbe) + 2 * 4) + cells * 16 + sample_slots.size() * sizeof(SampleSlot) + (size_t)rows * 8 + (TE.slots.size() + TL.slots.size()) * 4 + (TE.keys.size() + TL.keys.size()) * 12 + ((size_t)64 << 20);
     if (tags && h->reads_key_cap <= 0)
         while (key_cap > 1024 && fixed + (size_t)key_cap * 16 > free_b / 2) key_cap /= 2;      // the default gives way to what is free; half is left for the reads
     if (fixed + (size_t)key_cap * 16 > free_b)
-        return fail(MIPGEN_E_NOMEM, "read counter: tables of %d probes and %lld keys need %zu MiB of device memory, %zu MiB are free", n, (long long)key_cap,
-                    (fixed + (size_t)key_cap * 16) >> 20, free_b >> 20);
+        return fail(MIPGEN_E_NOMEM, "read counter: tables of %d probes x %lld rows and %lld keys need %zu MiB of device memory, %zu MiB are free", n, (long long)rows,
+                    (long long)key_cap, (fixed + (size_t)key_cap * 16) >> 20, free_b >> 20);
 
     ReadsSession* S_ = new ReadsSession;
     h->reads = S_;
     auto give_up = [&](int rc) { mipgen_reads_release(h); return rc; };
     S_->P = {ext_tag, lig_tag, max_mismatches, S, seed_mask, n, 0};
     S_->key_cap = key_cap;
-    int probe_bits = 1;
-    while (probe_bits < 32 && ((int64_t)1 << probe_bits) < n) probe_bits++;
+    S_->samples = barcodes != nullptr;
+    S_->rows = rows;
+    int probe_bits = 1;                                                    // (of the cell index rows * n - 1 at most: 32 bits when there are 2^32 cells)
+    while (probe_bits < 32 && ((int64_t)1 << probe_bits) < (int64_t)cells) probe_bits++;
     S_->end_bit = 32 + probe_bits;
-    if (S_->probes.reserve((size_t)n) || S_->reads.reserve((size_t)n) || S_->unique.reserve((size_t)n) || S_->ctr.reserve(1) ||
+    if (S_->probes.reserve((size_t)n) || S_->reads.reserve(cells) || S_->unique.reserve(cells) || S_->ctr.reserve(1) ||
         (key_cap && (S_->keys.reserve((size_t)key_cap) || S_->keys_alt.reserve((size_t)key_cap))))
         return give_up(MIPGEN_E_NOMEM);
+    if (barcodes && (S_->sample_slots.reserve(sample_slots.size()) || S_->row_pairs.reserve((size_t)rows) || S_->sctr.reserve(1))) return give_up(MIPGEN_E_NOMEM);
     int rc = upload_seed_table(h, TE, S_->ext_seeds);
     if (rc == MIPGEN_OK) rc = upload_seed_table(h, TL, S_->lig_seeds);
     hipError_t e = hipSuccess;
     if (rc == MIPGEN_OK) e = hipMemcpyAsync(S_->probes.p, packed.data(), (size_t)n * sizeof(ReadProbe), hipMemcpyHostToDevice, h->stream);
-    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->reads.p, 0, (size_t)n * sizeof(unsigned long long), h->stream);
-    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->unique.p, 0, (size_t)n * sizeof(unsigned long long), h->stream);
+    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->reads.p, 0, cells * sizeof(unsigned long long), h->stream);
+    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->unique.p, 0, cells * sizeof(unsigned long long), h->stream);
     if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->ctr.p, 0, sizeof(ReadsCounters), h->stream);
+    if (barcodes) {
+        if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemcpyAsync(S_->sample_slots.p, sample_slots.data(), sample_slots.size() * sizeof(SampleSlot), hipMemcpyHostToDevice, h->stream);
+        if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->row_pairs.p, 0, (size_t)rows * sizeof(unsigned long long), h->stream);
+        if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->sctr.p, 0, sizeof(SampleCounters), h->stream);
+        S_->sample_table = {S_->sample_slots.p, (uint32_t)(sample_slots.size() - 1), J, barcode_mismatches, n_samples};
+    }
     const hipError_t e2 = hipStreamSynchronize(h->stream);                 // (the host tables above live until here)
     if (rc == MIPGEN_OK && e == hipSuccess) e = e2;
     if (rc == MIPGEN_OK && e != hipSuccess) rc = fail(MIPGEN_E_HIP, "mipgen_accel_reads_open: %s", hipGetErrorString(e));
     if (rc != MIPGEN_OK) return give_up(rc);
     h->reads_assign_ms = 0.0;
+    h->sample_assign_ms = barcodes ? 0.0 : -1.0;
     return MIPGEN_OK;
 }
 
-int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets)
+// with_index: a call of the samples kind
+static int feed_impl(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets, bool with_index,
+                     const char* index_bytes, const int64_t* index_offsets)
 {
     if (!h || n_pairs < 0 || (n_pairs > 0 && (!ext_bytes || !ext_offsets || !lig_bytes || !lig_offsets))) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (with_index && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments");
     if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (h->reads->samples != with_index)
+        return fail(MIPGEN_E_STATE, with_index ? "the open session has no samples: mipgen_accel_reads_feed feeds it" : "the open session has samples: mipgen_accel_reads_feed_samples feeds it");
     if (n_pairs > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld pairs in one call (at most 2^31 - 1)", (long long)n_pairs);
     ReadsSession* S = h->reads;
     S->last_pairs = 0;
     if (n_pairs == 0) return MIPGEN_OK;
     // the kernel trusts the offsets: they are checked here
-    for (int f = 0; f < 2; f++) {
-        const int64_t* off = f ? lig_offsets : ext_offsets;
-        if (off[0] < 0) return fail(MIPGEN_E_INVALID, "%s offsets: negative", f ? "ligation" : "extension");
+    for (int f = 0; f < (with_index ? 3 : 2); f++) {
+        const int64_t* off = f == 2 ? index_offsets : f ? lig_offsets : ext_offsets;
+        const char* what = f == 2 ? "index" : f ? "ligation" : "extension";
+        if (off[0] < 0) return fail(MIPGEN_E_INVALID, "%s offsets: negative", what);
         for (int64_t i = 0; i < n_pairs; i++)
-            if (off[i + 1] < off[i]) return fail(MIPGEN_E_INVALID, "%s offsets: entry %lld below entry %lld", f ? "ligation" : "extension", (long long)(i + 1), (long long)i);
+            if (off[i + 1] < off[i]) return fail(MIPGEN_E_INVALID, "%s offsets: entry %lld below entry %lld", what, (long long)(i + 1), (long long)i);
     }
     const size_t eb = (size_t)(ext_offsets[n_pairs] - ext_offsets[0]), lb = (size_t)(lig_offsets[n_pairs] - lig_offsets[0]);
+    const size_t ib = with_index ? (size_t)(index_offsets[n_pairs] - index_offsets[0]) : 0;
     HIP_TRY(hipSetDevice(h->device));
     size_t free_b = 0;
     if (int rc = free_device_bytes(&free_b)) return rc;
-    const size_t have = S->ext_bytes.cap + S->lig_bytes.cap + (S->ext_off.cap + S->lig_off.cap) * 8 + S->assign.cap * 4;
-    const size_t need = eb + lb + 2 * (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 4;
+    const size_t have = S->ext_bytes.cap + S->lig_bytes.cap + (S->ext_off.cap + S->lig_off.cap) * 8 + S->assign.cap * 4 + S->idx_bytes.cap + S->idx_off.cap * 8 +
+                        (S->row.cap + S->sample_index.cap) * 4;
+    const size_t need = eb + lb + 2 * (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 4 + (with_index ? ib + (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 8 : 0);
     if (need + need / 8 + ((size_t)64 << 20) > free_b + have)
         return fail(MIPGEN_E_NOMEM, "read counter: a chunk of %lld pairs needs %zu MiB of device memory, %zu MiB are free (feed fewer pairs per call)", (long long)n_pairs,
                     need >> 20, (free_b + have) >> 20);
     // (+ 8: the kernel fetches the bases as aligned 32-bit words, up to 5 bytes beyond the last read)
     if (S->ext_bytes.reserve(eb + 8) || S->lig_bytes.reserve(lb + 8) || S->ext_off.reserve((size_t)n_pairs + 1) || S->lig_off.reserve((size_t)n_pairs + 1) ||
         S->assign.reserve((size_t)n_pairs))
+        return MIPGEN_E_NOMEM;
+    if (with_index && (S->idx_bytes.reserve(ib + 8) || S->idx_off.reserve((size_t)n_pairs + 1) || S->row.reserve((size_t)n_pairs) || S->sample_index.reserve((size_t)n_pairs)))
         return MIPGEN_E_NOMEM;
     struct IdleOnExit { hipStream_t s; ~IdleOnExit() { (void)hipStreamSynchronize(s); } } idle_on_exit{h->stream};      // the caller's arrays are free when the call returns
     if (eb) HIP_TRY(hipMemcpyAsync(S->ext_bytes.p, ext_bytes, eb, hipMemcpyHostToDevice, h->stream));
@@ -259,13 +363,25 @@ int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_by
     const bool tags = S->P.te + S->P.tl > 0;
     std::vector<hipEvent_t> ev;
     int rc = MIPGEN_OK;
+    hipEvent_t sa = nullptr, sb = nullptr;
+    if (with_index) {
+        // the sample row of every pair of the chunk, before the launches that count into its cells
+        if (ib) HIP_TRY(hipMemcpyAsync(S->idx_bytes.p, index_bytes, ib, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(S->idx_off.p, index_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, h->stream));
+        if (h->timing && hipEventCreate(&sa) == hipSuccess && hipEventCreate(&sb) == hipSuccess) (void)hipEventRecord(sa, h->stream);
+        const hipError_t e = mipgen_launch_sample_assign(h->stream, &S->sample_table, n_pairs, S->idx_bytes.p, S->idx_off.p, index_offsets[0], S->row.p, S->sample_index.p,
+                                                         S->row_pairs.p, S->sctr.p);
+        if (e != hipSuccess) rc = fail(MIPGEN_E_HIP, "k_sample_assign: %s", hipGetErrorString(e));
+        if (sb) (void)hipEventRecord(sb, h->stream);
+    }
     for (int64_t p0 = 0; p0 < n_pairs && rc == MIPGEN_OK;) {
         int64_t c = n_pairs - p0;
         if (tags) { if ((rc = make_key_room(h, S, c, &c))) break; c = std::min(c, n_pairs - p0); }
         hipEvent_t a = nullptr, b = nullptr;
         if (h->timing && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ev.push_back(a); ev.push_back(b); (void)hipEventRecord(a, h->stream); }
         const hipError_t e = mipgen_launch_read_assign(h->stream, &S->P, S->probes.p, &S->ext_seeds.view, &S->lig_seeds.view, p0, c, S->ext_bytes.p, S->ext_off.p, ext_offsets[0],
-                                                       S->lig_bytes.p, S->lig_off.p, lig_offsets[0], S->assign.p, S->reads.p, S->keys.p, S->key_cap, S->ctr.p);
+                                                       S->lig_bytes.p, S->lig_off.p, lig_offsets[0], S->assign.p, S->reads.p, S->keys.p, S->key_cap, S->ctr.p,
+                                                       with_index ? S->row.p : nullptr);
         if (e != hipSuccess) rc = fail(MIPGEN_E_HIP, "k_read_assign: %s", hipGetErrorString(e));
         if (b) (void)hipEventRecord(b, h->stream);
         if (tags) S->key_ub += c;
@@ -278,8 +394,49 @@ int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_by
         if (rc == MIPGEN_OK && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) h->reads_assign_ms += ms;
     }
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (sa && sb) {
+        float ms = 0.f;
+        if (rc == MIPGEN_OK && hipEventElapsedTime(&ms, sa, sb) == hipSuccess) h->sample_assign_ms += ms;
+    }
+    if (sa) (void)hipEventDestroy(sa);
+    if (sb) (void)hipEventDestroy(sb);
     if (rc == MIPGEN_OK) S->last_pairs = n_pairs;
     return rc;
+}
+
+int mipgen_accel_reads_open(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches)
+{
+    return open_impl(h, probes, n, ext_tag, lig_tag, max_mismatches, nullptr, 0, 0);
+}
+
+int mipgen_accel_reads_open_samples(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches,
+                                    const char* const* barcodes, int32_t n_samples, int32_t barcode_mismatches)
+{
+    if (!barcodes || n_samples < 1) return fail(MIPGEN_E_INVALID, "bad arguments: no barcodes");
+    return open_impl(h, probes, n, ext_tag, lig_tag, max_mismatches, barcodes, n_samples, barcode_mismatches);
+}
+
+int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets)
+{
+    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, false, nullptr, nullptr);
+}
+
+int mipgen_accel_reads_feed_samples(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets,
+                                    const char* index_bytes, const int64_t* index_offsets)
+{
+    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, true, index_bytes, index_offsets);
+}
+
+int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity)
+{
+    if (!h || !sample_index) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (!h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has no samples");
+    if (capacity < h->reads->last_pairs) return fail(MIPGEN_E_INVALID, "capacity %lld < %lld pairs", (long long)capacity, (long long)h->reads->last_pairs);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->reads->last_pairs) HIP_TRY(hipMemcpyAsync(sample_index, h->reads->sample_index.p, (size_t)h->reads->last_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MIPGEN_OK;
 }
 
 int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, int64_t capacity)
@@ -293,10 +450,11 @@ int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, in
     return MIPGEN_OK;
 }
 
-static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals)
+static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
+                       int64_t* row_pairs)
 {
     HIP_TRY(hipSetDevice(h->device));
-    const size_t n = (size_t)S->P.n_probes;
+    const size_t n = (size_t)S->P.n_probes * (size_t)S->rows;                // cells
     const bool tags = S->P.te + S->P.tl > 0;
     if (tags) {
         if (int rc = sort_unique_keys(h, S)) return rc;
@@ -307,8 +465,14 @@ static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are downloaded in place");
     if (reads) HIP_TRY(hipMemcpyAsync(reads, S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     if (unique_tags) HIP_TRY(hipMemcpyAsync(unique_tags, tags ? S->unique.p : S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    SampleCounters sc{0, 0};
+    if (S->samples) {
+        HIP_TRY(hipMemcpyAsync(&sc, S->sctr.p, sizeof sc, hipMemcpyDeviceToHost, h->stream));
+        if (row_pairs) HIP_TRY(hipMemcpyAsync(row_pairs, S->row_pairs.p, (size_t)S->rows * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    }
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (c.keys_lost) return fail(MIPGEN_E_STATE, "read counter: %llu keys did not fit the key buffer", c.keys_lost);
+    if (sample_totals) *sample_totals = {(int64_t)sc.none, (int64_t)sc.ambiguous};
     if (totals) *totals = {(int64_t)c.pairs, (int64_t)c.assigned, (int64_t)c.ambiguous, (int64_t)c.unassigned, (int64_t)c.tag_n, (int64_t)c.overflow};
     return MIPGEN_OK;
 }
@@ -317,7 +481,18 @@ int mipgen_accel_reads_finish(mipgen_accel* h, int64_t* reads, int64_t* unique_t
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    const int rc = finish_impl(h, h->reads, reads, unique_tags, totals);
+    if (h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has samples: mipgen_accel_reads_finish_samples closes it");
+    const int rc = finish_impl(h, h->reads, reads, unique_tags, totals, nullptr, nullptr);
+    mipgen_reads_release(h);
+    return rc;
+}
+
+int mipgen_accel_reads_finish_samples(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals, int64_t* row_pairs)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (!h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has no samples: mipgen_accel_reads_finish closes it");
+    const int rc = finish_impl(h, h->reads, reads, unique_tags, totals, sample_totals, row_pairs);
     mipgen_reads_release(h);
     return rc;
 }

@@ -112,7 +112,10 @@ hipError_t mipgen_launch_window_flags(hipStream_t st, const char* q, int64_t tot
 // kernels_reads.hip (pairs [pair0, pair0 + n_pairs) of the uploaded chunk; assign is indexed by the pair's position in the chunk)
 hipError_t mipgen_launch_read_assign(hipStream_t, const ReadsParams*, const ReadProbe* probes, const SeedTable* ext_seeds, const SeedTable* lig_seeds, int64_t pair0,
                                      int64_t n_pairs, const uint8_t* ext_bytes, const int64_t* ext_off, int64_t ext_base, const uint8_t* lig_bytes, const int64_t* lig_off,
-                                     int64_t lig_base, int32_t* assign, unsigned long long* reads, uint64_t* keys, int64_t key_cap, ReadsCounters* ctr);
+                                     int64_t lig_base, int32_t* assign, unsigned long long* reads, uint64_t* keys, int64_t key_cap, ReadsCounters* ctr,
+                                     const int32_t* row);        // row: nullptr, or the sample row of every pair of the chunk (counts and keys go to the cell row * n_probes + probe)
+hipError_t mipgen_launch_sample_assign(hipStream_t, const SampleTable*, int64_t n_pairs, const uint8_t* idx_bytes, const int64_t* idx_off, int64_t idx_base, int32_t* row,
+                                       int32_t* sample_index, unsigned long long* row_pairs, SampleCounters* sctr);
 hipError_t mipgen_launch_reads_histogram(hipStream_t, const uint64_t* keys, int64_t n, unsigned long long* unique);
 hipError_t mipgen_reads_sort_unique(hipStream_t, void* temp, size_t* temp_bytes, uint64_t* keys, uint64_t* alt, int64_t n, int end_bit, unsigned long long* n_out);
 }

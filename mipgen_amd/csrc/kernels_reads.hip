@@ -5,6 +5,9 @@
 //                     which sit in L2 / Infinity Cache for tables of 10^4-10^5 probes; 4 + 8 bytes written per pair.  A pair's work is two lookups
 //                     and a handful of popcounts with nothing to share between lanes: a wavefront per pair would leave 62 lanes idle through the
 //                     lookups and spend cross-lane reductions on a 16-30 base compare that one lane does in three instructions on bit planes.
+//                     With `row` (the sample row of every pair) a count goes to the cell row * n_probes + probe instead of the probe.
+//  k_sample_assign    a LANE per pair: the first J bases of the index read packed as a key, one lookup in the barcode hash (four at an index with
+//                     one byte that is not A C G T), the pairs of every row counted in LDS and flushed once per workgroup.
 //  k_reads_histogram  a lane per key of the sorted, duplicate-free key list: unique tags per probe (one atomic per distinct key).
 //  sort + unique      hipCUB (rocPRIM) radix sort and run-length unique on the accumulated 64-bit keys (probe << 32 | tag).
 #include <hipcub/hipcub.hpp>
@@ -65,13 +68,13 @@ __global__ __launch_bounds__(256) void k_read_assign(ReadsParams P, const ReadPr
                                                      const uint8_t* __restrict__ ext_bytes, const int64_t* __restrict__ ext_off, int64_t ext_base,
                                                      const uint8_t* __restrict__ lig_bytes, const int64_t* __restrict__ lig_off, int64_t lig_base,
                                                      int32_t* __restrict__ assign, unsigned long long* __restrict__ reads, uint64_t* __restrict__ keys,
-                                                     unsigned long long key_cap, ReadsCounters* __restrict__ ctr)
+                                                     unsigned long long key_cap, ReadsCounters* __restrict__ ctr, const int32_t* __restrict__ row)
 {
     const int64_t i = pair0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < pair0 + n_pairs;
     int result = READS_UNASSIGNED;
     bool tag_clean = false;
-    uint32_t tag = 0;
+    uint32_t tag = 0, cell = 0;
     if (active) {
         const int64_t eb = ext_off[i] - ext_base, ee = ext_off[i + 1] - ext_base;
         const int64_t lb = lig_off[i] - lig_base, le = lig_off[i + 1] - lig_base;
@@ -113,7 +116,8 @@ __global__ __launch_bounds__(256) void k_read_assign(ReadsParams P, const ReadPr
         if (result >= 0) {
             tag_clean = pack_tag(ext_bytes, eb, P.te, &tag);                               // (an assigned pair's reads hold their tags: avail >= arm >= 1)
             tag_clean = pack_tag(lig_bytes, lb, P.tl, &tag) && tag_clean;
-            atomicAdd(&reads[result], 1ull);
+            cell = row ? (uint32_t)row[i] * (uint32_t)P.n_probes + (uint32_t)result : (uint32_t)result;       // (rows * probes <= 2^32: accel_reads.hip)
+            atomicAdd(&reads[cell], 1ull);
         }
         assign[i] = result;
     }
@@ -139,12 +143,85 @@ __global__ __launch_bounds__(256) void k_read_assign(ReadsParams P, const ReadPr
     base = __shfl(base, 0);
     if (has_key) {
         const unsigned long long pos = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
-        if (pos < key_cap) keys[pos] = ((uint64_t)(uint32_t)result << 32) | tag;
+        if (pos < key_cap) keys[pos] = ((uint64_t)cell << 32) | tag;
         else atomicAdd(&ctr->keys_lost, 1ull);              // (the host sizes the buffer for every pair of the launch: never taken, and reported if it is)
     }
 }
 
-// keys[0, n): sorted and duplicate-free - one count per key into its probe
+// the sample of `key` in the barcode hash: the slot's kind (SAMPLE_SLOT_EMPTY: not there) and its sample
+__device__ static inline uint32_t sample_lookup(const SampleTable& T, uint64_t key, int32_t* sample)
+{
+    uint32_t s = reads_hash(key) & T.mask;
+    for (uint32_t step = 0; step <= T.mask; step++, s = (s + 1) & T.mask) {
+        const SampleSlot e = T.slots[s];                                    // one 16-byte load
+        if (e.kind == SAMPLE_SLOT_EMPTY) return SAMPLE_SLOT_EMPTY;
+        if (e.key == key) { *sample = e.sample; return e.kind; }
+    }
+    return SAMPLE_SLOT_EMPTY;
+}
+
+// DESIGN 4.10.  Pairs [0, n_pairs) of the uploaded chunk, grid-stride: row[i] (sample, or n_samples = undetermined) and sample_index[i] (>= 0, -1 none,
+// -2 ambiguous).  The pairs of a sample row are counted in LDS when `lds_rows` > 0 (= rows, the dynamic LDS of the launch) and flushed with one atomic per
+// row the workgroup met; none / ambiguous (and so the undetermined row) by ballot, one atomic per wavefront and counter.
+__global__ __launch_bounds__(256) void k_sample_assign(SampleTable T, int64_t n_pairs, const uint8_t* __restrict__ idx_bytes, const int64_t* __restrict__ idx_off,
+                                                       int64_t idx_base, int32_t* __restrict__ row, int32_t* __restrict__ sample_index,
+                                                       unsigned long long* __restrict__ row_pairs, SampleCounters* __restrict__ sctr, int lds_rows)
+{
+    extern __shared__ uint32_t row_count[];
+    for (int r = threadIdx.x; r < lds_rows; r += blockDim.x) row_count[r] = 0u;
+    __syncthreads();
+    const uint64_t jmask = reads_len_mask(T.J);
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    // (every lane of a wavefront runs the same number of rounds: the ballots below are whole)
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < n_pairs; i0 += stride) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool active = i < n_pairs;
+        int32_t sample = SAMPLE_NONE;
+        if (active) {
+            const int64_t b = idx_off[i] - idx_base, e = idx_off[i + 1] - idx_base;
+            if (e - b >= T.J) {
+                uint64_t p0, p1, bad;
+                pack_bases(idx_bytes, b, T.J, p0, p1, bad);
+                bad &= jmask;
+                if (bad == 0) {
+                    int32_t v = 0;
+                    if (sample_lookup(T, reads_seed_key(p0, p1, jmask), &v) != SAMPLE_SLOT_EMPTY) sample = v;
+                } else if (T.d == 1 && (bad & (bad - 1)) == 0) {
+                    // one byte that is not A C G T: every barcode is at distance >= 1, and one at distance 1 equals the index with one of the four
+                    // bases in that place
+                    const uint64_t bit = bad;
+                    int hits = 0;
+                    for (uint32_t c = 0; c < 4; c++) {
+                        const uint64_t q0 = (p0 & ~bit) | ((c & 1u) ? bit : 0ull), q1 = (p1 & ~bit) | ((c & 2u) ? bit : 0ull);
+                        int32_t v = 0;
+                        if (sample_lookup(T, reads_seed_key(q0, q1, jmask), &v) == SAMPLE_SLOT_EXACT) { hits++; sample = v; }
+                    }
+                    if (hits > 1) sample = SAMPLE_AMBIGUOUS;
+                }
+            }
+            row[i] = sample >= 0 ? sample : T.n_samples;
+            sample_index[i] = sample;
+            if (sample >= 0) {
+                if (lds_rows > 0) atomicAdd(&row_count[sample], 1u);
+                else atomicAdd(&row_pairs[sample], 1ull);
+            }
+        }
+        const int n_none = wave_count(active && sample == SAMPLE_NONE), n_amb = wave_count(active && sample == SAMPLE_AMBIGUOUS);
+        if (lane == 0) {
+            if (n_none) atomicAdd(&sctr->none, (unsigned long long)n_none);
+            if (n_amb) atomicAdd(&sctr->ambiguous, (unsigned long long)n_amb);
+            if (n_none + n_amb) atomicAdd(&row_pairs[T.n_samples], (unsigned long long)(n_none + n_amb));
+        }
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < lds_rows; r += blockDim.x) {
+        const uint32_t c = row_count[r];
+        if (c) atomicAdd(&row_pairs[r], (unsigned long long)c);
+    }
+}
+
+// keys[0, n): sorted and duplicate-free - one count per key into its probe (its cell, with sample rows)
 __global__ __launch_bounds__(256) void k_reads_histogram(const uint64_t* __restrict__ keys, int64_t n, unsigned long long* __restrict__ unique)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) atomicAdd(&unique[keys[i] >> 32], 1ull);
@@ -154,13 +231,25 @@ extern "C" {
 
 hipError_t mipgen_launch_read_assign(hipStream_t s, const ReadsParams* P, const ReadProbe* probes, const SeedTable* TE, const SeedTable* TL, int64_t pair0, int64_t n_pairs,
                                      const uint8_t* ext_bytes, const int64_t* ext_off, int64_t ext_base, const uint8_t* lig_bytes, const int64_t* lig_off, int64_t lig_base,
-                                     int32_t* assign, unsigned long long* reads, uint64_t* keys, int64_t key_cap, ReadsCounters* ctr)
+                                     int32_t* assign, unsigned long long* reads, uint64_t* keys, int64_t key_cap, ReadsCounters* ctr, const int32_t* row)
 {
     if (n_pairs <= 0) return hipSuccess;
     const int64_t blocks = (n_pairs + 255) / 256;
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_read_assign, dim3((unsigned)blocks), dim3(256), 0, s, *P, probes, *TE, *TL, pair0, n_pairs, ext_bytes, ext_off, ext_base, lig_bytes, lig_off,
-                       lig_base, assign, reads, keys, (unsigned long long)key_cap, ctr);
+                       lig_base, assign, reads, keys, (unsigned long long)key_cap, ctr, row);
+    return hipGetLastError();
+}
+
+hipError_t mipgen_launch_sample_assign(hipStream_t s, const SampleTable* T, int64_t n_pairs, const uint8_t* idx_bytes, const int64_t* idx_off, int64_t idx_base, int32_t* row,
+                                       int32_t* sample_index, unsigned long long* row_pairs, SampleCounters* sctr)
+{
+    if (n_pairs <= 0) return hipSuccess;
+    // at most 2,048 workgroups (8 per CU), each with pairs enough to be worth the clearing and the flush of its LDS counters
+    const int64_t blocks = std::min<int64_t>((n_pairs + 255) / 256, 2048);
+    const int lds_rows = T->n_samples <= SAMPLES_LDS_ROWS ? T->n_samples : 0;
+    hipLaunchKernelGGL(k_sample_assign, dim3((unsigned)blocks), dim3(256), (size_t)lds_rows * sizeof(uint32_t), s, *T, n_pairs, idx_bytes, idx_off, idx_base, row, sample_index,
+                       row_pairs, sctr, lds_rows);
     return hipGetLastError();
 }
 

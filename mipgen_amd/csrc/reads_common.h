@@ -39,6 +39,28 @@ struct ReadsParams {
     int32_t n_probes, pad;
 };
 
+// index key -> sample: an open-addressing hash (linear probing, load <= 1/2, reads_hash) keyed by the first J index bases packed like a seed
+// key.  One 16-byte slot per entry.  At barcode_mismatches = 1 it also holds every one-substitution neighbour of every barcode.
+#define SAMPLES_MAX_BARCODE 32       // bases of a barcode: 2 bits each in a 64-bit key
+#define SAMPLES_LDS_ROWS 4096        // k_sample_assign counts the pairs of up to this many samples in LDS (16 KiB); beyond it by one atomic per pair, spread over that many rows
+#define SAMPLE_NONE (-1)
+#define SAMPLE_AMBIGUOUS (-2)
+#define SAMPLE_SLOT_EMPTY 0u
+#define SAMPLE_SLOT_EXACT 1u         // the key is a barcode
+#define SAMPLE_SLOT_NEIGHBOUR 2u     // the key is one substitution from the barcode `sample`, or from several (sample = SAMPLE_AMBIGUOUS)
+
+struct alignas(16) SampleSlot { uint64_t key; int32_t sample; uint32_t kind; };
+
+struct SampleTable {
+    const SampleSlot* slots;
+    uint32_t mask;                    // slots - 1 (a power of two)
+    int32_t J;                        // barcode length
+    int32_t d;                        // barcode_mismatches
+    int32_t n_samples;
+};
+
+struct SampleCounters { unsigned long long none, ambiguous; };
+
 struct ReadsCounters { unsigned long long pairs, assigned, ambiguous, unassigned, tag_n, overflow, n_keys, keys_lost; };
 
 __host__ __device__ static inline uint32_t reads_base_code(uint32_t c)     // 0..3, or 4 for every other byte (lower case included)

@@ -11,6 +11,20 @@
 //   -labels    "mip_key <tab> value", the file `mipgen_rescore -features ... -labels` reads: unique_tags (tags, the default), reads, or
 //              log10(unique_tags + 1) printed with %.17g (log10tags)
 //   stderr     "mipgen_count: pairs P assigned A ambiguous B unassigned U tag_n T overflow O"
+// Per sample of a multiplexed lane (without -barcodes every line written is what it was):
+//   -barcodes samples.tsv   "label <tab> sequence" per sample (blank lines skipped): barcodes of one length (at most 32), upper-case A C G T, distinct;
+//                           labels distinct and not "undetermined"
+//   -index_reads i1.fq[,i2.fq]  the index read of every pair, in the order of -reads; -index_length j1[,j2]: the pair's index is the first j1 bases
+//                           of i1 followed by the first j2 of i2 (one file: j1 defaults to the barcode length; two files: required, j1 + j2 = barcode
+//                           length); an index read shorter than its j leaves the pair without a sample
+//   -barcode_mismatches 0|1 substitutions allowed between index and barcode (default 0)
+//   -o         then "sample <tab> mip_key <tab> mip_name <tab> reads <tab> unique_tags", one line per cell with reads > 0: samples in file order,
+//              "undetermined" last, probes in table order
+//   -samples   "sample <tab> barcode <tab> pairs <tab> assigned <tab> unique_tags <tab> probes_seen" under a header line of those words, one line per
+//              sample, always; the last line is "undetermined" with barcode "*"
+//   -labels    the value per probe over the NAMED samples: reads and unique tags summed over their rows (molecules of different samples are different
+//              molecules), log10tags of that sum
+//   stderr     a second line: "mipgen_count: samples N sample_none X sample_ambiguous Y"
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -32,7 +46,11 @@ static int usage(const std::string& msg)
             "-mismatches n : substitutions allowed per arm, 0..2 (default 0)\n"
             "-swap_reads : the first file of -reads holds the ligation reads\n"
             "-o file : mip_key, mip_name, reads, unique_tags per probe\n"
-            "-labels file : mip_key <tab> value for mipgen_rescore -labels; -label tags|reads|log10tags : the value (default tags)\n");
+            "-labels file : mip_key <tab> value for mipgen_rescore -labels; -label tags|reads|log10tags : the value (default tags)\n"
+            "-barcodes samples.tsv : label <tab> barcode per sample: counts per sample (-o gains a sample column); needs -index_reads\n"
+            "-index_reads i1.fq[,i2.fq] : the index reads of the pairs; -index_length j1[,j2] : bases taken from each (default: the barcode length)\n"
+            "-barcode_mismatches n : substitutions allowed between index and barcode, 0 or 1 (default 0)\n"
+            "-samples file : sample, barcode, pairs, assigned, unique_tags, probes_seen per sample\n");
     return 1;
 }
 
@@ -73,17 +91,65 @@ struct Fastq {
 };
 
 struct Chunk {
-    std::string ext, lig;
-    std::vector<int64_t> ext_off, lig_off;
+    std::string ext, lig, idx;
+    std::vector<int64_t> ext_off, lig_off, idx_off;
     int64_t n = 0;
     bool last = false, failed = false;
 };
 
+// "label <tab> sequence" per line; false with a message that names file and line
+static bool read_barcodes(const std::string& path, std::vector<std::string>& labels, std::vector<std::string>& seqs)
+{
+    FILE* fp = fopen(path.c_str(), "r");
+    if (!fp) { fprintf(stderr, "%s: can't open barcode file %s\n", PROG, path.c_str()); return false; }
+    char* line = nullptr;
+    size_t cap = 0;
+    long lineno = 0;
+    bool ok = true;
+    auto bad = [&](const std::string& what) { fprintf(stderr, "%s: %s:%ld: %s\n", PROG, path.c_str(), lineno, what.c_str()); ok = false; };
+    for (ssize_t n; ok && (n = getline(&line, &cap, fp)) >= 0;) {
+        lineno++;
+        while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r')) n--;
+        const std::string l(line, (size_t)n);
+        if (l.find_first_not_of(" \t") == std::string::npos) continue;
+        const size_t tab = l.find('\t');
+        if (tab == std::string::npos || tab == 0 || tab + 1 >= l.size() || l.find('\t', tab + 1) != std::string::npos) { bad("malformed line (expected label <tab> sequence)"); break; }
+        const std::string label = l.substr(0, tab), seq = l.substr(tab + 1);
+        if (label == "undetermined") { bad("the label undetermined is taken (it names the pairs without a sample)"); break; }
+        if (seq.size() > 32) { bad("barcode of " + std::to_string(seq.size()) + " bases (at most 32)"); break; }
+        if (!seqs.empty() && seq.size() != seqs[0].size()) {
+            bad("barcode of " + std::to_string(seq.size()) + " bases, the first has " + std::to_string(seqs[0].size()) + " (barcodes of unequal length)");
+            break;
+        }
+        const size_t q = seq.find_first_not_of("ACGT");
+        if (q != std::string::npos) { bad("barcode " + seq + ": byte " + std::to_string(q + 1) + " is not one of upper-case A C G T"); break; }
+        if (std::find(seqs.begin(), seqs.end(), seq) != seqs.end()) { bad("barcode " + seq + " is there twice"); break; }
+        if (std::find(labels.begin(), labels.end(), label) != labels.end()) { bad("label " + label + " is there twice"); break; }
+        labels.push_back(label); seqs.push_back(seq);
+    }
+    free(line);
+    fclose(fp);
+    if (ok && seqs.empty()) { fprintf(stderr, "%s: %s holds no barcode\n", PROG, path.c_str()); ok = false; }
+    return ok;
+}
+
+static bool parse_int_list(const std::string& v, std::vector<long>& out)
+{
+    for (size_t a = 0;;) {
+        const size_t c = v.find(',', a);
+        long x;
+        if (!svr_parse_int(v.substr(a, c == std::string::npos ? c : c - a).c_str(), &x)) return false;
+        out.push_back(x);
+        if (c == std::string::npos) return true;
+        a = c + 1;
+    }
+}
+
 int main(int argc, char** argv)
 {
-    int te = 5, tl = 0, mism = 0;
-    bool swap = false;
-    std::string out_path, label_path, label_kind = "tags", reads_a, reads_b;
+    int te = 5, tl = 0, mism = 0, bc_mism = 0;
+    bool swap = false, bc_mism_given = false;
+    std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -107,6 +173,14 @@ int main(int argc, char** argv)
         else if (a == "-label") { if (v != "tags" && v != "reads" && v != "log10tags") return usage("-label must be tags, reads or log10tags"); label_kind = v; }
         else if (a == "-o") out_path = v;
         else if (a == "-labels") label_path = v;
+        else if (a == "-barcodes") barcode_path = v;
+        else if (a == "-samples") samples_path = v;
+        else if (a == "-index_reads") index_arg = v;
+        else if (a == "-index_length") index_len_arg = v;
+        else if (a == "-barcode_mismatches") {
+            if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-barcode_mismatches must be 0 or 1");
+            bc_mism = (int)iv; bc_mism_given = true;
+        }
         else return usage("unknown option: " + a);
     }
     if (inputs.empty()) return usage("no MIP table");
@@ -114,8 +188,36 @@ int main(int argc, char** argv)
     if (reads_a.empty() || reads_b.empty()) return usage("no reads: -reads ext.fq lig.fq is missing");
     for (const std::string* p : {&reads_a, &reads_b})
         if (p->size() >= 3 && p->compare(p->size() - 3, 3, ".gz") == 0) return usage(*p + ": compressed FASTQ is not read (plain FASTQ only: decompress it first)");
+    const bool by_sample = !barcode_path.empty();
+    if (by_sample && index_arg.empty()) return usage("-barcodes needs -index_reads i1.fq[,i2.fq]");
+    if (!by_sample && !index_arg.empty()) return usage("-index_reads needs -barcodes samples.tsv");
+    if (!by_sample && (!samples_path.empty() || !index_len_arg.empty() || bc_mism_given)) return usage("-samples, -index_length and -barcode_mismatches need -barcodes samples.tsv");
+    std::vector<std::string> index_paths;
+    std::vector<long> index_len;
+    if (by_sample) {
+        const size_t c = index_arg.find(',');
+        index_paths.push_back(index_arg.substr(0, c));
+        if (c != std::string::npos) index_paths.push_back(index_arg.substr(c + 1));
+        for (const std::string& p : index_paths) {
+            if (p.empty() || p.find(',') != std::string::npos) return usage("-index_reads takes one file or two, i1.fq[,i2.fq]");
+            if (p.size() >= 3 && p.compare(p.size() - 3, 3, ".gz") == 0) return usage(p + ": compressed FASTQ is not read (plain FASTQ only: decompress it first)");
+        }
+        if (!index_len_arg.empty()) {
+            if (!parse_int_list(index_len_arg, index_len) || index_len.size() != index_paths.size()) return usage("-index_length takes one length per index file, j1[,j2]");
+            for (long j : index_len) if (j < 1 || j > 32) return usage("-index_length: a length is 1 to 32");
+        } else if (index_paths.size() == 2) return usage("two index files need -index_length j1,j2");
+    }
 
     // ---- everything is read and checked before the device is opened ----
+    std::vector<std::string> sample_labels, barcodes;
+    if (by_sample) {
+        if (!read_barcodes(barcode_path, sample_labels, barcodes)) return 1;
+        const long J = (long)barcodes[0].size();
+        if (index_len.empty()) index_len.push_back(J);
+        long sum = 0;
+        for (long j : index_len) sum += j;
+        if (sum != J) { fprintf(stderr, "%s: -index_length %s: the lengths must sum to the barcode length %ld\n", PROG, index_len_arg.c_str(), J); return 1; }
+    }
     std::vector<Table> tables(inputs.size());
     for (size_t k = 0; k < inputs.size(); k++) if (!read_table(PROG, inputs[k], 0, tables[k])) return 1;
     std::vector<mipgen_probe> probes;
@@ -135,7 +237,10 @@ int main(int argc, char** argv)
     if (shortest < 12) { fprintf(stderr, "%s: the shortest arm of the tables has %zu bases: a seed of fewer than 12 bases is refused\n", PROG, shortest); return 1; }
     Fastq fe, fl;
     fe.path = swap ? reads_b : reads_a; fl.path = swap ? reads_a : reads_b;
-    for (Fastq* f : {&fe, &fl}) if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; }
+    Fastq fi[2];
+    std::vector<Fastq*> files = {&fe, &fl};
+    for (size_t k = 0; k < index_paths.size(); k++) { fi[k].path = index_paths[k]; files.push_back(&fi[k]); }
+    for (Fastq* f : files) if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; }
     int64_t n_records = 0;
     for (;;) {
         const int a = fe.next(nullptr), b = fl.next(nullptr);
@@ -144,16 +249,28 @@ int main(int argc, char** argv)
             fprintf(stderr, "%s: %s holds %s records than %s (%lld pairs read)\n", PROG, fe.path.c_str(), a ? "more" : "fewer", fl.path.c_str(), (long long)n_records);
             return 1;
         }
+        for (size_t k = 0; k < index_paths.size(); k++) {
+            const int c = fi[k].next(nullptr);
+            if (c < 0) return 1;
+            if (c != a) {
+                fprintf(stderr, "%s: %s holds %s records than %s (%lld pairs read)\n", PROG, fi[k].path.c_str(), c ? "more" : "fewer", fe.path.c_str(), (long long)n_records);
+                return 1;
+            }
+        }
         if (!a) break;
         n_records++;
     }
-    for (Fastq* f : {&fe, &fl}) { fclose(f->fp); f->fp = nullptr; if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; } }
+    for (Fastq* f : files) { fclose(f->fp); f->fp = nullptr; if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; } }
 
     // ---- the device ----
     mipgen_accel* h = nullptr;
     if (svr_tool_handle(&h) != MIPGEN_OK) { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); return 1; }
     auto die = [&]() { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); mipgen_accel_destroy(h); return 1; };
-    if (mipgen_accel_reads_open(h, probes.data(), (int32_t)probes.size(), te, tl, mism) != MIPGEN_OK) return die();
+    if (by_sample) {
+        std::vector<const char*> bc;
+        for (const std::string& b : barcodes) bc.push_back(b.c_str());
+        if (mipgen_accel_reads_open_samples(h, probes.data(), (int32_t)probes.size(), te, tl, mism, bc.data(), (int32_t)bc.size(), bc_mism) != MIPGEN_OK) return die();
+    } else if (mipgen_accel_reads_open(h, probes.data(), (int32_t)probes.size(), te, tl, mism) != MIPGEN_OK) return die();
 
     // two chunks: the reader thread fills one while the device works on the other
     Chunk chunks[2];
@@ -164,11 +281,22 @@ int main(int argc, char** argv)
         for (int k = 0;; k ^= 1) {
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !full[k] || stop; }); if (stop) return; }
             Chunk& c = chunks[k];
-            c.ext.clear(); c.lig.clear(); c.ext_off.assign(1, 0); c.lig_off.assign(1, 0); c.n = 0; c.last = false;
+            c.ext.clear(); c.lig.clear(); c.idx.clear(); c.ext_off.assign(1, 0); c.lig_off.assign(1, 0); c.idx_off.assign(1, 0); c.n = 0; c.last = false;
+            std::string part[2];
             while (c.n < CHUNK_PAIRS) {
                 const int a = fe.next(&c.ext), b = fl.next(&c.lig);
                 if (a < 0 || b < 0 || a != b) { c.failed = true; break; }          // (the files changed since they were checked)
+                bool whole = true;
+                for (size_t k = 0; k < index_paths.size() && !c.failed; k++) {
+                    part[k].clear();
+                    if (fi[k].next(&part[k]) != a) c.failed = true;
+                    whole = whole && part[k].size() >= (size_t)index_len[k];
+                }
+                if (c.failed) break;
                 if (!a) { c.last = true; break; }
+                // the pair's index: the first j bases of each index read, or nothing when one of them is shorter than its j
+                for (size_t k = 0; whole && k < index_paths.size(); k++) c.idx.append(part[k], 0, (size_t)index_len[k]);
+                c.idx_off.push_back((int64_t)c.idx.size());
                 c.ext_off.push_back((int64_t)c.ext.size()); c.lig_off.push_back((int64_t)c.lig.size());
                 c.n++;
             }
@@ -183,7 +311,8 @@ int main(int argc, char** argv)
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return full[k]; }); }
         Chunk& c = chunks[k];
         if (c.failed) { fprintf(stderr, "%s: the FASTQ files changed while they were read\n", PROG); rc = 1; }
-        else if (c.n > 0 && mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data()) != MIPGEN_OK) {
+        else if (c.n > 0 && (by_sample ? mipgen_accel_reads_feed_samples(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data(), c.idx.data(), c.idx_off.data())
+                                       : mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data())) != MIPGEN_OK) {
             fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); rc = 1;
         }
         const bool done = rc != 0 || c.last;
@@ -193,17 +322,49 @@ int main(int argc, char** argv)
     }
     reader.join();
     if (rc) { mipgen_accel_destroy(h); return 1; }
-    std::vector<int64_t> reads(probes.size()), unique(probes.size());
+    const size_t n_probes = probes.size(), n_rows = by_sample ? barcodes.size() + 1 : 1;
+    std::vector<int64_t> reads(n_probes * n_rows), unique(n_probes * n_rows), row_pairs(n_rows);
     mipgen_read_totals tot;
-    if (mipgen_accel_reads_finish(h, reads.data(), unique.data(), &tot) != MIPGEN_OK) return die();
+    mipgen_sample_totals stot{0, 0};
+    if ((by_sample ? mipgen_accel_reads_finish_samples(h, reads.data(), unique.data(), &tot, &stot, row_pairs.data())
+                   : mipgen_accel_reads_finish(h, reads.data(), unique.data(), &tot)) != MIPGEN_OK) return die();
     mipgen_accel_destroy(h);
 
     FILE* out = fopen(out_path.c_str(), "w");
     if (!out) { fprintf(stderr, "%s: can't write %s\n", PROG, out_path.c_str()); return 1; }
-    fprintf(out, "mip_key\tmip_name\treads\tunique_tags\n");
-    for (size_t i = 0; i < rows.size(); i++)
-        fprintf(out, "%s\t%s\t%lld\t%lld\n", (*rows[i])[COL_KEY].c_str(), (*rows[i])[COL_NAME].c_str(), (long long)reads[i], (long long)unique[i]);
+    if (by_sample) {
+        fprintf(out, "sample\tmip_key\tmip_name\treads\tunique_tags\n");
+        for (size_t r = 0; r < n_rows; r++)
+            for (size_t i = 0; i < n_probes; i++)
+                if (reads[r * n_probes + i] > 0)
+                    fprintf(out, "%s\t%s\t%s\t%lld\t%lld\n", r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined", (*rows[i])[COL_KEY].c_str(), (*rows[i])[COL_NAME].c_str(),
+                            (long long)reads[r * n_probes + i], (long long)unique[r * n_probes + i]);
+    } else {
+        fprintf(out, "mip_key\tmip_name\treads\tunique_tags\n");
+        for (size_t i = 0; i < rows.size(); i++)
+            fprintf(out, "%s\t%s\t%lld\t%lld\n", (*rows[i])[COL_KEY].c_str(), (*rows[i])[COL_NAME].c_str(), (long long)reads[i], (long long)unique[i]);
+    }
     if (fclose(out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, out_path.c_str()); return 1; }
+    if (!samples_path.empty()) {
+        FILE* sf = fopen(samples_path.c_str(), "w");
+        if (!sf) { fprintf(stderr, "%s: can't write %s\n", PROG, samples_path.c_str()); return 1; }
+        fprintf(sf, "sample\tbarcode\tpairs\tassigned\tunique_tags\tprobes_seen\n");
+        for (size_t r = 0; r < n_rows; r++) {
+            long long assigned = 0, tags = 0, seen = 0;
+            for (size_t i = 0; i < n_probes; i++) { assigned += reads[r * n_probes + i]; tags += unique[r * n_probes + i]; seen += reads[r * n_probes + i] > 0; }
+            fprintf(sf, "%s\t%s\t%lld\t%lld\t%lld\t%lld\n", r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined", r + 1 < n_rows ? barcodes[r].c_str() : "*",
+                    (long long)row_pairs[r], assigned, tags, seen);
+        }
+        if (fclose(sf) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, samples_path.c_str()); return 1; }
+    }
+    if (by_sample) {
+        // the labels are over the NAMED samples: rows summed into row 0 (molecules of different samples are different molecules)
+        for (size_t i = 0; i < n_probes; i++) {
+            int64_t r_sum = 0, u_sum = 0;
+            for (size_t r = 0; r + 1 < n_rows; r++) { r_sum += reads[r * n_probes + i]; u_sum += unique[r * n_probes + i]; }
+            reads[i] = r_sum; unique[i] = u_sum;
+        }
+    }
     if (!label_path.empty()) {
         FILE* lab = fopen(label_path.c_str(), "w");
         if (!lab) { fprintf(stderr, "%s: can't write %s\n", PROG, label_path.c_str()); return 1; }
@@ -216,5 +377,7 @@ int main(int argc, char** argv)
     }
     fprintf(stderr, "%s: pairs %lld assigned %lld ambiguous %lld unassigned %lld tag_n %lld overflow %lld\n", PROG, (long long)tot.pairs, (long long)tot.assigned,
             (long long)tot.ambiguous, (long long)tot.unassigned, (long long)tot.tag_n, (long long)tot.overflow);
+    if (by_sample)
+        fprintf(stderr, "%s: samples %zu sample_none %lld sample_ambiguous %lld\n", PROG, barcodes.size(), (long long)stot.sample_none, (long long)stot.sample_ambiguous);
     return 0;
 }
