@@ -369,6 +369,41 @@ int mipgen_accel_reads_finish_samples(mipgen_accel* h, int64_t* reads, int64_t* 
                                       int64_t* row_pairs);
 int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity);
 
+/* ---- one consensus read per molecule (new entry points only: the ABI number does not change) ----
+ * The consensus model.  Probe, sample and tag rules are exactly those above: reads, unique_tags, the totals, row_pairs and the per-pair
+ * probe / sample indices of a consensus session EQUAL those of a plain or samples session on the same pairs.  A GROUP is all assigned pairs with a
+ * clean tag that share (row, probe, tag), row = 0 without barcodes; its FAMILY is their number.  The extension reads and the ligation reads of a group
+ * are collapsed separately, each behind its tag (the arms stay); the consensus of a side is as long as the shortest member of that side behind the tag.
+ * Per position, with q = clamp(quality byte - 33, 0, 93) and S[b] the sum of q over the members showing base b (a byte that is not upper-case A C G T
+ * casts no vote): the base is the b with the strictly largest S[b], or N when the largest is shared or every S is 0; v = S[best] - the sum of the other
+ * three, v = - the sum of all for N; the quality byte is 'I' for v > 40, '#' for v < 2, else v + 33.  Sums are exact (no overflow for any family).
+ * Groups come in ascending (row, probe, tag code) order - independent of feed order and of how the pairs were cut into feed calls.
+ *   open_consensus:   barcodes = NULL with n_samples = 0: one row; otherwise as open_samples.  arena_bytes: the device memory the session may use for
+ *                     retained reads (per feed call: twice its read bytes + 44 bytes per pair + at most 48 of alignment); 0 = half of the device memory that is
+ *                     free at open beside the tables.  Everything open / open_samples refuses, and MIPGEN_E_INVALID for ext_tag + lig_tag = 0, a negative
+ *                     arena_bytes, barcodes and n_samples that disagree, more than 2^31 cells.  Every check comes before any allocation.
+ *   feed_consensus:   as feed / feed_samples, with the quality bytes of both reads (they share the offsets of their bases); index_bytes / index_offsets
+ *                     are NULL for a session without barcodes.  The chunk stays on the device.  MIPGEN_E_NOMEM when the chunk does not fit what is left
+ *                     of the arena (or the device): the session is exactly as it was before the call, and finish_consensus works on what was fed.
+ *                     MIPGEN_E_INVALID beyond 2^31 - 1 pairs in a session.  last_assignment / last_samples work as in the other kinds.
+ *   finish_consensus: the outputs of finish_samples (sample_totals and row_pairs are left alone without barcodes) and sizes: groups and the bytes of
+ *                     all extension / ligation consensus reads; every output may be NULL.  sizes.n_groups is the sum of unique_tags.  The session is
+ *                     closed whichever way the call ends; the consensus reads stay on the handle until the next mipgen_accel_reads_open* call or
+ *                     mipgen_accel_destroy.
+ *   consensus_fetch:  per group cell (row * n + probe), tag (2 bits a base, the first tag base highest) and family; ext_off / lig_off: n_groups + 1
+ *                     offsets into the sequence and quality bytes of a side (ext_seq, ext_qual: sizes.ext_bytes each; no terminators).  Every pointer may
+ *                     be NULL.  MIPGEN_E_STATE when the handle holds no consensus reads (before a finish_consensus, after the next open).
+ * Feed, finish or last_samples of one kind on a session of another: MIPGEN_E_STATE, the session is left as it was and a later correct call works. */
+typedef struct mipgen_consensus_sizes { int64_t n_groups, ext_bytes, lig_bytes; } mipgen_consensus_sizes;
+int mipgen_accel_reads_open_consensus(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches,
+                                      const char* const* barcodes, int32_t n_samples, int32_t barcode_mismatches, int64_t arena_bytes);
+int mipgen_accel_reads_feed_consensus(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const char* ext_qual, const int64_t* ext_offsets, const char* lig_bytes,
+                                      const char* lig_qual, const int64_t* lig_offsets, const char* index_bytes, const int64_t* index_offsets);
+int mipgen_accel_reads_finish_consensus(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
+                                        int64_t* row_pairs, mipgen_consensus_sizes* sizes);
+int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t* tag, int32_t* family, int64_t* ext_off, char* ext_seq, char* ext_qual, int64_t* lig_off,
+                                       char* lig_seq, char* lig_qual);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -579,7 +614,9 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * 3 = replay + condense; 4 = genome pass of the last mipgen_accel_count_oligo_copies (always recorded);
  * 5 / 6 = the matrix-core SVR kernel / the feature kernel of the last mipgen_accel_score_candidates or mipgen_accel_score_probes call on a list
  * (>= 256 SVR candidates); 7 = k_read_assign summed over the feed calls since the last mipgen_accel_reads_open (timing enabled);
- * 8 = k_sample_assign summed over the feed calls since the last mipgen_accel_reads_open_samples (timing enabled). */
+ * 8 = k_sample_assign summed over the feed calls since the last mipgen_accel_reads_open_samples (timing enabled);
+ * 9 = the two k_consensus_vote kernels of the last mipgen_accel_reads_finish_consensus, 10 = its sort of (key, pair id) and the run boundaries
+ * (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

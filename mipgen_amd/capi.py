@@ -79,6 +79,10 @@ class SampleTotals(C.Structure):     # mipgen_sample_totals
     _fields_ = [(n, C.c_int64) for n in ("sample_none", "sample_ambiguous")]
 
 
+class ConsensusSizes(C.Structure):   # mipgen_consensus_sizes
+    _fields_ = [(n, C.c_int64) for n in ("n_groups", "ext_bytes", "lig_bytes")]
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -341,7 +345,13 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_feed_samples.argtypes = [vp, C.c_int64, C.c_void_p, i64p_, C.c_void_p, i64p_, C.c_void_p, i64p_]
     lib.mipgen_accel_reads_finish_samples.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals), C.POINTER(SampleTotals), i64p_]
     lib.mipgen_accel_reads_last_samples.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64]
-    for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples"):
+    lib.mipgen_accel_reads_open_consensus.argtypes = [vp, C.POINTER(Probe), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int64]
+    lib.mipgen_accel_reads_feed_consensus.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, i64p_, C.c_void_p, C.c_void_p, i64p_, C.c_void_p, i64p_]
+    lib.mipgen_accel_reads_finish_consensus.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals), C.POINTER(SampleTotals), i64p_, C.POINTER(ConsensusSizes)]
+    lib.mipgen_accel_reads_consensus_fetch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), i64p_, C.c_void_p, C.c_void_p, i64p_, C.c_void_p,
+                                                       C.c_void_p]
+    for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
+                 "feed_consensus", "finish_consensus", "consensus_fetch"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -420,6 +430,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_open", "mipgen_accel_reads_feed", "mipgen_accel_reads_finish", "mipgen_accel_reads_set_key_buffer",
     "mipgen_accel_reads_last_assignment",
     "mipgen_accel_reads_open_samples", "mipgen_accel_reads_feed_samples", "mipgen_accel_reads_finish_samples", "mipgen_accel_reads_last_samples",
+    "mipgen_accel_reads_open_consensus", "mipgen_accel_reads_feed_consensus", "mipgen_accel_reads_finish_consensus", "mipgen_accel_reads_consensus_fetch",
 ]
 
 
@@ -905,6 +916,77 @@ class Accel:
         totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
         totals.update({f[0]: int(getattr(stot, f[0])) for f in SampleTotals._fields_})
         return (reads, unique, totals, row_pairs, sample, probe) if want_assignment else (reads, unique, totals, row_pairs)
+
+    def consensus_fetch(self, sizes: "ConsensusSizes"):
+        """mipgen_accel_reads_consensus_fetch: the groups the handle holds as a list of (cell, tag code, family, ext_seq, ext_qual, lig_seq, lig_qual), the
+        sequences and qualities as bytes, in group order."""
+        G, nb_e, nb_l = int(sizes.n_groups), int(sizes.ext_bytes), int(sizes.lig_bytes)
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        cell = np.empty(G, dtype=np.int32); tag = np.empty(G, dtype=np.uint32); family = np.empty(G, dtype=np.int32)
+        eo = np.empty(G + 1, dtype=np.int64); lo = np.empty(G + 1, dtype=np.int64)
+        es, eq = np.empty(max(nb_e, 1), dtype=np.uint8), np.empty(max(nb_e, 1), dtype=np.uint8)
+        ls, lq = np.empty(max(nb_l, 1), dtype=np.uint8), np.empty(max(nb_l, 1), dtype=np.uint8)
+        self._check(self.lib.mipgen_accel_reads_consensus_fetch(self.h, cell.ctypes.data_as(i32p), tag.ctypes.data_as(C.POINTER(C.c_uint32)), family.ctypes.data_as(i32p),
+                                                                eo.ctypes.data_as(i64p), es.ctypes.data, eq.ctypes.data, lo.ctypes.data_as(i64p), ls.ctypes.data, lq.ctypes.data))
+        assert int(eo[G]) == nb_e and int(lo[G]) == nb_l
+        es, eq, ls, lq = es.tobytes(), eq.tobytes(), ls.tobytes(), lq.tobytes()
+        return [(int(cell[g]), int(tag[g]), int(family[g]), es[eo[g]:eo[g + 1]], eq[eo[g]:eo[g + 1]], ls[lo[g]:lo[g + 1]], lq[lo[g]:lo[g + 1]]) for g in range(G)]
+
+    def consensus_reads(self, arms: Sequence[tuple], ext_reads: Sequence[bytes], lig_reads: Sequence[bytes], ext_quals: Sequence[bytes], lig_quals: Sequence[bytes],
+                        index_reads: Optional[Sequence[bytes]] = None, barcodes: Optional[Sequence[bytes]] = None, barcode_mismatches: int = 0,
+                        tag_sizes: Tuple[int, int] = (5, 0), mismatches: int = 0, swap_reads: bool = False, chunks: int = 1, arena_bytes: int = 0,
+                        want_assignment: bool = False):
+        """mipgen_accel_reads_open_consensus / _feed_consensus / _finish_consensus / _consensus_fetch: the counts of count_reads (barcodes None: reads and
+        unique_tags have one row) or count_reads_samples, and one consensus read pair per (row, probe, tag) group.  ext_quals / lig_quals: the quality string
+        of every read, as long as the read.  Returns (reads[rows][n], unique_tags[rows][n], totals dict, row_pairs[rows] or None, groups[, sample index per
+        pair or None, probe index per pair]); groups as consensus_fetch gives them."""
+        if swap_reads:
+            ext_reads, lig_reads, ext_quals, lig_quals = lig_reads, ext_reads, lig_quals, ext_quals
+        n, n_pairs = len(arms), len(ext_reads)
+        assert len(lig_reads) == len(ext_quals) == len(lig_quals) == n_pairs and (barcodes is None) == (index_reads is None)
+        n_samples = len(barcodes) if barcodes is not None else 0
+        rows = n_samples + 1 if barcodes is not None else 1
+        arr = (Probe * max(n, 1))()
+        for i, q in enumerate(arms):
+            arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
+        bc = (C.c_char_p * max(n_samples, 1))(*barcodes) if barcodes is not None else None
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+
+        def pack(rs):
+            off = np.zeros(len(rs) + 1, dtype=np.int64)
+            np.cumsum([len(r) for r in rs], out=off[1:])
+            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
+
+        (eb, eo), (lb, lo), (eq, eqo), (lq, lqo) = pack(ext_reads), pack(lig_reads), pack(ext_quals), pack(lig_quals)
+        assert np.array_equal(eo, eqo) and np.array_equal(lo, lqo), "a quality string is as long as its read"
+        ib, io = pack(index_reads) if index_reads is not None else (None, None)
+        self._check(self.lib.mipgen_accel_reads_open_consensus(self.h, arr, n, tag_sizes[0], tag_sizes[1], mismatches, bc, n_samples, barcode_mismatches, arena_bytes))
+        sample = np.empty(n_pairs, dtype=np.int32) if barcodes is not None else None
+        probe = np.empty(n_pairs, dtype=np.int32)
+        try:
+            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                self._check(self.lib.mipgen_accel_reads_feed_consensus(
+                    self.h, b - a, eb[eo[a]:].ctypes.data, eq[eo[a]:].ctypes.data, eo[a:b + 1].ctypes.data_as(i64p), lb[lo[a]:].ctypes.data, lq[lo[a]:].ctypes.data,
+                    lo[a:b + 1].ctypes.data_as(i64p), ib[io[a]:].ctypes.data if ib is not None else None, io[a:b + 1].ctypes.data_as(i64p) if ib is not None else None))
+                if want_assignment and b > a:
+                    if sample is not None:
+                        self._check(self.lib.mipgen_accel_reads_last_samples(self.h, sample[a:b].ctypes.data_as(i32p), b - a))
+                    self._check(self.lib.mipgen_accel_reads_last_assignment(self.h, probe[a:b].ctypes.data_as(i32p), b - a))
+        except Exception:
+            self.lib.mipgen_accel_reads_finish_consensus(self.h, None, None, None, None, None, None)
+            raise
+        reads = np.empty((rows, n), dtype=np.int64)
+        unique = np.empty((rows, n), dtype=np.int64)
+        row_pairs = np.empty(rows, dtype=np.int64) if barcodes is not None else None
+        tot, stot, sizes = ReadTotals(), SampleTotals(), ConsensusSizes()
+        self._check(self.lib.mipgen_accel_reads_finish_consensus(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot), C.byref(stot),
+                                                                 row_pairs.ctypes.data_as(i64p) if row_pairs is not None else None, C.byref(sizes)))
+        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
+        if barcodes is not None:
+            totals.update({f[0]: int(getattr(stot, f[0])) for f in SampleTotals._fields_})
+        groups = self.consensus_fetch(sizes)
+        return (reads, unique, totals, row_pairs, groups, sample, probe) if want_assignment else (reads, unique, totals, row_pairs, groups)
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

@@ -143,6 +143,7 @@ void mipgen_accel_destroy(mipgen_accel* h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     mipgen_reads_release(h);
+    mipgen_consensus_release(h);
     h->model.release(); h->model_t.release(); h->sv_norm.release(); h->sv_coef.release(); h->sv_center.release(); h->regions.release(); h->bases.release(); h->unmap.release(); h->copy.release();
     h->log_tiles.release(); h->svr_tiles.release(); h->ld_tiles.release(); h->scores.release(); h->records.release();
     h->emitted.release(); h->survivors.release(); h->emitted_per_region.release(); h->pos_region.release(); h->pos_local.release();
@@ -579,6 +580,8 @@ double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which)
     if (h && which == 6) return h->list_feat_ms;
     if (h && which == 7) return h->reads_assign_ms;
     if (h && which == 8) return h->sample_assign_ms;
+    if (h && which == 9) return h->consensus_vote_ms;
+    if (h && which == 10) return h->consensus_sort_ms;
     if (!h || !h->timing) return -1.0;
     if (hipSetDevice(h->device) != hipSuccess) return -1.0;
     double total = 0.0;

@@ -138,6 +138,7 @@ struct RescoreList {
 };
 
 struct ReadsSession;                  // accel_reads.hip
+struct ConsensusResult;               // accel_reads.hip: the consensus reads of the last mipgen_accel_reads_finish_consensus
 
 struct mipgen_accel {
     int device = 0;
@@ -255,6 +256,9 @@ struct mipgen_accel {
     int64_t reads_key_cap = 0;       // mipgen_accel_reads_set_key_buffer (0: default)
     double reads_assign_ms = -1.0;   // k_read_assign over the feed calls of the last session (timing enabled)
     double sample_assign_ms = -1.0;  // k_sample_assign over the feed calls of the last samples session (timing enabled)
+    ConsensusResult* consensus = nullptr;   // held from mipgen_accel_reads_finish_consensus until the next mipgen_accel_reads_open* or mipgen_accel_destroy
+    double consensus_vote_ms = -1.0; // k_consensus_vote_wave + k_consensus_vote_wg of the last mipgen_accel_reads_finish_consensus (timing enabled)
+    double consensus_sort_ms = -1.0; // ... its radix sort of (key, pair id) and the run boundaries
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;
@@ -318,4 +322,5 @@ int mipgen_ensure_events(mipgen_accel* h);
 int mipgen_ensure_tiles(mipgen_accel* h, int32_t method);
 int mipgen_pb_check(mipgen_accel* h);                            // accel_score.hip
 void mipgen_reads_release(mipgen_accel* h);                      // accel_reads.hip: closes an open read-counting session
+void mipgen_consensus_release(mipgen_accel* h);                  // accel_reads.hip: lets go of the consensus reads the handle holds
 }

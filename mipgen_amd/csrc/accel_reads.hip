@@ -1,5 +1,6 @@
-// accel_reads.hip — reads and unique tags per probe from smMIP read pairs behind the C ABI: mipgen_accel_reads_open / _feed / _finish, and
-// per sample of a multiplexed lane: mipgen_accel_reads_open_samples / _feed_samples / _finish_samples / _last_samples.
+// accel_reads.hip — reads and unique tags per probe from smMIP read pairs behind the C ABI: mipgen_accel_reads_open / _feed / _finish,
+// per sample of a multiplexed lane: mipgen_accel_reads_open_samples / _feed_samples / _finish_samples / _last_samples, and with one consensus
+// read per molecule: mipgen_accel_reads_open_consensus / _feed_consensus / _finish_consensus / _consensus_fetch.
 // A session owns every buffer it uses (ReadsSession); of the handle it takes the device and the stream, nothing else.
 #include "accel_internal.h"
 
@@ -9,6 +10,32 @@ struct SeedTableBufs {
     DevBuf<int32_t> probes;
     SeedTable view{};
     void release() { slots.release(); start.release(); keys.release(); probes.release(); }
+};
+
+// one feed call of a consensus session, retained: ONE device block (ChunkLayout) with the records, keys and pair ids of its pairs and their bases and qualities
+struct ArenaChunk { uint8_t* block; size_t bytes; int64_t pair0, n; };
+
+// the parts of a chunk's block, each at a multiple of 8 bytes: the quality of a base lies `qdelta` bytes behind it on both sides
+struct ChunkLayout {
+    size_t recs, keys, ids, ext, lig, ext_qual, lig_qual, total;
+    int64_t qdelta;
+    ChunkLayout(int64_t n, size_t eb, size_t lb)
+    {
+        auto pad8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+        recs = 0; keys = recs + (size_t)n * sizeof(ConsensusPair); ids = keys + (size_t)n * 8; ext = ids + pad8((size_t)n * 4);
+        lig = ext + pad8(eb); ext_qual = lig + pad8(lb); lig_qual = ext_qual + pad8(eb);
+        total = lig_qual + pad8(lb) + 8;                     // (+ 8: k_read_assign fetches aligned 32-bit words, up to 5 bytes beyond the last read)
+        qdelta = (int64_t)(pad8(eb) + pad8(lb));
+    }
+};
+
+struct ConsensusResult {
+    int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
+    DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
+    DevBuf<int32_t> family;
+    DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
+    DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); }
 };
 
 struct ReadsSession {
@@ -36,13 +63,29 @@ struct ReadsSession {
     DevBuf<int32_t> row, sample_index;
     DevBuf<unsigned long long> row_pairs;
     DevBuf<SampleCounters> sctr;
+    // a consensus session: the reads of every feed call stay resident, chunk by chunk, within a budget of arena_cap bytes
+    bool consensus = false;
+    std::vector<ArenaChunk> chunks;
+    size_t arena_cap = 0, arena_used = 0;
+    int64_t total_pairs = 0;
+    DevBuf<ConsensusCounters> cctr;
+    DevBuf<uint64_t> c_keys_in, c_keys_out;                  // finish: the (key, pair id) of every pair, as fed and sorted
+    DevBuf<uint32_t> c_ids_in, c_ids_out, c_start, c_order;
+    DevBuf<ConsensusPair> c_recs;
+    DevBuf<int64_t> c_ext_len, c_lig_len;
     void release()
     {
+        for (const ArenaChunk& c : chunks) (void)hipFree(c.block);
+        chunks.clear();
+        cctr.release(); c_keys_in.release(); c_keys_out.release(); c_ids_in.release(); c_ids_out.release(); c_start.release(); c_order.release(); c_recs.release();
+        c_ext_len.release(); c_lig_len.release();
         sample_slots.release(); idx_bytes.release(); idx_off.release(); row.release(); sample_index.release(); row_pairs.release(); sctr.release();
         probes.release(); ext_seeds.release(); lig_seeds.release(); ext_bytes.release(); lig_bytes.release(); ext_off.release(); lig_off.release();
         assign.release(); reads.release(); unique.release(); keys.release(); keys_alt.release(); sort_temp.release(); ctr.release();
     }
 };
+
+enum { FEED_PLAIN = 0, FEED_SAMPLES = 1, FEED_CONSENSUS = 2 };
 
 static const int64_t READS_KEY_CAP_DEFAULT = (int64_t)1 << 26, READS_KEY_CAP_MAX = (int64_t)1 << 30;
 
@@ -198,6 +241,15 @@ void mipgen_reads_release(mipgen_accel* h)
     h->reads = nullptr;
 }
 
+void mipgen_consensus_release(mipgen_accel* h)
+{
+    if (!h->consensus) return;
+    (void)hipStreamSynchronize(h->stream);
+    h->consensus->release();
+    delete h->consensus;
+    h->consensus = nullptr;
+}
+
 int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys)
 {
     if (!h || n_keys < 0 || n_keys > READS_KEY_CAP_MAX) return fail(MIPGEN_E_INVALID, "bad arguments");
@@ -205,12 +257,14 @@ int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys)
     return MIPGEN_OK;
 }
 
-// barcodes == nullptr: a plain session
+// barcodes == nullptr: a session without samples; consensus: the reads stay resident within arena_bytes (0: the default)
 static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches, const char* const* barcodes,
-                     int32_t n_samples, int32_t barcode_mismatches)
+                     int32_t n_samples, int32_t barcode_mismatches, bool consensus = false, int64_t arena_bytes = 0)
 {
     if (!h || !probes || n < 1) return fail(MIPGEN_E_INVALID, "bad arguments");
     if (ext_tag < 0 || lig_tag < 0 || ext_tag + lig_tag > READS_MAX_TAG) return fail(MIPGEN_E_INVALID, "tag sizes %d,%d: at most %d tag bases in all", ext_tag, lig_tag, READS_MAX_TAG);
+    if (consensus && ext_tag + lig_tag == 0) return fail(MIPGEN_E_INVALID, "tag sizes 0,0: without tag bases there are no molecules to collapse");
+    if (consensus && arena_bytes < 0) return fail(MIPGEN_E_INVALID, "arena_bytes %lld is negative", (long long)arena_bytes);
     if (max_mismatches < 0 || max_mismatches > 2) return fail(MIPGEN_E_INVALID, "max_mismatches %d outside 0..2", max_mismatches);
     size_t shortest = MIPGEN_MAX_OLIGO;
     for (int i = 0; i < n; i++) {
@@ -245,6 +299,9 @@ static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int
         if ((uint64_t)rows * (uint64_t)n > ((uint64_t)1 << 32))
             return fail(MIPGEN_E_INVALID, "%d samples + undetermined x %d probes: more than 2^32 cells", n_samples, n);
     }
+    // (the sentinel key of a pair in no group is the key bit above the cell index: DESIGN 4.11)
+    if (consensus && (uint64_t)rows * (uint64_t)n > ((uint64_t)1 << 31))
+        return fail(MIPGEN_E_INVALID, "%lld rows x %d probes: more than 2^31 cells in a consensus session", (long long)rows, n);
     if (h->reads) return fail(MIPGEN_E_STATE, "a read-counting session is open: mipgen_accel_reads_finish closes it");
     const int S = (int)std::min<size_t>(shortest, READS_MAX_SEED);
 
@@ -273,16 +330,22 @@ static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int
     size_t free_b = 0;
     if (int rc = free_device_bytes(&free_b)) return rc;
     const bool tags = ext_tag + lig_tag > 0;
-    int64_t key_cap = !tags ? 0 : h->reads_key_cap > 0 ? h->reads_key_cap : READS_KEY_CAP_DEFAULT;
+    // (a consensus session keeps no key list across feed calls: its groups come from the sort of finish)
+    int64_t key_cap = !tags || consensus ? 0 : h->reads_key_cap > 0 ? h->reads_key_cap : READS_KEY_CAP_DEFAULT;
     const size_t fixed = (size_t)n * (sizeof(ReadProbe) + 2 * 4) + cells * 16 + sample_slots.size() * sizeof(SampleSlot) + (size_t)rows * 8 + (TE.slots.size() + TL.slots.size()) * 4 + (TE.keys.size() + TL.keys.size()) * 12 + ((size_t)64 << 20);
-    if (tags && h->reads_key_cap <= 0)
+    if (tags && !consensus && h->reads_key_cap <= 0)
         while (key_cap > 1024 && fixed + (size_t)key_cap * 16 > free_b / 2) key_cap /= 2;      // the default gives way to what is free; half is left for the reads
     if (fixed + (size_t)key_cap * 16 > free_b)
         return fail(MIPGEN_E_NOMEM, "read counter: tables of %d probes x %lld rows and %lld keys need %zu MiB of device memory, %zu MiB are free", n, (long long)rows,
                     (long long)key_cap, (fixed + (size_t)key_cap * 16) >> 20, free_b >> 20);
 
+    mipgen_consensus_release(h);                                            // the consensus reads of an earlier session end here
     ReadsSession* S_ = new ReadsSession;
     h->reads = S_;
+    S_->consensus = consensus;
+    // the arena's default: half of what is free beside the tables; the other half is left to finish (56 bytes per pair of sort buffers and records, and the
+    // consensus reads, which are no longer than the reads retained)
+    if (consensus) S_->arena_cap = arena_bytes > 0 ? (size_t)arena_bytes : (free_b - fixed) / 2;
     auto give_up = [&](int rc) { mipgen_reads_release(h); return rc; };
     S_->P = {ext_tag, lig_tag, max_mismatches, S, seed_mask, n, 0};
     S_->key_cap = key_cap;
@@ -295,6 +358,7 @@ static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int
         (key_cap && (S_->keys.reserve((size_t)key_cap) || S_->keys_alt.reserve((size_t)key_cap))))
         return give_up(MIPGEN_E_NOMEM);
     if (barcodes && (S_->sample_slots.reserve(sample_slots.size()) || S_->row_pairs.reserve((size_t)rows) || S_->sctr.reserve(1))) return give_up(MIPGEN_E_NOMEM);
+    if (consensus && S_->cctr.reserve(1)) return give_up(MIPGEN_E_NOMEM);
     int rc = upload_seed_table(h, TE, S_->ext_seeds);
     if (rc == MIPGEN_OK) rc = upload_seed_table(h, TL, S_->lig_seeds);
     hipError_t e = hipSuccess;
@@ -302,6 +366,7 @@ static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int
     if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->reads.p, 0, cells * sizeof(unsigned long long), h->stream);
     if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->unique.p, 0, cells * sizeof(unsigned long long), h->stream);
     if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->ctr.p, 0, sizeof(ReadsCounters), h->stream);
+    if (rc == MIPGEN_OK && e == hipSuccess && consensus) e = hipMemsetAsync(S_->cctr.p, 0, sizeof(ConsensusCounters), h->stream);
     if (barcodes) {
         if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemcpyAsync(S_->sample_slots.p, sample_slots.data(), sample_slots.size() * sizeof(SampleSlot), hipMemcpyHostToDevice, h->stream);
         if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->row_pairs.p, 0, (size_t)rows * sizeof(unsigned long long), h->stream);
@@ -317,18 +382,102 @@ static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int
     return MIPGEN_OK;
 }
 
-// with_index: a call of the samples kind
-static int feed_impl(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets, bool with_index,
-                     const char* index_bytes, const int64_t* index_offsets)
+// A feed call of a consensus session.  Everything that can refuse the chunk - the arena's budget, free device memory, every allocation - comes before the first
+// copy or launch: a refused chunk leaves the session as it was.  The chunk's bases and qualities go straight into its block and stay there; k_read_assign and
+// k_sample_assign read them where they lie.  The kernel trusts the offsets: feed_impl has checked them.
+static int feed_consensus(mipgen_accel* h, ReadsSession* S, int64_t n_pairs, const char* ext_bytes, const char* ext_qual, const int64_t* ext_offsets, size_t eb,
+                          const char* lig_bytes, const char* lig_qual, const int64_t* lig_offsets, size_t lb, const char* index_bytes, const int64_t* index_offsets, size_t ib)
+{
+    const bool with_index = S->samples;
+    const ChunkLayout L(n_pairs, eb, lb);
+    if (L.total > S->arena_cap - S->arena_used)
+        return fail(MIPGEN_E_NOMEM, "consensus reads: a chunk of %lld pairs needs %zu bytes of the arena, %zu of %zu are left (open the session with a larger arena_bytes)",
+                    (long long)n_pairs, L.total, S->arena_cap - S->arena_used, S->arena_cap);
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    const size_t have = (S->ext_off.cap + S->lig_off.cap + S->keys.cap) * 8 + S->assign.cap * 4 + S->idx_bytes.cap + S->idx_off.cap * 8 + (S->row.cap + S->sample_index.cap) * 4;
+    const size_t need = 2 * (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 12 + (with_index ? ib + (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 8 : 0);
+    if (L.total + need + need / 8 + ((size_t)64 << 20) > free_b + have)
+        return fail(MIPGEN_E_NOMEM, "consensus reads: a chunk of %lld pairs needs %zu MiB of device memory, %zu MiB are free", (long long)n_pairs, (L.total + need) >> 20,
+                    (free_b + have) >> 20);
+    // (keys: k_read_assign's sort-unique keys of this chunk, written and never read - a consensus session counts its unique tags from its groups)
+    if (S->ext_off.reserve((size_t)n_pairs + 1) || S->lig_off.reserve((size_t)n_pairs + 1) || S->assign.reserve((size_t)n_pairs) || S->keys.reserve((size_t)n_pairs))
+        return MIPGEN_E_NOMEM;
+    if (with_index && (S->idx_bytes.reserve(ib + 8) || S->idx_off.reserve((size_t)n_pairs + 1) || S->row.reserve((size_t)n_pairs) || S->sample_index.reserve((size_t)n_pairs)))
+        return MIPGEN_E_NOMEM;
+    uint8_t* block = nullptr;
+    if (hipMalloc((void**)&block, L.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIPGEN_E_NOMEM, "consensus reads: hipMalloc of a chunk of %zu bytes failed", L.total);
+    }
+    hipStream_t st = h->stream;
+    hipError_t e = hipSuccess;
+    auto step = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    if (eb) { step(hipMemcpyAsync(block + L.ext, ext_bytes, eb, hipMemcpyHostToDevice, st)); step(hipMemcpyAsync(block + L.ext_qual, ext_qual, eb, hipMemcpyHostToDevice, st)); }
+    if (lb) { step(hipMemcpyAsync(block + L.lig, lig_bytes, lb, hipMemcpyHostToDevice, st)); step(hipMemcpyAsync(block + L.lig_qual, lig_qual, lb, hipMemcpyHostToDevice, st)); }
+    step(hipMemcpyAsync(S->ext_off.p, ext_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+    step(hipMemcpyAsync(S->lig_off.p, lig_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+    step(hipMemsetAsync(&S->ctr.p->n_keys, 0, sizeof(unsigned long long), st));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    const bool timed = h->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventCreate(&ev[2]) == hipSuccess &&
+                       hipEventCreate(&ev[3]) == hipSuccess;
+    if (with_index) {
+        if (ib) step(hipMemcpyAsync(S->idx_bytes.p, index_bytes, ib, hipMemcpyHostToDevice, st));
+        step(hipMemcpyAsync(S->idx_off.p, index_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+        if (timed) (void)hipEventRecord(ev[0], st);
+        if (e == hipSuccess)
+            step(mipgen_launch_sample_assign(st, &S->sample_table, n_pairs, S->idx_bytes.p, S->idx_off.p, index_offsets[0], S->row.p, S->sample_index.p, S->row_pairs.p, S->sctr.p));
+        if (timed) (void)hipEventRecord(ev[1], st);
+    }
+    const int32_t* row = with_index ? S->row.p : nullptr;
+    if (timed) (void)hipEventRecord(ev[2], st);
+    if (e == hipSuccess)
+        step(mipgen_launch_read_assign(st, &S->P, S->probes.p, &S->ext_seeds.view, &S->lig_seeds.view, 0, n_pairs, block + L.ext, S->ext_off.p, ext_offsets[0], block + L.lig,
+                                       S->lig_off.p, lig_offsets[0], S->assign.p, S->reads.p, S->keys.p, (int64_t)S->keys.cap, S->ctr.p, row));
+    if (timed) (void)hipEventRecord(ev[3], st);
+    if (e == hipSuccess)
+        step(mipgen_launch_member_keys(st, &S->P, n_pairs, (uint32_t)S->total_pairs, S->assign.p, row, block + L.ext, S->ext_off.p, ext_offsets[0], block + L.lig, S->lig_off.p,
+                                       lig_offsets[0], L.qdelta, 1ull << S->end_bit, reinterpret_cast<uint64_t*>(block + L.keys), reinterpret_cast<uint32_t*>(block + L.ids),
+                                       reinterpret_cast<ConsensusPair*>(block + L.recs), S->cctr.p));
+    const hipError_t es = hipStreamSynchronize(st);                        // the caller's arrays are free when the call returns
+    step(es);
+    float ms = 0.f;
+    if (timed && e == hipSuccess) {
+        if (with_index && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) h->sample_assign_ms += ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) h->reads_assign_ms += ms;
+    }
+    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+    if (e != hipSuccess) {
+        (void)hipFree(block);
+        return fail(MIPGEN_E_HIP, "mipgen_accel_reads_feed_consensus: %s", hipGetErrorString(e));
+    }
+    S->chunks.push_back({block, L.total, S->total_pairs, n_pairs});
+    S->total_pairs += n_pairs;
+    S->arena_used += L.total;
+    S->last_pairs = n_pairs;
+    return MIPGEN_OK;
+}
+
+// kind: of the call (FEED_*); a consensus call carries the qualities, and the index reads if its session has samples
+static int feed_impl(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets, int kind,
+                     const char* index_bytes, const int64_t* index_offsets, const char* ext_qual = nullptr, const char* lig_qual = nullptr)
 {
     if (!h || n_pairs < 0 || (n_pairs > 0 && (!ext_bytes || !ext_offsets || !lig_bytes || !lig_offsets))) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (with_index && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (kind == FEED_SAMPLES && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (kind == FEED_CONSENSUS && n_pairs > 0 && (!ext_qual || !lig_qual)) return fail(MIPGEN_E_INVALID, "bad arguments: no qualities");
     if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (h->reads->consensus != (kind == FEED_CONSENSUS))
+        return fail(MIPGEN_E_STATE, kind == FEED_CONSENSUS ? "the open session keeps no reads: it was not opened by mipgen_accel_reads_open_consensus"
+                                                           : "the open session is a consensus session: mipgen_accel_reads_feed_consensus feeds it");
+    const bool with_index = kind == FEED_CONSENSUS ? h->reads->samples : kind == FEED_SAMPLES;
     if (h->reads->samples != with_index)
         return fail(MIPGEN_E_STATE, with_index ? "the open session has no samples: mipgen_accel_reads_feed feeds it" : "the open session has samples: mipgen_accel_reads_feed_samples feeds it");
+    if (kind == FEED_CONSENSUS && with_index && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments: the session has samples and the call no index reads");
     if (n_pairs > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld pairs in one call (at most 2^31 - 1)", (long long)n_pairs);
     ReadsSession* S = h->reads;
-    S->last_pairs = 0;
+    if (S->consensus && S->total_pairs + n_pairs > 0x7fffffff)
+        return fail(MIPGEN_E_INVALID, "%lld + %lld pairs: a consensus session holds at most 2^31 - 1 (pair ids are 32-bit)", (long long)S->total_pairs, (long long)n_pairs);
+    if (!S->consensus || n_pairs == 0) S->last_pairs = 0;                   // (a refused chunk leaves a consensus session as it was, its last assignment included)
     if (n_pairs == 0) return MIPGEN_OK;
     // the kernel trusts the offsets: they are checked here
     for (int f = 0; f < (with_index ? 3 : 2); f++) {
@@ -341,6 +490,7 @@ static int feed_impl(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, co
     const size_t eb = (size_t)(ext_offsets[n_pairs] - ext_offsets[0]), lb = (size_t)(lig_offsets[n_pairs] - lig_offsets[0]);
     const size_t ib = with_index ? (size_t)(index_offsets[n_pairs] - index_offsets[0]) : 0;
     HIP_TRY(hipSetDevice(h->device));
+    if (S->consensus) return feed_consensus(h, S, n_pairs, ext_bytes, ext_qual, ext_offsets, eb, lig_bytes, lig_qual, lig_offsets, lb, index_bytes, index_offsets, ib);
     size_t free_b = 0;
     if (int rc = free_device_bytes(&free_b)) return rc;
     const size_t have = S->ext_bytes.cap + S->lig_bytes.cap + (S->ext_off.cap + S->lig_off.cap) * 8 + S->assign.cap * 4 + S->idx_bytes.cap + S->idx_off.cap * 8 +
@@ -418,13 +568,13 @@ int mipgen_accel_reads_open_samples(mipgen_accel* h, const mipgen_probe* probes,
 
 int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets)
 {
-    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, false, nullptr, nullptr);
+    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, FEED_PLAIN, nullptr, nullptr);
 }
 
 int mipgen_accel_reads_feed_samples(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets,
                                     const char* index_bytes, const int64_t* index_offsets)
 {
-    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, true, index_bytes, index_offsets);
+    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, FEED_SAMPLES, index_bytes, index_offsets);
 }
 
 int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity)
@@ -450,13 +600,99 @@ int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, in
     return MIPGEN_OK;
 }
 
+// The groups of a consensus session and their consensus reads into R; unique tags per cell - the groups of the cell - into S->unique.
+static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R)
+{
+    hipStream_t st = h->stream;
+    const int64_t N = S->total_pairs;
+    h->consensus_vote_ms = h->consensus_sort_ms = -1.0;
+    ConsensusCounters cc;
+    HIP_TRY(hipMemcpyAsync(&cc, S->cctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t M = (int64_t)cc.members;                                   // pairs in a group: the keys below the sentinel
+    if (M == 0) return MIPGEN_OK;
+    // every pair's (key, id) and record, chunk after chunk, in feed order
+    if (S->c_keys_in.reserve((size_t)N) || S->c_keys_out.reserve((size_t)N) || S->c_ids_in.reserve((size_t)N) || S->c_ids_out.reserve((size_t)N) || S->c_recs.reserve((size_t)N))
+        return MIPGEN_E_NOMEM;
+    for (const ArenaChunk& c : S->chunks) {
+        const ChunkLayout L(c.n, 0, 0);                                      // (the per-pair parts lie in front of the bytes)
+        HIP_TRY(hipMemcpyAsync(S->c_recs.p + c.pair0, c.block + L.recs, (size_t)c.n * sizeof(ConsensusPair), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(S->c_keys_in.p + c.pair0, c.block + L.keys, (size_t)c.n * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(S->c_ids_in.p + c.pair0, c.block + L.ids, (size_t)c.n * 4, hipMemcpyDeviceToDevice, st));
+    }
+    // one scratch buffer for the sort, the run boundaries and the three scans (sized for the most entries any of them sees)
+    size_t t_sort = 0, t_runs = 0, t_u32 = 0, t_i64 = 0;
+    const int sort_bits = S->end_bit + 1;                                    // the cell and tag bits that can be set, and the sentinel's
+    HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, S->c_keys_in.p, S->c_keys_out.p, S->c_ids_in.p, S->c_ids_out.p, N, sort_bits));
+    HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, S->c_keys_out.p, M, S->c_keys_in.p, reinterpret_cast<int32_t*>(S->c_ids_in.p), &S->cctr.p->groups));
+    HIP_TRY(mipgen_consensus_scan_u32(st, nullptr, &t_u32, reinterpret_cast<int32_t*>(S->c_ids_in.p), S->c_ids_in.p, M + 1));
+    HIP_TRY(mipgen_consensus_scan_i64(st, nullptr, &t_i64, nullptr, nullptr, M + 1));
+    if (S->sort_temp.reserve(std::max(std::max(t_sort, t_runs), std::max(t_u32, t_i64)) + 16)) return MIPGEN_E_NOMEM;
+    size_t tb = S->sort_temp.cap;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    const bool timed = h->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventCreate(&ev[2]) == hipSuccess &&
+                       hipEventCreate(&ev[3]) == hipSuccess;
+    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } events{ev};
+    // sort; the runs of the member keys: group key and family size (the fed arrays are free once sorted, and take them)
+    if (timed) (void)hipEventRecord(ev[0], st);
+    HIP_TRY(mipgen_consensus_sort(st, S->sort_temp.p, &tb, S->c_keys_in.p, S->c_keys_out.p, S->c_ids_in.p, S->c_ids_out.p, N, sort_bits));
+    uint64_t* group_keys = S->c_keys_in.p;
+    int32_t* family = reinterpret_cast<int32_t*>(S->c_ids_in.p);
+    tb = S->sort_temp.cap;
+    HIP_TRY(mipgen_consensus_runs(st, S->sort_temp.p, &tb, S->c_keys_out.p, M, group_keys, family, &S->cctr.p->groups));
+    if (timed) (void)hipEventRecord(ev[1], st);
+    HIP_TRY(hipMemcpyAsync(&cc, S->cctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t G = (int64_t)cc.groups;
+    if (G < 1 || G > M) return fail(MIPGEN_E_STATE, "consensus reads: %lld groups of %lld members", (long long)G, (long long)M);
+    if (R->keys.reserve((size_t)G) || R->family.reserve((size_t)G) || R->ext_off.reserve((size_t)G + 1) || R->lig_off.reserve((size_t)G + 1) || S->c_start.reserve((size_t)G) ||
+        S->c_order.reserve((size_t)G) || S->c_ext_len.reserve((size_t)G + 1) || S->c_lig_len.reserve((size_t)G + 1))
+        return MIPGEN_E_NOMEM;
+    HIP_TRY(hipMemcpyAsync(R->keys.p, group_keys, (size_t)G * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R->family.p, family, (size_t)G * 4, hipMemcpyDeviceToDevice, st));
+    tb = S->sort_temp.cap;
+    HIP_TRY(mipgen_consensus_scan_u32(st, S->sort_temp.p, &tb, R->family.p, S->c_start.p, G));
+    HIP_TRY(mipgen_launch_consensus_partition(st, R->family.p, G, S->c_order.p, S->cctr.p));
+    HIP_TRY(hipMemcpyAsync(&cc, S->cctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_small = (int64_t)cc.n_small, n_big = (int64_t)cc.n_big;
+    if (n_small + n_big != G) return fail(MIPGEN_E_STATE, "consensus reads: %lld + %lld groups listed of %lld", (long long)n_small, (long long)n_big, (long long)G);
+    // the length of every group's two consensus reads (entry G stays 0), and from their exclusive sums where each is written
+    HIP_TRY(hipMemsetAsync(S->c_ext_len.p, 0, (size_t)(G + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(S->c_lig_len.p, 0, (size_t)(G + 1) * 8, st));
+    HIP_TRY(mipgen_launch_consensus_len(st, S->P.te, S->P.tl, G, S->c_order.p, n_big, S->c_start.p, R->family.p, S->c_ids_out.p, S->c_recs.p, S->c_ext_len.p, S->c_lig_len.p));
+    tb = S->sort_temp.cap;
+    HIP_TRY(mipgen_consensus_scan_i64(st, S->sort_temp.p, &tb, S->c_ext_len.p, R->ext_off.p, G + 1));
+    tb = S->sort_temp.cap;
+    HIP_TRY(mipgen_consensus_scan_i64(st, S->sort_temp.p, &tb, S->c_lig_len.p, R->lig_off.p, G + 1));
+    int64_t totals[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&totals[0], R->ext_off.p + G, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&totals[1], R->lig_off.p + G, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (R->ext_seq.reserve((size_t)totals[0] + 1) || R->ext_qual.reserve((size_t)totals[0] + 1) || R->lig_seq.reserve((size_t)totals[1] + 1) ||
+        R->lig_qual.reserve((size_t)totals[1] + 1))
+        return MIPGEN_E_NOMEM;
+    if (timed) (void)hipEventRecord(ev[2], st);
+    HIP_TRY(mipgen_launch_consensus_vote(st, S->P.te, S->P.tl, G, S->c_order.p, n_small, n_big, S->c_start.p, R->family.p, S->c_ids_out.p, S->c_recs.p, R->ext_off.p,
+                                         R->lig_off.p, R->ext_seq.p, R->ext_qual.p, R->lig_seq.p, R->lig_qual.p));
+    if (timed) (void)hipEventRecord(ev[3], st);
+    // unique tags of a cell = its groups: the group keys ARE the sorted, duplicate-free key list of a plain session
+    HIP_TRY(mipgen_launch_reads_histogram(st, R->keys.p, G, S->unique.p));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    if (timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) h->consensus_sort_ms = ms;
+    if (timed && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) h->consensus_vote_ms = ms;
+    R->n_groups = G; R->ext_bytes = totals[0]; R->lig_bytes = totals[1];
+    return MIPGEN_OK;
+}
+
 static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
                        int64_t* row_pairs)
 {
     HIP_TRY(hipSetDevice(h->device));
     const size_t n = (size_t)S->P.n_probes * (size_t)S->rows;                // cells
     const bool tags = S->P.te + S->P.tl > 0;
-    if (tags) {
+    if (tags && !S->consensus) {                                             // (a consensus session: consensus_finish counted its groups into `unique`)
         if (int rc = sort_unique_keys(h, S)) return rc;
         HIP_TRY(mipgen_launch_reads_histogram(h->stream, S->keys.p, S->key_ub, S->unique.p));
     }
@@ -481,6 +717,7 @@ int mipgen_accel_reads_finish(mipgen_accel* h, int64_t* reads, int64_t* unique_t
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (h->reads->consensus) return fail(MIPGEN_E_STATE, "the open session is a consensus session: mipgen_accel_reads_finish_consensus closes it");
     if (h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has samples: mipgen_accel_reads_finish_samples closes it");
     const int rc = finish_impl(h, h->reads, reads, unique_tags, totals, nullptr, nullptr);
     mipgen_reads_release(h);
@@ -491,10 +728,75 @@ int mipgen_accel_reads_finish_samples(mipgen_accel* h, int64_t* reads, int64_t* 
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (h->reads->consensus) return fail(MIPGEN_E_STATE, "the open session is a consensus session: mipgen_accel_reads_finish_consensus closes it");
     if (!h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has no samples: mipgen_accel_reads_finish closes it");
     const int rc = finish_impl(h, h->reads, reads, unique_tags, totals, sample_totals, row_pairs);
     mipgen_reads_release(h);
     return rc;
+}
+
+int mipgen_accel_reads_open_consensus(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches,
+                                      const char* const* barcodes, int32_t n_samples, int32_t barcode_mismatches, int64_t arena_bytes)
+{
+    if ((barcodes == nullptr) != (n_samples == 0) || n_samples < 0) return fail(MIPGEN_E_INVALID, "bad arguments: barcodes and n_samples disagree");
+    return open_impl(h, probes, n, ext_tag, lig_tag, max_mismatches, barcodes, n_samples, barcode_mismatches, true, arena_bytes);
+}
+
+int mipgen_accel_reads_feed_consensus(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const char* ext_qual, const int64_t* ext_offsets, const char* lig_bytes,
+                                      const char* lig_qual, const int64_t* lig_offsets, const char* index_bytes, const int64_t* index_offsets)
+{
+    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, FEED_CONSENSUS, index_bytes, index_offsets, ext_qual, lig_qual);
+}
+
+int mipgen_accel_reads_finish_consensus(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
+                                        int64_t* row_pairs, mipgen_consensus_sizes* sizes)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (!h->reads->consensus) return fail(MIPGEN_E_STATE, "the open session keeps no reads: mipgen_accel_reads_finish%s closes it", h->reads->samples ? "_samples" : "");
+    HIP_TRY(hipSetDevice(h->device));
+    ConsensusResult* R = new ConsensusResult;
+    int rc = consensus_finish(h, h->reads, R);
+    if (rc == MIPGEN_OK) rc = finish_impl(h, h->reads, reads, unique_tags, totals, sample_totals, row_pairs);
+    mipgen_reads_release(h);
+    if (rc != MIPGEN_OK) { R->release(); delete R; return rc; }
+    h->consensus = R;
+    if (sizes) *sizes = {R->n_groups, R->ext_bytes, R->lig_bytes};
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t* tag, int32_t* family, int64_t* ext_off, char* ext_seq, char* ext_qual, int64_t* lig_off,
+                                       char* lig_seq, char* lig_qual)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    HIP_TRY(hipSetDevice(h->device));
+    const ConsensusResult* R = h->consensus;
+    const size_t G = (size_t)R->n_groups;
+    if (G == 0) {
+        if (ext_off) ext_off[0] = 0;
+        if (lig_off) lig_off[0] = 0;
+        return MIPGEN_OK;
+    }
+    hipStream_t st = h->stream;
+    std::vector<uint64_t> keys;
+    if (cell || tag) {
+        keys.resize(G);
+        HIP_TRY(hipMemcpyAsync(keys.data(), R->keys.p, G * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (family) HIP_TRY(hipMemcpyAsync(family, R->family.p, G * 4, hipMemcpyDeviceToHost, st));
+    if (ext_off) HIP_TRY(hipMemcpyAsync(ext_off, R->ext_off.p, (G + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (lig_off) HIP_TRY(hipMemcpyAsync(lig_off, R->lig_off.p, (G + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (ext_seq && R->ext_bytes) HIP_TRY(hipMemcpyAsync(ext_seq, R->ext_seq.p, (size_t)R->ext_bytes, hipMemcpyDeviceToHost, st));
+    if (ext_qual && R->ext_bytes) HIP_TRY(hipMemcpyAsync(ext_qual, R->ext_qual.p, (size_t)R->ext_bytes, hipMemcpyDeviceToHost, st));
+    if (lig_seq && R->lig_bytes) HIP_TRY(hipMemcpyAsync(lig_seq, R->lig_seq.p, (size_t)R->lig_bytes, hipMemcpyDeviceToHost, st));
+    if (lig_qual && R->lig_bytes) HIP_TRY(hipMemcpyAsync(lig_qual, R->lig_qual.p, (size_t)R->lig_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t g = 0; g < keys.size(); g++) {
+        if (cell) cell[g] = (int32_t)(keys[g] >> 32);
+        if (tag) tag[g] = (uint32_t)keys[g];
+    }
+    return MIPGEN_OK;
 }
 
 }  // extern "C"

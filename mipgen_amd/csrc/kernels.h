@@ -118,4 +118,20 @@ hipError_t mipgen_launch_sample_assign(hipStream_t, const SampleTable*, int64_t 
                                        int32_t* sample_index, unsigned long long* row_pairs, SampleCounters* sctr);
 hipError_t mipgen_launch_reads_histogram(hipStream_t, const uint64_t* keys, int64_t n, unsigned long long* unique);
 hipError_t mipgen_reads_sort_unique(hipStream_t, void* temp, size_t* temp_bytes, uint64_t* keys, uint64_t* alt, int64_t n, int end_bit, unsigned long long* n_out);
+// kernels_consensus.hip (the hipCUB steps: temp == nullptr asks for the scratch size)
+hipError_t mipgen_launch_member_keys(hipStream_t, const ReadsParams*, int64_t n_pairs, uint32_t pair0, const int32_t* assign, const int32_t* row, const uint8_t* ext_bytes,
+                                     const int64_t* ext_off, int64_t ext_base, const uint8_t* lig_bytes, const int64_t* lig_off, int64_t lig_base, int64_t qdelta,
+                                     uint64_t sentinel, uint64_t* keys, uint32_t* ids, ConsensusPair* recs, ConsensusCounters* cctr);
+hipError_t mipgen_consensus_sort(hipStream_t, void* temp, size_t* temp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* ids_in, uint32_t* ids_out, int64_t n,
+                                 int end_bit);
+hipError_t mipgen_consensus_runs(hipStream_t, void* temp, size_t* temp_bytes, const uint64_t* keys, int64_t n, uint64_t* group_keys, int32_t* family,
+                                 unsigned long long* n_groups);
+hipError_t mipgen_consensus_scan_u32(hipStream_t, void* temp, size_t* temp_bytes, const int32_t* family, uint32_t* group_start, int64_t n);
+hipError_t mipgen_consensus_scan_i64(hipStream_t, void* temp, size_t* temp_bytes, const int64_t* len, int64_t* off, int64_t n);
+hipError_t mipgen_launch_consensus_partition(hipStream_t, const int32_t* family, int64_t n_groups, uint32_t* order, ConsensusCounters* cctr);
+hipError_t mipgen_launch_consensus_len(hipStream_t, int te, int tl, int64_t n_groups, const uint32_t* order, int64_t n_big, const uint32_t* group_start, const int32_t* family,
+                                       const uint32_t* ids, const ConsensusPair* recs, int64_t* ext_len, int64_t* lig_len);
+hipError_t mipgen_launch_consensus_vote(hipStream_t, int te, int tl, int64_t n_groups, const uint32_t* order, int64_t n_small, int64_t n_big, const uint32_t* group_start,
+                                        const int32_t* family, const uint32_t* ids, const ConsensusPair* recs, const int64_t* ext_off, const int64_t* lig_off, uint8_t* ext_seq,
+                                        uint8_t* ext_qual, uint8_t* lig_seq, uint8_t* lig_qual);
 }

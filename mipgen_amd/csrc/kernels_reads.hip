@@ -50,18 +50,6 @@ __device__ static inline void seed_lookup(const SeedTable& T, uint64_t key, uint
     }
 }
 
-// `n` tag bases from the head of a read into *tag (2 bits each, appended below what is there); false if one of them is not A C G T
-__device__ static inline bool pack_tag(const uint8_t* __restrict__ b, int64_t from, int n, uint32_t* tag)
-{
-    bool clean = true;
-    for (int i = 0; i < n; i++) {
-        const uint32_t c = reads_base_code(b[from + i]);
-        clean = clean && c < 4u;
-        *tag = (*tag << 2) | (c & 3u);
-    }
-    return clean;
-}
-
 __device__ static inline int wave_count(bool pred) { return __popcll(__ballot(pred)); }
 
 __global__ __launch_bounds__(256) void k_read_assign(ReadsParams P, const ReadProbe* __restrict__ probes, SeedTable TE, SeedTable TL, int64_t pair0, int64_t n_pairs,

@@ -1,5 +1,6 @@
-// reads_common.h — what kernels_reads.hip and accel_reads.hip share of the read counter: the packed probe arms, the seed tables, the
-// base code and the hash of a seed key.  The host packs the arms and builds the tables with the same functions the kernel reads them with.
+// reads_common.h — what kernels_reads.hip, kernels_consensus.hip and accel_reads.hip share of the read counter: the packed probe arms,
+// the seed tables, the base code, the hash of a seed key and the packing of a tag.  The host packs the arms and builds the tables with the same functions
+// the kernel reads them with.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,3 +80,26 @@ __host__ __device__ static inline uint32_t reads_hash(uint64_t k)           // s
     k ^= k >> 31;
     return (uint32_t)k;
 }
+
+// `n` tag bases from the head of a read into *tag (2 bits each, appended below what is there); false if one of them is not A C G T.  The one packing of a
+// tag: k_read_assign's sort-unique keys and k_member_keys' group keys are built with it.
+__device__ static inline bool pack_tag(const uint8_t* __restrict__ b, int64_t from, int n, uint32_t* tag)
+{
+    bool clean = true;
+    for (int i = 0; i < n; i++) {
+        const uint32_t c = reads_base_code(b[from + i]);
+        clean = clean && c < 4u;
+        *tag = (*tag << 2) | (c & 3u);
+    }
+    return clean;
+}
+
+// ---- consensus reads per tag group ----
+#define CONSENSUS_WG_FAMILY 256      // a family of more members than this is voted by a whole 256-thread workgroup (its four wavefronts stride over the members); up
+                                     // to it by one wavefront.  Below 64 members per wavefront the LDS combine and its two barriers per round cost more than they save.
+#define CONSENSUS_MAX_Q 93           // q = clamp(byte - 33, 0, 93)
+
+// where the two reads of a retained pair lie in the arena: the first byte of each read (tag included), its length, and the distance from a base to its quality
+struct alignas(16) ConsensusPair { const uint8_t* ext; const uint8_t* lig; int64_t qdelta; int32_t ext_len, lig_len; };      // 32 bytes
+
+struct ConsensusCounters { unsigned long long members, groups, n_small, n_big; };

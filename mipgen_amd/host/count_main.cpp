@@ -25,6 +25,12 @@
 //   -labels    the value per probe over the NAMED samples: reads and unique tags summed over their rows (molecules of different samples are different
 //              molecules), log10tags of that sum
 //   stderr     a second line: "mipgen_count: samples N sample_none X sample_ambiguous Y"
+// One consensus read per molecule (without -consensus every byte written is what it was):
+//   -consensus PREFIX       PREFIX.ext.fq and PREFIX.lig.fq: per (sample, probe, tag) group the quality-weighted consensus of its extension reads and of its
+//                           ligation reads, each behind its tag, in ascending (sample, probe, tag) order.  Header: "@smc<ordinal> <sample label | * without
+//                           -barcodes | undetermined> <tab> mip_key <tab> tag <tab> family"; the ordinal is the group's place among ALL groups, from 0
+//   -min_family k           only the groups of at least k pairs are written (default 1)
+//   stderr     a last line: "mipgen_count: consensus groups G written W members M" (M: the pairs of all G groups)
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -50,7 +56,8 @@ static int usage(const std::string& msg)
             "-barcodes samples.tsv : label <tab> barcode per sample: counts per sample (-o gains a sample column); needs -index_reads\n"
             "-index_reads i1.fq[,i2.fq] : the index reads of the pairs; -index_length j1[,j2] : bases taken from each (default: the barcode length)\n"
             "-barcode_mismatches n : substitutions allowed between index and barcode, 0 or 1 (default 0)\n"
-            "-samples file : sample, barcode, pairs, assigned, unique_tags, probes_seen per sample\n");
+            "-samples file : sample, barcode, pairs, assigned, unique_tags, probes_seen per sample\n"
+            "-consensus prefix : prefix.ext.fq and prefix.lig.fq, one consensus read pair per (sample, probe, tag) group; -min_family k : groups of at least k pairs (default 1)\n");
     return 1;
 }
 
@@ -72,8 +79,9 @@ struct Fastq {
         while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r')) n--;
         return n;
     }
-    // 1: a record, its sequence appended to *seq (NULL: checked only); 0: end of file; -1: malformed (message printed)
-    int next(std::string* seq)
+    // 1: a record, its sequence appended to *seq (NULL: checked only) and its quality line to *qual (NULL: dropped); 0: end of file; -1: malformed
+    // (message printed)
+    int next(std::string* seq, std::string* qual = nullptr)
     {
         ssize_t n = get();
         if (n < 0) return 0;
@@ -86,12 +94,13 @@ struct Fastq {
         if (n == 0 || line[0] != '+') return bad("the third line of a record does not start with '+'");
         if ((n = get()) < 0) { lineno++; return bad("the file ends before the quality line"); }
         if (n != len) return bad("sequence and quality differ in length");
+        if (qual) qual->append(line, (size_t)len);
         return 1;
     }
 };
 
 struct Chunk {
-    std::string ext, lig, idx;
+    std::string ext, lig, idx, ext_qual, lig_qual;          // (the qualities only with -consensus: they share the offsets of their bases)
     std::vector<int64_t> ext_off, lig_off, idx_off;
     int64_t n = 0;
     bool last = false, failed = false;
@@ -148,7 +157,9 @@ static bool parse_int_list(const std::string& v, std::vector<long>& out)
 int main(int argc, char** argv)
 {
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
-    bool swap = false, bc_mism_given = false;
+    long min_family = 1;
+    bool swap = false, bc_mism_given = false, min_family_given = false;
+    std::string consensus_prefix;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
@@ -177,6 +188,8 @@ int main(int argc, char** argv)
         else if (a == "-samples") samples_path = v;
         else if (a == "-index_reads") index_arg = v;
         else if (a == "-index_length") index_len_arg = v;
+        else if (a == "-consensus") { if (v.empty()) return usage("-consensus takes a prefix"); consensus_prefix = v; }
+        else if (a == "-min_family") { if (!svr_parse_int(v.c_str(), &min_family) || min_family < 1) return usage("-min_family must be 1 or more"); min_family_given = true; }
         else if (a == "-barcode_mismatches") {
             if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-barcode_mismatches must be 0 or 1");
             bc_mism = (int)iv; bc_mism_given = true;
@@ -192,6 +205,9 @@ int main(int argc, char** argv)
     if (by_sample && index_arg.empty()) return usage("-barcodes needs -index_reads i1.fq[,i2.fq]");
     if (!by_sample && !index_arg.empty()) return usage("-index_reads needs -barcodes samples.tsv");
     if (!by_sample && (!samples_path.empty() || !index_len_arg.empty() || bc_mism_given)) return usage("-samples, -index_length and -barcode_mismatches need -barcodes samples.tsv");
+    const bool consensus = !consensus_prefix.empty();
+    if (min_family_given && !consensus) return usage("-min_family needs -consensus prefix");
+    if (consensus && te + tl == 0) return usage("-consensus needs tag bases: with -tag_sizes 0,0 there are no molecules to collapse");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
     if (by_sample) {
@@ -262,11 +278,22 @@ int main(int argc, char** argv)
     }
     for (Fastq* f : files) { fclose(f->fp); f->fp = nullptr; if (!f->open()) { fprintf(stderr, "%s: can't open FASTQ file %s\n", PROG, f->path.c_str()); return 1; } }
 
+    FILE* cons_out[2] = {nullptr, nullptr};
+    const std::string cons_path[2] = {consensus_prefix + ".ext.fq", consensus_prefix + ".lig.fq"};
+    if (consensus)
+        for (int k = 0; k < 2; k++)
+            if (!(cons_out[k] = fopen(cons_path[k].c_str(), "w"))) return usage("-consensus " + consensus_prefix + ": can't write " + cons_path[k]);
+
     // ---- the device ----
     mipgen_accel* h = nullptr;
     if (svr_tool_handle(&h) != MIPGEN_OK) { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); return 1; }
     auto die = [&]() { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); mipgen_accel_destroy(h); return 1; };
-    if (by_sample) {
+    if (consensus) {
+        std::vector<const char*> bc;
+        for (const std::string& b : barcodes) bc.push_back(b.c_str());
+        if (mipgen_accel_reads_open_consensus(h, probes.data(), (int32_t)probes.size(), te, tl, mism, by_sample ? bc.data() : nullptr, (int32_t)bc.size(), bc_mism, 0) != MIPGEN_OK)
+            return die();
+    } else if (by_sample) {
         std::vector<const char*> bc;
         for (const std::string& b : barcodes) bc.push_back(b.c_str());
         if (mipgen_accel_reads_open_samples(h, probes.data(), (int32_t)probes.size(), te, tl, mism, bc.data(), (int32_t)bc.size(), bc_mism) != MIPGEN_OK) return die();
@@ -281,10 +308,10 @@ int main(int argc, char** argv)
         for (int k = 0;; k ^= 1) {
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !full[k] || stop; }); if (stop) return; }
             Chunk& c = chunks[k];
-            c.ext.clear(); c.lig.clear(); c.idx.clear(); c.ext_off.assign(1, 0); c.lig_off.assign(1, 0); c.idx_off.assign(1, 0); c.n = 0; c.last = false;
+            c.ext.clear(); c.lig.clear(); c.idx.clear(); c.ext_qual.clear(); c.lig_qual.clear(); c.ext_off.assign(1, 0); c.lig_off.assign(1, 0); c.idx_off.assign(1, 0); c.n = 0; c.last = false;
             std::string part[2];
             while (c.n < CHUNK_PAIRS) {
-                const int a = fe.next(&c.ext), b = fl.next(&c.lig);
+                const int a = fe.next(&c.ext, consensus ? &c.ext_qual : nullptr), b = fl.next(&c.lig, consensus ? &c.lig_qual : nullptr);
                 if (a < 0 || b < 0 || a != b) { c.failed = true; break; }          // (the files changed since they were checked)
                 bool whole = true;
                 for (size_t k = 0; k < index_paths.size() && !c.failed; k++) {
@@ -311,7 +338,9 @@ int main(int argc, char** argv)
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return full[k]; }); }
         Chunk& c = chunks[k];
         if (c.failed) { fprintf(stderr, "%s: the FASTQ files changed while they were read\n", PROG); rc = 1; }
-        else if (c.n > 0 && (by_sample ? mipgen_accel_reads_feed_samples(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data(), c.idx.data(), c.idx_off.data())
+        else if (c.n > 0 && (consensus ? mipgen_accel_reads_feed_consensus(h, c.n, c.ext.data(), c.ext_qual.data(), c.ext_off.data(), c.lig.data(), c.lig_qual.data(), c.lig_off.data(),
+                                                                           by_sample ? c.idx.data() : nullptr, by_sample ? c.idx_off.data() : nullptr)
+                             : by_sample ? mipgen_accel_reads_feed_samples(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data(), c.idx.data(), c.idx_off.data())
                                        : mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data())) != MIPGEN_OK) {
             fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); rc = 1;
         }
@@ -326,8 +355,16 @@ int main(int argc, char** argv)
     std::vector<int64_t> reads(n_probes * n_rows), unique(n_probes * n_rows), row_pairs(n_rows);
     mipgen_read_totals tot;
     mipgen_sample_totals stot{0, 0};
-    if ((by_sample ? mipgen_accel_reads_finish_samples(h, reads.data(), unique.data(), &tot, &stot, row_pairs.data())
-                   : mipgen_accel_reads_finish(h, reads.data(), unique.data(), &tot)) != MIPGEN_OK) return die();
+    mipgen_consensus_sizes csz{0, 0, 0};
+    if ((consensus ? mipgen_accel_reads_finish_consensus(h, reads.data(), unique.data(), &tot, &stot, row_pairs.data(), &csz)
+         : by_sample ? mipgen_accel_reads_finish_samples(h, reads.data(), unique.data(), &tot, &stot, row_pairs.data())
+                     : mipgen_accel_reads_finish(h, reads.data(), unique.data(), &tot)) != MIPGEN_OK) return die();
+    std::vector<int32_t> g_cell((size_t)csz.n_groups), g_family((size_t)csz.n_groups);
+    std::vector<uint32_t> g_tag((size_t)csz.n_groups);
+    std::vector<int64_t> g_off[2] = {std::vector<int64_t>((size_t)csz.n_groups + 1), std::vector<int64_t>((size_t)csz.n_groups + 1)};
+    std::string g_seq[2] = {std::string((size_t)csz.ext_bytes, '\0'), std::string((size_t)csz.lig_bytes, '\0')}, g_qual[2] = {g_seq[0], g_seq[1]};
+    if (consensus && mipgen_accel_reads_consensus_fetch(h, g_cell.data(), g_tag.data(), g_family.data(), g_off[0].data(), &g_seq[0][0], &g_qual[0][0], g_off[1].data(), &g_seq[1][0],
+                                                        &g_qual[1][0]) != MIPGEN_OK) return die();
     mipgen_accel_destroy(h);
 
     FILE* out = fopen(out_path.c_str(), "w");
@@ -357,6 +394,30 @@ int main(int argc, char** argv)
         }
         if (fclose(sf) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, samples_path.c_str()); return 1; }
     }
+    long long cons_written = 0, cons_members = 0;
+    if (consensus) {
+        const int T = te + tl;
+        for (int64_t g = 0; g < csz.n_groups; g++) {
+            cons_members += g_family[(size_t)g];
+            if (g_family[(size_t)g] < min_family) continue;
+            const size_t r = (size_t)g_cell[(size_t)g] / n_probes, i = (size_t)g_cell[(size_t)g] % n_probes;
+            char tag[33];
+            for (int j = 0; j < T; j++) tag[j] = "ACGT"[(g_tag[(size_t)g] >> (2 * (T - 1 - j))) & 3u];
+            tag[T] = 0;
+            for (int k = 0; k < 2; k++) {
+                const int64_t a = g_off[k][(size_t)g], len = g_off[k][(size_t)g + 1] - a;
+                fprintf(cons_out[k], "@smc%lld %s\t%s\t%s\t%d\n", (long long)g, !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined",
+                        (*rows[i])[COL_KEY].c_str(), tag, g_family[(size_t)g]);
+                fwrite(g_seq[k].data() + a, 1, (size_t)len, cons_out[k]);
+                fputs("\n+\n", cons_out[k]);
+                fwrite(g_qual[k].data() + a, 1, (size_t)len, cons_out[k]);
+                fputc('\n', cons_out[k]);
+            }
+            cons_written++;
+        }
+        for (int k = 0; k < 2; k++)
+            if (fclose(cons_out[k]) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, cons_path[k].c_str()); return 1; }
+    }
     if (by_sample) {
         // the labels are over the NAMED samples: rows summed into row 0 (molecules of different samples are different molecules)
         for (size_t i = 0; i < n_probes; i++) {
@@ -379,5 +440,6 @@ int main(int argc, char** argv)
             (long long)tot.ambiguous, (long long)tot.unassigned, (long long)tot.tag_n, (long long)tot.overflow);
     if (by_sample)
         fprintf(stderr, "%s: samples %zu sample_none %lld sample_ambiguous %lld\n", PROG, barcodes.size(), (long long)stot.sample_none, (long long)stot.sample_ambiguous);
+    if (consensus) fprintf(stderr, "%s: consensus groups %lld written %lld members %lld\n", PROG, (long long)csz.n_groups, cons_written, cons_members);
     return 0;
 }
