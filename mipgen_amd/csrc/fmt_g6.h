@@ -12,11 +12,21 @@
 #define FMT_HD static inline
 #endif
 
+// The error-free products below hold only while a product that was rounded once is not fused into the sum that consumes it.  hipcc contracts by
+// default: `n = p + e` became fma(s, t.hi, e), which counts the rounding error of p twice, and a value one ulp from a tie of the sixth digit
+// printed on the wrong side of it (-0x1.eae96bcb9c0c4p+308, just below 1.000005e+93: "-1.00001e+93" for the C library's "-1e+93").
+#ifdef __clang__
+#define FMT_EXACT _Pragma("clang fp contract(off)")
+#else
+#define FMT_EXACT
+#endif
+
 struct Pow10DD { double hi, lo; };
 
 // v * 10^k rounded to the nearest integer (ties to even); v > 0 finite, result < 2^53
 FMT_HD double fmt_scale_round(double v, int k, const Pow10DD* tab)
 {
+    FMT_EXACT
     double s = v, slo = 0.0;
     int left = k;
     while (left != 0) {                                   // 10^k in one or two table factors (|k| can exceed the double range for denormals)

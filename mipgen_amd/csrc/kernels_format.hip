@@ -10,7 +10,8 @@
 //   k_fmt_count   emitted candidates per row block            -> exclusive scan = rank of the block's first record
 //   k_fmt_length  record lengths (they depend on the rank: mip_name carries the running index) per block -> exclusive scan = byte offset
 //   k_fmt_write   the bytes
-// Numbers are printed as the C library prints them: fmt_g6.h is printf("%g") to the last digit (checked against glibc on 1.5e7 values).
+// Numbers are printed as the C library prints them: fmt_g6.h is printf("%g") to the last digit (tests/test_fmt_cpu.py holds its host side against the
+// C library on the crafted values of tests/fmt_cases.py and 2e6 random bit patterns, tests/test_gpu_format.py the device side on the crafted values).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include "kernels.h"

@@ -196,3 +196,29 @@ def compare_outputs(meta: dict, work: str, keys=("collapsed_mips", "picked_mips"
         assert hashlib.sha256(norm).hexdigest() == meta["sha256"]["all_mips_normalised"]
     else:
         assert hashlib.sha256(got_all).hexdigest() == meta["sha256"]["all_mips"]
+
+
+# ---- planted scores: the dense score buffer of the current result window overwritten in place (tests/test_gpu_format.py) -----------------------
+HIP_MEMCPY_HOST_TO_DEVICE = 1                                 # hipMemcpyKind
+
+
+def plant_scores(acc, scores: np.ndarray, window: Optional[int] = None) -> None:
+    """Overwrite the dense scores of the window scored last with `scores` (float64, one per dense candidate of that window, in dense order): a
+    host-to-device hipMemcpy of the whole array to the pointer of mipgen_accel_result_device_ptrs, on the HIP runtime the library itself is linked
+    against (its symbols are reached through the library's own handle, so no second runtime is loaded).  What the library then downloads must be
+    the planted bits: that also pins the pointer to candidate 0 of the window.  `window`: its index in a batch of several windows."""
+    import ctypes as C
+    scores = np.ascontiguousarray(scores, dtype=np.float64)
+    wi = acc.window_info(0 if window is None else window)
+    assert scores.shape == (wi["n_candidates"],), (scores.shape, wi)
+    acc.synchronize()
+    ptr, _ = acc.result_device_ptrs()
+    if scores.size:
+        assert ptr != 0
+        memcpy = acc.lib.hipMemcpy
+        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        memcpy.restype = C.c_int
+        rc = memcpy(C.c_void_p(ptr), scores.ctypes.data_as(C.c_void_p), scores.nbytes, HIP_MEMCPY_HOST_TO_DEVICE)
+        assert rc == 0, f"hipMemcpy failed: hipError_t {rc}"
+    back, _ = acc.download(wi["first_candidate"], wi["n_candidates"])
+    assert np.array_equal(back.view(np.uint64), scores.view(np.uint64)), "the downloaded scores are not the planted bits"
