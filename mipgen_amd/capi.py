@@ -213,6 +213,25 @@ def region_array(regions: Sequence[RegionData]):
     return arr
 
 
+def probe_array(arms: Sequence[tuple]):
+    """(ext_seq, lig_seq) bytes per probe -> the ctypes array of Probe that the read sessions take: the arms and nothing else."""
+    arr = (Probe * max(len(arms), 1))()
+    for i, q in enumerate(arms):
+        arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
+    return arr
+
+
+def c_strings(items: Sequence[Optional[bytes]]):
+    return (C.c_char_p * max(len(items), 1))(*items)
+
+
+def pack_reads(reads: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
+    """Reads as the feed calls take them: their bytes end to end (+ one NUL) as a uint8 array, and the int64 offset of each (+ the end)."""
+    off = np.zeros(len(reads) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in reads], out=off[1:])
+    return np.frombuffer(b"".join(reads) + b"\0", dtype=np.uint8), off
+
+
 def n_sizes_all(p: Params) -> int:
     if p.max_capture_size < p.min_capture_size:
         return 0
@@ -819,49 +838,92 @@ class Accel:
             feats.ctypes.data_as(dp) if feats is not None else None, ints))
         return scores, feats, ints
 
+    def _read_session(self, arms, ext_reads, lig_reads, quals=None, index_reads=None, barcodes=None, barcode_mismatches=0, tag_sizes=(5, 0), mismatches=0,
+                      swap_reads=False, chunks=1, key_buffer=0, arena_bytes=0, want_assignment=False):
+        """One read session of any kind through its own entry points - with samples when `barcodes` is given, a consensus session when `quals` = (ext_quals,
+        lig_quals) is: open, feed in `chunks` cuts (with the per-pair downloads if want_assignment), finish, and the groups of a consensus session.  An error
+        while feeding closes the session through its finish with null outputs.  Returns (reads[rows][n], unique_tags[rows][n], totals dict, row_pairs[rows] or
+        None, groups or None, sample index per pair or None, probe index per pair)."""
+        lib, h = self.lib, self.h
+        samples, consensus = barcodes is not None, quals is not None
+        if swap_reads:
+            ext_reads, lig_reads = lig_reads, ext_reads
+            quals = quals[::-1] if consensus else None
+        n, n_pairs = len(arms), len(ext_reads)
+        n_samples = len(barcodes) if samples else 0
+        rows = n_samples + 1
+        assert len(lig_reads) == n_pairs and (index_reads is None) == (not samples) and (not samples or len(index_reads) == n_pairs)
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        packed = {"ext": pack_reads(ext_reads), "lig": pack_reads(lig_reads)}
+        if samples:
+            packed["index"] = pack_reads(index_reads)
+        if consensus:
+            assert len(quals[0]) == len(quals[1]) == n_pairs
+            packed["ext_qual"], packed["lig_qual"] = pack_reads(quals[0]), pack_reads(quals[1])
+            assert np.array_equal(packed["ext"][1], packed["ext_qual"][1]) and np.array_equal(packed["lig"][1], packed["lig_qual"][1]), \
+                "a quality string is as long as its read"
+
+        def cut(name, a, b):
+            """The pairs a..b of one packed list as the entry points take them: the bytes from pair a on, and the offsets a..b."""
+            data, off = packed[name]
+            return data[off[a]:].ctypes.data, off[a:b + 1].ctypes.data_as(i64p)
+
+        arr = probe_array(arms)
+        bc = c_strings(barcodes) if samples else None
+        common = (h, arr, n, tag_sizes[0], tag_sizes[1], mismatches)
+        if consensus:                                              # (keeps no key list: the key buffer size is not its concern)
+            self._check(lib.mipgen_accel_reads_open_consensus(*common, bc, n_samples, barcode_mismatches, arena_bytes))
+            feed, finish, n_out = lib.mipgen_accel_reads_feed_consensus, lib.mipgen_accel_reads_finish_consensus, 6
+        else:
+            self._check(lib.mipgen_accel_reads_set_key_buffer(h, key_buffer))
+            try:                                                   # (only the open reads the key buffer size)
+                if samples:
+                    self._check(lib.mipgen_accel_reads_open_samples(*common, bc, n_samples, barcode_mismatches))
+                    feed, finish, n_out = lib.mipgen_accel_reads_feed_samples, lib.mipgen_accel_reads_finish_samples, 5
+                else:
+                    self._check(lib.mipgen_accel_reads_open(*common))
+                    feed, finish, n_out = lib.mipgen_accel_reads_feed, lib.mipgen_accel_reads_finish, 3
+            finally:
+                lib.mipgen_accel_reads_set_key_buffer(h, 0)
+        sample = np.empty(n_pairs, dtype=np.int32) if samples else None
+        probe = np.empty(n_pairs, dtype=np.int32)
+        try:
+            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                e, eo = cut("ext", a, b)
+                l, lo = cut("lig", a, b)
+                if consensus:
+                    args = (e, cut("ext_qual", a, b)[0], eo, l, cut("lig_qual", a, b)[0], lo)
+                    args += cut("index", a, b) if samples else (None, None)
+                else:
+                    args = (e, eo, l, lo) + (cut("index", a, b) if samples else ())
+                self._check(feed(h, b - a, *args))
+                if want_assignment and b > a:
+                    if samples:
+                        self._check(lib.mipgen_accel_reads_last_samples(h, sample[a:b].ctypes.data_as(i32p), b - a))
+                    self._check(lib.mipgen_accel_reads_last_assignment(h, probe[a:b].ctypes.data_as(i32p), b - a))
+        except Exception:
+            finish(h, *[None] * n_out)
+            raise
+        reads = np.empty((rows, n), dtype=np.int64)
+        unique = np.empty((rows, n), dtype=np.int64)
+        row_pairs = np.empty(rows, dtype=np.int64) if samples else None
+        tot, stot, sizes = ReadTotals(), SampleTotals(), ConsensusSizes()
+        outs = (reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot), C.byref(stot), row_pairs.ctypes.data_as(i64p) if samples else None, C.byref(sizes))
+        self._check(finish(h, *outs[:n_out]))
+        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
+        if samples:
+            totals.update({f[0]: int(getattr(stot, f[0])) for f in SampleTotals._fields_})
+        return reads, unique, totals, row_pairs, self.consensus_fetch(sizes) if consensus else None, sample, probe
+
     def count_reads(self, arms: Sequence[tuple], ext_reads: Sequence[bytes], lig_reads: Sequence[bytes], tag_sizes: Tuple[int, int] = (5, 0),
                     mismatches: int = 0, swap_reads: bool = False, chunks: int = 1, key_buffer: int = 0, want_assignment: bool = False):
         """mipgen_accel_reads_open / _feed / _finish: reads and unique tags per probe from read pairs.  arms: (ext_seq, lig_seq) bytes per probe as a
         MIP table prints them; ext_reads / lig_reads: the two reads of every pair (swap_reads: the first list holds the ligation reads); the pairs
         are fed in `chunks` calls.  Returns (reads, unique_tags, totals dict[, probe index per pair])."""
-        if swap_reads:
-            ext_reads, lig_reads = lig_reads, ext_reads
-        assert len(ext_reads) == len(lig_reads)
-        n, n_pairs = len(arms), len(ext_reads)
-        arr = (Probe * max(n, 1))()
-        for i, q in enumerate(arms):
-            arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
-        i64p = C.POINTER(C.c_int64)
-
-        def pack(rs):
-            off = np.zeros(len(rs) + 1, dtype=np.int64)
-            np.cumsum([len(r) for r in rs], out=off[1:])
-            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
-
-        eb, eo = pack(ext_reads)
-        lb, lo = pack(lig_reads)
-        self._check(self.lib.mipgen_accel_reads_set_key_buffer(self.h, key_buffer))
-        self._check(self.lib.mipgen_accel_reads_open(self.h, arr, n, tag_sizes[0], tag_sizes[1], mismatches))
-        assignment = np.empty(n_pairs, dtype=np.int32)
-        try:
-            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                # (a slice of the offsets with the bytes it starts at: what the entry point takes)
-                self._check(self.lib.mipgen_accel_reads_feed(self.h, b - a, eb[eo[a]:].ctypes.data, eo[a:b + 1].ctypes.data_as(i64p),
-                                                             lb[lo[a]:].ctypes.data, lo[a:b + 1].ctypes.data_as(i64p)))
-                if want_assignment and b > a:
-                    self._check(self.lib.mipgen_accel_reads_last_assignment(self.h, assignment[a:b].ctypes.data_as(C.POINTER(C.c_int32)), b - a))
-        except Exception:
-            self.lib.mipgen_accel_reads_finish(self.h, None, None, None)
-            raise
-        finally:
-            self.lib.mipgen_accel_reads_set_key_buffer(self.h, 0)
-        reads = np.empty(n, dtype=np.int64)
-        unique = np.empty(n, dtype=np.int64)
-        tot = ReadTotals()
-        self._check(self.lib.mipgen_accel_reads_finish(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot)))
-        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
-        return (reads, unique, totals, assignment) if want_assignment else (reads, unique, totals)
+        reads, unique, totals, _, _, _, probe = self._read_session(arms, ext_reads, lig_reads, tag_sizes=tag_sizes, mismatches=mismatches, swap_reads=swap_reads, chunks=chunks,
+                                                                   key_buffer=key_buffer, want_assignment=want_assignment)
+        return (reads[0], unique[0], totals, probe) if want_assignment else (reads[0], unique[0], totals)
 
     def count_reads_samples(self, arms: Sequence[tuple], ext_reads: Sequence[bytes], lig_reads: Sequence[bytes], index_reads: Sequence[bytes],
                             barcodes: Sequence[bytes], barcode_mismatches: int = 0, tag_sizes: Tuple[int, int] = (5, 0), mismatches: int = 0,
@@ -870,51 +932,8 @@ class Accel:
         read of every pair; barcodes: one per sample, of one length.  Returns (reads[rows][n], unique_tags[rows][n], totals dict (the six of
         count_reads, sample_none, sample_ambiguous), row_pairs[rows][, sample index per pair, probe index per pair]); rows = samples + 1, the last
         row is `undetermined`."""
-        if swap_reads:
-            ext_reads, lig_reads = lig_reads, ext_reads
-        assert len(ext_reads) == len(lig_reads) == len(index_reads)
-        n, n_pairs, n_samples = len(arms), len(ext_reads), len(barcodes)
-        arr = (Probe * max(n, 1))()
-        for i, q in enumerate(arms):
-            arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
-        bc = (C.c_char_p * max(n_samples, 1))(*barcodes)
-        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
-
-        def pack(rs):
-            off = np.zeros(len(rs) + 1, dtype=np.int64)
-            np.cumsum([len(r) for r in rs], out=off[1:])
-            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
-
-        eb, eo = pack(ext_reads)
-        lb, lo = pack(lig_reads)
-        ib, io = pack(index_reads)
-        self._check(self.lib.mipgen_accel_reads_set_key_buffer(self.h, key_buffer))
-        try:
-            self._check(self.lib.mipgen_accel_reads_open_samples(self.h, arr, n, tag_sizes[0], tag_sizes[1], mismatches, bc, n_samples, barcode_mismatches))
-        finally:
-            self.lib.mipgen_accel_reads_set_key_buffer(self.h, 0)
-        sample = np.empty(n_pairs, dtype=np.int32)
-        probe = np.empty(n_pairs, dtype=np.int32)
-        try:
-            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                self._check(self.lib.mipgen_accel_reads_feed_samples(self.h, b - a, eb[eo[a]:].ctypes.data, eo[a:b + 1].ctypes.data_as(i64p),
-                                                                     lb[lo[a]:].ctypes.data, lo[a:b + 1].ctypes.data_as(i64p),
-                                                                     ib[io[a]:].ctypes.data, io[a:b + 1].ctypes.data_as(i64p)))
-                if want_assignment and b > a:
-                    self._check(self.lib.mipgen_accel_reads_last_samples(self.h, sample[a:b].ctypes.data_as(i32p), b - a))
-                    self._check(self.lib.mipgen_accel_reads_last_assignment(self.h, probe[a:b].ctypes.data_as(i32p), b - a))
-        except Exception:
-            self.lib.mipgen_accel_reads_finish_samples(self.h, None, None, None, None, None)
-            raise
-        reads = np.empty((n_samples + 1, n), dtype=np.int64)
-        unique = np.empty((n_samples + 1, n), dtype=np.int64)
-        row_pairs = np.empty(n_samples + 1, dtype=np.int64)
-        tot, stot = ReadTotals(), SampleTotals()
-        self._check(self.lib.mipgen_accel_reads_finish_samples(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot), C.byref(stot),
-                                                               row_pairs.ctypes.data_as(i64p)))
-        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
-        totals.update({f[0]: int(getattr(stot, f[0])) for f in SampleTotals._fields_})
+        reads, unique, totals, row_pairs, _, sample, probe = self._read_session(arms, ext_reads, lig_reads, None, index_reads, barcodes, barcode_mismatches, tag_sizes,
+                                                                                mismatches, swap_reads, chunks, key_buffer, want_assignment=want_assignment)
         return (reads, unique, totals, row_pairs, sample, probe) if want_assignment else (reads, unique, totals, row_pairs)
 
     def consensus_fetch(self, sizes: "ConsensusSizes"):
@@ -940,53 +959,9 @@ class Accel:
         unique_tags have one row) or count_reads_samples, and one consensus read pair per (row, probe, tag) group.  ext_quals / lig_quals: the quality string
         of every read, as long as the read.  Returns (reads[rows][n], unique_tags[rows][n], totals dict, row_pairs[rows] or None, groups[, sample index per
         pair or None, probe index per pair]); groups as consensus_fetch gives them."""
-        if swap_reads:
-            ext_reads, lig_reads, ext_quals, lig_quals = lig_reads, ext_reads, lig_quals, ext_quals
-        n, n_pairs = len(arms), len(ext_reads)
-        assert len(lig_reads) == len(ext_quals) == len(lig_quals) == n_pairs and (barcodes is None) == (index_reads is None)
-        n_samples = len(barcodes) if barcodes is not None else 0
-        rows = n_samples + 1 if barcodes is not None else 1
-        arr = (Probe * max(n, 1))()
-        for i, q in enumerate(arms):
-            arr[i] = Probe(q[0], q[1], None, None, 0, 0, -1, 0)
-        bc = (C.c_char_p * max(n_samples, 1))(*barcodes) if barcodes is not None else None
-        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
-
-        def pack(rs):
-            off = np.zeros(len(rs) + 1, dtype=np.int64)
-            np.cumsum([len(r) for r in rs], out=off[1:])
-            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
-
-        (eb, eo), (lb, lo), (eq, eqo), (lq, lqo) = pack(ext_reads), pack(lig_reads), pack(ext_quals), pack(lig_quals)
-        assert np.array_equal(eo, eqo) and np.array_equal(lo, lqo), "a quality string is as long as its read"
-        ib, io = pack(index_reads) if index_reads is not None else (None, None)
-        self._check(self.lib.mipgen_accel_reads_open_consensus(self.h, arr, n, tag_sizes[0], tag_sizes[1], mismatches, bc, n_samples, barcode_mismatches, arena_bytes))
-        sample = np.empty(n_pairs, dtype=np.int32) if barcodes is not None else None
-        probe = np.empty(n_pairs, dtype=np.int32)
-        try:
-            cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                self._check(self.lib.mipgen_accel_reads_feed_consensus(
-                    self.h, b - a, eb[eo[a]:].ctypes.data, eq[eo[a]:].ctypes.data, eo[a:b + 1].ctypes.data_as(i64p), lb[lo[a]:].ctypes.data, lq[lo[a]:].ctypes.data,
-                    lo[a:b + 1].ctypes.data_as(i64p), ib[io[a]:].ctypes.data if ib is not None else None, io[a:b + 1].ctypes.data_as(i64p) if ib is not None else None))
-                if want_assignment and b > a:
-                    if sample is not None:
-                        self._check(self.lib.mipgen_accel_reads_last_samples(self.h, sample[a:b].ctypes.data_as(i32p), b - a))
-                    self._check(self.lib.mipgen_accel_reads_last_assignment(self.h, probe[a:b].ctypes.data_as(i32p), b - a))
-        except Exception:
-            self.lib.mipgen_accel_reads_finish_consensus(self.h, None, None, None, None, None, None)
-            raise
-        reads = np.empty((rows, n), dtype=np.int64)
-        unique = np.empty((rows, n), dtype=np.int64)
-        row_pairs = np.empty(rows, dtype=np.int64) if barcodes is not None else None
-        tot, stot, sizes = ReadTotals(), SampleTotals(), ConsensusSizes()
-        self._check(self.lib.mipgen_accel_reads_finish_consensus(self.h, reads.ctypes.data_as(i64p), unique.ctypes.data_as(i64p), C.byref(tot), C.byref(stot),
-                                                                 row_pairs.ctypes.data_as(i64p) if row_pairs is not None else None, C.byref(sizes)))
-        totals = {f[0]: int(getattr(tot, f[0])) for f in ReadTotals._fields_}
-        if barcodes is not None:
-            totals.update({f[0]: int(getattr(stot, f[0])) for f in SampleTotals._fields_})
-        groups = self.consensus_fetch(sizes)
-        return (reads, unique, totals, row_pairs, groups, sample, probe) if want_assignment else (reads, unique, totals, row_pairs, groups)
+        out = self._read_session(arms, ext_reads, lig_reads, (ext_quals, lig_quals), index_reads, barcodes, barcode_mismatches, tag_sizes, mismatches, swap_reads, chunks,
+                                 arena_bytes=arena_bytes, want_assignment=want_assignment)
+        return out if want_assignment else out[:5]
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

@@ -1,7 +1,10 @@
-// accel_reads.hip — reads and unique tags per probe from smMIP read pairs behind the C ABI: mipgen_accel_reads_open / _feed / _finish,
-// per sample of a multiplexed lane: mipgen_accel_reads_open_samples / _feed_samples / _finish_samples / _last_samples, and with one consensus
-// read per molecule: mipgen_accel_reads_open_consensus / _feed_consensus / _finish_consensus / _consensus_fetch.
-// A session owns every buffer it uses (ReadsSession); of the handle it takes the device and the stream, nothing else.
+// accel_reads.hip — read sessions behind the C ABI: reads and unique tags per probe from smMIP read pairs (mipgen_accel_reads_open / _feed / _finish), per sample of
+// a multiplexed lane (4.10: _open_samples / _feed_samples / _finish_samples / _last_samples), with one consensus read pair per molecule (4.11: _open_consensus / _feed_consensus /
+// _finish_consensus / _consensus_fetch).  The three families of entry points name ONE path.  ReadsSession is what every session has plus a KeyList, a SamplesPart and a
+// ConsensusPart; its flags `samples` and `consensus` say which parts are set up, and session_for() alone matches a call to the open session.  open_impl: check_open
+// (probe table, then barcodes), build_host_tables, the budget, upload_tables.  feed_impl: eleven stages, the kinds differing in data only - where the bases of the call live and where
+// k_read_assign's keys go.  finish_session: consensus_finish where reads were kept, finish_impl, release.  Errors are HIP_TRY returns; IdleOnExit and FreeOnExit put the
+// stream and a chunk's block right on every way out, SpanTimer books HIP-event times.  A session owns every buffer it uses; of the handle it takes the device and the stream.
 #include "accel_internal.h"
 
 struct SeedTableBufs {
@@ -37,56 +40,6 @@ struct ConsensusResult {
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
     void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); }
 };
-
-struct ReadsSession {
-    ReadsParams P{};
-    DevBuf<ReadProbe> probes;
-    SeedTableBufs ext_seeds, lig_seeds;
-    DevBuf<uint8_t> ext_bytes, lig_bytes;                   // the pairs of the current feed call
-    DevBuf<int64_t> ext_off, lig_off;
-    DevBuf<int32_t> assign;
-    int64_t last_pairs = 0;
-    DevBuf<unsigned long long> reads, unique;
-    DevBuf<uint64_t> keys, keys_alt;
-    DevBuf<char> sort_temp;
-    DevBuf<ReadsCounters> ctr;
-    int64_t key_cap = 0;                                     // entries of `keys` in use as capacity
-    int64_t key_ub = 0;                                      // no more keys than this are in the buffer (every pair fed since the last sort-unique counted)
-    int end_bit = 64;                                        // key bits that can be set
-    // a samples session: rows = n_samples + 1, the count matrices hold rows * n_probes cells
-    bool samples = false;
-    int64_t rows = 1;
-    SampleTable sample_table{};
-    DevBuf<SampleSlot> sample_slots;
-    DevBuf<uint8_t> idx_bytes;
-    DevBuf<int64_t> idx_off;
-    DevBuf<int32_t> row, sample_index;
-    DevBuf<unsigned long long> row_pairs;
-    DevBuf<SampleCounters> sctr;
-    // a consensus session: the reads of every feed call stay resident, chunk by chunk, within a budget of arena_cap bytes
-    bool consensus = false;
-    std::vector<ArenaChunk> chunks;
-    size_t arena_cap = 0, arena_used = 0;
-    int64_t total_pairs = 0;
-    DevBuf<ConsensusCounters> cctr;
-    DevBuf<uint64_t> c_keys_in, c_keys_out;                  // finish: the (key, pair id) of every pair, as fed and sorted
-    DevBuf<uint32_t> c_ids_in, c_ids_out, c_start, c_order;
-    DevBuf<ConsensusPair> c_recs;
-    DevBuf<int64_t> c_ext_len, c_lig_len;
-    void release()
-    {
-        for (const ArenaChunk& c : chunks) (void)hipFree(c.block);
-        chunks.clear();
-        cctr.release(); c_keys_in.release(); c_keys_out.release(); c_ids_in.release(); c_ids_out.release(); c_start.release(); c_order.release(); c_recs.release();
-        c_ext_len.release(); c_lig_len.release();
-        sample_slots.release(); idx_bytes.release(); idx_off.release(); row.release(); sample_index.release(); row_pairs.release(); sctr.release();
-        probes.release(); ext_seeds.release(); lig_seeds.release(); ext_bytes.release(); lig_bytes.release(); ext_off.release(); lig_off.release();
-        assign.release(); reads.release(); unique.release(); keys.release(); keys_alt.release(); sort_temp.release(); ctr.release();
-    }
-};
-
-enum { FEED_PLAIN = 0, FEED_SAMPLES = 1, FEED_CONSENSUS = 2 };
-
 static const int64_t READS_KEY_CAP_DEFAULT = (int64_t)1 << 26, READS_KEY_CAP_MAX = (int64_t)1 << 30;
 
 // an arm as bit planes (reads_common.h); rc: of its reverse complement
@@ -184,71 +137,258 @@ static int free_device_bytes(size_t* free_b)
     HIP_TRY(hipMemGetInfo(free_b, &total_b));
     return MIPGEN_OK;
 }
+// the stream is idle when the scope ends, however it ends: the caller's arrays and the host tables behind an asynchronous copy are free from then on
+struct IdleOnExit { hipStream_t s; bool idle = false; hipError_t wait() { idle = true; return hipStreamSynchronize(s); } ~IdleOnExit() { if (!idle) (void)hipStreamSynchronize(s); } };
+struct FreeOnExit { void* p; ~FreeOnExit() { if (p) (void)hipFree(p); } };
 
-// keys[0, n) of the session sorted and made duplicate-free; key_ub becomes their exact number
-static int sort_unique_keys(mipgen_accel* h, ReadsSession* S)
-{
-    unsigned long long n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, &S->ctr.p->n_keys, sizeof n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if ((int64_t)n > S->key_cap) return fail(MIPGEN_E_STATE, "read counter: %llu keys in a buffer of %lld", n, (long long)S->key_cap);
-    if (n > 0) {
-        size_t temp_bytes = 0;
-        HIP_TRY(mipgen_reads_sort_unique(h->stream, nullptr, &temp_bytes, S->keys.p, S->keys_alt.p, (int64_t)n, S->end_bit, &S->ctr.p->n_keys));
-        if (S->sort_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
-        temp_bytes = S->sort_temp.cap;
-        HIP_TRY(mipgen_reads_sort_unique(h->stream, S->sort_temp.p, &temp_bytes, S->keys.p, S->keys_alt.p, (int64_t)n, S->end_bit, &S->ctr.p->n_keys));
-        HIP_TRY(hipMemcpyAsync(&n, &S->ctr.p->n_keys, sizeof n, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+// HIP-event time of spans of the stream when timing is on (off: no event is ever created).  mark() before and after a span; add_to(), called once the stream is idle and the
+// call has succeeded, adds the ms of every span to *sum and says how many it added; the destructor destroys the events.
+struct SpanTimer {
+    bool on;
+    hipStream_t st;
+    std::vector<hipEvent_t> ev;                              // (before, after) of every span
+    ~SpanTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void mark() { hipEvent_t e = nullptr; if (on && (on = hipEventCreate(&e) == hipSuccess)) { ev.push_back(e); (void)hipEventRecord(e, st); } }
+    int add_to(double* sum) const
+    {
+        int n = 0;
+        float ms = 0.f;
+        for (size_t k = 0; on && k + 1 < ev.size(); k += 2)
+            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) { *sum += ms; n++; }
+        return n;
     }
-    S->key_ub = (int64_t)n;
+};
+
+// The (cell, tag) keys of a plain or samples session, sorted and duplicate-free between feed calls.  A consensus session keeps no list: its `keys` is the scratch
+// k_read_assign writes a chunk's keys to (cap stays 0), and `sort_temp` and `end_bit` serve the sort of its finish.
+struct KeyList {
+    DevBuf<uint64_t> keys, keys_alt;
+    DevBuf<char> sort_temp;
+    int64_t cap = 0;                                         // entries of `keys` in use as capacity
+    int64_t ub = 0;                                          // no more keys than this are in the buffer (every pair fed since the last sort-unique counted)
+    int end_bit = 64;                                        // key bits that can be set
+    void release() { keys.release(); keys_alt.release(); sort_temp.release(); }
+
+    // keys[0, n) sorted and made duplicate-free; ub becomes their exact number (n_keys: the session's device counter of keys written)
+    int sort_unique(mipgen_accel* h, unsigned long long* n_keys)
+    {
+        unsigned long long n = 0;
+        HIP_TRY(hipMemcpyAsync(&n, n_keys, sizeof n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if ((int64_t)n > cap) return fail(MIPGEN_E_STATE, "read counter: %llu keys in a buffer of %lld", n, (long long)cap);
+        if (n > 0) {
+            size_t temp_bytes = 0;
+            HIP_TRY(mipgen_reads_sort_unique(h->stream, nullptr, &temp_bytes, keys.p, keys_alt.p, (int64_t)n, end_bit, n_keys));
+            if (sort_temp.reserve(temp_bytes + 16)) return MIPGEN_E_NOMEM;
+            temp_bytes = sort_temp.cap;
+            HIP_TRY(mipgen_reads_sort_unique(h->stream, sort_temp.p, &temp_bytes, keys.p, keys_alt.p, (int64_t)n, end_bit, n_keys));
+            HIP_TRY(hipMemcpyAsync(&n, n_keys, sizeof n, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        ub = (int64_t)n;
+        return MIPGEN_OK;
+    }
+
+    // room for `want` more keys (at least 1): sort-unique what is there, and double the buffer while more than half of it is distinct keys
+    int make_room(mipgen_accel* h, unsigned long long* n_keys, int64_t want, int64_t* room)
+    {
+        if (cap - ub < std::min(want, std::max<int64_t>(cap / 2, 1))) {
+            if (int rc = sort_unique(h, n_keys)) return rc;
+            while (cap - ub < std::max<int64_t>(cap / 2, 1)) {
+                const int64_t grown_cap = cap * 2;
+                size_t free_b = 0;
+                if (int rc = free_device_bytes(&free_b)) return rc;
+                if (grown_cap > READS_KEY_CAP_MAX || (size_t)grown_cap * 16 + ((size_t)64 << 20) > free_b)
+                    return fail(MIPGEN_E_NOMEM, "read counter: %lld distinct (probe, tag) keys do not fit device memory (%zu MiB free)", (long long)ub, free_b >> 20);
+                DevBuf<uint64_t> grown;
+                if (grown.reserve((size_t)grown_cap)) return MIPGEN_E_NOMEM;
+                if (ub) HIP_TRY(hipMemcpyAsync(grown.p, keys.p, (size_t)ub * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                keys.release(); keys_alt.release();
+                keys = grown;
+                if (keys_alt.reserve((size_t)grown_cap)) return MIPGEN_E_NOMEM;
+                cap = grown_cap;
+            }
+        }
+        *room = cap - ub;
+        return MIPGEN_OK;
+    }
+};
+
+// a session with samples: the barcode table, the index reads of the current feed call and what k_sample_assign makes of them
+struct SamplesPart {
+    SampleTable table{};
+    DevBuf<SampleSlot> slots;
+    DevBuf<uint8_t> idx_bytes; DevBuf<int64_t> idx_off;      // the index reads of the current feed call
+    DevBuf<int32_t> row, sample_index;                       // ... and the row and sample of each of its pairs
+    DevBuf<unsigned long long> row_pairs;
+    DevBuf<SampleCounters> ctr;
+    void release() { slots.release(); idx_bytes.release(); idx_off.release(); row.release(); sample_index.release(); row_pairs.release(); ctr.release(); }
+};
+
+// a session that keeps its reads: every feed call's chunk stays resident, within a budget of arena_cap bytes; c_*: the scratch of finish
+struct ConsensusPart {
+    std::vector<ArenaChunk> chunks;
+    size_t arena_cap = 0, arena_used = 0; int64_t total_pairs = 0;
+    DevBuf<ConsensusCounters> ctr;
+    DevBuf<uint64_t> c_keys_in, c_keys_out;                  // the (key, pair id) of every pair, as fed and sorted
+    DevBuf<uint32_t> c_ids_in, c_ids_out, c_start, c_order;
+    DevBuf<ConsensusPair> c_recs;
+    DevBuf<int64_t> c_ext_len, c_lig_len;
+    void release()
+    {
+        for (const ArenaChunk& c : chunks) (void)hipFree(c.block);
+        chunks.clear();
+        ctr.release(); c_keys_in.release(); c_keys_out.release(); c_ids_in.release(); c_ids_out.release(); c_start.release(); c_order.release(); c_recs.release();
+        c_ext_len.release(); c_lig_len.release();
+    }
+};
+
+struct ReadsSession {
+    ReadsParams P{};
+    bool samples = false, consensus = false;                 // which parts are set up: smp / cons (and no key list: see KeyList)
+    int64_t rows = 1;                                        // n_samples + 1 with samples; the count matrices hold rows * n_probes cells
+    DevBuf<ReadProbe> probes;
+    SeedTableBufs ext_seeds, lig_seeds;
+    DevBuf<unsigned long long> reads, unique;
+    DevBuf<ReadsCounters> ctr;
+    DevBuf<uint8_t> ext_bytes, lig_bytes;                    // the pairs of the current feed call (a consensus session: in the chunk's block instead)
+    DevBuf<int64_t> ext_off, lig_off;
+    DevBuf<int32_t> assign;
+    int64_t last_pairs = 0;
+    KeyList keys;
+    SamplesPart smp;
+    ConsensusPart cons;
+    void release()
+    {
+        cons.release(); smp.release(); keys.release();
+        probes.release(); ext_seeds.release(); lig_seeds.release(); reads.release(); unique.release(); ctr.release();
+        ext_bytes.release(); lig_bytes.release(); ext_off.release(); lig_off.release(); assign.release();
+    }
+};
+
+enum { KIND_PLAIN = 0, KIND_SAMPLES = 1, KIND_CONSENSUS = 2 };      // the three families of entry points
+
+// The open session in *S when a call of `kind` (feed: a feed call; otherwise a finish) is the one that serves it.  If not, the refusal names the entry point that does.
+static int session_for(mipgen_accel* h, int kind, bool feed, ReadsSession** S)
+{
+    ReadsSession* s = h->reads;
+    if (!s) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    const char *verb = feed ? "feed" : "finish", *does = feed ? "feeds" : "closes";
+    if (s->consensus && kind != KIND_CONSENSUS) return fail(MIPGEN_E_STATE, "the open session is a consensus session: mipgen_accel_reads_%s_consensus %s it", verb, does);
+    if (!s->consensus && kind == KIND_CONSENSUS)
+        return feed ? fail(MIPGEN_E_STATE, "the open session keeps no reads: it was not opened by mipgen_accel_reads_open_consensus")
+                    : fail(MIPGEN_E_STATE, "the open session keeps no reads: mipgen_accel_reads_finish%s closes it", s->samples ? "_samples" : "");
+    if (!s->consensus && s->samples != (kind == KIND_SAMPLES))
+        return fail(MIPGEN_E_STATE, "the open session has %s: mipgen_accel_reads_%s%s %s it", s->samples ? "samples" : "no samples", verb, s->samples ? "_samples" : "", does);
+    *S = s;
     return MIPGEN_OK;
 }
 
-// room for `want` more keys (at least 1): sort-unique what is there, and double the buffer while more than half of it is distinct keys
-static int make_key_room(mipgen_accel* h, ReadsSession* S, int64_t want, int64_t* room)
+// Every check of an open, in the order in which the refusals win, before anything is built or allocated.  *shortest: the shortest arm; *J: the length of the barcodes.
+static int check_open(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches, const char* const* barcodes, int32_t n_samples,
+                      int32_t barcode_mismatches, bool consensus, int64_t arena_bytes, size_t* shortest, int* J)
 {
-    if (S->key_cap - S->key_ub < std::min(want, std::max<int64_t>(S->key_cap / 2, 1))) {
-        if (int rc = sort_unique_keys(h, S)) return rc;
-        while (S->key_cap - S->key_ub < std::max<int64_t>(S->key_cap / 2, 1)) {
-            const int64_t cap = S->key_cap * 2;
-            size_t free_b = 0;
-            if (int rc = free_device_bytes(&free_b)) return rc;
-            if (cap > READS_KEY_CAP_MAX || (size_t)cap * 16 + ((size_t)64 << 20) > free_b)
-                return fail(MIPGEN_E_NOMEM, "read counter: %lld distinct (probe, tag) keys do not fit device memory (%zu MiB free)", (long long)S->key_ub, free_b >> 20);
-            DevBuf<uint64_t> grown;
-            if (grown.reserve((size_t)cap)) return MIPGEN_E_NOMEM;
-            if (S->key_ub) HIP_TRY(hipMemcpyAsync(grown.p, S->keys.p, (size_t)S->key_ub * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            S->keys.release(); S->keys_alt.release();
-            S->keys = grown;
-            if (S->keys_alt.reserve((size_t)cap)) return MIPGEN_E_NOMEM;
-            S->key_cap = cap;
-        }
+    // the probe table and the session's numbers
+    if (!h || !probes || n < 1) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (ext_tag < 0 || lig_tag < 0 || ext_tag + lig_tag > READS_MAX_TAG) return fail(MIPGEN_E_INVALID, "tag sizes %d,%d: at most %d tag bases in all", ext_tag, lig_tag, READS_MAX_TAG);
+    if (consensus && ext_tag + lig_tag == 0) return fail(MIPGEN_E_INVALID, "tag sizes 0,0: without tag bases there are no molecules to collapse");
+    if (consensus && arena_bytes < 0) return fail(MIPGEN_E_INVALID, "arena_bytes %lld is negative", (long long)arena_bytes);
+    if (max_mismatches < 0 || max_mismatches > 2) return fail(MIPGEN_E_INVALID, "max_mismatches %d outside 0..2", max_mismatches);
+    *shortest = MIPGEN_MAX_OLIGO;
+    for (int i = 0; i < n; i++) {
+        const mipgen_probe& q = probes[i];
+        if (!q.ext_seq || !q.lig_seq) return fail(MIPGEN_E_INVALID, "probe %d: %s sequence is NULL", i, !q.ext_seq ? "extension arm" : "ligation arm");
+        const size_t e = strlen(q.ext_seq), l = strlen(q.lig_seq);
+        if (e < MIPGEN_MIN_OLIGO || l < MIPGEN_MIN_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: empty %s arm", i, e < MIPGEN_MIN_OLIGO ? "extension" : "ligation");
+        if (e > MIPGEN_MAX_OLIGO || l > MIPGEN_MAX_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: arm of %zu bases (at most %d)", i, std::max(e, l), MIPGEN_MAX_OLIGO);
+        *shortest = std::min(*shortest, std::min(e, l));
     }
-    *room = S->key_cap - S->key_ub;
+    if (*shortest < 12) return fail(MIPGEN_E_INVALID, "the shortest arm of the table has %zu bases: a seed of fewer than 12 bases is refused", *shortest);
+    // the barcodes, and the cells they make with the probes
+    const uint64_t cells = (uint64_t)(barcodes ? (int64_t)n_samples + 1 : 1) * (uint64_t)n;
+    if (barcodes) {
+        if (barcode_mismatches < 0 || barcode_mismatches > 1) return fail(MIPGEN_E_INVALID, "barcode_mismatches %d outside 0..1", barcode_mismatches);
+        for (int s = 0; s < n_samples; s++) {
+            if (!barcodes[s]) return fail(MIPGEN_E_INVALID, "barcode %d is NULL", s);
+            const size_t len = strlen(barcodes[s]);
+            if (s == 0) {
+                if (len < 1 || len > SAMPLES_MAX_BARCODE) return fail(MIPGEN_E_INVALID, "barcode 0 has %zu bases (1 to %d)", len, SAMPLES_MAX_BARCODE);
+                *J = (int)len;
+            } else if ((int)len != *J) return fail(MIPGEN_E_INVALID, "barcode %d has %zu bases, barcode 0 has %d: barcodes of unequal length", s, len, *J);
+            for (int j = 0; j < *J; j++)
+                if (reads_base_code((uint8_t)barcodes[s][j]) > 3u) return fail(MIPGEN_E_INVALID, "barcode %d: byte %d is not one of upper-case A C G T", s, j);
+        }
+        std::vector<std::string> seen(barcodes, barcodes + n_samples);
+        std::sort(seen.begin(), seen.end());
+        for (size_t s = 1; s < seen.size(); s++)
+            if (seen[s] == seen[s - 1]) return fail(MIPGEN_E_INVALID, "barcode %s is there twice", seen[s].c_str());
+        if (cells > ((uint64_t)1 << 32)) return fail(MIPGEN_E_INVALID, "%d samples + undetermined x %d probes: more than 2^32 cells", n_samples, n);
+    }
+    // (the sentinel key of a pair in no group is the key bit above the cell index: DESIGN 4.11)
+    if (consensus && cells > ((uint64_t)1 << 31)) return fail(MIPGEN_E_INVALID, "%lld rows x %d probes: more than 2^31 cells in a consensus session", (long long)(cells / (uint64_t)n), n);
+    if (h->reads) return fail(MIPGEN_E_STATE, "a read-counting session is open: mipgen_accel_reads_finish closes it");
     return MIPGEN_OK;
+}
+
+struct HostTables { std::vector<ReadProbe> packed; HostSeedTable ext, lig; std::vector<SampleSlot> sample_slots; };      // (no slots without barcodes)
+
+static void build_host_tables(const mipgen_probe* probes, int32_t n, uint64_t seed_mask, const char* const* barcodes, int32_t n_samples, int J, int32_t barcode_mismatches, HostTables& T)
+{
+    T.packed.resize((size_t)n);
+    std::vector<std::pair<uint64_t, int32_t>> ekp, lkp;
+    for (int i = 0; i < n; i++) {
+        ReadProbe& r = T.packed[(size_t)i];
+        memset(&r, 0, sizeof r);
+        r.e_len = (int32_t)strlen(probes[i].ext_seq); r.l_len = (int32_t)strlen(probes[i].lig_seq);
+        pack_arm(probes[i].ext_seq, r.e_len, false, &r.e0, &r.e1, &r.ebad);
+        pack_arm(probes[i].lig_seq, r.l_len, true, &r.l0, &r.l1, &r.lbad);
+        if ((r.ebad & seed_mask) == 0) ekp.emplace_back(reads_seed_key(r.e0, r.e1, seed_mask), i);
+        if ((r.lbad & seed_mask) == 0) lkp.emplace_back(reads_seed_key(r.l0, r.l1, seed_mask), i);
+    }
+    build_seed_table(ekp, T.ext);
+    build_seed_table(lkp, T.lig);
+    if (barcodes) build_sample_table(barcodes, n_samples, J, barcode_mismatches, T.sample_slots);
+}
+
+// the buffers of a new session (its flags, rows, P and key capacity are set) and the tables into them; the host tables are free when this returns
+static int upload_tables(mipgen_accel* h, ReadsSession* S, const HostTables& T, int J, int32_t barcode_mismatches)
+{
+    const size_t n = (size_t)S->P.n_probes, cells = (size_t)S->rows * n;
+    if (S->probes.reserve(n) || S->reads.reserve(cells) || S->unique.reserve(cells) || S->ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    if (S->keys.cap && (S->keys.keys.reserve((size_t)S->keys.cap) || S->keys.keys_alt.reserve((size_t)S->keys.cap))) return MIPGEN_E_NOMEM;
+    if (S->samples && (S->smp.slots.reserve(T.sample_slots.size()) || S->smp.row_pairs.reserve((size_t)S->rows) || S->smp.ctr.reserve(1))) return MIPGEN_E_NOMEM;
+    if (S->consensus && S->cons.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{h->stream};
+    if (int rc = upload_seed_table(h, T.ext, S->ext_seeds)) return rc;
+    if (int rc = upload_seed_table(h, T.lig, S->lig_seeds)) return rc;
+    HIP_TRY(hipMemcpyAsync(S->probes.p, T.packed.data(), n * sizeof(ReadProbe), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(S->reads.p, 0, cells * sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(S->unique.p, 0, cells * sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(S->ctr.p, 0, sizeof(ReadsCounters), h->stream));
+    if (S->consensus) HIP_TRY(hipMemsetAsync(S->cons.ctr.p, 0, sizeof(ConsensusCounters), h->stream));
+    if (S->samples) {
+        HIP_TRY(hipMemcpyAsync(S->smp.slots.p, T.sample_slots.data(), T.sample_slots.size() * sizeof(SampleSlot), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemsetAsync(S->smp.row_pairs.p, 0, (size_t)S->rows * sizeof(unsigned long long), h->stream));
+        HIP_TRY(hipMemsetAsync(S->smp.ctr.p, 0, sizeof(SampleCounters), h->stream));
+        S->smp.table = {S->smp.slots.p, (uint32_t)(T.sample_slots.size() - 1), J, barcode_mismatches, (int32_t)(S->rows - 1)};
+    }
+    HIP_TRY(idle.wait());
+    return MIPGEN_OK;
+}
+
+// a session, or the consensus reads a finished one left: the stream is idle before its buffers go
+template <typename T> static void release_owned(mipgen_accel* h, T*& owned)
+{
+    if (!owned) return;
+    (void)hipStreamSynchronize(h->stream);
+    owned->release(); delete owned; owned = nullptr;
 }
 
 extern "C" {
 
-void mipgen_reads_release(mipgen_accel* h)
-{
-    if (!h->reads) return;
-    (void)hipStreamSynchronize(h->stream);
-    h->reads->release();
-    delete h->reads;
-    h->reads = nullptr;
-}
-
-void mipgen_consensus_release(mipgen_accel* h)
-{
-    if (!h->consensus) return;
-    (void)hipStreamSynchronize(h->stream);
-    h->consensus->release();
-    delete h->consensus;
-    h->consensus = nullptr;
-}
+void mipgen_reads_release(mipgen_accel* h) { release_owned(h, h->reads); }
+void mipgen_consensus_release(mipgen_accel* h) { release_owned(h, h->consensus); }
 
 int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys)
 {
@@ -261,225 +401,68 @@ int mipgen_accel_reads_set_key_buffer(mipgen_accel* h, int64_t n_keys)
 static int open_impl(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches, const char* const* barcodes,
                      int32_t n_samples, int32_t barcode_mismatches, bool consensus = false, int64_t arena_bytes = 0)
 {
-    if (!h || !probes || n < 1) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (ext_tag < 0 || lig_tag < 0 || ext_tag + lig_tag > READS_MAX_TAG) return fail(MIPGEN_E_INVALID, "tag sizes %d,%d: at most %d tag bases in all", ext_tag, lig_tag, READS_MAX_TAG);
-    if (consensus && ext_tag + lig_tag == 0) return fail(MIPGEN_E_INVALID, "tag sizes 0,0: without tag bases there are no molecules to collapse");
-    if (consensus && arena_bytes < 0) return fail(MIPGEN_E_INVALID, "arena_bytes %lld is negative", (long long)arena_bytes);
-    if (max_mismatches < 0 || max_mismatches > 2) return fail(MIPGEN_E_INVALID, "max_mismatches %d outside 0..2", max_mismatches);
-    size_t shortest = MIPGEN_MAX_OLIGO;
-    for (int i = 0; i < n; i++) {
-        const mipgen_probe& q = probes[i];
-        if (!q.ext_seq || !q.lig_seq) return fail(MIPGEN_E_INVALID, "probe %d: %s sequence is NULL", i, !q.ext_seq ? "extension arm" : "ligation arm");
-        const size_t e = strlen(q.ext_seq), l = strlen(q.lig_seq);
-        if (e < MIPGEN_MIN_OLIGO || l < MIPGEN_MIN_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: empty %s arm", i, e < MIPGEN_MIN_OLIGO ? "extension" : "ligation");
-        if (e > MIPGEN_MAX_OLIGO || l > MIPGEN_MAX_OLIGO) return fail(MIPGEN_E_INVALID, "probe %d: arm of %zu bases (at most %d)", i, std::max(e, l), MIPGEN_MAX_OLIGO);
-        shortest = std::min(shortest, std::min(e, l));
-    }
-    if (shortest < 12) return fail(MIPGEN_E_INVALID, "the shortest arm of the table has %zu bases: a seed of fewer than 12 bases is refused", shortest);
-    int J = 0;
+    size_t shortest = 0; int J = 0;
+    if (int rc = check_open(h, probes, n, ext_tag, lig_tag, max_mismatches, barcodes, n_samples, barcode_mismatches, consensus, arena_bytes, &shortest, &J)) return rc;
     const int64_t rows = barcodes ? (int64_t)n_samples + 1 : 1;
-    if (barcodes) {
-        if (barcode_mismatches < 0 || barcode_mismatches > 1) return fail(MIPGEN_E_INVALID, "barcode_mismatches %d outside 0..1", barcode_mismatches);
-        for (int s = 0; s < n_samples; s++) {
-            if (!barcodes[s]) return fail(MIPGEN_E_INVALID, "barcode %d is NULL", s);
-            const size_t len = strlen(barcodes[s]);
-            if (s == 0) {
-                if (len < 1 || len > SAMPLES_MAX_BARCODE) return fail(MIPGEN_E_INVALID, "barcode 0 has %zu bases (1 to %d)", len, SAMPLES_MAX_BARCODE);
-                J = (int)len;
-            } else if ((int)len != J) return fail(MIPGEN_E_INVALID, "barcode %d has %zu bases, barcode 0 has %d: barcodes of unequal length", s, len, J);
-            for (int j = 0; j < J; j++)
-                if (reads_base_code((uint8_t)barcodes[s][j]) > 3u) return fail(MIPGEN_E_INVALID, "barcode %d: byte %d is not one of upper-case A C G T", s, j);
-        }
-        std::vector<std::string> seen;
-        seen.reserve((size_t)n_samples);
-        for (int s = 0; s < n_samples; s++) seen.emplace_back(barcodes[s]);
-        std::sort(seen.begin(), seen.end());
-        for (size_t s = 1; s < seen.size(); s++)
-            if (seen[s] == seen[s - 1]) return fail(MIPGEN_E_INVALID, "barcode %s is there twice", seen[s].c_str());
-        if ((uint64_t)rows * (uint64_t)n > ((uint64_t)1 << 32))
-            return fail(MIPGEN_E_INVALID, "%d samples + undetermined x %d probes: more than 2^32 cells", n_samples, n);
-    }
-    // (the sentinel key of a pair in no group is the key bit above the cell index: DESIGN 4.11)
-    if (consensus && (uint64_t)rows * (uint64_t)n > ((uint64_t)1 << 31))
-        return fail(MIPGEN_E_INVALID, "%lld rows x %d probes: more than 2^31 cells in a consensus session", (long long)rows, n);
-    if (h->reads) return fail(MIPGEN_E_STATE, "a read-counting session is open: mipgen_accel_reads_finish closes it");
-    const int S = (int)std::min<size_t>(shortest, READS_MAX_SEED);
-
     // the tables, on the host
-    std::vector<ReadProbe> packed((size_t)n);
-    std::vector<std::pair<uint64_t, int32_t>> ekp, lkp;
-    const uint64_t seed_mask = reads_len_mask(S);
-    for (int i = 0; i < n; i++) {
-        ReadProbe& r = packed[(size_t)i];
-        memset(&r, 0, sizeof r);
-        r.e_len = (int32_t)strlen(probes[i].ext_seq); r.l_len = (int32_t)strlen(probes[i].lig_seq);
-        pack_arm(probes[i].ext_seq, r.e_len, false, &r.e0, &r.e1, &r.ebad);
-        pack_arm(probes[i].lig_seq, r.l_len, true, &r.l0, &r.l1, &r.lbad);
-        if ((r.ebad & seed_mask) == 0) ekp.emplace_back(reads_seed_key(r.e0, r.e1, seed_mask), i);
-        if ((r.lbad & seed_mask) == 0) lkp.emplace_back(reads_seed_key(r.l0, r.l1, seed_mask), i);
-    }
-    HostSeedTable TE, TL;
-    build_seed_table(ekp, TE);
-    build_seed_table(lkp, TL);
-    std::vector<SampleSlot> sample_slots;
-    if (barcodes) build_sample_table(barcodes, n_samples, J, barcode_mismatches, sample_slots);
+    const int seed = (int)std::min<size_t>(shortest, READS_MAX_SEED);
+    const uint64_t seed_mask = reads_len_mask(seed);
+    HostTables T;
+    build_host_tables(probes, n, seed_mask, barcodes, n_samples, J, barcode_mismatches, T);
     const size_t cells = (size_t)rows * (size_t)n;
-
-    HIP_TRY(hipSetDevice(h->device));
     // the budget: tables + counters + two key buffers, against free device memory
+    HIP_TRY(hipSetDevice(h->device));
     size_t free_b = 0;
     if (int rc = free_device_bytes(&free_b)) return rc;
     const bool tags = ext_tag + lig_tag > 0;
     // (a consensus session keeps no key list across feed calls: its groups come from the sort of finish)
     int64_t key_cap = !tags || consensus ? 0 : h->reads_key_cap > 0 ? h->reads_key_cap : READS_KEY_CAP_DEFAULT;
-    const size_t fixed = (size_t)n * (sizeof(ReadProbe) + 2 * 4) + cells * 16 + sample_slots.size() * sizeof(SampleSlot) + (size_t)rows * 8 + (TE.slots.size() + TL.slots.size()) * 4 + (TE.keys.size() + TL.keys.size()) * 12 + ((size_t)64 << 20);
+    const size_t fixed = (size_t)n * (sizeof(ReadProbe) + 2 * 4) + cells * 16 + T.sample_slots.size() * sizeof(SampleSlot) + (size_t)rows * 8 + (T.ext.slots.size() + T.lig.slots.size()) * 4 + (T.ext.keys.size() + T.lig.keys.size()) * 12 + ((size_t)64 << 20);
     if (tags && !consensus && h->reads_key_cap <= 0)
         while (key_cap > 1024 && fixed + (size_t)key_cap * 16 > free_b / 2) key_cap /= 2;      // the default gives way to what is free; half is left for the reads
     if (fixed + (size_t)key_cap * 16 > free_b)
         return fail(MIPGEN_E_NOMEM, "read counter: tables of %d probes x %lld rows and %lld keys need %zu MiB of device memory, %zu MiB are free", n, (long long)rows,
                     (long long)key_cap, (fixed + (size_t)key_cap * 16) >> 20, free_b >> 20);
-
-    mipgen_consensus_release(h);                                            // the consensus reads of an earlier session end here
-    ReadsSession* S_ = new ReadsSession;
-    h->reads = S_;
-    S_->consensus = consensus;
+    // the session: from here on it is certain to be attempted, and the consensus reads of an earlier session end here
+    mipgen_consensus_release(h);
+    ReadsSession* S = new ReadsSession;
+    h->reads = S;
+    S->P = {ext_tag, lig_tag, max_mismatches, seed, seed_mask, n, 0};
+    S->samples = barcodes != nullptr; S->consensus = consensus; S->rows = rows;
     // the arena's default: half of what is free beside the tables; the other half is left to finish (56 bytes per pair of sort buffers and records, and the
     // consensus reads, which are no longer than the reads retained)
-    if (consensus) S_->arena_cap = arena_bytes > 0 ? (size_t)arena_bytes : (free_b - fixed) / 2;
-    auto give_up = [&](int rc) { mipgen_reads_release(h); return rc; };
-    S_->P = {ext_tag, lig_tag, max_mismatches, S, seed_mask, n, 0};
-    S_->key_cap = key_cap;
-    S_->samples = barcodes != nullptr;
-    S_->rows = rows;
+    if (consensus) S->cons.arena_cap = arena_bytes > 0 ? (size_t)arena_bytes : (free_b - fixed) / 2;
+    S->keys.cap = key_cap;
     int probe_bits = 1;                                                    // (of the cell index rows * n - 1 at most: 32 bits when there are 2^32 cells)
     while (probe_bits < 32 && ((int64_t)1 << probe_bits) < (int64_t)cells) probe_bits++;
-    S_->end_bit = 32 + probe_bits;
-    if (S_->probes.reserve((size_t)n) || S_->reads.reserve(cells) || S_->unique.reserve(cells) || S_->ctr.reserve(1) ||
-        (key_cap && (S_->keys.reserve((size_t)key_cap) || S_->keys_alt.reserve((size_t)key_cap))))
-        return give_up(MIPGEN_E_NOMEM);
-    if (barcodes && (S_->sample_slots.reserve(sample_slots.size()) || S_->row_pairs.reserve((size_t)rows) || S_->sctr.reserve(1))) return give_up(MIPGEN_E_NOMEM);
-    if (consensus && S_->cctr.reserve(1)) return give_up(MIPGEN_E_NOMEM);
-    int rc = upload_seed_table(h, TE, S_->ext_seeds);
-    if (rc == MIPGEN_OK) rc = upload_seed_table(h, TL, S_->lig_seeds);
-    hipError_t e = hipSuccess;
-    if (rc == MIPGEN_OK) e = hipMemcpyAsync(S_->probes.p, packed.data(), (size_t)n * sizeof(ReadProbe), hipMemcpyHostToDevice, h->stream);
-    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->reads.p, 0, cells * sizeof(unsigned long long), h->stream);
-    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->unique.p, 0, cells * sizeof(unsigned long long), h->stream);
-    if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->ctr.p, 0, sizeof(ReadsCounters), h->stream);
-    if (rc == MIPGEN_OK && e == hipSuccess && consensus) e = hipMemsetAsync(S_->cctr.p, 0, sizeof(ConsensusCounters), h->stream);
-    if (barcodes) {
-        if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemcpyAsync(S_->sample_slots.p, sample_slots.data(), sample_slots.size() * sizeof(SampleSlot), hipMemcpyHostToDevice, h->stream);
-        if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->row_pairs.p, 0, (size_t)rows * sizeof(unsigned long long), h->stream);
-        if (rc == MIPGEN_OK && e == hipSuccess) e = hipMemsetAsync(S_->sctr.p, 0, sizeof(SampleCounters), h->stream);
-        S_->sample_table = {S_->sample_slots.p, (uint32_t)(sample_slots.size() - 1), J, barcode_mismatches, n_samples};
-    }
-    const hipError_t e2 = hipStreamSynchronize(h->stream);                 // (the host tables above live until here)
-    if (rc == MIPGEN_OK && e == hipSuccess) e = e2;
-    if (rc == MIPGEN_OK && e != hipSuccess) rc = fail(MIPGEN_E_HIP, "mipgen_accel_reads_open: %s", hipGetErrorString(e));
-    if (rc != MIPGEN_OK) return give_up(rc);
+    S->keys.end_bit = 32 + probe_bits;
+    if (int rc = upload_tables(h, S, T, J, barcode_mismatches)) { mipgen_reads_release(h); return rc; }
     h->reads_assign_ms = 0.0;
     h->sample_assign_ms = barcodes ? 0.0 : -1.0;
     return MIPGEN_OK;
 }
 
-// A feed call of a consensus session.  Everything that can refuse the chunk - the arena's budget, free device memory, every allocation - comes before the first
-// copy or launch: a refused chunk leaves the session as it was.  The chunk's bases and qualities go straight into its block and stay there; k_read_assign and
-// k_sample_assign read them where they lie.  The kernel trusts the offsets: feed_impl has checked them.
-static int feed_consensus(mipgen_accel* h, ReadsSession* S, int64_t n_pairs, const char* ext_bytes, const char* ext_qual, const int64_t* ext_offsets, size_t eb,
-                          const char* lig_bytes, const char* lig_qual, const int64_t* lig_offsets, size_t lb, const char* index_bytes, const int64_t* index_offsets, size_t ib)
+// One feed call (kind: of the entry point; a consensus call carries the qualities, and the index reads if its session has samples).  A session that keeps its reads puts the
+// chunk's bases and qualities straight into a block of its own (ChunkLayout), where the kernels read them and where they stay.  Everything that can refuse such a chunk - the
+// arena's budget, free device memory, every allocation - comes before the first copy or launch: a refused chunk leaves the session as it was.
+static int feed_impl(mipgen_accel* h, int kind, int64_t n_pairs, const char* ext_bytes, const char* ext_qual, const int64_t* ext_offsets, const char* lig_bytes,
+                     const char* lig_qual, const int64_t* lig_offsets, const char* index_bytes, const int64_t* index_offsets)
 {
-    const bool with_index = S->samples;
-    const ChunkLayout L(n_pairs, eb, lb);
-    if (L.total > S->arena_cap - S->arena_used)
-        return fail(MIPGEN_E_NOMEM, "consensus reads: a chunk of %lld pairs needs %zu bytes of the arena, %zu of %zu are left (open the session with a larger arena_bytes)",
-                    (long long)n_pairs, L.total, S->arena_cap - S->arena_used, S->arena_cap);
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    const size_t have = (S->ext_off.cap + S->lig_off.cap + S->keys.cap) * 8 + S->assign.cap * 4 + S->idx_bytes.cap + S->idx_off.cap * 8 + (S->row.cap + S->sample_index.cap) * 4;
-    const size_t need = 2 * (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 12 + (with_index ? ib + (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 8 : 0);
-    if (L.total + need + need / 8 + ((size_t)64 << 20) > free_b + have)
-        return fail(MIPGEN_E_NOMEM, "consensus reads: a chunk of %lld pairs needs %zu MiB of device memory, %zu MiB are free", (long long)n_pairs, (L.total + need) >> 20,
-                    (free_b + have) >> 20);
-    // (keys: k_read_assign's sort-unique keys of this chunk, written and never read - a consensus session counts its unique tags from its groups)
-    if (S->ext_off.reserve((size_t)n_pairs + 1) || S->lig_off.reserve((size_t)n_pairs + 1) || S->assign.reserve((size_t)n_pairs) || S->keys.reserve((size_t)n_pairs))
-        return MIPGEN_E_NOMEM;
-    if (with_index && (S->idx_bytes.reserve(ib + 8) || S->idx_off.reserve((size_t)n_pairs + 1) || S->row.reserve((size_t)n_pairs) || S->sample_index.reserve((size_t)n_pairs)))
-        return MIPGEN_E_NOMEM;
-    uint8_t* block = nullptr;
-    if (hipMalloc((void**)&block, L.total) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MIPGEN_E_NOMEM, "consensus reads: hipMalloc of a chunk of %zu bytes failed", L.total);
-    }
-    hipStream_t st = h->stream;
-    hipError_t e = hipSuccess;
-    auto step = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    if (eb) { step(hipMemcpyAsync(block + L.ext, ext_bytes, eb, hipMemcpyHostToDevice, st)); step(hipMemcpyAsync(block + L.ext_qual, ext_qual, eb, hipMemcpyHostToDevice, st)); }
-    if (lb) { step(hipMemcpyAsync(block + L.lig, lig_bytes, lb, hipMemcpyHostToDevice, st)); step(hipMemcpyAsync(block + L.lig_qual, lig_qual, lb, hipMemcpyHostToDevice, st)); }
-    step(hipMemcpyAsync(S->ext_off.p, ext_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
-    step(hipMemcpyAsync(S->lig_off.p, lig_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
-    step(hipMemsetAsync(&S->ctr.p->n_keys, 0, sizeof(unsigned long long), st));
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    const bool timed = h->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventCreate(&ev[2]) == hipSuccess &&
-                       hipEventCreate(&ev[3]) == hipSuccess;
-    if (with_index) {
-        if (ib) step(hipMemcpyAsync(S->idx_bytes.p, index_bytes, ib, hipMemcpyHostToDevice, st));
-        step(hipMemcpyAsync(S->idx_off.p, index_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
-        if (timed) (void)hipEventRecord(ev[0], st);
-        if (e == hipSuccess)
-            step(mipgen_launch_sample_assign(st, &S->sample_table, n_pairs, S->idx_bytes.p, S->idx_off.p, index_offsets[0], S->row.p, S->sample_index.p, S->row_pairs.p, S->sctr.p));
-        if (timed) (void)hipEventRecord(ev[1], st);
-    }
-    const int32_t* row = with_index ? S->row.p : nullptr;
-    if (timed) (void)hipEventRecord(ev[2], st);
-    if (e == hipSuccess)
-        step(mipgen_launch_read_assign(st, &S->P, S->probes.p, &S->ext_seeds.view, &S->lig_seeds.view, 0, n_pairs, block + L.ext, S->ext_off.p, ext_offsets[0], block + L.lig,
-                                       S->lig_off.p, lig_offsets[0], S->assign.p, S->reads.p, S->keys.p, (int64_t)S->keys.cap, S->ctr.p, row));
-    if (timed) (void)hipEventRecord(ev[3], st);
-    if (e == hipSuccess)
-        step(mipgen_launch_member_keys(st, &S->P, n_pairs, (uint32_t)S->total_pairs, S->assign.p, row, block + L.ext, S->ext_off.p, ext_offsets[0], block + L.lig, S->lig_off.p,
-                                       lig_offsets[0], L.qdelta, 1ull << S->end_bit, reinterpret_cast<uint64_t*>(block + L.keys), reinterpret_cast<uint32_t*>(block + L.ids),
-                                       reinterpret_cast<ConsensusPair*>(block + L.recs), S->cctr.p));
-    const hipError_t es = hipStreamSynchronize(st);                        // the caller's arrays are free when the call returns
-    step(es);
-    float ms = 0.f;
-    if (timed && e == hipSuccess) {
-        if (with_index && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) h->sample_assign_ms += ms;
-        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) h->reads_assign_ms += ms;
-    }
-    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
-    if (e != hipSuccess) {
-        (void)hipFree(block);
-        return fail(MIPGEN_E_HIP, "mipgen_accel_reads_feed_consensus: %s", hipGetErrorString(e));
-    }
-    S->chunks.push_back({block, L.total, S->total_pairs, n_pairs});
-    S->total_pairs += n_pairs;
-    S->arena_used += L.total;
-    S->last_pairs = n_pairs;
-    return MIPGEN_OK;
-}
-
-// kind: of the call (FEED_*); a consensus call carries the qualities, and the index reads if its session has samples
-static int feed_impl(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets, int kind,
-                     const char* index_bytes, const int64_t* index_offsets, const char* ext_qual = nullptr, const char* lig_qual = nullptr)
-{
-    if (!h || n_pairs < 0 || (n_pairs > 0 && (!ext_bytes || !ext_offsets || !lig_bytes || !lig_offsets))) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (kind == FEED_SAMPLES && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (kind == FEED_CONSENSUS && n_pairs > 0 && (!ext_qual || !lig_qual)) return fail(MIPGEN_E_INVALID, "bad arguments: no qualities");
-    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    if (h->reads->consensus != (kind == FEED_CONSENSUS))
-        return fail(MIPGEN_E_STATE, kind == FEED_CONSENSUS ? "the open session keeps no reads: it was not opened by mipgen_accel_reads_open_consensus"
-                                                           : "the open session is a consensus session: mipgen_accel_reads_feed_consensus feeds it");
-    const bool with_index = kind == FEED_CONSENSUS ? h->reads->samples : kind == FEED_SAMPLES;
-    if (h->reads->samples != with_index)
-        return fail(MIPGEN_E_STATE, with_index ? "the open session has no samples: mipgen_accel_reads_feed feeds it" : "the open session has samples: mipgen_accel_reads_feed_samples feeds it");
-    if (kind == FEED_CONSENSUS && with_index && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments: the session has samples and the call no index reads");
+    // 1. arguments and state
+    if (!h || n_pairs < 0 || (n_pairs > 0 && (!ext_bytes || !ext_offsets || !lig_bytes || !lig_offsets || (kind == KIND_SAMPLES && (!index_bytes || !index_offsets)))))
+        return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (kind == KIND_CONSENSUS && n_pairs > 0 && (!ext_qual || !lig_qual)) return fail(MIPGEN_E_INVALID, "bad arguments: no qualities");
+    ReadsSession* S = nullptr;
+    if (int rc = session_for(h, kind, true, &S)) return rc;
+    const bool with_index = S->samples, keep = S->consensus;
+    if (keep && with_index && n_pairs > 0 && (!index_bytes || !index_offsets)) return fail(MIPGEN_E_INVALID, "bad arguments: the session has samples and the call no index reads");
     if (n_pairs > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld pairs in one call (at most 2^31 - 1)", (long long)n_pairs);
-    ReadsSession* S = h->reads;
-    if (S->consensus && S->total_pairs + n_pairs > 0x7fffffff)
-        return fail(MIPGEN_E_INVALID, "%lld + %lld pairs: a consensus session holds at most 2^31 - 1 (pair ids are 32-bit)", (long long)S->total_pairs, (long long)n_pairs);
-    if (!S->consensus || n_pairs == 0) S->last_pairs = 0;                   // (a refused chunk leaves a consensus session as it was, its last assignment included)
+    if (keep && S->cons.total_pairs + n_pairs > 0x7fffffff)
+        return fail(MIPGEN_E_INVALID, "%lld + %lld pairs: a consensus session holds at most 2^31 - 1 (pair ids are 32-bit)", (long long)S->cons.total_pairs, (long long)n_pairs);
+    if (!keep || n_pairs == 0) S->last_pairs = 0;                           // (a refused chunk leaves a consensus session as it was, its last assignment included)
     if (n_pairs == 0) return MIPGEN_OK;
-    // the kernel trusts the offsets: they are checked here
+
+    // 2. the kernels trust the offsets: they are checked here
     for (int f = 0; f < (with_index ? 3 : 2); f++) {
         const int64_t* off = f == 2 ? index_offsets : f ? lig_offsets : ext_offsets;
         const char* what = f == 2 ? "index" : f ? "ligation" : "extension";
@@ -489,68 +472,237 @@ static int feed_impl(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, co
     }
     const size_t eb = (size_t)(ext_offsets[n_pairs] - ext_offsets[0]), lb = (size_t)(lig_offsets[n_pairs] - lig_offsets[0]);
     const size_t ib = with_index ? (size_t)(index_offsets[n_pairs] - index_offsets[0]) : 0;
+    const size_t np = (size_t)n_pairs;
     HIP_TRY(hipSetDevice(h->device));
-    if (S->consensus) return feed_consensus(h, S, n_pairs, ext_bytes, ext_qual, ext_offsets, eb, lig_bytes, lig_qual, lig_offsets, lb, index_bytes, index_offsets, ib);
+
+    // 3. the budget: the arena's, then what the call allocates against free device memory (`have`: what its buffers hold already); a kept chunk has 8 bytes per pair of scratch keys
+    const ChunkLayout L(n_pairs, eb, lb);
+    const size_t block_bytes = keep ? L.total : 0;
+    if (keep && L.total > S->cons.arena_cap - S->cons.arena_used)
+        return fail(MIPGEN_E_NOMEM, "consensus reads: a chunk of %lld pairs needs %zu bytes of the arena, %zu of %zu are left (open the session with a larger arena_bytes)",
+                    (long long)n_pairs, L.total, S->cons.arena_cap - S->cons.arena_used, S->cons.arena_cap);
     size_t free_b = 0;
     if (int rc = free_device_bytes(&free_b)) return rc;
-    const size_t have = S->ext_bytes.cap + S->lig_bytes.cap + (S->ext_off.cap + S->lig_off.cap) * 8 + S->assign.cap * 4 + S->idx_bytes.cap + S->idx_off.cap * 8 +
-                        (S->row.cap + S->sample_index.cap) * 4;
-    const size_t need = eb + lb + 2 * (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 4 + (with_index ? ib + (size_t)(n_pairs + 1) * 8 + (size_t)n_pairs * 8 : 0);
-    if (need + need / 8 + ((size_t)64 << 20) > free_b + have)
-        return fail(MIPGEN_E_NOMEM, "read counter: a chunk of %lld pairs needs %zu MiB of device memory, %zu MiB are free (feed fewer pairs per call)", (long long)n_pairs,
-                    need >> 20, (free_b + have) >> 20);
-    // (+ 8: the kernel fetches the bases as aligned 32-bit words, up to 5 bytes beyond the last read)
-    if (S->ext_bytes.reserve(eb + 8) || S->lig_bytes.reserve(lb + 8) || S->ext_off.reserve((size_t)n_pairs + 1) || S->lig_off.reserve((size_t)n_pairs + 1) ||
-        S->assign.reserve((size_t)n_pairs))
-        return MIPGEN_E_NOMEM;
-    if (with_index && (S->idx_bytes.reserve(ib + 8) || S->idx_off.reserve((size_t)n_pairs + 1) || S->row.reserve((size_t)n_pairs) || S->sample_index.reserve((size_t)n_pairs)))
-        return MIPGEN_E_NOMEM;
-    struct IdleOnExit { hipStream_t s; ~IdleOnExit() { (void)hipStreamSynchronize(s); } } idle_on_exit{h->stream};      // the caller's arrays are free when the call returns
-    if (eb) HIP_TRY(hipMemcpyAsync(S->ext_bytes.p, ext_bytes, eb, hipMemcpyHostToDevice, h->stream));
-    if (lb) HIP_TRY(hipMemcpyAsync(S->lig_bytes.p, lig_bytes, lb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(S->ext_off.p, ext_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(S->lig_off.p, lig_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    const bool tags = S->P.te + S->P.tl > 0;
-    std::vector<hipEvent_t> ev;
-    int rc = MIPGEN_OK;
-    hipEvent_t sa = nullptr, sb = nullptr;
+    const size_t have = (keep ? S->keys.keys.cap * 8 : S->ext_bytes.cap + S->lig_bytes.cap) + (S->ext_off.cap + S->lig_off.cap) * 8 + S->assign.cap * 4 + S->smp.idx_bytes.cap +
+                        S->smp.idx_off.cap * 8 + (S->smp.row.cap + S->smp.sample_index.cap) * 4;
+    const size_t need = (keep ? np * 8 : eb + lb) + 2 * (np + 1) * 8 + np * 4 + (with_index ? ib + (np + 1) * 8 + np * 8 : 0);
+    if (block_bytes + need + need / 8 + ((size_t)64 << 20) > free_b + have)
+        return fail(MIPGEN_E_NOMEM, "%s: a chunk of %lld pairs needs %zu MiB of device memory, %zu MiB are free%s", keep ? "consensus reads" : "read counter", (long long)n_pairs,
+                    (block_bytes + need) >> 20, (free_b + have) >> 20, keep ? "" : " (feed fewer pairs per call)");
+
+    // 4. reservations (+ 8: k_read_assign fetches the bases as aligned 32-bit words, up to 5 bytes beyond the last read; ChunkLayout has the same tail), and the chunk's block
+    if (!keep && (S->ext_bytes.reserve(eb + 8) || S->lig_bytes.reserve(lb + 8))) return MIPGEN_E_NOMEM;
+    if (S->ext_off.reserve(np + 1) || S->lig_off.reserve(np + 1) || S->assign.reserve(np)) return MIPGEN_E_NOMEM;
+    // (keys of a kept chunk: k_read_assign's, written and never read - a consensus session counts its unique tags from its groups)
+    if (keep && S->keys.keys.reserve(np)) return MIPGEN_E_NOMEM;
+    if (with_index && (S->smp.idx_bytes.reserve(ib + 8) || S->smp.idx_off.reserve(np + 1) || S->smp.row.reserve(np) || S->smp.sample_index.reserve(np))) return MIPGEN_E_NOMEM;
+    uint8_t* block = nullptr;
+    if (keep && hipMalloc((void**)&block, L.total) != hipSuccess) { (void)hipGetLastError(); return fail(MIPGEN_E_NOMEM, "consensus reads: hipMalloc of a chunk of %zu bytes failed", L.total); }
+    FreeOnExit free_block{block};                                           // (until the chunk is the session's: stage 11)
+    hipStream_t st = h->stream;
+    SpanTimer sample_time{h->timing, st}, assign_time{h->timing, st};
+    IdleOnExit idle{st};                                                    // (ends before free_block and the timers do: events go once the stream is idle)
+
+    // 5. uploads
+    uint8_t *ext_dev = keep ? block + L.ext : S->ext_bytes.p, *lig_dev = keep ? block + L.lig : S->lig_bytes.p;
+    if (eb) HIP_TRY(hipMemcpyAsync(ext_dev, ext_bytes, eb, hipMemcpyHostToDevice, st));
+    if (eb && keep) HIP_TRY(hipMemcpyAsync(block + L.ext_qual, ext_qual, eb, hipMemcpyHostToDevice, st));
+    if (lb) HIP_TRY(hipMemcpyAsync(lig_dev, lig_bytes, lb, hipMemcpyHostToDevice, st));
+    if (lb && keep) HIP_TRY(hipMemcpyAsync(block + L.lig_qual, lig_qual, lb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S->ext_off.p, ext_offsets, (np + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S->lig_off.p, lig_offsets, (np + 1) * 8, hipMemcpyHostToDevice, st));
+    if (keep) HIP_TRY(hipMemsetAsync(&S->ctr.p->n_keys, 0, sizeof(unsigned long long), st));
+
+    // 6. the sample row of every pair of the chunk, before the launches that count into its cells
     if (with_index) {
-        // the sample row of every pair of the chunk, before the launches that count into its cells
-        if (ib) HIP_TRY(hipMemcpyAsync(S->idx_bytes.p, index_bytes, ib, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(S->idx_off.p, index_offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, h->stream));
-        if (h->timing && hipEventCreate(&sa) == hipSuccess && hipEventCreate(&sb) == hipSuccess) (void)hipEventRecord(sa, h->stream);
-        const hipError_t e = mipgen_launch_sample_assign(h->stream, &S->sample_table, n_pairs, S->idx_bytes.p, S->idx_off.p, index_offsets[0], S->row.p, S->sample_index.p,
-                                                         S->row_pairs.p, S->sctr.p);
-        if (e != hipSuccess) rc = fail(MIPGEN_E_HIP, "k_sample_assign: %s", hipGetErrorString(e));
-        if (sb) (void)hipEventRecord(sb, h->stream);
+        if (ib) HIP_TRY(hipMemcpyAsync(S->smp.idx_bytes.p, index_bytes, ib, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(S->smp.idx_off.p, index_offsets, (np + 1) * 8, hipMemcpyHostToDevice, st));
+        sample_time.mark();
+        HIP_TRY(mipgen_launch_sample_assign(st, &S->smp.table, n_pairs, S->smp.idx_bytes.p, S->smp.idx_off.p, index_offsets[0], S->smp.row.p, S->smp.sample_index.p,
+                                            S->smp.row_pairs.p, S->smp.ctr.p));
+        sample_time.mark();
     }
-    for (int64_t p0 = 0; p0 < n_pairs && rc == MIPGEN_OK;) {
+    const int32_t* row = with_index ? S->smp.row.p : nullptr;
+
+    // 7. k_read_assign: a key list takes as many pairs per launch as it has room for; a kept chunk goes in one launch, its keys into the scratch list
+    const bool listed = !keep && S->P.te + S->P.tl > 0;
+    for (int64_t p0 = 0; p0 < n_pairs;) {
         int64_t c = n_pairs - p0;
-        if (tags) { if ((rc = make_key_room(h, S, c, &c))) break; c = std::min(c, n_pairs - p0); }
-        hipEvent_t a = nullptr, b = nullptr;
-        if (h->timing && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ev.push_back(a); ev.push_back(b); (void)hipEventRecord(a, h->stream); }
-        const hipError_t e = mipgen_launch_read_assign(h->stream, &S->P, S->probes.p, &S->ext_seeds.view, &S->lig_seeds.view, p0, c, S->ext_bytes.p, S->ext_off.p, ext_offsets[0],
-                                                       S->lig_bytes.p, S->lig_off.p, lig_offsets[0], S->assign.p, S->reads.p, S->keys.p, S->key_cap, S->ctr.p,
-                                                       with_index ? S->row.p : nullptr);
-        if (e != hipSuccess) rc = fail(MIPGEN_E_HIP, "k_read_assign: %s", hipGetErrorString(e));
-        if (b) (void)hipEventRecord(b, h->stream);
-        if (tags) S->key_ub += c;
+        if (listed) {
+            if (int rc = S->keys.make_room(h, &S->ctr.p->n_keys, c, &c)) return rc;
+            c = std::min(c, n_pairs - p0);
+        }
+        assign_time.mark();
+        HIP_TRY(mipgen_launch_read_assign(st, &S->P, S->probes.p, &S->ext_seeds.view, &S->lig_seeds.view, p0, c, ext_dev, S->ext_off.p, ext_offsets[0], lig_dev, S->lig_off.p,
+                                          lig_offsets[0], S->assign.p, S->reads.p, S->keys.keys.p, keep ? (int64_t)S->keys.keys.cap : S->keys.cap, S->ctr.p, row));
+        assign_time.mark();
+        if (listed) S->keys.ub += c;
         p0 += c;
     }
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc == MIPGEN_OK && es != hipSuccess) rc = fail(MIPGEN_E_HIP, "mipgen_accel_reads_feed: %s", hipGetErrorString(es));
-    for (size_t k = 0; k + 1 < ev.size(); k += 2) {
-        float ms = 0.f;
-        if (rc == MIPGEN_OK && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) h->reads_assign_ms += ms;
+
+    // 8. the (key, pair id) and record of every pair of a kept chunk
+    if (keep)
+        HIP_TRY(mipgen_launch_member_keys(st, &S->P, n_pairs, (uint32_t)S->cons.total_pairs, S->assign.p, row, ext_dev, S->ext_off.p, ext_offsets[0], lig_dev, S->lig_off.p,
+                                          lig_offsets[0], L.qdelta, 1ull << S->keys.end_bit, reinterpret_cast<uint64_t*>(block + L.keys), reinterpret_cast<uint32_t*>(block + L.ids),
+                                          reinterpret_cast<ConsensusPair*>(block + L.recs), S->cons.ctr.p));
+
+    // 9. - 11. synchronise, book the times, commit
+    HIP_TRY(idle.wait());
+    sample_time.add_to(&h->sample_assign_ms); assign_time.add_to(&h->reads_assign_ms);
+    if (keep) {
+        S->cons.chunks.push_back({block, L.total, S->cons.total_pairs, n_pairs});
+        free_block.p = nullptr;
+        S->cons.total_pairs += n_pairs;
+        S->cons.arena_used += L.total;
     }
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (sa && sb) {
-        float ms = 0.f;
-        if (rc == MIPGEN_OK && hipEventElapsedTime(&ms, sa, sb) == hipSuccess) h->sample_assign_ms += ms;
+    S->last_pairs = n_pairs;
+    return MIPGEN_OK;
+}
+
+// the sample index (sample: true) or the probe index of every pair of the last feed call
+static int download_last(mipgen_accel* h, bool sample, int32_t* out, int64_t capacity)
+{
+    if (!h || !out) return fail(MIPGEN_E_INVALID, "bad arguments");
+    const ReadsSession* S = h->reads;
+    if (!S) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (sample && !S->samples) return fail(MIPGEN_E_STATE, "the open session has no samples");
+    if (capacity < S->last_pairs) return fail(MIPGEN_E_INVALID, "capacity %lld < %lld pairs", (long long)capacity, (long long)S->last_pairs);
+    HIP_TRY(hipSetDevice(h->device));
+    if (S->last_pairs) HIP_TRY(hipMemcpyAsync(out, sample ? S->smp.sample_index.p : S->assign.p, (size_t)S->last_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MIPGEN_OK;
+}
+
+// The groups of a consensus session and their consensus reads into R (DESIGN 4.11); unique tags per cell - the groups of the cell - into S->unique.
+static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R)
+{
+    hipStream_t st = h->stream;
+    ConsensusPart& C = S->cons;
+    DevBuf<char>& temp = S->keys.sort_temp;
+    const int64_t N = C.total_pairs;
+    h->consensus_vote_ms = h->consensus_sort_ms = -1.0;
+    ConsensusCounters cc;
+    HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t M = (int64_t)cc.members;                                   // pairs in a group: the keys below the sentinel
+    if (M == 0) return MIPGEN_OK;
+    // every pair's (key, id) and record, chunk after chunk, in feed order
+    if (C.c_keys_in.reserve((size_t)N) || C.c_keys_out.reserve((size_t)N) || C.c_ids_in.reserve((size_t)N) || C.c_ids_out.reserve((size_t)N) || C.c_recs.reserve((size_t)N))
+        return MIPGEN_E_NOMEM;
+    for (const ArenaChunk& c : C.chunks) {
+        const ChunkLayout L(c.n, 0, 0);                                      // (the per-pair parts lie in front of the bytes)
+        HIP_TRY(hipMemcpyAsync(C.c_recs.p + c.pair0, c.block + L.recs, (size_t)c.n * sizeof(ConsensusPair), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(C.c_keys_in.p + c.pair0, c.block + L.keys, (size_t)c.n * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(C.c_ids_in.p + c.pair0, c.block + L.ids, (size_t)c.n * 4, hipMemcpyDeviceToDevice, st));
     }
-    if (sa) (void)hipEventDestroy(sa);
-    if (sb) (void)hipEventDestroy(sb);
-    if (rc == MIPGEN_OK) S->last_pairs = n_pairs;
+    // one scratch buffer for the sort, the run boundaries and the three scans (sized for the most entries any of them sees)
+    size_t t_sort = 0, t_runs = 0, t_u32 = 0, t_i64 = 0;
+    const int sort_bits = S->keys.end_bit + 1;                               // the cell and tag bits that can be set, and the sentinel's
+    HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, C.c_keys_in.p, C.c_keys_out.p, C.c_ids_in.p, C.c_ids_out.p, N, sort_bits));
+    HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, C.c_keys_out.p, M, C.c_keys_in.p, reinterpret_cast<int32_t*>(C.c_ids_in.p), &C.ctr.p->groups));
+    HIP_TRY(mipgen_consensus_scan_u32(st, nullptr, &t_u32, reinterpret_cast<int32_t*>(C.c_ids_in.p), C.c_ids_in.p, M + 1));
+    HIP_TRY(mipgen_consensus_scan_i64(st, nullptr, &t_i64, nullptr, nullptr, M + 1));
+    if (temp.reserve(std::max(std::max(t_sort, t_runs), std::max(t_u32, t_i64)) + 16)) return MIPGEN_E_NOMEM;
+    size_t tb = 0;
+    auto temp_bytes = [&]() { tb = temp.cap; return &tb; };                  // (every user of the scratch is told its whole size)
+    SpanTimer sort_time{h->timing, st}, vote_time{h->timing, st};
+    // sort; the runs of the member keys: group key and family size (the fed arrays are free once sorted, and take them)
+    sort_time.mark();
+    HIP_TRY(mipgen_consensus_sort(st, temp.p, temp_bytes(), C.c_keys_in.p, C.c_keys_out.p, C.c_ids_in.p, C.c_ids_out.p, N, sort_bits));
+    uint64_t* group_keys = C.c_keys_in.p;
+    int32_t* family = reinterpret_cast<int32_t*>(C.c_ids_in.p);
+    HIP_TRY(mipgen_consensus_runs(st, temp.p, temp_bytes(), C.c_keys_out.p, M, group_keys, family, &C.ctr.p->groups));
+    sort_time.mark();
+    HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t G = (int64_t)cc.groups;
+    if (G < 1 || G > M) return fail(MIPGEN_E_STATE, "consensus reads: %lld groups of %lld members", (long long)G, (long long)M);
+    if (R->keys.reserve((size_t)G) || R->family.reserve((size_t)G) || R->ext_off.reserve((size_t)G + 1) || R->lig_off.reserve((size_t)G + 1) || C.c_start.reserve((size_t)G) ||
+        C.c_order.reserve((size_t)G) || C.c_ext_len.reserve((size_t)G + 1) || C.c_lig_len.reserve((size_t)G + 1))
+        return MIPGEN_E_NOMEM;
+    HIP_TRY(hipMemcpyAsync(R->keys.p, group_keys, (size_t)G * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R->family.p, family, (size_t)G * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(mipgen_consensus_scan_u32(st, temp.p, temp_bytes(), R->family.p, C.c_start.p, G));
+    HIP_TRY(mipgen_launch_consensus_partition(st, R->family.p, G, C.c_order.p, C.ctr.p));
+    HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_small = (int64_t)cc.n_small, n_big = (int64_t)cc.n_big;
+    if (n_small + n_big != G) return fail(MIPGEN_E_STATE, "consensus reads: %lld + %lld groups listed of %lld", (long long)n_small, (long long)n_big, (long long)G);
+    // the length of every group's two consensus reads (entry G stays 0), and from their exclusive sums where each is written
+    HIP_TRY(hipMemsetAsync(C.c_ext_len.p, 0, (size_t)(G + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(C.c_lig_len.p, 0, (size_t)(G + 1) * 8, st));
+    HIP_TRY(mipgen_launch_consensus_len(st, S->P.te, S->P.tl, G, C.c_order.p, n_big, C.c_start.p, R->family.p, C.c_ids_out.p, C.c_recs.p, C.c_ext_len.p, C.c_lig_len.p));
+    HIP_TRY(mipgen_consensus_scan_i64(st, temp.p, temp_bytes(), C.c_ext_len.p, R->ext_off.p, G + 1));
+    HIP_TRY(mipgen_consensus_scan_i64(st, temp.p, temp_bytes(), C.c_lig_len.p, R->lig_off.p, G + 1));
+    int64_t totals[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&totals[0], R->ext_off.p + G, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&totals[1], R->lig_off.p + G, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (R->ext_seq.reserve((size_t)totals[0] + 1) || R->ext_qual.reserve((size_t)totals[0] + 1) || R->lig_seq.reserve((size_t)totals[1] + 1) ||
+        R->lig_qual.reserve((size_t)totals[1] + 1))
+        return MIPGEN_E_NOMEM;
+    vote_time.mark();
+    HIP_TRY(mipgen_launch_consensus_vote(st, S->P.te, S->P.tl, G, C.c_order.p, n_small, n_big, C.c_start.p, R->family.p, C.c_ids_out.p, C.c_recs.p, R->ext_off.p,
+                                         R->lig_off.p, R->ext_seq.p, R->ext_qual.p, R->lig_seq.p, R->lig_qual.p));
+    vote_time.mark();
+    // unique tags of a cell = its groups: the group keys ARE the sorted, duplicate-free key list of a plain session
+    HIP_TRY(mipgen_launch_reads_histogram(st, R->keys.p, G, S->unique.p));
+    HIP_TRY(hipStreamSynchronize(st));
+    double sort_ms = 0.0, vote_ms = 0.0;
+    if (sort_time.add_to(&sort_ms)) h->consensus_sort_ms = sort_ms;
+    if (vote_time.add_to(&vote_ms)) h->consensus_vote_ms = vote_ms;
+    R->n_groups = G; R->ext_bytes = totals[0]; R->lig_bytes = totals[1];
+    return MIPGEN_OK;
+}
+
+static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
+                       int64_t* row_pairs)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n = (size_t)S->P.n_probes * (size_t)S->rows;                // cells
+    const bool tags = S->P.te + S->P.tl > 0;
+    if (tags && !S->consensus) {                                             // (a consensus session: consensus_finish counted its groups into `unique`)
+        if (int rc = S->keys.sort_unique(h, &S->ctr.p->n_keys)) return rc;
+        HIP_TRY(mipgen_launch_reads_histogram(h->stream, S->keys.keys.p, S->keys.ub, S->unique.p));
+    }
+    ReadsCounters c;
+    HIP_TRY(hipMemcpyAsync(&c, S->ctr.p, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are downloaded in place");
+    if (reads) HIP_TRY(hipMemcpyAsync(reads, S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    if (unique_tags) HIP_TRY(hipMemcpyAsync(unique_tags, tags ? S->unique.p : S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    SampleCounters sc{0, 0};
+    if (S->samples) {
+        HIP_TRY(hipMemcpyAsync(&sc, S->smp.ctr.p, sizeof sc, hipMemcpyDeviceToHost, h->stream));
+        if (row_pairs) HIP_TRY(hipMemcpyAsync(row_pairs, S->smp.row_pairs.p, (size_t)S->rows * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (c.keys_lost) return fail(MIPGEN_E_STATE, "read counter: %llu keys did not fit the key buffer", c.keys_lost);
+    if (sample_totals) *sample_totals = {(int64_t)sc.none, (int64_t)sc.ambiguous};
+    if (totals) *totals = {(int64_t)c.pairs, (int64_t)c.assigned, (int64_t)c.ambiguous, (int64_t)c.unassigned, (int64_t)c.tag_n, (int64_t)c.overflow};
+    return MIPGEN_OK;
+}
+
+// A finish call of any kind: the session is released whatever comes of it; the consensus reads of a session that kept its reads stay on the handle.
+static int finish_session(mipgen_accel* h, int kind, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals, int64_t* row_pairs,
+                          mipgen_consensus_sizes* sizes)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    ReadsSession* S = nullptr;
+    if (int rc = session_for(h, kind, false, &S)) return rc;
+    ConsensusResult* R = nullptr;
+    int rc = MIPGEN_OK;
+    if (S->consensus) {
+        HIP_TRY(hipSetDevice(h->device));
+        R = new ConsensusResult;
+        rc = consensus_finish(h, S, R);
+    }
+    if (rc == MIPGEN_OK) rc = finish_impl(h, S, reads, unique_tags, totals, sample_totals, row_pairs);
+    mipgen_reads_release(h);
+    if (R && rc != MIPGEN_OK) { R->release(); delete R; }
+    if (R && rc == MIPGEN_OK) {
+        h->consensus = R;
+        if (sizes) *sizes = {R->n_groups, R->ext_bytes, R->lig_bytes};
+    }
     return rc;
 }
 
@@ -566,175 +718,6 @@ int mipgen_accel_reads_open_samples(mipgen_accel* h, const mipgen_probe* probes,
     return open_impl(h, probes, n, ext_tag, lig_tag, max_mismatches, barcodes, n_samples, barcode_mismatches);
 }
 
-int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets)
-{
-    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, FEED_PLAIN, nullptr, nullptr);
-}
-
-int mipgen_accel_reads_feed_samples(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets,
-                                    const char* index_bytes, const int64_t* index_offsets)
-{
-    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, FEED_SAMPLES, index_bytes, index_offsets);
-}
-
-int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity)
-{
-    if (!h || !sample_index) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    if (!h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has no samples");
-    if (capacity < h->reads->last_pairs) return fail(MIPGEN_E_INVALID, "capacity %lld < %lld pairs", (long long)capacity, (long long)h->reads->last_pairs);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->reads->last_pairs) HIP_TRY(hipMemcpyAsync(sample_index, h->reads->sample_index.p, (size_t)h->reads->last_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MIPGEN_OK;
-}
-
-int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, int64_t capacity)
-{
-    if (!h || !probe_index) return fail(MIPGEN_E_INVALID, "bad arguments");
-    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    if (capacity < h->reads->last_pairs) return fail(MIPGEN_E_INVALID, "capacity %lld < %lld pairs", (long long)capacity, (long long)h->reads->last_pairs);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->reads->last_pairs) HIP_TRY(hipMemcpyAsync(probe_index, h->reads->assign.p, (size_t)h->reads->last_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MIPGEN_OK;
-}
-
-// The groups of a consensus session and their consensus reads into R (DESIGN 4.11); unique tags per cell - the groups of the cell - into S->unique.
-static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R)
-{
-    hipStream_t st = h->stream;
-    const int64_t N = S->total_pairs;
-    h->consensus_vote_ms = h->consensus_sort_ms = -1.0;
-    ConsensusCounters cc;
-    HIP_TRY(hipMemcpyAsync(&cc, S->cctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t M = (int64_t)cc.members;                                   // pairs in a group: the keys below the sentinel
-    if (M == 0) return MIPGEN_OK;
-    // every pair's (key, id) and record, chunk after chunk, in feed order
-    if (S->c_keys_in.reserve((size_t)N) || S->c_keys_out.reserve((size_t)N) || S->c_ids_in.reserve((size_t)N) || S->c_ids_out.reserve((size_t)N) || S->c_recs.reserve((size_t)N))
-        return MIPGEN_E_NOMEM;
-    for (const ArenaChunk& c : S->chunks) {
-        const ChunkLayout L(c.n, 0, 0);                                      // (the per-pair parts lie in front of the bytes)
-        HIP_TRY(hipMemcpyAsync(S->c_recs.p + c.pair0, c.block + L.recs, (size_t)c.n * sizeof(ConsensusPair), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(S->c_keys_in.p + c.pair0, c.block + L.keys, (size_t)c.n * 8, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(S->c_ids_in.p + c.pair0, c.block + L.ids, (size_t)c.n * 4, hipMemcpyDeviceToDevice, st));
-    }
-    // one scratch buffer for the sort, the run boundaries and the three scans (sized for the most entries any of them sees)
-    size_t t_sort = 0, t_runs = 0, t_u32 = 0, t_i64 = 0;
-    const int sort_bits = S->end_bit + 1;                                    // the cell and tag bits that can be set, and the sentinel's
-    HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, S->c_keys_in.p, S->c_keys_out.p, S->c_ids_in.p, S->c_ids_out.p, N, sort_bits));
-    HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, S->c_keys_out.p, M, S->c_keys_in.p, reinterpret_cast<int32_t*>(S->c_ids_in.p), &S->cctr.p->groups));
-    HIP_TRY(mipgen_consensus_scan_u32(st, nullptr, &t_u32, reinterpret_cast<int32_t*>(S->c_ids_in.p), S->c_ids_in.p, M + 1));
-    HIP_TRY(mipgen_consensus_scan_i64(st, nullptr, &t_i64, nullptr, nullptr, M + 1));
-    if (S->sort_temp.reserve(std::max(std::max(t_sort, t_runs), std::max(t_u32, t_i64)) + 16)) return MIPGEN_E_NOMEM;
-    size_t tb = S->sort_temp.cap;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    const bool timed = h->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventCreate(&ev[2]) == hipSuccess &&
-                       hipEventCreate(&ev[3]) == hipSuccess;
-    struct Events { hipEvent_t* e; ~Events() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } events{ev};
-    // sort; the runs of the member keys: group key and family size (the fed arrays are free once sorted, and take them)
-    if (timed) (void)hipEventRecord(ev[0], st);
-    HIP_TRY(mipgen_consensus_sort(st, S->sort_temp.p, &tb, S->c_keys_in.p, S->c_keys_out.p, S->c_ids_in.p, S->c_ids_out.p, N, sort_bits));
-    uint64_t* group_keys = S->c_keys_in.p;
-    int32_t* family = reinterpret_cast<int32_t*>(S->c_ids_in.p);
-    tb = S->sort_temp.cap;
-    HIP_TRY(mipgen_consensus_runs(st, S->sort_temp.p, &tb, S->c_keys_out.p, M, group_keys, family, &S->cctr.p->groups));
-    if (timed) (void)hipEventRecord(ev[1], st);
-    HIP_TRY(hipMemcpyAsync(&cc, S->cctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t G = (int64_t)cc.groups;
-    if (G < 1 || G > M) return fail(MIPGEN_E_STATE, "consensus reads: %lld groups of %lld members", (long long)G, (long long)M);
-    if (R->keys.reserve((size_t)G) || R->family.reserve((size_t)G) || R->ext_off.reserve((size_t)G + 1) || R->lig_off.reserve((size_t)G + 1) || S->c_start.reserve((size_t)G) ||
-        S->c_order.reserve((size_t)G) || S->c_ext_len.reserve((size_t)G + 1) || S->c_lig_len.reserve((size_t)G + 1))
-        return MIPGEN_E_NOMEM;
-    HIP_TRY(hipMemcpyAsync(R->keys.p, group_keys, (size_t)G * 8, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(R->family.p, family, (size_t)G * 4, hipMemcpyDeviceToDevice, st));
-    tb = S->sort_temp.cap;
-    HIP_TRY(mipgen_consensus_scan_u32(st, S->sort_temp.p, &tb, R->family.p, S->c_start.p, G));
-    HIP_TRY(mipgen_launch_consensus_partition(st, R->family.p, G, S->c_order.p, S->cctr.p));
-    HIP_TRY(hipMemcpyAsync(&cc, S->cctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t n_small = (int64_t)cc.n_small, n_big = (int64_t)cc.n_big;
-    if (n_small + n_big != G) return fail(MIPGEN_E_STATE, "consensus reads: %lld + %lld groups listed of %lld", (long long)n_small, (long long)n_big, (long long)G);
-    // the length of every group's two consensus reads (entry G stays 0), and from their exclusive sums where each is written
-    HIP_TRY(hipMemsetAsync(S->c_ext_len.p, 0, (size_t)(G + 1) * 8, st));
-    HIP_TRY(hipMemsetAsync(S->c_lig_len.p, 0, (size_t)(G + 1) * 8, st));
-    HIP_TRY(mipgen_launch_consensus_len(st, S->P.te, S->P.tl, G, S->c_order.p, n_big, S->c_start.p, R->family.p, S->c_ids_out.p, S->c_recs.p, S->c_ext_len.p, S->c_lig_len.p));
-    tb = S->sort_temp.cap;
-    HIP_TRY(mipgen_consensus_scan_i64(st, S->sort_temp.p, &tb, S->c_ext_len.p, R->ext_off.p, G + 1));
-    tb = S->sort_temp.cap;
-    HIP_TRY(mipgen_consensus_scan_i64(st, S->sort_temp.p, &tb, S->c_lig_len.p, R->lig_off.p, G + 1));
-    int64_t totals[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(&totals[0], R->ext_off.p + G, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&totals[1], R->lig_off.p + G, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (R->ext_seq.reserve((size_t)totals[0] + 1) || R->ext_qual.reserve((size_t)totals[0] + 1) || R->lig_seq.reserve((size_t)totals[1] + 1) ||
-        R->lig_qual.reserve((size_t)totals[1] + 1))
-        return MIPGEN_E_NOMEM;
-    if (timed) (void)hipEventRecord(ev[2], st);
-    HIP_TRY(mipgen_launch_consensus_vote(st, S->P.te, S->P.tl, G, S->c_order.p, n_small, n_big, S->c_start.p, R->family.p, S->c_ids_out.p, S->c_recs.p, R->ext_off.p,
-                                         R->lig_off.p, R->ext_seq.p, R->ext_qual.p, R->lig_seq.p, R->lig_qual.p));
-    if (timed) (void)hipEventRecord(ev[3], st);
-    // unique tags of a cell = its groups: the group keys ARE the sorted, duplicate-free key list of a plain session
-    HIP_TRY(mipgen_launch_reads_histogram(st, R->keys.p, G, S->unique.p));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (timed && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) h->consensus_sort_ms = ms;
-    if (timed && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) h->consensus_vote_ms = ms;
-    R->n_groups = G; R->ext_bytes = totals[0]; R->lig_bytes = totals[1];
-    return MIPGEN_OK;
-}
-
-static int finish_impl(mipgen_accel* h, ReadsSession* S, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
-                       int64_t* row_pairs)
-{
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t n = (size_t)S->P.n_probes * (size_t)S->rows;                // cells
-    const bool tags = S->P.te + S->P.tl > 0;
-    if (tags && !S->consensus) {                                             // (a consensus session: consensus_finish counted its groups into `unique`)
-        if (int rc = sort_unique_keys(h, S)) return rc;
-        HIP_TRY(mipgen_launch_reads_histogram(h->stream, S->keys.p, S->key_ub, S->unique.p));
-    }
-    ReadsCounters c;
-    HIP_TRY(hipMemcpyAsync(&c, S->ctr.p, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are downloaded in place");
-    if (reads) HIP_TRY(hipMemcpyAsync(reads, S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (unique_tags) HIP_TRY(hipMemcpyAsync(unique_tags, tags ? S->unique.p : S->reads.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    SampleCounters sc{0, 0};
-    if (S->samples) {
-        HIP_TRY(hipMemcpyAsync(&sc, S->sctr.p, sizeof sc, hipMemcpyDeviceToHost, h->stream));
-        if (row_pairs) HIP_TRY(hipMemcpyAsync(row_pairs, S->row_pairs.p, (size_t)S->rows * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (c.keys_lost) return fail(MIPGEN_E_STATE, "read counter: %llu keys did not fit the key buffer", c.keys_lost);
-    if (sample_totals) *sample_totals = {(int64_t)sc.none, (int64_t)sc.ambiguous};
-    if (totals) *totals = {(int64_t)c.pairs, (int64_t)c.assigned, (int64_t)c.ambiguous, (int64_t)c.unassigned, (int64_t)c.tag_n, (int64_t)c.overflow};
-    return MIPGEN_OK;
-}
-
-int mipgen_accel_reads_finish(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals)
-{
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    if (h->reads->consensus) return fail(MIPGEN_E_STATE, "the open session is a consensus session: mipgen_accel_reads_finish_consensus closes it");
-    if (h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has samples: mipgen_accel_reads_finish_samples closes it");
-    const int rc = finish_impl(h, h->reads, reads, unique_tags, totals, nullptr, nullptr);
-    mipgen_reads_release(h);
-    return rc;
-}
-
-int mipgen_accel_reads_finish_samples(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals, int64_t* row_pairs)
-{
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    if (h->reads->consensus) return fail(MIPGEN_E_STATE, "the open session is a consensus session: mipgen_accel_reads_finish_consensus closes it");
-    if (!h->reads->samples) return fail(MIPGEN_E_STATE, "the open session has no samples: mipgen_accel_reads_finish closes it");
-    const int rc = finish_impl(h, h->reads, reads, unique_tags, totals, sample_totals, row_pairs);
-    mipgen_reads_release(h);
-    return rc;
-}
-
 int mipgen_accel_reads_open_consensus(mipgen_accel* h, const mipgen_probe* probes, int32_t n, int32_t ext_tag, int32_t lig_tag, int32_t max_mismatches,
                                       const char* const* barcodes, int32_t n_samples, int32_t barcode_mismatches, int64_t arena_bytes)
 {
@@ -742,27 +725,40 @@ int mipgen_accel_reads_open_consensus(mipgen_accel* h, const mipgen_probe* probe
     return open_impl(h, probes, n, ext_tag, lig_tag, max_mismatches, barcodes, n_samples, barcode_mismatches, true, arena_bytes);
 }
 
+int mipgen_accel_reads_feed(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets)
+{
+    return feed_impl(h, KIND_PLAIN, n_pairs, ext_bytes, nullptr, ext_offsets, lig_bytes, nullptr, lig_offsets, nullptr, nullptr);
+}
+
+int mipgen_accel_reads_feed_samples(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const int64_t* ext_offsets, const char* lig_bytes, const int64_t* lig_offsets,
+                                    const char* index_bytes, const int64_t* index_offsets)
+{
+    return feed_impl(h, KIND_SAMPLES, n_pairs, ext_bytes, nullptr, ext_offsets, lig_bytes, nullptr, lig_offsets, index_bytes, index_offsets);
+}
+
 int mipgen_accel_reads_feed_consensus(mipgen_accel* h, int64_t n_pairs, const char* ext_bytes, const char* ext_qual, const int64_t* ext_offsets, const char* lig_bytes,
                                       const char* lig_qual, const int64_t* lig_offsets, const char* index_bytes, const int64_t* index_offsets)
 {
-    return feed_impl(h, n_pairs, ext_bytes, ext_offsets, lig_bytes, lig_offsets, FEED_CONSENSUS, index_bytes, index_offsets, ext_qual, lig_qual);
+    return feed_impl(h, KIND_CONSENSUS, n_pairs, ext_bytes, ext_qual, ext_offsets, lig_bytes, lig_qual, lig_offsets, index_bytes, index_offsets);
+}
+
+int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity) { return download_last(h, true, sample_index, capacity); }
+int mipgen_accel_reads_last_assignment(mipgen_accel* h, int32_t* probe_index, int64_t capacity) { return download_last(h, false, probe_index, capacity); }
+
+int mipgen_accel_reads_finish(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals)
+{
+    return finish_session(h, KIND_PLAIN, reads, unique_tags, totals, nullptr, nullptr, nullptr);
+}
+
+int mipgen_accel_reads_finish_samples(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals, int64_t* row_pairs)
+{
+    return finish_session(h, KIND_SAMPLES, reads, unique_tags, totals, sample_totals, row_pairs, nullptr);
 }
 
 int mipgen_accel_reads_finish_consensus(mipgen_accel* h, int64_t* reads, int64_t* unique_tags, mipgen_read_totals* totals, mipgen_sample_totals* sample_totals,
                                         int64_t* row_pairs, mipgen_consensus_sizes* sizes)
 {
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->reads) return fail(MIPGEN_E_STATE, "no read-counting session is open");
-    if (!h->reads->consensus) return fail(MIPGEN_E_STATE, "the open session keeps no reads: mipgen_accel_reads_finish%s closes it", h->reads->samples ? "_samples" : "");
-    HIP_TRY(hipSetDevice(h->device));
-    ConsensusResult* R = new ConsensusResult;
-    int rc = consensus_finish(h, h->reads, R);
-    if (rc == MIPGEN_OK) rc = finish_impl(h, h->reads, reads, unique_tags, totals, sample_totals, row_pairs);
-    mipgen_reads_release(h);
-    if (rc != MIPGEN_OK) { R->release(); delete R; return rc; }
-    h->consensus = R;
-    if (sizes) *sizes = {R->n_groups, R->ext_bytes, R->lig_bytes};
-    return MIPGEN_OK;
+    return finish_session(h, KIND_CONSENSUS, reads, unique_tags, totals, sample_totals, row_pairs, sizes);
 }
 
 int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t* tag, int32_t* family, int64_t* ext_off, char* ext_seq, char* ext_qual, int64_t* lig_off,

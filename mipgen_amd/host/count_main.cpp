@@ -288,16 +288,27 @@ int main(int argc, char** argv)
     mipgen_accel* h = nullptr;
     if (svr_tool_handle(&h) != MIPGEN_OK) { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); return 1; }
     auto die = [&]() { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); mipgen_accel_destroy(h); return 1; };
-    if (consensus) {
-        std::vector<const char*> bc;
-        for (const std::string& b : barcodes) bc.push_back(b.c_str());
-        if (mipgen_accel_reads_open_consensus(h, probes.data(), (int32_t)probes.size(), te, tl, mism, by_sample ? bc.data() : nullptr, (int32_t)bc.size(), bc_mism, 0) != MIPGEN_OK)
-            return die();
-    } else if (by_sample) {
-        std::vector<const char*> bc;
-        for (const std::string& b : barcodes) bc.push_back(b.c_str());
-        if (mipgen_accel_reads_open_samples(h, probes.data(), (int32_t)probes.size(), te, tl, mism, bc.data(), (int32_t)bc.size(), bc_mism) != MIPGEN_OK) return die();
-    } else if (mipgen_accel_reads_open(h, probes.data(), (int32_t)probes.size(), te, tl, mism) != MIPGEN_OK) return die();
+    // the three kinds of session (plain, -barcodes, -consensus with or without -barcodes) behind one open / feed / finish each
+    std::vector<const char*> bc;
+    for (const std::string& b : barcodes) bc.push_back(b.c_str());
+    const int32_t n_probes32 = (int32_t)probes.size(), n_bc = (int32_t)bc.size();
+    auto open_session = [&]() {
+        return consensus ? mipgen_accel_reads_open_consensus(h, probes.data(), n_probes32, te, tl, mism, by_sample ? bc.data() : nullptr, n_bc, bc_mism, 0)
+               : by_sample ? mipgen_accel_reads_open_samples(h, probes.data(), n_probes32, te, tl, mism, bc.data(), n_bc, bc_mism)
+                           : mipgen_accel_reads_open(h, probes.data(), n_probes32, te, tl, mism);
+    };
+    auto feed_chunk = [&](const Chunk& c) {
+        return consensus ? mipgen_accel_reads_feed_consensus(h, c.n, c.ext.data(), c.ext_qual.data(), c.ext_off.data(), c.lig.data(), c.lig_qual.data(), c.lig_off.data(),
+                                                             by_sample ? c.idx.data() : nullptr, by_sample ? c.idx_off.data() : nullptr)
+               : by_sample ? mipgen_accel_reads_feed_samples(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data(), c.idx.data(), c.idx_off.data())
+                           : mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data());
+    };
+    auto finish_session = [&](int64_t* reads, int64_t* unique, mipgen_read_totals* tot, mipgen_sample_totals* stot, int64_t* row_pairs, mipgen_consensus_sizes* csz) {
+        return consensus ? mipgen_accel_reads_finish_consensus(h, reads, unique, tot, stot, row_pairs, csz)
+               : by_sample ? mipgen_accel_reads_finish_samples(h, reads, unique, tot, stot, row_pairs)
+                           : mipgen_accel_reads_finish(h, reads, unique, tot);
+    };
+    if (open_session() != MIPGEN_OK) return die();
 
     // two chunks: the reader thread fills one while the device works on the other
     Chunk chunks[2];
@@ -338,10 +349,7 @@ int main(int argc, char** argv)
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return full[k]; }); }
         Chunk& c = chunks[k];
         if (c.failed) { fprintf(stderr, "%s: the FASTQ files changed while they were read\n", PROG); rc = 1; }
-        else if (c.n > 0 && (consensus ? mipgen_accel_reads_feed_consensus(h, c.n, c.ext.data(), c.ext_qual.data(), c.ext_off.data(), c.lig.data(), c.lig_qual.data(), c.lig_off.data(),
-                                                                           by_sample ? c.idx.data() : nullptr, by_sample ? c.idx_off.data() : nullptr)
-                             : by_sample ? mipgen_accel_reads_feed_samples(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data(), c.idx.data(), c.idx_off.data())
-                                       : mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data())) != MIPGEN_OK) {
+        else if (c.n > 0 && feed_chunk(c) != MIPGEN_OK) {
             fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); rc = 1;
         }
         const bool done = rc != 0 || c.last;
@@ -356,9 +364,7 @@ int main(int argc, char** argv)
     mipgen_read_totals tot;
     mipgen_sample_totals stot{0, 0};
     mipgen_consensus_sizes csz{0, 0, 0};
-    if ((consensus ? mipgen_accel_reads_finish_consensus(h, reads.data(), unique.data(), &tot, &stot, row_pairs.data(), &csz)
-         : by_sample ? mipgen_accel_reads_finish_samples(h, reads.data(), unique.data(), &tot, &stot, row_pairs.data())
-                     : mipgen_accel_reads_finish(h, reads.data(), unique.data(), &tot)) != MIPGEN_OK) return die();
+    if (finish_session(reads.data(), unique.data(), &tot, &stot, row_pairs.data(), &csz) != MIPGEN_OK) return die();
     std::vector<int32_t> g_cell((size_t)csz.n_groups), g_family((size_t)csz.n_groups);
     std::vector<uint32_t> g_tag((size_t)csz.n_groups);
     std::vector<int64_t> g_off[2] = {std::vector<int64_t>((size_t)csz.n_groups + 1), std::vector<int64_t>((size_t)csz.n_groups + 1)};

@@ -276,23 +276,6 @@ def test_chunks_do_not_change_the_result(acc, rows, d):
 
 
 # ---- arena, refusals, state ----------------------------------------------------------------------------------------------------------------------------
-def _probes(arms):
-    arr = (capi.Probe * len(arms))()
-    for i, (e, l) in enumerate(arms):
-        arr[i] = capi.Probe(e, l, None, None, 0, 0, -1, 0)
-    return arr
-
-
-def _strings(items):
-    return (capi.C.c_char_p * max(len(items), 1))(*items)
-
-
-def _packed(rs):
-    off = np.zeros(len(rs) + 1, dtype=np.int64)
-    np.cumsum([len(r) for r in rs], out=off[1:])
-    return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
-
-
 def test_arena_refusals_state_and_untouched_handle(rows):
     genome = synth.random_genome(12000, 5)
     P = capi.make_params(130, 140, score_method=capi.SCORE_LOGISTIC, arm_pairs=synth.arm_pairs_from_sums([43, 44]))
@@ -312,12 +295,12 @@ def test_arena_refusals_state_and_untouched_handle(rows):
         n_pairs, half = len(ext), len(ext) // 2
         lib, h = a.lib, a.h
         i64p, i32p = capi.C.POINTER(capi.C.c_int64), capi.C.POINTER(capi.C.c_int32)
-        arr, n = _probes(arms), len(arms)
+        arr, n = capi.probe_array(arms), len(arms)
         bcs = [b"ACGTACGT", b"TTGCAAGC"]
-        bc = _strings(bcs)
-        (eb, eo), (lb, lo), (qe, _), (ql, _) = _packed(ext), _packed(lig), _packed(eq), _packed(lq)
+        bc = capi.c_strings(bcs)
+        (eb, eo), (lb, lo), (qe, _), (ql, _) = capi.pack_reads(ext), capi.pack_reads(lig), capi.pack_reads(eq), capi.pack_reads(lq)
         idx = [bcs[k % 2] for k in range(n_pairs)]
-        ib, io = _packed(idx)
+        ib, io = capi.pack_reads(idx)
         open_c, fin_c, fetch = lib.mipgen_accel_reads_open_consensus, lib.mipgen_accel_reads_finish_consensus, lib.mipgen_accel_reads_consensus_fetch
         feed_c = lambda x, y, index=False: lib.mipgen_accel_reads_feed_consensus(
             h, y - x, eb[eo[x]:].ctypes.data, qe[eo[x]:].ctypes.data, eo[x:y + 1].ctypes.data_as(i64p), lb[lo[x]:].ctypes.data, ql[lo[x]:].ctypes.data,
@@ -333,10 +316,10 @@ def test_arena_refusals_state_and_untouched_handle(rows):
         assert open_c(h, None, n, 5, 0, 0, None, 0, 0, 0) == E_INVALID and open_c(h, arr, 0, 5, 0, 0, None, 0, 0, 0) == E_INVALID
         assert open_c(h, arr, n, 9, 8, 0, None, 0, 0, 0) == E_INVALID and open_c(h, arr, n, -1, 3, 0, None, 0, 0, 0) == E_INVALID
         assert open_c(h, arr, n, 5, 0, 3, None, 0, 0, 0) == E_INVALID
-        assert open_c(h, _probes([(b"ACGTACGTACG", b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, None, 0, 0, 0) == E_INVALID and b"12" in lib.mipgen_accel_last_error()
-        assert open_c(h, _probes([(b"ACGTACGTACGTACGTAA", None)]), 1, 5, 0, 0, None, 0, 0, 0) == E_INVALID
-        assert open_c(h, arr, n, 5, 0, 0, bc, 2, 2, 0) == E_INVALID and open_c(h, arr, n, 5, 0, 0, _strings([b"ACGTACGT", b"ACGTACG"]), 2, 0, 0) == E_INVALID
-        assert open_c(h, arr, n, 5, 0, 0, _strings([b"ACGTACGN"]), 1, 0, 0) == E_INVALID and open_c(h, arr, n, 5, 0, 0, _strings([b"ACGT", b"ACGT"]), 2, 0, 0) == E_INVALID
+        assert open_c(h, capi.probe_array([(b"ACGTACGTACG", b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, None, 0, 0, 0) == E_INVALID and b"12" in lib.mipgen_accel_last_error()
+        assert open_c(h, capi.probe_array([(b"ACGTACGTACGTACGTAA", None)]), 1, 5, 0, 0, None, 0, 0, 0) == E_INVALID
+        assert open_c(h, arr, n, 5, 0, 0, bc, 2, 2, 0) == E_INVALID and open_c(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGT", b"ACGTACG"]), 2, 0, 0) == E_INVALID
+        assert open_c(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGN"]), 1, 0, 0) == E_INVALID and open_c(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGT", b"ACGT"]), 2, 0, 0) == E_INVALID
         assert open_c(h, arr, n, 0, 0, 0, None, 0, 0, 0) == E_INVALID and b"no molecules" in lib.mipgen_accel_last_error()
         assert open_c(h, arr, n, 5, 0, 0, None, 0, 0, -1) == E_INVALID and b"arena_bytes" in lib.mipgen_accel_last_error()
         assert open_c(h, arr, n, 5, 0, 0, bc, 0, 0, 0) == E_INVALID and open_c(h, arr, n, 5, 0, 0, None, 2, 0, 0) == E_INVALID; unchanged()
@@ -406,9 +389,9 @@ def test_destroy_with_a_consensus_session_open_and_with_results_held(rows):
     ext, lig, eq, lq = families(rows, rng, [3, 70, WG + 5], 5, 0, lengths=(80,), low=False)
     a = _accel()
     a.consensus_reads(arms_of(rows), ext, lig, eq, lq)                                               # results held ...
-    arr = _probes(arms_of(rows))
+    arr = capi.probe_array(arms_of(rows))
     assert a.lib.mipgen_accel_reads_open_consensus(a.h, arr, len(rows), 5, 0, 0, None, 0, 0, 0) == 0  # ... dropped, and a session open with a chunk retained
-    (eb, eo), (lb, lo), (qe, _), (ql, _) = _packed(ext), _packed(lig), _packed(eq), _packed(lq)
+    (eb, eo), (lb, lo), (qe, _), (ql, _) = capi.pack_reads(ext), capi.pack_reads(lig), capi.pack_reads(eq), capi.pack_reads(lq)
     i64p = capi.C.POINTER(capi.C.c_int64)
     assert a.lib.mipgen_accel_reads_feed_consensus(a.h, len(ext), eb.ctypes.data, qe.ctypes.data, eo.ctypes.data_as(i64p), lb.ctypes.data, ql.ctypes.data, lo.ctypes.data_as(i64p),
                                                    None, None) == 0

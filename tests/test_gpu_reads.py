@@ -311,6 +311,52 @@ def test_chunks_and_key_buffer_do_not_change_the_result(acc):
         assert np.array_equal(got[0], first[0]) and np.array_equal(got[1], first[1]) and got[2] == first[2] and np.array_equal(got[3], first[3]), (chunks, key_buffer)
 
 
+def test_timing_does_not_change_the_result():
+    """Each kind of session with the HIP-event timing off and on: every output is the same, and mipgen_accel_last_kernel_ms 7..10 hold what each
+    kind leaves there.  The plain session in 3 chunks with 1,024 keys sorts or grows its key buffer between calls (a call of about 700 pairs is one k_read_assign
+    launch, or two where the buffer has between 512 and 700 keys free).  "plain, one call": all pairs (> 1,800) in one feed call against a buffer of 256 keys - a launch takes no more pairs
+    than the buffer has free keys, 256 at first and at most twice as many after each growth, so that one call makes several timed launches."""
+    rows = table_rows("svr_small", "all_mips", limit=40)
+    arms = arms_of(rows)
+    rng = np.random.default_rng(61)
+    ext, lig = _mixed_reads(rows, rng, 5, 0, 100)
+    assert 1800 < len(ext) < 2600
+    barcodes = [b"ACGTACGT", b"TTGCAAGC", b"GGATCCTA", b"CATGTGAC"]
+    idx = [barcodes[int(k)] for k in rng.integers(0, 4, len(ext))]
+    eq, lq = [bytes(rng.integers(35, 74, len(r), dtype=np.uint8)) for r in ext], [bytes(rng.integers(35, 74, len(r), dtype=np.uint8)) for r in lig]
+    kinds = {
+        "plain": lambda a: a.count_reads(arms, ext, lig, (5, 0), chunks=3, key_buffer=1024, want_assignment=True),
+        "plain, one call": lambda a: a.count_reads(arms, ext, lig, (5, 0), chunks=1, key_buffer=256, want_assignment=True),
+        "samples": lambda a: a.count_reads_samples(arms, ext, lig, idx, barcodes, tag_sizes=(5, 0), chunks=2, want_assignment=True),
+        "consensus": lambda a: a.consensus_reads(arms, ext, lig, eq, lq, idx, barcodes, tag_sizes=(5, 0), chunks=2, want_assignment=True),
+    }
+
+    def same(x, y):
+        return np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y
+
+    a = _accel()                                                                             # (a fresh handle: 7..10 start at -1.0)
+    try:
+        for kind, run in kinds.items():
+            plain = kind.startswith("plain")
+            a.set_timing(False)
+            off = run(a)
+            ms_off = [a.last_kernel_ms(k) for k in (7, 8, 9, 10)]
+            a.set_timing(True)
+            on = run(a)
+            ms_on = [a.last_kernel_ms(k) for k in (7, 8, 9, 10)]
+            print(kind, ms_off, ms_on)
+            assert len(off) == len(on) and all(same(x, y) for x, y in zip(off, on)), kind
+            assert off[2]["assigned"] > 1000
+            # timing off: every open zeroes 7, a samples open zeroes 8 and another sets it to -1.0, a consensus finish sets 9 and 10 to -1.0
+            assert ms_off == [0.0, -1.0 if plain else 0.0, -1.0, -1.0], kind
+            assert ms_on[0] > 0.0, kind
+            assert ms_on[1] == -1.0 if plain else ms_on[1] > 0.0, kind
+            assert (ms_on[2] > 0.0 and ms_on[3] > 0.0) if kind == "consensus" else ms_on[2:] == [-1.0, -1.0], kind
+    finally:
+        a.set_timing(False)
+        a.close()
+
+
 def test_handle_state_is_untouched_and_refusals(acc):
     """A dense result of the handle downloads unchanged after a session and after every refused call; refusals carry their codes."""
     genome = synth.random_genome(12000, 5)

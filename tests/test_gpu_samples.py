@@ -207,17 +207,6 @@ def test_chunks_and_key_buffer_do_not_change_the_result(acc):
         assert all(np.array_equal(g, f) for g, f in zip(got[:2] + got[3:], first[:2] + first[3:])) and got[2] == first[2], (chunks, key_buffer)
 
 
-def _probes(arms):
-    arr = (capi.Probe * len(arms))()
-    for i, (e, l) in enumerate(arms):
-        arr[i] = capi.Probe(e, l, None, None, 0, 0, -1, 0)
-    return arr
-
-
-def _strings(items):
-    return (capi.C.c_char_p * max(len(items), 1))(*items)
-
-
 def test_refusals_state_and_untouched_handle():
     """Every refusal of open_samples with its code, feed / finish of the wrong kind (the session then completes correctly), and the handle's dense
     results unchanged after each refused call and after a session."""
@@ -242,7 +231,7 @@ def test_refusals_state_and_untouched_handle():
         unchanged()
         lib, h = a.lib, a.h
         i64p, i32p = capi.C.POINTER(capi.C.c_int64), capi.C.POINTER(capi.C.c_int32)
-        arr, bc = _probes(arms), _strings(barcodes)
+        arr, bc = capi.probe_array(arms), capi.c_strings(barcodes)
         n, ns = len(arms), len(barcodes)
         open_s = lib.mipgen_accel_reads_open_samples
         one = np.zeros(2, dtype=np.int64)
@@ -257,34 +246,29 @@ def test_refusals_state_and_untouched_handle():
         assert open_s(h, arr, n, 9, 8, 0, bc, ns, 0) == E_INVALID
         assert open_s(h, arr, n, -1, 0, 0, bc, ns, 0) == E_INVALID
         assert open_s(h, arr, n, 5, 0, 3, bc, ns, 0) == E_INVALID
-        assert open_s(h, _probes([(b"ACGTACGTACG", b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID and b"12" in lib.mipgen_accel_last_error()
-        assert open_s(h, _probes([(b"", b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID
-        assert open_s(h, _probes([(b"ACGTACGTACGTACGTAA", None)]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID
-        assert open_s(h, _probes([(b"ACGT" * 17, b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID; unchanged()
+        assert open_s(h, capi.probe_array([(b"ACGTACGTACG", b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID and b"12" in lib.mipgen_accel_last_error()
+        assert open_s(h, capi.probe_array([(b"", b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID
+        assert open_s(h, capi.probe_array([(b"ACGTACGTACGTACGTAA", None)]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID
+        assert open_s(h, capi.probe_array([(b"ACGT" * 17, b"ACGTACGTACGTACGTAA")]), 1, 5, 0, 0, bc, ns, 0) == E_INVALID; unchanged()
         # and what the barcodes add
         assert open_s(h, arr, n, 5, 0, 0, None, ns, 0) == E_INVALID
         assert open_s(h, arr, n, 5, 0, 0, bc, 0, 0) == E_INVALID
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b"ACGTACGT", None]), 2, 0) == E_INVALID
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b"ACGTACGT", b"ACGTACG"]), 2, 0) == E_INVALID and b"unequal length" in lib.mipgen_accel_last_error()
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b""]), 1, 0) == E_INVALID
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b"ACGTACGN"]), 1, 0) == E_INVALID and b"A C G T" in lib.mipgen_accel_last_error()
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b"ACGTACGt"]), 1, 0) == E_INVALID
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b"ACGTACGT", b"TTTTACGT", b"ACGTACGT"]), 3, 0) == E_INVALID and b"twice" in lib.mipgen_accel_last_error()
-        assert open_s(h, arr, n, 5, 0, 0, _strings([b"ACGT" * 8 + b"A"]), 1, 0) == E_INVALID
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGT", None]), 2, 0) == E_INVALID
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGT", b"ACGTACG"]), 2, 0) == E_INVALID and b"unequal length" in lib.mipgen_accel_last_error()
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b""]), 1, 0) == E_INVALID
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGN"]), 1, 0) == E_INVALID and b"A C G T" in lib.mipgen_accel_last_error()
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGt"]), 1, 0) == E_INVALID
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGTACGT", b"TTTTACGT", b"ACGTACGT"]), 3, 0) == E_INVALID and b"twice" in lib.mipgen_accel_last_error()
+        assert open_s(h, arr, n, 5, 0, 0, capi.c_strings([b"ACGT" * 8 + b"A"]), 1, 0) == E_INVALID
         assert open_s(h, arr, n, 5, 0, 0, bc, ns, 2) == E_INVALID
         assert open_s(h, arr, n, 5, 0, 0, bc, ns, -1) == E_INVALID; unchanged()
         # (n_samples + 1) * n > 2^32: every barcode of 8 bases and 65,536 probes
         every = [bytes(BASES[[(k >> (2 * j)) & 3 for j in range(8)]]) for k in range(65536)]
-        many = _probes([arms[0]] * 65536)
-        assert open_s(h, many, 65536, 5, 0, 0, _strings(every), 65536, 0) == E_INVALID and b"2^32" in lib.mipgen_accel_last_error(); unchanged()
+        many = capi.probe_array([arms[0]] * 65536)
+        assert open_s(h, many, 65536, 5, 0, 0, capi.c_strings(every), 65536, 0) == E_INVALID and b"2^32" in lib.mipgen_accel_last_error(); unchanged()
 
         # the wrong kind: refused, the session left as it was, and it completes correctly
-        def packed(rs):
-            off = np.zeros(len(rs) + 1, dtype=np.int64)
-            np.cumsum([len(r) for r in rs], out=off[1:])
-            return np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8), off
-
-        (eb, eo), (lb, lo), (ib, io) = packed(ext), packed(lig), packed(idx)
+        (eb, eo), (lb, lo), (ib, io) = capi.pack_reads(ext), capi.pack_reads(lig), capi.pack_reads(idx)
         half = len(ext) // 2
         feed_s = lambda x, y: lib.mipgen_accel_reads_feed_samples(h, y - x, eb[eo[x]:].ctypes.data, eo[x:y + 1].ctypes.data_as(i64p), lb[lo[x]:].ctypes.data,
                                                                   lo[x:y + 1].ctypes.data_as(i64p), ib[io[x]:].ctypes.data, io[x:y + 1].ctypes.data_as(i64p))
@@ -330,8 +314,8 @@ def test_refusals_state_and_untouched_handle():
 
 def test_destroy_with_a_samples_session_open():
     a = _accel()
-    arr = _probes([(b"ACGTACGTACGTACGTAA", b"ACGTACGTACGTACGTAA")])
-    assert a.lib.mipgen_accel_reads_open_samples(a.h, arr, 1, 5, 0, 0, _strings([b"ACGTAC", b"TTTTTT"]), 2, 1) == 0
+    arr = capi.probe_array([(b"ACGTACGTACGTACGTAA", b"ACGTACGTACGTACGTAA")])
+    assert a.lib.mipgen_accel_reads_open_samples(a.h, arr, 1, 5, 0, 0, capi.c_strings([b"ACGTAC", b"TTTTTT"]), 2, 1) == 0
     off = np.array([0, 30], dtype=np.int64)
     ioff = np.array([0, 6], dtype=np.int64)
     i64p = capi.C.POINTER(capi.C.c_int64)
