@@ -404,6 +404,24 @@ int mipgen_accel_reads_finish_consensus(mipgen_accel* h, int64_t* reads, int64_t
 int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t* tag, int32_t* family, int64_t* ext_off, char* ext_seq, char* ext_qual, int64_t* lig_off,
                                        char* lig_seq, char* lig_qual);
 
+/* ---- allele counts per captured base from the consensus reads (new entry point only: the ABI number does not change) ----
+ * The pileup model.  The call reads the consensus reads the handle holds since the last finish_consensus and nothing else.  Probe p has a molecule
+ * length mol_len[p] >= 1: the bytes of M = ext arm + scan target + lig arm.  Every read of a probe starts at the same template base, so position t of the extension
+ * consensus of any molecule (group) of p is base t of M, and position j of its ligation consensus is the complement of base mol_len[p] - 1 - j; consensus positions
+ * at or beyond mol_len[p] (a read that ran through into the backbone) are ignored.  An observation is usable if its base is one of A C G T (the ligation base after
+ * A<->T, C<->G) and its quality byte - 33 is >= min_quality (the consensus writes 2..40).  One vote per molecule and position: no usable observation counts nothing,
+ * one counts its base, two of the same base count it once, two of different bases count `discordant` and no base.  Groups of fewer than min_family pairs are
+ * skipped.  counts[pos_off[p] + t][5] (int32: A, C, G, T, discordant; the bases in the orientation of M; pos_off = the exclusive sum of mol_len) for the groups
+ * of ONE row (the sample row; 0 without barcodes; the last row is `undetermined`); sum(mol_len) * 5 entries, may be NULL.  totals (may be NULL): groups = the groups
+ * of the row, used = those of at least min_family pairs, bases = the sum of columns A..T, discordant = the sum of the fifth.
+ * MIPGEN_E_STATE: the handle holds no consensus reads.  MIPGEN_E_INVALID: NULL mol_len, n different from the session's, a mol_len < 1, row outside [0, rows),
+ * min_family < 1, min_quality outside 0..40, more than 2^31 - 1 rounds of 64 positions.  MIPGEN_E_NOMEM: the count buffer (20 bytes per position) and the
+ * temporaries against free device memory.  Every check comes before any allocation or launch.  The consensus reads, the resident batch, its windows and results
+ * and the model are left as they were; the call may be repeated, for any row in any order.  A handle with zero groups gives zeros. */
+typedef struct mipgen_pileup_totals { int64_t groups, used, bases, discordant; } mipgen_pileup_totals;
+int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, int32_t* counts,
+                                        mipgen_pileup_totals* totals);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -616,7 +634,7 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * (>= 256 SVR candidates); 7 = k_read_assign summed over the feed calls since the last mipgen_accel_reads_open (timing enabled);
  * 8 = k_sample_assign summed over the feed calls since the last mipgen_accel_reads_open_samples (timing enabled);
  * 9 = the two k_consensus_vote kernels of the last mipgen_accel_reads_finish_consensus, 10 = its sort of (key, pair id) and the run boundaries
- * (timing enabled). */
+ * (timing enabled); 11 = the pileup kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -83,6 +83,10 @@ class ConsensusSizes(C.Structure):   # mipgen_consensus_sizes
     _fields_ = [(n, C.c_int64) for n in ("n_groups", "ext_bytes", "lig_bytes")]
 
 
+class PileupTotals(C.Structure):    # mipgen_pileup_totals
+    _fields_ = [(n, C.c_int64) for n in ("groups", "used", "bases", "discordant")]
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -369,8 +373,9 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_finish_consensus.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals), C.POINTER(SampleTotals), i64p_, C.POINTER(ConsensusSizes)]
     lib.mipgen_accel_reads_consensus_fetch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), i64p_, C.c_void_p, C.c_void_p, i64p_, C.c_void_p,
                                                        C.c_void_p]
+    lib.mipgen_accel_reads_consensus_pileup.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(PileupTotals)]
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
-                 "feed_consensus", "finish_consensus", "consensus_fetch"):
+                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -450,6 +455,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_last_assignment",
     "mipgen_accel_reads_open_samples", "mipgen_accel_reads_feed_samples", "mipgen_accel_reads_finish_samples", "mipgen_accel_reads_last_samples",
     "mipgen_accel_reads_open_consensus", "mipgen_accel_reads_feed_consensus", "mipgen_accel_reads_finish_consensus", "mipgen_accel_reads_consensus_fetch",
+    "mipgen_accel_reads_consensus_pileup",
 ]
 
 
@@ -962,6 +968,20 @@ class Accel:
         out = self._read_session(arms, ext_reads, lig_reads, (ext_quals, lig_quals), index_reads, barcodes, barcode_mismatches, tag_sizes, mismatches, swap_reads, chunks,
                                  arena_bytes=arena_bytes, want_assignment=want_assignment)
         return out if want_assignment else out[:5]
+
+    def consensus_pileup(self, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0):
+        """mipgen_accel_reads_consensus_pileup, callable after consensus_reads: allele counts per template position of every probe from the consensus reads the
+        handle holds, for the groups of one row.  mol_len: the bytes of ext arm + scan target + lig arm per probe.  Returns (counts[sum(mol_len)][5] int32 - A, C,
+        G, T, discordant, the bases in the orientation of the molecule; probe p starts at row sum(mol_len[:p]) - and the totals dict: groups, used, bases,
+        discordant)."""
+        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
+        total = int(lens.astype(np.int64).clip(min=0).sum())
+        counts = np.empty((total, 5), dtype=np.int32)
+        tot = PileupTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_reads_consensus_pileup(self.h, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, counts.ctypes.data_as(i32p),
+                                                                 C.byref(tot)))
+        return counts, {f[0]: int(getattr(tot, f[0])) for f in PileupTotals._fields_}
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

@@ -1,6 +1,6 @@
 // accel_reads.hip — read sessions behind the C ABI: reads and unique tags per probe from smMIP read pairs (mipgen_accel_reads_open / _feed / _finish), per sample of
 // a multiplexed lane (4.10: _open_samples / _feed_samples / _finish_samples / _last_samples), with one consensus read pair per molecule (4.11: _open_consensus / _feed_consensus /
-// _finish_consensus / _consensus_fetch).  The three families of entry points name ONE path.  ReadsSession is what every session has plus a KeyList, a SamplesPart and a
+// _finish_consensus / _consensus_fetch), and the allele counts per template position read off those (4.12: _consensus_pileup).  The three families of entry points name ONE path.  ReadsSession is what every session has plus a KeyList, a SamplesPart and a
 // ConsensusPart; its flags `samples` and `consensus` say which parts are set up, and session_for() alone matches a call to the open session.  open_impl: check_open
 // (probe table, then barcodes), build_host_tables, the budget, upload_tables.  feed_impl: eleven stages, the kinds differing in data only - where the bases of the call live and where
 // k_read_assign's keys go.  finish_session: consensus_finish where reads were kept, finish_impl, release.  Errors are HIP_TRY returns; IdleOnExit and FreeOnExit put the
@@ -32,13 +32,27 @@ struct ChunkLayout {
     }
 };
 
+// what mipgen_accel_reads_consensus_pileup needs beside the consensus reads: kept with them between calls - a call per row would otherwise pay the
+// allocation of the count buffer every time - and never read by anything else
+struct PileupScratch {
+    DevBuf<int32_t> mol_len, counts;                         // n; positions x PILEUP_COLUMNS
+    DevBuf<int64_t> pos_off;                                 // n
+    DevBuf<uint32_t> start;                                  // n + 1
+    DevBuf<uint2> units;                                     // the rounds of all probes
+    DevBuf<PileupCounters> ctr;
+    size_t held() const { return mol_len.cap * 4 + counts.cap * 4 + pos_off.cap * 8 + start.cap * 4 + units.cap * 8 + ctr.cap * sizeof(PileupCounters); }
+    void release() { mol_len.release(); counts.release(); pos_off.release(); start.release(); units.release(); ctr.release(); }
+};
+
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
+    int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
+    PileupScratch pile;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); }
 };
 static const int64_t READS_KEY_CAP_DEFAULT = (int64_t)1 << 26, READS_KEY_CAP_MAX = (int64_t)1 << 30;
 
@@ -694,6 +708,7 @@ static int finish_session(mipgen_accel* h, int kind, int64_t* reads, int64_t* un
     if (S->consensus) {
         HIP_TRY(hipSetDevice(h->device));
         R = new ConsensusResult;
+        R->n = S->P.n_probes; R->rows = S->rows;
         rc = consensus_finish(h, S, R);
     }
     if (rc == MIPGEN_OK) rc = finish_impl(h, S, reads, unique_tags, totals, sample_totals, row_pairs);
@@ -792,6 +807,75 @@ int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t*
         if (cell) cell[g] = (int32_t)(keys[g] >> 32);
         if (tag) tag[g] = (uint32_t)keys[g];
     }
+    return MIPGEN_OK;
+}
+
+// Allele counts per template position of one row from the consensus reads the handle holds.  Reads R's groups and reads; writes R->pile only.
+int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, int32_t* counts,
+                                        mipgen_pileup_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    ConsensusResult* R = h->consensus;
+    if (!mol_len) return fail(MIPGEN_E_INVALID, "bad arguments: no molecule lengths");
+    if ((int64_t)n != R->n) return fail(MIPGEN_E_INVALID, "%d molecule lengths: the session that left the consensus reads had %lld probes", n, (long long)R->n);
+    int64_t n_pos = 0, n_units = 0;                                          // template positions; rounds of 64 of them
+    for (int32_t p = 0; p < n; p++) {
+        if (mol_len[p] < 1) return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: a length is 1 or more", mol_len[p], p);
+        n_pos += mol_len[p]; n_units += ((int64_t)mol_len[p] + 63) / 64;
+    }
+    if (row < 0 || (int64_t)row >= R->rows) return fail(MIPGEN_E_INVALID, "row %d: the session had %lld row%s", row, (long long)R->rows, R->rows == 1 ? "" : "s");
+    if (min_family < 1) return fail(MIPGEN_E_INVALID, "min_family %d: 1 or more", min_family);
+    if (min_quality < 0 || min_quality > 40) return fail(MIPGEN_E_INVALID, "min_quality %d: 0 to 40 (the consensus writes 2 to 40)", min_quality);
+    if (n_units > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld template positions: more than 2^31 - 1 rounds of 64", (long long)n_pos);
+    HIP_TRY(hipSetDevice(h->device));
+    h->pileup_ms = -1.0;
+    if (R->n_groups == 0) {                                                  // (no buffer exists: nothing to read, nothing to launch)
+        if (counts) memset(counts, 0, (size_t)n_pos * PILEUP_COLUMNS * sizeof(int32_t));
+        if (totals) *totals = {0, 0, 0, 0};
+        return MIPGEN_OK;
+    }
+    PileupScratch& W = R->pile;
+    auto padded = [](size_t count, size_t size) { return (count + count / 8 + 64) * size; };      // (what DevBuf::reserve asks for at most)
+    const size_t need = padded((size_t)n_pos * PILEUP_COLUMNS, 4) + padded((size_t)n, 4) + padded((size_t)n, 8) + padded((size_t)n + 1, 4) + padded((size_t)n_units, 8) +
+                        padded(1, sizeof(PileupCounters));
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (need > W.held() + free_b)
+        return fail(MIPGEN_E_NOMEM, "pileup: %lld template positions need %zu MiB of device memory, %zu MiB are free", (long long)n_pos, need >> 20, (W.held() + free_b) >> 20);
+    if (W.counts.reserve((size_t)n_pos * PILEUP_COLUMNS) || W.mol_len.reserve((size_t)n) || W.pos_off.reserve((size_t)n) || W.start.reserve((size_t)n + 1) ||
+        W.units.reserve((size_t)n_units) || W.ctr.reserve(1))
+        return MIPGEN_E_NOMEM;
+    std::vector<int64_t> pos_off((size_t)n);
+    for (int64_t p = 0, at = 0; p < n; at += mol_len[p], p++) pos_off[(size_t)p] = at;
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemcpyAsync(W.mol_len.p, mol_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.pos_off.p, pos_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(PileupCounters), st));
+    SpanTimer pile_time{h->timing, st};
+    pile_time.mark();
+    HIP_TRY(mipgen_launch_pileup_prepare(st, R->keys.p, R->family.p, R->n_groups, (uint32_t)((int64_t)row * R->n), n, W.mol_len.p, min_family, n_units, W.start.p, W.units.p,
+                                         W.ctr.p));
+    pile_time.mark();
+    PileupCounters pc;
+    uint32_t first = 0, last = 0;                                            // the row's groups: [first, last)
+    HIP_TRY(hipMemcpyAsync(&pc, W.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&first, W.start.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last, W.start.p + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_small = (int64_t)pc.n_small, n_big = (int64_t)pc.n_big;
+    if (n_small + n_big != n_units) return fail(MIPGEN_E_STATE, "pileup: %lld + %lld rounds listed of %lld", (long long)n_small, (long long)n_big, (long long)n_units);
+    pile_time.mark();
+    HIP_TRY(mipgen_launch_pileup(st, W.units.p, n_units, n_small, n_big, W.mol_len.p, W.pos_off.p, W.start.p, R->family.p, R->ext_off.p, R->lig_off.p, R->ext_seq.p, R->ext_qual.p,
+                                 R->lig_seq.p, R->lig_qual.p, min_family, min_quality, n_pos, W.counts.p, W.ctr.p));
+    pile_time.mark();
+    HIP_TRY(hipMemcpyAsync(&pc, W.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, (size_t)n_pos * PILEUP_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    double ms = 0.0;
+    if (pile_time.add_to(&ms)) h->pileup_ms = ms;
+    if (totals) *totals = {(int64_t)last - (int64_t)first, (int64_t)pc.used, (int64_t)pc.bases, (int64_t)pc.discordant};
     return MIPGEN_OK;
 }
 

@@ -134,4 +134,10 @@ hipError_t mipgen_launch_consensus_len(hipStream_t, int te, int tl, int64_t n_gr
 hipError_t mipgen_launch_consensus_vote(hipStream_t, int te, int tl, int64_t n_groups, const uint32_t* order, int64_t n_small, int64_t n_big, const uint32_t* group_start,
                                         const int32_t* family, const uint32_t* ids, const ConsensusPair* recs, const int64_t* ext_off, const int64_t* lig_off, uint8_t* ext_seq,
                                         uint8_t* ext_qual, uint8_t* lig_seq, uint8_t* lig_qual);
+// kernels_pileup.hip: the cell boundaries of one row, its (cell, round) units and its used groups; then the counts and their sums
+hipError_t mipgen_launch_pileup_prepare(hipStream_t, const uint64_t* keys, const int32_t* family, int64_t n_groups, uint32_t cell0, int32_t n, const int32_t* mol_len,
+                                        int min_family, int64_t n_units, uint32_t* start, uint2* units, PileupCounters* ctr);
+hipError_t mipgen_launch_pileup(hipStream_t, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const int32_t* mol_len, const int64_t* pos_off,
+                                const uint32_t* start, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual,
+                                const uint8_t* lig_seq, const uint8_t* lig_qual, int min_family, int min_quality, int64_t n_pos, int32_t* counts, PileupCounters* ctr);
 }

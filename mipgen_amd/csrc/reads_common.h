@@ -103,3 +103,12 @@ __device__ static inline bool pack_tag(const uint8_t* __restrict__ b, int64_t fr
 struct alignas(16) ConsensusPair { const uint8_t* ext; const uint8_t* lig; int64_t qdelta; int32_t ext_len, lig_len; };      // 32 bytes
 
 struct ConsensusCounters { unsigned long long members, groups, n_small, n_big; };
+
+// ---- allele counts per template position from the consensus reads ----
+#define PILEUP_WG_CELL 256           // a (row, probe) cell of more molecules than this takes a 256-thread workgroup per round of 64 positions (its four wavefronts stride
+                                     // over the molecules); up to it one wavefront.  The trade is CONSENSUS_WG_FAMILY's: two barriers and an LDS combine per round.
+#define PILEUP_COLUMNS 5             // A, C, G, T, discordant
+
+// n_small / n_big: the (cell, round) units listed for the one-wavefront / the workgroup kernel; used: the row's groups of at least min_family pairs; bases / discordant:
+// the sums of columns 0..3 / of column 4
+struct PileupCounters { unsigned long long n_small, n_big, used, bases, discordant; };

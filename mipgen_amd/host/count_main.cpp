@@ -31,10 +31,20 @@
 //                           -barcodes | undetermined> <tab> mip_key <tab> tag <tab> family"; the ordinal is the group's place among ALL groups, from 0
 //   -min_family k           only the groups of at least k pairs are written (default 1)
 //   stderr     a last line: "mipgen_count: consensus groups G written W members M" (M: the pairs of all G groups)
+// Allele counts per captured base (without -pileup every byte written is what it was):
+//   -pileup FILE            per (sample, probe, template position) the molecules that show A, C, G, T there and those whose two reads disagree, from the consensus
+//                           reads (a consensus session is opened whether or not -consensus is given); needs tag bases.  Header
+//                           ">sample <tab> mip_key <tab> chr <tab> position <tab> strand <tab> part <tab> ref <tab> A <tab> C <tab> G <tab> T <tab> discordant"; one line
+//                           per position with a non-zero counter, in sample, table and position order; part = ext | target | lig.  Everything is in genome PLUS
+//                           orientation: on a '-' probe position = ext_probe_stop - t, ref is the complement of the molecule's base and A/T, C/G swap columns
+//   -pileup_min_family k    only molecules of at least k pairs count (default 1); -pileup_min_quality q: only consensus bases of quality >= q, 0..40 (default 0)
+//   stderr     a last line: "mipgen_count: pileup molecules U positions P bases B nonref R discordant D" (U: the molecules counted; P: lines written)
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
+#include <cctype>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 
@@ -57,7 +67,8 @@ static int usage(const std::string& msg)
             "-index_reads i1.fq[,i2.fq] : the index reads of the pairs; -index_length j1[,j2] : bases taken from each (default: the barcode length)\n"
             "-barcode_mismatches n : substitutions allowed between index and barcode, 0 or 1 (default 0)\n"
             "-samples file : sample, barcode, pairs, assigned, unique_tags, probes_seen per sample\n"
-            "-consensus prefix : prefix.ext.fq and prefix.lig.fq, one consensus read pair per (sample, probe, tag) group; -min_family k : groups of at least k pairs (default 1)\n");
+            "-consensus prefix : prefix.ext.fq and prefix.lig.fq, one consensus read pair per (sample, probe, tag) group; -min_family k : groups of at least k pairs (default 1)\n"
+            "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n");
     return 1;
 }
 
@@ -157,9 +168,9 @@ static bool parse_int_list(const std::string& v, std::vector<long>& out)
 int main(int argc, char** argv)
 {
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
-    long min_family = 1;
-    bool swap = false, bc_mism_given = false, min_family_given = false;
-    std::string consensus_prefix;
+    long min_family = 1, pile_family = 1, pile_quality = 0;
+    bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
+    std::string consensus_prefix, pileup_path;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
@@ -190,6 +201,9 @@ int main(int argc, char** argv)
         else if (a == "-index_length") index_len_arg = v;
         else if (a == "-consensus") { if (v.empty()) return usage("-consensus takes a prefix"); consensus_prefix = v; }
         else if (a == "-min_family") { if (!svr_parse_int(v.c_str(), &min_family) || min_family < 1) return usage("-min_family must be 1 or more"); min_family_given = true; }
+        else if (a == "-pileup") { if (v.empty()) return usage("-pileup takes a file"); pileup_path = v; }
+        else if (a == "-pileup_min_family") { if (!svr_parse_int(v.c_str(), &pile_family) || pile_family < 1 || pile_family > INT32_MAX) return usage("-pileup_min_family must be 1 or more"); pile_option_given = true; }
+        else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
         else if (a == "-barcode_mismatches") {
             if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-barcode_mismatches must be 0 or 1");
             bc_mism = (int)iv; bc_mism_given = true;
@@ -208,6 +222,9 @@ int main(int argc, char** argv)
     const bool consensus = !consensus_prefix.empty();
     if (min_family_given && !consensus) return usage("-min_family needs -consensus prefix");
     if (consensus && te + tl == 0) return usage("-consensus needs tag bases: with -tag_sizes 0,0 there are no molecules to collapse");
+    const bool pileup = !pileup_path.empty(), keep_reads = consensus || pileup;      // (-pileup reads the consensus reads: its session keeps the reads too)
+    if (pile_option_given && !pileup) return usage("-pileup_min_family and -pileup_min_quality need -pileup file");
+    if (pileup && te + tl == 0) return usage("-pileup needs tag bases: with -tag_sizes 0,0 there are no molecules to count");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
     if (by_sample) {
@@ -250,6 +267,17 @@ int main(int argc, char** argv)
         }
     if (probes.empty()) { fprintf(stderr, "%s: the tables hold no probe\n", PROG); return 1; }
     if (probes.size() > (size_t)INT32_MAX) { fprintf(stderr, "%s: too many probes\n", PROG); return 1; }
+    // -pileup: the length of every probe's molecule and where it lies on the genome
+    std::vector<int32_t> mol_len;
+    std::vector<RowCoords> coords;
+    if (pileup)
+        for (const auto* r : rows) {
+            RowCoords c;
+            const char* what = nullptr;
+            if (!row_coords(*r, &c, &what)) { fprintf(stderr, "%s: -pileup: probe %s: %s\n", PROG, (*r)[COL_KEY].c_str(), what); return 1; }
+            coords.push_back(c);
+            mol_len.push_back((int32_t)((*r)[COL_EXT_SEQ].size() + (*r)[COL_INS_SEQ].size() + (*r)[COL_LIG_SEQ].size()));
+        }
     if (shortest < 12) { fprintf(stderr, "%s: the shortest arm of the tables has %zu bases: a seed of fewer than 12 bases is refused\n", PROG, shortest); return 1; }
     Fastq fe, fl;
     fe.path = swap ? reads_b : reads_a; fl.path = swap ? reads_a : reads_b;
@@ -283,6 +311,8 @@ int main(int argc, char** argv)
     if (consensus)
         for (int k = 0; k < 2; k++)
             if (!(cons_out[k] = fopen(cons_path[k].c_str(), "w"))) return usage("-consensus " + consensus_prefix + ": can't write " + cons_path[k]);
+    FILE* pile_out = nullptr;
+    if (pileup && !(pile_out = fopen(pileup_path.c_str(), "w"))) return usage("-pileup " + pileup_path + ": can't write " + pileup_path);
 
     // ---- the device ----
     mipgen_accel* h = nullptr;
@@ -293,18 +323,18 @@ int main(int argc, char** argv)
     for (const std::string& b : barcodes) bc.push_back(b.c_str());
     const int32_t n_probes32 = (int32_t)probes.size(), n_bc = (int32_t)bc.size();
     auto open_session = [&]() {
-        return consensus ? mipgen_accel_reads_open_consensus(h, probes.data(), n_probes32, te, tl, mism, by_sample ? bc.data() : nullptr, n_bc, bc_mism, 0)
+        return keep_reads ? mipgen_accel_reads_open_consensus(h, probes.data(), n_probes32, te, tl, mism, by_sample ? bc.data() : nullptr, n_bc, bc_mism, 0)
                : by_sample ? mipgen_accel_reads_open_samples(h, probes.data(), n_probes32, te, tl, mism, bc.data(), n_bc, bc_mism)
                            : mipgen_accel_reads_open(h, probes.data(), n_probes32, te, tl, mism);
     };
     auto feed_chunk = [&](const Chunk& c) {
-        return consensus ? mipgen_accel_reads_feed_consensus(h, c.n, c.ext.data(), c.ext_qual.data(), c.ext_off.data(), c.lig.data(), c.lig_qual.data(), c.lig_off.data(),
+        return keep_reads ? mipgen_accel_reads_feed_consensus(h, c.n, c.ext.data(), c.ext_qual.data(), c.ext_off.data(), c.lig.data(), c.lig_qual.data(), c.lig_off.data(),
                                                              by_sample ? c.idx.data() : nullptr, by_sample ? c.idx_off.data() : nullptr)
                : by_sample ? mipgen_accel_reads_feed_samples(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data(), c.idx.data(), c.idx_off.data())
                            : mipgen_accel_reads_feed(h, c.n, c.ext.data(), c.ext_off.data(), c.lig.data(), c.lig_off.data());
     };
     auto finish_session = [&](int64_t* reads, int64_t* unique, mipgen_read_totals* tot, mipgen_sample_totals* stot, int64_t* row_pairs, mipgen_consensus_sizes* csz) {
-        return consensus ? mipgen_accel_reads_finish_consensus(h, reads, unique, tot, stot, row_pairs, csz)
+        return keep_reads ? mipgen_accel_reads_finish_consensus(h, reads, unique, tot, stot, row_pairs, csz)
                : by_sample ? mipgen_accel_reads_finish_samples(h, reads, unique, tot, stot, row_pairs)
                            : mipgen_accel_reads_finish(h, reads, unique, tot);
     };
@@ -322,7 +352,7 @@ int main(int argc, char** argv)
             c.ext.clear(); c.lig.clear(); c.idx.clear(); c.ext_qual.clear(); c.lig_qual.clear(); c.ext_off.assign(1, 0); c.lig_off.assign(1, 0); c.idx_off.assign(1, 0); c.n = 0; c.last = false;
             std::string part[2];
             while (c.n < CHUNK_PAIRS) {
-                const int a = fe.next(&c.ext, consensus ? &c.ext_qual : nullptr), b = fl.next(&c.lig, consensus ? &c.lig_qual : nullptr);
+                const int a = fe.next(&c.ext, keep_reads ? &c.ext_qual : nullptr), b = fl.next(&c.lig, keep_reads ? &c.lig_qual : nullptr);
                 if (a < 0 || b < 0 || a != b) { c.failed = true; break; }          // (the files changed since they were checked)
                 bool whole = true;
                 for (size_t k = 0; k < index_paths.size() && !c.failed; k++) {
@@ -365,12 +395,61 @@ int main(int argc, char** argv)
     mipgen_sample_totals stot{0, 0};
     mipgen_consensus_sizes csz{0, 0, 0};
     if (finish_session(reads.data(), unique.data(), &tot, &stot, row_pairs.data(), &csz) != MIPGEN_OK) return die();
-    std::vector<int32_t> g_cell((size_t)csz.n_groups), g_family((size_t)csz.n_groups);
-    std::vector<uint32_t> g_tag((size_t)csz.n_groups);
-    std::vector<int64_t> g_off[2] = {std::vector<int64_t>((size_t)csz.n_groups + 1), std::vector<int64_t>((size_t)csz.n_groups + 1)};
-    std::string g_seq[2] = {std::string((size_t)csz.ext_bytes, '\0'), std::string((size_t)csz.lig_bytes, '\0')}, g_qual[2] = {g_seq[0], g_seq[1]};
+    const mipgen_consensus_sizes fsz = consensus ? csz : mipgen_consensus_sizes{0, 0, 0};      // (-pileup alone downloads no consensus read)
+    std::vector<int32_t> g_cell((size_t)fsz.n_groups), g_family((size_t)fsz.n_groups);
+    std::vector<uint32_t> g_tag((size_t)fsz.n_groups);
+    std::vector<int64_t> g_off[2] = {std::vector<int64_t>((size_t)fsz.n_groups + 1), std::vector<int64_t>((size_t)fsz.n_groups + 1)};
+    std::string g_seq[2] = {std::string((size_t)fsz.ext_bytes, '\0'), std::string((size_t)fsz.lig_bytes, '\0')}, g_qual[2] = {g_seq[0], g_seq[1]};
     if (consensus && mipgen_accel_reads_consensus_fetch(h, g_cell.data(), g_tag.data(), g_family.data(), g_off[0].data(), &g_seq[0][0], &g_qual[0][0], g_off[1].data(), &g_seq[1][0],
                                                         &g_qual[1][0]) != MIPGEN_OK) return die();
+    // -pileup: one call per row; a second thread turns the counts of a row into lines while the device counts the next row
+    long long pile_used = 0, pile_lines = 0, pile_bases = 0, pile_nonref = 0, pile_disc = 0;
+    if (pileup) {
+        int64_t n_pos = 0;
+        std::vector<int64_t> pos_off;
+        for (int32_t l : mol_len) { pos_off.push_back(n_pos); n_pos += l; }
+        std::vector<int32_t> table[2] = {std::vector<int32_t>((size_t)n_pos * 5), std::vector<int32_t>(n_rows > 1 ? (size_t)n_pos * 5 : 0)};
+        auto write_row = [&](size_t r, const std::vector<int32_t>& counts) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text;
+            char buf[160];
+            for (size_t i = 0; i < n_probes; i++) {
+                const std::vector<std::string>& f = *rows[i];
+                const RowCoords& c = coords[i];
+                const size_t n_ext = f[COL_EXT_SEQ].size(), n_ins = f[COL_INS_SEQ].size();
+                for (int32_t t = 0; t < mol_len[i]; t++) {
+                    const int32_t* k = &counts[(size_t)(pos_off[i] + t) * 5];
+                    if (!(k[0] | k[1] | k[2] | k[3] | k[4])) continue;
+                    const size_t ut = (size_t)t;
+                    char ref = (char)toupper((unsigned char)(ut < n_ext ? f[COL_EXT_SEQ][ut] : ut < n_ext + n_ins ? f[COL_INS_SEQ][ut - n_ext] : f[COL_LIG_SEQ][ut - n_ext - n_ins]));
+                    int32_t plus[4] = {k[0], k[1], k[2], k[3]};
+                    if (c.minus) {                                                       // the molecule shows the minus strand: complement everything
+                        ref = ref == 'A' ? 'T' : ref == 'C' ? 'G' : ref == 'G' ? 'C' : ref == 'T' ? 'A' : ref;
+                        plus[0] = k[3]; plus[1] = k[2]; plus[2] = k[1]; plus[3] = k[0];
+                    }
+                    for (int b = 0; b < 4; b++) { pile_bases += plus[b]; if ("ACGT"[b] != ref) pile_nonref += plus[b]; }
+                    pile_disc += k[4];
+                    snprintf(buf, sizeof buf, "\t%ld\t%c\t%s\t%c\t%d\t%d\t%d\t%d\t%d\n", c.minus ? c.ext_stop - t : c.ext_start + t, c.minus ? '-' : '+',
+                             ut < n_ext ? "ext" : ut < n_ext + n_ins ? "target" : "lig", ref, plus[0], plus[1], plus[2], plus[3], k[4]);
+                    text.append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf);
+                    pile_lines++;
+                }
+            }
+            fwrite(text.data(), 1, text.size(), pile_out);
+        };
+        fputs(">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
+        std::thread writer;
+        for (size_t r = 0; r < n_rows; r++) {
+            mipgen_pileup_totals pt;
+            const int prc = mipgen_accel_reads_consensus_pileup(h, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality, table[r & 1].data(), &pt);
+            if (writer.joinable()) writer.join();
+            if (prc != MIPGEN_OK) return die();
+            pile_used += pt.used;
+            writer = std::thread(write_row, r, std::cref(table[r & 1]));
+        }
+        if (writer.joinable()) writer.join();
+        if (fclose(pile_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, pileup_path.c_str()); mipgen_accel_destroy(h); return 1; }
+    }
     mipgen_accel_destroy(h);
 
     FILE* out = fopen(out_path.c_str(), "w");
@@ -447,5 +526,6 @@ int main(int argc, char** argv)
     if (by_sample)
         fprintf(stderr, "%s: samples %zu sample_none %lld sample_ambiguous %lld\n", PROG, barcodes.size(), (long long)stot.sample_none, (long long)stot.sample_ambiguous);
     if (consensus) fprintf(stderr, "%s: consensus groups %lld written %lld members %lld\n", PROG, (long long)csz.n_groups, cons_written, cons_members);
+    if (pileup) fprintf(stderr, "%s: pileup molecules %lld positions %lld bases %lld nonref %lld discordant %lld\n", PROG, pile_used, pile_lines, pile_bases, pile_nonref, pile_disc);
     return 0;
 }

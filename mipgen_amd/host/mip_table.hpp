@@ -9,8 +9,8 @@
 #include "mipgen_host.hpp"
 #include "svr_problem.hpp"
 
-enum { COL_KEY = 0, COL_SCORE = 1, COL_CHR = 2, COL_EXT_COPY = 5, COL_EXT_SEQ = 6, COL_LIG_COPY = 9, COL_LIG_SEQ = 10, COL_INS_SEQ = 13, COL_MIP_SEQ = 14,
-       COL_FEAT_START = 15, COL_FEAT_STOP = 16, COL_NAME = 19, N_COLS = 20 };
+enum { COL_KEY = 0, COL_SCORE = 1, COL_CHR = 2, COL_EXT_START = 3, COL_EXT_STOP = 4, COL_EXT_COPY = 5, COL_EXT_SEQ = 6, COL_LIG_START = 7, COL_LIG_STOP = 8, COL_LIG_COPY = 9,
+       COL_LIG_SEQ = 10, COL_INS_SEQ = 13, COL_MIP_SEQ = 14, COL_FEAT_START = 15, COL_FEAT_STOP = 16, COL_STRAND = 17, COL_NAME = 19, N_COLS = 20 };
 
 struct Table {
     std::string path, header;
@@ -76,5 +76,22 @@ static inline bool read_table(const char* PROG, const std::string& path, int fla
         t.feature.push_back(it->second);
         t.rows.push_back(std::move(f));
     }
+    return true;
+}
+
+// Where the captured molecule M = ext_probe_sequence + scan_target_sequence + lig_probe_sequence of a row lies on the genome (1-based, as the table prints its
+// coordinates).  On '+' M runs from ext_probe_start to lig_probe_stop; on '-' it is the reverse complement of lig_probe_start .. ext_probe_stop.  So base t of M
+// is genome position ext_probe_start + t on '+' and ext_probe_stop - t on '-', where it shows the complement of the plus-strand base.
+struct RowCoords { long ext_start, ext_stop, lig_start, lig_stop; bool minus; };
+
+// read_table does not look at these columns (its checks stay what they were); a caller that needs them asks here.  false: *what names the column at fault
+static inline bool row_coords(const std::vector<std::string>& f, RowCoords* c, const char** what)
+{
+    if (!svr_parse_int(f[COL_EXT_START].c_str(), &c->ext_start)) { *what = "ext_probe_start is not an integer"; return false; }
+    if (!svr_parse_int(f[COL_EXT_STOP].c_str(), &c->ext_stop)) { *what = "ext_probe_stop is not an integer"; return false; }
+    if (!svr_parse_int(f[COL_LIG_START].c_str(), &c->lig_start)) { *what = "lig_probe_start is not an integer"; return false; }
+    if (!svr_parse_int(f[COL_LIG_STOP].c_str(), &c->lig_stop)) { *what = "lig_probe_stop is not an integer"; return false; }
+    if (f[COL_STRAND] != "+" && f[COL_STRAND] != "-") { *what = "probe_strand is neither + nor -"; return false; }
+    c->minus = f[COL_STRAND] == "-";
     return true;
 }
