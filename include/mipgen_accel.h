@@ -422,6 +422,28 @@ typedef struct mipgen_pileup_totals { int64_t groups, used, bases, discordant; }
 int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, int32_t* counts,
                                         mipgen_pileup_totals* totals);
 
+/* ---- the pileup with indels (new entry point only: the ABI number does not change) ----
+ * The gapped pileup model.  As the call above, but every consensus read is first PLACED on its template by a banded alignment anchored at its arm,
+ * so that the bases behind an insertion or deletion are counted against the template position they came from.  mol_seq: the template bases of every probe, M_p
+ * upper-cased, mol_len[p] bytes each, concatenated in probe order (sum(mol_len) bytes; any byte other than A C G T matches nothing).  Per side: the extension
+ * consensus against M, the ligation consensus against revcomp(M); score +1 / -1 / 0 (either byte not A C G T), linear gap -2, cells |i - j| <= max_indel, start
+ * fixed at (0, 0), end free on the last row of the read or the last column of the template (largest score, then smallest |j - i|, then larger j); traceback
+ * preferring diagonal, deletion, insertion on the extension side and deletion, insertion, diagonal on the ligation side.  Quality plays no part in the placement.
+ * A diagonal step observes its read base at its template position, a deletion step observes `del` (always usable); per molecule and position the two sides vote as
+ * above with `del` as a fifth class.  Insertions are recorded at the anchor t (between t and t + 1, orientation of M) by length only: a side covers t if its path
+ * consumes t and t + 1; one covering side counts `ins` if its length is > 0, two with equal length > 0 count it once, two with different lengths count
+ * `ins_discordant`.  counts[pos_off[p] + t][8] (int32: A, C, G, T, discordant, del, ins, ins_discordant), sum(mol_len) * 8 entries, may be NULL.  totals (may be
+ * NULL): groups, used as above; bases, discordant, deletions, insertions, ins_discordant = the column sums; gapped_sides = the sides of used groups whose path holds
+ * at least one gap step.
+ * MIPGEN_E_STATE: the handle holds no consensus reads.  MIPGEN_E_INVALID: every case of the call above, NULL mol_seq, max_indel outside 1..15, a mol_len above
+ * MIPGEN_GAPPED_MAX_MOL.  MIPGEN_E_NOMEM: the count buffer (32 bytes per position), the projections (at most 3 mol_len bytes per side of the session) and the
+ * temporaries against free device memory.  Every check comes before any allocation or launch.  mipgen_accel_reads_consensus_pileup and everything else on the
+ * handle are untouched by the call; it may be repeated, for any row in any order.  A handle with zero groups gives zeros. */
+#define MIPGEN_GAPPED_MAX_MOL 2048
+typedef struct mipgen_gapped_totals { int64_t groups, used, bases, discordant, deletions, insertions, ins_discordant, gapped_sides; } mipgen_gapped_totals;
+int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                               int32_t max_indel, int32_t* counts, mipgen_gapped_totals* totals);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -634,7 +656,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * (>= 256 SVR candidates); 7 = k_read_assign summed over the feed calls since the last mipgen_accel_reads_open (timing enabled);
  * 8 = k_sample_assign summed over the feed calls since the last mipgen_accel_reads_open_samples (timing enabled);
  * 9 = the two k_consensus_vote kernels of the last mipgen_accel_reads_finish_consensus, 10 = its sort of (key, pair id) and the run boundaries
- * (timing enabled); 11 = the pileup kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled). */
+ * (timing enabled); 11 = the pileup kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled); 12 = the kernels of the last
+ * mipgen_accel_reads_consensus_pileup_gapped (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -87,6 +87,10 @@ class PileupTotals(C.Structure):    # mipgen_pileup_totals
     _fields_ = [(n, C.c_int64) for n in ("groups", "used", "bases", "discordant")]
 
 
+class GappedTotals(C.Structure):    # mipgen_gapped_totals
+    _fields_ = [(n, C.c_int64) for n in ("groups", "used", "bases", "discordant", "deletions", "insertions", "ins_discordant", "gapped_sides")]
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -374,8 +378,10 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_consensus_fetch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), i64p_, C.c_void_p, C.c_void_p, i64p_, C.c_void_p,
                                                        C.c_void_p]
     lib.mipgen_accel_reads_consensus_pileup.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(PileupTotals)]
+    lib.mipgen_accel_reads_consensus_pileup_gapped.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                               C.POINTER(C.c_int32), C.POINTER(GappedTotals)]
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
-                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup"):
+                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -456,6 +462,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_open_samples", "mipgen_accel_reads_feed_samples", "mipgen_accel_reads_finish_samples", "mipgen_accel_reads_last_samples",
     "mipgen_accel_reads_open_consensus", "mipgen_accel_reads_feed_consensus", "mipgen_accel_reads_finish_consensus", "mipgen_accel_reads_consensus_fetch",
     "mipgen_accel_reads_consensus_pileup",
+    "mipgen_accel_reads_consensus_pileup_gapped",
 ]
 
 
@@ -982,6 +989,23 @@ class Accel:
         self._check(self.lib.mipgen_accel_reads_consensus_pileup(self.h, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, counts.ctypes.data_as(i32p),
                                                                  C.byref(tot)))
         return counts, {f[0]: int(getattr(tot, f[0])) for f in PileupTotals._fields_}
+
+    def consensus_pileup_gapped(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 8):
+        """mipgen_accel_reads_consensus_pileup_gapped, callable after consensus_reads: the pileup with indels.  mol_seq: the template of every probe -
+        ext arm + scan target + lig arm - as one bytes object of sum(mol_len) bytes or as a sequence of one bytes object per probe; it is upper-cased here.
+        Returns (counts[sum(mol_len)][8] int32 - A, C, G, T, discordant, del, ins, ins_discordant - and the totals dict: groups, used, bases, discordant,
+        deletions, insertions, ins_discordant, gapped_sides)."""
+        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
+        total = int(lens.astype(np.int64).clip(min=0).sum())
+        seq = (mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper()
+        if len(seq) != total:
+            raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
+        counts = np.empty((total, 8), dtype=np.int32)
+        tot = GappedTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_reads_consensus_pileup_gapped(self.h, bytes(seq), lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
+                                                                        counts.ctypes.data_as(i32p), C.byref(tot)))
+        return counts, {f[0]: int(getattr(tot, f[0])) for f in GappedTotals._fields_}
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

@@ -583,6 +583,7 @@ double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which)
     if (h && which == 9) return h->consensus_vote_ms;
     if (h && which == 10) return h->consensus_sort_ms;
     if (h && which == 11) return h->pileup_ms;
+    if (h && which == 12) return h->gapped_ms;
     if (!h || !h->timing) return -1.0;
     if (hipSetDevice(h->device) != hipSuccess) return -1.0;
     double total = 0.0;

@@ -260,6 +260,7 @@ struct mipgen_accel {
     double consensus_vote_ms = -1.0; // k_consensus_vote_wave + k_consensus_vote_wg of the last mipgen_accel_reads_finish_consensus (timing enabled)
     double consensus_sort_ms = -1.0; // ... its radix sort of (key, pair id) and the run boundaries
     double pileup_ms = -1.0;         // the kernels_pileup.hip kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled)
+    double gapped_ms = -1.0;         // the kernels of the last mipgen_accel_reads_consensus_pileup_gapped (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -140,4 +140,14 @@ hipError_t mipgen_launch_pileup_prepare(hipStream_t, const uint64_t* keys, const
 hipError_t mipgen_launch_pileup(hipStream_t, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const int32_t* mol_len, const int64_t* pos_off,
                                 const uint32_t* start, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual,
                                 const uint8_t* lig_seq, const uint8_t* lig_qual, int min_family, int min_quality, int64_t n_pos, int32_t* counts, PileupCounters* ctr);
+// kernels_gapped.hip: the sides of one row that need the banded alignment; then the alignment, the counts with indels and their sums
+size_t mipgen_gap_align_lds_bytes(int max_len, int W);
+hipError_t mipgen_launch_gap_list(hipStream_t, const uint64_t* keys, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq,
+                                  const uint8_t* lig_seq, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first,
+                                  int64_t n_row_groups, int min_family, int max_indel, uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr);
+hipError_t mipgen_launch_gapped(hipStream_t, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const uint32_t* start, const uint64_t* keys,
+                                const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual, const uint8_t* lig_seq,
+                                const uint8_t* lig_qual, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first, int min_family,
+                                int min_quality, int max_indel, int max_len, const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int64_t n_pos,
+                                int32_t* counts, GappedCounters* ctr);
 }

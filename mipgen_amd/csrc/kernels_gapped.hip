@@ -1,0 +1,353 @@
+// kernels_gapped.hip — the pileup with indels: every consensus read placed on its probe's template by a banded, anchored alignment, then allele, deletion and
+// insertion counts per template position.  The cell boundaries, the (cell, round) units and the used groups are kernels_pileup.hip's
+// (mipgen_launch_pileup_prepare); the pieces of the alignment are gapped_align.h's.
+//
+//  k_gap_screen   a WAVEFRONT per group of the row, LANES OVER POSITIONS, both sides in turn: does the side need the dynamic program?  THE EXACT SHORTCUT: a side
+//                 whose k = min(m, L) leading bases all equal r (A C G T on both) has the ungapped path as its model path.  (1) A path holds at most min(i, j) <= k
+//                 diagonal steps, each worth at most +1, and every gap step costs 2: k is the largest score any path reaches, and only the path of k diagonal
+//                 steps reaches it.  (2) That path ends at (k, k), an end cell (i == m or j == L) with |j - i| = 0; every other end cell scores less, so no tie
+//                 is broken.  (3) On the path H(c, c) = c, while the gap candidates are H(c, c - 1) - 2 <= c - 3 and H(c - 1, c) - 2 <= c - 3: no cell of the
+//                 path has a tied candidate, so the traceback has no choice.  Such a side gets no projection; the count reads its consensus read as 4.12 does.
+//                 A side of an unused group (family < min_family) or of length 0 is not listed either: it observes nothing.
+//  k_gap_list     a lane per (group, side): the listed sides reserve a slot of list[] and 3 L bytes of the projection buffer, by a wavefront scan and one atomic
+//                 per wavefront and counter, as k_pileup_partition reserves its slots.  The order of the slots is not defined; nothing depends on it.
+//  k_gap_align    HALF A WAVEFRONT per listed side, lanes over the 2 W + 1 <= 31 diagonals of the band, rows in sequence.  The template byte of a lane moves one
+//                 lane down per row (the new one enters at lane 2 W); query and template come in 32-row chunks, a byte per lane, loaded one chunk ahead and
+//                 handed out by __shfl, so no row waits for memory.  The in-row dependency is a prefix maximum of V + 2 d over the 32 lanes (five __shfl_up
+//                 steps of width 32).  Per row two words of directions (two ballots) go to LDS: 8 bytes per row and side.  Then the 32 lanes reduce the end
+//                 key, lane 0 walks back and writes the projection of the consumed columns, and the half fills the rest.
+//  k_gapped_wave  k_pileup_wave / k_pileup_wg with eight counters: lanes over template positions, a loop over the cell's groups; a side with a projection is
+//  k_gapped_wg    read from it (base, quality and insertion byte at t), any other from its consensus read.  32 bytes per position, two 16-byte stores, no atomic.
+//  k_gapped_sum   the column sums, as k_pileup_sum.
+#include "kernels.h"
+#include "gapped_align.h"
+
+struct GapIn {
+    const uint64_t* __restrict__ keys;
+    const int32_t* __restrict__ family;
+    const int64_t* __restrict__ ext_off;
+    const int64_t* __restrict__ lig_off;
+    const uint8_t* __restrict__ ext_seq;
+    const uint8_t* __restrict__ ext_qual;
+    const uint8_t* __restrict__ lig_seq;
+    const uint8_t* __restrict__ lig_qual;
+    const uint8_t* __restrict__ mol_seq;      // the templates, concatenated: probe p at pos_off[p]
+    const int32_t* __restrict__ mol_len;
+    const int64_t* __restrict__ pos_off;
+    uint32_t cell0, g_first;                  // the row's first cell; its first group
+    int min_family, min_quality, W;
+};
+
+__device__ static inline uint32_t gap_wave_sum(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t u = __shfl_up(v, d);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// need[2 gi + side] for the row's groups gi = g - g_first
+__global__ __launch_bounds__(256) void k_gap_screen(GapIn I, int64_t n_row_groups, uint8_t* __restrict__ need)
+{
+    const int64_t gi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gi >= n_row_groups) return;                                                         // (wave-uniform)
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = I.g_first + (uint32_t)gi;
+    const uint32_t p = (uint32_t)(I.keys[g] >> 32) - I.cell0;
+    const int L = I.mol_len[p];
+    const uint8_t* __restrict__ M = I.mol_seq + I.pos_off[p];
+    const bool used = I.family[g] >= I.min_family;
+    for (int side = 0; side < 2; side++) {
+        const int64_t o = side ? I.lig_off[g] : I.ext_off[g];
+        const int m = (int)((side ? I.lig_off[g + 1] : I.ext_off[g + 1]) - o);
+        const uint8_t* __restrict__ q = (side ? I.lig_seq : I.ext_seq) + o;
+        const int k = used ? min(m, L) : 0;
+        bool differs = false;
+        for (int x0 = 0; x0 < k && !differs; x0 += 64) {                                    // (differs is the wavefront's: it comes from a ballot)
+            const int x = x0 + lane;
+            bool bad = false;
+            if (x < k) {
+                const int a = q[x], b = gap_template_byte(M, L, side, x);
+                bad = a != b || gap_base_code(a) > 3;
+            }
+            differs = __ballot(bad) != 0ull;
+        }
+        if (lane == 0) need[2 * gi + side] = differs ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gap_list(GapIn I, int64_t n_row_sides, const uint8_t* __restrict__ need, uint32_t* __restrict__ list, int64_t* __restrict__ proj_off,
+                                                  GappedCounters* __restrict__ ctr)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool listed = s < n_row_sides && need[s];
+    uint32_t bytes = 0;
+    if (listed) {
+        const uint32_t g = I.g_first + (uint32_t)(s >> 1);
+        bytes = 3u * (uint32_t)I.mol_len[(uint32_t)(I.keys[g] >> 32) - I.cell0];
+    }
+    const uint32_t in = gap_wave_sum(listed ? 1u : 0u, lane), ib = gap_wave_sum(bytes, lane);       // (at most 64 x 3 x GAP_MAX_MOL bytes per wavefront)
+    const uint32_t tn = __shfl(in, 63), tb = __shfl(ib, 63);
+    unsigned long long bn = 0, bb = 0;
+    if (lane == 0 && tn) { bn = atomicAdd(&ctr->n_sides, (unsigned long long)tn); bb = atomicAdd(&ctr->proj_bytes, (unsigned long long)tb); }
+    bn = __shfl(bn, 0); bb = __shfl(bb, 0);
+    if (s < n_row_sides) proj_off[s] = listed ? (int64_t)(bb + (ib - bytes)) : -1;
+    if (listed) list[bn + (in - 1u)] = (uint32_t)s;
+}
+
+// ---- the alignment ------------------------------------------------------------------------------------------------------------------------------------
+// Dynamic LDS: [2 halves][rows_cap][2] words of directions; rows_cap = (the longest template of the call) + W >= min(m, L + W), the rows of any side.
+extern __shared__ uint32_t gap_dirs[];
+
+__global__ __launch_bounds__(64) void k_gap_align(const uint32_t* __restrict__ list, int64_t n_sides, const int64_t* __restrict__ proj_off, uint8_t* __restrict__ proj, GapIn I,
+                                                  int rows_cap, GappedCounters* __restrict__ ctr)
+{
+    const int lane = threadIdx.x, half = lane >> 5, d = lane & 31;
+    const int64_t slot = (int64_t)blockIdx.x * 2 + half;
+    const bool live = slot < n_sides;
+    const int W = I.W;
+    const uint32_t s = list[live ? slot : 0];                                               // (a half without a side reads slot 0 and does nothing with it)
+    const uint32_t g = I.g_first + (s >> 1);
+    const int side = (int)(s & 1u);
+    const uint32_t p = (uint32_t)(I.keys[g] >> 32) - I.cell0;
+    const int L = I.mol_len[p];
+    const uint8_t* __restrict__ M = I.mol_seq + I.pos_off[p];
+    const int64_t qo = side ? I.lig_off[g] : I.ext_off[g];
+    const int m = live ? (int)((side ? I.lig_off[g + 1] : I.ext_off[g + 1]) - qo) : 0;
+    const uint8_t* __restrict__ q = (side ? I.lig_seq : I.ext_seq) + qo;
+    const uint8_t* __restrict__ qq = (side ? I.lig_qual : I.ext_qual) + qo;
+    const int rows = min(min(m, L + W), rows_cap);                                          // rows beyond L + W lie outside the band; (rows_cap >= L + W: the host's)
+    const int rows_all = max(rows, __shfl_xor(rows, 32));
+    uint32_t* dirs = gap_dirs + (size_t)half * (size_t)rows_cap * 2;
+
+    // row 0
+    int H = gap_in_band(0, d, W, L) ? -2 * (d - W) : GAP_NEG;
+    uint64_t best = 0;
+    if (live && H != GAP_NEG && d - W == L) best = gap_end_key(H, 0, L);                    // (m >= 1 for a listed side: row 0 is an end row for column L only)
+    // lane d holds the template byte of its cell's column: r[i + d - W - 1] in row i
+    int rwin = 0;
+    { const int x = d - W - 1; if (live && x >= 0 && x < L) rwin = gap_template_byte(M, L, side, x); }
+    // chunks of 32 rows: lane k holds q[c + k] and r[c + k + W], c = 32 (chunk)
+    auto q_at = [&](int x) { return live && x < m ? (int)q[x] : 0; };
+    auto r_at = [&](int x) { return live && x < L ? gap_template_byte(M, L, side, x) : 0; };
+    int q_next = q_at(d), r_next = r_at(d + W), q_chunk = 0, r_chunk = 0;
+    for (int i = 1; i <= rows_all; i++) {
+        const int k = (i - 1) & 31;
+        if (k == 0) { q_chunk = q_next; r_chunk = r_next; q_next = q_at(i + 31 + d); r_next = r_at(i + 31 + d + W); }
+        const int qb = __shfl(q_chunk, k, 32), r_new = __shfl(r_chunk, k, 32);
+        const int r_down = __shfl_down(rwin, 1, 32);
+        rwin = d == 2 * W ? r_new : r_down;
+        const int j = i + d - W;
+        const bool valid = i <= rows && gap_in_band(i, d, W, L);
+        int up = __shfl_down(H, 1, 32);
+        if (d >= 2 * W) up = GAP_NEG;
+        const int cd = j >= 1 ? gap_cand_diag(H, gap_score(qb, rwin)) : GAP_NEG, ci = gap_cand_ins(up);
+        int X = (valid ? max(cd, ci) : GAP_NEG) + 2 * d;
+#pragma unroll
+        for (int off = 1; off < 32; off <<= 1) {
+            const int u = __shfl_up(X, off, 32);
+            if (d >= off) X = max(X, u);
+        }
+        H = valid ? gap_clip(X - 2 * d) : GAP_NEG;
+        int left = __shfl_up(H, 1, 32);
+        if (d == 0) left = GAP_NEG;
+        const int dir = valid ? gap_dir(H, cd, gap_cand_del(left), ci, side) : GAP_STOP;
+        const unsigned long long b0 = __ballot(dir & 1), b1 = __ballot(dir & 2);
+        if (d == 0 && i <= rows) { dirs[2 * (i - 1)] = (uint32_t)(b0 >> (32 * half)); dirs[2 * (i - 1) + 1] = (uint32_t)(b1 >> (32 * half)); }
+        if (valid && (j == L || i == m)) { const uint64_t key = gap_end_key(H, i, j); best = key > best ? key : best; }
+    }
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) {
+        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)best, off, 32);
+        best = o > best ? o : best;
+    }
+    // the walk back: lane 0 of the half (the lane that wrote the directions)
+    const int je = gap_end_j(best);
+    const int64_t po = live ? proj_off[s] : 0;
+    uint8_t* base = proj + po;
+    int gaps = 0;
+    if (live && d == 0 && best != 0) gaps = gap_traceback(dirs, W, L, side, gap_end_i(best), je, q, qq, base, base + L, base + 2 * (size_t)L, nullptr);
+    // the positions the path does not consume: columns je + 1 .. L
+    if (live) {
+        const int t0 = side ? 0 : je, t1 = side ? L - je : L;                               // [t0, t1)
+        for (int t = t0 + d; t < t1; t += 32) { base[t] = 0; base[L + t] = 0; base[2 * (size_t)L + t] = GAP_NOT_COVERED; }
+    }
+    const int n_gapped = __popcll(__ballot(gaps > 0));
+    if (lane == 0 && n_gapped) atomicAdd(&ctr->gapped_sides, (unsigned long long)n_gapped);
+}
+
+// ---- the count ------------------------------------------------------------------------------------------------------------------------------------------
+#define GAP_CLASS_DEL 4u
+#define GAP_CLASS_NONE 5u
+#define GAP_CLASS_DISC 6u
+
+struct GapPile {
+    int a = 0, c = 0, g = 0, t = 0, disc = 0, del = 0, ins = 0, insd = 0;
+    // the vote of one molecule at one position and at the anchor behind it: ce / cl - each side's usable observation (0..3, del, none), ve / vl -
+    // the side covers the anchor (t, t + 1), ne / nl - its insertion length there
+    __device__ inline void add(bool ok, uint32_t ce, uint32_t cl, bool ve, bool vl, uint32_t ne, uint32_t nl)
+    {
+        const bool ue = ok && ce < GAP_CLASS_NONE, ul = ok && cl < GAP_CLASS_NONE;
+        const uint32_t col = ue && ul && ce != cl ? GAP_CLASS_DISC : ue ? ce : ul ? cl : GAP_CLASS_NONE;
+        a += col == 0u; c += col == 1u; g += col == 2u; t += col == 3u; del += col == GAP_CLASS_DEL; disc += col == GAP_CLASS_DISC;
+        const bool xe = ok && ve, xl = ok && vl;
+        ins += xe && xl ? (ne == nl && ne > 0u) : xe ? ne > 0u : xl ? nl > 0u : false;
+        insd += xe && xl && ne != nl;
+    }
+};
+
+// one side of group g at template position t (t < L, or t == L for a lane beyond the template: its index is clamped and its value discarded).  po is the
+// wavefront's: a side with a projection (po >= 0) or without.  idx: the index of t in the consensus read (t itself, or L - 1 - t on the ligation side).
+__device__ static inline void gap_observe(const uint8_t* __restrict__ proj, int64_t po, const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual, int64_t o, int n, int idx,
+                                          int t, int L, bool lig, int min_q, uint32_t& cls, bool& covers, uint32_t& ins_len)
+{
+    if (po >= 0) {
+        const uint8_t* __restrict__ P = proj + po;
+        const int tt = min(t, L - 1);
+        const uint32_t b = P[tt], qv = P[L + tt], il = P[2 * (size_t)L + tt];
+        const uint32_t c = reads_base_code(b);
+        cls = b == '-' ? GAP_CLASS_DEL : c < 4u && (int)qv - 33 >= min_q ? c : GAP_CLASS_NONE;
+        covers = il != GAP_NOT_COVERED; ins_len = il;
+    } else {
+        const bool present = idx >= 0 && idx < n;
+        const int64_t at = o + max(min(idx, n - 1), 0);                                     // clamped: see the head of kernels_pileup.hip
+        const uint32_t b = seq[at], qv = qual[at];
+        uint32_t c = reads_base_code(b);
+        if (lig) c = c < 4u ? 3u - c : 4u;
+        cls = present && c < 4u && (int)qv - 33 >= min_q ? c : GAP_CLASS_NONE;
+        covers = present && (lig ? idx >= 1 : (t + 1 < n && t + 1 < L));                   // the ungapped path consumes t and t + 1
+        ins_len = 0u;
+    }
+}
+
+__device__ static inline void gap_pile_groups(GapPile& S, const GapIn& I, const int64_t* __restrict__ proj_off, const uint8_t* __restrict__ proj, uint32_t g0, uint32_t g1,
+                                              uint32_t stride, int t, int L)
+{
+    for (uint32_t g = g0; g < g1; g += stride) {
+        const int64_t eo = I.ext_off[g], lo = I.lig_off[g];
+        const int el = (int)(I.ext_off[g + 1] - eo), ll = (int)(I.lig_off[g + 1] - lo);
+        const int64_t pe = proj_off[2 * (size_t)(g - I.g_first)], pl = proj_off[2 * (size_t)(g - I.g_first) + 1];
+        uint32_t ce, cl, ne, nl;
+        bool ve, vl;
+        gap_observe(proj, pe, I.ext_seq, I.ext_qual, eo, el, t, t, L, false, I.min_quality, ce, ve, ne);
+        gap_observe(proj, pl, I.lig_seq, I.lig_qual, lo, ll, L - 1 - t, t, L, true, I.min_quality, cl, vl, nl);
+        S.add(I.family[g] >= I.min_family, ce, cl, ve, vl, ne, nl);
+    }
+}
+
+__device__ static inline void gap_store(int32_t* __restrict__ o, const GapPile& S)
+{
+    int4* __restrict__ v = reinterpret_cast<int4*>(o);                                      // (32 bytes per position, the table 256-byte aligned)
+    v[0] = make_int4(S.a, S.c, S.g, S.t);
+    v[1] = make_int4(S.disc, S.del, S.ins, S.insd);
+}
+
+__global__ __launch_bounds__(256) void k_gapped_wave(const uint2* __restrict__ units, int64_t n_units, const uint32_t* __restrict__ start, GapIn I,
+                                                     const int64_t* __restrict__ proj_off, const uint8_t* __restrict__ proj, int32_t* __restrict__ counts)
+{
+    const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= n_units) return;                                                               // (wave-uniform)
+    const int lane = threadIdx.x & 63;
+    const uint2 unit = units[k];
+    const uint32_t p = __builtin_amdgcn_readfirstlane(unit.x), r = __builtin_amdgcn_readfirstlane(unit.y);
+    const int len = I.mol_len[p];
+    const int t = (int)min((int64_t)r * 64 + lane, (int64_t)len);
+    GapPile S;
+    gap_pile_groups(S, I, proj_off, proj, start[p], start[p + 1], 1u, t, len);
+    if (t < len) gap_store(counts + (I.pos_off[p] + t) * GAPPED_COLUMNS, S);
+}
+
+__global__ __launch_bounds__(256) void k_gapped_wg(const uint2* __restrict__ units, const uint32_t* __restrict__ start, GapIn I, const int64_t* __restrict__ proj_off,
+                                                   const uint8_t* __restrict__ proj, int32_t* __restrict__ counts)
+{
+    __shared__ int part[3][GAPPED_COLUMNS][64];                                             // the counters of wavefronts 1..3: 6,144 bytes
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint2 unit = units[blockIdx.x];
+    const uint32_t p = unit.x, r = unit.y;
+    const int len = I.mol_len[p];
+    const int t = (int)min((int64_t)r * 64 + lane, (int64_t)len);
+    GapPile S;
+    gap_pile_groups(S, I, proj_off, proj, start[p] + wave, start[p + 1], 4u, t, len);
+    if (wave) {
+        int (*w)[64] = part[wave - 1];
+        w[0][lane] = S.a; w[1][lane] = S.c; w[2][lane] = S.g; w[3][lane] = S.t; w[4][lane] = S.disc; w[5][lane] = S.del; w[6][lane] = S.ins; w[7][lane] = S.insd;
+    }
+    __syncthreads();
+    if (wave == 0 && t < len) {
+#pragma unroll
+        for (int w = 0; w < 3; w++) {
+            S.a += part[w][0][lane]; S.c += part[w][1][lane]; S.g += part[w][2][lane]; S.t += part[w][3][lane];
+            S.disc += part[w][4][lane]; S.del += part[w][5][lane]; S.ins += part[w][6][lane]; S.insd += part[w][7][lane];
+        }
+        gap_store(counts + (I.pos_off[p] + t) * GAPPED_COLUMNS, S);
+    }
+}
+
+__device__ static inline long long gap_wave_sum_i64(long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_gapped_sum(const int32_t* __restrict__ counts, int64_t n_pos, GappedCounters* __restrict__ ctr)
+{
+    long long s[5] = {0, 0, 0, 0, 0};                                                       // bases, discordant, del, ins, ins_discordant
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pos; i += (int64_t)gridDim.x * blockDim.x) {
+        const int4* __restrict__ v = reinterpret_cast<const int4*>(counts + i * GAPPED_COLUMNS);
+        const int4 x = v[0], y = v[1];
+        s[0] += (long long)x.x + x.y + x.z + x.w; s[1] += y.x; s[2] += y.y; s[3] += y.z; s[4] += y.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++) s[k] = gap_wave_sum_i64(s[k]);
+    if ((threadIdx.x & 63) == 0) {
+        if (s[0]) atomicAdd(&ctr->bases, (unsigned long long)s[0]);
+        if (s[1]) atomicAdd(&ctr->discordant, (unsigned long long)s[1]);
+        if (s[2]) atomicAdd(&ctr->deletions, (unsigned long long)s[2]);
+        if (s[3]) atomicAdd(&ctr->insertions, (unsigned long long)s[3]);
+        if (s[4]) atomicAdd(&ctr->ins_discordant, (unsigned long long)s[4]);
+    }
+}
+
+extern "C" {
+
+size_t mipgen_gap_align_lds_bytes(int max_len, int W) { return (size_t)2 * (size_t)(max_len + W) * 2 * sizeof(uint32_t); }
+
+// the sides of the row's groups [g_first, g_first + n_row_groups) that need the dynamic program: list[0, ctr->n_sides), proj_off[2 n_row_groups] (-1: no
+// projection), ctr->proj_bytes; ctr is zero on entry
+hipError_t mipgen_launch_gap_list(hipStream_t st, const uint64_t* keys, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq,
+                                  const uint8_t* lig_seq, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first,
+                                  int64_t n_row_groups, int min_family, int max_indel, uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr)
+{
+    if (n_row_groups < 1 || n_row_groups > 0x3fffffff || max_indel < 1 || max_indel > GAP_MAX_INDEL) return hipErrorInvalidValue;
+    const GapIn I{keys, family, ext_off, lig_off, ext_seq, nullptr, lig_seq, nullptr, mol_seq, mol_len, pos_off, cell0, g_first, min_family, 0, max_indel};
+    hipLaunchKernelGGL(k_gap_screen, dim3((unsigned)((n_row_groups + 3) / 4)), dim3(256), 0, st, I, n_row_groups, need);
+    hipLaunchKernelGGL(k_gap_list, dim3((unsigned)((2 * n_row_groups + 255) / 256)), dim3(256), 0, st, I, 2 * n_row_groups, need, list, proj_off, ctr);
+    return hipGetLastError();
+}
+
+// the alignment of the n_sides listed sides into proj, then counts[n_pos][8] written whole and summed into ctr
+hipError_t mipgen_launch_gapped(hipStream_t st, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const uint32_t* start, const uint64_t* keys,
+                                const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual, const uint8_t* lig_seq,
+                                const uint8_t* lig_qual, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first, int min_family,
+                                int min_quality, int max_indel, int max_len, const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int64_t n_pos,
+                                int32_t* counts, GappedCounters* ctr)
+{
+    if (n_small < 0 || n_big < 0 || n_small + n_big != n_units || n_units > 0x7fffffff || n_pos < 1 || n_sides < 0 || n_sides > 0x7fffffff || max_indel < 1 ||
+        max_indel > GAP_MAX_INDEL || max_len < 1 || max_len > GAP_MAX_MOL)
+        return hipErrorInvalidValue;
+    const GapIn I{keys, family, ext_off, lig_off, ext_seq, ext_qual, lig_seq, lig_qual, mol_seq, mol_len, pos_off, cell0, g_first, min_family, min_quality, max_indel};
+    if (n_sides > 0)
+        hipLaunchKernelGGL(k_gap_align, dim3((unsigned)((n_sides + 1) / 2)), dim3(64), mipgen_gap_align_lds_bytes(max_len, max_indel), st, list, n_sides, proj_off, proj, I,
+                           max_len + max_indel, ctr);
+    if (n_small > 0) hipLaunchKernelGGL(k_gapped_wave, dim3((unsigned)((n_small + 3) / 4)), dim3(256), 0, st, units, n_small, start, I, proj_off, proj, counts);
+    if (n_big > 0) hipLaunchKernelGGL(k_gapped_wg, dim3((unsigned)n_big), dim3(256), 0, st, units + n_small, start, I, proj_off, proj, counts);
+    hipLaunchKernelGGL(k_gapped_sum, dim3((unsigned)std::min<int64_t>((n_pos + 255) / 256, 2048)), dim3(256), 0, st, counts, n_pos, ctr);
+    return hipGetLastError();
+}
+
+}

@@ -112,3 +112,10 @@ struct ConsensusCounters { unsigned long long members, groups, n_small, n_big; }
 // n_small / n_big: the (cell, round) units listed for the one-wavefront / the workgroup kernel; used: the row's groups of at least min_family pairs; bases / discordant:
 // the sums of columns 0..3 / of column 4
 struct PileupCounters { unsigned long long n_small, n_big, used, bases, discordant; };
+
+// ---- the pileup with indels ----
+#define GAPPED_COLUMNS 8             // A, C, G, T, discordant, del, ins, ins_discordant
+
+// n_sides / proj_bytes: the (group, side) pairs listed for k_gap_align and the bytes of their projections; gapped_sides: those whose path holds a gap step; the others:
+// the sums of columns 0..3, 4, 5, 6 and 7
+struct GappedCounters { unsigned long long n_sides, proj_bytes, gapped_sides, bases, discordant, deletions, insertions, ins_discordant; };

@@ -39,6 +39,10 @@
 //                           orientation: on a '-' probe position = ext_probe_stop - t, ref is the complement of the molecule's base and A/T, C/G swap columns
 //   -pileup_min_family k    only molecules of at least k pairs count (default 1); -pileup_min_quality q: only consensus bases of quality >= q, 0..40 (default 0)
 //   stderr     a last line: "mipgen_count: pileup molecules U positions P bases B nonref R discordant D" (U: the molecules counted; P: lines written)
+//   -pileup_indels W        place every consensus read on its template by a banded alignment of at most W (1..15) inserted or deleted bases first: the
+//                           header and every line gain the columns del, ins and ins_discordant (molecules that show a deletion of the base; an insertion between
+//                           this base and the next one in genome plus orientation; two different insertion lengths there), a line is written when any of its eight
+//                           numbers is non-zero, and a second stderr line follows: "mipgen_count: pileup indels deletions X insertions Y ins_discordant Z gapped_sides S"
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -68,7 +72,8 @@ static int usage(const std::string& msg)
             "-barcode_mismatches n : substitutions allowed between index and barcode, 0 or 1 (default 0)\n"
             "-samples file : sample, barcode, pairs, assigned, unique_tags, probes_seen per sample\n"
             "-consensus prefix : prefix.ext.fq and prefix.lig.fq, one consensus read pair per (sample, probe, tag) group; -min_family k : groups of at least k pairs (default 1)\n"
-            "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n");
+            "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n"
+            "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n");
     return 1;
 }
 
@@ -168,7 +173,7 @@ static bool parse_int_list(const std::string& v, std::vector<long>& out)
 int main(int argc, char** argv)
 {
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
-    long min_family = 1, pile_family = 1, pile_quality = 0;
+    long min_family = 1, pile_family = 1, pile_quality = 0, pile_indels = 0;
     bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
     std::string consensus_prefix, pileup_path;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
@@ -204,6 +209,7 @@ int main(int argc, char** argv)
         else if (a == "-pileup") { if (v.empty()) return usage("-pileup takes a file"); pileup_path = v; }
         else if (a == "-pileup_min_family") { if (!svr_parse_int(v.c_str(), &pile_family) || pile_family < 1 || pile_family > INT32_MAX) return usage("-pileup_min_family must be 1 or more"); pile_option_given = true; }
         else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
+        else if (a == "-pileup_indels") { if (!svr_parse_int(v.c_str(), &pile_indels) || pile_indels < 1 || pile_indels > 15) return usage("-pileup_indels must be 1 to 15"); }
         else if (a == "-barcode_mismatches") {
             if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-barcode_mismatches must be 0 or 1");
             bc_mism = (int)iv; bc_mism_given = true;
@@ -224,6 +230,7 @@ int main(int argc, char** argv)
     if (consensus && te + tl == 0) return usage("-consensus needs tag bases: with -tag_sizes 0,0 there are no molecules to collapse");
     const bool pileup = !pileup_path.empty(), keep_reads = consensus || pileup;      // (-pileup reads the consensus reads: its session keeps the reads too)
     if (pile_option_given && !pileup) return usage("-pileup_min_family and -pileup_min_quality need -pileup file");
+    if (pile_indels && !pileup) return usage("-pileup_indels needs -pileup file");
     if (pileup && te + tl == 0) return usage("-pileup needs tag bases: with -tag_sizes 0,0 there are no molecules to count");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
@@ -269,6 +276,7 @@ int main(int argc, char** argv)
     if (probes.size() > (size_t)INT32_MAX) { fprintf(stderr, "%s: too many probes\n", PROG); return 1; }
     // -pileup: the length of every probe's molecule and where it lies on the genome
     std::vector<int32_t> mol_len;
+    std::string mol_seq;                                                                 // -pileup_indels: the templates, upper-cased, in probe order
     std::vector<RowCoords> coords;
     if (pileup)
         for (const auto* r : rows) {
@@ -277,6 +285,14 @@ int main(int argc, char** argv)
             if (!row_coords(*r, &c, &what)) { fprintf(stderr, "%s: -pileup: probe %s: %s\n", PROG, (*r)[COL_KEY].c_str(), what); return 1; }
             coords.push_back(c);
             mol_len.push_back((int32_t)((*r)[COL_EXT_SEQ].size() + (*r)[COL_INS_SEQ].size() + (*r)[COL_LIG_SEQ].size()));
+            if (pile_indels) {
+                if (mol_len.back() > MIPGEN_GAPPED_MAX_MOL) {
+                    fprintf(stderr, "%s: -pileup_indels: probe %s: a molecule of %d bases (at most %d are placed)\n", PROG, (*r)[COL_KEY].c_str(), mol_len.back(), MIPGEN_GAPPED_MAX_MOL);
+                    return 1;
+                }
+                for (const std::string* part : {&(*r)[COL_EXT_SEQ], &(*r)[COL_INS_SEQ], &(*r)[COL_LIG_SEQ]})
+                    for (char ch : *part) mol_seq.push_back((char)toupper((unsigned char)ch));
+            }
         }
     if (shortest < 12) { fprintf(stderr, "%s: the shortest arm of the tables has %zu bases: a seed of fewer than 12 bases is refused\n", PROG, shortest); return 1; }
     Fastq fe, fl;
@@ -403,12 +419,13 @@ int main(int argc, char** argv)
     if (consensus && mipgen_accel_reads_consensus_fetch(h, g_cell.data(), g_tag.data(), g_family.data(), g_off[0].data(), &g_seq[0][0], &g_qual[0][0], g_off[1].data(), &g_seq[1][0],
                                                         &g_qual[1][0]) != MIPGEN_OK) return die();
     // -pileup: one call per row; a second thread turns the counts of a row into lines while the device counts the next row
-    long long pile_used = 0, pile_lines = 0, pile_bases = 0, pile_nonref = 0, pile_disc = 0;
+    long long pile_used = 0, pile_lines = 0, pile_bases = 0, pile_nonref = 0, pile_disc = 0, pile_del = 0, pile_ins = 0, pile_insd = 0, pile_gapped = 0;
+    const size_t pile_cols = pile_indels ? 8 : 5;
     if (pileup) {
         int64_t n_pos = 0;
         std::vector<int64_t> pos_off;
         for (int32_t l : mol_len) { pos_off.push_back(n_pos); n_pos += l; }
-        std::vector<int32_t> table[2] = {std::vector<int32_t>((size_t)n_pos * 5), std::vector<int32_t>(n_rows > 1 ? (size_t)n_pos * 5 : 0)};
+        std::vector<int32_t> table[2] = {std::vector<int32_t>((size_t)n_pos * pile_cols), std::vector<int32_t>(n_rows > 1 ? (size_t)n_pos * pile_cols : 0)};
         auto write_row = [&](size_t r, const std::vector<int32_t>& counts) {
             const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
             std::string text;
@@ -418,8 +435,16 @@ int main(int argc, char** argv)
                 const RowCoords& c = coords[i];
                 const size_t n_ext = f[COL_EXT_SEQ].size(), n_ins = f[COL_INS_SEQ].size();
                 for (int32_t t = 0; t < mol_len[i]; t++) {
-                    const int32_t* k = &counts[(size_t)(pos_off[i] + t) * 5];
-                    if (!(k[0] | k[1] | k[2] | k[3] | k[4])) continue;
+                    const int32_t* k = &counts[(size_t)(pos_off[i] + t) * pile_cols];
+                    // -pileup_indels: del at t; the insertion columns of the anchor whose LOWER genome coordinate this line is - anchor t (between t and t + 1) on
+                    // the plus strand, anchor t - 1 on the minus strand
+                    int32_t indel[3] = {0, 0, 0};
+                    if (pile_indels) {
+                        indel[0] = k[5];
+                        const int32_t* a = c.minus ? (t > 0 ? k - 8 : nullptr) : k;
+                        if (a) { indel[1] = a[6]; indel[2] = a[7]; }
+                    }
+                    if (!(k[0] | k[1] | k[2] | k[3] | k[4] | indel[0] | indel[1] | indel[2])) continue;
                     const size_t ut = (size_t)t;
                     char ref = (char)toupper((unsigned char)(ut < n_ext ? f[COL_EXT_SEQ][ut] : ut < n_ext + n_ins ? f[COL_INS_SEQ][ut - n_ext] : f[COL_LIG_SEQ][ut - n_ext - n_ins]));
                     int32_t plus[4] = {k[0], k[1], k[2], k[3]};
@@ -429,19 +454,30 @@ int main(int argc, char** argv)
                     }
                     for (int b = 0; b < 4; b++) { pile_bases += plus[b]; if ("ACGT"[b] != ref) pile_nonref += plus[b]; }
                     pile_disc += k[4];
-                    snprintf(buf, sizeof buf, "\t%ld\t%c\t%s\t%c\t%d\t%d\t%d\t%d\t%d\n", c.minus ? c.ext_stop - t : c.ext_start + t, c.minus ? '-' : '+',
-                             ut < n_ext ? "ext" : ut < n_ext + n_ins ? "target" : "lig", ref, plus[0], plus[1], plus[2], plus[3], k[4]);
+                    int at = snprintf(buf, sizeof buf, "\t%ld\t%c\t%s\t%c\t%d\t%d\t%d\t%d\t%d", c.minus ? c.ext_stop - t : c.ext_start + t, c.minus ? '-' : '+',
+                                      ut < n_ext ? "ext" : ut < n_ext + n_ins ? "target" : "lig", ref, plus[0], plus[1], plus[2], plus[3], k[4]);
+                    if (pile_indels) {
+                        at += snprintf(buf + at, sizeof buf - (size_t)at, "\t%d\t%d\t%d", indel[0], indel[1], indel[2]);
+                        pile_del += indel[0]; pile_ins += indel[1]; pile_insd += indel[2];
+                    }
+                    snprintf(buf + at, sizeof buf - (size_t)at, "\n");
                     text.append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf);
                     pile_lines++;
                 }
             }
             fwrite(text.data(), 1, text.size(), pile_out);
         };
-        fputs(">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
+        fputs(pile_indels ? ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n"
+                          : ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
         std::thread writer;
         for (size_t r = 0; r < n_rows; r++) {
-            mipgen_pileup_totals pt;
-            const int prc = mipgen_accel_reads_consensus_pileup(h, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality, table[r & 1].data(), &pt);
+            mipgen_pileup_totals pt{0, 0, 0, 0};
+            mipgen_gapped_totals gt{0, 0, 0, 0, 0, 0, 0, 0};
+            const int prc = pile_indels ? mipgen_accel_reads_consensus_pileup_gapped(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
+                                                                                     (int32_t)pile_quality, (int32_t)pile_indels, table[r & 1].data(), &gt)
+                                        : mipgen_accel_reads_consensus_pileup(h, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
+                                                                              table[r & 1].data(), &pt);
+            if (pile_indels) { pt.used = gt.used; pile_gapped += gt.gapped_sides; }
             if (writer.joinable()) writer.join();
             if (prc != MIPGEN_OK) return die();
             pile_used += pt.used;
@@ -527,5 +563,6 @@ int main(int argc, char** argv)
         fprintf(stderr, "%s: samples %zu sample_none %lld sample_ambiguous %lld\n", PROG, barcodes.size(), (long long)stot.sample_none, (long long)stot.sample_ambiguous);
     if (consensus) fprintf(stderr, "%s: consensus groups %lld written %lld members %lld\n", PROG, (long long)csz.n_groups, cons_written, cons_members);
     if (pileup) fprintf(stderr, "%s: pileup molecules %lld positions %lld bases %lld nonref %lld discordant %lld\n", PROG, pile_used, pile_lines, pile_bases, pile_nonref, pile_disc);
+    if (pile_indels) fprintf(stderr, "%s: pileup indels deletions %lld insertions %lld ins_discordant %lld gapped_sides %lld\n", PROG, pile_del, pile_ins, pile_insd, pile_gapped);
     return 0;
 }
