@@ -1,6 +1,7 @@
 // accel_internal.h — what the host-side translation units of libmipgen_accel.so share (the kernel launchers are in kernels.h): the error convention,
 // device buffers, the handle (struct mipgen_accel) and the helpers that cross files.  accel.hip: lifecycle, model, region batch; accel_tiles.hip:
-// tile lists of the scoring kernels; accel_score.hip: scoring / replay / collapse / record text / downloads; accel_kmer.hip: section 8f-3.
+// tile lists of the scoring kernels; accel_score.hip: scoring / replay / collapse / record text / downloads; accel_kmer.hip: section 8f-3;
+// accel_reads.hip: read sessions; accel_pileup.hip: the pileups read off the consensus reads a session leaves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,7 +139,48 @@ struct RescoreList {
 };
 
 struct ReadsSession;                  // accel_reads.hip
-struct ConsensusResult;               // accel_reads.hip: the consensus reads of the last mipgen_accel_reads_finish_consensus
+
+// ---- the consensus reads a session leaves on the handle and the scratch of the two pileups read off them (accel_pileup.hip) ----
+// what both pileup calls hold of one row: kept with the consensus reads between calls - a call per row would otherwise pay the allocations every time
+struct RowScratch {
+    DevBuf<int32_t> mol_len;                                 // n
+    DevBuf<int64_t> pos_off;                                 // n
+    DevBuf<uint32_t> start;                                  // n + 1
+    DevBuf<uint2> units;                                     // the rounds of all probes
+    DevBuf<PileupCounters> pctr;
+    size_t held() const { return mol_len.cap * 4 + pos_off.cap * 8 + start.cap * 4 + units.cap * 8 + pctr.cap * sizeof(PileupCounters); }
+    void release() { mol_len.release(); pos_off.release(); start.release(); units.release(); pctr.release(); }
+};
+// mipgen_accel_reads_consensus_pileup
+struct PileupScratch {
+    RowScratch row;
+    DevBuf<int32_t> counts;                                  // positions x PILEUP_COLUMNS
+    size_t held() const { return row.held() + counts.cap * 4; }
+    void release() { row.release(); counts.release(); }
+};
+// mipgen_accel_reads_consensus_pileup_gapped: its own buffers throughout, so that neither pileup call touches what the other holds
+struct GappedScratch {
+    RowScratch row;
+    DevBuf<int32_t> counts;                                  // positions x GAPPED_COLUMNS
+    DevBuf<int64_t> proj_off;                                // 2 x the row's groups
+    DevBuf<uint32_t> list;                                   // the listed sides
+    DevBuf<uint8_t> mol_seq, need, proj;                     // positions; 2 x the row's groups; the projections of the listed sides
+    DevBuf<GappedCounters> ctr;
+    size_t held() const { return row.held() + counts.cap * 4 + proj_off.cap * 8 + list.cap * 4 + mol_seq.cap + need.cap + proj.cap + ctr.cap * sizeof(GappedCounters); }
+    void release() { row.release(); counts.release(); proj_off.release(); list.release(); mol_seq.release(); need.release(); proj.release(); ctr.release(); }
+};
+struct ConsensusResult {
+    int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
+    int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
+    PileupScratch pile;
+    GappedScratch gapped;
+    DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
+    DevBuf<int32_t> family;
+    DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
+    DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
+    ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); }
+};
 
 struct mipgen_accel {
     int device = 0;
@@ -316,6 +358,34 @@ struct DiagClock {                           // host seconds per stage of a call
 #define DIAG_CLOCK(name) do { } while (0)
 #define DIAG_LAP(stage) do { } while (0)
 #endif
+
+// ---- what the read sessions and the pileups share of a call's plumbing ----
+static inline int free_device_bytes(size_t* free_b)
+{
+    size_t total_b = 0;
+    HIP_TRY(hipMemGetInfo(free_b, &total_b));
+    return MIPGEN_OK;
+}
+// the stream is idle when the scope ends, however it ends: the caller's arrays and the host tables behind an asynchronous copy are free from then on
+struct IdleOnExit { hipStream_t s; bool idle = false; hipError_t wait() { idle = true; return hipStreamSynchronize(s); } ~IdleOnExit() { if (!idle) (void)hipStreamSynchronize(s); } };
+
+// HIP-event time of spans of the stream when timing is on (off: no event is ever created).  mark() before and after a span; add_to(), called once the stream is idle and the
+// call has succeeded, adds the ms of every span to *sum and says how many it added; the destructor destroys the events.
+struct SpanTimer {
+    bool on;
+    hipStream_t st;
+    std::vector<hipEvent_t> ev;                              // (before, after) of every span
+    ~SpanTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void mark() { hipEvent_t e = nullptr; if (on && (on = hipEventCreate(&e) == hipSuccess)) { ev.push_back(e); (void)hipEventRecord(e, st); } }
+    int add_to(double* sum) const
+    {
+        int n = 0;
+        float ms = 0.f;
+        for (size_t k = 0; on && k + 1 < ev.size(); k += 2)
+            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) { *sum += ms; n++; }
+        return n;
+    }
+};
 
 // ---- helpers that cross translation units ----------------------------------------------------------------------
 extern "C" {

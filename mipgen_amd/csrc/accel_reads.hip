@@ -1,12 +1,11 @@
 // accel_reads.hip — read sessions behind the C ABI: reads and unique tags per probe from smMIP read pairs (mipgen_accel_reads_open / _feed / _finish), per sample of
 // a multiplexed lane (4.10: _open_samples / _feed_samples / _finish_samples / _last_samples), with one consensus read pair per molecule (4.11: _open_consensus / _feed_consensus /
-// _finish_consensus / _consensus_fetch), and the allele counts per template position read off those (4.12: _consensus_pileup; with indels, 4.13: _consensus_pileup_gapped).  The three families of entry points name ONE path.  ReadsSession is what every session has plus a KeyList, a SamplesPart and a
+// _finish_consensus / _consensus_fetch; the pileups read off the ConsensusResult a finish leaves on the handle are accel_pileup.hip's).  The three families of entry points name ONE path.  ReadsSession is what every session has plus a KeyList, a SamplesPart and a
 // ConsensusPart; its flags `samples` and `consensus` say which parts are set up, and session_for() alone matches a call to the open session.  open_impl: check_open
 // (probe table, then barcodes), build_host_tables, the budget, upload_tables.  feed_impl: eleven stages, the kinds differing in data only - where the bases of the call live and where
 // k_read_assign's keys go.  finish_session: consensus_finish where reads were kept, finish_impl, release.  Errors are HIP_TRY returns; IdleOnExit and FreeOnExit put the
 // stream and a chunk's block right on every way out, SpanTimer books HIP-event times.  A session owns every buffer it uses; of the handle it takes the device and the stream.
 #include "accel_internal.h"
-#include "gapped_align.h"
 
 struct SeedTableBufs {
     DevBuf<uint32_t> slots, start;
@@ -33,50 +32,6 @@ struct ChunkLayout {
     }
 };
 
-// what mipgen_accel_reads_consensus_pileup needs beside the consensus reads: kept with them between calls - a call per row would otherwise pay the
-// allocation of the count buffer every time - and never read by anything else
-struct PileupScratch {
-    DevBuf<int32_t> mol_len, counts;                         // n; positions x PILEUP_COLUMNS
-    DevBuf<int64_t> pos_off;                                 // n
-    DevBuf<uint32_t> start;                                  // n + 1
-    DevBuf<uint2> units;                                     // the rounds of all probes
-    DevBuf<PileupCounters> ctr;
-    size_t held() const { return mol_len.cap * 4 + counts.cap * 4 + pos_off.cap * 8 + start.cap * 4 + units.cap * 8 + ctr.cap * sizeof(PileupCounters); }
-    void release() { mol_len.release(); counts.release(); pos_off.release(); start.release(); units.release(); ctr.release(); }
-};
-
-// what mipgen_accel_reads_consensus_pileup_gapped needs: its own buffers throughout, so that neither pileup call touches what the other holds
-struct GappedScratch {
-    DevBuf<int32_t> mol_len, counts;                         // n; positions x GAPPED_COLUMNS
-    DevBuf<int64_t> pos_off, proj_off;                       // n; 2 x the row's groups
-    DevBuf<uint32_t> start, list;                            // n + 1; the listed sides
-    DevBuf<uint2> units;
-    DevBuf<uint8_t> mol_seq, need, proj;                     // positions; 2 x the row's groups; the projections of the listed sides
-    DevBuf<PileupCounters> pctr;
-    DevBuf<GappedCounters> ctr;
-    size_t held() const
-    {
-        return mol_len.cap * 4 + counts.cap * 4 + pos_off.cap * 8 + proj_off.cap * 8 + start.cap * 4 + list.cap * 4 + units.cap * 8 + mol_seq.cap + need.cap + proj.cap +
-               pctr.cap * sizeof(PileupCounters) + ctr.cap * sizeof(GappedCounters);
-    }
-    void release()
-    {
-        mol_len.release(); counts.release(); pos_off.release(); proj_off.release(); start.release(); list.release(); units.release(); mol_seq.release(); need.release();
-        proj.release(); pctr.release(); ctr.release();
-    }
-};
-
-struct ConsensusResult {
-    int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
-    int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
-    PileupScratch pile;
-    GappedScratch gapped;
-    DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
-    DevBuf<int32_t> family;
-    DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
-    DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); }
-};
 static const int64_t READS_KEY_CAP_DEFAULT = (int64_t)1 << 26, READS_KEY_CAP_MAX = (int64_t)1 << 30;
 
 // an arm as bit planes (reads_common.h); rc: of its reverse complement
@@ -168,33 +123,7 @@ static void build_sample_table(const char* const* barcodes, int n_samples, int J
     }
 }
 
-static int free_device_bytes(size_t* free_b)
-{
-    size_t total_b = 0;
-    HIP_TRY(hipMemGetInfo(free_b, &total_b));
-    return MIPGEN_OK;
-}
-// the stream is idle when the scope ends, however it ends: the caller's arrays and the host tables behind an asynchronous copy are free from then on
-struct IdleOnExit { hipStream_t s; bool idle = false; hipError_t wait() { idle = true; return hipStreamSynchronize(s); } ~IdleOnExit() { if (!idle) (void)hipStreamSynchronize(s); } };
 struct FreeOnExit { void* p; ~FreeOnExit() { if (p) (void)hipFree(p); } };
-
-// HIP-event time of spans of the stream when timing is on (off: no event is ever created).  mark() before and after a span; add_to(), called once the stream is idle and the
-// call has succeeded, adds the ms of every span to *sum and says how many it added; the destructor destroys the events.
-struct SpanTimer {
-    bool on;
-    hipStream_t st;
-    std::vector<hipEvent_t> ev;                              // (before, after) of every span
-    ~SpanTimer() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    void mark() { hipEvent_t e = nullptr; if (on && (on = hipEventCreate(&e) == hipSuccess)) { ev.push_back(e); (void)hipEventRecord(e, st); } }
-    int add_to(double* sum) const
-    {
-        int n = 0;
-        float ms = 0.f;
-        for (size_t k = 0; on && k + 1 < ev.size(); k += 2)
-            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) { *sum += ms; n++; }
-        return n;
-    }
-};
 
 // The (cell, tag) keys of a plain or samples session, sorted and duplicate-free between feed calls.  A consensus session keeps no list: its `keys` is the scratch
 // k_read_assign writes a chunk's keys to (cap stays 0), and `sort_temp` and `end_bit` serve the sort of its finish.
@@ -830,174 +759,6 @@ int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t*
         if (cell) cell[g] = (int32_t)(keys[g] >> 32);
         if (tag) tag[g] = (uint32_t)keys[g];
     }
-    return MIPGEN_OK;
-}
-
-// Allele counts per template position of one row from the consensus reads the handle holds.  Reads R's groups and reads; writes R->pile only.
-int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, int32_t* counts,
-                                        mipgen_pileup_totals* totals)
-{
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
-    ConsensusResult* R = h->consensus;
-    if (!mol_len) return fail(MIPGEN_E_INVALID, "bad arguments: no molecule lengths");
-    if ((int64_t)n != R->n) return fail(MIPGEN_E_INVALID, "%d molecule lengths: the session that left the consensus reads had %lld probes", n, (long long)R->n);
-    int64_t n_pos = 0, n_units = 0;                                          // template positions; rounds of 64 of them
-    for (int32_t p = 0; p < n; p++) {
-        if (mol_len[p] < 1) return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: a length is 1 or more", mol_len[p], p);
-        n_pos += mol_len[p]; n_units += ((int64_t)mol_len[p] + 63) / 64;
-    }
-    if (row < 0 || (int64_t)row >= R->rows) return fail(MIPGEN_E_INVALID, "row %d: the session had %lld row%s", row, (long long)R->rows, R->rows == 1 ? "" : "s");
-    if (min_family < 1) return fail(MIPGEN_E_INVALID, "min_family %d: 1 or more", min_family);
-    if (min_quality < 0 || min_quality > 40) return fail(MIPGEN_E_INVALID, "min_quality %d: 0 to 40 (the consensus writes 2 to 40)", min_quality);
-    if (n_units > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld template positions: more than 2^31 - 1 rounds of 64", (long long)n_pos);
-    HIP_TRY(hipSetDevice(h->device));
-    h->pileup_ms = -1.0;
-    if (R->n_groups == 0) {                                                  // (no buffer exists: nothing to read, nothing to launch)
-        if (counts) memset(counts, 0, (size_t)n_pos * PILEUP_COLUMNS * sizeof(int32_t));
-        if (totals) *totals = {0, 0, 0, 0};
-        return MIPGEN_OK;
-    }
-    PileupScratch& W = R->pile;
-    auto padded = [](size_t count, size_t size) { return (count + count / 8 + 64) * size; };      // (what DevBuf::reserve asks for at most)
-    const size_t need = padded((size_t)n_pos * PILEUP_COLUMNS, 4) + padded((size_t)n, 4) + padded((size_t)n, 8) + padded((size_t)n + 1, 4) + padded((size_t)n_units, 8) +
-                        padded(1, sizeof(PileupCounters));
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > W.held() + free_b)
-        return fail(MIPGEN_E_NOMEM, "pileup: %lld template positions need %zu MiB of device memory, %zu MiB are free", (long long)n_pos, need >> 20, (W.held() + free_b) >> 20);
-    if (W.counts.reserve((size_t)n_pos * PILEUP_COLUMNS) || W.mol_len.reserve((size_t)n) || W.pos_off.reserve((size_t)n) || W.start.reserve((size_t)n + 1) ||
-        W.units.reserve((size_t)n_units) || W.ctr.reserve(1))
-        return MIPGEN_E_NOMEM;
-    std::vector<int64_t> pos_off((size_t)n);
-    for (int64_t p = 0, at = 0; p < n; at += mol_len[p], p++) pos_off[(size_t)p] = at;
-    hipStream_t st = h->stream;
-    IdleOnExit idle{st};
-    HIP_TRY(hipMemcpyAsync(W.mol_len.p, mol_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(W.pos_off.p, pos_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(PileupCounters), st));
-    SpanTimer pile_time{h->timing, st};
-    pile_time.mark();
-    HIP_TRY(mipgen_launch_pileup_prepare(st, R->keys.p, R->family.p, R->n_groups, (uint32_t)((int64_t)row * R->n), n, W.mol_len.p, min_family, n_units, W.start.p, W.units.p,
-                                         W.ctr.p));
-    pile_time.mark();
-    PileupCounters pc;
-    uint32_t first = 0, last = 0;                                            // the row's groups: [first, last)
-    HIP_TRY(hipMemcpyAsync(&pc, W.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&first, W.start.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&last, W.start.p + n, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t n_small = (int64_t)pc.n_small, n_big = (int64_t)pc.n_big;
-    if (n_small + n_big != n_units) return fail(MIPGEN_E_STATE, "pileup: %lld + %lld rounds listed of %lld", (long long)n_small, (long long)n_big, (long long)n_units);
-    pile_time.mark();
-    HIP_TRY(mipgen_launch_pileup(st, W.units.p, n_units, n_small, n_big, W.mol_len.p, W.pos_off.p, W.start.p, R->family.p, R->ext_off.p, R->lig_off.p, R->ext_seq.p, R->ext_qual.p,
-                                 R->lig_seq.p, R->lig_qual.p, min_family, min_quality, n_pos, W.counts.p, W.ctr.p));
-    pile_time.mark();
-    HIP_TRY(hipMemcpyAsync(&pc, W.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, (size_t)n_pos * PILEUP_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(idle.wait());
-    double ms = 0.0;
-    if (pile_time.add_to(&ms)) h->pileup_ms = ms;
-    if (totals) *totals = {(int64_t)last - (int64_t)first, (int64_t)pc.used, (int64_t)pc.bases, (int64_t)pc.discordant};
-    return MIPGEN_OK;
-}
-
-// The pileup with indels of one row.  Reads R's groups and reads; writes R->gapped only.
-int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
-                                               int32_t max_indel, int32_t* counts, mipgen_gapped_totals* totals)
-{
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
-    ConsensusResult* R = h->consensus;
-    if (!mol_len) return fail(MIPGEN_E_INVALID, "bad arguments: no molecule lengths");
-    if (!mol_seq) return fail(MIPGEN_E_INVALID, "bad arguments: no template bases");
-    if ((int64_t)n != R->n) return fail(MIPGEN_E_INVALID, "%d molecule lengths: the session that left the consensus reads had %lld probes", n, (long long)R->n);
-    int64_t n_pos = 0, n_units = 0;
-    int32_t max_len = 0;
-    for (int32_t p = 0; p < n; p++) {
-        if (mol_len[p] < 1) return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: a length is 1 or more", mol_len[p], p);
-        if (mol_len[p] > MIPGEN_GAPPED_MAX_MOL)
-            return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: the gapped pileup places molecules of at most %d bases", mol_len[p], p, MIPGEN_GAPPED_MAX_MOL);
-        n_pos += mol_len[p]; n_units += ((int64_t)mol_len[p] + 63) / 64; max_len = std::max(max_len, mol_len[p]);
-    }
-    if (row < 0 || (int64_t)row >= R->rows) return fail(MIPGEN_E_INVALID, "row %d: the session had %lld row%s", row, (long long)R->rows, R->rows == 1 ? "" : "s");
-    if (min_family < 1) return fail(MIPGEN_E_INVALID, "min_family %d: 1 or more", min_family);
-    if (min_quality < 0 || min_quality > 40) return fail(MIPGEN_E_INVALID, "min_quality %d: 0 to 40 (the consensus writes 2 to 40)", min_quality);
-    if (max_indel < 1 || max_indel > GAP_MAX_INDEL) return fail(MIPGEN_E_INVALID, "max_indel %d: 1 to %d", max_indel, GAP_MAX_INDEL);
-    if (n_units > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld template positions: more than 2^31 - 1 rounds of 64", (long long)n_pos);
-    HIP_TRY(hipSetDevice(h->device));
-    h->gapped_ms = -1.0;
-    if (R->n_groups == 0) {
-        if (counts) memset(counts, 0, (size_t)n_pos * GAPPED_COLUMNS * sizeof(int32_t));
-        if (totals) *totals = {0, 0, 0, 0, 0, 0, 0, 0};
-        return MIPGEN_OK;
-    }
-    GappedScratch& W = R->gapped;
-    // the budget, before anything is allocated: the row's groups are not known yet, so every buffer that grows with them is taken at the session's groups, and a
-    // projection at the longest template
-    const size_t G = (size_t)R->n_groups;
-    auto padded = [](size_t count, size_t size) { return (count + count / 8 + 64) * size; };      // (what DevBuf::reserve asks for at most)
-    const size_t need = padded((size_t)n_pos * GAPPED_COLUMNS, 4) + padded((size_t)n, 4) + padded((size_t)n, 8) + padded((size_t)n + 1, 4) + padded((size_t)n_units, 8) +
-                        padded((size_t)n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) + padded(2 * G * 3 * (size_t)max_len, 1) +
-                        padded(1, sizeof(PileupCounters)) + padded(1, sizeof(GappedCounters));
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > W.held() + free_b)
-        return fail(MIPGEN_E_NOMEM, "gapped pileup: %lld template positions and %lld groups need up to %zu MiB of device memory, %zu MiB are free", (long long)n_pos,
-                    (long long)R->n_groups, need >> 20, (W.held() + free_b) >> 20);
-    if (W.counts.reserve((size_t)n_pos * GAPPED_COLUMNS) || W.mol_len.reserve((size_t)n) || W.pos_off.reserve((size_t)n) || W.start.reserve((size_t)n + 1) ||
-        W.units.reserve((size_t)n_units) || W.mol_seq.reserve((size_t)n_pos) || W.pctr.reserve(1) || W.ctr.reserve(1))
-        return MIPGEN_E_NOMEM;
-    std::vector<int64_t> pos_off((size_t)n);
-    for (int64_t p = 0, at = 0; p < n; at += mol_len[p], p++) pos_off[(size_t)p] = at;
-    hipStream_t st = h->stream;
-    IdleOnExit idle{st};
-    HIP_TRY(hipMemcpyAsync(W.mol_len.p, mol_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(W.pos_off.p, pos_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(W.mol_seq.p, mol_seq, (size_t)n_pos, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(W.pctr.p, 0, sizeof(PileupCounters), st));
-    HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(GappedCounters), st));
-    SpanTimer gap_time{h->timing, st};
-    const uint32_t cell0 = (uint32_t)((int64_t)row * R->n);
-    gap_time.mark();
-    HIP_TRY(mipgen_launch_pileup_prepare(st, R->keys.p, R->family.p, R->n_groups, cell0, n, W.mol_len.p, min_family, n_units, W.start.p, W.units.p, W.pctr.p));
-    gap_time.mark();
-    PileupCounters pc;
-    GappedCounters gc;
-    memset(&gc, 0, sizeof gc);
-    uint32_t first = 0, last = 0;                                            // the row's groups: [first, last)
-    HIP_TRY(hipMemcpyAsync(&pc, W.pctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&first, W.start.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&last, W.start.p + n, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t n_small = (int64_t)pc.n_small, n_big = (int64_t)pc.n_big, n_row = (int64_t)last - (int64_t)first;
-    if (n_small + n_big != n_units) return fail(MIPGEN_E_STATE, "gapped pileup: %lld + %lld rounds listed of %lld", (long long)n_small, (long long)n_big, (long long)n_units);
-    if (n_row < 0 || n_row > R->n_groups) return fail(MIPGEN_E_STATE, "gapped pileup: groups [%u, %u) of %lld", first, last, (long long)R->n_groups);
-    if (n_row > 0) {
-        if (W.need.reserve(2 * (size_t)n_row) || W.list.reserve(2 * (size_t)n_row) || W.proj_off.reserve(2 * (size_t)n_row)) return MIPGEN_E_NOMEM;
-        gap_time.mark();
-        HIP_TRY(mipgen_launch_gap_list(st, R->keys.p, R->family.p, R->ext_off.p, R->lig_off.p, R->ext_seq.p, R->lig_seq.p, W.mol_seq.p, W.mol_len.p, W.pos_off.p, cell0, first,
-                                       n_row, min_family, max_indel, W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
-        gap_time.mark();
-        HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * 3ull * (unsigned long long)max_len)
-            return fail(MIPGEN_E_STATE, "gapped pileup: %llu sides listed of %lld, %llu projection bytes", gc.n_sides, (long long)(2 * n_row), gc.proj_bytes);
-        if (gc.proj_bytes && W.proj.reserve((size_t)gc.proj_bytes)) return MIPGEN_E_NOMEM;
-    }
-    gap_time.mark();
-    HIP_TRY(mipgen_launch_gapped(st, W.units.p, n_units, n_small, n_big, W.start.p, R->keys.p, R->family.p, R->ext_off.p, R->lig_off.p, R->ext_seq.p, R->ext_qual.p, R->lig_seq.p,
-                                 R->lig_qual.p, W.mol_seq.p, W.mol_len.p, W.pos_off.p, cell0, first, min_family, min_quality, max_indel, max_len, W.list.p, (int64_t)gc.n_sides,
-                                 W.proj_off.p, W.proj.p, n_pos, W.counts.p, W.ctr.p));
-    gap_time.mark();
-    HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, (size_t)n_pos * GAPPED_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(idle.wait());
-    double ms = 0.0;
-    if (gap_time.add_to(&ms)) h->gapped_ms = ms;
-    if (totals)
-        *totals = {n_row, (int64_t)pc.used, (int64_t)gc.bases, (int64_t)gc.discordant, (int64_t)gc.deletions, (int64_t)gc.insertions, (int64_t)gc.ins_discordant,
-                   (int64_t)gc.gapped_sides};
     return MIPGEN_OK;
 }
 

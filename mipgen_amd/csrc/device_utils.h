@@ -44,6 +44,24 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
+__device__ __forceinline__ long long wave_sum_i64(long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// inclusive prefix sum over the wavefront; lane = the caller's lane
+__device__ __forceinline__ uint32_t wave_inclusive_sum_u32(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint32_t u = __shfl_up(v, d);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
 // XCD-aware block remap (8 XCDs, round-robin dispatch): consecutive logical tiles, which share a region's
 // bytes, land on the same XCD's L2.  Bijective for any grid size (cdna_hip_programming.md section 5.5 T1).
 __device__ __forceinline__ int xcd_remap(int b, int n)

@@ -29,6 +29,33 @@ struct KmerParams {
     uint64_t cap_mask;                 // partition capacity - 1 (power of two)
 };
 
+// the consensus reads a handle holds, as the pileup kernels see them
+struct ConsensusView {
+    const uint64_t* __restrict__ keys;        // (cell << 32) | tag of every group, ascending
+    const int32_t* __restrict__ family;
+    const int64_t* __restrict__ ext_off;      // n_groups + 1
+    const int64_t* __restrict__ lig_off;
+    const uint8_t* __restrict__ ext_seq;
+    const uint8_t* __restrict__ ext_qual;
+    const uint8_t* __restrict__ lig_seq;
+    const uint8_t* __restrict__ lig_qual;
+    int64_t n_groups;
+};
+
+// the plan of one row of a pileup: units[0, n_small) are the (probe, round) units of the one-wavefront kernel, units[n_small, n_small + n_big) of
+// the workgroup kernel; the groups of probe p are [start[p], start[p + 1]); its positions lie at pos_off[p] of the n_pos positions of the table
+struct PileRow {
+    const uint2* __restrict__ units;
+    int64_t n_small, n_big;
+    const uint32_t* __restrict__ start;       // n + 1
+    const int32_t* __restrict__ mol_len;      // n
+    const int64_t* __restrict__ pos_off;      // n
+    int32_t n;
+    int64_t n_pos;
+    uint32_t cell0;                           // the row's first cell
+    int min_family, min_quality;
+};
+
 extern "C" {
 // kernels_logistic.hip
 size_t mipgen_logistic_lds_bytes(int span);
@@ -134,20 +161,14 @@ hipError_t mipgen_launch_consensus_len(hipStream_t, int te, int tl, int64_t n_gr
 hipError_t mipgen_launch_consensus_vote(hipStream_t, int te, int tl, int64_t n_groups, const uint32_t* order, int64_t n_small, int64_t n_big, const uint32_t* group_start,
                                         const int32_t* family, const uint32_t* ids, const ConsensusPair* recs, const int64_t* ext_off, const int64_t* lig_off, uint8_t* ext_seq,
                                         uint8_t* ext_qual, uint8_t* lig_seq, uint8_t* lig_qual);
-// kernels_pileup.hip: the cell boundaries of one row, its (cell, round) units and its used groups; then the counts and their sums
-hipError_t mipgen_launch_pileup_prepare(hipStream_t, const uint64_t* keys, const int32_t* family, int64_t n_groups, uint32_t cell0, int32_t n, const int32_t* mol_len,
-                                        int min_family, int64_t n_units, uint32_t* start, uint2* units, PileupCounters* ctr);
-hipError_t mipgen_launch_pileup(hipStream_t, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const int32_t* mol_len, const int64_t* pos_off,
-                                const uint32_t* start, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual,
-                                const uint8_t* lig_seq, const uint8_t* lig_qual, int min_family, int min_quality, int64_t n_pos, int32_t* counts, PileupCounters* ctr);
+// kernels_pileup.hip: the cell boundaries of one row, its (cell, round) units and its used groups (R: cell0, n, mol_len and min_family are read; start, units
+// and ctr are written, ctr zero on entry); then the counts and their sums
+hipError_t mipgen_launch_pileup_prepare(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, uint32_t* start, uint2* units, PileupCounters* ctr);
+hipError_t mipgen_launch_pileup(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, int32_t* counts, PileupCounters* ctr);
 // kernels_gapped.hip: the sides of one row that need the banded alignment; then the alignment, the counts with indels and their sums
 size_t mipgen_gap_align_lds_bytes(int max_len, int W);
-hipError_t mipgen_launch_gap_list(hipStream_t, const uint64_t* keys, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq,
-                                  const uint8_t* lig_seq, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first,
-                                  int64_t n_row_groups, int min_family, int max_indel, uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr);
-hipError_t mipgen_launch_gapped(hipStream_t, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const uint32_t* start, const uint64_t* keys,
-                                const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual, const uint8_t* lig_seq,
-                                const uint8_t* lig_qual, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first, int min_family,
-                                int min_quality, int max_indel, int max_len, const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int64_t n_pos,
-                                int32_t* counts, GappedCounters* ctr);
+hipError_t mipgen_launch_gap_list(hipStream_t, const ConsensusView& C, const PileRow& R, const uint8_t* mol_seq, uint32_t g_first, int64_t n_row_groups, int max_indel,
+                                  uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr);
+hipError_t mipgen_launch_gapped(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, const uint8_t* mol_seq, uint32_t g_first, int max_indel, int max_len,
+                                const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int32_t* counts, GappedCounters* ctr);
 }

@@ -16,37 +16,20 @@
 //                 handed out by __shfl, so no row waits for memory.  The in-row dependency is a prefix maximum of V + 2 d over the 32 lanes (five __shfl_up
 //                 steps of width 32).  Per row two words of directions (two ballots) go to LDS: 8 bytes per row and side.  Then the 32 lanes reduce the end
 //                 key, lane 0 walks back and writes the projection of the consumed columns, and the half fills the rest.
-//  k_gapped_wave  k_pileup_wave / k_pileup_wg with eight counters: lanes over template positions, a loop over the cell's groups; a side with a projection is
-//  k_gapped_wg    read from it (base, quality and insertion byte at t), any other from its consensus read.  32 bytes per position, two 16-byte stores, no atomic.
-//  k_gapped_sum   the column sums, as k_pileup_sum.
-#include "kernels.h"
+//  GapPile        the vote of the gapped table, plugged into the count frame of pileup_frame.h: k_gapped_wave = k_pile_wave<GapPile, GapProj>, k_gapped_wg =
+//                 k_pile_wg<GapPile, GapProj>, k_gapped_sum = k_pile_sum<GapPile>.  Eight counters; a side with a projection is read from it (base, quality and
+//                 insertion byte at t), any other from its consensus read.  32 bytes per position, two 16-byte stores.  Column sums: bases (columns 0..3),
+//                 discordant, deletions, insertions, ins_discordant (columns 4..7).
+#include "pileup_frame.h"
 #include "gapped_align.h"
 
 struct GapIn {
-    const uint64_t* __restrict__ keys;
-    const int32_t* __restrict__ family;
-    const int64_t* __restrict__ ext_off;
-    const int64_t* __restrict__ lig_off;
-    const uint8_t* __restrict__ ext_seq;
-    const uint8_t* __restrict__ ext_qual;
-    const uint8_t* __restrict__ lig_seq;
-    const uint8_t* __restrict__ lig_qual;
-    const uint8_t* __restrict__ mol_seq;      // the templates, concatenated: probe p at pos_off[p]
-    const int32_t* __restrict__ mol_len;
-    const int64_t* __restrict__ pos_off;
-    uint32_t cell0, g_first;                  // the row's first cell; its first group
-    int min_family, min_quality, W;
+    ConsensusView C;
+    PileRow R;
+    const uint8_t* __restrict__ mol_seq;      // the templates, concatenated: probe p at R.pos_off[p]
+    uint32_t g_first;                         // the row's first group
+    int W;
 };
-
-__device__ static inline uint32_t gap_wave_sum(uint32_t v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 
 // need[2 gi + side] for the row's groups gi = g - g_first
 __global__ __launch_bounds__(256) void k_gap_screen(GapIn I, int64_t n_row_groups, uint8_t* __restrict__ need)
@@ -55,14 +38,14 @@ __global__ __launch_bounds__(256) void k_gap_screen(GapIn I, int64_t n_row_group
     if (gi >= n_row_groups) return;                                                         // (wave-uniform)
     const int lane = threadIdx.x & 63;
     const uint32_t g = I.g_first + (uint32_t)gi;
-    const uint32_t p = (uint32_t)(I.keys[g] >> 32) - I.cell0;
-    const int L = I.mol_len[p];
-    const uint8_t* __restrict__ M = I.mol_seq + I.pos_off[p];
-    const bool used = I.family[g] >= I.min_family;
+    const uint32_t p = (uint32_t)(I.C.keys[g] >> 32) - I.R.cell0;
+    const int L = I.R.mol_len[p];
+    const uint8_t* __restrict__ M = I.mol_seq + I.R.pos_off[p];
+    const bool used = I.C.family[g] >= I.R.min_family;
     for (int side = 0; side < 2; side++) {
-        const int64_t o = side ? I.lig_off[g] : I.ext_off[g];
-        const int m = (int)((side ? I.lig_off[g + 1] : I.ext_off[g + 1]) - o);
-        const uint8_t* __restrict__ q = (side ? I.lig_seq : I.ext_seq) + o;
+        const int64_t o = side ? I.C.lig_off[g] : I.C.ext_off[g];
+        const int m = (int)((side ? I.C.lig_off[g + 1] : I.C.ext_off[g + 1]) - o);
+        const uint8_t* __restrict__ q = (side ? I.C.lig_seq : I.C.ext_seq) + o;
         const int k = used ? min(m, L) : 0;
         bool differs = false;
         for (int x0 = 0; x0 < k && !differs; x0 += 64) {                                    // (differs is the wavefront's: it comes from a ballot)
@@ -87,9 +70,9 @@ __global__ __launch_bounds__(256) void k_gap_list(GapIn I, int64_t n_row_sides, 
     uint32_t bytes = 0;
     if (listed) {
         const uint32_t g = I.g_first + (uint32_t)(s >> 1);
-        bytes = 3u * (uint32_t)I.mol_len[(uint32_t)(I.keys[g] >> 32) - I.cell0];
+        bytes = 3u * (uint32_t)I.R.mol_len[(uint32_t)(I.C.keys[g] >> 32) - I.R.cell0];
     }
-    const uint32_t in = gap_wave_sum(listed ? 1u : 0u, lane), ib = gap_wave_sum(bytes, lane);       // (at most 64 x 3 x GAP_MAX_MOL bytes per wavefront)
+    const uint32_t in = wave_inclusive_sum_u32(listed ? 1u : 0u, lane), ib = wave_inclusive_sum_u32(bytes, lane);       // (at most 64 x 3 x GAP_MAX_MOL bytes per wavefront)
     const uint32_t tn = __shfl(in, 63), tb = __shfl(ib, 63);
     unsigned long long bn = 0, bb = 0;
     if (lane == 0 && tn) { bn = atomicAdd(&ctr->n_sides, (unsigned long long)tn); bb = atomicAdd(&ctr->proj_bytes, (unsigned long long)tb); }
@@ -112,13 +95,13 @@ __global__ __launch_bounds__(64) void k_gap_align(const uint32_t* __restrict__ l
     const uint32_t s = list[live ? slot : 0];                                               // (a half without a side reads slot 0 and does nothing with it)
     const uint32_t g = I.g_first + (s >> 1);
     const int side = (int)(s & 1u);
-    const uint32_t p = (uint32_t)(I.keys[g] >> 32) - I.cell0;
-    const int L = I.mol_len[p];
-    const uint8_t* __restrict__ M = I.mol_seq + I.pos_off[p];
-    const int64_t qo = side ? I.lig_off[g] : I.ext_off[g];
-    const int m = live ? (int)((side ? I.lig_off[g + 1] : I.ext_off[g + 1]) - qo) : 0;
-    const uint8_t* __restrict__ q = (side ? I.lig_seq : I.ext_seq) + qo;
-    const uint8_t* __restrict__ qq = (side ? I.lig_qual : I.ext_qual) + qo;
+    const uint32_t p = (uint32_t)(I.C.keys[g] >> 32) - I.R.cell0;
+    const int L = I.R.mol_len[p];
+    const uint8_t* __restrict__ M = I.mol_seq + I.R.pos_off[p];
+    const int64_t qo = side ? I.C.lig_off[g] : I.C.ext_off[g];
+    const int m = live ? (int)((side ? I.C.lig_off[g + 1] : I.C.ext_off[g + 1]) - qo) : 0;
+    const uint8_t* __restrict__ q = (side ? I.C.lig_seq : I.C.ext_seq) + qo;
+    const uint8_t* __restrict__ qq = (side ? I.C.lig_qual : I.C.ext_qual) + qo;
     const int rows = min(min(m, L + W), rows_cap);                                          // rows beyond L + W lie outside the band; (rows_cap >= L + W: the host's)
     const int rows_all = max(rows, __shfl_xor(rows, 32));
     uint32_t* dirs = gap_dirs + (size_t)half * (size_t)rows_cap * 2;
@@ -184,20 +167,8 @@ __global__ __launch_bounds__(64) void k_gap_align(const uint32_t* __restrict__ l
 #define GAP_CLASS_NONE 5u
 #define GAP_CLASS_DISC 6u
 
-struct GapPile {
-    int a = 0, c = 0, g = 0, t = 0, disc = 0, del = 0, ins = 0, insd = 0;
-    // the vote of one molecule at one position and at the anchor behind it (DESIGN 4.13): ce / cl - each side's usable observation (0..3, del, none), ve / vl -
-    // the side covers the anchor (t, t + 1), ne / nl - its insertion length there
-    __device__ inline void add(bool ok, uint32_t ce, uint32_t cl, bool ve, bool vl, uint32_t ne, uint32_t nl)
-    {
-        const bool ue = ok && ce < GAP_CLASS_NONE, ul = ok && cl < GAP_CLASS_NONE;
-        const uint32_t col = ue && ul && ce != cl ? GAP_CLASS_DISC : ue ? ce : ul ? cl : GAP_CLASS_NONE;
-        a += col == 0u; c += col == 1u; g += col == 2u; t += col == 3u; del += col == GAP_CLASS_DEL; disc += col == GAP_CLASS_DISC;
-        const bool xe = ok && ve, xl = ok && vl;
-        ins += xe && xl ? (ne == nl && ne > 0u) : xe ? ne > 0u : xl ? nl > 0u : false;
-        insd += xe && xl && ne != nl;
-    }
-};
+// where the count finds the projections: proj_off[2 (g - g_first) + side] into proj, or -1
+struct GapProj { uint32_t g_first; const int64_t* __restrict__ off; const uint8_t* __restrict__ bytes; };
 
 // one side of group g at template position t (t < L, or t == L for a lane beyond the template: its index is clamped and its value discarded).  po is the
 // wavefront's: a side with a projection (po >= 0) or without.  idx: the index of t in the consensus read (t itself, or L - 1 - t on the ligation side).
@@ -223,95 +194,43 @@ __device__ static inline void gap_observe(const uint8_t* __restrict__ proj, int6
     }
 }
 
-__device__ static inline void gap_pile_groups(GapPile& S, const GapIn& I, const int64_t* __restrict__ proj_off, const uint8_t* __restrict__ proj, uint32_t g0, uint32_t g1,
-                                              uint32_t stride, int t, int L)
-{
-    for (uint32_t g = g0; g < g1; g += stride) {
-        const int64_t eo = I.ext_off[g], lo = I.lig_off[g];
-        const int el = (int)(I.ext_off[g + 1] - eo), ll = (int)(I.lig_off[g + 1] - lo);
-        const int64_t pe = proj_off[2 * (size_t)(g - I.g_first)], pl = proj_off[2 * (size_t)(g - I.g_first) + 1];
-        uint32_t ce, cl, ne, nl;
-        bool ve, vl;
-        gap_observe(proj, pe, I.ext_seq, I.ext_qual, eo, el, t, t, L, false, I.min_quality, ce, ve, ne);
-        gap_observe(proj, pl, I.lig_seq, I.lig_qual, lo, ll, L - 1 - t, t, L, true, I.min_quality, cl, vl, nl);
-        S.add(I.family[g] >= I.min_family, ce, cl, ve, vl, ne, nl);
+struct GapPile {
+    static constexpr int COLUMNS = GAPPED_COLUMNS;
+    using Counters = GappedCounters;
+    static constexpr ColumnSum<GappedCounters> SUMS[5] = {{0, 4, &GappedCounters::bases}, {4, 5, &GappedCounters::discordant}, {5, 6, &GappedCounters::deletions},
+                                                          {6, 7, &GappedCounters::insertions}, {7, 8, &GappedCounters::ins_discordant}};
+    int n[COLUMNS] = {0, 0, 0, 0, 0, 0, 0, 0};                                              // A, C, G, T, discordant, del, ins, ins_discordant
+    // the vote of one molecule at one position and at the anchor behind it (DESIGN 4.13): ce / cl - each side's usable observation (0..3, del, none), ve / vl -
+    // the side covers the anchor (t, t + 1), ne / nl - its insertion length there
+    __device__ inline void add(bool ok, uint32_t ce, uint32_t cl, bool ve, bool vl, uint32_t ne, uint32_t nl)
+    {
+        const bool ue = ok && ce < GAP_CLASS_NONE, ul = ok && cl < GAP_CLASS_NONE;
+        const uint32_t col = ue && ul && ce != cl ? GAP_CLASS_DISC : ue ? ce : ul ? cl : GAP_CLASS_NONE;
+        n[0] += col == 0u; n[1] += col == 1u; n[2] += col == 2u; n[3] += col == 3u; n[5] += col == GAP_CLASS_DEL; n[4] += col == GAP_CLASS_DISC;
+        const bool xe = ok && ve, xl = ok && vl;
+        n[6] += xe && xl ? (ne == nl && ne > 0u) : xe ? ne > 0u : xl ? nl > 0u : false;
+        n[7] += xe && xl && ne != nl;
     }
-}
-
-__device__ static inline void gap_store(int32_t* __restrict__ o, const GapPile& S)
-{
-    int4* __restrict__ v = reinterpret_cast<int4*>(o);                                      // (32 bytes per position, the table 256-byte aligned)
-    v[0] = make_int4(S.a, S.c, S.g, S.t);
-    v[1] = make_int4(S.disc, S.del, S.ins, S.insd);
-}
-
-__global__ __launch_bounds__(256) void k_gapped_wave(const uint2* __restrict__ units, int64_t n_units, const uint32_t* __restrict__ start, GapIn I,
-                                                     const int64_t* __restrict__ proj_off, const uint8_t* __restrict__ proj, int32_t* __restrict__ counts)
-{
-    const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (k >= n_units) return;                                                               // (wave-uniform)
-    const int lane = threadIdx.x & 63;
-    const uint2 unit = units[k];
-    const uint32_t p = __builtin_amdgcn_readfirstlane(unit.x), r = __builtin_amdgcn_readfirstlane(unit.y);
-    const int len = I.mol_len[p];
-    const int t = (int)min((int64_t)r * 64 + lane, (int64_t)len);
-    GapPile S;
-    gap_pile_groups(S, I, proj_off, proj, start[p], start[p + 1], 1u, t, len);
-    if (t < len) gap_store(counts + (I.pos_off[p] + t) * GAPPED_COLUMNS, S);
-}
-
-__global__ __launch_bounds__(256) void k_gapped_wg(const uint2* __restrict__ units, const uint32_t* __restrict__ start, GapIn I, const int64_t* __restrict__ proj_off,
-                                                   const uint8_t* __restrict__ proj, int32_t* __restrict__ counts)
-{
-    __shared__ int part[3][GAPPED_COLUMNS][64];                                             // the counters of wavefronts 1..3: 6,144 bytes
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint2 unit = units[blockIdx.x];
-    const uint32_t p = unit.x, r = unit.y;
-    const int len = I.mol_len[p];
-    const int t = (int)min((int64_t)r * 64 + lane, (int64_t)len);
-    GapPile S;
-    gap_pile_groups(S, I, proj_off, proj, start[p] + wave, start[p + 1], 4u, t, len);
-    if (wave) {
-        int (*w)[64] = part[wave - 1];
-        w[0][lane] = S.a; w[1][lane] = S.c; w[2][lane] = S.g; w[3][lane] = S.t; w[4][lane] = S.disc; w[5][lane] = S.del; w[6][lane] = S.ins; w[7][lane] = S.insd;
-    }
-    __syncthreads();
-    if (wave == 0 && t < len) {
-#pragma unroll
-        for (int w = 0; w < 3; w++) {
-            S.a += part[w][0][lane]; S.c += part[w][1][lane]; S.g += part[w][2][lane]; S.t += part[w][3][lane];
-            S.disc += part[w][4][lane]; S.del += part[w][5][lane]; S.ins += part[w][6][lane]; S.insd += part[w][7][lane];
+    __device__ static inline void groups(GapPile& S, const ConsensusView& I, const PileRow& R, uint32_t g0, uint32_t g1, uint32_t stride, int t, int L, const GapProj& P)
+    {
+        for (uint32_t g = g0; g < g1; g += stride) {
+            const int64_t eo = I.ext_off[g], lo = I.lig_off[g];
+            const int el = (int)(I.ext_off[g + 1] - eo), ll = (int)(I.lig_off[g + 1] - lo);
+            const int64_t pe = P.off[2 * (size_t)(g - P.g_first)], pl = P.off[2 * (size_t)(g - P.g_first) + 1];
+            uint32_t ce, cl, ne, nl;
+            bool ve, vl;
+            gap_observe(P.bytes, pe, I.ext_seq, I.ext_qual, eo, el, t, t, L, false, R.min_quality, ce, ve, ne);
+            gap_observe(P.bytes, pl, I.lig_seq, I.lig_qual, lo, ll, L - 1 - t, t, L, true, R.min_quality, cl, vl, nl);
+            S.add(I.family[g] >= R.min_family, ce, cl, ve, vl, ne, nl);
         }
-        gap_store(counts + (I.pos_off[p] + t) * GAPPED_COLUMNS, S);
     }
-}
-
-__device__ static inline long long gap_wave_sum_i64(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_gapped_sum(const int32_t* __restrict__ counts, int64_t n_pos, GappedCounters* __restrict__ ctr)
-{
-    long long s[5] = {0, 0, 0, 0, 0};                                                       // bases, discordant, del, ins, ins_discordant
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pos; i += (int64_t)gridDim.x * blockDim.x) {
-        const int4* __restrict__ v = reinterpret_cast<const int4*>(counts + i * GAPPED_COLUMNS);
-        const int4 x = v[0], y = v[1];
-        s[0] += (long long)x.x + x.y + x.z + x.w; s[1] += y.x; s[2] += y.y; s[3] += y.z; s[4] += y.w;
+    __device__ inline void store(int32_t* __restrict__ o) const
+    {
+        int4* __restrict__ v = reinterpret_cast<int4*>(o);                                  // (32 bytes per position, the table 256-byte aligned)
+        v[0] = make_int4(n[0], n[1], n[2], n[3]);
+        v[1] = make_int4(n[4], n[5], n[6], n[7]);
     }
-#pragma unroll
-    for (int k = 0; k < 5; k++) s[k] = gap_wave_sum_i64(s[k]);
-    if ((threadIdx.x & 63) == 0) {
-        if (s[0]) atomicAdd(&ctr->bases, (unsigned long long)s[0]);
-        if (s[1]) atomicAdd(&ctr->discordant, (unsigned long long)s[1]);
-        if (s[2]) atomicAdd(&ctr->deletions, (unsigned long long)s[2]);
-        if (s[3]) atomicAdd(&ctr->insertions, (unsigned long long)s[3]);
-        if (s[4]) atomicAdd(&ctr->ins_discordant, (unsigned long long)s[4]);
-    }
-}
+};
 
 extern "C" {
 
@@ -319,35 +238,28 @@ size_t mipgen_gap_align_lds_bytes(int max_len, int W) { return (size_t)2 * (size
 
 // the sides of the row's groups [g_first, g_first + n_row_groups) that need the dynamic program: list[0, ctr->n_sides), proj_off[2 n_row_groups] (-1: no
 // projection), ctr->proj_bytes; ctr is zero on entry
-hipError_t mipgen_launch_gap_list(hipStream_t st, const uint64_t* keys, const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq,
-                                  const uint8_t* lig_seq, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first,
-                                  int64_t n_row_groups, int min_family, int max_indel, uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr)
+hipError_t mipgen_launch_gap_list(hipStream_t st, const ConsensusView& C, const PileRow& R, const uint8_t* mol_seq, uint32_t g_first, int64_t n_row_groups, int max_indel,
+                                  uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr)
 {
     if (n_row_groups < 1 || n_row_groups > 0x3fffffff || max_indel < 1 || max_indel > GAP_MAX_INDEL) return hipErrorInvalidValue;
-    const GapIn I{keys, family, ext_off, lig_off, ext_seq, nullptr, lig_seq, nullptr, mol_seq, mol_len, pos_off, cell0, g_first, min_family, 0, max_indel};
+    const GapIn I{C, R, mol_seq, g_first, max_indel};
     hipLaunchKernelGGL(k_gap_screen, dim3((unsigned)((n_row_groups + 3) / 4)), dim3(256), 0, st, I, n_row_groups, need);
     hipLaunchKernelGGL(k_gap_list, dim3((unsigned)((2 * n_row_groups + 255) / 256)), dim3(256), 0, st, I, 2 * n_row_groups, need, list, proj_off, ctr);
     return hipGetLastError();
 }
 
-// the alignment of the n_sides listed sides into proj, then counts[n_pos][8] written whole and summed into ctr
-hipError_t mipgen_launch_gapped(hipStream_t st, const uint2* units, int64_t n_units, int64_t n_small, int64_t n_big, const uint32_t* start, const uint64_t* keys,
-                                const int32_t* family, const int64_t* ext_off, const int64_t* lig_off, const uint8_t* ext_seq, const uint8_t* ext_qual, const uint8_t* lig_seq,
-                                const uint8_t* lig_qual, const uint8_t* mol_seq, const int32_t* mol_len, const int64_t* pos_off, uint32_t cell0, uint32_t g_first, int min_family,
-                                int min_quality, int max_indel, int max_len, const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int64_t n_pos,
-                                int32_t* counts, GappedCounters* ctr)
+// the alignment of the n_sides listed sides into proj, then counts[R.n_pos][8] written whole and summed into ctr
+hipError_t mipgen_launch_gapped(hipStream_t st, const ConsensusView& C, const PileRow& R, int64_t n_units, const uint8_t* mol_seq, uint32_t g_first, int max_indel, int max_len,
+                                const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int32_t* counts, GappedCounters* ctr)
 {
-    if (n_small < 0 || n_big < 0 || n_small + n_big != n_units || n_units > 0x7fffffff || n_pos < 1 || n_sides < 0 || n_sides > 0x7fffffff || max_indel < 1 ||
+    if (R.n_small < 0 || R.n_big < 0 || R.n_small + R.n_big != n_units || n_units > 0x7fffffff || R.n_pos < 1 || n_sides < 0 || n_sides > 0x7fffffff || max_indel < 1 ||
         max_indel > GAP_MAX_INDEL || max_len < 1 || max_len > GAP_MAX_MOL)
         return hipErrorInvalidValue;
-    const GapIn I{keys, family, ext_off, lig_off, ext_seq, ext_qual, lig_seq, lig_qual, mol_seq, mol_len, pos_off, cell0, g_first, min_family, min_quality, max_indel};
+    const GapIn I{C, R, mol_seq, g_first, max_indel};
     if (n_sides > 0)
         hipLaunchKernelGGL(k_gap_align, dim3((unsigned)((n_sides + 1) / 2)), dim3(64), mipgen_gap_align_lds_bytes(max_len, max_indel), st, list, n_sides, proj_off, proj, I,
                            max_len + max_indel, ctr);
-    if (n_small > 0) hipLaunchKernelGGL(k_gapped_wave, dim3((unsigned)((n_small + 3) / 4)), dim3(256), 0, st, units, n_small, start, I, proj_off, proj, counts);
-    if (n_big > 0) hipLaunchKernelGGL(k_gapped_wg, dim3((unsigned)n_big), dim3(256), 0, st, units + n_small, start, I, proj_off, proj, counts);
-    hipLaunchKernelGGL(k_gapped_sum, dim3((unsigned)std::min<int64_t>((n_pos + 255) / 256, 2048)), dim3(256), 0, st, counts, n_pos, ctr);
-    return hipGetLastError();
+    return pile_launch<GapPile>(st, C, R, counts, ctr, GapProj{g_first, proj_off, proj});
 }
 
 }

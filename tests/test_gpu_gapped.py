@@ -198,6 +198,42 @@ def test_rows_and_independence_of_the_two_calls(acc, genome):
         assert np.array_equal(plain[0], PR.pileup(want, lens, len(arms), r)[0])
 
 
+def shared_frame_lane(rng, genome):
+    """Two probes of 64 and 65 bases (one round; two, the second of one position); a cell above the workgroup threshold and a small one; a one-base deletion
+    in six molecules of the first cell and two of the second."""
+    mols, arms = cut_probes(genome, [64, 65])
+    sizes = [WG + 1, 3]
+    L = Lane(rng)
+    for M, s in zip(mols, sizes):
+        for k in range(s):
+            if k % 50 == 1 or (s == 3 and k == 2):
+                Mv = plant(M, "del", ARM + 5 + k % 20, 1, rng)
+                variant(L, M, Mv, Mv, len(Mv), len(Mv))
+            else:
+                L.molecule(M, len(M), len(M) - 2 * (k % 3))
+    return mols, arms, sizes, L.shuffled()
+
+
+def test_the_two_tables_share_code_but_not_state(acc, genome):
+    """One handle, the ungapped call, the gapped call, the ungapped call again: both ungapped tables are byte for byte the oracle's, the gapped table is its
+    oracle's, totals included.  The cell of 257 molecules takes the workgroup frame in both instantiations, the cell of 3 the one-wavefront frame."""
+    mols, arms, sizes, cols = shared_frame_lane(np.random.default_rng(509), genome)
+    got, want = session(acc, arms, cols, chunks=2)
+    assert got == want and [sum(1 for g in got if g[0] == p) for p in range(2)] == sizes
+    lens = [len(m) for m in mols]
+    first = acc.consensus_pileup(lens, 0)
+    gapped = acc.consensus_pileup_gapped(mols, lens, 0, 1, 0, 4)
+    again = acc.consensus_pileup(lens, 0)
+    w_counts, w_totals = PR.pileup(want, lens, 2, 0)
+    assert first[0].dtype == again[0].dtype == w_counts.dtype == np.int32
+    assert first[0].tobytes() == again[0].tobytes() == w_counts.tobytes()
+    assert first[1] == again[1] == w_totals
+    g_counts, g_totals = G.pileup(want, mols, 2, 0, 1, 0, 4)
+    assert gapped[0].dtype == np.int32 and gapped[0].tobytes() == g_counts.tobytes()
+    assert gapped[1] == g_totals and tuple(gapped[1]) == KEYS
+    assert g_totals["groups"] == WG + 4 and g_totals["deletions"] == 8 and g_totals["gapped_sides"] == 16 and w_totals["discordant"] > g_totals["discordant"] == 0
+
+
 def test_the_substitution_only_lane(acc, genome):
     """On molecules with sparse substitutions only, columns 0-4 are the ungapped call's and columns 5-7 are zero."""
     rng = np.random.default_rng(457)
