@@ -238,6 +238,27 @@ def gapped_host(tmp_path_factory):
     return exe
 
 
+def host_against_oracle(gapped_host, tmp_path, cases, more_than):
+    """Every (q, M, W, side) through the stand-alone program: end cell, score, path, projected bases and insertion bytes equal the oracle's; there are more than
+    `more_than` of them.  Returns the number of cases whose path holds a gap."""
+    with open(tmp_path / "cases.txt", "w") as fh:
+        fh.write("".join(f"{q.decode()} {M.decode()} {W} {side}\n" for q, M, W, side in cases))
+    p = subprocess.run([gapped_host, str(tmp_path / "cases.txt")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    got = p.stdout.decode().splitlines()
+    assert len(got) == len(cases) > more_than
+    gapped = 0
+    for (q, M, W, side), line in zip(cases, got):
+        ie, je, h, path, bases, ins = line.split()
+        want = G.align(q, M if side == EXT else G.revcomp(M), W, side)
+        assert (int(ie), int(je), int(h), path) == want, (q, M, W, side)
+        obs, w_ins, gaps = G.side_view(q, b"I" * len(q), M, W, side)
+        assert bases == "".join(chr(obs[t][0]) if t in obs else "." for t in range(len(M))), (q, M, W, side)
+        assert ins == ",".join(str(w_ins.get(t, 255)) for t in range(len(M))), (q, M, W, side)
+        gapped += gaps > 0
+    return gapped
+
+
 def test_the_host_functions_of_the_header_equal_the_oracle(gapped_host, tmp_path):
     from mipgen_amd import synth
     rng = np.random.default_rng(461)
@@ -257,22 +278,27 @@ def test_the_host_functions_of_the_header_equal_the_oracle(gapped_host, tmp_path
             at, n = int(rng.integers(0, len(q))), int(rng.integers(1, W + 2))
             q = plant(q, "del" if rng.random() < 0.5 else "ins", at, n, rng) or b"A"
         cases.append((q, M, W, side))
-    with open(tmp_path / "cases.txt", "w") as fh:
-        fh.write("".join(f"{q.decode()} {M.decode()} {W} {side}\n" for q, M, W, side in cases))
-    p = subprocess.run([gapped_host, str(tmp_path / "cases.txt")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    got = p.stdout.decode().splitlines()
-    assert len(got) == len(cases) > 1500
-    gapped = 0
-    for (q, M, W, side), line in zip(cases, got):
-        ie, je, h, path, bases, ins = line.split()
-        want = G.align(q, M if side == EXT else G.revcomp(M), W, side)
-        assert (int(ie), int(je), int(h), path) == want, (q, M, W, side)
-        obs, w_ins, gaps = G.side_view(q, b"I" * len(q), M, W, side)
-        assert bases == "".join(chr(obs[t][0]) if t in obs else "." for t in range(len(M))), (q, M, W, side)
-        assert ins == ",".join(str(w_ins.get(t, 255)) for t in range(len(M))), (q, M, W, side)
-        gapped += gaps > 0
+    gapped = host_against_oracle(gapped_host, tmp_path, cases, 1500)
     assert gapped > 800
+
+
+def test_the_shared_generator_cases_equal_the_oracle_on_the_host(gapped_host, tmp_path):
+    """The cases tests/test_gpu_gapped_shapes.py sends to the device, through the host functions under the sanitizers: the sides of tests/gapped_cases.py - low
+    complexity templates, several edits, N and lower case matched and unmatched, short and long reads - and the sides of the very molecules the device's test
+    (a) piles up, at every W it uses.  A case that passes here and fails there fails in the kernel's lanes, not in the shared pieces."""
+    from tests import gapped_cases as GC
+    cases = GC.side_cases(547, 600)
+    kinds = {k: 0 for k in GC.PATH_KINDS}
+    for q, M, W, side in cases:
+        for k in GC.path_kinds(q, M, W, side, want_preference=False):
+            kinds[k] += 1
+    assert all(kinds[k] >= 30 for k in GC.PATH_KINDS[:4]), kinds
+    assert sum(1 for q, M, _, _ in cases if set(M) - set(b"ACGT")) > 100 and sum(1 for q, M, _, _ in cases if any(c in b"acgt" for c in q)) > 10
+    for n, probe in enumerate(GC.probes(GC.SESSION_SEED, GC.SESSION_LENGTHS)):
+        for k, (e, l, _family) in enumerate(probe.molecules):
+            if (n + k) % 4 == 0:                                                      # a quarter of the session's molecules, both sides
+                cases += [(q, probe.M, W, side) for q, side in ((e, EXT), (l, LIG)) for W in (1, 4, 15) if GC.listed(q, probe.M, side)]
+    assert host_against_oracle(gapped_host, tmp_path, cases, 1000) > 500
 
 
 # ---- the command line, before the device is opened ------------------------------------------------------------------------------------------------------
