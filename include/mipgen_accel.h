@@ -444,6 +444,43 @@ typedef struct mipgen_gapped_totals { int64_t groups, used, bases, discordant, d
 int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
                                                int32_t max_indel, int32_t* counts, mipgen_gapped_totals* totals);
 
+/* ---- variant calls from the pileup against a background of the other samples (new entry points only: the ABI number does not change) ----
+ * The model.  Allele classes: A, C, G, T (0..3) and, in the gapped table, del (4).  At position x with ref = upper(template byte) one of A C G T,
+ * an alt allele a is any class but ref (insertions are not called); depth n = A + C + G + T (+ del), alt count k = counts[x][a].  The POOL holds per (x, a) the sums
+ * K, N of k', n' over the sample rows that qualify there (n' > 0 and k' 10^6 <= bg_max_ppm n'); sample rows are all rows of the session but the last
+ * (undetermined) when it has barcodes, the one row otherwise.  For the row being called K_o = K - k, N_o = N - n when it is itself a qualifying sample row, else K, N.
+ * Error rate e = (K_o + a0) / (N_o + n0).  A cell is a CANDIDATE iff min_depth <= n <= MIPGEN_CALL_MAX_DEPTH, k >= min_alt, k 10^6 >= min_ppm n and
+ * k (N_o + n0) > n (K_o + a0); its score is Q = min(9999, floor(-10 log10 P)), P the binomial tail sum_{i >= k} C(n,i) e^i (1-e)^(n-i); it is a CALL iff Q >= min_q.
+ * Records come in ascending (pos, allele); two calls on the same input return the same bytes.  totals: tested = positions with a usable ref and
+ * min_depth <= n <= the cap; too_deep = those above the cap (not tested); candidates; calls.
+ *   call_tables:          from host arrays, no read session needed: counts[n_pos][columns] (columns 5: the pileup's table, 8: the gapped one), pool[n_pos][10] int32
+ *                         (K[5] then N[5] per position), ref[n_pos] bytes; own_row_is_sample != 0: the row is part of the pool (leave-one-out applies).
+ *   consensus_call_pool:  the pileup of every sample row of the session (max_indel 0: mipgen_accel_reads_consensus_pileup's table; 1..15: the gapped one) into a
+ *                         scratch of its own, pooled on the device.  The pool stays with the consensus reads and remembers these arguments.  mol_seq is required
+ *                         (it supplies the ref bytes; for max_indel > 0 it is the gapped call's mol_seq, upper case).
+ *   consensus_call:       recomputes the pileup of `row` (any row, undetermined included) with the pool's arguments - counts (may be NULL) is what the matching
+ *                         pileup call returns - then flags, scores and orders its calls.
+ *   call_fetch:           the records of the last call of either kind; n must equal its totals.calls.
+ *   call_pileup_totals:   the pileup totals of the row consensus_call counted last.
+ * MIPGEN_E_INVALID: every refusal of the underlying pileup call; NULL counts / pool / ref / params; columns not 5 or 8; n_pos outside 1..2^29 - 1; max_indel
+ * outside 0..15; min_depth < 1; min_alt < 1; min_ppm or bg_max_ppm outside 0..10^6; min_q outside 0..9999; a prior outside 0 < a0 < n0 <= 2^30; fetch with n
+ * different from the last totals.calls.  MIPGEN_E_STATE: no consensus reads; consensus_call without a pool, or with params.bg_max_ppm different from the pool's;
+ * fetch before any call.  MIPGEN_E_NOMEM: the pool (40 bytes per position), the counts, the ref bytes and the candidate list at its worst case (4 per position)
+ * against free device memory.  Every check comes before any allocation or launch. */
+#define MIPGEN_CALL_MAX_DEPTH (1 << 20)
+typedef struct mipgen_call_params { int32_t min_depth, min_alt, min_ppm, min_q, a0, n0, bg_max_ppm; } mipgen_call_params;
+typedef struct mipgen_call_record { int64_t pos; int32_t allele, depth, alt, bg_alt, bg_depth, q; } mipgen_call_record;
+typedef struct mipgen_call_totals { int64_t tested, too_deep, candidates, calls; } mipgen_call_totals;
+int mipgen_accel_call_tables(mipgen_accel* h, const int32_t* counts, int32_t columns, const int32_t* pool, const uint8_t* ref, int64_t n_pos, int32_t own_row_is_sample,
+                             const mipgen_call_params* params, mipgen_call_totals* totals);
+int mipgen_accel_reads_consensus_call_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                           int32_t max_indel, int32_t bg_max_ppm);
+int mipgen_accel_reads_consensus_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, mipgen_call_totals* totals);
+int mipgen_accel_call_fetch(mipgen_accel* h, mipgen_call_record* records, int64_t n);
+/* The totals the matching pileup call would have returned for the row of the last mipgen_accel_reads_consensus_call (the ungapped table fills groups, used, bases,
+ * discordant and leaves the rest 0): a caller that writes the pileup from that call's counts needs no second count.  MIPGEN_E_STATE before such a call. */
+int mipgen_accel_reads_consensus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -657,7 +694,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * 8 = k_sample_assign summed over the feed calls since the last mipgen_accel_reads_open_samples (timing enabled);
  * 9 = the two k_consensus_vote kernels of the last mipgen_accel_reads_finish_consensus, 10 = its sort of (key, pair id) and the run boundaries
  * (timing enabled); 11 = the pileup kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled); 12 = the kernels of the last
- * mipgen_accel_reads_consensus_pileup_gapped (timing enabled). */
+ * mipgen_accel_reads_consensus_pileup_gapped (timing enabled); 13 = the kernels of the last mipgen_accel_call_tables, mipgen_accel_reads_consensus_call (its pileup
+ * included) or mipgen_accel_reads_consensus_call_pool (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

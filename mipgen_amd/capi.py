@@ -91,6 +91,21 @@ class GappedTotals(C.Structure):    # mipgen_gapped_totals
     _fields_ = [(n, C.c_int64) for n in ("groups", "used", "bases", "discordant", "deletions", "insertions", "ins_discordant", "gapped_sides")]
 
 
+class CallParams(C.Structure):     # mipgen_call_params; the defaults are those of `mipgen_count -call`
+    _fields_ = [(n, C.c_int32) for n in ("min_depth", "min_alt", "min_ppm", "min_q", "a0", "n0", "bg_max_ppm")]
+
+    def __init__(self, min_depth=20, min_alt=3, min_ppm=0, min_q=30, a0=1, n0=1000, bg_max_ppm=200000):
+        super().__init__(min_depth, min_alt, min_ppm, min_q, a0, n0, bg_max_ppm)
+
+
+class CallTotals(C.Structure):     # mipgen_call_totals
+    _fields_ = [(n, C.c_int64) for n in ("tested", "too_deep", "candidates", "calls")]
+
+
+CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("allele", "<i4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4")])   # mipgen_call_record
+CALL_MAX_DEPTH = 1 << 20
+
+
 class Survivor(C.Structure):
     _fields_ = [("cand_index", C.c_int64), ("score", C.c_double), ("record", C.c_uint64)]
 
@@ -380,8 +395,15 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_consensus_pileup.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(PileupTotals)]
     lib.mipgen_accel_reads_consensus_pileup_gapped.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                                C.POINTER(C.c_int32), C.POINTER(GappedTotals)]
+    lib.mipgen_accel_call_tables.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CallParams),
+                                             C.POINTER(CallTotals)]
+    lib.mipgen_accel_reads_consensus_call_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.mipgen_accel_reads_consensus_call.argtypes = [vp, C.c_int32, C.POINTER(CallParams), C.POINTER(C.c_int32), C.POINTER(CallTotals)]
+    lib.mipgen_accel_call_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
+    lib.mipgen_accel_reads_consensus_call_pileup_totals.argtypes = [vp, C.POINTER(GappedTotals)]
+    lib.mipgen_accel_call_tables.restype = lib.mipgen_accel_call_fetch.restype = lib.mipgen_accel_reads_consensus_call_pileup_totals.restype = C.c_int
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
-                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped"):
+                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped", "consensus_call_pool", "consensus_call"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -463,6 +485,8 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_open_consensus", "mipgen_accel_reads_feed_consensus", "mipgen_accel_reads_finish_consensus", "mipgen_accel_reads_consensus_fetch",
     "mipgen_accel_reads_consensus_pileup",
     "mipgen_accel_reads_consensus_pileup_gapped",
+    "mipgen_accel_call_tables", "mipgen_accel_reads_consensus_call_pool", "mipgen_accel_reads_consensus_call", "mipgen_accel_call_fetch",
+    "mipgen_accel_reads_consensus_call_pileup_totals",
 ]
 
 
@@ -1006,6 +1030,53 @@ class Accel:
         self._check(self.lib.mipgen_accel_reads_consensus_pileup_gapped(self.h, bytes(seq), lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
                                                                         counts.ctypes.data_as(i32p), C.byref(tot)))
         return counts, {f[0]: int(getattr(tot, f[0])) for f in GappedTotals._fields_}
+
+    def call_fetch(self, n: int) -> np.ndarray:
+        """mipgen_accel_call_fetch: the n records of the last call of either kind as an array of CALL_RECORD_DTYPE, in ascending (pos, allele)."""
+        records = np.zeros(n, dtype=CALL_RECORD_DTYPE)
+        self._check(self.lib.mipgen_accel_call_fetch(self.h, records.ctypes.data if n else None, n))
+        return records
+
+    def call_tables(self, counts, pool, ref, own_row_is_sample: bool, params: "CallParams"):
+        """mipgen_accel_call_tables: variant calls from host arrays, no read session needed.  counts: int32 [n_pos][5 or 8], a pileup table; pool: int32
+        [n_pos][10], K[5] then N[5] per position; ref: n_pos bytes.  Returns (records, totals dict: tested, too_deep, candidates, calls)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        pool = np.ascontiguousarray(pool, dtype=np.int32)
+        ref = np.frombuffer(bytes(ref), dtype=np.uint8) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, dtype=np.uint8)
+        n_pos = len(ref)
+        if counts.ndim != 2 or counts.shape[0] != n_pos or pool.shape != (n_pos, 10):
+            raise ValueError(f"counts {counts.shape} and pool {pool.shape} do not match {n_pos} ref bytes")
+        tot = CallTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_call_tables(self.h, counts.ctypes.data_as(i32p), counts.shape[1], pool.ctypes.data_as(i32p), ref.ctypes.data, n_pos,
+                                                      int(bool(own_row_is_sample)), C.byref(params), C.byref(tot)))
+        return self.call_fetch(int(tot.calls)), {f[0]: int(getattr(tot, f[0])) for f in CallTotals._fields_}
+
+    def consensus_call_pool(self, mol_seq, mol_len: Sequence[int], min_family: int = 1, min_quality: int = 0, max_indel: int = 0, bg_max_ppm: int = 200000) -> None:
+        """mipgen_accel_reads_consensus_call_pool, callable after consensus_reads: the background pool over the sample rows of the session (max_indel 0: from the
+        ungapped pileup; 1..15: from the gapped one).  mol_seq as consensus_pileup_gapped takes it; it supplies the ref bytes."""
+        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
+        total = int(lens.astype(np.int64).clip(min=0).sum())
+        seq = (mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper()
+        if len(seq) != total:
+            raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
+        self._check(self.lib.mipgen_accel_reads_consensus_call_pool(self.h, bytes(seq), lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), min_family, min_quality, max_indel,
+                                                                    bg_max_ppm))
+        self._call_shape = (total, 8 if max_indel else 5)
+
+    def consensus_call(self, row: int, params: "CallParams"):
+        """mipgen_accel_reads_consensus_call, callable after consensus_call_pool: the calls of one row against the pool.  Returns (counts - the table the matching pileup
+        call returns -, records, totals dict)."""
+        counts = np.empty(self._call_shape, dtype=np.int32)
+        tot = CallTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_call(self.h, row, C.byref(params), counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(tot)))
+        return counts, self.call_fetch(int(tot.calls)), {f[0]: int(getattr(tot, f[0])) for f in CallTotals._fields_}
+
+    def consensus_call_pileup_totals(self) -> dict:
+        """mipgen_accel_reads_consensus_call_pileup_totals: the totals the matching pileup call returns for the row consensus_call counted last."""
+        tot = GappedTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_call_pileup_totals(self.h, C.byref(tot)))
+        return {f[0]: int(getattr(tot, f[0])) for f in GappedTotals._fields_}
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

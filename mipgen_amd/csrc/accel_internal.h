@@ -169,17 +169,49 @@ struct GappedScratch {
     size_t held() const { return row.held() + counts.cap * 4 + proj_off.cap * 8 + list.cap * 4 + mol_seq.cap + need.cap + proj.cap + ctr.cap * sizeof(GappedCounters); }
     void release() { row.release(); counts.release(); proj_off.release(); list.release(); mol_seq.release(); need.release(); proj.release(); ctr.release(); }
 };
+// mipgen_accel_reads_consensus_call_pool / _consensus_call: the pool over the sample rows, the ref bytes, the arguments the pool was built with and a
+// pileup scratch of each kind of its own - the calls share nothing with `pile` / `gapped` of the two pileup entry points
+struct CallScratch {
+    bool have = false;                                       // a pool is held
+    PileupScratch pile;
+    GappedScratch gapped;
+    DevBuf<int32_t> pool;                                    // positions x (K[5], N[5])
+    DevBuf<uint8_t> ref;                                     // positions
+    std::vector<int32_t> mol_len;
+    std::string mol_seq;
+    int32_t min_family = 1, min_quality = 0, max_indel = 0, bg_max_ppm = 0;
+    mipgen_gapped_totals last{0, 0, 0, 0, 0, 0, 0, 0};        // the pileup totals of the row called last
+    bool have_last = false;
+    size_t held() const { return pile.held() + gapped.held() + pool.cap * 4 + ref.cap; }
+    void release() { have = have_last = false; pile.release(); gapped.release(); pool.release(); ref.release(); }
+};
+// what a call of either kind (mipgen_accel_call_tables too) leaves on the HANDLE: the candidate list, the sort's buffers and the ordered records of the last call
+struct CallRun {
+    DevBuf<mipgen_call_record> cand, records;                // 4 per position at most; the candidates of the call
+    DevBuf<uint64_t> keys, keys_sorted;
+    DevBuf<uint32_t> ids, ids_sorted;
+    DevBuf<char> temp;
+    DevBuf<CallCounters> ctr;
+    DevBuf<int32_t> counts, pool;                            // the uploaded arrays of mipgen_accel_call_tables
+    DevBuf<uint8_t> ref;
+    int64_t n_calls = -1;                                    // the records of the last call (-1: none yet)
+    size_t held() const { return (cand.cap + records.cap) * sizeof(mipgen_call_record) + (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap) * 4 + temp.cap +
+                                 ctr.cap * sizeof(CallCounters) + (counts.cap + pool.cap) * 4 + ref.cap; }
+    void release() { cand.release(); records.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release(); ctr.release();
+                     counts.release(); pool.release(); ref.release(); n_calls = -1; }
+};
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
     int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
     PileupScratch pile;
     GappedScratch gapped;
+    CallScratch call;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); }
 };
 
 struct mipgen_accel {
@@ -303,6 +335,8 @@ struct mipgen_accel {
     double consensus_sort_ms = -1.0; // ... its radix sort of (key, pair id) and the run boundaries
     double pileup_ms = -1.0;         // the kernels_pileup.hip kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled)
     double gapped_ms = -1.0;         // the kernels of the last mipgen_accel_reads_consensus_pileup_gapped (timing enabled)
+    CallRun call_run;                // the last call's candidates and records (accel_pileup.hip)
+    double call_ms = -1.0;           // the kernels of the last mipgen_accel_call_tables / _reads_consensus_call / _reads_consensus_call_pool (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

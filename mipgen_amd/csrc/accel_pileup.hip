@@ -1,11 +1,13 @@
 // accel_pileup.hip — the two pileups read off the consensus reads a session left on the handle: allele counts per template position of one row (DESIGN 4.12:
-// mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped).  Both are plan_row (every check, nothing allocated or launched),
-// the call's own budget term, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), then the call's own launches,
-// download and totals.  Each call writes its own scratch of the ConsensusResult only (pile / gapped), so neither touches what the other holds.
+// mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped), and the variant calls made from them (4.14: mipgen_accel_call_tables,
+// _reads_consensus_call_pool, _reads_consensus_call, _call_fetch).  A pileup is plan_row (every check, nothing allocated or launched), then count_plain / count_gapped:
+// the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches, download and totals of ONE row into the
+// scratch it is given.  The two pileup entry points give `pile` / `gapped` of the ConsensusResult, the calls give the pair inside its CallScratch: three callers of one
+// count, and no call touches what another holds.
 #include "accel_internal.h"
 #include "gapped_align.h"
 
-struct GappedArgs { const char* mol_seq; int32_t max_indel; };         // what the gapped call adds to the arguments of a row
+struct GappedArgs { const char* mol_seq; int32_t max_indel; bool seq_only = false; };   // what the gapped call adds to the arguments of a row (seq_only: the bases are needed, nothing is placed)
 
 struct RowPlan {
     ConsensusResult* R = nullptr;
@@ -22,19 +24,20 @@ static int plan_row(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t 
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
     const ConsensusResult* R = P->R = h->consensus;
+    const bool placed = G && !G->seq_only;
     if (!mol_len) return fail(MIPGEN_E_INVALID, "bad arguments: no molecule lengths");
     if (G && !G->mol_seq) return fail(MIPGEN_E_INVALID, "bad arguments: no template bases");
     if ((int64_t)n != R->n) return fail(MIPGEN_E_INVALID, "%d molecule lengths: the session that left the consensus reads had %lld probes", n, (long long)R->n);
     for (int32_t p = 0; p < n; p++) {
         if (mol_len[p] < 1) return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: a length is 1 or more", mol_len[p], p);
-        if (G && mol_len[p] > MIPGEN_GAPPED_MAX_MOL)
+        if (placed && mol_len[p] > MIPGEN_GAPPED_MAX_MOL)
             return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: the gapped pileup places molecules of at most %d bases", mol_len[p], p, MIPGEN_GAPPED_MAX_MOL);
         P->n_pos += mol_len[p]; P->n_units += ((int64_t)mol_len[p] + 63) / 64; P->max_len = std::max(P->max_len, mol_len[p]);
     }
     if (row < 0 || (int64_t)row >= R->rows) return fail(MIPGEN_E_INVALID, "row %d: the session had %lld row%s", row, (long long)R->rows, R->rows == 1 ? "" : "s");
     if (min_family < 1) return fail(MIPGEN_E_INVALID, "min_family %d: 1 or more", min_family);
     if (min_quality < 0 || min_quality > 40) return fail(MIPGEN_E_INVALID, "min_quality %d: 0 to 40 (the consensus writes 2 to 40)", min_quality);
-    if (G && (G->max_indel < 1 || G->max_indel > GAP_MAX_INDEL)) return fail(MIPGEN_E_INVALID, "max_indel %d: 1 to %d", G->max_indel, GAP_MAX_INDEL);
+    if (placed && (G->max_indel < 1 || G->max_indel > GAP_MAX_INDEL)) return fail(MIPGEN_E_INVALID, "max_indel %d: 1 to %d", G->max_indel, GAP_MAX_INDEL);
     if (P->n_units > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld template positions: more than 2^31 - 1 rounds of 64", (long long)P->n_pos);
     P->bytes = padded((size_t)n, 4) + padded((size_t)n, 8) + padded((size_t)n + 1, 4) + padded((size_t)P->n_units, 8) + padded(1, sizeof(PileupCounters));
     HIP_TRY(hipSetDevice(h->device));
@@ -70,6 +73,178 @@ static int prepare_row(mipgen_accel* h, const RowPlan& P, RowScratch& W, const c
     return MIPGEN_OK;
 }
 
+
+// What a call adds to the budget of the row it counts: the bytes it will still allocate beside the row's, and what it already holds of them.  what: the call's name.
+struct Budget { const char* what; size_t more_need = 0, more_held = 0; bool keep_on_device = false; };   // keep_on_device: a session without groups still leaves a zeroed table in W.counts
+
+// One row of the ungapped table counted into W: W.counts holds it afterwards, `counts` (may be NULL) a copy; the kernels are spans of `timer`.
+static int count_plain(mipgen_accel* h, const RowPlan& P, PileupScratch& W, const Budget& B, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family,
+                       int32_t min_quality, SpanTimer& timer, int32_t* counts, mipgen_pileup_totals* totals)
+{
+    const ConsensusResult* R = P.R;
+    hipStream_t st = h->stream;
+    if (R->n_groups == 0) {                                              // (no buffer exists: nothing to read, nothing to launch)
+        if (counts) memset(counts, 0, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t));
+        if (totals) *totals = {0, 0, 0, 0};
+        if (B.keep_on_device) {
+            if (W.counts.reserve((size_t)P.n_pos * PILEUP_COLUMNS)) return MIPGEN_E_NOMEM;
+            HIP_TRY(hipMemsetAsync(W.counts.p, 0, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t), st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return MIPGEN_OK;
+    }
+    const size_t need = P.bytes + padded((size_t)P.n_pos * PILEUP_COLUMNS, 4) + B.more_need;
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (need > W.held() + B.more_held + free_b)
+        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions need %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos, need >> 20,
+                    (W.held() + B.more_held + free_b) >> 20);
+    if (W.counts.reserve((size_t)P.n_pos * PILEUP_COLUMNS)) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{st};
+    PileRow Row;
+    PileupCounters pc;
+    uint32_t first = 0, last = 0;                                        // the row's groups: [first, last)
+    if (int rc = prepare_row(h, P, W.row, B.what, mol_len, n, row, min_family, min_quality, timer, &Row, &pc, &first, &last)) return rc;
+    timer.mark();
+    HIP_TRY(mipgen_launch_pileup(st, R->view(), Row, P.n_units, W.counts.p, W.row.pctr.p));
+    timer.mark();
+    HIP_TRY(hipMemcpyAsync(&pc, W.row.pctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    if (totals) *totals = {(int64_t)last - (int64_t)first, (int64_t)pc.used, (int64_t)pc.bases, (int64_t)pc.discordant};
+    return MIPGEN_OK;
+}
+
+// One row of the table with indels counted into W, as count_plain.
+static int count_gapped(mipgen_accel* h, const RowPlan& P, GappedScratch& W, const Budget& B, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row,
+                        int32_t min_family, int32_t min_quality, int32_t max_indel, SpanTimer& gap_time, int32_t* counts, mipgen_gapped_totals* totals)
+{
+    const ConsensusResult* R = P.R;
+    hipStream_t st = h->stream;
+    const size_t n_pos = (size_t)P.n_pos;
+    if (R->n_groups == 0) {
+        if (counts) memset(counts, 0, n_pos * GAPPED_COLUMNS * sizeof(int32_t));
+        if (totals) *totals = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (B.keep_on_device) {
+            if (W.counts.reserve(n_pos * GAPPED_COLUMNS)) return MIPGEN_E_NOMEM;
+            HIP_TRY(hipMemsetAsync(W.counts.p, 0, n_pos * GAPPED_COLUMNS * sizeof(int32_t), st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return MIPGEN_OK;
+    }
+    // the budget, before anything is allocated: the row's groups are not known yet, so every buffer that grows with them is taken at the session's groups, and a
+    // projection at the longest template
+    const size_t G = (size_t)R->n_groups;
+    const size_t need = P.bytes + padded(n_pos * GAPPED_COLUMNS, 4) + padded(n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) +
+                        padded(2 * G * 3 * (size_t)P.max_len, 1) + padded(1, sizeof(GappedCounters)) + B.more_need;
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (need > W.held() + B.more_held + free_b)
+        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions and %lld groups need up to %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos,
+                    (long long)R->n_groups, need >> 20, (W.held() + B.more_held + free_b) >> 20);
+    if (W.counts.reserve(n_pos * GAPPED_COLUMNS) || W.mol_seq.reserve(n_pos) || W.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemcpyAsync(W.mol_seq.p, mol_seq, n_pos, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(GappedCounters), st));
+    PileRow Row;
+    PileupCounters pc;
+    GappedCounters gc;
+    memset(&gc, 0, sizeof gc);
+    uint32_t first = 0, last = 0;                                        // the row's groups: [first, last)
+    if (int rc = prepare_row(h, P, W.row, B.what, mol_len, n, row, min_family, min_quality, gap_time, &Row, &pc, &first, &last)) return rc;
+    const ConsensusView C = R->view();
+    const int64_t n_row = (int64_t)last - (int64_t)first;
+    if (n_row < 0 || n_row > R->n_groups) return fail(MIPGEN_E_STATE, "%s: groups [%u, %u) of %lld", B.what, first, last, (long long)R->n_groups);
+    if (n_row > 0) {
+        if (W.need.reserve(2 * (size_t)n_row) || W.list.reserve(2 * (size_t)n_row) || W.proj_off.reserve(2 * (size_t)n_row)) return MIPGEN_E_NOMEM;
+        gap_time.mark();
+        HIP_TRY(mipgen_launch_gap_list(st, C, Row, W.mol_seq.p, first, n_row, max_indel, W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
+        gap_time.mark();
+        HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * 3ull * (unsigned long long)P.max_len)
+            return fail(MIPGEN_E_STATE, "%s: %llu sides listed of %lld, %llu projection bytes", B.what, gc.n_sides, (long long)(2 * n_row), gc.proj_bytes);
+        if (gc.proj_bytes && W.proj.reserve((size_t)gc.proj_bytes)) return MIPGEN_E_NOMEM;
+    }
+    gap_time.mark();
+    HIP_TRY(mipgen_launch_gapped(st, C, Row, P.n_units, W.mol_seq.p, first, max_indel, P.max_len, W.list.p, (int64_t)gc.n_sides, W.proj_off.p, W.proj.p, W.counts.p, W.ctr.p));
+    gap_time.mark();
+    HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, n_pos * GAPPED_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    if (totals)
+        *totals = {n_row, (int64_t)pc.used, (int64_t)gc.bases, (int64_t)gc.discordant, (int64_t)gc.deletions, (int64_t)gc.insertions, (int64_t)gc.ins_discordant,
+                   (int64_t)gc.gapped_sides};
+    return MIPGEN_OK;
+}
+
+// ---- variant calls ---------------------------------------------------------------------------------------------------------------------------
+static int check_call_params(const mipgen_call_params* p)
+{
+    if (!p) return fail(MIPGEN_E_INVALID, "bad arguments: no call parameters");
+    if (p->min_depth < 1) return fail(MIPGEN_E_INVALID, "min_depth %d: 1 or more", p->min_depth);
+    if (p->min_alt < 1) return fail(MIPGEN_E_INVALID, "min_alt %d: 1 or more", p->min_alt);
+    if (p->min_ppm < 0 || p->min_ppm > 1000000) return fail(MIPGEN_E_INVALID, "min_ppm %d: 0 to 1000000", p->min_ppm);
+    if (p->min_q < 0 || p->min_q > CALL_Q_CAP) return fail(MIPGEN_E_INVALID, "min_q %d: 0 to %d", p->min_q, CALL_Q_CAP);
+    if (!(p->a0 > 0 && p->a0 < p->n0 && p->n0 <= (1 << 30))) return fail(MIPGEN_E_INVALID, "prior %d / %d: 0 < a0 < n0 <= 2^30", p->a0, p->n0);
+    if (p->bg_max_ppm < 0 || p->bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", p->bg_max_ppm);
+    return MIPGEN_OK;
+}
+
+// what flag, tail, sort and gather of n_pos positions take at the worst (4 candidates per position): the list, the ordered records, two (key, slot) pairs per candidate
+// and the sort's own scratch (measured at 1/16 of the sort's bytes, taken at 1/4)
+static size_t call_run_bytes(int64_t n_pos)
+{
+    const size_t c = 4 * (size_t)n_pos;
+    return 2 * padded(c, sizeof(mipgen_call_record)) + 2 * padded(c, 8) + 2 * padded(c, 4) + padded(c * 6, 1) + padded(1, sizeof(CallCounters));
+}
+
+// The calls of one finished table on the device against pool and ref there: flag, one read of the candidate count, tail, sort, gather.  The stream is idle and
+// h->call_run.n_calls set on success.
+static int run_call(mipgen_accel* h, const int32_t* counts, int columns, const int32_t* pool, const uint8_t* ref, int64_t n_pos, bool own_row_is_sample,
+                    const mipgen_call_params& prm, SpanTimer& timer, mipgen_call_totals* totals)
+{
+    CallRun& U = h->call_run;
+    U.n_calls = -1;
+    const CallModel M{prm.min_depth, prm.min_alt, prm.min_ppm, prm.min_q, prm.a0, prm.n0, prm.bg_max_ppm};
+    if (U.cand.reserve(4 * (size_t)n_pos) || U.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    CallCounters cc;
+    HIP_TRY(hipMemsetAsync(U.ctr.p, 0, sizeof cc, st));
+    timer.mark();
+    HIP_TRY(mipgen_launch_call_flag(st, counts, columns, pool, ref, n_pos, own_row_is_sample ? 1 : 0, M, U.cand.p, U.ctr.p));
+    timer.mark();
+    HIP_TRY(hipMemcpyAsync(&cc, U.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_cand = (int64_t)cc.candidates;
+    if (n_cand < 0 || n_cand > 4 * n_pos) return fail(MIPGEN_E_STATE, "call: %lld candidates listed of %lld positions", (long long)n_cand, (long long)n_pos);
+    if (n_cand > 0) {
+        int end_bit = 4;                                                 // the bits of the sentinel n_pos << 3, the largest key
+        while (end_bit < 64 && (((uint64_t)n_pos << 3) >> end_bit)) end_bit++;
+        size_t temp_bytes = 0;
+        HIP_TRY(mipgen_consensus_sort(st, nullptr, &temp_bytes, nullptr, nullptr, nullptr, nullptr, n_cand, end_bit));
+        if (U.keys.reserve((size_t)n_cand) || U.keys_sorted.reserve((size_t)n_cand) || U.ids.reserve((size_t)n_cand) || U.ids_sorted.reserve((size_t)n_cand) ||
+            U.records.reserve((size_t)n_cand) || U.temp.reserve(std::max<size_t>(temp_bytes, 1)))
+            return MIPGEN_E_NOMEM;
+        temp_bytes = U.temp.cap;
+        timer.mark();
+        HIP_TRY(mipgen_launch_call_tail(st, U.cand.p, n_cand, n_pos, M, U.keys.p, U.ids.p, U.ctr.p));
+        HIP_TRY(mipgen_consensus_sort(st, U.temp.p, &temp_bytes, U.keys.p, U.keys_sorted.p, U.ids.p, U.ids_sorted.p, n_cand, end_bit));
+        HIP_TRY(mipgen_launch_call_gather(st, U.cand.p, U.ids_sorted.p, n_cand, U.ctr.p, U.records.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&cc, U.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(idle.wait());
+    if ((int64_t)cc.calls > n_cand) return fail(MIPGEN_E_STATE, "call: %llu calls of %lld candidates", cc.calls, (long long)n_cand);
+    U.n_calls = (int64_t)cc.calls;
+    if (totals) *totals = {(int64_t)cc.tested, (int64_t)cc.too_deep, n_cand, (int64_t)cc.calls};
+    return MIPGEN_OK;
+}
+
+// the sample rows of a session: all but the last (undetermined) when it had barcodes, the one row otherwise
+static int64_t sample_rows(const ConsensusResult* R) { return R->rows > 1 ? R->rows - 1 : 1; }
+
 extern "C" {
 
 // Allele counts per template position of one row from the consensus reads the handle holds.  Reads R's groups and reads; writes R->pile only.
@@ -78,36 +253,11 @@ int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len,
 {
     RowPlan P;
     if (int rc = plan_row(h, mol_len, n, row, min_family, min_quality, nullptr, &P)) return rc;
-    const ConsensusResult* R = P.R;
     h->pileup_ms = -1.0;
-    if (R->n_groups == 0) {                                              // (no buffer exists: nothing to read, nothing to launch)
-        if (counts) memset(counts, 0, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t));
-        if (totals) *totals = {0, 0, 0, 0};
-        return MIPGEN_OK;
-    }
-    PileupScratch& W = P.R->pile;
-    const size_t need = P.bytes + padded((size_t)P.n_pos * PILEUP_COLUMNS, 4);
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > W.held() + free_b)
-        return fail(MIPGEN_E_NOMEM, "pileup: %lld template positions need %zu MiB of device memory, %zu MiB are free", (long long)P.n_pos, need >> 20, (W.held() + free_b) >> 20);
-    if (W.counts.reserve((size_t)P.n_pos * PILEUP_COLUMNS)) return MIPGEN_E_NOMEM;
-    hipStream_t st = h->stream;
-    IdleOnExit idle{st};
-    SpanTimer pile_time{h->timing, st};
-    PileRow Row;
-    PileupCounters pc;
-    uint32_t first = 0, last = 0;                                        // the row's groups: [first, last)
-    if (int rc = prepare_row(h, P, W.row, "pileup", mol_len, n, row, min_family, min_quality, pile_time, &Row, &pc, &first, &last)) return rc;
-    pile_time.mark();
-    HIP_TRY(mipgen_launch_pileup(st, R->view(), Row, P.n_units, W.counts.p, W.row.pctr.p));
-    pile_time.mark();
-    HIP_TRY(hipMemcpyAsync(&pc, W.row.pctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(idle.wait());
+    SpanTimer pile_time{h->timing, h->stream};
+    if (int rc = count_plain(h, P, P.R->pile, Budget{"pileup"}, mol_len, n, row, min_family, min_quality, pile_time, counts, totals)) return rc;
     double ms = 0.0;
     if (pile_time.add_to(&ms)) h->pileup_ms = ms;
-    if (totals) *totals = {(int64_t)last - (int64_t)first, (int64_t)pc.used, (int64_t)pc.bases, (int64_t)pc.discordant};
     return MIPGEN_OK;
 }
 
@@ -118,61 +268,150 @@ int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_
     RowPlan P;
     const GappedArgs args{mol_seq, max_indel};
     if (int rc = plan_row(h, mol_len, n, row, min_family, min_quality, &args, &P)) return rc;
-    const ConsensusResult* R = P.R;
     h->gapped_ms = -1.0;
-    if (R->n_groups == 0) {
-        if (counts) memset(counts, 0, (size_t)P.n_pos * GAPPED_COLUMNS * sizeof(int32_t));
-        if (totals) *totals = {0, 0, 0, 0, 0, 0, 0, 0};
-        return MIPGEN_OK;
-    }
-    GappedScratch& W = P.R->gapped;
-    // the budget, before anything is allocated: the row's groups are not known yet, so every buffer that grows with them is taken at the session's groups, and a
-    // projection at the longest template
-    const size_t G = (size_t)R->n_groups, n_pos = (size_t)P.n_pos;
-    const size_t need = P.bytes + padded(n_pos * GAPPED_COLUMNS, 4) + padded(n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) +
-                        padded(2 * G * 3 * (size_t)P.max_len, 1) + padded(1, sizeof(GappedCounters));
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > W.held() + free_b)
-        return fail(MIPGEN_E_NOMEM, "gapped pileup: %lld template positions and %lld groups need up to %zu MiB of device memory, %zu MiB are free", (long long)P.n_pos,
-                    (long long)R->n_groups, need >> 20, (W.held() + free_b) >> 20);
-    if (W.counts.reserve(n_pos * GAPPED_COLUMNS) || W.mol_seq.reserve(n_pos) || W.ctr.reserve(1)) return MIPGEN_E_NOMEM;
-    hipStream_t st = h->stream;
-    IdleOnExit idle{st};
-    HIP_TRY(hipMemcpyAsync(W.mol_seq.p, mol_seq, n_pos, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(GappedCounters), st));
-    SpanTimer gap_time{h->timing, st};
-    PileRow Row;
-    PileupCounters pc;
-    GappedCounters gc;
-    memset(&gc, 0, sizeof gc);
-    uint32_t first = 0, last = 0;                                        // the row's groups: [first, last)
-    if (int rc = prepare_row(h, P, W.row, "gapped pileup", mol_len, n, row, min_family, min_quality, gap_time, &Row, &pc, &first, &last)) return rc;
-    const ConsensusView C = R->view();
-    const int64_t n_row = (int64_t)last - (int64_t)first;
-    if (n_row < 0 || n_row > R->n_groups) return fail(MIPGEN_E_STATE, "gapped pileup: groups [%u, %u) of %lld", first, last, (long long)R->n_groups);
-    if (n_row > 0) {
-        if (W.need.reserve(2 * (size_t)n_row) || W.list.reserve(2 * (size_t)n_row) || W.proj_off.reserve(2 * (size_t)n_row)) return MIPGEN_E_NOMEM;
-        gap_time.mark();
-        HIP_TRY(mipgen_launch_gap_list(st, C, Row, W.mol_seq.p, first, n_row, max_indel, W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
-        gap_time.mark();
-        HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * 3ull * (unsigned long long)P.max_len)
-            return fail(MIPGEN_E_STATE, "gapped pileup: %llu sides listed of %lld, %llu projection bytes", gc.n_sides, (long long)(2 * n_row), gc.proj_bytes);
-        if (gc.proj_bytes && W.proj.reserve((size_t)gc.proj_bytes)) return MIPGEN_E_NOMEM;
-    }
-    gap_time.mark();
-    HIP_TRY(mipgen_launch_gapped(st, C, Row, P.n_units, W.mol_seq.p, first, max_indel, P.max_len, W.list.p, (int64_t)gc.n_sides, W.proj_off.p, W.proj.p, W.counts.p, W.ctr.p));
-    gap_time.mark();
-    HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, n_pos * GAPPED_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(idle.wait());
+    SpanTimer gap_time{h->timing, h->stream};
+    if (int rc = count_gapped(h, P, P.R->gapped, Budget{"gapped pileup"}, mol_seq, mol_len, n, row, min_family, min_quality, max_indel, gap_time, counts, totals)) return rc;
     double ms = 0.0;
     if (gap_time.add_to(&ms)) h->gapped_ms = ms;
-    if (totals)
-        *totals = {n_row, (int64_t)pc.used, (int64_t)gc.bases, (int64_t)gc.discordant, (int64_t)gc.deletions, (int64_t)gc.insertions, (int64_t)gc.ins_discordant,
-                   (int64_t)gc.gapped_sides};
+    return MIPGEN_OK;
+}
+
+// Calls from host arrays: no read session is needed; the arrays are uploaded into the handle's CallRun.
+int mipgen_accel_call_tables(mipgen_accel* h, const int32_t* counts, int32_t columns, const int32_t* pool, const uint8_t* ref, int64_t n_pos, int32_t own_row_is_sample,
+                             const mipgen_call_params* params, mipgen_call_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!counts || !pool || !ref) return fail(MIPGEN_E_INVALID, "bad arguments: no counts, no pool or no ref bytes");
+    if (columns != PILEUP_COLUMNS && columns != GAPPED_COLUMNS) return fail(MIPGEN_E_INVALID, "%d columns: %d (the pileup's table) or %d (the gapped one)", columns, PILEUP_COLUMNS, GAPPED_COLUMNS);
+    if (n_pos < 1 || n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld positions: 1 to 2^29 - 1", (long long)n_pos);
+    if (int rc = check_call_params(params)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    CallRun& U = h->call_run;
+    h->call_ms = -1.0;
+    const size_t np = (size_t)n_pos, need = padded(np * (size_t)columns, 4) + padded(np * 10, 4) + padded(np, 1) + call_run_bytes(n_pos);
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (need > U.held() + free_b)
+        return fail(MIPGEN_E_NOMEM, "call: %lld positions need up to %zu MiB of device memory, %zu MiB are free", (long long)n_pos, need >> 20, (U.held() + free_b) >> 20);
+    if (U.counts.reserve(np * (size_t)columns) || U.pool.reserve(np * 10) || U.ref.reserve(np)) return MIPGEN_E_NOMEM;
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemcpyAsync(U.counts.p, counts, np * (size_t)columns * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(U.pool.p, pool, np * 40, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(U.ref.p, ref, np, hipMemcpyHostToDevice, st));
+    SpanTimer timer{h->timing, st};
+    if (int rc = run_call(h, U.counts.p, columns, U.pool.p, U.ref.p, n_pos, own_row_is_sample != 0, *params, timer, totals)) return rc;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->call_ms = ms;
+    return MIPGEN_OK;
+}
+
+// The pool over the sample rows of the session: every row's pileup into R->call's own scratch, added on the device.  Writes R->call only.
+int mipgen_accel_reads_consensus_call_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                           int32_t max_indel, int32_t bg_max_ppm)
+{
+    RowPlan P;
+    const GappedArgs args{mol_seq, max_indel, max_indel == 0};
+    if (int rc = plan_row(h, mol_len, n, 0, min_family, min_quality, &args, &P)) return rc;
+    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    if (P.n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: a call takes 2^29 - 1 at most", (long long)P.n_pos);
+    ConsensusResult* R = P.R;
+    CallScratch& C = R->call;
+    C.have = C.have_last = false;                                        // (a pool that fails leaves none)
+    h->call_ms = -1.0;
+    const size_t np = (size_t)P.n_pos;
+    // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_plain's / count_gapped's
+    const size_t more = padded(np * 10, 4) + padded(np, 1) + call_run_bytes(P.n_pos);
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (more > C.pool.cap * 4 + C.ref.cap + h->call_run.held() + free_b)
+        return fail(MIPGEN_E_NOMEM, "call pool: %lld template positions need up to %zu MiB of device memory beside the pileup's, %zu MiB are free", (long long)P.n_pos,
+                    more >> 20, (C.pool.cap * 4 + C.ref.cap + h->call_run.held() + free_b) >> 20);
+    const Budget B{"call pool", more, C.pool.cap * 4 + C.ref.cap + h->call_run.held(), true};
+    if (C.pool.reserve(np * 10) || C.ref.reserve(np)) return MIPGEN_E_NOMEM;
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemcpyAsync(C.ref.p, mol_seq, np, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(C.pool.p, 0, np * 40, st));
+    SpanTimer timer{h->timing, st};
+    for (int64_t r = 0; r < sample_rows(R); r++) {
+        const int32_t* table = nullptr;
+        if (max_indel) {
+            if (int rc = count_gapped(h, P, C.gapped, B, mol_seq, mol_len, n, (int32_t)r, min_family, min_quality, max_indel, timer, nullptr, nullptr)) return rc;
+            table = C.gapped.counts.p;
+        } else {
+            if (int rc = count_plain(h, P, C.pile, B, mol_len, n, (int32_t)r, min_family, min_quality, timer, nullptr, nullptr)) return rc;
+            table = C.pile.counts.p;
+        }
+        timer.mark();
+        HIP_TRY(mipgen_launch_call_pool(st, table, max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, P.n_pos, bg_max_ppm, C.pool.p));
+        timer.mark();
+    }
+    HIP_TRY(idle.wait());
+    C.mol_len.assign(mol_len, mol_len + n);
+    C.mol_seq.assign(mol_seq, np);
+    C.min_family = min_family; C.min_quality = min_quality; C.max_indel = max_indel; C.bg_max_ppm = bg_max_ppm;
+    C.have = true;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->call_ms = ms;
+    return MIPGEN_OK;
+}
+
+// The calls of one row against the pool: the row's pileup recomputed with the pool's arguments into R->call's scratch, then flag, tail and order.
+int mipgen_accel_reads_consensus_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, mipgen_call_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    CallScratch& C = h->consensus->call;
+    if (!C.have) return fail(MIPGEN_E_STATE, "the consensus reads have no pool: mipgen_accel_reads_consensus_call_pool builds it");
+    RowPlan P;
+    const GappedArgs args{C.mol_seq.data(), C.max_indel, C.max_indel == 0};
+    const int32_t n = (int32_t)C.mol_len.size();
+    if (int rc = plan_row(h, C.mol_len.data(), n, row, C.min_family, C.min_quality, &args, &P)) return rc;
+    if (int rc = check_call_params(params)) return rc;
+    if (params->bg_max_ppm != C.bg_max_ppm) return fail(MIPGEN_E_STATE, "bg_max_ppm %d: the pool was built with %d", params->bg_max_ppm, C.bg_max_ppm);
+    h->call_ms = -1.0;
+    h->call_run.n_calls = -1;
+    const Budget B{"call", call_run_bytes(P.n_pos), h->call_run.held(), true};
+    SpanTimer timer{h->timing, h->stream};
+    const int32_t* table = nullptr;
+    C.have_last = false;
+    if (C.max_indel) {
+        if (int rc = count_gapped(h, P, C.gapped, B, C.mol_seq.data(), C.mol_len.data(), n, row, C.min_family, C.min_quality, C.max_indel, timer, counts, &C.last)) return rc;
+        table = C.gapped.counts.p;
+    } else {
+        mipgen_pileup_totals pt{0, 0, 0, 0};
+        if (int rc = count_plain(h, P, C.pile, B, C.mol_len.data(), n, row, C.min_family, C.min_quality, timer, counts, &pt)) return rc;
+        C.last = {pt.groups, pt.used, pt.bases, pt.discordant, 0, 0, 0, 0};
+        table = C.pile.counts.p;
+    }
+    C.have_last = true;
+    if (int rc = run_call(h, table, C.max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, C.pool.p, C.ref.p, P.n_pos, (int64_t)row < sample_rows(P.R), *params, timer, totals)) return rc;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->call_ms = ms;
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_consensus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus || !h->consensus->call.have_last) return fail(MIPGEN_E_STATE, "no row was called: mipgen_accel_reads_consensus_call counts one");
+    if (totals) *totals = h->consensus->call.last;
+    return MIPGEN_OK;
+}
+
+// The records of the last call of either kind, in ascending (pos, allele).
+int mipgen_accel_call_fetch(mipgen_accel* h, mipgen_call_record* records, int64_t n)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    const CallRun& U = h->call_run;
+    if (U.n_calls < 0) return fail(MIPGEN_E_STATE, "the handle holds no calls: mipgen_accel_call_tables or mipgen_accel_reads_consensus_call leaves them");
+    if (n != U.n_calls) return fail(MIPGEN_E_INVALID, "%lld records asked: the last call left %lld", (long long)n, (long long)U.n_calls);
+    if (n == 0) return MIPGEN_OK;
+    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(records, U.records.p, (size_t)n * sizeof(mipgen_call_record), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MIPGEN_OK;
 }
 

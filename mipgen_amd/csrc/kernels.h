@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include "common.h"
 #include "reads_common.h"
+#include "call_model.h"
 
 struct HostConsts;                   // logistic_device.h: crosses the boundary by pointer only
 struct LrcMers { int8_t k[MIPGEN_N_LRC], code[MIPGEN_N_LRC], rc[MIPGEN_N_LRC]; };   // per mer: length, base-4 code, code of its reverse complement (-1: palindrome)
@@ -55,6 +56,10 @@ struct PileRow {
     uint32_t cell0;                           // the row's first cell
     int min_family, min_quality;
 };
+
+// variant calls: what k_call_flag and k_call_tail count; the positions one call takes: 4 candidates per position stay below the 2^31 - 1 pairs of the sort
+struct CallCounters { unsigned long long tested, too_deep, candidates, calls; };
+#define MIPGEN_CALL_MAX_POSITIONS (((int64_t)1 << 29) - 1)
 
 extern "C" {
 // kernels_logistic.hip
@@ -171,4 +176,11 @@ hipError_t mipgen_launch_gap_list(hipStream_t, const ConsensusView& C, const Pil
                                   uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr);
 hipError_t mipgen_launch_gapped(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, const uint8_t* mol_seq, uint32_t g_first, int max_indel, int max_len,
                                 const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int32_t* counts, GappedCounters* ctr);
+// kernels_call.hip: one row's table added into the pool (K[5], N[5] per position); the candidates of a table against the pool (cand: 4 n_pos records, ctr
+// zero on entry); their scores, sort keys and ctr->calls; the calls in key order
+hipError_t mipgen_launch_call_pool(hipStream_t, const int32_t* counts, int columns, int64_t n_pos, int32_t bg_max_ppm, int32_t* pool);
+hipError_t mipgen_launch_call_flag(hipStream_t, const int32_t* counts, int columns, const int32_t* pool, const uint8_t* ref, int64_t n_pos, int own_row_is_sample,
+                                   const CallModel& P, mipgen_call_record* cand, CallCounters* ctr);
+hipError_t mipgen_launch_call_tail(hipStream_t, mipgen_call_record* cand, int64_t n_cand, int64_t n_pos, const CallModel& P, uint64_t* keys, uint32_t* ids, CallCounters* ctr);
+hipError_t mipgen_launch_call_gather(hipStream_t, const mipgen_call_record* cand, const uint32_t* ids, int64_t n_cand, const CallCounters* ctr, mipgen_call_record* records);
 }

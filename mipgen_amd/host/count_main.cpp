@@ -43,6 +43,15 @@
 //                           header and every line gain the columns del, ins and ins_discordant (molecules that show a deletion of the base; an insertion between
 //                           this base and the next one in genome plus orientation; two different insertion lengths there), a line is written when any of its eight
 //                           numbers is non-zero, and a second stderr line follows: "mipgen_count: pileup indels deletions X insertions Y ins_discordant Z gapped_sides S"
+// Variant calls from the pileup against a background of the other samples (without -call every byte written is what it was):
+//   -call CALLS             needs -pileup and uses -pileup_min_family, -pileup_min_quality and -pileup_indels as given: one pool over the sample rows, then one call per
+//                           row (undetermined too) that feeds BOTH files - FILE is byte for byte what it is without -call.  Header
+//                           ">sample <tab> mip_key <tab> chr <tab> position <tab> strand <tab> part <tab> ref <tab> alt <tab> depth <tab> alt_count <tab> alt_ppm <tab>
+//                           bg_alt <tab> bg_depth <tab> q"; one line per call in row, table and position order, within a position in the order A C G T - of the printed
+//                           alt; genome plus orientation as in -pileup (ref and alt complemented on a '-' probe; a deleted base prints alt "-" on the line of that
+//                           base); alt_ppm = floor(alt_count 10^6 / depth); bg_alt, bg_depth: the background without this row
+//   -call_min_depth 20  -call_min_alt 3  -call_min_ppm 0  -call_min_q 30  -call_prior 1,1000  -call_background_max_ppm 200000     the parameters of the model
+//   stderr     a last line: "mipgen_count: calls C candidates K tested P too_deep D"
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -73,7 +82,9 @@ static int usage(const std::string& msg)
             "-samples file : sample, barcode, pairs, assigned, unique_tags, probes_seen per sample\n"
             "-consensus prefix : prefix.ext.fq and prefix.lig.fq, one consensus read pair per (sample, probe, tag) group; -min_family k : groups of at least k pairs (default 1)\n"
             "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n"
-            "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n");
+            "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n"
+            "-call file : with -pileup, variant calls of every sample against the background of the others; -call_min_depth n (default 20), -call_min_alt k (3), -call_min_ppm p (0),\n"
+            "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n");
     return 1;
 }
 
@@ -175,7 +186,9 @@ int main(int argc, char** argv)
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
     long min_family = 1, pile_family = 1, pile_quality = 0, pile_indels = 0;
     bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
-    std::string consensus_prefix, pileup_path;
+    std::string consensus_prefix, pileup_path, call_path;
+    mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
+    bool call_option_given = false;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
@@ -210,6 +223,17 @@ int main(int argc, char** argv)
         else if (a == "-pileup_min_family") { if (!svr_parse_int(v.c_str(), &pile_family) || pile_family < 1 || pile_family > INT32_MAX) return usage("-pileup_min_family must be 1 or more"); pile_option_given = true; }
         else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
         else if (a == "-pileup_indels") { if (!svr_parse_int(v.c_str(), &pile_indels) || pile_indels < 1 || pile_indels > 15) return usage("-pileup_indels must be 1 to 15"); }
+        else if (a == "-call") { if (v.empty()) return usage("-call takes a file"); call_path = v; }
+        else if (a == "-call_min_depth") { if (!svr_parse_int(v.c_str(), &iv) || iv < 1 || iv > INT32_MAX) return usage("-call_min_depth must be 1 or more"); call_prm.min_depth = (int32_t)iv; call_option_given = true; }
+        else if (a == "-call_min_alt") { if (!svr_parse_int(v.c_str(), &iv) || iv < 1 || iv > INT32_MAX) return usage("-call_min_alt must be 1 or more"); call_prm.min_alt = (int32_t)iv; call_option_given = true; }
+        else if (a == "-call_min_ppm") { if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1000000) return usage("-call_min_ppm must be 0 to 1000000"); call_prm.min_ppm = (int32_t)iv; call_option_given = true; }
+        else if (a == "-call_min_q") { if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 9999) return usage("-call_min_q must be 0 to 9999"); call_prm.min_q = (int32_t)iv; call_option_given = true; }
+        else if (a == "-call_background_max_ppm") { if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1000000) return usage("-call_background_max_ppm must be 0 to 1000000"); call_prm.bg_max_ppm = (int32_t)iv; call_option_given = true; }
+        else if (a == "-call_prior") {
+            std::vector<long> pr;
+            if (!parse_int_list(v, pr) || pr.size() != 2 || !(pr[0] > 0 && pr[0] < pr[1] && pr[1] <= (1L << 30))) return usage("-call_prior takes a,n with 0 < a < n <= 2^30");
+            call_prm.a0 = (int32_t)pr[0]; call_prm.n0 = (int32_t)pr[1]; call_option_given = true;
+        }
         else if (a == "-barcode_mismatches") {
             if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-barcode_mismatches must be 0 or 1");
             bc_mism = (int)iv; bc_mism_given = true;
@@ -231,6 +255,9 @@ int main(int argc, char** argv)
     const bool pileup = !pileup_path.empty(), keep_reads = consensus || pileup;      // (-pileup reads the consensus reads: its session keeps the reads too)
     if (pile_option_given && !pileup) return usage("-pileup_min_family and -pileup_min_quality need -pileup file");
     if (pile_indels && !pileup) return usage("-pileup_indels needs -pileup file");
+    const bool call = !call_path.empty();
+    if (call && !pileup) return usage("-call needs -pileup file");
+    if (call_option_given && !call) return usage("the -call_* options need -call file");
     if (pileup && te + tl == 0) return usage("-pileup needs tag bases: with -tag_sizes 0,0 there are no molecules to count");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
@@ -276,7 +303,7 @@ int main(int argc, char** argv)
     if (probes.size() > (size_t)INT32_MAX) { fprintf(stderr, "%s: too many probes\n", PROG); return 1; }
     // -pileup: the length of every probe's molecule and where it lies on the genome
     std::vector<int32_t> mol_len;
-    std::string mol_seq;                                                                 // -pileup_indels: the templates, upper-cased, in probe order
+    std::string mol_seq;                                                                 // -pileup_indels, -call: the templates, upper-cased, in probe order
     std::vector<RowCoords> coords;
     if (pileup)
         for (const auto* r : rows) {
@@ -285,8 +312,8 @@ int main(int argc, char** argv)
             if (!row_coords(*r, &c, &what)) { fprintf(stderr, "%s: -pileup: probe %s: %s\n", PROG, (*r)[COL_KEY].c_str(), what); return 1; }
             coords.push_back(c);
             mol_len.push_back((int32_t)((*r)[COL_EXT_SEQ].size() + (*r)[COL_INS_SEQ].size() + (*r)[COL_LIG_SEQ].size()));
-            if (pile_indels) {
-                if (mol_len.back() > MIPGEN_GAPPED_MAX_MOL) {
+            if (pile_indels || call) {                                                   // (-call: the templates supply the ref bytes)
+                if (pile_indels && mol_len.back() > MIPGEN_GAPPED_MAX_MOL) {
                     fprintf(stderr, "%s: -pileup_indels: probe %s: a molecule of %d bases (at most %d are placed)\n", PROG, (*r)[COL_KEY].c_str(), mol_len.back(), MIPGEN_GAPPED_MAX_MOL);
                     return 1;
                 }
@@ -329,6 +356,8 @@ int main(int argc, char** argv)
             if (!(cons_out[k] = fopen(cons_path[k].c_str(), "w"))) return usage("-consensus " + consensus_prefix + ": can't write " + cons_path[k]);
     FILE* pile_out = nullptr;
     if (pileup && !(pile_out = fopen(pileup_path.c_str(), "w"))) return usage("-pileup " + pileup_path + ": can't write " + pileup_path);
+    FILE* call_out = nullptr;
+    if (call && !(call_out = fopen(call_path.c_str(), "w"))) return usage("-call " + call_path + ": can't write " + call_path);
 
     // ---- the device ----
     mipgen_accel* h = nullptr;
@@ -420,6 +449,7 @@ int main(int argc, char** argv)
                                                         &g_qual[1][0]) != MIPGEN_OK) return die();
     // -pileup: one call per row; a second thread turns the counts of a row into lines while the device counts the next row
     long long pile_used = 0, pile_lines = 0, pile_bases = 0, pile_nonref = 0, pile_disc = 0, pile_del = 0, pile_ins = 0, pile_insd = 0, pile_gapped = 0;
+    long long call_calls = 0, call_cands = 0, call_tested = 0, call_deep = 0;
     const size_t pile_cols = pile_indels ? 8 : 5;
     if (pileup) {
         int64_t n_pos = 0;
@@ -467,13 +497,59 @@ int main(int argc, char** argv)
             }
             fwrite(text.data(), 1, text.size(), pile_out);
         };
+        // -call: the records of a row (ascending position, then allele class) as lines; within a position the printed alts go A C G T -, which on a '-' probe is
+        // the reverse of the class order of the four bases
+        std::vector<mipgen_call_record> recs[2];
+        auto write_calls = [&](size_t r, const std::vector<mipgen_call_record>& rec) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text;
+            char buf[200];
+            for (size_t a = 0; a < rec.size();) {
+                size_t b = a;
+                while (b < rec.size() && rec[b].pos == rec[a].pos) b++;
+                const size_t i = (size_t)(std::upper_bound(pos_off.begin(), pos_off.end(), rec[a].pos) - pos_off.begin()) - 1;
+                const std::vector<std::string>& f = *rows[i];
+                const RowCoords& c = coords[i];
+                const size_t n_ext = f[COL_EXT_SEQ].size(), n_ins = f[COL_INS_SEQ].size(), ut = (size_t)(rec[a].pos - pos_off[i]);
+                char ref = (char)toupper((unsigned char)(ut < n_ext ? f[COL_EXT_SEQ][ut] : ut < n_ext + n_ins ? f[COL_INS_SEQ][ut - n_ext] : f[COL_LIG_SEQ][ut - n_ext - n_ins]));
+                if (c.minus) ref = ref == 'A' ? 'T' : ref == 'C' ? 'G' : ref == 'G' ? 'C' : ref == 'T' ? 'A' : ref;
+                for (int printed = 0; printed < 5; printed++) {                          // A C G T - as printed
+                    const int cls = printed < 4 && c.minus ? 3 - printed : printed;
+                    for (size_t k = a; k < b; k++) {
+                        if (rec[k].allele != cls) continue;
+                        const mipgen_call_record& q = rec[k];
+                        snprintf(buf, sizeof buf, "\t%ld\t%c\t%s\t%c\t%c\t%d\t%d\t%lld\t%d\t%d\t%d\n", c.minus ? c.ext_stop - (long)ut : c.ext_start + (long)ut, c.minus ? '-' : '+',
+                                 ut < n_ext ? "ext" : ut < n_ext + n_ins ? "target" : "lig", ref, "ACGT-"[printed], q.depth, q.alt, (long long)q.alt * 1000000ll / q.depth, q.bg_alt,
+                                 q.bg_depth, q.q);
+                        text.append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf);
+                    }
+                }
+                a = b;
+            }
+            fwrite(text.data(), 1, text.size(), call_out);
+        };
+        if (call) {
+            fputs(">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\talt\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\n", call_out);
+            if (mipgen_accel_reads_consensus_call_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
+                                                       call_prm.bg_max_ppm) != MIPGEN_OK) return die();
+        }
         fputs(pile_indels ? ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n"
                           : ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
         std::thread writer;
         for (size_t r = 0; r < n_rows; r++) {
             mipgen_pileup_totals pt{0, 0, 0, 0};
             mipgen_gapped_totals gt{0, 0, 0, 0, 0, 0, 0, 0};
-            const int prc = pile_indels ? mipgen_accel_reads_consensus_pileup_gapped(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
+            mipgen_call_totals ct{0, 0, 0, 0};
+            int prc;
+            if (call) {                                                                  // one call per row feeds both files: its counts are the pileup's
+                prc = mipgen_accel_reads_consensus_call(h, (int32_t)r, &call_prm, table[r & 1].data(), &ct);
+                if (prc == MIPGEN_OK) prc = mipgen_accel_reads_consensus_call_pileup_totals(h, &gt);
+                if (writer.joinable()) writer.join();                                    // (recs[r & 1] is the writer's until then)
+                if (prc == MIPGEN_OK) { recs[r & 1].resize((size_t)ct.calls); prc = mipgen_accel_call_fetch(h, recs[r & 1].data(), ct.calls); }
+                pt.used = gt.used;
+                call_calls += ct.calls; call_cands += ct.candidates; call_tested += ct.tested; call_deep += ct.too_deep;
+            } else
+            prc = pile_indels ? mipgen_accel_reads_consensus_pileup_gapped(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
                                                                                      (int32_t)pile_quality, (int32_t)pile_indels, table[r & 1].data(), &gt)
                                         : mipgen_accel_reads_consensus_pileup(h, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
                                                                               table[r & 1].data(), &pt);
@@ -481,10 +557,11 @@ int main(int argc, char** argv)
             if (writer.joinable()) writer.join();
             if (prc != MIPGEN_OK) return die();
             pile_used += pt.used;
-            writer = std::thread(write_row, r, std::cref(table[r & 1]));
+            writer = std::thread([&, r]() { write_row(r, table[r & 1]); if (call) write_calls(r, recs[r & 1]); });
         }
         if (writer.joinable()) writer.join();
         if (fclose(pile_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, pileup_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (call && fclose(call_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_path.c_str()); mipgen_accel_destroy(h); return 1; }
     }
     mipgen_accel_destroy(h);
 
@@ -564,5 +641,6 @@ int main(int argc, char** argv)
     if (consensus) fprintf(stderr, "%s: consensus groups %lld written %lld members %lld\n", PROG, (long long)csz.n_groups, cons_written, cons_members);
     if (pileup) fprintf(stderr, "%s: pileup molecules %lld positions %lld bases %lld nonref %lld discordant %lld\n", PROG, pile_used, pile_lines, pile_bases, pile_nonref, pile_disc);
     if (pile_indels) fprintf(stderr, "%s: pileup indels deletions %lld insertions %lld ins_discordant %lld gapped_sides %lld\n", PROG, pile_del, pile_ins, pile_insd, pile_gapped);
+    if (call) fprintf(stderr, "%s: calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, call_calls, call_cands, call_tested, call_deep);
     return 0;
 }
