@@ -481,6 +481,44 @@ int mipgen_accel_call_fetch(mipgen_accel* h, mipgen_call_record* records, int64_
  * discordant and leaves the rest 0): a caller that writes the pileup from that call's counts needs no second count.  MIPGEN_E_STATE before such a call. */
 int mipgen_accel_reads_consensus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals);
 
+/* ---- pileup and calls per genome locus, merged over the probes that cover it (new entry points only: the ABI number does not change) ----
+ * A LOCUS is one genome base; a session has n_pos template positions x (the rows of the pileup tables) and n_loci loci, both 1..2^29 - 1.  The PLAN holds one int64
+ * per template position: -1 - the position contributes to no locus - or locus * 4 + flags with 0 <= locus < n_loci; flag bit 0: the probe is on the minus strand;
+ * flag bit 1: the insertion columns of this source are those of row x - 1 (it needs x >= 1).  The library does not know what an arm is: the caller decides what is
+ * left out.  The MERGED row of a locus is the sum over its sources, in the column layout of the source table: a plus source adds its row as it is, a minus source
+ * adds A <-> T and C <-> G swapped (columns 0 <-> 3, 1 <-> 2), discordant and del as they are; the insertion columns (6, 7) are the source's own on a plus source and
+ * 0 on a minus one, and those of row x - 1 under bit 1 on either strand.  A locus without a source has a zero row.  totals: covered = loci with a non-zero counter,
+ * bases = the sum of A + C + G + T, then the column sums (the last three stay 0 with 5 columns).  A merged counter is a 32-bit sum: the sources of one locus must
+ * add up to fewer than 2^31 per column (they do whenever a locus takes at most one position per probe: a counter is then at most the groups of the session).
+ * Calls are the calls above with x := locus on the merged tables against locus_ref, the upper-case plus-strand base of every locus; mipgen_call_record.pos is the
+ * locus index; records are fetched with mipgen_accel_call_fetch.
+ *   locus_tables:      from host arrays, no read session needed: counts[n_pos][columns] -> merged[n_loci][columns] (may be NULL), which mipgen_accel_call_tables takes.
+ *   locus_plan:        installs plan and locus_ref for the consensus reads the handle holds; a second plan replaces the first and drops a locus pool
+ *                      (a plan refused with MIPGEN_E_INVALID or for its budget leaves the first and its pool as they were).
+ *   locus_pileup:      the pileup of `row` (max_indel 0: the 5-column table, mol_seq may be NULL; 1..15: the gapped one) counted into scratch of its own, then merged:
+ *                      probe_counts (may be NULL) is what the matching pileup call returns, locus_counts (may be NULL) n_loci x columns; pileup_totals as the gapped
+ *                      pileup's (the ungapped table fills groups, used, bases, discordant).
+ *   locus_call_pool:   consensus_call_pool with the merge between every row's count and the pool, over n_loci.
+ *   locus_call:        consensus_call likewise: probe_counts and locus_counts (either may be NULL) are those of locus_pileup with the pool's arguments.
+ * MIPGEN_E_INVALID: every refusal of the underlying pileup or call; NULL plan or ref; n_loci or n_pos outside 1..2^29 - 1; a plan entry below -1, or whose locus is
+ * >= n_loci; bit 1 at x = 0; a sum of mol_len different from the plan's n_pos; columns not 5 or 8.  MIPGEN_E_STATE: no consensus reads; no plan; locus_call without a
+ * locus pool or with params.bg_max_ppm different from the pool's.  MIPGEN_E_NOMEM: the plan (24 bytes per position, the sort's scratch and sorted pairs, 4 bytes per
+ * locus), the merged table, the pool and the candidate list over n_loci do not fit free memory; refused before anything is allocated.  The existing pileup and call
+ * entry points, their scratch and timing indices 11-13 are untouched by these calls. */
+typedef struct mipgen_locus_totals { int64_t covered, bases, discordant, deletions, insertions, ins_discordant; } mipgen_locus_totals;
+int mipgen_accel_locus_tables(mipgen_accel* h, const int32_t* counts, int32_t columns, const int64_t* plan, int64_t n_pos, int64_t n_loci, int32_t* merged,
+                              mipgen_locus_totals* totals);
+int mipgen_accel_reads_consensus_locus_plan(mipgen_accel* h, const int64_t* plan, int64_t n_pos, const uint8_t* locus_ref, int64_t n_loci);
+int mipgen_accel_reads_consensus_locus_pileup(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                              int32_t max_indel, int32_t* probe_counts, int32_t* locus_counts, mipgen_gapped_totals* pileup_totals, mipgen_locus_totals* totals);
+int mipgen_accel_reads_consensus_locus_call_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                                 int32_t max_indel, int32_t bg_max_ppm);
+int mipgen_accel_reads_consensus_locus_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* probe_counts, int32_t* locus_counts,
+                                            mipgen_call_totals* totals);
+/* The totals locus_pileup would have returned as pileup_totals for the row of the last mipgen_accel_reads_consensus_locus_call: a caller that writes the pileup from
+ * that call's probe_counts needs no second count.  MIPGEN_E_STATE before such a call. */
+int mipgen_accel_reads_consensus_locus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -695,7 +733,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * 9 = the two k_consensus_vote kernels of the last mipgen_accel_reads_finish_consensus, 10 = its sort of (key, pair id) and the run boundaries
  * (timing enabled); 11 = the pileup kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled); 12 = the kernels of the last
  * mipgen_accel_reads_consensus_pileup_gapped (timing enabled); 13 = the kernels of the last mipgen_accel_call_tables, mipgen_accel_reads_consensus_call (its pileup
- * included) or mipgen_accel_reads_consensus_call_pool (timing enabled). */
+ * included) or mipgen_accel_reads_consensus_call_pool (timing enabled); 14 = the kernels of the last locus call of any kind (mipgen_accel_locus_tables,
+ * mipgen_accel_reads_consensus_locus_*), its pileup included (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

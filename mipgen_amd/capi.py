@@ -102,6 +102,10 @@ class CallTotals(C.Structure):     # mipgen_call_totals
     _fields_ = [(n, C.c_int64) for n in ("tested", "too_deep", "candidates", "calls")]
 
 
+class LocusTotals(C.Structure):    # mipgen_locus_totals
+    _fields_ = [(n, C.c_int64) for n in ("covered", "bases", "discordant", "deletions", "insertions", "ins_discordant")]
+
+
 CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("allele", "<i4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4")])   # mipgen_call_record
 CALL_MAX_DEPTH = 1 << 20
 
@@ -401,9 +405,18 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_consensus_call.argtypes = [vp, C.c_int32, C.POINTER(CallParams), C.POINTER(C.c_int32), C.POINTER(CallTotals)]
     lib.mipgen_accel_call_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
     lib.mipgen_accel_reads_consensus_call_pileup_totals.argtypes = [vp, C.POINTER(GappedTotals)]
+    lib.mipgen_accel_locus_tables.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, i64p_, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(LocusTotals)]
+    lib.mipgen_accel_locus_tables.restype = C.c_int
+    lib.mipgen_accel_reads_consensus_locus_plan.argtypes = [vp, i64p_, C.c_int64, C.c_void_p, C.c_int64]
+    lib.mipgen_accel_reads_consensus_locus_pileup.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                              C.POINTER(C.c_int32), C.POINTER(GappedTotals), C.POINTER(LocusTotals)]
+    lib.mipgen_accel_reads_consensus_locus_call_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.mipgen_accel_reads_consensus_locus_call.argtypes = [vp, C.c_int32, C.POINTER(CallParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(CallTotals)]
+    lib.mipgen_accel_reads_consensus_locus_call_pileup_totals.argtypes = [vp, C.POINTER(GappedTotals)]
     lib.mipgen_accel_call_tables.restype = lib.mipgen_accel_call_fetch.restype = lib.mipgen_accel_reads_consensus_call_pileup_totals.restype = C.c_int
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
-                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped", "consensus_call_pool", "consensus_call"):
+                 "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped", "consensus_call_pool", "consensus_call",
+                 "consensus_locus_plan", "consensus_locus_pileup", "consensus_locus_call_pool", "consensus_locus_call", "consensus_locus_call_pileup_totals"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -487,6 +500,8 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_consensus_pileup_gapped",
     "mipgen_accel_call_tables", "mipgen_accel_reads_consensus_call_pool", "mipgen_accel_reads_consensus_call", "mipgen_accel_call_fetch",
     "mipgen_accel_reads_consensus_call_pileup_totals",
+    "mipgen_accel_locus_tables", "mipgen_accel_reads_consensus_locus_plan", "mipgen_accel_reads_consensus_locus_pileup",
+    "mipgen_accel_reads_consensus_locus_call_pool", "mipgen_accel_reads_consensus_locus_call", "mipgen_accel_reads_consensus_locus_call_pileup_totals",
 ]
 
 
@@ -515,6 +530,8 @@ class Accel:
         self._check(self.lib.mipgen_accel_create(C.byref(params), device, C.c_void_p(stream), C.byref(self.h)))
         self.grids: List[Grid] = []
         self._regions: Sequence[RegionData] = []
+        self._locus_shape = None                                         # (positions, loci) of the plan consensus_locus_plan installed last
+        self._locus_call_cols = None                                     # (positions, columns) of the pool consensus_locus_call_pool built last
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -1077,6 +1094,89 @@ class Accel:
         tot = GappedTotals()
         self._check(self.lib.mipgen_accel_reads_consensus_call_pileup_totals(self.h, C.byref(tot)))
         return {f[0]: int(getattr(tot, f[0])) for f in GappedTotals._fields_}
+
+    # ---- loci ----
+    @staticmethod
+    def _totals(tot) -> dict:
+        return {f[0]: int(getattr(tot, f[0])) for f in tot._fields_}
+
+    def locus_tables(self, counts, plan, n_loci: int):
+        """mipgen_accel_locus_tables: a count table from host arrays folded per locus, no read session needed.  counts: int32 [n_pos][5 or 8]; plan: int64 [n_pos], -1 or
+        locus * 4 + flags (bit 0: minus strand; bit 1: the insertion columns come from row x - 1).  Returns (merged int32 [n_loci][columns] - what call_tables takes -
+        and the totals dict: covered, bases, discordant, deletions, insertions, ins_discordant)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        plan = np.ascontiguousarray(plan, dtype=np.int64)
+        if counts.ndim != 2 or counts.shape[0] != len(plan):
+            raise ValueError(f"counts {counts.shape} do not match a plan of {len(plan)} positions")
+        merged = np.empty((max(int(n_loci), 0), counts.shape[1]), dtype=np.int32)
+        tot = LocusTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_locus_tables(self.h, counts.ctypes.data_as(i32p), counts.shape[1], plan.ctypes.data_as(C.POINTER(C.c_int64)), len(plan), n_loci,
+                                                       merged.ctypes.data_as(i32p), C.byref(tot)))
+        return merged, self._totals(tot)
+
+    def consensus_locus_plan(self, plan, locus_ref) -> None:
+        """mipgen_accel_reads_consensus_locus_plan, callable after consensus_reads: installs the plan (int64 per template position) and the upper-case plus-strand ref
+        byte of every locus; a second plan replaces the first and drops a locus pool."""
+        plan = np.ascontiguousarray(plan, dtype=np.int64)
+        ref = np.frombuffer(bytes(locus_ref), dtype=np.uint8) if isinstance(locus_ref, (bytes, bytearray)) else np.ascontiguousarray(locus_ref, dtype=np.uint8)
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_plan(self.h, plan.ctypes.data_as(C.POINTER(C.c_int64)), len(plan), ref.ctypes.data, len(ref)))
+        self._locus_shape, self._locus_call_cols = (len(plan), len(ref)), None
+
+    def _locus_out(self, rows, cols):
+        """An output table of a locus call and its pointer; (None, None) where no wrapper has installed what gives its shape: the library refuses such a call
+        (MIPGEN_E_STATE) before it writes anything, and takes NULL for a table that is not wanted."""
+        if rows is None:
+            return None, None
+        a = np.empty((rows, cols), dtype=np.int32)
+        return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+    @staticmethod
+    def _templates(mol_seq, mol_len):
+        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
+        total = int(lens.astype(np.int64).clip(min=0).sum())
+        seq = None
+        if mol_seq is not None:
+            seq = bytes((mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper())
+            if len(seq) != total:
+                raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
+        return lens, total, seq
+
+    def consensus_locus_pileup(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 0):
+        """mipgen_accel_reads_consensus_locus_pileup, callable after consensus_locus_plan: one row counted per template position and folded per locus.  max_indel 0:
+        the 5-column table (mol_seq may be None); 1..15: the gapped one.  Returns (probe_counts - what the matching pileup call returns -, locus_counts
+        [n_loci][columns], the pileup's totals dict as consensus_pileup_gapped names them, the locus totals dict)."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        cols = 8 if max_indel else 5
+        probe, probe_p = self._locus_out(total, cols)
+        loci, loci_p = self._locus_out(self._locus_shape[1] if self._locus_shape else None, cols)
+        pt, lt = GappedTotals(), LocusTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_pileup(self.h, seq, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), row, min_family, min_quality,
+                                                                       max_indel, probe_p, loci_p, C.byref(pt), C.byref(lt)))
+        return probe, loci, self._totals(pt), self._totals(lt)
+
+    def consensus_locus_call_pool(self, mol_seq, mol_len: Sequence[int], min_family: int = 1, min_quality: int = 0, max_indel: int = 0, bg_max_ppm: int = 200000) -> None:
+        """mipgen_accel_reads_consensus_locus_call_pool, callable after consensus_locus_plan: the background pool per locus over the sample rows of the session."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_call_pool(self.h, seq, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), min_family, min_quality, max_indel,
+                                                                          bg_max_ppm))
+        self._locus_call_cols = (total, 8 if max_indel else 5)
+
+    def consensus_locus_call(self, row: int, params: "CallParams"):
+        """mipgen_accel_reads_consensus_locus_call, callable after consensus_locus_call_pool: the calls of one row per locus.  Returns (probe_counts, locus_counts,
+        records - pos is the locus index -, totals dict)."""
+        total, cols = self._locus_call_cols or (None, 0)
+        probe, probe_p = self._locus_out(total, cols)
+        loci, loci_p = self._locus_out(self._locus_shape[1] if self._locus_shape and total is not None else None, cols)
+        tot = CallTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_call(self.h, row, C.byref(params), probe_p, loci_p, C.byref(tot)))
+        return probe, loci, self.call_fetch(int(tot.calls)), self._totals(tot)
+
+    def consensus_locus_call_pileup_totals(self) -> dict:
+        """mipgen_accel_reads_consensus_locus_call_pileup_totals: the pileup totals of the row consensus_locus_call counted last."""
+        tot = GappedTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_call_pileup_totals(self.h, C.byref(tot)))
+        return self._totals(tot)
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

@@ -200,18 +200,58 @@ struct CallRun {
     void release() { cand.release(); records.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release(); ctr.release();
                      counts.release(); pool.release(); ref.release(); n_calls = -1; }
 };
+// loci.  A plan on the device: src and first are what a merge reads; the rest is held only while the plan is built
+struct LocusPlan {
+    DevBuf<int64_t> plan;                                    // positions (transient)
+    DevBuf<uint64_t> keys, keys_sorted;                      // positions (transient)
+    DevBuf<uint32_t> ids, ids_sorted;                        // positions (transient)
+    DevBuf<char> temp;                                       // the sort's scratch (transient)
+    DevBuf<uint32_t> src, first;                             // positions: x << 2 | flags in locus order; loci + 1
+    int64_t n_pos = 0, n_loci = 0;
+    bool have = false;
+    size_t held() const { return plan.cap * 8 + (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap + src.cap + first.cap) * 4 + temp.cap; }
+    void release_transient() { plan.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release(); }
+    void release() { release_transient(); src.release(); first.release(); have = false; n_pos = n_loci = 0; }
+};
+// what mipgen_accel_locus_tables leaves on the HANDLE: its plan and the uploaded and merged tables
+struct LocusRun {
+    LocusPlan plan;
+    DevBuf<int32_t> counts, merged;
+    DevBuf<LocusCounters> ctr;
+    size_t held() const { return plan.held() + (counts.cap + merged.cap) * 4 + ctr.cap * sizeof(LocusCounters); }
+    void release() { plan.release(); counts.release(); merged.release(); ctr.release(); }
+};
+// mipgen_accel_reads_consensus_locus_* : the installed plan and locus_ref, a pileup scratch of each kind of its own (no locus call touches what the pileup or call
+// entry points hold), the merged table, the pool over the loci and the arguments it was built with; released with the reads, as CallScratch
+struct LocusScratch {
+    LocusPlan plan;
+    DevBuf<uint8_t> ref;                                     // loci
+    PileupScratch pile;
+    GappedScratch gapped;
+    DevBuf<int32_t> merged, pool;                            // loci x columns; loci x (K[5], N[5])
+    DevBuf<LocusCounters> ctr;
+    bool have_pool = false;
+    std::vector<int32_t> mol_len;
+    std::string mol_seq;
+    int32_t min_family = 1, min_quality = 0, max_indel = 0, bg_max_ppm = 0;
+    mipgen_gapped_totals last{0, 0, 0, 0, 0, 0, 0, 0};        // the pileup totals of the row mipgen_accel_reads_consensus_locus_call counted last
+    bool have_last = false;
+    size_t held() const { return plan.held() + ref.cap + pile.held() + gapped.held() + (merged.cap + pool.cap) * 4 + ctr.cap * sizeof(LocusCounters); }
+    void release() { plan.release(); ref.release(); pile.release(); gapped.release(); merged.release(); pool.release(); ctr.release(); have_pool = have_last = false; }
+};
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
     int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
     PileupScratch pile;
     GappedScratch gapped;
     CallScratch call;
+    LocusScratch locus;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); }
 };
 
 struct mipgen_accel {
@@ -337,6 +377,8 @@ struct mipgen_accel {
     double gapped_ms = -1.0;         // the kernels of the last mipgen_accel_reads_consensus_pileup_gapped (timing enabled)
     CallRun call_run;                // the last call's candidates and records (accel_pileup.hip)
     double call_ms = -1.0;           // the kernels of the last mipgen_accel_call_tables / _reads_consensus_call / _reads_consensus_call_pool (timing enabled)
+    LocusRun locus_run;              // the plan and tables of the last mipgen_accel_locus_tables (accel_pileup.hip)
+    double locus_ms = -1.0;          // the kernels of the last locus call of any kind, its pileup included (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -3,7 +3,9 @@
 // _reads_consensus_call_pool, _reads_consensus_call, _call_fetch).  A pileup is plan_row (every check, nothing allocated or launched), then count_plain / count_gapped:
 // the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches, download and totals of ONE row into the
 // scratch it is given.  The two pileup entry points give `pile` / `gapped` of the ConsensusResult, the calls give the pair inside its CallScratch: three callers of one
-// count, and no call touches what another holds.
+// count, and no call touches what another holds.  The locus calls (4.15: mipgen_accel_locus_tables, _reads_consensus_locus_plan / _locus_pileup / _locus_call_pool /
+// _locus_call) are a fourth caller, with the pair inside the LocusScratch: between the count and the pool or run_call they fold the row's table into one row per
+// genome locus (kernels_locus.hip) by the plan the caller installed.
 #include "accel_internal.h"
 #include "gapped_align.h"
 
@@ -245,6 +247,112 @@ static int run_call(mipgen_accel* h, const int32_t* counts, int columns, const i
 // the sample rows of a session: all but the last (undetermined) when it had barcodes, the one row otherwise
 static int64_t sample_rows(const ConsensusResult* R) { return R->rows > 1 ? R->rows - 1 : 1; }
 
+// ---- loci ------------------------------------------------------------------------------------------------------------------------------------
+// every refusal of a plan
+static int check_locus_plan(const int64_t* plan, int64_t n_pos, int64_t n_loci)
+{
+    if (!plan) return fail(MIPGEN_E_INVALID, "bad arguments: no locus plan");
+    if (n_loci < 1 || n_loci > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld loci: 1 to 2^29 - 1", (long long)n_loci);
+    if (n_pos < 1 || n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld positions: 1 to 2^29 - 1", (long long)n_pos);
+    for (int64_t x = 0; x < n_pos; x++) {
+        const int64_t e = plan[x];
+        if (e < -1) return fail(MIPGEN_E_INVALID, "locus plan entry %lld of position %lld: -1 or locus * 4 + flags", (long long)e, (long long)x);
+        if (e >= 0 && (e >> 2) >= n_loci) return fail(MIPGEN_E_INVALID, "locus %lld of position %lld: the plan has %lld loci", (long long)(e >> 2), (long long)x, (long long)n_loci);
+        if (e >= 0 && (e & 2) && x == 0) return fail(MIPGEN_E_INVALID, "locus plan entry %lld of position 0: bit 1 takes the insertion columns of row x - 1", (long long)e);
+    }
+    return MIPGEN_OK;
+}
+
+static int locus_end_bit(int64_t n_loci)                                 // the bits of the sentinel n_loci, the largest key
+{
+    int end_bit = 1;
+    while (end_bit < 64 && ((uint64_t)n_loci >> end_bit)) end_bit++;
+    return end_bit;
+}
+
+// A checked plan onto the device (timed as one span of `timer`): the budget - the plan, the pairs and the sorted pairs, the sort's scratch, src and first, and
+// `more_need` bytes the caller allocates next, against what is held and free - before anything is allocated; then keys, sort, sources and first.  The stream is idle
+// and only src and first are still held on success.  what: the call's name.
+static int build_locus_plan(mipgen_accel* h, LocusPlan& L, const int64_t* plan, int64_t n_pos, int64_t n_loci, size_t more_need, size_t more_held, const char* what,
+                            SpanTimer& timer)
+{
+    hipStream_t st = h->stream;
+    const size_t np = (size_t)n_pos, nl = (size_t)n_loci;
+    const int end_bit = locus_end_bit(n_loci);
+    size_t temp_bytes = 0;
+    HIP_TRY(mipgen_consensus_sort(st, nullptr, &temp_bytes, nullptr, nullptr, nullptr, nullptr, n_pos, end_bit));
+    const size_t need = 3 * padded(np, 8) + 3 * padded(np, 4) + padded(std::max<size_t>(temp_bytes, 1), 1) + padded(nl + 1, 4) + more_need;
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (need > L.held() + more_held + free_b)
+        return fail(MIPGEN_E_NOMEM, "%s: a plan of %lld positions and %lld loci needs up to %zu MiB of device memory, %zu MiB are free", what, (long long)n_pos,
+                    (long long)n_loci, need >> 20, (L.held() + more_held + free_b) >> 20);
+    L.have = false;
+    if (L.plan.reserve(np) || L.keys.reserve(np) || L.keys_sorted.reserve(np) || L.ids.reserve(np) || L.ids_sorted.reserve(np) || L.src.reserve(np) ||
+        L.first.reserve(nl + 1) || L.temp.reserve(std::max<size_t>(temp_bytes, 1)))
+        return MIPGEN_E_NOMEM;
+    temp_bytes = L.temp.cap;
+    IdleOnExit idle{st};                                                 // (the caller's plan outlives its copy)
+    HIP_TRY(hipMemcpyAsync(L.plan.p, plan, np * 8, hipMemcpyHostToDevice, st));
+    timer.mark();
+    HIP_TRY(mipgen_launch_locus_keys(st, L.plan.p, n_pos, n_loci, L.keys.p, L.ids.p));
+    HIP_TRY(mipgen_consensus_sort(st, L.temp.p, &temp_bytes, L.keys.p, L.keys_sorted.p, L.ids.p, L.ids_sorted.p, n_pos, end_bit));
+    HIP_TRY(mipgen_launch_locus_index(st, L.keys_sorted.p, L.ids_sorted.p, L.plan.p, n_pos, n_loci, L.src.p, L.first.p));
+    timer.mark();
+    HIP_TRY(idle.wait());
+    L.release_transient();
+    L.n_pos = n_pos; L.n_loci = n_loci; L.have = true;
+    return MIPGEN_OK;
+}
+
+// One table on the device folded into merged[n_loci][columns] there (reserved by the caller, as ctr) and summed: a span of `timer`; out (may be NULL) a copy, totals
+// (may be NULL) the sums.  The stream is idle on return.
+static int merge_loci(mipgen_accel* h, const LocusPlan& L, const int32_t* counts, int columns, int32_t* merged, LocusCounters* ctr, SpanTimer& timer, int32_t* out,
+                      mipgen_locus_totals* totals)
+{
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    LocusCounters lc;
+    HIP_TRY(hipMemsetAsync(ctr, 0, sizeof lc, st));
+    timer.mark();
+    HIP_TRY(mipgen_launch_locus_merge(st, counts, columns, L.src.p, L.first.p, L.n_pos, L.n_loci, merged, ctr));
+    timer.mark();
+    HIP_TRY(hipMemcpyAsync(&lc, ctr, sizeof lc, hipMemcpyDeviceToHost, st));
+    if (out) HIP_TRY(hipMemcpyAsync(out, merged, (size_t)L.n_loci * (size_t)columns * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    if (totals)
+        *totals = {(int64_t)lc.covered, (int64_t)lc.bases, (int64_t)lc.discordant, (int64_t)lc.deletions, (int64_t)lc.insertions, (int64_t)lc.ins_discordant};
+    return MIPGEN_OK;
+}
+
+// what the locus calls of a session share after plan_row: a plan is installed and is of this table
+static int check_locus_session(const LocusScratch& L, const RowPlan& P)
+{
+    if (!L.plan.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus plan: mipgen_accel_reads_consensus_locus_plan installs it");
+    if (P.n_pos != L.plan.n_pos)
+        return fail(MIPGEN_E_INVALID, "%lld template positions: the locus plan was installed for %lld", (long long)P.n_pos, (long long)L.plan.n_pos);
+    return MIPGEN_OK;
+}
+
+// One row counted into the locus scratch (probe_counts: a copy, may be NULL; pt: the pileup's totals, may be NULL) and folded into L.merged (locus_counts, lt likewise).
+static int count_and_merge(mipgen_accel* h, const RowPlan& P, LocusScratch& L, const Budget& B, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row,
+                           int32_t min_family, int32_t min_quality, int32_t max_indel, SpanTimer& timer, int32_t* probe_counts, int32_t* locus_counts,
+                           mipgen_gapped_totals* pt, mipgen_locus_totals* lt)
+{
+    const int32_t* table = nullptr;
+    if (max_indel) {
+        if (int rc = count_gapped(h, P, L.gapped, B, mol_seq, mol_len, n, row, min_family, min_quality, max_indel, timer, probe_counts, pt)) return rc;
+        table = L.gapped.counts.p;
+    } else {
+        mipgen_pileup_totals t{0, 0, 0, 0};
+        if (int rc = count_plain(h, P, L.pile, B, mol_len, n, row, min_family, min_quality, timer, probe_counts, &t)) return rc;
+        if (pt) *pt = {t.groups, t.used, t.bases, t.discordant, 0, 0, 0, 0};
+        table = L.pile.counts.p;
+    }
+    return merge_loci(h, L.plan, table, max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, L.merged.p, L.ctr.p, timer, locus_counts, lt);
+}
+
+
 extern "C" {
 
 // Allele counts per template position of one row from the consensus reads the handle holds.  Reads R's groups and reads; writes R->pile only.
@@ -397,6 +505,166 @@ int mipgen_accel_reads_consensus_call_pileup_totals(mipgen_accel* h, mipgen_gapp
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     if (!h->consensus || !h->consensus->call.have_last) return fail(MIPGEN_E_STATE, "no row was called: mipgen_accel_reads_consensus_call counts one");
     if (totals) *totals = h->consensus->call.last;
+    return MIPGEN_OK;
+}
+
+// A table from host arrays folded by a plan from host arrays: no read session is needed; everything is uploaded into the handle's LocusRun.
+int mipgen_accel_locus_tables(mipgen_accel* h, const int32_t* counts, int32_t columns, const int64_t* plan, int64_t n_pos, int64_t n_loci, int32_t* merged,
+                              mipgen_locus_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!counts) return fail(MIPGEN_E_INVALID, "bad arguments: no counts");
+    if (columns != PILEUP_COLUMNS && columns != GAPPED_COLUMNS) return fail(MIPGEN_E_INVALID, "%d columns: %d (the pileup's table) or %d (the gapped one)", columns, PILEUP_COLUMNS, GAPPED_COLUMNS);
+    if (int rc = check_locus_plan(plan, n_pos, n_loci)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    LocusRun& U = h->locus_run;
+    h->locus_ms = -1.0;
+    const size_t np = (size_t)n_pos, nl = (size_t)n_loci, cols = (size_t)columns;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = build_locus_plan(h, U.plan, plan, n_pos, n_loci, padded(np * cols, 4) + padded(nl * cols, 4) + padded(1, sizeof(LocusCounters)),
+                                  (U.counts.cap + U.merged.cap) * 4 + U.ctr.cap * sizeof(LocusCounters), "locus tables", timer)) return rc;
+    if (U.counts.reserve(np * cols) || U.merged.reserve(nl * cols) || U.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    {
+        IdleOnExit idle{h->stream};
+        HIP_TRY(hipMemcpyAsync(U.counts.p, counts, np * cols * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (int rc = merge_loci(h, U.plan, U.counts.p, columns, U.merged.p, U.ctr.p, timer, merged, totals)) return rc;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->locus_ms = ms;
+    return MIPGEN_OK;
+}
+
+// The plan and the ref bytes of the loci for the consensus reads the handle holds.  Writes R->locus only; a pool over an earlier plan is dropped.
+int mipgen_accel_reads_consensus_locus_plan(mipgen_accel* h, const int64_t* plan, int64_t n_pos, const uint8_t* locus_ref, int64_t n_loci)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    if (!locus_ref) return fail(MIPGEN_E_INVALID, "bad arguments: no ref bytes of the loci");
+    if (int rc = check_locus_plan(plan, n_pos, n_loci)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    LocusScratch& L = h->consensus->locus;
+    h->locus_ms = -1.0;
+    SpanTimer timer{h->timing, h->stream};
+    const int built = build_locus_plan(h, L.plan, plan, n_pos, n_loci, padded((size_t)n_loci, 1), L.ref.cap, "locus plan", timer);
+    if (!L.plan.have || built == MIPGEN_OK) L.have_pool = L.have_last = false;   // the pool goes with its plan: a plan refused for its budget leaves both as they were
+    if (built) return built;
+    L.plan.have = false;                                                 // (until the ref bytes are there too)
+    if (L.ref.reserve((size_t)n_loci)) return MIPGEN_E_NOMEM;
+    HIP_TRY(hipMemcpyAsync(L.ref.p, locus_ref, (size_t)n_loci, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    L.plan.have = true;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->locus_ms = ms;
+    return MIPGEN_OK;
+}
+
+// One row counted per template position and folded per locus.  Reads R's groups and reads and the installed plan; writes R->locus only.
+int mipgen_accel_reads_consensus_locus_pileup(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                              int32_t max_indel, int32_t* probe_counts, int32_t* locus_counts, mipgen_gapped_totals* pileup_totals, mipgen_locus_totals* totals)
+{
+    RowPlan P;
+    const GappedArgs args{mol_seq, max_indel};
+    if (int rc = plan_row(h, mol_len, n, row, min_family, min_quality, max_indel ? &args : nullptr, &P)) return rc;
+    LocusScratch& L = P.R->locus;
+    if (int rc = check_locus_session(L, P)) return rc;
+    h->locus_ms = -1.0;
+    const size_t nl = (size_t)L.plan.n_loci, cols = max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS;
+    const size_t more = padded(nl * cols, 4) + padded(1, sizeof(LocusCounters));
+    const auto held = [&] { return L.merged.cap * 4 + L.ctr.cap * sizeof(LocusCounters); };
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (more > held() + free_b)
+        return fail(MIPGEN_E_NOMEM, "locus pileup: %lld loci need %zu MiB of device memory beside the pileup's, %zu MiB are free", (long long)L.plan.n_loci, more >> 20,
+                    (held() + free_b) >> 20);
+    if (L.merged.reserve(nl * cols) || L.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    const Budget B{"locus pileup", more, held(), true};                  // held AFTER the reserves: what they took is no longer free, and the count tests need <= held + free
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = count_and_merge(h, P, L, B, mol_seq, mol_len, n, row, min_family, min_quality, max_indel, timer, probe_counts, locus_counts, pileup_totals, totals)) return rc;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->locus_ms = ms;
+    return MIPGEN_OK;
+}
+
+// The pool over the sample rows of the session, per locus: every row counted, folded and added on the device.  Writes R->locus only.
+int mipgen_accel_reads_consensus_locus_call_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                                 int32_t max_indel, int32_t bg_max_ppm)
+{
+    RowPlan P;
+    const GappedArgs args{mol_seq, max_indel};
+    if (int rc = plan_row(h, mol_len, n, 0, min_family, min_quality, max_indel ? &args : nullptr, &P)) return rc;
+    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    ConsensusResult* R = P.R;
+    LocusScratch& L = R->locus;
+    if (int rc = check_locus_session(L, P)) return rc;
+    L.have_pool = L.have_last = false;                                   // (a pool that fails leaves none)
+    h->locus_ms = -1.0;
+    const int64_t n_loci = L.plan.n_loci;
+    const size_t nl = (size_t)n_loci, cols = max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS;
+    // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_plain's / count_gapped's
+    const size_t more = padded(nl * cols, 4) + padded(nl * 10, 4) + padded(1, sizeof(LocusCounters)) + call_run_bytes(n_loci);
+    const auto held = [&] { return (L.merged.cap + L.pool.cap) * 4 + L.ctr.cap * sizeof(LocusCounters) + h->call_run.held(); };
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    if (more > held() + free_b)
+        return fail(MIPGEN_E_NOMEM, "locus call pool: %lld loci need up to %zu MiB of device memory beside the pileup's, %zu MiB are free", (long long)n_loci, more >> 20,
+                    (held() + free_b) >> 20);
+    if (L.merged.reserve(nl * cols) || L.pool.reserve(nl * 10) || L.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    const Budget B{"locus call pool", more, held(), true};               // held AFTER the reserves, as in the locus pileup
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemsetAsync(L.pool.p, 0, nl * 40, st));
+    SpanTimer timer{h->timing, st};
+    for (int64_t r = 0; r < sample_rows(R); r++) {
+        if (int rc = count_and_merge(h, P, L, B, mol_seq, mol_len, n, (int32_t)r, min_family, min_quality, max_indel, timer, nullptr, nullptr, nullptr, nullptr)) return rc;
+        timer.mark();
+        HIP_TRY(mipgen_launch_call_pool(st, L.merged.p, (int)cols, n_loci, bg_max_ppm, L.pool.p));
+        timer.mark();
+    }
+    HIP_TRY(idle.wait());
+    L.mol_len.assign(mol_len, mol_len + n);
+    if (mol_seq) L.mol_seq.assign(mol_seq, (size_t)P.n_pos); else L.mol_seq.clear();
+    L.min_family = min_family; L.min_quality = min_quality; L.max_indel = max_indel; L.bg_max_ppm = bg_max_ppm;
+    L.have_pool = true;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->locus_ms = ms;
+    return MIPGEN_OK;
+}
+
+// The calls of one row per locus against the locus pool: the row counted with the pool's arguments and folded, then run_call over the loci.
+int mipgen_accel_reads_consensus_locus_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* probe_counts, int32_t* locus_counts,
+                                            mipgen_call_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    LocusScratch& L = h->consensus->locus;
+    if (!L.plan.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus plan: mipgen_accel_reads_consensus_locus_plan installs it");
+    if (!L.have_pool) return fail(MIPGEN_E_STATE, "the consensus reads have no locus pool: mipgen_accel_reads_consensus_locus_call_pool builds it");
+    RowPlan P;
+    const GappedArgs args{L.mol_seq.data(), L.max_indel};
+    const int32_t n = (int32_t)L.mol_len.size();
+    if (int rc = plan_row(h, L.mol_len.data(), n, row, L.min_family, L.min_quality, L.max_indel ? &args : nullptr, &P)) return rc;
+    if (int rc = check_call_params(params)) return rc;
+    if (params->bg_max_ppm != L.bg_max_ppm) return fail(MIPGEN_E_STATE, "bg_max_ppm %d: the locus pool was built with %d", params->bg_max_ppm, L.bg_max_ppm);
+    h->locus_ms = -1.0;
+    h->call_run.n_calls = -1;
+    const Budget B{"locus call", call_run_bytes(L.plan.n_loci), h->call_run.held(), true};
+    SpanTimer timer{h->timing, h->stream};
+    L.have_last = false;
+    if (int rc = count_and_merge(h, P, L, B, L.mol_seq.data(), L.mol_len.data(), n, row, L.min_family, L.min_quality, L.max_indel, timer, probe_counts, locus_counts, &L.last,
+                                 nullptr)) return rc;
+    L.have_last = true;
+    if (int rc = run_call(h, L.merged.p, L.max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, L.pool.p, L.ref.p, L.plan.n_loci, (int64_t)row < sample_rows(P.R), *params, timer, totals))
+        return rc;
+    double ms = 0.0;
+    if (timer.add_to(&ms)) h->locus_ms = ms;
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_consensus_locus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus || !h->consensus->locus.have_last) return fail(MIPGEN_E_STATE, "no row was called per locus: mipgen_accel_reads_consensus_locus_call counts one");
+    if (totals) *totals = h->consensus->locus.last;
     return MIPGEN_OK;
 }
 

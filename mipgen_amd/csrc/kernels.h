@@ -61,6 +61,9 @@ struct PileRow {
 struct CallCounters { unsigned long long tested, too_deep, candidates, calls; };
 #define MIPGEN_CALL_MAX_POSITIONS (((int64_t)1 << 29) - 1)
 
+// loci: the totals of a merged table, as k_locus_sum counts them
+struct LocusCounters { unsigned long long covered, bases, discordant, deletions, insertions, ins_discordant; };
+
 extern "C" {
 // kernels_logistic.hip
 size_t mipgen_logistic_lds_bytes(int span);
@@ -183,4 +186,11 @@ hipError_t mipgen_launch_call_flag(hipStream_t, const int32_t* counts, int colum
                                    const CallModel& P, mipgen_call_record* cand, CallCounters* ctr);
 hipError_t mipgen_launch_call_tail(hipStream_t, mipgen_call_record* cand, int64_t n_cand, int64_t n_pos, const CallModel& P, uint64_t* keys, uint32_t* ids, CallCounters* ctr);
 hipError_t mipgen_launch_call_gather(hipStream_t, const mipgen_call_record* cand, const uint32_t* ids, int64_t n_cand, const CallCounters* ctr, mipgen_call_record* records);
+// kernels_locus.hip: the (locus, x) pairs of a plan for the sort; src[n_pos] and first[n_loci + 1] from the sorted pairs; a count table folded into
+// merged[n_loci][columns] and its totals (ctr zero on entry)
+hipError_t mipgen_launch_locus_keys(hipStream_t, const int64_t* plan, int64_t n_pos, int64_t n_loci, uint64_t* keys, uint32_t* ids);
+hipError_t mipgen_launch_locus_index(hipStream_t, const uint64_t* keys_sorted, const uint32_t* ids_sorted, const int64_t* plan, int64_t n_pos, int64_t n_loci, uint32_t* src,
+                                     uint32_t* first);
+hipError_t mipgen_launch_locus_merge(hipStream_t, const int32_t* counts, int columns, const uint32_t* src, const uint32_t* first, int64_t n_pos, int64_t n_loci,
+                                     int32_t* merged, LocusCounters* ctr);
 }

@@ -21,21 +21,7 @@
 #include "kernels.h"
 #include "device_utils.h"
 #include "call_model.h"
-
-typedef int call_v4i __attribute__((ext_vector_type(4)));
-struct CallRow4 { call_v4i v; } __attribute__((packed, aligned(4)));       // four counters of a row that is only 4-byte aligned
-
-// the 5 or 8 counters of position x into c[8] (the columns a 5-column row lacks stay 0)
-__device__ static inline void call_load_row(const int32_t* __restrict__ counts, int columns, int64_t x, int32_t c[8])
-{
-    if (columns == 8) {
-        const call_v4i a = *(const call_v4i*)(counts + x * 8), b = *(const call_v4i*)(counts + x * 8 + 4);
-        c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = b.x; c[5] = b.y; c[6] = b.z; c[7] = b.w;
-    } else {
-        const call_v4i a = ((const CallRow4*)(counts + x * 5))->v;
-        c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = counts[x * 5 + 4]; c[5] = 0; c[6] = 0; c[7] = 0;
-    }
-}
+#include "count_row.h"
 
 __global__ __launch_bounds__(256) void k_call_pool(const int32_t* __restrict__ counts, int columns, int64_t n_pos, int32_t bg_max_ppm, int32_t* __restrict__ pool)
 {

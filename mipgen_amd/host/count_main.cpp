@@ -52,6 +52,18 @@
 //                           base); alt_ppm = floor(alt_count 10^6 / depth); bg_alt, bg_depth: the background without this row
 //   -call_min_depth 20  -call_min_alt 3  -call_min_ppm 0  -call_min_q 30  -call_prior 1,1000  -call_background_max_ppm 200000     the parameters of the model
 //   stderr     a last line: "mipgen_count: calls C candidates K tested P too_deep D"
+// Pileup and calls per genome locus, merged over the probes that cover it (without these options every byte written is what it was):
+//   -pileup_loci LOCI       needs -pileup: per (sample, genome base) the counts of -pileup summed over every probe whose template covers the base, minus-strand probes
+//                           folded into plus orientation first.  Header ">sample <tab> chr <tab> position <tab> ref <tab> probes <tab> A <tab> C <tab> G <tab> T <tab>
+//                           discordant" (and del, ins, ins_discordant under -pileup_indels); one line per (sample, locus) with a non-zero counter, samples in row order,
+//                           loci by chromosome in order of first appearance in the tables, then by position; probes = the template positions that land on the locus
+//   -loci_parts target|all  what of a probe contributes: its target only (the default: a read's arm bases are the probe oligo, not the sample) or the arms too.  Two
+//                           probes that give one locus different ref bases are an error that names both table rows
+//   -call_loci CALLS        needs -pileup_loci: the calls of -call made per locus on the merged counts - pool, leave-one-out, filters and score over loci - under the
+//                           -call_* options, which now apply to -call, -call_loci or both.  Header ">sample <tab> chr <tab> position <tab> ref <tab> alt <tab> depth
+//                           <tab> alt_count <tab> alt_ppm <tab> bg_alt <tab> bg_depth <tab> q <tab> probes"; a deleted base prints alt "-"
+//   stderr     after the lines above: "mipgen_count: loci L lines P bases B nonref R discordant D" and, with -call_loci, "mipgen_count: locus calls C candidates K
+//              tested P too_deep D"
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -61,6 +73,7 @@
 #include <mutex>
 #include <thread>
 
+#include "locus_plan.hpp"
 #include "mip_table.hpp"
 
 static const char* PROG = "mipgen_count";
@@ -84,7 +97,9 @@ static int usage(const std::string& msg)
             "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n"
             "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n"
             "-call file : with -pileup, variant calls of every sample against the background of the others; -call_min_depth n (default 20), -call_min_alt k (3), -call_min_ppm p (0),\n"
-            "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n");
+            "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n"
+            "-pileup_loci file : with -pileup, the counts per genome base, summed over the probes that cover it; -loci_parts target|all : what of a probe counts (default target)\n"
+            "-call_loci file : with -pileup_loci, the variant calls per genome base on the merged counts, under the -call_* options\n");
     return 1;
 }
 
@@ -188,7 +203,8 @@ int main(int argc, char** argv)
     bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
     std::string consensus_prefix, pileup_path, call_path;
     mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
-    bool call_option_given = false;
+    bool call_option_given = false, loci_parts_given = false, loci_all = false;
+    std::string loci_path, call_loci_path;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
@@ -224,6 +240,9 @@ int main(int argc, char** argv)
         else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
         else if (a == "-pileup_indels") { if (!svr_parse_int(v.c_str(), &pile_indels) || pile_indels < 1 || pile_indels > 15) return usage("-pileup_indels must be 1 to 15"); }
         else if (a == "-call") { if (v.empty()) return usage("-call takes a file"); call_path = v; }
+        else if (a == "-pileup_loci") { if (v.empty()) return usage("-pileup_loci takes a file"); loci_path = v; }
+        else if (a == "-call_loci") { if (v.empty()) return usage("-call_loci takes a file"); call_loci_path = v; }
+        else if (a == "-loci_parts") { if (v != "target" && v != "all") return usage("-loci_parts must be target or all"); loci_all = v == "all"; loci_parts_given = true; }
         else if (a == "-call_min_depth") { if (!svr_parse_int(v.c_str(), &iv) || iv < 1 || iv > INT32_MAX) return usage("-call_min_depth must be 1 or more"); call_prm.min_depth = (int32_t)iv; call_option_given = true; }
         else if (a == "-call_min_alt") { if (!svr_parse_int(v.c_str(), &iv) || iv < 1 || iv > INT32_MAX) return usage("-call_min_alt must be 1 or more"); call_prm.min_alt = (int32_t)iv; call_option_given = true; }
         else if (a == "-call_min_ppm") { if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1000000) return usage("-call_min_ppm must be 0 to 1000000"); call_prm.min_ppm = (int32_t)iv; call_option_given = true; }
@@ -257,7 +276,10 @@ int main(int argc, char** argv)
     if (pile_indels && !pileup) return usage("-pileup_indels needs -pileup file");
     const bool call = !call_path.empty();
     if (call && !pileup) return usage("-call needs -pileup file");
-    if (call_option_given && !call) return usage("the -call_* options need -call file");
+    const bool loci = !loci_path.empty(), call_loci = !call_loci_path.empty();
+    if (loci && !pileup) return usage("-pileup_loci needs -pileup file");
+    if ((call_loci || loci_parts_given) && !loci) return usage("-call_loci and -loci_parts need -pileup_loci file");
+    if (call_option_given && !call && !call_loci) return usage("the -call_* options need -call file or -call_loci file");
     if (pileup && te + tl == 0) return usage("-pileup needs tag bases: with -tag_sizes 0,0 there are no molecules to count");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
@@ -312,7 +334,7 @@ int main(int argc, char** argv)
             if (!row_coords(*r, &c, &what)) { fprintf(stderr, "%s: -pileup: probe %s: %s\n", PROG, (*r)[COL_KEY].c_str(), what); return 1; }
             coords.push_back(c);
             mol_len.push_back((int32_t)((*r)[COL_EXT_SEQ].size() + (*r)[COL_INS_SEQ].size() + (*r)[COL_LIG_SEQ].size()));
-            if (pile_indels || call) {                                                   // (-call: the templates supply the ref bytes)
+            if (pile_indels || call || loci) {                                           // (-call, -pileup_loci: the templates supply the ref bytes)
                 if (pile_indels && mol_len.back() > MIPGEN_GAPPED_MAX_MOL) {
                     fprintf(stderr, "%s: -pileup_indels: probe %s: a molecule of %d bases (at most %d are placed)\n", PROG, (*r)[COL_KEY].c_str(), mol_len.back(), MIPGEN_GAPPED_MAX_MOL);
                     return 1;
@@ -321,6 +343,25 @@ int main(int argc, char** argv)
                     for (char ch : *part) mol_seq.push_back((char)toupper((unsigned char)ch));
             }
         }
+    // -pileup_loci: the plan, before the device is opened
+    locus::Plan lplan;
+    if (loci) {
+        std::vector<locus::Row> lrows;
+        for (size_t i = 0, at = 0; i < rows.size(); at += (size_t)mol_len[i], i++) {
+            const auto& f = *rows[i];
+            locus::Row r;
+            r.chr = f[COL_CHR]; r.ext_start = coords[i].ext_start; r.ext_stop = coords[i].ext_stop; r.minus = coords[i].minus;
+            r.n_ext = f[COL_EXT_SEQ].size(); r.n_lig = f[COL_LIG_SEQ].size(); r.mol = mol_seq.substr(at, (size_t)mol_len[i]);
+            lrows.push_back(r);
+        }
+        locus::Conflict bad;
+        if (!locus::build_plan(lrows, loci_all, &lplan, &bad))
+            return usage("-pileup_loci: locus " + bad.chr + ":" + std::to_string(bad.position) + ": table row " + std::to_string(bad.row_a + 1) + " (" + (*rows[bad.row_a])[COL_KEY] +
+                         ") gives ref " + std::string(1, bad.ref_a) + ", table row " + std::to_string(bad.row_b + 1) + " (" + (*rows[bad.row_b])[COL_KEY] + ") gives ref " +
+                         std::string(1, bad.ref_b));
+        if (lplan.locus_pos.empty()) return usage("-pileup_loci: no template position is included: the targets of the tables are empty (-loci_parts all keeps the arms)");
+        if (lplan.plan.size() > ((size_t)1 << 29) - 1) return usage("-pileup_loci: more than 2^29 - 1 template positions");
+    }
     if (shortest < 12) { fprintf(stderr, "%s: the shortest arm of the tables has %zu bases: a seed of fewer than 12 bases is refused\n", PROG, shortest); return 1; }
     Fastq fe, fl;
     fe.path = swap ? reads_b : reads_a; fl.path = swap ? reads_a : reads_b;
@@ -358,6 +399,9 @@ int main(int argc, char** argv)
     if (pileup && !(pile_out = fopen(pileup_path.c_str(), "w"))) return usage("-pileup " + pileup_path + ": can't write " + pileup_path);
     FILE* call_out = nullptr;
     if (call && !(call_out = fopen(call_path.c_str(), "w"))) return usage("-call " + call_path + ": can't write " + call_path);
+    FILE *loci_out = nullptr, *call_loci_out = nullptr;
+    if (loci && !(loci_out = fopen(loci_path.c_str(), "w"))) return usage("-pileup_loci " + loci_path + ": can't write " + loci_path);
+    if (call_loci && !(call_loci_out = fopen(call_loci_path.c_str(), "w"))) return usage("-call_loci " + call_loci_path + ": can't write " + call_loci_path);
 
     // ---- the device ----
     mipgen_accel* h = nullptr;
@@ -450,6 +494,7 @@ int main(int argc, char** argv)
     // -pileup: one call per row; a second thread turns the counts of a row into lines while the device counts the next row
     long long pile_used = 0, pile_lines = 0, pile_bases = 0, pile_nonref = 0, pile_disc = 0, pile_del = 0, pile_ins = 0, pile_insd = 0, pile_gapped = 0;
     long long call_calls = 0, call_cands = 0, call_tested = 0, call_deep = 0;
+    long long loci_lines = 0, loci_bases = 0, loci_nonref = 0, loci_disc = 0, lcall_calls = 0, lcall_cands = 0, lcall_tested = 0, lcall_deep = 0;
     const size_t pile_cols = pile_indels ? 8 : 5;
     if (pileup) {
         int64_t n_pos = 0;
@@ -528,6 +573,51 @@ int main(int argc, char** argv)
             }
             fwrite(text.data(), 1, text.size(), call_out);
         };
+        // -pileup_loci: the merged table of a row as lines (it is in plus orientation already, the insertion columns on their lower coordinate); -call_loci: the
+        // records of a row, ascending (locus, allele class), which is the printed order A C G T -
+        const size_t n_loci = lplan.locus_pos.size();
+        std::vector<int32_t> ltable[2] = {std::vector<int32_t>(n_loci * pile_cols), std::vector<int32_t>(n_rows > 1 ? n_loci * pile_cols : 0)};
+        std::vector<mipgen_call_record> lrecs[2];
+        auto write_loci = [&](size_t r, const std::vector<int32_t>& merged, const std::vector<mipgen_call_record>& rec) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text;
+            char buf[200];
+            for (size_t l = 0; l < n_loci; l++) {
+                const int32_t* k = &merged[l * pile_cols];
+                int32_t any = 0;
+                for (size_t c = 0; c < pile_cols; c++) any |= k[c];
+                if (!any) continue;
+                const char ref = lplan.locus_ref[l];
+                for (int b = 0; b < 4; b++) { loci_bases += k[b]; if ("ACGT"[b] != ref) loci_nonref += k[b]; }
+                loci_disc += k[4];
+                int at = snprintf(buf, sizeof buf, "\t%ld\t%c\t%d\t%d\t%d\t%d\t%d\t%d", lplan.locus_pos[l], ref, lplan.sources[l], k[0], k[1], k[2], k[3], k[4]);
+                if (pile_indels) at += snprintf(buf + at, sizeof buf - (size_t)at, "\t%d\t%d\t%d", k[5], k[6], k[7]);
+                snprintf(buf + at, sizeof buf - (size_t)at, "\n");
+                text.append(sample).append("\t").append(lplan.chroms[(size_t)lplan.locus_chr[l]]).append(buf);
+                loci_lines++;
+            }
+            fwrite(text.data(), 1, text.size(), loci_out);
+            if (!call_loci) return;
+            text.clear();
+            for (const mipgen_call_record& q : rec) {
+                const size_t l = (size_t)q.pos;
+                snprintf(buf, sizeof buf, "\t%ld\t%c\t%c\t%d\t%d\t%lld\t%d\t%d\t%d\t%d\n", lplan.locus_pos[l], lplan.locus_ref[l], "ACGT-"[q.allele], q.depth, q.alt,
+                         (long long)q.alt * 1000000ll / q.depth, q.bg_alt, q.bg_depth, q.q, lplan.sources[l]);
+                text.append(sample).append("\t").append(lplan.chroms[(size_t)lplan.locus_chr[l]]).append(buf);
+            }
+            fwrite(text.data(), 1, text.size(), call_loci_out);
+        };
+        if (loci) {
+            fputs(pile_indels ? ">sample\tchr\tposition\tref\tprobes\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n" : ">sample\tchr\tposition\tref\tprobes\tA\tC\tG\tT\tdiscordant\n",
+                  loci_out);
+            if (mipgen_accel_reads_consensus_locus_plan(h, lplan.plan.data(), (int64_t)lplan.plan.size(), (const uint8_t*)lplan.locus_ref.data(), (int64_t)n_loci) != MIPGEN_OK)
+                return die();
+        }
+        if (call_loci) {
+            fputs(">sample\tchr\tposition\tref\talt\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\tprobes\n", call_loci_out);
+            if (mipgen_accel_reads_consensus_locus_call_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
+                                                             call_prm.bg_max_ppm) != MIPGEN_OK) return die();
+        }
         if (call) {
             fputs(">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\talt\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\n", call_out);
             if (mipgen_accel_reads_consensus_call_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
@@ -544,10 +634,30 @@ int main(int argc, char** argv)
             if (call) {                                                                  // one call per row feeds both files: its counts are the pileup's
                 prc = mipgen_accel_reads_consensus_call(h, (int32_t)r, &call_prm, table[r & 1].data(), &ct);
                 if (prc == MIPGEN_OK) prc = mipgen_accel_reads_consensus_call_pileup_totals(h, &gt);
-                if (writer.joinable()) writer.join();                                    // (recs[r & 1] is the writer's until then)
+                if (!loci && writer.joinable()) writer.join();                           // (not needed for the buffers - the running writer, of row r - 1, owns index
+                                                                                         // (r - 1) & 1 of each - and kept where no locus option is given; with one, the join
+                                                                                         // below lets the locus count of the row run beside the writing too)
                 if (prc == MIPGEN_OK) { recs[r & 1].resize((size_t)ct.calls); prc = mipgen_accel_call_fetch(h, recs[r & 1].data(), ct.calls); }
                 pt.used = gt.used;
                 call_calls += ct.calls; call_cands += ct.candidates; call_tested += ct.tested; call_deep += ct.too_deep;
+                if (loci && prc == MIPGEN_OK) {                                          // beside -call: the locus call of the row feeds LOCI (and CALLS of -call_loci) only
+                    mipgen_call_totals lct{0, 0, 0, 0};
+                    prc = call_loci ? mipgen_accel_reads_consensus_locus_call(h, (int32_t)r, &call_prm, nullptr, ltable[r & 1].data(), &lct)
+                                    : mipgen_accel_reads_consensus_locus_pileup(h, pile_indels ? mol_seq.data() : nullptr, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
+                                                                                (int32_t)pile_quality, (int32_t)pile_indels, nullptr, ltable[r & 1].data(), nullptr, nullptr);
+                    if (prc == MIPGEN_OK && call_loci) { lrecs[r & 1].resize((size_t)lct.calls); prc = mipgen_accel_call_fetch(h, lrecs[r & 1].data(), lct.calls); }
+                    lcall_calls += lct.calls; lcall_cands += lct.candidates; lcall_tested += lct.tested; lcall_deep += lct.too_deep;
+                }
+            } else if (loci) {                                                           // one locus call per row feeds FILE and LOCI (and CALLS of -call_loci)
+                mipgen_locus_totals lt;
+                mipgen_call_totals lct{0, 0, 0, 0};
+                prc = call_loci ? mipgen_accel_reads_consensus_locus_call(h, (int32_t)r, &call_prm, table[r & 1].data(), ltable[r & 1].data(), &lct)
+                                : mipgen_accel_reads_consensus_locus_pileup(h, pile_indels ? mol_seq.data() : nullptr, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
+                                                                            (int32_t)pile_quality, (int32_t)pile_indels, table[r & 1].data(), ltable[r & 1].data(), &gt, &lt);
+                if (prc == MIPGEN_OK && call_loci) prc = mipgen_accel_reads_consensus_locus_call_pileup_totals(h, &gt);
+                if (prc == MIPGEN_OK && call_loci) { lrecs[r & 1].resize((size_t)lct.calls); prc = mipgen_accel_call_fetch(h, lrecs[r & 1].data(), lct.calls); }
+                pt.used = gt.used;
+                lcall_calls += lct.calls; lcall_cands += lct.candidates; lcall_tested += lct.tested; lcall_deep += lct.too_deep;
             } else
             prc = pile_indels ? mipgen_accel_reads_consensus_pileup_gapped(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
                                                                                      (int32_t)pile_quality, (int32_t)pile_indels, table[r & 1].data(), &gt)
@@ -557,11 +667,13 @@ int main(int argc, char** argv)
             if (writer.joinable()) writer.join();
             if (prc != MIPGEN_OK) return die();
             pile_used += pt.used;
-            writer = std::thread([&, r]() { write_row(r, table[r & 1]); if (call) write_calls(r, recs[r & 1]); });
+            writer = std::thread([&, r]() { write_row(r, table[r & 1]); if (call) write_calls(r, recs[r & 1]); if (loci) write_loci(r, ltable[r & 1], lrecs[r & 1]); });
         }
         if (writer.joinable()) writer.join();
         if (fclose(pile_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, pileup_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call && fclose(call_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (loci && fclose(loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (call_loci && fclose(call_loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
     }
     mipgen_accel_destroy(h);
 
@@ -642,5 +754,7 @@ int main(int argc, char** argv)
     if (pileup) fprintf(stderr, "%s: pileup molecules %lld positions %lld bases %lld nonref %lld discordant %lld\n", PROG, pile_used, pile_lines, pile_bases, pile_nonref, pile_disc);
     if (pile_indels) fprintf(stderr, "%s: pileup indels deletions %lld insertions %lld ins_discordant %lld gapped_sides %lld\n", PROG, pile_del, pile_ins, pile_insd, pile_gapped);
     if (call) fprintf(stderr, "%s: calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, call_calls, call_cands, call_tested, call_deep);
+    if (loci) fprintf(stderr, "%s: loci %zu lines %lld bases %lld nonref %lld discordant %lld\n", PROG, lplan.locus_pos.size(), loci_lines, loci_bases, loci_nonref, loci_disc);
+    if (call_loci) fprintf(stderr, "%s: locus calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, lcall_calls, lcall_cands, lcall_tested, lcall_deep);
     return 0;
 }
