@@ -1017,36 +1017,48 @@ class Accel:
                                  arena_bytes=arena_bytes, want_assignment=want_assignment)
         return out if want_assignment else out[:5]
 
+    # ---- pileups, calls and loci off the consensus reads ----
+    @staticmethod
+    def _totals(tot) -> dict:
+        return {f[0]: int(getattr(tot, f[0])) for f in tot._fields_}
+
+    @staticmethod
+    def _templates(mol_seq, mol_len):
+        """(mol_len as int32 array, its sum, mol_seq as one upper-case bytes object or None)."""
+        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
+        total = int(lens.astype(np.int64).clip(min=0).sum())
+        seq = None
+        if mol_seq is not None:
+            seq = bytes((mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper())
+            if len(seq) != total:
+                raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
+        return lens, total, seq
+
     def consensus_pileup(self, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0):
         """mipgen_accel_reads_consensus_pileup, callable after consensus_reads: allele counts per template position of every probe from the consensus reads the
         handle holds, for the groups of one row.  mol_len: the bytes of ext arm + scan target + lig arm per probe.  Returns (counts[sum(mol_len)][5] int32 - A, C,
         G, T, discordant, the bases in the orientation of the molecule; probe p starts at row sum(mol_len[:p]) - and the totals dict: groups, used, bases,
         discordant)."""
-        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
-        total = int(lens.astype(np.int64).clip(min=0).sum())
+        lens, total, _ = self._templates(None, mol_len)
         counts = np.empty((total, 5), dtype=np.int32)
         tot = PileupTotals()
         i32p = C.POINTER(C.c_int32)
         self._check(self.lib.mipgen_accel_reads_consensus_pileup(self.h, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, counts.ctypes.data_as(i32p),
                                                                  C.byref(tot)))
-        return counts, {f[0]: int(getattr(tot, f[0])) for f in PileupTotals._fields_}
+        return counts, self._totals(tot)
 
     def consensus_pileup_gapped(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 8):
         """mipgen_accel_reads_consensus_pileup_gapped, callable after consensus_reads: the pileup with indels.  mol_seq: the template of every probe -
         ext arm + scan target + lig arm - as one bytes object of sum(mol_len) bytes or as a sequence of one bytes object per probe; it is upper-cased here.
         Returns (counts[sum(mol_len)][8] int32 - A, C, G, T, discordant, del, ins, ins_discordant - and the totals dict: groups, used, bases, discordant,
         deletions, insertions, ins_discordant, gapped_sides)."""
-        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
-        total = int(lens.astype(np.int64).clip(min=0).sum())
-        seq = (mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper()
-        if len(seq) != total:
-            raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
+        lens, total, seq = self._templates(mol_seq, mol_len)
         counts = np.empty((total, 8), dtype=np.int32)
         tot = GappedTotals()
         i32p = C.POINTER(C.c_int32)
-        self._check(self.lib.mipgen_accel_reads_consensus_pileup_gapped(self.h, bytes(seq), lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
+        self._check(self.lib.mipgen_accel_reads_consensus_pileup_gapped(self.h, seq, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
                                                                         counts.ctypes.data_as(i32p), C.byref(tot)))
-        return counts, {f[0]: int(getattr(tot, f[0])) for f in GappedTotals._fields_}
+        return counts, self._totals(tot)
 
     def call_fetch(self, n: int) -> np.ndarray:
         """mipgen_accel_call_fetch: the n records of the last call of either kind as an array of CALL_RECORD_DTYPE, in ascending (pos, allele)."""
@@ -1067,17 +1079,13 @@ class Accel:
         i32p = C.POINTER(C.c_int32)
         self._check(self.lib.mipgen_accel_call_tables(self.h, counts.ctypes.data_as(i32p), counts.shape[1], pool.ctypes.data_as(i32p), ref.ctypes.data, n_pos,
                                                       int(bool(own_row_is_sample)), C.byref(params), C.byref(tot)))
-        return self.call_fetch(int(tot.calls)), {f[0]: int(getattr(tot, f[0])) for f in CallTotals._fields_}
+        return self.call_fetch(int(tot.calls)), self._totals(tot)
 
     def consensus_call_pool(self, mol_seq, mol_len: Sequence[int], min_family: int = 1, min_quality: int = 0, max_indel: int = 0, bg_max_ppm: int = 200000) -> None:
         """mipgen_accel_reads_consensus_call_pool, callable after consensus_reads: the background pool over the sample rows of the session (max_indel 0: from the
         ungapped pileup; 1..15: from the gapped one).  mol_seq as consensus_pileup_gapped takes it; it supplies the ref bytes."""
-        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
-        total = int(lens.astype(np.int64).clip(min=0).sum())
-        seq = (mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper()
-        if len(seq) != total:
-            raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
-        self._check(self.lib.mipgen_accel_reads_consensus_call_pool(self.h, bytes(seq), lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), min_family, min_quality, max_indel,
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        self._check(self.lib.mipgen_accel_reads_consensus_call_pool(self.h, seq, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), min_family, min_quality, max_indel,
                                                                     bg_max_ppm))
         self._call_shape = (total, 8 if max_indel else 5)
 
@@ -1087,19 +1095,15 @@ class Accel:
         counts = np.empty(self._call_shape, dtype=np.int32)
         tot = CallTotals()
         self._check(self.lib.mipgen_accel_reads_consensus_call(self.h, row, C.byref(params), counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(tot)))
-        return counts, self.call_fetch(int(tot.calls)), {f[0]: int(getattr(tot, f[0])) for f in CallTotals._fields_}
+        return counts, self.call_fetch(int(tot.calls)), self._totals(tot)
 
     def consensus_call_pileup_totals(self) -> dict:
         """mipgen_accel_reads_consensus_call_pileup_totals: the totals the matching pileup call returns for the row consensus_call counted last."""
         tot = GappedTotals()
         self._check(self.lib.mipgen_accel_reads_consensus_call_pileup_totals(self.h, C.byref(tot)))
-        return {f[0]: int(getattr(tot, f[0])) for f in GappedTotals._fields_}
+        return self._totals(tot)
 
-    # ---- loci (DESIGN 4.15) ----
-    @staticmethod
-    def _totals(tot) -> dict:
-        return {f[0]: int(getattr(tot, f[0])) for f in tot._fields_}
-
+    # loci (DESIGN 4.15)
     def locus_tables(self, counts, plan, n_loci: int):
         """mipgen_accel_locus_tables: a count table from host arrays folded per locus, no read session needed.  counts: int32 [n_pos][5 or 8]; plan: int64 [n_pos], -1 or
         locus * 4 + flags (bit 0: minus strand; bit 1: the insertion columns come from row x - 1).  Returns (merged int32 [n_loci][columns] - what call_tables takes -
@@ -1130,17 +1134,6 @@ class Accel:
             return None, None
         a = np.empty((rows, cols), dtype=np.int32)
         return a, a.ctypes.data_as(C.POINTER(C.c_int32))
-
-    @staticmethod
-    def _templates(mol_seq, mol_len):
-        lens = np.ascontiguousarray(mol_len, dtype=np.int32)
-        total = int(lens.astype(np.int64).clip(min=0).sum())
-        seq = None
-        if mol_seq is not None:
-            seq = bytes((mol_seq if isinstance(mol_seq, (bytes, bytearray)) else b"".join(mol_seq)).upper())
-            if len(seq) != total:
-                raise ValueError(f"mol_seq holds {len(seq)} bytes, mol_len sums to {total}")
-        return lens, total, seq
 
     def consensus_locus_pileup(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 0):
         """mipgen_accel_reads_consensus_locus_pileup, callable after consensus_locus_plan: one row counted per template position and folded per locus.  max_indel 0:

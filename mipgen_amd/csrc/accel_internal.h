@@ -141,7 +141,7 @@ struct RescoreList {
 struct ReadsSession;                  // accel_reads.hip
 
 // ---- the consensus reads a session leaves on the handle and the scratch of the two pileups read off them (accel_pileup.hip) ----
-// what both pileup calls hold of one row: kept with the consensus reads between calls - a call per row would otherwise pay the allocations every time
+// what every count holds of one row: kept with the consensus reads between calls - a call per row would otherwise pay the allocations every time
 struct RowScratch {
     DevBuf<int32_t> mol_len;                                 // n
     DevBuf<int64_t> pos_off;                                 // n
@@ -151,17 +151,11 @@ struct RowScratch {
     size_t held() const { return mol_len.cap * 4 + pos_off.cap * 8 + start.cap * 4 + units.cap * 8 + pctr.cap * sizeof(PileupCounters); }
     void release() { mol_len.release(); pos_off.release(); start.release(); units.release(); pctr.release(); }
 };
-// mipgen_accel_reads_consensus_pileup
-struct PileupScratch {
+// One counted row: the row's buffers and its table.  A count with indels reserves the alignment buffers too; the plain count leaves them unreserved.
+// Every instance has its own buffers throughout, so that no entry point touches what another holds.
+struct CountScratch {
     RowScratch row;
-    DevBuf<int32_t> counts;                                  // positions x PILEUP_COLUMNS
-    size_t held() const { return row.held() + counts.cap * 4; }
-    void release() { row.release(); counts.release(); }
-};
-// mipgen_accel_reads_consensus_pileup_gapped: its own buffers throughout, so that neither pileup call touches what the other holds
-struct GappedScratch {
-    RowScratch row;
-    DevBuf<int32_t> counts;                                  // positions x GAPPED_COLUMNS
+    DevBuf<int32_t> counts;                                  // positions x PILEUP_COLUMNS or GAPPED_COLUMNS
     DevBuf<int64_t> proj_off;                                // 2 x the row's groups
     DevBuf<uint32_t> list;                                   // the listed sides
     DevBuf<uint8_t> mol_seq, need, proj;                     // positions; 2 x the row's groups; the projections of the listed sides
@@ -169,21 +163,27 @@ struct GappedScratch {
     size_t held() const { return row.held() + counts.cap * 4 + proj_off.cap * 8 + list.cap * 4 + mol_seq.cap + need.cap + proj.cap + ctr.cap * sizeof(GappedCounters); }
     void release() { row.release(); counts.release(); proj_off.release(); list.release(); mol_seq.release(); need.release(); proj.release(); ctr.release(); }
 };
-// mipgen_accel_reads_consensus_call_pool / _consensus_call: the pool over the sample rows, the ref bytes, the arguments the pool was built with and a
-// pileup scratch of each kind of its own - the calls share nothing with `pile` / `gapped` of the two pileup entry points
-struct CallScratch {
+// A background pool over the sample rows, the arguments it was built with - a call recomputes its row with them - and the pileup totals of the
+// row called last
+struct PoolState {
     bool have = false;                                       // a pool is held
-    PileupScratch pile;
-    GappedScratch gapped;
-    DevBuf<int32_t> pool;                                    // positions x (K[5], N[5])
-    DevBuf<uint8_t> ref;                                     // positions
+    DevBuf<int32_t> pool;                                    // positions or loci x (K[5], N[5])
     std::vector<int32_t> mol_len;
-    std::string mol_seq;
+    std::string mol_seq;                                     // (empty: the pool was built without template bases)
     int32_t min_family = 1, min_quality = 0, max_indel = 0, bg_max_ppm = 0;
     mipgen_gapped_totals last{0, 0, 0, 0, 0, 0, 0, 0};        // the pileup totals of the row called last
     bool have_last = false;
-    size_t held() const { return pile.held() + gapped.held() + pool.cap * 4 + ref.cap; }
-    void release() { have = have_last = false; pile.release(); gapped.release(); pool.release(); ref.release(); }
+    void drop() { have = have_last = false; }
+    void release() { drop(); pool.release(); }
+};
+// mipgen_accel_reads_consensus_call_pool / _consensus_call: the pool over the sample rows, the ref bytes and a count scratch of each kind of its own -
+// the calls share nothing with `pile` / `gapped` of the two pileup entry points
+struct CallScratch {
+    CountScratch pile, gapped;
+    PoolState state;
+    DevBuf<uint8_t> ref;                                     // positions
+    size_t held() const { return pile.held() + gapped.held() + state.pool.cap * 4 + ref.cap; }
+    void release() { state.release(); pile.release(); gapped.release(); ref.release(); }
 };
 // what a call of either kind (mipgen_accel_call_tables too) leaves on the HANDLE: the candidate list, the sort's buffers and the ordered records of the last call
 struct CallRun {
@@ -221,29 +221,22 @@ struct LocusRun {
     size_t held() const { return plan.held() + (counts.cap + merged.cap) * 4 + ctr.cap * sizeof(LocusCounters); }
     void release() { plan.release(); counts.release(); merged.release(); ctr.release(); }
 };
-// mipgen_accel_reads_consensus_locus_* : the installed plan and locus_ref, a pileup scratch of each kind of its own (no locus call touches what the pileup or call
-// entry points hold), the merged table, the pool over the loci and the arguments it was built with; released with the reads, as CallScratch
+// mipgen_accel_reads_consensus_locus_* : the installed plan and locus_ref, a count scratch of each kind of its own (no locus call touches what the pileup or call
+// entry points hold), the merged table and the pool over the loci; released with the reads, as CallScratch
 struct LocusScratch {
     LocusPlan plan;
     DevBuf<uint8_t> ref;                                     // loci
-    PileupScratch pile;
-    GappedScratch gapped;
-    DevBuf<int32_t> merged, pool;                            // loci x columns; loci x (K[5], N[5])
+    CountScratch pile, gapped;
+    DevBuf<int32_t> merged;                                  // loci x columns
     DevBuf<LocusCounters> ctr;
-    bool have_pool = false;
-    std::vector<int32_t> mol_len;
-    std::string mol_seq;
-    int32_t min_family = 1, min_quality = 0, max_indel = 0, bg_max_ppm = 0;
-    mipgen_gapped_totals last{0, 0, 0, 0, 0, 0, 0, 0};        // the pileup totals of the row mipgen_accel_reads_consensus_locus_call counted last
-    bool have_last = false;
-    size_t held() const { return plan.held() + ref.cap + pile.held() + gapped.held() + (merged.cap + pool.cap) * 4 + ctr.cap * sizeof(LocusCounters); }
-    void release() { plan.release(); ref.release(); pile.release(); gapped.release(); merged.release(); pool.release(); ctr.release(); have_pool = have_last = false; }
+    PoolState state;
+    size_t held() const { return plan.held() + ref.cap + pile.held() + gapped.held() + (merged.cap + state.pool.cap) * 4 + ctr.cap * sizeof(LocusCounters); }
+    void release() { plan.release(); ref.release(); pile.release(); gapped.release(); merged.release(); ctr.release(); state.release(); }
 };
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
     int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
-    PileupScratch pile;
-    GappedScratch gapped;
+    CountScratch pile, gapped;                               // of mipgen_accel_reads_consensus_pileup and _pileup_gapped
     CallScratch call;
     LocusScratch locus;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending

@@ -1,15 +1,22 @@
 // accel_pileup.hip — the two pileups read off the consensus reads a session left on the handle: allele counts per template position of one row (DESIGN 4.12:
-// mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped), and the variant calls made from them (4.14: mipgen_accel_call_tables,
-// _reads_consensus_call_pool, _reads_consensus_call, _call_fetch).  A pileup is plan_row (every check, nothing allocated or launched), then count_plain / count_gapped:
-// the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches, download and totals of ONE row into the
-// scratch it is given.  The two pileup entry points give `pile` / `gapped` of the ConsensusResult, the calls give the pair inside its CallScratch: three callers of one
-// count, and no call touches what another holds.  The locus calls (4.15: mipgen_accel_locus_tables, _reads_consensus_locus_plan / _locus_pileup / _locus_call_pool /
-// _locus_call) are a fourth caller, with the pair inside the LocusScratch: between the count and the pool or run_call they fold the row's table into one row per
-// genome locus (kernels_locus.hip) by the plan the caller installed.
+// mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped), the variant calls made from them (4.14: mipgen_accel_call_tables,
+// _reads_consensus_call_pool, _reads_consensus_call, _call_fetch) and the same per genome locus (4.15: mipgen_accel_locus_tables, _reads_consensus_locus_plan /
+// _locus_pileup / _locus_call_pool / _locus_call).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
+// count_row is the ONE count: the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches of the plain
+// or the gapped table, download and totals of one row into the CountScratch it is given.  Every entry point gives a scratch of its own - `pile` / `gapped` of the
+// ConsensusResult, of its CallScratch, of its LocusScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
+// a Target: per template position, or per locus, where count_target folds the row's table by the installed plan (kernels_locus.hip) between the count and the pool
+// or run_call.  An entry point is its own refusals, its budget and one call of the shared route.
 #include "accel_internal.h"
 #include "gapped_align.h"
 
-struct GappedArgs { const char* mol_seq; int32_t max_indel; bool seq_only = false; };   // what the gapped call adds to the arguments of a row (seq_only: the bases are needed, nothing is placed)
+// The arguments of a row, as every level takes them.  need_seq: the call refuses a NULL mol_seq; must_place: it places with indels whatever max_indel says (the gapped
+// pileup, which so refuses max_indel 0); otherwise a row is placed when max_indel is not 0.
+struct RowArgs {
+    const char* mol_seq; const int32_t* mol_len; int32_t n, min_family, min_quality, max_indel;
+    bool need_seq = false, must_place = false;
+    bool placed() const { return must_place || max_indel != 0; }
+};
 
 struct RowPlan {
     ConsensusResult* R = nullptr;
@@ -20,54 +27,78 @@ struct RowPlan {
 
 static size_t padded(size_t count, size_t size) { return (count + count / 8 + 64) * size; }      // (what DevBuf::reserve asks for at most)
 
-// Every refusal of a pileup call, in one order for both; G: the gapped call's arguments (molecules are then bounded by MIPGEN_GAPPED_MAX_MOL), or nullptr.
-static int plan_row(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, const GappedArgs* G, RowPlan* P)
+// what a call may take: the bytes it holds already and the free ones
+static int room_beside(size_t held, size_t* room)
+{
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    *room = held + free_b;
+    return MIPGEN_OK;
+}
+
+// the end of a call that succeeded, its stream idle: the spans of `timer` into *ms when timing is on
+static int booked(const SpanTimer& timer, double* ms)
+{
+    double sum = 0.0;
+    if (timer.add_to(&sum)) *ms = sum;
+    return MIPGEN_OK;
+}
+
+// the two refusals every call that reads the session begins with
+static int check_reads(const mipgen_accel* h)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    return MIPGEN_OK;
+}
+
+// Every refusal of a row, in one order for all callers; placed molecules are bounded by MIPGEN_GAPPED_MAX_MOL.
+static int plan_row(mipgen_accel* h, const RowArgs& A, int32_t row, RowPlan* P)
+{
+    if (int rc = check_reads(h)) return rc;
     const ConsensusResult* R = P->R = h->consensus;
-    const bool placed = G && !G->seq_only;
-    if (!mol_len) return fail(MIPGEN_E_INVALID, "bad arguments: no molecule lengths");
-    if (G && !G->mol_seq) return fail(MIPGEN_E_INVALID, "bad arguments: no template bases");
-    if ((int64_t)n != R->n) return fail(MIPGEN_E_INVALID, "%d molecule lengths: the session that left the consensus reads had %lld probes", n, (long long)R->n);
-    for (int32_t p = 0; p < n; p++) {
-        if (mol_len[p] < 1) return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: a length is 1 or more", mol_len[p], p);
-        if (placed && mol_len[p] > MIPGEN_GAPPED_MAX_MOL)
-            return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: the gapped pileup places molecules of at most %d bases", mol_len[p], p, MIPGEN_GAPPED_MAX_MOL);
-        P->n_pos += mol_len[p]; P->n_units += ((int64_t)mol_len[p] + 63) / 64; P->max_len = std::max(P->max_len, mol_len[p]);
+    if (!A.mol_len) return fail(MIPGEN_E_INVALID, "bad arguments: no molecule lengths");
+    if (A.need_seq && !A.mol_seq) return fail(MIPGEN_E_INVALID, "bad arguments: no template bases");
+    if ((int64_t)A.n != R->n) return fail(MIPGEN_E_INVALID, "%d molecule lengths: the session that left the consensus reads had %lld probes", A.n, (long long)R->n);
+    for (int32_t p = 0; p < A.n; p++) {
+        if (A.mol_len[p] < 1) return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: a length is 1 or more", A.mol_len[p], p);
+        if (A.placed() && A.mol_len[p] > MIPGEN_GAPPED_MAX_MOL)
+            return fail(MIPGEN_E_INVALID, "molecule length %d of probe %d: the gapped pileup places molecules of at most %d bases", A.mol_len[p], p, MIPGEN_GAPPED_MAX_MOL);
+        P->n_pos += A.mol_len[p]; P->n_units += ((int64_t)A.mol_len[p] + 63) / 64; P->max_len = std::max(P->max_len, A.mol_len[p]);
     }
     if (row < 0 || (int64_t)row >= R->rows) return fail(MIPGEN_E_INVALID, "row %d: the session had %lld row%s", row, (long long)R->rows, R->rows == 1 ? "" : "s");
-    if (min_family < 1) return fail(MIPGEN_E_INVALID, "min_family %d: 1 or more", min_family);
-    if (min_quality < 0 || min_quality > 40) return fail(MIPGEN_E_INVALID, "min_quality %d: 0 to 40 (the consensus writes 2 to 40)", min_quality);
-    if (placed && (G->max_indel < 1 || G->max_indel > GAP_MAX_INDEL)) return fail(MIPGEN_E_INVALID, "max_indel %d: 1 to %d", G->max_indel, GAP_MAX_INDEL);
+    if (A.min_family < 1) return fail(MIPGEN_E_INVALID, "min_family %d: 1 or more", A.min_family);
+    if (A.min_quality < 0 || A.min_quality > 40) return fail(MIPGEN_E_INVALID, "min_quality %d: 0 to 40 (the consensus writes 2 to 40)", A.min_quality);
+    if (A.placed() && (A.max_indel < 1 || A.max_indel > GAP_MAX_INDEL)) return fail(MIPGEN_E_INVALID, "max_indel %d: 1 to %d", A.max_indel, GAP_MAX_INDEL);
     if (P->n_units > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%lld template positions: more than 2^31 - 1 rounds of 64", (long long)P->n_pos);
-    P->bytes = padded((size_t)n, 4) + padded((size_t)n, 8) + padded((size_t)n + 1, 4) + padded((size_t)P->n_units, 8) + padded(1, sizeof(PileupCounters));
+    const size_t n = (size_t)A.n;
+    P->bytes = padded(n, 4) + padded(n, 8) + padded(n + 1, 4) + padded((size_t)P->n_units, 8) + padded(1, sizeof(PileupCounters));
     HIP_TRY(hipSetDevice(h->device));
     return MIPGEN_OK;
 }
 
 // The row's buffers filled and its kernels run (timed as one span of `timer`): *row is complete, *pc holds `used`, [*first, *last) are the row's groups.
 // what: the call's name in a message.
-static int prepare_row(mipgen_accel* h, const RowPlan& P, RowScratch& W, const char* what, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family,
-                       int32_t min_quality, SpanTimer& timer, PileRow* out, PileupCounters* pc, uint32_t* first, uint32_t* last)
+static int prepare_row(mipgen_accel* h, const RowPlan& P, RowScratch& W, const char* what, const RowArgs& A, int32_t row, SpanTimer& timer, PileRow* out,
+                       PileupCounters* pc, uint32_t* first, uint32_t* last)
 {
     const ConsensusResult* R = P.R;
-    if (W.mol_len.reserve((size_t)n) || W.pos_off.reserve((size_t)n) || W.start.reserve((size_t)n + 1) || W.units.reserve((size_t)P.n_units) || W.pctr.reserve(1))
-        return MIPGEN_E_NOMEM;
-    std::vector<int64_t> pos_off((size_t)n);
-    for (int64_t p = 0, at = 0; p < n; at += mol_len[p], p++) pos_off[(size_t)p] = at;
+    const size_t n = (size_t)A.n;
+    if (W.mol_len.reserve(n) || W.pos_off.reserve(n) || W.start.reserve(n + 1) || W.units.reserve((size_t)P.n_units) || W.pctr.reserve(1)) return MIPGEN_E_NOMEM;
+    std::vector<int64_t> pos_off(n);
+    for (int64_t p = 0, at = 0; p < A.n; at += A.mol_len[p], p++) pos_off[(size_t)p] = at;
     hipStream_t st = h->stream;
     IdleOnExit idle{st};                                                 // (pos_off outlives its copy)
-    HIP_TRY(hipMemcpyAsync(W.mol_len.p, mol_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(W.pos_off.p, pos_off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.mol_len.p, A.mol_len, n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.pos_off.p, pos_off.data(), n * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(W.pctr.p, 0, sizeof(PileupCounters), st));
-    *out = {W.units.p, 0, 0, W.start.p, W.mol_len.p, W.pos_off.p, n, P.n_pos, (uint32_t)((int64_t)row * R->n), min_family, min_quality};
+    *out = {W.units.p, 0, 0, W.start.p, W.mol_len.p, W.pos_off.p, A.n, P.n_pos, (uint32_t)((int64_t)row * R->n), A.min_family, A.min_quality};
     timer.mark();
     HIP_TRY(mipgen_launch_pileup_prepare(st, R->view(), *out, P.n_units, W.start.p, W.units.p, W.pctr.p));
     timer.mark();
     HIP_TRY(hipMemcpyAsync(pc, W.pctr.p, sizeof *pc, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(first, W.start.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(last, W.start.p + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(last, W.start.p + A.n, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(idle.wait());
     out->n_small = (int64_t)pc->n_small; out->n_big = (int64_t)pc->n_big;
     if (out->n_small + out->n_big != P.n_units)
@@ -75,108 +106,88 @@ static int prepare_row(mipgen_accel* h, const RowPlan& P, RowScratch& W, const c
     return MIPGEN_OK;
 }
 
-
 // What a call adds to the budget of the row it counts: the bytes it will still allocate beside the row's, and what it already holds of them.  what: the call's name.
 struct Budget { const char* what; size_t more_need = 0, more_held = 0; bool keep_on_device = false; };   // keep_on_device: a session without groups still leaves a zeroed table in W.counts
+// a counted table on the device and its columns
+struct Counted { const int32_t* table = nullptr; int columns = 0; };
 
-// One row of the ungapped table counted into W: W.counts holds it afterwards, `counts` (may be NULL) a copy; the kernels are spans of `timer`.
-static int count_plain(mipgen_accel* h, const RowPlan& P, PileupScratch& W, const Budget& B, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family,
-                       int32_t min_quality, SpanTimer& timer, int32_t* counts, mipgen_pileup_totals* totals)
+// One row counted into W: the plain table at max_indel 0, else the one with indels (4.13).  W.counts holds it afterwards - *out says so -, `counts` (may
+// be NULL) a copy, *totals (may be NULL) its sums, the gapped-only ones 0 for the plain table; the kernels are spans of `timer`.
+static int count_row(mipgen_accel* h, const RowPlan& P, CountScratch& W, const Budget& B, const RowArgs& A, int32_t row, SpanTimer& timer, int32_t* counts,
+                     mipgen_gapped_totals* totals, Counted* out)
 {
     const ConsensusResult* R = P.R;
     hipStream_t st = h->stream;
-    if (R->n_groups == 0) {                                              // (no buffer exists: nothing to read, nothing to launch)
-        if (counts) memset(counts, 0, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t));
-        if (totals) *totals = {0, 0, 0, 0};
-        if (B.keep_on_device) {
-            if (W.counts.reserve((size_t)P.n_pos * PILEUP_COLUMNS)) return MIPGEN_E_NOMEM;
-            HIP_TRY(hipMemsetAsync(W.counts.p, 0, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t), st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        return MIPGEN_OK;
-    }
-    const size_t need = P.bytes + padded((size_t)P.n_pos * PILEUP_COLUMNS, 4) + B.more_need;
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > W.held() + B.more_held + free_b)
-        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions need %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos, need >> 20,
-                    (W.held() + B.more_held + free_b) >> 20);
-    if (W.counts.reserve((size_t)P.n_pos * PILEUP_COLUMNS)) return MIPGEN_E_NOMEM;
-    IdleOnExit idle{st};
-    PileRow Row;
-    PileupCounters pc;
-    uint32_t first = 0, last = 0;                                        // the row's groups: [first, last)
-    if (int rc = prepare_row(h, P, W.row, B.what, mol_len, n, row, min_family, min_quality, timer, &Row, &pc, &first, &last)) return rc;
-    timer.mark();
-    HIP_TRY(mipgen_launch_pileup(st, R->view(), Row, P.n_units, W.counts.p, W.row.pctr.p));
-    timer.mark();
-    HIP_TRY(hipMemcpyAsync(&pc, W.row.pctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, (size_t)P.n_pos * PILEUP_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(idle.wait());
-    if (totals) *totals = {(int64_t)last - (int64_t)first, (int64_t)pc.used, (int64_t)pc.bases, (int64_t)pc.discordant};
-    return MIPGEN_OK;
-}
-
-// One row of the table with indels counted into W, as count_plain.
-static int count_gapped(mipgen_accel* h, const RowPlan& P, GappedScratch& W, const Budget& B, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row,
-                        int32_t min_family, int32_t min_quality, int32_t max_indel, SpanTimer& gap_time, int32_t* counts, mipgen_gapped_totals* totals)
-{
-    const ConsensusResult* R = P.R;
-    hipStream_t st = h->stream;
-    const size_t n_pos = (size_t)P.n_pos;
-    if (R->n_groups == 0) {
-        if (counts) memset(counts, 0, n_pos * GAPPED_COLUMNS * sizeof(int32_t));
-        if (totals) *totals = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (B.keep_on_device) {
-            if (W.counts.reserve(n_pos * GAPPED_COLUMNS)) return MIPGEN_E_NOMEM;
-            HIP_TRY(hipMemsetAsync(W.counts.p, 0, n_pos * GAPPED_COLUMNS * sizeof(int32_t), st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        return MIPGEN_OK;
-    }
-    // the budget, before anything is allocated: the row's groups are not known yet, so every buffer that grows with them is taken at the session's groups, and a
-    // projection at the longest template
-    const size_t G = (size_t)R->n_groups;
-    const size_t need = P.bytes + padded(n_pos * GAPPED_COLUMNS, 4) + padded(n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) +
-                        padded(2 * G * 3 * (size_t)P.max_len, 1) + padded(1, sizeof(GappedCounters)) + B.more_need;
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > W.held() + B.more_held + free_b)
-        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions and %lld groups need up to %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos,
-                    (long long)R->n_groups, need >> 20, (W.held() + B.more_held + free_b) >> 20);
-    if (W.counts.reserve(n_pos * GAPPED_COLUMNS) || W.mol_seq.reserve(n_pos) || W.ctr.reserve(1)) return MIPGEN_E_NOMEM;
-    IdleOnExit idle{st};
-    HIP_TRY(hipMemcpyAsync(W.mol_seq.p, mol_seq, n_pos, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(GappedCounters), st));
-    PileRow Row;
-    PileupCounters pc;
+    const bool gapped = A.max_indel != 0;
+    const int columns = gapped ? GAPPED_COLUMNS : PILEUP_COLUMNS;
+    const size_t n_pos = (size_t)P.n_pos, cells = n_pos * (size_t)columns;
     GappedCounters gc;
     memset(&gc, 0, sizeof gc);
+    if (R->n_groups == 0) {                                              // (no buffer exists: nothing to read, nothing to launch)
+        if (counts) memset(counts, 0, cells * sizeof(int32_t));
+        if (totals) *totals = mipgen_gapped_totals{};
+        if (B.keep_on_device) {
+            if (W.counts.reserve(cells)) return MIPGEN_E_NOMEM;
+            HIP_TRY(hipMemsetAsync(W.counts.p, 0, cells * sizeof(int32_t), st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        *out = {W.counts.p, columns};
+        return MIPGEN_OK;
+    }
+    // the budget, before anything is allocated: the row's groups are not known yet, so every gapped buffer that grows with them is taken at the session's groups, and a
+    // projection at the longest template
+    const size_t G = (size_t)R->n_groups;
+    size_t need = P.bytes + padded(cells, 4) + B.more_need, room = 0;
+    if (gapped)
+        need += padded(n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) + padded(2 * G * 3 * (size_t)P.max_len, 1) + padded(1, sizeof(GappedCounters));
+    if (int rc = room_beside(W.held() + B.more_held, &room)) return rc;
+    if (need > room && gapped)
+        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions and %lld groups need up to %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos,
+                    (long long)R->n_groups, need >> 20, room >> 20);
+    if (need > room)
+        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions need %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos, need >> 20, room >> 20);
+    if (W.counts.reserve(cells) || (gapped && (W.mol_seq.reserve(n_pos) || W.ctr.reserve(1)))) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{st};
+    if (gapped) {
+        HIP_TRY(hipMemcpyAsync(W.mol_seq.p, A.mol_seq, n_pos, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(W.ctr.p, 0, sizeof(GappedCounters), st));
+    }
+    PileRow Row;
+    PileupCounters pc;
     uint32_t first = 0, last = 0;                                        // the row's groups: [first, last)
-    if (int rc = prepare_row(h, P, W.row, B.what, mol_len, n, row, min_family, min_quality, gap_time, &Row, &pc, &first, &last)) return rc;
+    if (int rc = prepare_row(h, P, W.row, B.what, A, row, timer, &Row, &pc, &first, &last)) return rc;
     const ConsensusView C = R->view();
     const int64_t n_row = (int64_t)last - (int64_t)first;
-    if (n_row < 0 || n_row > R->n_groups) return fail(MIPGEN_E_STATE, "%s: groups [%u, %u) of %lld", B.what, first, last, (long long)R->n_groups);
-    if (n_row > 0) {
-        if (W.need.reserve(2 * (size_t)n_row) || W.list.reserve(2 * (size_t)n_row) || W.proj_off.reserve(2 * (size_t)n_row)) return MIPGEN_E_NOMEM;
-        gap_time.mark();
-        HIP_TRY(mipgen_launch_gap_list(st, C, Row, W.mol_seq.p, first, n_row, max_indel, W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
-        gap_time.mark();
+    if (!gapped) {
+        timer.mark();
+        HIP_TRY(mipgen_launch_pileup(st, C, Row, P.n_units, W.counts.p, W.row.pctr.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&pc, W.row.pctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
+    } else {
+        if (n_row < 0 || n_row > R->n_groups) return fail(MIPGEN_E_STATE, "%s: groups [%u, %u) of %lld", B.what, first, last, (long long)R->n_groups);
+        if (n_row > 0) {
+            if (W.need.reserve(2 * (size_t)n_row) || W.list.reserve(2 * (size_t)n_row) || W.proj_off.reserve(2 * (size_t)n_row)) return MIPGEN_E_NOMEM;
+            timer.mark();
+            HIP_TRY(mipgen_launch_gap_list(st, C, Row, W.mol_seq.p, first, n_row, A.max_indel, W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
+            timer.mark();
+            HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * 3ull * (unsigned long long)P.max_len)
+                return fail(MIPGEN_E_STATE, "%s: %llu sides listed of %lld, %llu projection bytes", B.what, gc.n_sides, (long long)(2 * n_row), gc.proj_bytes);
+            if (gc.proj_bytes && W.proj.reserve((size_t)gc.proj_bytes)) return MIPGEN_E_NOMEM;
+        }
+        timer.mark();
+        HIP_TRY(mipgen_launch_gapped(st, C, Row, P.n_units, W.mol_seq.p, first, A.max_indel, P.max_len, W.list.p, (int64_t)gc.n_sides, W.proj_off.p, W.proj.p, W.counts.p, W.ctr.p));
+        timer.mark();
         HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * 3ull * (unsigned long long)P.max_len)
-            return fail(MIPGEN_E_STATE, "%s: %llu sides listed of %lld, %llu projection bytes", B.what, gc.n_sides, (long long)(2 * n_row), gc.proj_bytes);
-        if (gc.proj_bytes && W.proj.reserve((size_t)gc.proj_bytes)) return MIPGEN_E_NOMEM;
     }
-    gap_time.mark();
-    HIP_TRY(mipgen_launch_gapped(st, C, Row, P.n_units, W.mol_seq.p, first, max_indel, P.max_len, W.list.p, (int64_t)gc.n_sides, W.proj_off.p, W.proj.p, W.counts.p, W.ctr.p));
-    gap_time.mark();
-    HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, n_pos * GAPPED_COLUMNS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, W.counts.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(idle.wait());
+    if (!gapped) { gc.bases = pc.bases; gc.discordant = pc.discordant; } // (the plain kernels sum into the row's own counters; every other sum stays 0)
     if (totals)
         *totals = {n_row, (int64_t)pc.used, (int64_t)gc.bases, (int64_t)gc.discordant, (int64_t)gc.deletions, (int64_t)gc.insertions, (int64_t)gc.ins_discordant,
                    (int64_t)gc.gapped_sides};
+    *out = {W.counts.p, columns};
     return MIPGEN_OK;
 }
 
@@ -282,11 +293,11 @@ static int build_locus_plan(mipgen_accel* h, LocusPlan& L, const int64_t* plan, 
     size_t temp_bytes = 0;
     HIP_TRY(mipgen_consensus_sort(st, nullptr, &temp_bytes, nullptr, nullptr, nullptr, nullptr, n_pos, end_bit));
     const size_t need = 3 * padded(np, 8) + 3 * padded(np, 4) + padded(std::max<size_t>(temp_bytes, 1), 1) + padded(nl + 1, 4) + more_need;
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > L.held() + more_held + free_b)
+    size_t room = 0;
+    if (int rc = room_beside(L.held() + more_held, &room)) return rc;
+    if (need > room)
         return fail(MIPGEN_E_NOMEM, "%s: a plan of %lld positions and %lld loci needs up to %zu MiB of device memory, %zu MiB are free", what, (long long)n_pos,
-                    (long long)n_loci, need >> 20, (L.held() + more_held + free_b) >> 20);
+                    (long long)n_loci, need >> 20, room >> 20);
     L.have = false;
     if (L.plan.reserve(np) || L.keys.reserve(np) || L.keys_sorted.reserve(np) || L.ids.reserve(np) || L.ids_sorted.reserve(np) || L.src.reserve(np) ||
         L.first.reserve(nl + 1) || L.temp.reserve(std::max<size_t>(temp_bytes, 1)))
@@ -334,22 +345,93 @@ static int check_locus_session(const LocusScratch& L, const RowPlan& P)
     return MIPGEN_OK;
 }
 
-// One row counted into the locus scratch (probe_counts: a copy, may be NULL; pt: the pileup's totals, may be NULL) and folded into L.merged (locus_counts, lt likewise).
-static int count_and_merge(mipgen_accel* h, const RowPlan& P, LocusScratch& L, const Budget& B, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row,
-                           int32_t min_family, int32_t min_quality, int32_t max_indel, SpanTimer& timer, int32_t* probe_counts, int32_t* locus_counts,
-                           mipgen_gapped_totals* pt, mipgen_locus_totals* lt)
+// Where a pool or a call puts the rows it counts: per template position - the scratch, pool and ref bytes of the CallScratch - or, with L set, per locus: every
+// counted table is folded by L->plan into L->merged, and pool, ref bytes and run_call are over the loci.  ms: the timing index the route writes.
+struct Target {
+    CountScratch &pile, &gapped;
+    PoolState& S;
+    LocusScratch* L;
+    const DevBuf<uint8_t>& ref;
+    double* ms;
+    int64_t n_out(const RowPlan& P) const { return L ? L->plan.n_loci : P.n_pos; }      // the rows of the table a pool adds up and a call tests
+};
+static Target probe_target(mipgen_accel* h, ConsensusResult* R) { return {R->call.pile, R->call.gapped, R->call.state, nullptr, R->call.ref, &h->call_ms}; }
+static Target locus_target(mipgen_accel* h, ConsensusResult* R) { return {R->locus.pile, R->locus.gapped, R->locus.state, &R->locus, R->locus.ref, &h->locus_ms}; }
+
+// One row counted into the target's scratch of the kind A asks for (probe_counts: a copy, may be NULL; pt: the pileup's totals, may be NULL) and, per locus, folded
+// into L->merged (locus_counts, lt likewise).  *out: the table the pool or the call reads.
+static int count_target(mipgen_accel* h, const RowPlan& P, const Target& T, const Budget& B, const RowArgs& A, int32_t row, SpanTimer& timer, int32_t* probe_counts,
+                        int32_t* locus_counts, mipgen_gapped_totals* pt, mipgen_locus_totals* lt, Counted* out)
 {
-    const int32_t* table = nullptr;
-    if (max_indel) {
-        if (int rc = count_gapped(h, P, L.gapped, B, mol_seq, mol_len, n, row, min_family, min_quality, max_indel, timer, probe_counts, pt)) return rc;
-        table = L.gapped.counts.p;
-    } else {
-        mipgen_pileup_totals t{0, 0, 0, 0};
-        if (int rc = count_plain(h, P, L.pile, B, mol_len, n, row, min_family, min_quality, timer, probe_counts, &t)) return rc;
-        if (pt) *pt = {t.groups, t.used, t.bases, t.discordant, 0, 0, 0, 0};
-        table = L.pile.counts.p;
+    if (int rc = count_row(h, P, A.max_indel ? T.gapped : T.pile, B, A, row, timer, probe_counts, pt, out)) return rc;
+    if (!T.L) return MIPGEN_OK;
+    const int32_t* counted = out->table;
+    out->table = T.L->merged.p;
+    return merge_loci(h, T.L->plan, counted, out->columns, T.L->merged.p, T.L->ctr.p, timer, locus_counts, lt);
+}
+
+// The pool of a target over the sample rows of the session: every row counted (and folded) and added on the device, then the arguments remembered for the calls.
+// The caller has made its refusals, dropped the pool that was held, taken the budget B and reserved and filled what is its own.
+static int build_pool(mipgen_accel* h, const RowPlan& P, const Target& T, const Budget& B, const RowArgs& A, int32_t bg_max_ppm)
+{
+    PoolState& S = T.S;
+    const int64_t n_out = T.n_out(P);
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemsetAsync(S.pool.p, 0, (size_t)n_out * 40, st));
+    SpanTimer timer{h->timing, st};
+    for (int64_t r = 0; r < sample_rows(P.R); r++) {
+        Counted row;
+        if (int rc = count_target(h, P, T, B, A, (int32_t)r, timer, nullptr, nullptr, nullptr, nullptr, &row)) return rc;
+        timer.mark();
+        HIP_TRY(mipgen_launch_call_pool(st, row.table, row.columns, n_out, bg_max_ppm, S.pool.p));
+        timer.mark();
     }
-    return merge_loci(h, L.plan, table, max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, L.merged.p, L.ctr.p, timer, locus_counts, lt);
+    HIP_TRY(idle.wait());
+    S.mol_len.assign(A.mol_len, A.mol_len + A.n);
+    if (A.mol_seq) S.mol_seq.assign(A.mol_seq, (size_t)P.n_pos); else S.mol_seq.clear();
+    S.min_family = A.min_family; S.min_quality = A.min_quality; S.max_indel = A.max_indel; S.bg_max_ppm = bg_max_ppm;
+    S.have = true;
+    return booked(timer, T.ms);
+}
+
+// What a call of one row against the pool of a target shares up to its refusals of the row and the parameters: the row planned with the pool's arguments.
+// pool_name: "pool" or "locus pool", as the message names it.
+static int plan_call(mipgen_accel* h, const PoolState& S, int32_t row, const mipgen_call_params* params, const char* pool_name, RowArgs* A, RowPlan* P)
+{
+    *A = {S.mol_seq.data(), S.mol_len.data(), (int32_t)S.mol_len.size(), S.min_family, S.min_quality, S.max_indel};
+    if (int rc = plan_row(h, *A, row, P)) return rc;
+    if (int rc = check_call_params(params)) return rc;
+    if (params->bg_max_ppm != S.bg_max_ppm) return fail(MIPGEN_E_STATE, "bg_max_ppm %d: the %s was built with %d", params->bg_max_ppm, pool_name, S.bg_max_ppm);
+    return MIPGEN_OK;
+}
+
+// The calls of one row against the pool of a target: the row recomputed with the pool's arguments (and folded), then flag, tail and order.  what: the call's name.
+static int call_row(mipgen_accel* h, const RowPlan& P, const Target& T, const RowArgs& A, const char* what, int32_t row, const mipgen_call_params& prm,
+                    int32_t* probe_counts, int32_t* locus_counts, mipgen_call_totals* totals)
+{
+    PoolState& S = T.S;
+    const int64_t n_out = T.n_out(P);
+    *T.ms = -1.0;
+    h->call_run.n_calls = -1;
+    const Budget B{what, call_run_bytes(n_out), h->call_run.held(), true};
+    SpanTimer timer{h->timing, h->stream};
+    S.have_last = false;
+    Counted counted;
+    if (int rc = count_target(h, P, T, B, A, row, timer, probe_counts, locus_counts, &S.last, nullptr, &counted)) return rc;
+    S.have_last = true;
+    if (int rc = run_call(h, counted.table, counted.columns, S.pool.p, T.ref.p, n_out, (int64_t)row < sample_rows(P.R), prm, timer, totals)) return rc;
+    return booked(timer, T.ms);
+}
+
+// the pileup totals of the row a target's call counted last; none: the refusal's text
+static int last_pileup_totals(mipgen_accel* h, bool locus, const char* none, mipgen_gapped_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    const PoolState* S = !h->consensus ? nullptr : locus ? &h->consensus->locus.state : &h->consensus->call.state;
+    if (!S || !S->have_last) return fail(MIPGEN_E_STATE, "%s", none);
+    if (totals) *totals = S->last;
+    return MIPGEN_OK;
 }
 
 
@@ -360,13 +442,15 @@ int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len,
                                         mipgen_pileup_totals* totals)
 {
     RowPlan P;
-    if (int rc = plan_row(h, mol_len, n, row, min_family, min_quality, nullptr, &P)) return rc;
+    const RowArgs A{nullptr, mol_len, n, min_family, min_quality, 0};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
     h->pileup_ms = -1.0;
     SpanTimer pile_time{h->timing, h->stream};
-    if (int rc = count_plain(h, P, P.R->pile, Budget{"pileup"}, mol_len, n, row, min_family, min_quality, pile_time, counts, totals)) return rc;
-    double ms = 0.0;
-    if (pile_time.add_to(&ms)) h->pileup_ms = ms;
-    return MIPGEN_OK;
+    mipgen_gapped_totals t;
+    Counted counted;
+    if (int rc = count_row(h, P, P.R->pile, Budget{"pileup"}, A, row, pile_time, counts, &t, &counted)) return rc;
+    if (totals) *totals = {t.groups, t.used, t.bases, t.discordant};
+    return booked(pile_time, &h->pileup_ms);
 }
 
 // The pileup with indels of one row.  Reads R's groups and reads; writes R->gapped only.
@@ -374,14 +458,13 @@ int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_
                                                int32_t max_indel, int32_t* counts, mipgen_gapped_totals* totals)
 {
     RowPlan P;
-    const GappedArgs args{mol_seq, max_indel};
-    if (int rc = plan_row(h, mol_len, n, row, min_family, min_quality, &args, &P)) return rc;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
     h->gapped_ms = -1.0;
     SpanTimer gap_time{h->timing, h->stream};
-    if (int rc = count_gapped(h, P, P.R->gapped, Budget{"gapped pileup"}, mol_seq, mol_len, n, row, min_family, min_quality, max_indel, gap_time, counts, totals)) return rc;
-    double ms = 0.0;
-    if (gap_time.add_to(&ms)) h->gapped_ms = ms;
-    return MIPGEN_OK;
+    Counted counted;
+    if (int rc = count_row(h, P, P.R->gapped, Budget{"gapped pileup"}, A, row, gap_time, counts, totals, &counted)) return rc;
+    return booked(gap_time, &h->gapped_ms);
 }
 
 // Calls from host arrays: no read session is needed; the arrays are uploaded into the handle's CallRun.
@@ -397,10 +480,9 @@ int mipgen_accel_call_tables(mipgen_accel* h, const int32_t* counts, int32_t col
     CallRun& U = h->call_run;
     h->call_ms = -1.0;
     const size_t np = (size_t)n_pos, need = padded(np * (size_t)columns, 4) + padded(np * 10, 4) + padded(np, 1) + call_run_bytes(n_pos);
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (need > U.held() + free_b)
-        return fail(MIPGEN_E_NOMEM, "call: %lld positions need up to %zu MiB of device memory, %zu MiB are free", (long long)n_pos, need >> 20, (U.held() + free_b) >> 20);
+    size_t room = 0;
+    if (int rc = room_beside(U.held(), &room)) return rc;
+    if (need > room) return fail(MIPGEN_E_NOMEM, "call: %lld positions need up to %zu MiB of device memory, %zu MiB are free", (long long)n_pos, need >> 20, room >> 20);
     if (U.counts.reserve(np * (size_t)columns) || U.pool.reserve(np * 10) || U.ref.reserve(np)) return MIPGEN_E_NOMEM;
     hipStream_t st = h->stream;
     IdleOnExit idle{st};
@@ -409,9 +491,7 @@ int mipgen_accel_call_tables(mipgen_accel* h, const int32_t* counts, int32_t col
     HIP_TRY(hipMemcpyAsync(U.ref.p, ref, np, hipMemcpyHostToDevice, st));
     SpanTimer timer{h->timing, st};
     if (int rc = run_call(h, U.counts.p, columns, U.pool.p, U.ref.p, n_pos, own_row_is_sample != 0, *params, timer, totals)) return rc;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->call_ms = ms;
-    return MIPGEN_OK;
+    return booked(timer, &h->call_ms);
 }
 
 // The pool over the sample rows of the session: every row's pileup into R->call's own scratch, added on the device.  Writes R->call only.
@@ -419,93 +499,42 @@ int mipgen_accel_reads_consensus_call_pool(mipgen_accel* h, const char* mol_seq,
                                            int32_t max_indel, int32_t bg_max_ppm)
 {
     RowPlan P;
-    const GappedArgs args{mol_seq, max_indel, max_indel == 0};
-    if (int rc = plan_row(h, mol_len, n, 0, min_family, min_quality, &args, &P)) return rc;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true};      // the template bases are the ref bytes: needed without indels too
+    if (int rc = plan_row(h, A, 0, &P)) return rc;
     if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
     if (P.n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: a call takes 2^29 - 1 at most", (long long)P.n_pos);
-    ConsensusResult* R = P.R;
-    CallScratch& C = R->call;
-    C.have = C.have_last = false;                                        // (a pool that fails leaves none)
+    CallScratch& C = P.R->call;
+    C.state.drop();                                                      // (a pool that fails leaves none)
     h->call_ms = -1.0;
     const size_t np = (size_t)P.n_pos;
-    // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_plain's / count_gapped's
-    const size_t more = padded(np * 10, 4) + padded(np, 1) + call_run_bytes(P.n_pos);
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (more > C.pool.cap * 4 + C.ref.cap + h->call_run.held() + free_b)
+    // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_row's
+    const size_t more = padded(np * 10, 4) + padded(np, 1) + call_run_bytes(P.n_pos), held = C.state.pool.cap * 4 + C.ref.cap + h->call_run.held();
+    size_t room = 0;
+    if (int rc = room_beside(held, &room)) return rc;
+    if (more > room)
         return fail(MIPGEN_E_NOMEM, "call pool: %lld template positions need up to %zu MiB of device memory beside the pileup's, %zu MiB are free", (long long)P.n_pos,
-                    more >> 20, (C.pool.cap * 4 + C.ref.cap + h->call_run.held() + free_b) >> 20);
-    const Budget B{"call pool", more, C.pool.cap * 4 + C.ref.cap + h->call_run.held(), true};
-    if (C.pool.reserve(np * 10) || C.ref.reserve(np)) return MIPGEN_E_NOMEM;
-    hipStream_t st = h->stream;
-    IdleOnExit idle{st};
-    HIP_TRY(hipMemcpyAsync(C.ref.p, mol_seq, np, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(C.pool.p, 0, np * 40, st));
-    SpanTimer timer{h->timing, st};
-    for (int64_t r = 0; r < sample_rows(R); r++) {
-        const int32_t* table = nullptr;
-        if (max_indel) {
-            if (int rc = count_gapped(h, P, C.gapped, B, mol_seq, mol_len, n, (int32_t)r, min_family, min_quality, max_indel, timer, nullptr, nullptr)) return rc;
-            table = C.gapped.counts.p;
-        } else {
-            if (int rc = count_plain(h, P, C.pile, B, mol_len, n, (int32_t)r, min_family, min_quality, timer, nullptr, nullptr)) return rc;
-            table = C.pile.counts.p;
-        }
-        timer.mark();
-        HIP_TRY(mipgen_launch_call_pool(st, table, max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, P.n_pos, bg_max_ppm, C.pool.p));
-        timer.mark();
-    }
-    HIP_TRY(idle.wait());
-    C.mol_len.assign(mol_len, mol_len + n);
-    C.mol_seq.assign(mol_seq, np);
-    C.min_family = min_family; C.min_quality = min_quality; C.max_indel = max_indel; C.bg_max_ppm = bg_max_ppm;
-    C.have = true;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->call_ms = ms;
-    return MIPGEN_OK;
+                    more >> 20, room >> 20);
+    const Budget B{"call pool", more, held, true};                       // held BEFORE the reserves, as it always was here (the locus route below takes it after)
+    if (C.state.pool.reserve(np * 10) || C.ref.reserve(np)) return MIPGEN_E_NOMEM;
+    HIP_TRY(hipMemcpyAsync(C.ref.p, mol_seq, np, hipMemcpyHostToDevice, h->stream));      // (build_pool leaves the stream idle however it ends)
+    return build_pool(h, P, probe_target(h, P.R), B, A, bg_max_ppm);
 }
 
 // The calls of one row against the pool: the row's pileup recomputed with the pool's arguments into R->call's scratch, then flag, tail and order.
 int mipgen_accel_reads_consensus_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, mipgen_call_totals* totals)
 {
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
-    CallScratch& C = h->consensus->call;
-    if (!C.have) return fail(MIPGEN_E_STATE, "the consensus reads have no pool: mipgen_accel_reads_consensus_call_pool builds it");
+    if (int rc = check_reads(h)) return rc;
+    const PoolState& S = h->consensus->call.state;
+    if (!S.have) return fail(MIPGEN_E_STATE, "the consensus reads have no pool: mipgen_accel_reads_consensus_call_pool builds it");
     RowPlan P;
-    const GappedArgs args{C.mol_seq.data(), C.max_indel, C.max_indel == 0};
-    const int32_t n = (int32_t)C.mol_len.size();
-    if (int rc = plan_row(h, C.mol_len.data(), n, row, C.min_family, C.min_quality, &args, &P)) return rc;
-    if (int rc = check_call_params(params)) return rc;
-    if (params->bg_max_ppm != C.bg_max_ppm) return fail(MIPGEN_E_STATE, "bg_max_ppm %d: the pool was built with %d", params->bg_max_ppm, C.bg_max_ppm);
-    h->call_ms = -1.0;
-    h->call_run.n_calls = -1;
-    const Budget B{"call", call_run_bytes(P.n_pos), h->call_run.held(), true};
-    SpanTimer timer{h->timing, h->stream};
-    const int32_t* table = nullptr;
-    C.have_last = false;
-    if (C.max_indel) {
-        if (int rc = count_gapped(h, P, C.gapped, B, C.mol_seq.data(), C.mol_len.data(), n, row, C.min_family, C.min_quality, C.max_indel, timer, counts, &C.last)) return rc;
-        table = C.gapped.counts.p;
-    } else {
-        mipgen_pileup_totals pt{0, 0, 0, 0};
-        if (int rc = count_plain(h, P, C.pile, B, C.mol_len.data(), n, row, C.min_family, C.min_quality, timer, counts, &pt)) return rc;
-        C.last = {pt.groups, pt.used, pt.bases, pt.discordant, 0, 0, 0, 0};
-        table = C.pile.counts.p;
-    }
-    C.have_last = true;
-    if (int rc = run_call(h, table, C.max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, C.pool.p, C.ref.p, P.n_pos, (int64_t)row < sample_rows(P.R), *params, timer, totals)) return rc;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->call_ms = ms;
-    return MIPGEN_OK;
+    RowArgs A;
+    if (int rc = plan_call(h, S, row, params, "pool", &A, &P)) return rc;
+    return call_row(h, P, probe_target(h, P.R), A, "call", row, *params, counts, nullptr, totals);
 }
 
 int mipgen_accel_reads_consensus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals)
 {
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus || !h->consensus->call.have_last) return fail(MIPGEN_E_STATE, "no row was called: mipgen_accel_reads_consensus_call counts one");
-    if (totals) *totals = h->consensus->call.last;
-    return MIPGEN_OK;
+    return last_pileup_totals(h, false, "no row was called: mipgen_accel_reads_consensus_call counts one", totals);
 }
 
 // A table from host arrays folded by a plan from host arrays: no read session is needed; everything is uploaded into the handle's LocusRun.
@@ -529,16 +558,13 @@ int mipgen_accel_locus_tables(mipgen_accel* h, const int32_t* counts, int32_t co
         HIP_TRY(hipMemcpyAsync(U.counts.p, counts, np * cols * 4, hipMemcpyHostToDevice, h->stream));
     }
     if (int rc = merge_loci(h, U.plan, U.counts.p, columns, U.merged.p, U.ctr.p, timer, merged, totals)) return rc;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->locus_ms = ms;
-    return MIPGEN_OK;
+    return booked(timer, &h->locus_ms);
 }
 
 // The plan and the ref bytes of the loci for the consensus reads the handle holds.  Writes R->locus only; a pool over an earlier plan is dropped.
 int mipgen_accel_reads_consensus_locus_plan(mipgen_accel* h, const int64_t* plan, int64_t n_pos, const uint8_t* locus_ref, int64_t n_loci)
 {
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    if (int rc = check_reads(h)) return rc;
     if (!locus_ref) return fail(MIPGEN_E_INVALID, "bad arguments: no ref bytes of the loci");
     if (int rc = check_locus_plan(plan, n_pos, n_loci)) return rc;
     HIP_TRY(hipSetDevice(h->device));
@@ -546,16 +572,14 @@ int mipgen_accel_reads_consensus_locus_plan(mipgen_accel* h, const int64_t* plan
     h->locus_ms = -1.0;
     SpanTimer timer{h->timing, h->stream};
     const int built = build_locus_plan(h, L.plan, plan, n_pos, n_loci, padded((size_t)n_loci, 1), L.ref.cap, "locus plan", timer);
-    if (!L.plan.have || built == MIPGEN_OK) L.have_pool = L.have_last = false;   // the pool goes with its plan: a plan refused for its budget leaves both as they were
+    if (!L.plan.have || built == MIPGEN_OK) L.state.drop();                      // the pool goes with its plan: a plan refused for its budget leaves both as they were
     if (built) return built;
     L.plan.have = false;                                                 // (until the ref bytes are there too)
     if (L.ref.reserve((size_t)n_loci)) return MIPGEN_E_NOMEM;
     HIP_TRY(hipMemcpyAsync(L.ref.p, locus_ref, (size_t)n_loci, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     L.plan.have = true;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->locus_ms = ms;
-    return MIPGEN_OK;
+    return booked(timer, &h->locus_ms);
 }
 
 // One row counted per template position and folded per locus.  Reads R's groups and reads and the installed plan; writes R->locus only.
@@ -563,26 +587,25 @@ int mipgen_accel_reads_consensus_locus_pileup(mipgen_accel* h, const char* mol_s
                                               int32_t max_indel, int32_t* probe_counts, int32_t* locus_counts, mipgen_gapped_totals* pileup_totals, mipgen_locus_totals* totals)
 {
     RowPlan P;
-    const GappedArgs args{mol_seq, max_indel};
-    if (int rc = plan_row(h, mol_len, n, row, min_family, min_quality, max_indel ? &args : nullptr, &P)) return rc;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, max_indel != 0};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
     LocusScratch& L = P.R->locus;
     if (int rc = check_locus_session(L, P)) return rc;
     h->locus_ms = -1.0;
     const size_t nl = (size_t)L.plan.n_loci, cols = max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS;
     const size_t more = padded(nl * cols, 4) + padded(1, sizeof(LocusCounters));
     const auto held = [&] { return L.merged.cap * 4 + L.ctr.cap * sizeof(LocusCounters); };
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (more > held() + free_b)
+    size_t room = 0;
+    if (int rc = room_beside(held(), &room)) return rc;
+    if (more > room)
         return fail(MIPGEN_E_NOMEM, "locus pileup: %lld loci need %zu MiB of device memory beside the pileup's, %zu MiB are free", (long long)L.plan.n_loci, more >> 20,
-                    (held() + free_b) >> 20);
+                    room >> 20);
     if (L.merged.reserve(nl * cols) || L.ctr.reserve(1)) return MIPGEN_E_NOMEM;
     const Budget B{"locus pileup", more, held(), true};                  // held AFTER the reserves: what they took is no longer free, and the count tests need <= held + free
     SpanTimer timer{h->timing, h->stream};
-    if (int rc = count_and_merge(h, P, L, B, mol_seq, mol_len, n, row, min_family, min_quality, max_indel, timer, probe_counts, locus_counts, pileup_totals, totals)) return rc;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->locus_ms = ms;
-    return MIPGEN_OK;
+    Counted counted;
+    if (int rc = count_target(h, P, locus_target(h, P.R), B, A, row, timer, probe_counts, locus_counts, pileup_totals, totals, &counted)) return rc;
+    return booked(timer, &h->locus_ms);
 }
 
 // The pool over the sample rows of the session, per locus: every row counted, folded and added on the device.  Writes R->locus only.
@@ -590,82 +613,45 @@ int mipgen_accel_reads_consensus_locus_call_pool(mipgen_accel* h, const char* mo
                                                  int32_t max_indel, int32_t bg_max_ppm)
 {
     RowPlan P;
-    const GappedArgs args{mol_seq, max_indel};
-    if (int rc = plan_row(h, mol_len, n, 0, min_family, min_quality, max_indel ? &args : nullptr, &P)) return rc;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, max_indel != 0};      // (the ref bytes came with the plan, which also bounded the loci)
+    if (int rc = plan_row(h, A, 0, &P)) return rc;
     if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
-    ConsensusResult* R = P.R;
-    LocusScratch& L = R->locus;
+    LocusScratch& L = P.R->locus;
     if (int rc = check_locus_session(L, P)) return rc;
-    L.have_pool = L.have_last = false;                                   // (a pool that fails leaves none)
+    L.state.drop();                                                      // (a pool that fails leaves none)
     h->locus_ms = -1.0;
     const int64_t n_loci = L.plan.n_loci;
     const size_t nl = (size_t)n_loci, cols = max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS;
-    // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_plain's / count_gapped's
+    // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_row's
     const size_t more = padded(nl * cols, 4) + padded(nl * 10, 4) + padded(1, sizeof(LocusCounters)) + call_run_bytes(n_loci);
-    const auto held = [&] { return (L.merged.cap + L.pool.cap) * 4 + L.ctr.cap * sizeof(LocusCounters) + h->call_run.held(); };
-    size_t free_b = 0;
-    if (int rc = free_device_bytes(&free_b)) return rc;
-    if (more > held() + free_b)
+    const auto held = [&] { return (L.merged.cap + L.state.pool.cap) * 4 + L.ctr.cap * sizeof(LocusCounters) + h->call_run.held(); };
+    size_t room = 0;
+    if (int rc = room_beside(held(), &room)) return rc;
+    if (more > room)
         return fail(MIPGEN_E_NOMEM, "locus call pool: %lld loci need up to %zu MiB of device memory beside the pileup's, %zu MiB are free", (long long)n_loci, more >> 20,
-                    (held() + free_b) >> 20);
-    if (L.merged.reserve(nl * cols) || L.pool.reserve(nl * 10) || L.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+                    room >> 20);
+    if (L.merged.reserve(nl * cols) || L.state.pool.reserve(nl * 10) || L.ctr.reserve(1)) return MIPGEN_E_NOMEM;
     const Budget B{"locus call pool", more, held(), true};               // held AFTER the reserves, as in the locus pileup
-    hipStream_t st = h->stream;
-    IdleOnExit idle{st};
-    HIP_TRY(hipMemsetAsync(L.pool.p, 0, nl * 40, st));
-    SpanTimer timer{h->timing, st};
-    for (int64_t r = 0; r < sample_rows(R); r++) {
-        if (int rc = count_and_merge(h, P, L, B, mol_seq, mol_len, n, (int32_t)r, min_family, min_quality, max_indel, timer, nullptr, nullptr, nullptr, nullptr)) return rc;
-        timer.mark();
-        HIP_TRY(mipgen_launch_call_pool(st, L.merged.p, (int)cols, n_loci, bg_max_ppm, L.pool.p));
-        timer.mark();
-    }
-    HIP_TRY(idle.wait());
-    L.mol_len.assign(mol_len, mol_len + n);
-    if (mol_seq) L.mol_seq.assign(mol_seq, (size_t)P.n_pos); else L.mol_seq.clear();
-    L.min_family = min_family; L.min_quality = min_quality; L.max_indel = max_indel; L.bg_max_ppm = bg_max_ppm;
-    L.have_pool = true;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->locus_ms = ms;
-    return MIPGEN_OK;
+    return build_pool(h, P, locus_target(h, P.R), B, A, bg_max_ppm);
 }
 
 // The calls of one row per locus against the locus pool: the row counted with the pool's arguments and folded, then run_call over the loci.
 int mipgen_accel_reads_consensus_locus_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* probe_counts, int32_t* locus_counts,
                                             mipgen_call_totals* totals)
 {
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
-    LocusScratch& L = h->consensus->locus;
+    if (int rc = check_reads(h)) return rc;
+    const LocusScratch& L = h->consensus->locus;
     if (!L.plan.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus plan: mipgen_accel_reads_consensus_locus_plan installs it");
-    if (!L.have_pool) return fail(MIPGEN_E_STATE, "the consensus reads have no locus pool: mipgen_accel_reads_consensus_locus_call_pool builds it");
+    if (!L.state.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus pool: mipgen_accel_reads_consensus_locus_call_pool builds it");
     RowPlan P;
-    const GappedArgs args{L.mol_seq.data(), L.max_indel};
-    const int32_t n = (int32_t)L.mol_len.size();
-    if (int rc = plan_row(h, L.mol_len.data(), n, row, L.min_family, L.min_quality, L.max_indel ? &args : nullptr, &P)) return rc;
-    if (int rc = check_call_params(params)) return rc;
-    if (params->bg_max_ppm != L.bg_max_ppm) return fail(MIPGEN_E_STATE, "bg_max_ppm %d: the locus pool was built with %d", params->bg_max_ppm, L.bg_max_ppm);
-    h->locus_ms = -1.0;
-    h->call_run.n_calls = -1;
-    const Budget B{"locus call", call_run_bytes(L.plan.n_loci), h->call_run.held(), true};
-    SpanTimer timer{h->timing, h->stream};
-    L.have_last = false;
-    if (int rc = count_and_merge(h, P, L, B, L.mol_seq.data(), L.mol_len.data(), n, row, L.min_family, L.min_quality, L.max_indel, timer, probe_counts, locus_counts, &L.last,
-                                 nullptr)) return rc;
-    L.have_last = true;
-    if (int rc = run_call(h, L.merged.p, L.max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS, L.pool.p, L.ref.p, L.plan.n_loci, (int64_t)row < sample_rows(P.R), *params, timer, totals))
-        return rc;
-    double ms = 0.0;
-    if (timer.add_to(&ms)) h->locus_ms = ms;
-    return MIPGEN_OK;
+    RowArgs A;
+    if (int rc = plan_call(h, L.state, row, params, "locus pool", &A, &P)) return rc;
+    return call_row(h, P, locus_target(h, P.R), A, "locus call", row, *params, probe_counts, locus_counts, totals);
 }
 
 int mipgen_accel_reads_consensus_locus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals)
 {
-    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    if (!h->consensus || !h->consensus->locus.have_last) return fail(MIPGEN_E_STATE, "no row was called per locus: mipgen_accel_reads_consensus_locus_call counts one");
-    if (totals) *totals = h->consensus->locus.last;
-    return MIPGEN_OK;
+    return last_pileup_totals(h, true, "no row was called per locus: mipgen_accel_reads_consensus_locus_call counts one", totals);
 }
 
 // The records of the last call of either kind, in ascending (pos, allele).
