@@ -19,8 +19,16 @@
 //    and e = 1/2 it is 0.98: 2^-54 relative).  S >= 1, every exp argument is <= 0, and ln S adds a few 1e-16.
 //  At the depth cap n = 2^20 the magnitudes that meet in lt_k - three lnfact of up to 1.4e7, two products of up to 2.2e7 - sum to about 7e7; some six roundings of
 //  1.1e-16 of that are 5e-8 in natural-log units, 2e-7 in phred units (x 4.34), below the band of 1e-6 around an integer within which the tests do not compare.
-//  MIPGEN_CALL_MAX_DEPTH exists so that this holds: do not raise it without redoing the sum.  At n = 5,000, where the tests stay, the same sum is 2e5 and the
-//  error 6e-10.
+//  MIPGEN_CALL_MAX_DEPTH exists so that this holds: do not raise it without redoing the sum.
+//  What is compared.  Up to n = 5,000 the tests hold an exact integer sum (tests/call_ref.py::exact_phred); there the magnitudes sum to 2e5 and the error is
+//  6e-10.  From there to the cap the reference is hp_phred of the same file: the sum over every term in fixed point with 320 fractional bits, the logarithms in
+//  80-digit decimal, good to 1e-70 and equal to the exact sum to 6e-11 where both exist.  tests/golden/call_sharp_cells.json (tools/call_sharp_cells.py) holds, for
+//  each of the depths 200, 5,000, 5,001, 2^14, 2^16, 2^18, 2^20 - 1, 2^20 and each background near 1e-3, 1e-2, 0.3, 0.5, 0.9, a candidate whose score lies 2e-6 to
+//  2e-5 above an integer and one as far below - an error of either sign beyond 2e-6 flips a floor - plus k = n - 17 .. n under e = 0.999 (the last round of lanes
+//  runs into i > n) and e = (B - 1) / B at B = 10^6 and 2^31 - 1 + 2^30.  The host functions of this file stay within 8e-9 of hp_phred on all of them (4.9e-13 at
+//  n = 200, 4e-11 at 5,001, 3.5e-10 at 2^16, 1.3e-9 at 2^18, 8e-9 at 2^20: a twenty-fifth of the 2e-7 bounded above, the roundings partly cancelling), and
+//  k_call_tail returns the floor of hp_phred for every one, in every position of the wavefront and beside neighbours of any length
+//  (tests/test_call_cpu.py, tests/test_gpu_call_deep.py).
 #pragma once
 #include <math.h>
 #include <stdint.h>

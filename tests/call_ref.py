@@ -2,8 +2,10 @@
 `mipgen_count -call`): plain loops over rows, positions and allele classes, and the binomial tail as an EXACT Python integer: the sum of C(n,i) A^i B^(n-i) over
 ALL i = k..n with e = A / (A + B), over (A + B)^n.  No early stop, no log-gamma, no table; -10 log10 comes from math.log10 of the two big integers.  Test
 infrastructure."""
+import decimal
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from fractions import Fraction
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -82,7 +84,102 @@ def exact_phred(k: int, n: int, A: int, B: int) -> float:
     return -10.0 * (math.log10(total) - n * math.log10(B))
 
 
-def near_integer(phred: float) -> bool:
+# ---- the same score where the exact sum is out of reach: up to the depth cap --------------------------------------------------------------------------------
+HP_FRACTION_BITS = 320               # of the fixed-point sum
+HP_DIGITS = 80                       # of the decimal context the logarithms are taken in
+HP_STIRLING_FROM = 1000              # ln m! from math.factorial below, from Stirling's series from here on
+HP_STIRLING_TERMS = 8                # B_2j / (2j (2j-1) m^(2j-1)), j = 1..8
+
+
+def _bernoulli(count: int) -> List[Fraction]:
+    """B_0 .. B_count (B_1 = -1/2) from the recurrence sum_{j<=m} C(m+1, j) B_j = 0."""
+    B = [Fraction(1)]
+    for m in range(1, count + 1):
+        B.append(-sum(math.comb(m + 1, j) * B[j] for j in range(m)) / (m + 1))
+    return B
+
+
+_HP_CTX = decimal.Context(prec=HP_DIGITS, rounding=decimal.ROUND_HALF_EVEN, Emax=decimal.MAX_EMAX, Emin=decimal.MIN_EMIN)
+_HP_BERNOULLI = _bernoulli(2 * HP_STIRLING_TERMS)
+_HP_HALF_LN_2PI = None               # (set on first use: pi is not in the decimal module)
+_hp_lnfact_cache: Dict[int, decimal.Decimal] = {}
+
+
+def _hp_pi(ctx: decimal.Context) -> decimal.Decimal:
+    """Machin: pi = 16 atan(1/5) - 4 atan(1/239), as scaled integers with 20 guard digits."""
+    scale = 10 ** (HP_DIGITS + 20)
+
+    def atan_inv(x: int) -> int:
+        total, term, j = 0, scale // x, 0
+        while term:
+            total += term // (2 * j + 1) if j % 2 == 0 else -(term // (2 * j + 1))
+            term //= x * x
+            j += 1
+        return total
+
+    return ctx.divide(decimal.Decimal(16 * atan_inv(5) - 4 * atan_inv(239)), decimal.Decimal(scale))
+
+
+def hp_lnfact(m: int) -> decimal.Decimal:
+    """ln m! to about 1e-75 relative.  Below HP_STIRLING_FROM: the logarithm of the exact integer.  From there on Stirling's series (m + 1/2) ln m - m + ln(2 pi) / 2 +
+    sum_{j=1..8} B_2j / (2j (2j-1) m^(2j-1)).  The series is asymptotic with terms of alternating sign, so what it leaves is smaller than the first dropped term,
+    B_18 / (18 x 17 m^17) = 54.97 / 306 / m^17 < 1.8e-52 at m = 1,000 - far below the 1e-40 asked for."""
+    global _HP_HALF_LN_2PI
+    got = _hp_lnfact_cache.get(m)
+    if got is not None:
+        return got
+    ctx, D = _HP_CTX, decimal.Decimal
+    if m < HP_STIRLING_FROM:
+        out = ctx.ln(D(math.factorial(m)))
+    else:
+        if _HP_HALF_LN_2PI is None:
+            _HP_HALF_LN_2PI = ctx.divide(ctx.ln(ctx.multiply(D(2), _hp_pi(ctx))), D(2))
+        series = Fraction(0)
+        for j in range(1, HP_STIRLING_TERMS + 1):
+            series += _HP_BERNOULLI[2 * j] / (2 * j * (2 * j - 1) * m ** (2 * j - 1))
+        out = ctx.multiply(D(2 * m + 1) / 2, ctx.ln(D(m)))
+        out = ctx.add(ctx.subtract(out, D(m)), _HP_HALF_LN_2PI)
+        out = ctx.add(out, ctx.divide(D(series.numerator), D(series.denominator)))
+    if len(_hp_lnfact_cache) < 4096:
+        _hp_lnfact_cache[m] = out
+    return out
+
+
+def hp_phred(k: int, n: int, A: int, B: int) -> decimal.Decimal:
+    """-10 log10 of P(X >= k), X binomial(n, A / B), for a k above expectation (k B > n A: the terms fall from k on) at any depth up to the cap, from the standard
+    library alone: P = t_k S with S = sum_{i=k..n} t_i / t_k.
+     - S in fixed point, Python integers with HP_FRACTION_BITS fractional bits: t <- t (n-i) a // ((i+1) b), a = A, b = B - A, from t = 1, run to i = n or until the
+       fixed-point term is 0.  There is no relative early stop.  Truncation: every step floors once, which costs the term at most 1 unit in the last place, and the
+       factor (n-i) a / ((i+1) b) is below 1, so it does not grow what the term carries: after j steps the term is at most j units low, the sum of m terms at most
+       m^2 / 2 units.  When the fixed-point term reaches 0 after j steps the true term is below j + 1 units, and so is every later one, the terms falling: with
+       n <= 2^20 all of that stays below 2^41 units = 2^-279 of an S >= 1.
+     - ln t_k = ln n! - ln k! - ln (n-k)! + k ln(a / B) + (n-k) ln(b / B) in `decimal` at HP_DIGITS digits (hp_lnfact); the magnitudes that meet are below 1e8, so
+       the result carries about 1e-70.  No math.comb: at k about n / 2 and n = 2^20 it takes tens of seconds.
+    Returns a Decimal."""
+    a, b = A, B - A
+    assert 0 < a < B and 0 <= k <= n and k * B > n * a
+    one = 1 << HP_FRACTION_BITS
+    t = total = one
+    for i in range(k, n):
+        t = t * ((n - i) * a) // ((i + 1) * b)
+        if t == 0:
+            break
+        total += t
+    ctx, D = _HP_CTX, decimal.Decimal
+    ln_B = ctx.ln(D(B))
+    ln_tk = ctx.subtract(ctx.subtract(hp_lnfact(n), hp_lnfact(k)), hp_lnfact(n - k))
+    ln_tk = ctx.add(ln_tk, ctx.multiply(D(k), ctx.subtract(ctx.ln(D(a)), ln_B)))
+    ln_tk = ctx.add(ln_tk, ctx.multiply(D(n - k), ctx.subtract(ctx.ln(D(b)), ln_B)))
+    ln_S = ctx.subtract(ctx.ln(D(total)), ctx.multiply(D(HP_FRACTION_BITS), ctx.ln(D(2))))
+    return ctx.divide(ctx.multiply(D(-10), ctx.add(ln_tk, ln_S)), ctx.ln(D(10)))
+
+
+def hp_text(score: decimal.Decimal) -> str:
+    """The decimal string of a high-precision score as the fixtures hold it: 30 places."""
+    return str(score.quantize(decimal.Decimal(1).scaleb(-30), rounding=decimal.ROUND_HALF_EVEN, context=_HP_CTX))
+
+
+def near_integer(phred) -> bool:
     """Within DELTA of an integer at or below the cap - the floor could go either way - and so within DELTA of the cap itself."""
     if phred > Q_CAP + DELTA:
         return False
@@ -93,9 +190,10 @@ def q_of(phred: float) -> int:
     return min(Q_CAP, max(0, math.floor(phred)))
 
 
-def call_cells(counts: np.ndarray, pool_: np.ndarray, ref: bytes, own_row_is_sample: bool, p: Dict[str, int], filters_only: bool = False):
+def call_cells(counts: np.ndarray, pool_: np.ndarray, ref: bytes, own_row_is_sample: bool, p: Dict[str, int], filters_only: bool = False,
+               score: Callable[[int, int, int, int], object] = exact_phred):
     """(totals dict, candidates): every candidate as a dict of the record's fields plus `phred` (exact, before the floor; None with filters_only or above the depth
-    the exact sum is asked for) and `excluded` (near_integer).  Ascending (pos, allele).  totals["calls"] counts candidates with q >= min_q that are not excluded;
+    the exact sum is asked for) and `excluded` (near_integer).  score: exact_phred, or hp_phred for tables deeper than the exact sum can go.  Ascending (pos, allele).  totals["calls"] counts candidates with q >= min_q that are not excluded;
     totals["excluded"] says how many the band dropped."""
     n_pos, columns = counts.shape
     totals = {"tested": 0, "too_deep": 0, "candidates": 0, "calls": 0, "excluded": 0}
@@ -121,7 +219,7 @@ def call_cells(counts: np.ndarray, pool_: np.ndarray, ref: bytes, own_row_is_sam
             totals["candidates"] += 1
             rec = {"pos": x, "allele": a, "depth": n, "alt": k, "bg_alt": K_o, "bg_depth": N_o, "phred": None, "excluded": False, "q": None}
             if not filters_only:
-                rec["phred"] = exact_phred(k, n, K_o + p["a0"], N_o + p["n0"])
+                rec["phred"] = score(k, n, K_o + p["a0"], N_o + p["n0"])
                 rec["excluded"] = near_integer(rec["phred"])
                 rec["q"] = q_of(rec["phred"])
                 totals["excluded"] += rec["excluded"]

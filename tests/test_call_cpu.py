@@ -1,7 +1,10 @@
 """CPU: what of the variant calls needs no device - the new entry points under an unchanged ABI number and their ctypes mirrors, the oracle
 (tests/call_ref.py) against cells small enough to work out by hand, the lines of `mipgen_count -call` on both strands, every usage error of the new options, and
-the host functions of mipgen_amd/csrc/call_model.h, run as a stand-alone program under AddressSanitizer and UBSan, against the oracle on 2,000 random cells."""
+the host functions of mipgen_amd/csrc/call_model.h, run as a stand-alone program under AddressSanitizer and UBSan, against the oracle on 2,000 random cells;
+the high-precision score (call_ref.hp_phred) against the exact one, the fixture of sharp cells up to the depth cap against hp_phred, and the host functions on it."""
 import ctypes as C
+import decimal
+import json
 import math
 import os
 import shutil
@@ -174,13 +177,11 @@ def call_host(tmp_path_factory):
     return exe
 
 
-def test_the_host_functions_of_the_header_equal_the_oracle(call_host, tmp_path):
-    """2,000 random cells: candidate yes / no, K_o, N_o and Q.  A cell whose exact score lies within 1e-6 of an integer is not compared on Q; at most 1 in 1,000
-    may be (the priors are no powers of ten: under 1 / 1000 alone every k = n cell scores the integer 30 n).  The
-    largest |score - exact score| before the floor is asserted below 1e-8 - the accuracy argument of call_model.h gives 6e-10 at these depths."""
-    rng = np.random.default_rng(7301)
+def random_cells(seed, count):
+    """(cases, the lines call_host reads): cells of every kind at n <= 5,000."""
+    rng = np.random.default_rng(seed)
     cases, lines = [], []
-    for i in range(2000):
+    for i in range(count):
         columns = 8 if i % 2 else 5
         n = int(rng.choice([rng.integers(1, 40), rng.integers(40, 400), rng.integers(400, 5001)], p=[0.3, 0.6, 0.1]))
         a = int(rng.integers(0, CR.alleles(columns)))
@@ -199,6 +200,27 @@ def test_the_host_functions_of_the_header_equal_the_oracle(call_host, tmp_path):
             K, N = K + k, N + n                                                      # a sample row that qualifies is part of its pool
         cases.append((columns, row, K, N, a, own, p))
         lines.append(" ".join(str(v) for v in [columns, *row, K, N, a, own, *[p[f[0]] for f in capi.CallParams._fields_]]))
+    return cases, lines
+
+
+@pytest.fixture(scope="module")
+def shallow_cells():
+    """The 2,000 random cells of the host test with, per cell, (k, n, K_o, N_o, candidate?, exact score or None): the exact sums are taken once for the module."""
+    cases, lines = random_cells(7301, 2000)
+    scored = []
+    for columns, row, K, N, a, own, p in cases:
+        n, k = CR.depth(row, columns), CR.allele_count(row, columns, a)
+        K_o, N_o = CR.leave_one_out(K, N, k, n, bool(own), p["bg_max_ppm"])
+        is_cand = CR.candidate(k, n, K_o, N_o, p)
+        scored.append((k, n, K_o, N_o, is_cand, CR.exact_phred(k, n, K_o + p["a0"], N_o + p["n0"]) if is_cand else None))
+    return cases, lines, scored
+
+
+def test_the_host_functions_of_the_header_equal_the_oracle(call_host, shallow_cells, tmp_path):
+    """2,000 random cells: candidate yes / no, K_o, N_o and Q.  A cell whose exact score lies within 1e-6 of an integer is not compared on Q; at most 1 in 1,000
+    may be (the priors are no powers of ten: under 1 / 1000 alone every k = n cell scores the integer 30 n).  The
+    largest |score - exact score| before the floor is asserted below 1e-8 - the accuracy argument of call_model.h gives 6e-10 at these depths."""
+    cases, lines, scored = shallow_cells
     (tmp_path / "cases.txt").write_text("\n".join(lines) + "\n")
     out = subprocess.run([call_host, str(tmp_path / "cases.txt")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
@@ -206,19 +228,103 @@ def test_the_host_functions_of_the_header_equal_the_oracle(call_host, tmp_path):
     assert len(got) == len(cases)
     n_cand = skipped = 0
     worst = 0.0
-    for (columns, row, K, N, a, own, p), g in zip(cases, got):
-        n, k = CR.depth(row, columns), CR.allele_count(row, columns, a)
-        K_o, N_o = CR.leave_one_out(K, N, k, n, bool(own), p["bg_max_ppm"])
-        is_cand = CR.candidate(k, n, K_o, N_o, p)
+    for (columns, row, K, N, a, own, p), (k, n, K_o, N_o, is_cand, exact), g in zip(cases, scored, got):
         assert (int(g[0]), int(g[1]), int(g[2])) == (int(is_cand), K_o, N_o)
         if not is_cand:
             assert int(g[3]) == -1
             continue
         n_cand += 1
-        exact = CR.exact_phred(k, n, K_o + p["a0"], N_o + p["n0"])
         worst = max(worst, abs(float(g[4]) - exact))
         if CR.near_integer(exact):
             skipped += 1
         else:
             assert int(g[3]) == CR.q_of(exact), (k, n, K_o, N_o, p, g, exact)
     assert n_cand > 600 and skipped * 1000 <= n_cand and worst < 1e-8, (n_cand, skipped, worst)
+
+
+# ---- the high-precision reference and the cells it was used to choose (tools/call_sharp_cells.py) ----------------------------------------------------------------
+def test_the_high_precision_score_equals_the_exact_one_up_to_5000(shallow_cells):
+    """Every candidate among the 2,000 random cells (more than 600), n <= 5,000: |hp_phred - exact_phred| < 1e-9.  The bound is exact_phred's own rounding: two
+    math.log10 of magnitudes up to 3.5e4, each rounded to 7e-12, times 10; hp_phred carries 1e-70."""
+    cases, _, scored = shallow_cells
+    worst, at, n_cand = 0.0, None, 0
+    for (_, _, _, _, _, _, p), (k, n, K_o, N_o, is_cand, exact) in zip(cases, scored):
+        if not is_cand:
+            continue
+        n_cand += 1
+        hp = CR.hp_phred(k, n, K_o + p["a0"], N_o + p["n0"])
+        assert isinstance(hp, decimal.Decimal)
+        d = abs(float(hp - decimal.Decimal(exact)))
+        if d > worst:
+            worst, at = d, (k, n, K_o + p["a0"], N_o + p["n0"])
+    assert n_cand >= 300 and worst < 1e-9, f"largest |hp - exact| {worst:.3g} at (k, n, A, B) = {at} over {n_cand} candidates"
+    # the cells the series is about: ln m! on both sides of the switch from the exact factorial to Stirling's series
+    for m in (CR.HP_STIRLING_FROM - 1, CR.HP_STIRLING_FROM, CR.HP_STIRLING_FROM + 1, 4097):
+        assert abs(CR.hp_lnfact(m) - decimal.Context(prec=80).ln(decimal.Decimal(math.factorial(m)))) < decimal.Decimal("1e-45"), m
+
+
+FIXTURE = os.path.join(ROOT, "tests", "golden", "call_sharp_cells.json")
+SHARP_DEPTHS = [200, 5000, 5001, 1 << 14, 1 << 16, 1 << 18, (1 << 20) - 1, 1 << 20]
+
+
+def fixture_cells():
+    """(the fixture, all its cells as (kind, cell dict))."""
+    doc = json.load(open(FIXTURE))
+    return doc, [(kind, c) for kind in ("sharp", "loop_end", "near_one") for c in doc[kind]]
+
+
+def test_the_fixture_is_what_the_reference_computes_and_as_sharp_as_it_says():
+    doc, cells = fixture_cells()
+    lo, hi = decimal.Decimal("2e-6"), decimal.Decimal("2e-5")
+    assert [decimal.Decimal(b) for b in doc["band"]] == [lo, hi]
+    sides = {n: set() for n in SHARP_DEPTHS}
+    per_depth = {n: 0 for n in SHARP_DEPTHS}
+    backgrounds = {n: set() for n in SHARP_DEPTHS}
+    for kind, c in cells:
+        p = CR.params(**doc["filters"], a0=c["a0"], n0=c["n0"])
+        assert CR.candidate(c["k"], c["n"], c["K_o"], c["N_o"], p), c
+        hp = CR.hp_phred(c["k"], c["n"], c["K_o"] + c["a0"], c["N_o"] + c["n0"])
+        assert CR.hp_text(hp) == c["hp"], c
+        assert 0 < hp < CR.Q_CAP
+        d = hp - hp.to_integral_value(rounding=decimal.ROUND_HALF_EVEN)
+        if kind == "sharp":
+            assert lo <= abs(d) <= hi and (1 if d > 0 else -1) == c["side"], (c, d)
+            e = (c["K_o"] + c["a0"]) / (c["N_o"] + c["n0"])
+            mean, sigma = c["n"] * e, math.sqrt(c["n"] * e * (1 - e))
+            A, B = c["K_o"] + c["a0"], c["N_o"] + c["n0"]                            # the generator draws A within 3 % of e B and rounds it to an integer
+            assert mean < c["k"] <= mean + 8 * sigma + 1 and abs(A - c["e"] * B) <= 0.03 * c["e"] * B + 0.5, c
+            sides[c["n"]].add(c["side"])
+            per_depth[c["n"]] += 1
+            backgrounds[c["n"]].add(c["e"])
+        else:
+            assert abs(d) > decimal.Decimal("1e-4"), c
+    assert all(s == {1, -1} for s in sides.values()), sides
+    assert all(v >= 6 for v in per_depth.values()) and sum(per_depth.values()) >= 64, per_depth
+    assert all(b == {1e-3, 1e-2, 0.3, 0.5, 0.9} for b in backgrounds.values())
+    cap = CR.MAX_DEPTH
+    assert sorted((c["n"], c["n"] - c["k"]) for c in doc["loop_end"]) == sorted((n, back) for n in (20000, cap) for back in (17, 16, 15, 1, 0))
+    assert all((c["K_o"] + c["a0"]) * 1000 >= 999 * (c["N_o"] + c["n0"]) for c in doc["loop_end"])
+    assert all(c["k"] == c["n"] and c["K_o"] + c["a0"] == c["N_o"] + c["n0"] - 1 for c in doc["near_one"])
+    assert {c["N_o"] + c["n0"] for c in doc["near_one"]} == {10 ** 6, (1 << 31) - 1 + (1 << 30)}
+
+
+def test_the_host_functions_of_the_header_on_every_fixture_cell(call_host, tmp_path):
+    """Every cell of the fixture through call_model.h's host functions under the sanitizers: q is the floor of the high-precision score for EVERY cell - the sharp
+    ones lie 2e-6 from an integer, so none is excluded - and |score - hp| < 2e-7, the bound the header states for the depth cap.  The largest difference per
+    depth goes into the assertion message (DESIGN 4.14 records them)."""
+    doc, cells = fixture_cells()
+    lines = [f"5 {c['n'] - c['k']} {c['k']} 0 0 0 {c['K_o']} {c['N_o']} 1 0 1 1 0 0 {c['a0']} {c['n0']} 1000000" for _, c in cells]
+    (tmp_path / "cases.txt").write_text("\n".join(lines) + "\n")
+    out = subprocess.run([call_host, str(tmp_path / "cases.txt")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    got = [l.split() for l in out.stdout.decode().splitlines()]
+    assert len(got) == len(cells)
+    worst, wrong = {}, []
+    for (kind, c), g in zip(cells, got):
+        hp = decimal.Decimal(c["hp"])
+        assert (int(g[0]), int(g[1]), int(g[2])) == (1, c["K_o"], c["N_o"])
+        if int(g[3]) != math.floor(hp):
+            wrong.append((kind, c, g))
+        worst[c["n"]] = max(worst.get(c["n"], 0.0), abs(float(decimal.Decimal(g[4]) - hp)))
+    report = ", ".join(f"n {n}: {d:.2g}" for n, d in sorted(worst.items()))
+    assert not wrong and max(worst.values()) < 2e-7, (report, wrong)
