@@ -519,6 +519,34 @@ int mipgen_accel_reads_consensus_locus_call(mipgen_accel* h, int32_t row, const 
  * that call's probe_counts needs no second count.  MIPGEN_E_STATE before such a call. */
 int mipgen_accel_reads_consensus_locus_call_pileup_totals(mipgen_accel* h, mipgen_gapped_totals* totals);
 
+/* ---- insertion alleles: the inserted bases per anchor, counted per sample (new entry points only: the ABI number does not change) ----
+ * Everything up to the vote at an anchor is the gapped pileup above, unchanged.  A used molecule at anchor t (0 <= t <= mol_len - 2) that no side covers counts
+ * nothing; two covering sides with different lengths count `ins_discordant`; every other molecule SPANS the anchor with an agreed length l >= 0 (`span`), and with
+ * l > 0 it is one EVENT (`ins`: exactly the molecules column 6 of the gapped table counts).  The inserted string of an event, in the orientation of M: a covering
+ * side's run is the l read bases q[i .. i + l - 1], i the read index its path holds when it consumes the column in front of the run; base j is q[i + j] on the
+ * extension side and complement(q[i + l - 1 - j]) on the ligation side, each with its quality; a base is usable as in the pileup (A C G T, quality - 33 >=
+ * min_quality); base j of the molecule is the one usable base, or the common base of two usable ones that agree, else AMBIGUOUS, and so is the event then.  A run of
+ * more than 15 bases (up to 2 max_indel, behind deletions) is always ambiguous.  An ALLELE is (pos = pos_off[p] + t, length, ambiguous, bases): bases holds 2 bits
+ * per base (A C G T = 0..3), base 0 in the most significant of the 2 length used bits, and is 0 for an ambiguous event; all ambiguous events of one (pos, length) are
+ * one allele.  Records come in ascending order of the key pos << 35 | length << 31 | ambiguous << 30 | bases (an allele longer than 15 bases: length field 0, its
+ * length in the low bits - it comes first at its position), distinct, the same bytes from call to call.
+ *   consensus_insertions: counts (n_pos x 8, may be NULL) is what mipgen_accel_reads_consensus_pileup_gapped returns for the same arguments; anchors (n_pos x 4 int32,
+ *                         may be NULL): span, ins, ins_discordant, ambiguous (= the ambiguous events) per anchor, the row of t = mol_len - 1 zero.
+ *                         anchors[:, 1] == counts[:, 6] and anchors[:, 2] == counts[:, 7]; per position the counts of the records add up to anchors[:, 1], those
+ *                         of the ambiguous ones to anchors[:, 3].  totals (may be NULL): groups, used, gapped_sides as the gapped pileup's; span, insertions,
+ *                         ins_discordant, ambiguous = the column sums; alleles = the records left on the handle.
+ *   insertions_fetch:     the records of the last consensus_insertions; n must equal its totals.alleles.
+ * MIPGEN_E_INVALID: every refusal of the gapped pileup; more than 2^29 - 1 template positions; more than 2^31 - 1 events in the row; fetch with another n.
+ * MIPGEN_E_STATE: no consensus reads; fetch before any call (or after one that failed).  MIPGEN_E_NOMEM: the gapped pileup's bytes with 5 bytes per projected
+ * position, 16 bytes per position of anchors, and - once the count has given the events - 48 bytes per event and the sort's scratch, against free device memory; each
+ * check comes before the allocations it covers.  The call counts into scratch of its own (released with the reads): the pileup, call and locus entry points, their
+ * scratch and timing indices 11-14 are untouched by it; it may be repeated, for any row in any order.  A handle with zero groups gives zeros. */
+typedef struct mipgen_insertion_record { int64_t pos; int32_t length, count; uint32_t bases; int32_t ambiguous; } mipgen_insertion_record;
+typedef struct mipgen_insertion_totals { int64_t groups, used, span, insertions, ins_discordant, ambiguous, alleles, gapped_sides; } mipgen_insertion_totals;
+int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                            int32_t max_indel, int32_t* counts, int32_t* anchors, mipgen_insertion_totals* totals);
+int mipgen_accel_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* records, int64_t n);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -734,7 +762,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * (timing enabled); 11 = the pileup kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled); 12 = the kernels of the last
  * mipgen_accel_reads_consensus_pileup_gapped (timing enabled); 13 = the kernels of the last mipgen_accel_call_tables, mipgen_accel_reads_consensus_call (its pileup
  * included) or mipgen_accel_reads_consensus_call_pool (timing enabled); 14 = the kernels of the last locus call of any kind (mipgen_accel_locus_tables,
- * mipgen_accel_reads_consensus_locus_*), its pileup included (timing enabled). */
+ * mipgen_accel_reads_consensus_locus_*), its pileup included (timing enabled); 15 = the kernels of the last mipgen_accel_reads_consensus_insertions, its
+ * placement and count included (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

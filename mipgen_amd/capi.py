@@ -106,6 +106,11 @@ class LocusTotals(C.Structure):    # mipgen_locus_totals
     _fields_ = [(n, C.c_int64) for n in ("covered", "bases", "discordant", "deletions", "insertions", "ins_discordant")]
 
 
+class InsertionTotals(C.Structure):    # mipgen_insertion_totals
+    _fields_ = [(n, C.c_int64) for n in ("groups", "used", "span", "insertions", "ins_discordant", "ambiguous", "alleles", "gapped_sides")]
+
+
+INSERTION_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("count", "<i4"), ("bases", "<u4"), ("ambiguous", "<i4")])   # mipgen_insertion_record, 24 bytes
 CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("allele", "<i4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4")])   # mipgen_call_record
 CALL_MAX_DEPTH = 1 << 20
 
@@ -399,6 +404,10 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_consensus_pileup.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(PileupTotals)]
     lib.mipgen_accel_reads_consensus_pileup_gapped.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                                C.POINTER(C.c_int32), C.POINTER(GappedTotals)]
+    lib.mipgen_accel_reads_consensus_insertions.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(InsertionTotals)]
+    lib.mipgen_accel_insertions_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
+    lib.mipgen_accel_insertions_fetch.restype = C.c_int
     lib.mipgen_accel_call_tables.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CallParams),
                                              C.POINTER(CallTotals)]
     lib.mipgen_accel_reads_consensus_call_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -416,7 +425,8 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_call_tables.restype = lib.mipgen_accel_call_fetch.restype = lib.mipgen_accel_reads_consensus_call_pileup_totals.restype = C.c_int
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
                  "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped", "consensus_call_pool", "consensus_call",
-                 "consensus_locus_plan", "consensus_locus_pileup", "consensus_locus_call_pool", "consensus_locus_call", "consensus_locus_call_pileup_totals"):
+                 "consensus_locus_plan", "consensus_locus_pileup", "consensus_locus_call_pool", "consensus_locus_call", "consensus_locus_call_pileup_totals",
+                 "consensus_insertions"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -502,6 +512,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_consensus_call_pileup_totals",
     "mipgen_accel_locus_tables", "mipgen_accel_reads_consensus_locus_plan", "mipgen_accel_reads_consensus_locus_pileup",
     "mipgen_accel_reads_consensus_locus_call_pool", "mipgen_accel_reads_consensus_locus_call", "mipgen_accel_reads_consensus_locus_call_pileup_totals",
+    "mipgen_accel_reads_consensus_insertions", "mipgen_accel_insertions_fetch",
 ]
 
 
@@ -1059,6 +1070,26 @@ class Accel:
         self._check(self.lib.mipgen_accel_reads_consensus_pileup_gapped(self.h, seq, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
                                                                         counts.ctypes.data_as(i32p), C.byref(tot)))
         return counts, self._totals(tot)
+
+    def consensus_insertions(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 8):
+        """mipgen_accel_reads_consensus_insertions, callable after consensus_reads: the insertion alleles of one row.  Arguments as consensus_pileup_gapped
+        takes them.  Returns (counts[sum(mol_len)][8] - the gapped pileup's table -, anchors[sum(mol_len)][4] int32 - span, ins, ins_discordant, ambiguous per anchor -,
+        the records as an array of INSERTION_RECORD_DTYPE in ascending key order, and the totals dict: groups, used, span, insertions, ins_discordant, ambiguous,
+        alleles, gapped_sides)."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        counts = np.empty((total, 8), dtype=np.int32)
+        anchors = np.empty((total, 4), dtype=np.int32)
+        tot = InsertionTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_reads_consensus_insertions(self.h, seq, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
+                                                                     counts.ctypes.data_as(i32p), anchors.ctypes.data_as(i32p), C.byref(tot)))
+        return counts, anchors, self.insertions_fetch(int(tot.alleles)), self._totals(tot)
+
+    def insertions_fetch(self, n: int) -> np.ndarray:
+        """mipgen_accel_insertions_fetch: the n records of the last consensus_insertions as an array of INSERTION_RECORD_DTYPE."""
+        records = np.zeros(n, dtype=INSERTION_RECORD_DTYPE)
+        self._check(self.lib.mipgen_accel_insertions_fetch(self.h, records.ctypes.data if n else None, n))
+        return records
 
     def call_fetch(self, n: int) -> np.ndarray:
         """mipgen_accel_call_fetch: the n records of the last call of either kind as an array of CALL_RECORD_DTYPE, in ascending (pos, allele)."""

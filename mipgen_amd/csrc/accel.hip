@@ -588,6 +588,7 @@ double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which)
     if (h && which == 12) return h->gapped_ms;
     if (h && which == 13) return h->call_ms;
     if (h && which == 14) return h->locus_ms;
+    if (h && which == 15) return h->insertions_ms;
     if (!h || !h->timing) return -1.0;
     if (hipSetDevice(h->device) != hipSuccess) return -1.0;
     double total = 0.0;

@@ -233,18 +233,35 @@ struct LocusScratch {
     size_t held() const { return plan.held() + ref.cap + pile.held() + gapped.held() + (merged.cap + state.pool.cap) * 4 + ctr.cap * sizeof(LocusCounters); }
     void release() { plan.release(); ref.release(); pile.release(); gapped.release(); merged.release(); ctr.release(); state.release(); }
 };
+// mipgen_accel_reads_consensus_insertions: a count scratch of its own - its projections have five planes -, the anchor table, the events and what
+// orders them; released with the reads.  run keys and run counts take the place of keys and ids once the sort has read them.
+struct InsScratch {
+    CountScratch count;
+    DevBuf<int32_t> anchors;                                 // positions x INSERTION_COLUMNS
+    DevBuf<InsCounters> ctr;
+    DevBuf<uint64_t> keys, keys_sorted;                      // events
+    DevBuf<uint32_t> ids, ids_sorted;                        // events (the sort moves pairs; nothing reads them)
+    DevBuf<char> temp;
+    DevBuf<mipgen_insertion_record> records;                 // events at most
+    int64_t n_alleles = -1;                                  // the records of the last call (-1: none, or it failed)
+    size_t event_held() const { return (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap) * 4 + temp.cap + records.cap * sizeof(mipgen_insertion_record); }
+    size_t table_held() const { return anchors.cap * 4 + ctr.cap * sizeof(InsCounters); }
+    void release() { count.release(); anchors.release(); ctr.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release();
+                     records.release(); n_alleles = -1; }
+};
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
     int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
     CountScratch pile, gapped;                               // of mipgen_accel_reads_consensus_pileup and _pileup_gapped
     CallScratch call;
     LocusScratch locus;
+    InsScratch ins;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); }
 };
 
 struct mipgen_accel {
@@ -372,6 +389,7 @@ struct mipgen_accel {
     double call_ms = -1.0;           // the kernels of the last mipgen_accel_call_tables / _reads_consensus_call / _reads_consensus_call_pool (timing enabled)
     LocusRun locus_run;              // the plan and tables of the last mipgen_accel_locus_tables (accel_pileup.hip)
     double locus_ms = -1.0;          // the kernels of the last locus call of any kind, its pileup included (timing enabled)
+    double insertions_ms = -1.0;     // the kernels of the last mipgen_accel_reads_consensus_insertions (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

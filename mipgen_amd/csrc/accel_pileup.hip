@@ -1,21 +1,23 @@
 // accel_pileup.hip — the two pileups read off the consensus reads a session left on the handle: allele counts per template position of one row (DESIGN 4.12:
 // mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped), the variant calls made from them (4.14: mipgen_accel_call_tables,
 // _reads_consensus_call_pool, _reads_consensus_call, _call_fetch) and the same per genome locus (4.15: mipgen_accel_locus_tables, _reads_consensus_locus_plan /
-// _locus_pileup / _locus_call_pool / _locus_call).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
+// _locus_pileup / _locus_call_pool / _locus_call), and the insertion alleles of a row (4.16: mipgen_accel_reads_consensus_insertions, mipgen_accel_insertions_fetch).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
 // count_row is the ONE count: the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches of the plain
 // or the gapped table, download and totals of one row into the CountScratch it is given.  Every entry point gives a scratch of its own - `pile` / `gapped` of the
-// ConsensusResult, of its CallScratch, of its LocusScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
+// ConsensusResult, of its CallScratch, of its LocusScratch, of its InsScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
 // a Target: per template position, or per locus, where count_target folds the row's table by the installed plan (kernels_locus.hip) between the count and the pool
 // or run_call.  An entry point is its own refusals, its budget and one call of the shared route.
 #include "accel_internal.h"
 #include "gapped_align.h"
 
 // The arguments of a row, as every level takes them.  need_seq: the call refuses a NULL mol_seq; must_place: it places with indels whatever max_indel says (the gapped
-// pileup, which so refuses max_indel 0); otherwise a row is placed when max_indel is not 0.
+// pileup, which so refuses max_indel 0); otherwise a row is placed when max_indel is not 0.  runs: the projections take five planes, the run indices of DESIGN 4.16 in the
+// last two.
 struct RowArgs {
     const char* mol_seq; const int32_t* mol_len; int32_t n, min_family, min_quality, max_indel;
-    bool need_seq = false, must_place = false;
+    bool need_seq = false, must_place = false, runs = false;
     bool placed() const { return must_place || max_indel != 0; }
+    int planes() const { return runs ? 5 : 3; }
 };
 
 struct RowPlan {
@@ -108,8 +110,8 @@ static int prepare_row(mipgen_accel* h, const RowPlan& P, RowScratch& W, const c
 
 // What a call adds to the budget of the row it counts: the bytes it will still allocate beside the row's, and what it already holds of them.  what: the call's name.
 struct Budget { const char* what; size_t more_need = 0, more_held = 0; bool keep_on_device = false; };   // keep_on_device: a session without groups still leaves a zeroed table in W.counts
-// a counted table on the device and its columns
-struct Counted { const int32_t* table = nullptr; int columns = 0; };
+// a counted table on the device and its columns; of a row that launched (have_row), its plan and its first group: what a further pass over the row's projections needs
+struct Counted { const int32_t* table = nullptr; int columns = 0; bool have_row = false; PileRow row{}; uint32_t g_first = 0; };
 
 // One row counted into W: the plain table at max_indel 0, else the one with indels (4.13).  W.counts holds it afterwards - *out says so -, `counts` (may
 // be NULL) a copy, *totals (may be NULL) its sums, the gapped-only ones 0 for the plain table; the kernels are spans of `timer`.
@@ -139,7 +141,7 @@ static int count_row(mipgen_accel* h, const RowPlan& P, CountScratch& W, const B
     const size_t G = (size_t)R->n_groups;
     size_t need = P.bytes + padded(cells, 4) + B.more_need, room = 0;
     if (gapped)
-        need += padded(n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) + padded(2 * G * 3 * (size_t)P.max_len, 1) + padded(1, sizeof(GappedCounters));
+        need += padded(n_pos, 1) + padded(2 * G, 8) + padded(2 * G, 4) + padded(2 * G, 1) + padded(2 * G * (size_t)A.planes() * (size_t)P.max_len, 1) + padded(1, sizeof(GappedCounters));
     if (int rc = room_beside(W.held() + B.more_held, &room)) return rc;
     if (need > room && gapped)
         return fail(MIPGEN_E_NOMEM, "%s: %lld template positions and %lld groups need up to %zu MiB of device memory, %zu MiB are free", B.what, (long long)P.n_pos,
@@ -168,16 +170,16 @@ static int count_row(mipgen_accel* h, const RowPlan& P, CountScratch& W, const B
         if (n_row > 0) {
             if (W.need.reserve(2 * (size_t)n_row) || W.list.reserve(2 * (size_t)n_row) || W.proj_off.reserve(2 * (size_t)n_row)) return MIPGEN_E_NOMEM;
             timer.mark();
-            HIP_TRY(mipgen_launch_gap_list(st, C, Row, W.mol_seq.p, first, n_row, A.max_indel, W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
+            HIP_TRY(mipgen_launch_gap_list(st, C, Row, W.mol_seq.p, first, n_row, A.max_indel, A.planes(), W.need.p, W.list.p, W.proj_off.p, W.ctr.p));
             timer.mark();
             HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * 3ull * (unsigned long long)P.max_len)
+            if ((int64_t)gc.n_sides > 2 * n_row || gc.proj_bytes > (unsigned long long)gc.n_sides * (unsigned long long)A.planes() * (unsigned long long)P.max_len)
                 return fail(MIPGEN_E_STATE, "%s: %llu sides listed of %lld, %llu projection bytes", B.what, gc.n_sides, (long long)(2 * n_row), gc.proj_bytes);
             if (gc.proj_bytes && W.proj.reserve((size_t)gc.proj_bytes)) return MIPGEN_E_NOMEM;
         }
         timer.mark();
-        HIP_TRY(mipgen_launch_gapped(st, C, Row, P.n_units, W.mol_seq.p, first, A.max_indel, P.max_len, W.list.p, (int64_t)gc.n_sides, W.proj_off.p, W.proj.p, W.counts.p, W.ctr.p));
+        HIP_TRY(mipgen_launch_gapped(st, C, Row, P.n_units, W.mol_seq.p, first, A.max_indel, P.max_len, A.planes(), W.list.p, (int64_t)gc.n_sides, W.proj_off.p, W.proj.p, W.counts.p, W.ctr.p));
         timer.mark();
         HIP_TRY(hipMemcpyAsync(&gc, W.ctr.p, sizeof gc, hipMemcpyDeviceToHost, st));
     }
@@ -187,7 +189,7 @@ static int count_row(mipgen_accel* h, const RowPlan& P, CountScratch& W, const B
     if (totals)
         *totals = {n_row, (int64_t)pc.used, (int64_t)gc.bases, (int64_t)gc.discordant, (int64_t)gc.deletions, (int64_t)gc.insertions, (int64_t)gc.ins_discordant,
                    (int64_t)gc.gapped_sides};
-    *out = {W.counts.p, columns};
+    *out = {W.counts.p, columns, true, Row, first};
     return MIPGEN_OK;
 }
 
@@ -465,6 +467,95 @@ int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_
     Counted counted;
     if (int rc = count_row(h, P, P.R->gapped, Budget{"gapped pileup"}, A, row, gap_time, counts, totals, &counted)) return rc;
     return booked(gap_time, &h->gapped_ms);
+}
+
+// Insertion alleles of one row: the gapped count with five-plane projections, then - the events being its `insertions` total - the anchor table and the
+// events in one pass of the count frame, the keys sorted, their runs, and a record per run.  Reads R's groups and reads; writes R->ins only.
+int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                            int32_t max_indel, int32_t* counts, int32_t* anchors, mipgen_insertion_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
+    if (P.n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: the insertion alleles take 2^29 - 1 at most", (long long)P.n_pos);
+    InsScratch& S = P.R->ins;
+    S.n_alleles = -1;
+    h->insertions_ms = -1.0;
+    const size_t np = (size_t)P.n_pos, cells = np * INSERTION_COLUMNS;
+    hipStream_t st = h->stream;
+    SpanTimer timer{h->timing, st};
+    mipgen_gapped_totals gt;
+    Counted counted;
+    const Budget B{"insertions", padded(cells, 4) + padded(1, sizeof(InsCounters)), S.table_held()};
+    if (int rc = count_row(h, P, S.count, B, A, row, timer, counts, &gt, &counted)) return rc;
+    if (!counted.have_row) {                                             // (a session without groups: nothing was launched)
+        if (anchors) memset(anchors, 0, cells * sizeof(int32_t));
+        if (totals) *totals = mipgen_insertion_totals{};
+        S.n_alleles = 0;
+        return booked(timer, &h->insertions_ms);
+    }
+    const int64_t events = gt.insertions;
+    if (events < 0 || events > 0x7fffffff) return fail(MIPGEN_E_INVALID, "insertions: %lld events in row %d: 2^31 - 1 at most", (long long)events, row);
+    // the events' bytes, known only now: checked before they are allocated
+    const size_t ne = (size_t)events;
+    size_t temp_bytes = 0;
+    if (events > 0) {
+        size_t t_sort = 0, t_runs = 0;
+        HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, nullptr, nullptr, nullptr, nullptr, events, 64));
+        HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, nullptr, events, nullptr, nullptr, nullptr));
+        temp_bytes = std::max<size_t>(std::max(t_sort, t_runs), 1);
+        const size_t need = 2 * padded(ne, 8) + 2 * padded(ne, 4) + padded(temp_bytes, 1) + padded(ne, sizeof(mipgen_insertion_record));
+        size_t room = 0;
+        if (int rc = room_beside(S.event_held(), &room)) return rc;
+        if (need > room)
+            return fail(MIPGEN_E_NOMEM, "insertions: %lld events need %zu MiB of device memory, %zu MiB are free", (long long)events, need >> 20, room >> 20);
+        if (S.keys.reserve(ne) || S.keys_sorted.reserve(ne) || S.ids.reserve(ne) || S.ids_sorted.reserve(ne) || S.temp.reserve(temp_bytes) || S.records.reserve(ne))
+            return MIPGEN_E_NOMEM;
+        temp_bytes = S.temp.cap;
+    }
+    if (S.anchors.reserve(cells) || S.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{st};
+    InsCounters ic;
+    HIP_TRY(hipMemsetAsync(S.ctr.p, 0, sizeof ic, st));
+    if (events > 0) HIP_TRY(hipMemsetAsync(S.ids.p, 0, ne * 4, st));
+    const CountScratch& W = S.count;
+    timer.mark();
+    HIP_TRY(mipgen_launch_insertions(st, P.R->view(), counted.row, P.n_units, counted.g_first, W.proj_off.p, W.proj.p, S.anchors.p, S.keys.p, events, S.ctr.p));
+    timer.mark();
+    HIP_TRY(hipMemcpyAsync(&ic, S.ctr.p, sizeof ic, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((int64_t)ic.events != events || (int64_t)ic.insertions != events || (int64_t)ic.ins_discordant != gt.ins_discordant)
+        return fail(MIPGEN_E_STATE, "insertions: %llu events emitted and %llu counted of %lld, %llu discordant of %lld", ic.events, ic.insertions, (long long)events,
+                    ic.ins_discordant, (long long)gt.ins_discordant);
+    if (events > 0) {
+        timer.mark();
+        HIP_TRY(mipgen_consensus_sort(st, S.temp.p, &temp_bytes, S.keys.p, S.keys_sorted.p, S.ids.p, S.ids_sorted.p, events, 64));
+        HIP_TRY(mipgen_consensus_runs(st, S.temp.p, &temp_bytes, S.keys_sorted.p, events, S.keys.p, reinterpret_cast<int32_t*>(S.ids.p), &S.ctr.p->alleles));
+        HIP_TRY(mipgen_launch_insertion_records(st, S.keys.p, reinterpret_cast<const int32_t*>(S.ids.p), &S.ctr.p->alleles, events, S.records.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&ic, S.ctr.p, sizeof ic, hipMemcpyDeviceToHost, st));
+    }
+    if (anchors) HIP_TRY(hipMemcpyAsync(anchors, S.anchors.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    if ((int64_t)ic.alleles > events || (events > 0 && ic.alleles == 0)) return fail(MIPGEN_E_STATE, "insertions: %llu alleles of %lld events", ic.alleles, (long long)events);
+    S.n_alleles = (int64_t)ic.alleles;
+    if (totals) *totals = {gt.groups, gt.used, (int64_t)ic.span, events, (int64_t)ic.ins_discordant, (int64_t)ic.ambiguous, S.n_alleles, gt.gapped_sides};
+    return booked(timer, &h->insertions_ms);
+}
+
+// The records of the last insertions call, in ascending key order.
+int mipgen_accel_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* records, int64_t n)
+{
+    if (int rc = check_reads(h)) return rc;
+    const InsScratch& S = h->consensus->ins;
+    if (S.n_alleles < 0) return fail(MIPGEN_E_STATE, "the consensus reads hold no insertion alleles: mipgen_accel_reads_consensus_insertions leaves them");
+    if (n != S.n_alleles) return fail(MIPGEN_E_INVALID, "%lld records asked: the last insertions call left %lld", (long long)n, (long long)S.n_alleles);
+    if (n == 0) return MIPGEN_OK;
+    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(records, S.records.p, (size_t)n * sizeof(mipgen_insertion_record), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MIPGEN_OK;
 }
 
 // Calls from host arrays: no read session is needed; the arrays are uploaded into the handle's CallRun.

@@ -8,6 +8,7 @@
 // Because the gap is linear, that in-row dependency is a prefix maximum: with V[d] the best of the two candidates from the row before,
 // H[d] = max over k <= d of (V[k] - 2 (d - k)) = (prefix max of V[k] + 2 k) - 2 d.  Serially that is run = max(run - 2, V[d]) (gap_scan_step).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -95,7 +96,12 @@ GAP_HD int gap_dir_at(const uint32_t* dirs, int i, int j, int W)
 // GAP_NOT_COVERED if not.  Insertion steps at column 0 and after column je are dropped.  The caller writes the positions the path does not consume (0, 0,
 // GAP_NOT_COVERED).  Returns the gap steps of the path, dropped insertion steps included; path (may be null) receives the steps from the end cell backwards as
 // 'M', 'D', 'I' and a closing 0 - at most ie + je + 1 bytes.
-GAP_HD int gap_traceback(const uint32_t* dirs, int W, int L, int side, int ie, int je, const uint8_t* q, const uint8_t* qq, uint8_t* base, uint8_t* qual, uint8_t* ins, char* path)
+// RUNS: beside every insertion byte it writes, the walk also leaves the read index of the run - the i it holds when it consumes the column in front
+// of the run, so that the run is q[i .. i + length - 1] - as two byte planes run_lo / run_hi (i <= GAP_MAX_MOL + GAP_MAX_INDEL < 2^16).  The insertion steps dropped
+// at column 0 have moved i like any other.
+template <bool RUNS>
+GAP_HD int gap_traceback_core(const uint32_t* dirs, int W, int L, int side, int ie, int je, const uint8_t* q, const uint8_t* qq, uint8_t* base, uint8_t* qual, uint8_t* ins,
+                              uint8_t* run_lo, uint8_t* run_hi, char* path)
 {
     int i = ie, j = je, run = 0, gaps = 0, n = 0;
     while (i > 0 || j > 0) {
@@ -107,6 +113,7 @@ GAP_HD int gap_traceback(const uint32_t* dirs, int W, int L, int side, int ie, i
             continue;
         }
         const int t = side == GAP_LIG ? L - j : j - 1;
+        const int at = i;                                                       // q[0, at) is consumed through column j: the run behind it starts at q[at]
         if (dir == GAP_DIAG) {
             base[t] = (uint8_t)(side == GAP_LIG ? gap_complement(q[i - 1]) : q[i - 1]);
             qual[t] = qq[i - 1];
@@ -116,16 +123,60 @@ GAP_HD int gap_traceback(const uint32_t* dirs, int W, int L, int side, int ie, i
         }
         // `run` insertion steps lie between column j and column j + 1
         if (side == GAP_LIG) {
-            if (j < je) ins[t - 1] = (uint8_t)run;                              // the anchor is the lower position: that of column j + 1
+            if (j < je) {                                                       // the anchor is the lower position: that of column j + 1
+                ins[t - 1] = (uint8_t)run;
+                if (RUNS) { run_lo[t - 1] = (uint8_t)at; run_hi[t - 1] = (uint8_t)(at >> 8); }
+            }
             if (j == 1) ins[t] = GAP_NOT_COVERED;                               // t = L - 1 anchors nothing
-        } else
+        } else {
             ins[t] = j < je ? (uint8_t)run : (uint8_t)GAP_NOT_COVERED;
+            if (RUNS && j < je) { run_lo[t] = (uint8_t)at; run_hi[t] = (uint8_t)(at >> 8); }
+        }
         if (path) path[n++] = dir == GAP_DIAG ? 'M' : 'D';
         run = 0; j--;
     }
     if (path) path[n] = 0;
     return gaps;
 }
+
+GAP_HD int gap_traceback(const uint32_t* dirs, int W, int L, int side, int ie, int je, const uint8_t* q, const uint8_t* qq, uint8_t* base, uint8_t* qual, uint8_t* ins, char* path)
+{
+    return gap_traceback_core<false>(dirs, W, L, side, ie, je, q, qq, base, qual, ins, nullptr, nullptr, path);
+}
+
+GAP_HD int gap_traceback_runs(const uint32_t* dirs, int W, int L, int side, int ie, int je, const uint8_t* q, const uint8_t* qq, uint8_t* base, uint8_t* qual, uint8_t* ins,
+                              uint8_t* run_lo, uint8_t* run_hi, char* path)
+{
+    return gap_traceback_core<true>(dirs, W, L, side, ie, je, q, qq, base, qual, ins, run_lo, run_hi, path);
+}
+
+// ---- insertion alleles ----------------------------------------------------------------------------------------------------------------------
+#define GAP_ALLELE_MAX_LEN 15        // the bases an allele spells out: 2 bits each in the 30 low bits of its key
+
+// Base j (orientation of M) of a side's run of l read bases starting at q[at]: its index in the read.  Extension: at + j; ligation: at + l - 1 - j (the byte is then
+// complemented).
+GAP_HD int gap_run_index(int side, int at, int l, int j) { return side == GAP_LIG ? at + l - 1 - j : at + j; }
+
+// One base of an event from the one or two contributing sides: 0..3, or 4 = ambiguous.  be / bl: each side's byte in M's orientation (the ligation byte complemented
+// already), ue / ul: the side contributes and its byte is usable (one of A C G T, quality - 33 >= min_quality).
+GAP_HD int gap_allele_base(int be, bool ue, int bl, bool ul)
+{
+    if (ue && ul) return be == bl ? gap_base_code(be) : 4;
+    return ue ? gap_base_code(be) : ul ? gap_base_code(bl) : 4;
+}
+
+// The 64-bit key of an allele: x << 35 | l << 31 | ambiguous << 30 | bases, x < 2^29, bases 2 bits per base with base 0 in the most significant of the 2 l used
+// bits.  A run of more than GAP_ALLELE_MAX_LEN bases (up to 2 W: deletions in front of it make the room inside the band) spells nothing out: it is ambiguous,
+// its length field is 0 - no other event has that - and its length stands in the low bits.
+GAP_HD uint64_t gap_allele_key(int64_t x, int l, bool ambiguous, uint32_t bases)
+{
+    if (l > GAP_ALLELE_MAX_LEN) return ((uint64_t)x << 35) | ((uint64_t)1 << 30) | (uint64_t)(uint32_t)l;
+    return ((uint64_t)x << 35) | ((uint64_t)(uint32_t)l << 31) | ((uint64_t)(ambiguous ? 1u : 0u) << 30) | (uint64_t)(ambiguous ? 0u : bases);
+}
+GAP_HD int64_t gap_allele_pos(uint64_t key) { return (int64_t)(key >> 35); }
+GAP_HD bool gap_allele_ambiguous(uint64_t key) { return ((key >> 30) & 1u) != 0; }
+GAP_HD int gap_allele_length(uint64_t key) { const int l = (int)((key >> 31) & 15u); return l ? l : (int)(key & 0x3fffffffu); }
+GAP_HD uint32_t gap_allele_bases(uint64_t key) { return ((key >> 31) & 15u) ? (uint32_t)(key & 0x3fffffffu) : 0u; }
 
 // ---- the serial row: what k_gap_align's lanes do for row i >= 1, one lane after the other (host only) ----------------------------------------------------
 // h_prev / h: the GAP_LANES values of row i - 1 / i (GAP_NEG outside the band); q_byte = q[i - 1]; two words of directions go to dirs2.

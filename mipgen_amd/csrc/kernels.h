@@ -175,10 +175,16 @@ hipError_t mipgen_launch_pileup_prepare(hipStream_t, const ConsensusView& C, con
 hipError_t mipgen_launch_pileup(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, int32_t* counts, PileupCounters* ctr);
 // kernels_gapped.hip: the sides of one row that need the banded alignment; then the alignment, the counts with indels and their sums
 size_t mipgen_gap_align_lds_bytes(int max_len, int W);
+// (planes: 3 bytes per projected position, or 5 - the projection that also holds the run indices of DESIGN 4.16)
 hipError_t mipgen_launch_gap_list(hipStream_t, const ConsensusView& C, const PileRow& R, const uint8_t* mol_seq, uint32_t g_first, int64_t n_row_groups, int max_indel,
-                                  uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr);
+                                  int planes, uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr);
 hipError_t mipgen_launch_gapped(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, const uint8_t* mol_seq, uint32_t g_first, int max_indel, int max_len,
-                                const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int32_t* counts, GappedCounters* ctr);
+                                int planes, const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int32_t* counts, GappedCounters* ctr);
+// insertion alleles: the anchor table and the events of a row from its five-plane projections; the runs of the sorted keys as records
+hipError_t mipgen_launch_insertions(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, uint32_t g_first, const int64_t* proj_off, const uint8_t* proj,
+                                    int32_t* anchors, uint64_t* keys, int64_t cap, InsCounters* ctr);
+hipError_t mipgen_launch_insertion_records(hipStream_t, const uint64_t* run_keys, const int32_t* run_counts, const unsigned long long* n_runs, int64_t cap,
+                                           mipgen_insertion_record* records);
 // kernels_call.hip: one row's table added into the pool (K[5], N[5] per position); the candidates of a table against the pool (cand: 4 n_pos records, ctr
 // zero on entry); their scores, sort keys and ctr->calls; the calls in key order
 hipError_t mipgen_launch_call_pool(hipStream_t, const int32_t* counts, int columns, int64_t n_pos, int32_t bg_max_ppm, int32_t* pool);

@@ -20,6 +20,15 @@
 //                 k_pile_wg<GapPile, GapProj>, k_gapped_sum = k_pile_sum<GapPile>.  Eight counters; a side with a projection is read from it (base, quality and
 //                 insertion byte at t), any other from its consensus read.  32 bytes per position, two 16-byte stores.  Column sums: bases (columns 0..3),
 //                 discordant, deletions, insertions, ins_discordant (columns 4..7).
+//
+// Insertion alleles.  k_gap_list<5> and k_gap_align<true> are the same kernels with the WIDER projection: two more byte planes hold, per anchor, the
+// read index of the insertion run (gap_traceback_runs).  The 3-plane instances are the code of 4.13 as it was.
+//  InsPile        a second policy of the count frame, k_ins_wave / k_ins_wg: four counters per anchor (span, ins, ins_discordant, ambiguous; one 16-byte store) from
+//                 the insertion bytes alone, and THE EVENTS as a side effect: a ballot of the lanes whose molecule carries an agreed insertion at their anchor;
+//                 only where it is non-zero, one atomic per wavefront reserves the slots, every such lane reads its <= 15 bases and qualities from the one or two
+//                 consensus reads through the run indices, votes per base, packs the key (gap_allele_key) and writes it with one 8-byte store.  The group loop is
+//                 wave-uniform, so the ballot sees the whole wavefront.  The slots are exact beforehand: the `insertions` total of the GapPile count.
+//  k_ins_records  a lane per run of the sorted keys (mipgen_consensus_sort, mipgen_consensus_runs): key and count decoded into a 24-byte record.
 #include "pileup_frame.h"
 #include "gapped_align.h"
 
@@ -61,6 +70,8 @@ __global__ __launch_bounds__(256) void k_gap_screen(GapIn I, int64_t n_row_group
     }
 }
 
+// PLANES: the byte planes of a projection - 3 (base, quality, insertion length: DESIGN 4.13) or 5 (and the two bytes of the run index: 4.16)
+template <int PLANES>
 __global__ __launch_bounds__(256) void k_gap_list(GapIn I, int64_t n_row_sides, const uint8_t* __restrict__ need, uint32_t* __restrict__ list, int64_t* __restrict__ proj_off,
                                                   GappedCounters* __restrict__ ctr)
 {
@@ -70,9 +81,9 @@ __global__ __launch_bounds__(256) void k_gap_list(GapIn I, int64_t n_row_sides, 
     uint32_t bytes = 0;
     if (listed) {
         const uint32_t g = I.g_first + (uint32_t)(s >> 1);
-        bytes = 3u * (uint32_t)I.R.mol_len[(uint32_t)(I.C.keys[g] >> 32) - I.R.cell0];
+        bytes = (uint32_t)PLANES * (uint32_t)I.R.mol_len[(uint32_t)(I.C.keys[g] >> 32) - I.R.cell0];
     }
-    const uint32_t in = wave_inclusive_sum_u32(listed ? 1u : 0u, lane), ib = wave_inclusive_sum_u32(bytes, lane);       // (at most 64 x 3 x GAP_MAX_MOL bytes per wavefront)
+    const uint32_t in = wave_inclusive_sum_u32(listed ? 1u : 0u, lane), ib = wave_inclusive_sum_u32(bytes, lane);       // (at most 64 x 5 x GAP_MAX_MOL bytes per wavefront)
     const uint32_t tn = __shfl(in, 63), tb = __shfl(ib, 63);
     unsigned long long bn = 0, bb = 0;
     if (lane == 0 && tn) { bn = atomicAdd(&ctr->n_sides, (unsigned long long)tn); bb = atomicAdd(&ctr->proj_bytes, (unsigned long long)tb); }
@@ -85,6 +96,8 @@ __global__ __launch_bounds__(256) void k_gap_list(GapIn I, int64_t n_row_sides, 
 // Dynamic LDS: [2 halves][rows_cap][2] words of directions; rows_cap = (the longest template of the call) + W >= min(m, L + W), the rows of any side.
 extern __shared__ uint32_t gap_dirs[];
 
+// RUNS: the side's projection has five planes and the walk back leaves the run indices in the last two
+template <bool RUNS>
 __global__ __launch_bounds__(64) void k_gap_align(const uint32_t* __restrict__ list, int64_t n_sides, const int64_t* __restrict__ proj_off, uint8_t* __restrict__ proj, GapIn I,
                                                   int rows_cap, GappedCounters* __restrict__ ctr)
 {
@@ -152,7 +165,12 @@ __global__ __launch_bounds__(64) void k_gap_align(const uint32_t* __restrict__ l
     const int64_t po = live ? proj_off[s] : 0;
     uint8_t* base = proj + po;
     int gaps = 0;
-    if (live && d == 0 && best != 0) gaps = gap_traceback(dirs, W, L, side, gap_end_i(best), je, q, qq, base, base + L, base + 2 * (size_t)L, nullptr);
+    if constexpr (RUNS) {
+        if (live && d == 0 && best != 0)
+            gaps = gap_traceback_runs(dirs, W, L, side, gap_end_i(best), je, q, qq, base, base + L, base + 2 * (size_t)L, base + 3 * (size_t)L, base + 4 * (size_t)L, nullptr);
+    } else {
+        if (live && d == 0 && best != 0) gaps = gap_traceback(dirs, W, L, side, gap_end_i(best), je, q, qq, base, base + L, base + 2 * (size_t)L, nullptr);
+    }
     // the positions the path does not consume: columns je + 1 .. L
     if (live) {
         const int t0 = side ? 0 : je, t1 = side ? L - je : L;                               // [t0, t1)
@@ -232,6 +250,102 @@ struct GapPile {
     }
 };
 
+// ---- insertion alleles ------------------------------------------------------------------------------------------------------------------------
+// where the events go: keys[0, cap), the slots reserved through ctr->events
+struct InsEmit { uint64_t* __restrict__ keys; unsigned long long cap; InsCounters* __restrict__ ctr; };
+
+// one side at the anchor (t, t + 1): does it cover it, with which insertion length, and (a side with a run) where the run starts in its read.  A side without a
+// projection has the ungapped path: gap_observe's cover rule, length 0.
+__device__ static inline void ins_side(const uint8_t* __restrict__ proj, int64_t po, int n, int idx, int t, int L, bool lig, bool& covers, uint32_t& len, int& at)
+{
+    at = 0;
+    if (po >= 0) {
+        const uint8_t* __restrict__ P = proj + po;
+        const int tt = min(t, L - 1);
+        const uint32_t il = P[2 * (size_t)L + tt];
+        covers = il != GAP_NOT_COVERED; len = il;
+        if (covers && il > 0u) at = (int)P[3 * (size_t)L + tt] | ((int)P[4 * (size_t)L + tt] << 8);
+    } else {
+        const bool present = idx >= 0 && idx < n;
+        covers = present && (lig ? idx >= 1 : (t + 1 < n && t + 1 < L));
+        len = 0u;
+    }
+}
+
+struct InsPile {
+    static constexpr int COLUMNS = INSERTION_COLUMNS;
+    using Counters = InsCounters;
+    static constexpr ColumnSum<InsCounters> SUMS[4] = {{0, 1, &InsCounters::span}, {1, 2, &InsCounters::insertions}, {2, 3, &InsCounters::ins_discordant},
+                                                       {3, 4, &InsCounters::ambiguous}};
+    int n[COLUMNS] = {0, 0, 0, 0};                                                          // span, ins, ins_discordant, ambiguous
+    __device__ static inline void groups(InsPile& S, const ConsensusView& I, const PileRow& R, uint32_t g0, uint32_t g1, uint32_t stride, int t, int L, const GapProj& P,
+                                         const InsEmit& E)
+    {
+        const int lane = threadIdx.x & 63;
+        for (uint32_t g = g0; g < g1; g += stride) {                                        // (wave-uniform: every lane of the wavefront is here)
+            const int64_t eo = I.ext_off[g], lo = I.lig_off[g];
+            const int el = (int)(I.ext_off[g + 1] - eo), ll = (int)(I.lig_off[g + 1] - lo);
+            const int64_t pe = P.off[2 * (size_t)(g - P.g_first)], pl = P.off[2 * (size_t)(g - P.g_first) + 1];
+            const bool ok = I.family[g] >= R.min_family;
+            bool ve, vl;
+            uint32_t ne, nl;
+            int ae, al;
+            ins_side(P.bytes, pe, el, t, t, L, false, ve, ne, ae);
+            ins_side(P.bytes, pl, ll, L - 1 - t, t, L, true, vl, nl, al);
+            const bool xe = ok && ve, xl = ok && vl;
+            const bool disc = xe && xl && ne != nl, spans = (xe || xl) && !disc;
+            const int l = (int)(xe ? ne : nl);                                              // the agreed length of a molecule that spans
+            const bool event = spans && l > 0 && t < L - 1;                                 // (a lane clamped beyond the template emits nothing)
+            S.n[0] += spans; S.n[1] += spans && l > 0; S.n[2] += disc;
+            const unsigned long long events = __ballot(event);
+            if (events == 0ull) continue;                                                   // (the wavefront's)
+            uint32_t bases = 0u;
+            bool amb = l > GAP_ALLELE_MAX_LEN;
+            if (event && !amb) {
+                for (int j = 0; j < l; j++) {
+                    int be = 0, bl = 0;
+                    bool ue = false, ul = false;
+                    if (xe) {                                                               // (el >= 1: the side has a projection)
+                        const int64_t at = eo + max(min(gap_run_index(GAP_EXT, ae, l, j), el - 1), 0);
+                        be = I.ext_seq[at];
+                        ue = gap_base_code(be) < 4 && (int)I.ext_qual[at] - 33 >= R.min_quality;
+                    }
+                    if (xl) {
+                        const int64_t at = lo + max(min(gap_run_index(GAP_LIG, al, l, j), ll - 1), 0);
+                        bl = gap_complement(I.lig_seq[at]);
+                        ul = gap_base_code(bl) < 4 && (int)I.lig_qual[at] - 33 >= R.min_quality;
+                    }
+                    const int c = gap_allele_base(be, ue, bl, ul);
+                    amb = amb || c > 3;
+                    bases = (bases << 2) | (uint32_t)(c & 3);
+                }
+            }
+            S.n[3] += event && amb;
+            unsigned long long first = 0;
+            if (lane == 0) first = atomicAdd(&E.ctr->events, (unsigned long long)__popcll(events));
+            first = __shfl(first, 0);
+            if (event) {
+                const unsigned long long slot = first + (unsigned long long)__popcll(events & ((1ull << lane) - 1ull));
+                const uint32_t p = (uint32_t)(I.keys[g] >> 32) - R.cell0;
+                if (slot < E.cap) E.keys[slot] = gap_allele_key(R.pos_off[p] + t, l, amb, bases);
+            }
+        }
+    }
+    __device__ inline void store(int32_t* __restrict__ o) const { *reinterpret_cast<int4*>(o) = make_int4(n[0], n[1], n[2], n[3]); }      // (16 bytes per anchor, the table 256-byte aligned)
+};
+
+// a lane per run of the sorted keys
+__global__ __launch_bounds__(256) void k_ins_records(const uint64_t* __restrict__ run_keys, const int32_t* __restrict__ run_counts, const unsigned long long* __restrict__ n_runs,
+                                                     int64_t cap, mipgen_insertion_record* __restrict__ records)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap || (unsigned long long)i >= *n_runs) return;
+    const uint64_t key = run_keys[i];
+    mipgen_insertion_record r;
+    r.pos = gap_allele_pos(key); r.length = gap_allele_length(key); r.count = run_counts[i]; r.bases = gap_allele_bases(key); r.ambiguous = gap_allele_ambiguous(key) ? 1 : 0;
+    records[i] = r;
+}
+
 extern "C" {
 
 size_t mipgen_gap_align_lds_bytes(int max_len, int W) { return (size_t)2 * (size_t)(max_len + W) * 2 * sizeof(uint32_t); }
@@ -239,27 +353,50 @@ size_t mipgen_gap_align_lds_bytes(int max_len, int W) { return (size_t)2 * (size
 // the sides of the row's groups [g_first, g_first + n_row_groups) that need the dynamic program: list[0, ctr->n_sides), proj_off[2 n_row_groups] (-1: no
 // projection), ctr->proj_bytes; ctr is zero on entry
 hipError_t mipgen_launch_gap_list(hipStream_t st, const ConsensusView& C, const PileRow& R, const uint8_t* mol_seq, uint32_t g_first, int64_t n_row_groups, int max_indel,
-                                  uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr)
+                                  int planes, uint8_t* need, uint32_t* list, int64_t* proj_off, GappedCounters* ctr)
 {
-    if (n_row_groups < 1 || n_row_groups > 0x3fffffff || max_indel < 1 || max_indel > GAP_MAX_INDEL) return hipErrorInvalidValue;
+    if (n_row_groups < 1 || n_row_groups > 0x3fffffff || max_indel < 1 || max_indel > GAP_MAX_INDEL || (planes != 3 && planes != 5)) return hipErrorInvalidValue;
     const GapIn I{C, R, mol_seq, g_first, max_indel};
     hipLaunchKernelGGL(k_gap_screen, dim3((unsigned)((n_row_groups + 3) / 4)), dim3(256), 0, st, I, n_row_groups, need);
-    hipLaunchKernelGGL(k_gap_list, dim3((unsigned)((2 * n_row_groups + 255) / 256)), dim3(256), 0, st, I, 2 * n_row_groups, need, list, proj_off, ctr);
+    const dim3 grid((unsigned)((2 * n_row_groups + 255) / 256));
+    if (planes == 5) hipLaunchKernelGGL(k_gap_list<5>, grid, dim3(256), 0, st, I, 2 * n_row_groups, need, list, proj_off, ctr);
+    else hipLaunchKernelGGL(k_gap_list<3>, grid, dim3(256), 0, st, I, 2 * n_row_groups, need, list, proj_off, ctr);
     return hipGetLastError();
 }
 
-// the alignment of the n_sides listed sides into proj, then counts[R.n_pos][8] written whole and summed into ctr
+// the alignment of the n_sides listed sides into proj (planes: as the list was made), then counts[R.n_pos][8] written whole and summed into ctr
 hipError_t mipgen_launch_gapped(hipStream_t st, const ConsensusView& C, const PileRow& R, int64_t n_units, const uint8_t* mol_seq, uint32_t g_first, int max_indel, int max_len,
+                                int planes,
                                 const uint32_t* list, int64_t n_sides, const int64_t* proj_off, uint8_t* proj, int32_t* counts, GappedCounters* ctr)
 {
     if (R.n_small < 0 || R.n_big < 0 || R.n_small + R.n_big != n_units || n_units > 0x7fffffff || R.n_pos < 1 || n_sides < 0 || n_sides > 0x7fffffff || max_indel < 1 ||
-        max_indel > GAP_MAX_INDEL || max_len < 1 || max_len > GAP_MAX_MOL)
+        max_indel > GAP_MAX_INDEL || max_len < 1 || max_len > GAP_MAX_MOL || (planes != 3 && planes != 5))
         return hipErrorInvalidValue;
     const GapIn I{C, R, mol_seq, g_first, max_indel};
-    if (n_sides > 0)
-        hipLaunchKernelGGL(k_gap_align, dim3((unsigned)((n_sides + 1) / 2)), dim3(64), mipgen_gap_align_lds_bytes(max_len, max_indel), st, list, n_sides, proj_off, proj, I,
-                           max_len + max_indel, ctr);
+    const dim3 grid((unsigned)((n_sides + 1) / 2));
+    const size_t lds = mipgen_gap_align_lds_bytes(max_len, max_indel);
+    if (n_sides > 0 && planes == 5) hipLaunchKernelGGL(k_gap_align<true>, grid, dim3(64), lds, st, list, n_sides, proj_off, proj, I, max_len + max_indel, ctr);
+    else if (n_sides > 0) hipLaunchKernelGGL(k_gap_align<false>, grid, dim3(64), lds, st, list, n_sides, proj_off, proj, I, max_len + max_indel, ctr);
     return pile_launch<GapPile>(st, C, R, counts, ctr, GapProj{g_first, proj_off, proj});
+}
+
+// anchors[R.n_pos][4] written whole and summed into ctr, the events of the row into keys[0, cap) in no defined order, ctr->events their number (ctr zero on entry);
+// proj_off / proj: the five-plane projections of the row
+hipError_t mipgen_launch_insertions(hipStream_t st, const ConsensusView& C, const PileRow& R, int64_t n_units, uint32_t g_first, const int64_t* proj_off, const uint8_t* proj,
+                                    int32_t* anchors, uint64_t* keys, int64_t cap, InsCounters* ctr)
+{
+    if (R.n_small < 0 || R.n_big < 0 || R.n_small + R.n_big != n_units || n_units > 0x7fffffff || R.n_pos < 1 || R.n_pos > MIPGEN_CALL_MAX_POSITIONS || cap < 0 || cap > 0x7fffffff)
+        return hipErrorInvalidValue;
+    return pile_launch<InsPile>(st, C, R, anchors, ctr, GapProj{g_first, proj_off, proj}, InsEmit{keys, (unsigned long long)cap, ctr});
+}
+
+// the first min(*n_runs, cap) runs decoded into records
+hipError_t mipgen_launch_insertion_records(hipStream_t st, const uint64_t* run_keys, const int32_t* run_counts, const unsigned long long* n_runs, int64_t cap,
+                                           mipgen_insertion_record* records)
+{
+    if (cap < 1 || cap > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ins_records, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, run_keys, run_counts, n_runs, cap, records);
+    return hipGetLastError();
 }
 
 }

@@ -119,3 +119,6 @@ struct PileupCounters { unsigned long long n_small, n_big, used, bases, discorda
 // n_sides / proj_bytes: the (group, side) pairs listed for k_gap_align and the bytes of their projections; gapped_sides: those whose path holds a gap step; the others:
 // the sums of columns 0..3, 4, 5, 6 and 7
 struct GappedCounters { unsigned long long n_sides, proj_bytes, gapped_sides, bases, discordant, deletions, insertions, ins_discordant; };
+// insertion alleles: the columns of the anchor table; what InsPile sums and emits, and the runs of the sorted keys
+#define INSERTION_COLUMNS 4          // span, ins, ins_discordant, ambiguous
+struct InsCounters { unsigned long long span, insertions, ins_discordant, ambiguous, events, alleles; };

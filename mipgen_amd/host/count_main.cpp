@@ -43,6 +43,14 @@
 //                           header and every line gain the columns del, ins and ins_discordant (molecules that show a deletion of the base; an insertion between
 //                           this base and the next one in genome plus orientation; two different insertion lengths there), a line is written when any of its eight
 //                           numbers is non-zero, and a second stderr line follows: "mipgen_count: pileup indels deletions X insertions Y ins_discordant Z gapped_sides S"
+//   -pileup_insertions INS  needs -pileup_indels: the inserted bases themselves.  One insertions call per row (undetermined too) feeds BOTH files - FILE is
+//                           byte for byte what it is without the option; beside -call or -pileup_loci those routes run unchanged and the insertions call of a row feeds
+//                           INS only.  Header ">sample <tab> mip_key <tab> chr <tab> position <tab> strand <tab> length <tab> inserted <tab> count <tab> span <tab> ppm";
+//                           one line per allele in row order, then table order, then the order of the records.  position is the lower genome coordinate of the two
+//                           bases the insertion lies between, on both strands; inserted is in genome plus orientation (reverse-complemented on a '-' probe) and
+//                           `length` times N for the molecules whose inserted bases could not be told; span = the molecules that cover the anchor with one agreed
+//                           length, 0 included; ppm = floor(count 10^6 / span)
+//   stderr     a last line: "mipgen_count: insertion alleles A events I ambiguous B span S"
 // Variant calls from the pileup against a background of the other samples (without -call every byte written is what it was):
 //   -call CALLS             needs -pileup and uses -pileup_min_family, -pileup_min_quality and -pileup_indels as given: one pool over the sample rows, then one call per
 //                           row (undetermined too) that feeds BOTH files - FILE is byte for byte what it is without -call.  Header
@@ -96,6 +104,7 @@ static int usage(const std::string& msg)
             "-consensus prefix : prefix.ext.fq and prefix.lig.fq, one consensus read pair per (sample, probe, tag) group; -min_family k : groups of at least k pairs (default 1)\n"
             "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n"
             "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n"
+            "-pileup_insertions file : with -pileup_indels, the inserted bases per anchor: length, bases, molecules, spanning molecules and ppm per allele\n"
             "-call file : with -pileup, variant calls of every sample against the background of the others; -call_min_depth n (default 20), -call_min_alt k (3), -call_min_ppm p (0),\n"
             "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n"
             "-pileup_loci file : with -pileup, the counts per genome base, summed over the probes that cover it; -loci_parts target|all : what of a probe counts (default target)\n"
@@ -201,7 +210,7 @@ int main(int argc, char** argv)
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
     long min_family = 1, pile_family = 1, pile_quality = 0, pile_indels = 0;
     bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
-    std::string consensus_prefix, pileup_path, call_path;
+    std::string consensus_prefix, pileup_path, call_path, ins_path;
     mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
     bool call_option_given = false, loci_parts_given = false, loci_all = false;
     std::string loci_path, call_loci_path;
@@ -239,6 +248,7 @@ int main(int argc, char** argv)
         else if (a == "-pileup_min_family") { if (!svr_parse_int(v.c_str(), &pile_family) || pile_family < 1 || pile_family > INT32_MAX) return usage("-pileup_min_family must be 1 or more"); pile_option_given = true; }
         else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
         else if (a == "-pileup_indels") { if (!svr_parse_int(v.c_str(), &pile_indels) || pile_indels < 1 || pile_indels > 15) return usage("-pileup_indels must be 1 to 15"); }
+        else if (a == "-pileup_insertions") { if (v.empty()) return usage("-pileup_insertions takes a file"); ins_path = v; }
         else if (a == "-call") { if (v.empty()) return usage("-call takes a file"); call_path = v; }
         else if (a == "-pileup_loci") { if (v.empty()) return usage("-pileup_loci takes a file"); loci_path = v; }
         else if (a == "-call_loci") { if (v.empty()) return usage("-call_loci takes a file"); call_loci_path = v; }
@@ -274,6 +284,8 @@ int main(int argc, char** argv)
     const bool pileup = !pileup_path.empty(), keep_reads = consensus || pileup;      // (-pileup reads the consensus reads: its session keeps the reads too)
     if (pile_option_given && !pileup) return usage("-pileup_min_family and -pileup_min_quality need -pileup file");
     if (pile_indels && !pileup) return usage("-pileup_indels needs -pileup file");
+    const bool insertions = !ins_path.empty();
+    if (insertions && !pile_indels) return usage("-pileup_insertions needs -pileup file -pileup_indels W");
     const bool call = !call_path.empty();
     if (call && !pileup) return usage("-call needs -pileup file");
     const bool loci = !loci_path.empty(), call_loci = !call_loci_path.empty();
@@ -397,6 +409,8 @@ int main(int argc, char** argv)
             if (!(cons_out[k] = fopen(cons_path[k].c_str(), "w"))) return usage("-consensus " + consensus_prefix + ": can't write " + cons_path[k]);
     FILE* pile_out = nullptr;
     if (pileup && !(pile_out = fopen(pileup_path.c_str(), "w"))) return usage("-pileup " + pileup_path + ": can't write " + pileup_path);
+    FILE* ins_out = nullptr;
+    if (insertions && !(ins_out = fopen(ins_path.c_str(), "w"))) return usage("-pileup_insertions " + ins_path + ": can't write " + ins_path);
     FILE* call_out = nullptr;
     if (call && !(call_out = fopen(call_path.c_str(), "w"))) return usage("-call " + call_path + ": can't write " + call_path);
     FILE *loci_out = nullptr, *call_loci_out = nullptr;
@@ -495,6 +509,7 @@ int main(int argc, char** argv)
     long long pile_used = 0, pile_lines = 0, pile_bases = 0, pile_nonref = 0, pile_disc = 0, pile_del = 0, pile_ins = 0, pile_insd = 0, pile_gapped = 0;
     long long call_calls = 0, call_cands = 0, call_tested = 0, call_deep = 0;
     long long loci_lines = 0, loci_bases = 0, loci_nonref = 0, loci_disc = 0, lcall_calls = 0, lcall_cands = 0, lcall_tested = 0, lcall_deep = 0;
+    long long ins_alleles = 0, ins_events = 0, ins_amb = 0, ins_span = 0;
     const size_t pile_cols = pile_indels ? 8 : 5;
     if (pileup) {
         int64_t n_pos = 0;
@@ -541,6 +556,32 @@ int main(int argc, char** argv)
                 }
             }
             fwrite(text.data(), 1, text.size(), pile_out);
+        };
+        // -pileup_insertions: the records of a row (ascending anchor, so table order) as lines; span comes from the anchor table of the row
+        std::vector<int32_t> ianch[2] = {std::vector<int32_t>(insertions ? (size_t)n_pos * 4 : 0), std::vector<int32_t>(insertions && n_rows > 1 ? (size_t)n_pos * 4 : 0)};
+        std::vector<mipgen_insertion_record> irecs[2];
+        auto write_insertions = [&](size_t r, const std::vector<int32_t>& anch, const std::vector<mipgen_insertion_record>& rec) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text, inserted;
+            char buf[120];
+            for (const mipgen_insertion_record& q : rec) {
+                const size_t i = (size_t)(std::upper_bound(pos_off.begin(), pos_off.end(), q.pos) - pos_off.begin()) - 1;
+                const std::vector<std::string>& f = *rows[i];
+                const RowCoords& c = coords[i];
+                const long t = (long)(q.pos - pos_off[i]);
+                inserted.assign((size_t)q.length, 'N');
+                if (!q.ambiguous)
+                    for (int j = 0; j < q.length; j++) {                                 // base j of the molecule; on a '-' probe the plus strand reads it from the far end, complemented
+                        const unsigned code = (q.bases >> (2 * (q.length - 1 - j))) & 3u;
+                        if (c.minus) inserted[(size_t)(q.length - 1 - j)] = "TGCA"[code]; else inserted[(size_t)j] = "ACGT"[code];
+                    }
+                const int32_t span = anch[(size_t)q.pos * 4];
+                snprintf(buf, sizeof buf, "\t%ld\t%c\t%d\t", c.minus ? c.ext_stop - (t + 1) : c.ext_start + t, c.minus ? '-' : '+', q.length);
+                text.append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf).append(inserted);
+                snprintf(buf, sizeof buf, "\t%d\t%d\t%lld\n", q.count, span, (long long)q.count * 1000000ll / span);
+                text.append(buf);
+            }
+            fwrite(text.data(), 1, text.size(), ins_out);
         };
         // -call: the records of a row (ascending position, then allele class) as lines; within a position the printed alts go A C G T -, which on a '-' probe is
         // the reverse of the class order of the four bases
@@ -623,6 +664,7 @@ int main(int argc, char** argv)
             if (mipgen_accel_reads_consensus_call_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
                                                        call_prm.bg_max_ppm) != MIPGEN_OK) return die();
         }
+        if (insertions) fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tinserted\tcount\tspan\tppm\n", ins_out);
         fputs(pile_indels ? ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n"
                           : ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
         std::thread writer;
@@ -658,19 +700,41 @@ int main(int argc, char** argv)
                 if (prc == MIPGEN_OK && call_loci) { lrecs[r & 1].resize((size_t)lct.calls); prc = mipgen_accel_call_fetch(h, lrecs[r & 1].data(), lct.calls); }
                 pt.used = gt.used;
                 lcall_calls += lct.calls; lcall_cands += lct.candidates; lcall_tested += lct.tested; lcall_deep += lct.too_deep;
+            } else if (insertions) {                                                     // one insertions call per row feeds FILE and INS: its counts are the gapped pileup's
+                mipgen_insertion_totals it;
+                prc = mipgen_accel_reads_consensus_insertions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
+                                                              (int32_t)pile_indels, table[r & 1].data(), ianch[r & 1].data(), &it);
+                if (prc == MIPGEN_OK) { irecs[r & 1].resize((size_t)it.alleles); prc = mipgen_accel_insertions_fetch(h, irecs[r & 1].data(), it.alleles); }
+                if (prc == MIPGEN_OK) {
+                    gt.used = it.used; gt.gapped_sides = it.gapped_sides;
+                    ins_alleles += it.alleles; ins_events += it.insertions; ins_amb += it.ambiguous; ins_span += it.span;
+                }
             } else
             prc = pile_indels ? mipgen_accel_reads_consensus_pileup_gapped(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
                                                                                      (int32_t)pile_quality, (int32_t)pile_indels, table[r & 1].data(), &gt)
                                         : mipgen_accel_reads_consensus_pileup(h, mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
                                                                               table[r & 1].data(), &pt);
+            if (insertions && (call || loci) && prc == MIPGEN_OK) {                      // beside -call or -pileup_loci: the insertions call of the row feeds INS only
+                mipgen_insertion_totals it;
+                prc = mipgen_accel_reads_consensus_insertions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
+                                                              (int32_t)pile_indels, nullptr, ianch[r & 1].data(), &it);
+                if (prc == MIPGEN_OK) { irecs[r & 1].resize((size_t)it.alleles); prc = mipgen_accel_insertions_fetch(h, irecs[r & 1].data(), it.alleles); }
+                if (prc == MIPGEN_OK) { ins_alleles += it.alleles; ins_events += it.insertions; ins_amb += it.ambiguous; ins_span += it.span; }
+            }
             if (pile_indels) { pt.used = gt.used; pile_gapped += gt.gapped_sides; }
             if (writer.joinable()) writer.join();
             if (prc != MIPGEN_OK) return die();
             pile_used += pt.used;
-            writer = std::thread([&, r]() { write_row(r, table[r & 1]); if (call) write_calls(r, recs[r & 1]); if (loci) write_loci(r, ltable[r & 1], lrecs[r & 1]); });
+            writer = std::thread([&, r]() {
+                write_row(r, table[r & 1]);
+                if (call) write_calls(r, recs[r & 1]);
+                if (loci) write_loci(r, ltable[r & 1], lrecs[r & 1]);
+                if (insertions) write_insertions(r, ianch[r & 1], irecs[r & 1]);
+            });
         }
         if (writer.joinable()) writer.join();
         if (fclose(pile_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, pileup_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (insertions && fclose(ins_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, ins_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call && fclose(call_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (loci && fclose(loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call_loci && fclose(call_loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
@@ -756,5 +820,6 @@ int main(int argc, char** argv)
     if (call) fprintf(stderr, "%s: calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, call_calls, call_cands, call_tested, call_deep);
     if (loci) fprintf(stderr, "%s: loci %zu lines %lld bases %lld nonref %lld discordant %lld\n", PROG, lplan.locus_pos.size(), loci_lines, loci_bases, loci_nonref, loci_disc);
     if (call_loci) fprintf(stderr, "%s: locus calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, lcall_calls, lcall_cands, lcall_tested, lcall_deep);
+    if (insertions) fprintf(stderr, "%s: insertion alleles %lld events %lld ambiguous %lld span %lld\n", PROG, ins_alleles, ins_events, ins_amb, ins_span);
     return 0;
 }
