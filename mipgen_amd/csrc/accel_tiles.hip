@@ -156,16 +156,16 @@ static int build_svr_tiles(mipgen_accel* h)             // k_svr_dense (+ the re
                 int np = std::max(1, std::min(lanes / kc, d.n_pos));       // every lane of a pair chunk owns one (position, capture size)
                 size_t lds_t = 0;
                 for (; np >= 1; np--) {
-                    lds_t = mipgen_svr_lds_bytes_tile(np, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64);
+                    lds_t = mipgen_svr_lds_bytes_tile(np, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64, 0);
                     if (lds_t <= 160 * 1024) break;
                 }
                 if (np < 1) { ok = false; break; }
                 // np = -inc (mod 32) makes the candidate steps' downstream-factor loads conflict free (see the kernel's lane mapping):
                 // taken when it costs few positions
-                { const int np_cf = np - ((np + D.inc) % 32); if (np_cf >= 1 && np_cf * 10 >= np * 9) { np = np_cf; lds_t = mipgen_svr_lds_bytes_tile(np, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64); } }
+                { const int np_cf = np - ((np + D.inc) % 32); if (np_cf >= 1 && np_cf * 10 >= np * 9) { np = np_cf; lds_t = mipgen_svr_lds_bytes_tile(np, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64, 0); } }
                 // the same number of tiles, evenly filled (the last tile of a region is not a stub that costs a full table stage)
                 { const int nt = (d.n_pos + np - 1) / np, np_even = (d.n_pos + nt - 1) / nt;
-                  if (np_even < np) { np = np_even; lds_t = mipgen_svr_lds_bytes_tile(np, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64); } }
+                  if (np_even < np) { np = np_even; lds_t = mipgen_svr_lds_bytes_tile(np, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64, 0); } }
                 runs.push_back({ki0, kc, np});
                 lds_r = std::max(lds_r, lds_t);
                 const double tiles = std::ceil((double)d.n_pos / np);
@@ -207,8 +207,13 @@ static int build_svr_tiles(mipgen_accel* h)             // k_svr_dense (+ the re
                     const int Cmax_t = Cmax - r.ki0 * D.inc, ssmax = Cmax_t - D.min_sum, ssr = (r.kc - 1) * D.inc + D.max_sum - D.min_sum + 1;
                     const double ent = (npt + (npt + ssr - 1)) * (h->geom.n_e + h->geom.n_l) / 2.0 + (double)npt * ssr;
                     const double cost = 19.0 * ent + 100.0 * (npt + ssmax + 2 * Lmax) + 75000.0;
-                    const int fits = mipgen_svr_scores_fit_lds(npt, r.kc, D.n_pairs, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, h->geom.nchunk * h->geom.wpc * 64);
-                    for (int s2 = 0; s2 < 2; s2++) { SvrTile t = {i, s2, p0, npt, r.ki0, r.kc, (int)lvl, fits}; st.push_back(t); st_cost.push_back(cost); st_few.push_back(few ? 1 : 0); }
+                    // the position pitch of the tile's insert table: padded to a conflict-free one where the tile's LDS has the room at this np (common.h:
+                    // svr_it_pitch) - the shapes above are sized with the unpadded table, so the pitch never changes them
+                    const int nthr = h->geom.nchunk * h->geom.wpc * 64;
+                    const int it_pitch = svr_it_pitch(npt, r.kc, D.inc, h->geom.wpc * 64, ssmax - ssr + 1, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, nthr);
+                    if (it_pitch) svr_lds = std::max(svr_lds, mipgen_svr_lds_bytes_tile(npt, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, nthr, it_pitch));
+                    const int fits = mipgen_svr_scores_fit_lds(npt, r.kc, D.n_pairs, ssr, ssmax, Lmax, n_arm, h->geom.group, h->geom.n_e, h->geom.n_l, nthr, it_pitch);
+                    for (int s2 = 0; s2 < 2; s2++) { SvrTile t = {i, s2, p0, npt, r.ki0, r.kc, (int)lvl, fits | (it_pitch << 8)}; st.push_back(t); st_cost.push_back(cost); st_few.push_back(few ? 1 : 0); }
                 }
             }
         }

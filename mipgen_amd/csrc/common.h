@@ -105,8 +105,9 @@ struct SvrTile {
     int32_t strand;
     int32_t p0, np;        // positions (0-based within region)
     int32_t ki0, kc;       // capture sizes ki0 .. ki0+kc-1 (0-based within the region's surviving list)
-    int32_t level, pad;    // dense SVR tiles: which of the region's capture-size runs this is (0 = the largest sizes; kernels_skip.hip); pad = the tile's
-                           // scores fit the LDS staging area of the kernel's epilogue (whole-row stores), as the host has checked
+    int32_t level, pad;    // dense SVR tiles: which of the region's capture-size runs this is (0 = the largest sizes; kernels_skip.hip); pad bit 0 = the tile's
+                           // scores fit the LDS staging area of the kernel's epilogue (whole-row stores), as the host has checked; pad >> 8 = the position
+                           // pitch of the tile's insert-factor table as the host has chosen it (svr_it_pitch below; 0 = unpadded)
 };
 
 // the entries of a re-score list (accel_score.hip: rescore): what k_print_boundary_scan tests - or, for RESCORE_SATURATED, the dense indices
@@ -175,7 +176,7 @@ struct SvrLayout {
     int ku, kd, ci, pf_stride;                 // PF block: per-length constants, insert constant; slots per SV
     int tj, ti;                                // PF block: junction terms [18], insert scan-size terms [ssr] (per SV, like the rest of the block)
     int tu, td, tb_stride;                     // TB block: first upstream / downstream slot; slots per SV
-    int ssr_p;                                 // IT row pitch in slots (scan-size range rounded up to odd: bank spread)
+    int it_p;                                  // IT is [scan size][it_p positions][group]: the position pitch in slots (svr_it_pitch: the host's choice per tile)
     int bytes_kpar;                            // 16 ints: the scalars of the window-norm pass after the SV loop
     int bytes_desc, bytes_ent, bytes_idx, bytes_sb, bytes_psum;   // byte offsets: scan descriptors (int), table-entry
                                                // descriptors (2 x u32), per-slot SV-row indices of the scans (2 x u16), bases (u8),
@@ -215,7 +216,7 @@ __attribute__((always_inline)) static inline int svr_arr_chunk(const SvrLayout& 
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
-__attribute__((always_inline)) static inline SvrLayout svr_layout(int np, int ssmin, int ssmax, int Lmax, int n_arm, int group, int n_up, int n_dn, int n_threads)
+__attribute__((always_inline)) static inline SvrLayout svr_layout(int np, int ssmin, int ssmax, int Lmax, int n_arm, int group, int n_up, int n_dn, int n_threads, int it_pitch)
 {
     SvrLayout L;
     const int ssr = ssmax - ssmin + 1;
@@ -245,8 +246,10 @@ __attribute__((always_inline)) static inline SvrLayout svr_layout(int np, int ss
     L.pf = o; o += pf_doubles;
     L.tu = 0; L.td = np * n_arm; L.tb_stride = np * n_arm + L.nq * n_arm;
     L.tb = o; o += group * L.tb_stride;
-    L.ssr_p = ssr | 1;
-    L.it = o; o += group * np * L.ssr_p;
+    // it_pitch = 0: the unpadded table (pitch np) in the footprint the tile shapes are sized with, np rows of ssr | 1 slots - a padded table is used
+    // only where it fits beside the rest at the tile's np (svr_it_pitch), so the pitch never changes a tile's shape
+    L.it_p = it_pitch > 0 ? it_pitch : np;
+    L.it = o; o += group * (it_pitch > 0 ? ssr * it_pitch : np * (ssr | 1));
     int bytes = o * 8;
     L.bytes_desc = bytes; bytes += SVR_N_ARR * 16 * 4;
     L.n_ent_lds = L.n_ent; (void)n_threads;
@@ -261,4 +264,52 @@ __attribute__((always_inline)) static inline SvrLayout svr_layout(int np, int ss
     return L;
 }
 
-
+// ---- lane and bank geometry of the candidate steps (kernel and host: the host chooses the insert table's pitch per tile; tests/svr_it_banks.cpp) ----
+#if defined(__HIPCC__)
+#define SVR_HD __host__ __device__ __attribute__((always_inline)) static inline
+#else
+#define SVR_HD __attribute__((always_inline)) static inline
+#endif
+#define SVR_LDS_LIMIT (160 * 1024)
+// Lanes of a pair chunk are capture-size major, np_lane positions per capture size: lane j = kci * np_lane + pl.  With np_lane = -inc (mod 32) the
+// downstream-factor row of lane j, pl - kci * inc + (kc - 1) * inc, is = j + (kc - 1) * inc (mod 32): a half-wavefront reads 32 distinct bank pairs.  The
+// pitch is the tile's position count rounded up to such a value where the chunk's lanes allow it (the surplus lanes idle).
+SVR_HD int svr_np_lane(int np, int kc, int inc, int lanes)
+{
+    const int padded = np + (32 - (np + inc) % 32) % 32;
+    return padded * kc > lanes ? np : padded;
+}
+SVR_HD bool svr_lane_pitch_spreads(int np_lane, int kc, int inc) { return kc == 1 || (np_lane + inc) % 32 == 0; }
+// The insert table is [scan size][pitch positions][group].  Lane j reads slot (C - kci * inc - sum - ssmin) * pitch + pl: with -inc * pitch = np_lane (mod 32)
+// that is j + const (mod 32), and the 24-byte slots of 32 consecutive lanes fall on 32 distinct bank pairs (3 j mod 32); a tile of one capture size reads
+// slot pl + const at any pitch.  Odd: the table stage writes consecutive scan sizes from consecutive lanes.
+SVR_HD bool svr_it_pitch_spreads(int pitch, int np_lane, int kc, int inc)
+{
+    return (pitch & 1) && (kc == 1 || (((np_lane + inc * pitch) % 32) + 32) % 32 == 0);
+}
+// A lane that owns no candidate reads along with its wavefront (the value is never stored).  Parked on lane 0's rows it shares a bank pair with the owner
+// j' = 0 (mod 32) of its half-wavefront and doubles the array cycles of the load - in a tile of 26 positions at a lane pitch of 27 that is seven
+// half-wavefronts of eight.  Where the owners are spread it takes the row / column of its own residue instead - if the table holds such a row for every arm
+// sum (sum_span = largest - smallest) / the pitch such a column; elsewhere the idle lanes stay together on lane 0's address, one bank pair, not up to 32.
+SVR_HD int svr_idle_d_row(int j, int np_lane, int kc, int inc, int nq, int sum_span)
+{
+    const int r = (j + (kc - 1) * inc) & 31;
+    return svr_lane_pitch_spreads(np_lane, kc, inc) && r + sum_span < nq ? r : (kc - 1) * inc;
+}
+SVR_HD int svr_idle_it_col(int j, int pitch, int np_lane, int kc, int inc)
+{
+    return svr_it_pitch_spreads(pitch, np_lane, kc, inc) && (j & 31) < pitch ? (j & 31) : 0;
+}
+// Host: the position pitch of a tile's insert table (SvrTile::pad >> 8).  The smallest conflict-free pitch >= np if the tile still fits its LDS with it, at
+// both strands' role assignments; otherwise np | 1 (conflict-free table-stage writes) if that fits; otherwise 0, the unpadded table.
+static inline int svr_it_pitch(int np, int kc, int inc, int lanes, int ssmin, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads)
+{
+    const int np_lane = svr_np_lane(np, kc, inc, lanes);
+    auto fits = [&](int pitch) {
+        return svr_layout(np, ssmin, ssmax, Lmax, n_arm, group, n_e, n_l, n_threads, pitch).total_bytes <= SVR_LDS_LIMIT &&
+               svr_layout(np, ssmin, ssmax, Lmax, n_arm, group, n_l, n_e, n_threads, pitch).total_bytes <= SVR_LDS_LIMIT;
+    };
+    for (int pitch = np; pitch < np + 64; pitch++)
+        if (svr_it_pitch_spreads(pitch, np_lane, kc, inc)) { if (fits(pitch)) return pitch; break; }
+    return fits(np | 1) ? (np | 1) : 0;
+}

@@ -74,8 +74,8 @@ size_t mipgen_logistic_dense_lds_bytes(int np_all, int np, int ssr, int ssmax, i
 hipError_t mipgen_launch_logistic_dense(hipStream_t, int n_tiles, size_t lds_bytes, const DevParams*, const DevRegion*, const SvrTile*, const uint8_t*, const int32_t*,
                                         const uint8_t*, const HostConsts*, double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
 // kernels_svr.hip
-size_t mipgen_svr_lds_bytes_tile(int np, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads);
-int mipgen_svr_scores_fit_lds(int np, int kc, int n_pairs, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads);
+size_t mipgen_svr_lds_bytes_tile(int np, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads, int it_pitch);
+int mipgen_svr_scores_fit_lds(int np, int kc, int n_pairs, int ss_range, int ssmax, int Lmax, int n_arm, int group, int n_e, int n_l, int n_threads, int it_pitch);
 hipError_t mipgen_launch_svr_dense(hipStream_t, int n_tiles, int n_tiles_few, size_t lds_bytes, const DevParams*, const SvrGeom*, const SvrGeom* geom_few, const DevRegion*,
                                    const SvrTile*, const uint8_t*, const int32_t*, const double* log10_tab, const double* model, int n_sv, double gamma_l2e, double rho,
                                    double s_guard, const uint64_t* records, double* scores, int64_t n_cand, int n_split, double* partials);
