@@ -359,7 +359,7 @@ struct mipgen_accel {
     DevBuf<double> model_t, sv_norm, sv_coef, sv_center;   // the model centred and transposed for the survivor-list scorer (kernels_svr_gemm.hip)
     int n_sv_pad = 0;
     double kmer_count_ms = -1.0;             // genome pass of the last mipgen_accel_count_oligo_copies
-    double list_feat_ms = -1.0, list_svr_ms = -1.0;   // k_features_batch (k_probe_features) / k_svr_gemm of the last list call (timing enabled)
+    double list_feat_ms = -1.0, list_svr_ms = -1.0;   // k_features_batch / k_svr_gemm of the last list call (timing enabled)
     int64_t kmer_genome_bytes = 0;
     // sparse scratch
     DevBuf<mipgen_candidate> cand_in;

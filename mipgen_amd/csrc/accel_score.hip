@@ -29,6 +29,13 @@ static RescoreLimits rescore_limits(const mipgen_accel* h, int kind, int method,
     return {(unsigned int)cap, svr ? 1e-10 : 1e-11, svr ? 1e-13 * std::max(1.0, h->sum_abs_coef) : 1e-300};
 }
 
+// what the list kernels read their entries from: the probes of ps, or cands in the resident batch
+static ListSrc list_src(const mipgen_accel* h, const mipgen_candidate* cands, const ProbeSrc* ps)
+{
+    if (ps) return {LIST_PROBES, {}, *ps};
+    return {LIST_BATCH, {h->dp, h->regions.p, cands, h->bases.p, h->copy.p, h->unmap.p}, {}};
+}
+
 // List -> re-score -> scatter back: every route that recomputes selected scores after the fast kernels.
 //  * Print-exact (RESCORE_DENSE / LIST / SURV): k_print_boundary_scan lists the scores within the kernels' error of a midpoint between two
 //    6-significant-digit numbers (what the front end prints, mipgen.cpp:774), so that the printed digit is the reference's (the re-score's
@@ -40,7 +47,8 @@ static RescoreLimits rescore_limits(const mipgen_accel* h, int kind, int method,
 //    of a megabase of (CCG)n fills it.)
 // k_candidates re-scores the list in the reference's own operation order (literal; logistic: logistic_exponent_exact, pow_base_cr), its grid the
 // list's capacity; k_scatter_scores writes the values back where they came from.
-// ps: the entries are probes given by sequence (RESCORE_PROBES) - the list keeps their positions only and k_candidates reads the probes through them.
+// ps: the entries are probes given by sequence (RESCORE_PROBES) - the list keeps their positions only and k_candidates reads the probes through them
+// (ProbeSrc::sel).
 static int rescore(mipgen_accel* h, const RescoreSrc& src, int method, const ProbeSrc* ps = nullptr)
 {
     const bool sat = src.kind == RESCORE_SATURATED;
@@ -53,14 +61,10 @@ static int rescore(mipgen_accel* h, const RescoreSrc& src, int method, const Pro
         HIP_TRY(hipMemsetAsync(L.count.p, 0, sizeof(unsigned int), h->stream));
         HIP_TRY(mipgen_launch_print_boundary_scan(h->stream, h->dp, h->regions.p, &src, lim.tol_rel, lim.tol_abs, L.cands.p, L.idx.p, L.count.p, lim.cap, h->n_cu));
     }
-    if (ps) {
-        ProbeSrc listed = *ps;
-        listed.sel = L.idx.p; listed.order = nullptr;
-        HIP_TRY(mipgen_launch_candidates_probes(h->stream, (int)lim.cap, &listed, h->dconsts, h->model.p, h->n_sv, h->gamma, h->rho, method, L.vals.p, nullptr, nullptr,
-                                                nullptr, 1, L.count.p));
-    } else
-    HIP_TRY(mipgen_launch_candidates(h->stream, (int)lim.cap, h->dp, h->regions.p, L.cands.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->model.p, h->n_sv,
-                                     h->gamma, h->rho, method, L.vals.p, nullptr, nullptr, nullptr, 1, L.count.p));
+    ListSrc listed = list_src(h, L.cands.p, ps);
+    if (ps) { listed.probes.sel = L.idx.p; listed.probes.order = nullptr; }
+    HIP_TRY(mipgen_launch_candidates(h->stream, (int)lim.cap, listed, h->dconsts, h->model.p, h->n_sv, h->gamma, h->rho, method, L.vals.p, nullptr, nullptr, nullptr, 1,
+                                     L.count.p));
     HIP_TRY(mipgen_launch_scatter_scores(h->stream, L.vals.p, L.idx.p, lim.cap, L.count.p, src.scores, src.surv, sat ? nullptr : h->pb_over));
     return MIPGEN_OK;
 }
@@ -84,7 +88,7 @@ static int fix_survivor_print_boundaries(mipgen_accel* h, int w, int method)
 
 // The route choice of the list scorer, held once: SVR scores of a list of 256 and more go through the feature kernel and the matrix cores ...
 static bool list_is_batched(int n, int method, bool want_scores) { return method == MIPGEN_SCORE_SVR && n >= 256 && want_scores; }
-// ... and the wavefront-per-entry feature kernel (k_features_batch / k_probe_features) runs unless the integer features are asked for too
+// ... and the wavefront-per-entry feature kernel (k_features_batch) runs unless the integer features are asked for too
 static bool list_runs_feature_kernel(int n, int method, bool want_scores, bool ints) { return list_is_batched(n, method, want_scores) && !ints; }
 
 // The list scorer: the candidates cand_in[0, n) -> cand_scores, cand_records (+ cand_feats / cand_ints where asked).  Long SVR lists (a mixed
@@ -92,32 +96,25 @@ static bool list_runs_feature_kernel(int n, int method, bool want_scores, bool i
 // candidate x support-vector distances instead of one model walk per candidate), then the print-exact re-score; the others through k_candidates.
 // le (optional): three events around the two stages of a matrix-core list, created here when timing is on.
 // ps (optional): the list is made of probes given by sequence (mipgen_accel_score_probes) instead of cand_in - the same choice of route, the same
-// scorers: k_probe_features in k_features_batch's place, k_candidates reading the probes' bytes instead of the resident batch.
+// kernels: only the ListSrc they read their entries from differs.
 static int score_list(mipgen_accel* h, int n, int method, bool want_scores, bool features, bool ints, hipEvent_t* le, const ProbeSrc* ps = nullptr)
 {
     const bool batched = list_is_batched(n, method, want_scores);
     if (batched && h->cand_feats.reserve((size_t)n * MIPGEN_N_FEATURES)) return MIPGEN_E_NOMEM;
     const bool time_list = le && batched && !ints && h->timing;
     if (time_list) { for (int k = 0; k < 3; k++) HIP_TRY(hipEventCreate(&le[k])); HIP_TRY(hipEventRecord(le[0], h->stream)); }
-    if (list_runs_feature_kernel(n, method, want_scores, ints) && ps)
-        HIP_TRY(mipgen_launch_probe_features(h->stream, n, ps, h->dconsts, h->cand_records.p, h->cand_feats.p));
-    else if (list_runs_feature_kernel(n, method, want_scores, ints))
-        HIP_TRY(mipgen_launch_features_batch(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->cand_records.p,
-                                             h->cand_feats.p));
-    else if (ps)
-        HIP_TRY(mipgen_launch_candidates_probes(h->stream, n, ps, h->dconsts, h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p,
-                                                h->cand_records.p, (features || batched) ? h->cand_feats.p : nullptr, ints ? h->cand_ints.p : nullptr, 0, nullptr));
+    const ListSrc src = list_src(h, h->cand_in.p, ps);
+    if (list_runs_feature_kernel(n, method, want_scores, ints))
+        HIP_TRY(mipgen_launch_features_batch(h->stream, n, src, h->dconsts, h->cand_records.p, h->cand_feats.p));
     else
-        HIP_TRY(mipgen_launch_candidates(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts,
-                                         h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p, h->cand_records.p,
-                                         (features || batched) ? h->cand_feats.p : nullptr, ints ? h->cand_ints.p : nullptr, 0, nullptr));
+        HIP_TRY(mipgen_launch_candidates(h->stream, n, src, h->dconsts, h->model.p, h->n_sv, h->gamma, h->rho, method, batched ? nullptr : h->cand_scores.p,
+                                         h->cand_records.p, (features || batched) ? h->cand_feats.p : nullptr, ints ? h->cand_ints.p : nullptr, 0, nullptr));
     if (time_list) HIP_TRY(hipEventRecord(le[1], h->stream));
     if (batched) HIP_TRY(mipgen_launch_svr_gemm(h->stream, n, h->cand_feats.p, h->cand_records.p, h->model_t.p, h->sv_norm.p, h->sv_coef.p, h->sv_center.p, h->n_sv_pad,
                                             h->gamma, h->rho, h->cand_scores.p));
     if (time_list) HIP_TRY(hipEventRecord(le[2], h->stream));
     if (!batched) return MIPGEN_OK;
-    if (ps) return rescore(h, {RESCORE_PROBES, n, h->cand_scores.p, h->cand_records.p, nullptr, nullptr, 0, 0, 0}, MIPGEN_SCORE_SVR, ps);
-    return rescore(h, {RESCORE_LIST, n, h->cand_scores.p, h->cand_records.p, h->cand_in.p, nullptr, 0, 0, 0}, MIPGEN_SCORE_SVR);
+    return rescore(h, {ps ? RESCORE_PROBES : RESCORE_LIST, n, h->cand_scores.p, h->cand_records.p, ps ? nullptr : h->cand_in.p, nullptr, 0, 0, 0}, MIPGEN_SCORE_SVR, ps);
 }
 
 // The dense grid of a window through the LIST scorer: the route of SVR parameter sets outside the tiled kernel's limits (scan size < 3,
@@ -132,8 +129,7 @@ static int svr_window_via_list(mipgen_accel* h, const Window& W)
     for (int64_t c0 = 0; c0 < W.n_cand; c0 += CH) {
         const int n = (int)std::min<int64_t>(CH, W.n_cand - c0);
         HIP_TRY(mipgen_launch_dense_candidates(h->stream, h->dp, h->regions.p, W.r0, W.r1, c0, n, h->cand_in.p));
-        HIP_TRY(mipgen_launch_features_batch(h->stream, n, h->dp, h->regions.p, h->cand_in.p, h->bases.p, h->copy.p, h->unmap.p, h->dconsts, h->cand_records.p,
-                                             h->cand_feats.p));
+        HIP_TRY(mipgen_launch_features_batch(h->stream, n, list_src(h, h->cand_in.p, nullptr), h->dconsts, h->cand_records.p, h->cand_feats.p));
         HIP_TRY(mipgen_launch_svr_gemm(h->stream, n, h->cand_feats.p, h->cand_records.p, h->model_t.p, h->sv_norm.p, h->sv_coef.p, h->sv_center.p, h->n_sv_pad,
                                        h->gamma, h->rho, h->scores.p + c0));
         HIP_TRY(mipgen_launch_dense_list_fix(h->stream, n, h->records.p + c0, h->rho, h->s_guard, h->scores.p + c0));
@@ -411,7 +407,7 @@ int mipgen_accel_score_candidates(mipgen_accel* h, const mipgen_candidate* cands
 // Probes given by their sequences (ABI 6, new entry point only): the strand-oriented extension arm, ligation arm and insert of each probe as a MIP
 // table holds them (print_details, mipgen.cpp:765-794), its copy numbers and a row of long-range content - everything SVMipv4::get_parameters and
 // get_score read - so that a design that exists only as a file can be featurized and scored.  No resident batch is needed and none is touched: the
-// list goes through score_list (k_probe_features / k_candidates over the probes' bytes, then the scorers of mipgen_accel_score_candidates), in the
+// list goes through score_list (k_features_batch / k_candidates over the probes' bytes, then the scorers of mipgen_accel_score_candidates), in the
 // handle's list scratch; win_state, cur_window, the result arrays and the resident batch stay as they were.
 int mipgen_accel_score_probes(mipgen_accel* h, const mipgen_probe* probes, int32_t n, const double* lrc, int32_t n_lrc, int32_t method, double* scores,
                               double* features, mipgen_candidate_ints* ints)
@@ -448,7 +444,7 @@ int mipgen_accel_score_probes(mipgen_accel* h, const mipgen_probe* probes, int32
     }
     // launch order of the wavefront-per-probe kernel: falling insert length in classes of 64 bases (a counting sort; the last class holds the rest)
     std::vector<int32_t> order;
-    if (list_runs_feature_kernel(n, method, scores != nullptr, ints != nullptr)) {          // (score_list's own choice: the order is k_probe_features')
+    if (list_runs_feature_kernel(n, method, scores != nullptr, ints != nullptr)) {          // (score_list's own choice: the order is the feature kernel's)
         const int NB = 64;
         auto bucket = [](int32_t len) { return NB - 1 - std::min(len >> 6, NB - 1); };
         int64_t first[NB + 1] = {0};

@@ -135,13 +135,29 @@ struct ProbeRec {
     int32_t pad;
 };
 // the probe list of a launch, by value.  sel (optional): the launch's entry b is probe sel[b] and writes result b (the re-score of listed positions);
-// order (optional, k_probe_features): wavefront w takes probe order[w] (longest inserts first) and writes at the probe's own index
+// order (optional, the feature kernel): entry w is probe order[w] (longest inserts first) and writes at the probe's own index
 struct ProbeSrc {
     const ProbeRec* probes;
     const uint8_t* bytes;
     const double* lrc;                   // [n_lrc][44]
     const int64_t* sel;
     const int32_t* order;
+};
+// ... and a list of candidates addressed by coordinates in the resident batch: entry b is cands[b] and writes result b
+struct BatchSrc {
+    const DevParams* __restrict__ P;
+    const DevRegion* __restrict__ regions;
+    const mipgen_candidate* __restrict__ cands;
+    const uint8_t* __restrict__ bases;
+    const int32_t* __restrict__ copy;
+    const uint8_t* __restrict__ unmap;
+};
+// what the list scorers (k_features_batch, k_candidates) read their entries from: one of the two sources (list_stage.h stages either)
+enum { LIST_BATCH, LIST_PROBES };
+struct ListSrc {
+    int kind;
+    BatchSrc batch;
+    ProbeSrc probes;
 };
 
 // static thread geometry of the dense SVR kernel for a parameter set (computed on the host once)

@@ -89,19 +89,13 @@ hipError_t mipgen_launch_svr_tile_compact(hipStream_t s, int n_tiles, const SvrT
 // kernels_svr_gemm.hip
 hipError_t mipgen_launch_svr_gemm(hipStream_t, int n, const double* feats, const uint64_t* records, const double* model_t, const double* sv_norm, const double* sv_coef,
                                   const double* center, int n_sv_pad, double gamma, double rho, double* scores);
-// kernels_misc.hip
+// kernels_misc.hip: the list scorers over either source of a list (candidates by coordinates / probes by sequence: ListSrc, common.h) ...
+hipError_t mipgen_launch_features_batch(hipStream_t, int n, const ListSrc&, const HostConsts*, uint64_t* records, double* features);
+hipError_t mipgen_launch_candidates(hipStream_t, int n, const ListSrc&, const HostConsts*, const double* model, int n_sv, double gamma, double rho, int method, double* scores,
+                                    uint64_t* records, double* features, mipgen_candidate_ints*, int literal, const unsigned int* n_dev);
+// ... the dense grid as a list, the print-exact scan and its scatter, survivors as a list, long-range content
 hipError_t mipgen_launch_dense_candidates(hipStream_t, const DevParams* P, const DevRegion* regions, int r0, int r1, int64_t c0, int n, mipgen_candidate* out);
 hipError_t mipgen_launch_dense_list_fix(hipStream_t, int n, const uint64_t* records, double rho, double s_guard, double* scores);
-hipError_t mipgen_launch_features_batch(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t* bases, const int32_t* copy,
-                                        const uint8_t* unmap, const HostConsts*, uint64_t* records, double* features);
-hipError_t mipgen_launch_candidates(hipStream_t, int n, const DevParams*, const DevRegion*, const mipgen_candidate*, const uint8_t*, const int32_t*, const uint8_t*,
-                                    const HostConsts*, const double* model, int n_sv, double gamma, double rho, int method, double*, uint64_t*, double*, mipgen_candidate_ints*,
-                                    int literal, const unsigned int* n_dev);
-// the same kernel over probes given by sequence (no resident batch)
-hipError_t mipgen_launch_candidates_probes(hipStream_t, int n, const ProbeSrc*, const HostConsts*, const double* model, int n_sv, double gamma, double rho, int method,
-                                           double*, uint64_t*, double*, mipgen_candidate_ints*, int literal, const unsigned int* n_dev);
-// kernels_probe.hip
-hipError_t mipgen_launch_probe_features(hipStream_t, int n, const ProbeSrc*, const HostConsts*, uint64_t* records, double* features);
 hipError_t mipgen_launch_print_boundary_scan(hipStream_t, const DevParams*, const DevRegion*, const RescoreSrc*, double tol_rel, double tol_abs, mipgen_candidate* out,
                                              int64_t* out_idx, unsigned int* count, unsigned int cap, int n_cu);
 hipError_t mipgen_launch_index_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const int64_t* idx, const unsigned int* count, unsigned int cap,

@@ -1,16 +1,17 @@
 // kernels_misc.hip — sparse-candidate scorer (mixed-mode re-scores, inspection) and Featurev5::get_long_range_content.
 //
 // k_candidates: one workgroup per candidate.  It is the literal form of the reference arithmetic:
-//   * the strand-oriented ext / lig / insert sequences are materialised in LDS (reverse_comp, MinusSVMipv4.cpp:6-29),
-//   * one lane per mer counts its overlapping occurrences (SVMipv4.cpp:31-57),
+//   * the strand-oriented ext / lig / insert sequences are materialised in LDS (list_stage.h: the one front of both list kernels),
+//   * their overlapping 1- / 2- / 3-mers are counted into an LDS histogram (mip_features.h; SVMipv4.cpp:31-57),
 //   * the 192 features are formed with the reference's own expressions (SVMipv4.cpp:72-112),
 //   * lanes then own support vectors: each walks the 192 dimensions in index order (svm.cpp:329-368), takes
 //     exp(-gamma*d2) and the partial sums coef*k are reduced with wavefront shuffles (svm.cpp:2511-2515).
 // It doubles as an on-device cross-check of the window-separable dense kernel (kernels_svr.hip).
-// Two sources of a candidate's sequences, one kernel (template parameter PROBE): coordinates in the resident region batch (strand orientation,
-// record fields and copy numbers from the batch's tables), or a probe given by its oriented sequences (ProbeSrc, mipgen_accel_score_probes: the
-// bytes of a MIP table, copies and long-range row come with the probe).  Everything behind the staged sequences - mer counts, features, integer
-// features, the logistic score, the SVR walks - is the same code.
+// k_features_batch: a wavefront per entry, features + record only - the front end of the matrix-core SVR (kernels_svr_gemm.hip).
+// Both are templates over the SOURCE of a list entry (common.h): BatchSrc, coordinates in the resident region batch, or ProbeSrc, a probe given
+// by its oriented sequences (mipgen_accel_score_probes).  The source decides how the bytes get to LDS and where copies and the long-range row come
+// from (list_stage.h); everything behind the staged sequences - mer counts, features, integer features, the logistic score, the SVR walks - is the
+// same code.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "kernels.h"
@@ -18,39 +19,12 @@
 #include "mip_record.h"
 #include "logistic_device.h"
 #include "mip_features.h"
+#include "list_stage.h"
 #include "pow_base_cr.h"
 
 #define CAND_THREADS 256
 
 namespace {
-
-// mer idx -> (k, codes) in the reference's lexicographic lists
-__device__ __forceinline__ void arm_mer(int idx, int& k, int& x, int& y)
-{
-    x = idx / 5; int r = idx - 5 * x;
-    if (r == 0) { k = 1; y = 0; } else { k = 2; y = r - 1; }
-}
-__device__ __forceinline__ void ins_mer(int idx, int& k, int& x, int& y, int& z)
-{
-    x = idx / 21; int r = idx - 21 * x;
-    y = 0; z = 0;
-    if (r == 0) { k = 1; return; }
-    r -= 1; y = r / 5; int r2 = r - 5 * y;
-    if (r2 == 0) { k = 2; return; }
-    k = 3; z = r2 - 1;
-}
-// windows that START in s[0, n) and end inside s[0, nx)
-__device__ int count_mer(const uint8_t* s, int n, int nx, int k, int x, int y, int z)
-{
-    int c = 0;
-    for (int i = 0; i < n && i + k <= nx; i++) {
-        bool m = s[i] == x;
-        if (k >= 2) m = m && s[i + 1] == y;
-        if (k >= 3) m = m && s[i + 2] == z;
-        c += m;
-    }
-    return c;
-}
 
 // one piece of the class-switch walk of run_count_slow (logistic_device.h; SVMipv4.cpp:118-142) over oriented codes: `last` < 0 before the first base
 __device__ void run_count_piece(const uint8_t* s, int n, int& last, int& run)
@@ -66,145 +40,68 @@ __device__ void run_count_piece(const uint8_t* s, int n, int& last, int& run)
 
 }  // namespace
 
-template <bool PROBE>
+template <class Src>
 __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
-    const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, const mipgen_candidate* __restrict__ cands,
-    const uint8_t* __restrict__ bases, const int32_t* __restrict__ copy, const uint8_t* __restrict__ unmap, const ProbeSrc S,
-    const HostConsts* __restrict__ HC, const double* __restrict__ model, int n_sv, double gamma, double rho, int method,
+    const Src S, const HostConsts* __restrict__ HC, const double* __restrict__ model, int n_sv, double gamma, double rho, int method,
     double* __restrict__ scores, uint64_t* __restrict__ records, double* __restrict__ features,
     mipgen_candidate_ints* __restrict__ ints_out, int literal, const unsigned int* __restrict__ n_dev)
 {
     if (n_dev && blockIdx.x >= *n_dev) return;          // a device-side list length (the grid is the list's capacity): no host round trip
     __shared__ double s_term[CAND_THREADS];
     __shared__ uint8_t s_ext[MIPGEN_MAX_OLIGO + 2], s_lig[MIPGEN_MAX_OLIGO + 2], s_ins[MAX_INSERT + 2];
-    __shared__ uint8_t s_raw[2][MIPGEN_MAX_OLIGO + 2];     // the arms' bytes as stored (code | masked bit | SNP class), in genome order
     __shared__ int s_cnt[128];          // 0..83 insert mers, 84..103 ext mers, 104..123 lig mers
     __shared__ double s_x[MIPGEN_N_FEATURES];
     __shared__ double s_red[CAND_THREADS / WAVE];
     __shared__ int s_info[16];
 
     const int tid = threadIdx.x;
-    const int64_t oi = blockIdx.x;                        // where this workgroup's results go
-    int p = 0, e, l, ss;
-    bool minus = false;
-    const DevRegion* Rp = nullptr;
-    const double* lrc;
-    ProbeRec pr = {};
-    if constexpr (PROBE) {
-        pr = S.probes[S.sel ? S.sel[blockIdx.x] : (int64_t)blockIdx.x];
-        e = pr.ext_len; l = pr.lig_len; ss = pr.ins_len;
-        lrc = pr.lrc_index >= 0 ? S.lrc + (int64_t)pr.lrc_index * MIPGEN_N_LRC : nullptr;
-        // the oriented arms as the file holds them: no strand, no masked / SNP bits, no table to look a copy number up in
-        for (int i = tid; i < e; i += CAND_THREADS) s_ext[i] = ascii_base_code(S.bytes[pr.ext_off + i]);
-        for (int i = tid; i < l; i += CAND_THREADS) s_lig[i] = ascii_base_code(S.bytes[pr.lig_off + i]);
-        if (tid == 0 && l < 2) s_lig[1] = BASE_OTHER;     // a one-base arm has no junction dimer (lig_probe_sequence.substr(0, 2), SVMipv4.cpp:103)
-        __syncthreads();
+    const auto en = list_entry(S, blockIdx.x);
+    const int64_t oi = en.out;                            // where this workgroup's results go
+    const int e = en.e, l = en.l, ss = en.ss;
+    if (!en.valid) {
         if (tid == 0) {
-            int bad = pr.guard != 0;
-            for (int i = 0; i < e; i++) bad += (s_ext[i] == BASE_N || s_ext[i] == BASE_DASH);
-            for (int i = 0; i < l; i++) bad += (s_lig[i] == BASE_N || s_lig[i] == BASE_DASH);
-            s_info[0] = pr.ext_copy; s_info[1] = pr.lig_copy; s_info[2] = 0; s_info[3] = 0;
-            s_info[4] = (int)(MIPGEN_FLAG_VALID | (bad ? MIPGEN_FLAG_GUARD : 0u));
-            s_info[5] = bad;
+            if (scores) scores[oi] = 0.0;
+            if (records) records[oi] = 0;
         }
-    } else {
-    const mipgen_candidate c = cands[blockIdx.x];
-    const DevRegion& R = regions[c.region];
-    Rp = &R; lrc = R.lrc;
-    const int C = c.capture_size;
-    p = c.scan_start; e = c.ext_len; l = c.lig_len;
-    minus = c.strand != 0;
-    ss = C - e - l;
-    const bool valid = constructed(R, p, C, e, l) && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
-    if (!valid) {
-        if (tid == 0) {
-            if (scores) scores[blockIdx.x] = 0.0;
-            if (records) records[blockIdx.x] = 0;
-        }
-        if (features) for (int j = tid; j < MIPGEN_N_FEATURES; j += CAND_THREADS) features[(int64_t)blockIdx.x * MIPGEN_N_FEATURES + j] = 0.0;
-        if (ints_out && tid == 0) { mipgen_candidate_ints z = {}; ints_out[blockIdx.x] = z; }
+        if (features) for (int j = tid; j < MIPGEN_N_FEATURES; j += CAND_THREADS) features[oi * MIPGEN_N_FEATURES + j] = 0.0;
+        if (ints_out && tid == 0) { mipgen_candidate_ints z = {}; ints_out[oi] = z; }
         return;
     }
-    const ArmStarts st = arm_starts(p, ss, e, l, minus);
-    const int ext_start = st.ext, lig_start = st.lig;
-    auto base_at = [&](int pos) -> uint8_t {
-        int ri = pos - R.seq_start;
-        return (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
-    };
-    // oriented sequences (codes); complement + reverse on '-'
-    for (int i = tid; i < e; i += CAND_THREADS) {
-        const int off = minus ? e - 1 - i : i;
-        const uint8_t raw = base_at(ext_start + off);
-        s_raw[0][off] = raw;
-        const int b = raw & BASE_CODE_MASK;
-        s_ext[i] = (uint8_t)(minus ? comp_code(b) : b);
-    }
-    for (int i = tid; i < l; i += CAND_THREADS) {
-        const int off = minus ? l - 1 - i : i;
-        const uint8_t raw = base_at(lig_start + off);
-        s_raw[1][off] = raw;
-        const int b = raw & BASE_CODE_MASK;
-        s_lig[i] = (uint8_t)(minus ? comp_code(b) : b);
-    }
-    __syncthreads();
-    // integer record fields (design_mip, mipgen.cpp:606-760)
-    if (tid == 0) {
-        int masked_n = 0, snp_any = 0, snp_bad = 0, snp_ok = 0, bad = 0;
-        for (int arm = 0; arm < 2; arm++) {
-            const int n = arm == 0 ? e : l;
-            for (int i = 0; i < n; i++) {
-                const uint8_t b = s_raw[arm][i];
-                int code = b & BASE_CODE_MASK, snp = (b >> BASE_SNP_SHIFT) & 3;
-                masked_n += (b & BASE_MASKED_BIT) != 0;
-                snp_any += snp != 0; snp_bad += snp == 2; snp_ok += snp == 1;
-                bad += (code == BASE_N || code == BASE_DASH);
-            }
+    // wave 0 stages the arms and the integer record fields (design_mip, mipgen.cpp:606-760)
+    if (tid < 128) s_cnt[tid] = 0;
+    if (tid < WAVE) {
+        const ArmInts a = en.stage_arms(s_ext, s_lig, tid);
+        if (tid == 0) {
+            s_info[0] = a.ext_copy; s_info[1] = a.lig_copy; s_info[2] = a.masked_n; s_info[3] = a.snp_count; s_info[4] = a.flags;
+            s_info[5] = a.guard; s_info[6] = a.jc;
         }
-        const int ext_copy = oligo_copy(P, R, copy, ext_start, e), lig_copy = oligo_copy(P, R, copy, lig_start, l);
-        const int k = (P->max_capture - C) / P->inc;
-        const bool mapping = k >= 0 && k < P->n_sizes_all && unmapped(P, R, unmap, k, minus, ext_start, lig_start);
-        int snp_count;
-        const uint32_t flags = record_flags(mapping, masked_n, l + e, P->masked_arm_threshold, snp_any, snp_bad, snp_ok, bad != 0, snp_count);
-        s_info[0] = ext_copy; s_info[1] = lig_copy; s_info[2] = masked_n; s_info[3] = snp_count; s_info[4] = (int)flags;
-        s_info[5] = bad;
-    }
     }
     __syncthreads();
     const int ext_copy = s_info[0], lig_copy = s_info[1];
     const bool guard = s_info[5] != 0;
-    const int j0 = s_lig[0], j1 = s_lig[1];
-    const int jc = (int)junction_code(j0, j1);
+    const int jc = s_info[6];
 
-    // mer counts: one lane per mer.  The oriented insert passes through LDS in pieces of MAX_INSERT bases (+ two of look-ahead for the 2- / 3-mers
-    // that start in a piece): one piece for every realistic capture size, no limit on the others; the class-switch walk (SVMipv4.cpp:118-142) of the
-    // logistic score carries its state across the pieces
+    // mer counts: the histogram of mip_features.h.  The oriented insert passes through LDS in pieces of MAX_INSERT bases (+ two of look-ahead for the
+    // 2- / 3-mers that start in a piece): one piece for every realistic capture size, no limit on the others; the class-switch walk
+    // (SVMipv4.cpp:118-142) of the logistic score carries its state across the pieces
     const bool want_run = ints_out || method == MIPGEN_SCORE_LOGISTIC;
-    int ins_count = 0, run_last = -1, run_n = 0;
+    int run_last = -1, run_n = 0;
     for (int c0 = 0; c0 < ss; c0 += MAX_INSERT) {
         const int len = min(MAX_INSERT, ss - c0), lenx = min(len + 2, ss - c0);
         if (c0) __syncthreads();
-        for (int i = tid; i < lenx; i += CAND_THREADS) {
-            if constexpr (PROBE) s_ins[i] = ascii_base_code(S.bytes[pr.ins_off + c0 + i]);
-            else {
-                const DevRegion& R = *Rp;
-                const int ri = (minus ? p + ss - 1 - (c0 + i) : p + c0 + i) - R.seq_start;
-                const int b = ((ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER) & BASE_CODE_MASK;
-                s_ins[i] = (uint8_t)(minus ? comp_code(b) : b);
-            }
-        }
+        en.stage_insert(s_ins, c0, lenx, tid, CAND_THREADS);
         __syncthreads();
-        if (tid < 84) { int k, x, y, z; ins_mer(tid, k, x, y, z); ins_count += count_mer(s_ins, len, lenx, k, x, y, z); }
+        hist_insert_piece(s_ins, len, lenx, s_cnt, tid, CAND_THREADS);
         if (tid == 0 && want_run) run_count_piece(s_ins, len, run_last, run_n);   // (a serial walk: only where it is used)
     }
-    if (tid < 84) s_cnt[tid] = ins_count;
-    else if (tid < 104) { int k, x, y; arm_mer(tid - 84, k, x, y); s_cnt[tid] = count_mer(s_ext, e, e, k, x, y, 0); }
-    else if (tid < 124) { int k, x, y; arm_mer(tid - 104, k, x, y); s_cnt[tid] = count_mer(s_lig, l, l, k, x, y, 0); }
+    hist_arm(s_ext, e, s_cnt + 84, tid);
+    hist_arm(s_lig, l, s_cnt + 104, tid);
     __syncthreads();
 
     // 192 features, SVMipv4.cpp:72-112
     if (tid < MIPGEN_N_FEATURES) {
         const int f = tid;
-        const double v = mip_feature(f, s_cnt, e, l, ss, lrc, jc, ext_copy, lig_copy, guard, HC);
+        const double v = mip_feature(f, s_cnt, e, l, ss, en.lrc, jc, ext_copy, lig_copy, guard, HC);
         s_x[f] = v;
         if (features) features[oi * MIPGEN_N_FEATURES + f] = v;
     }
@@ -307,89 +204,57 @@ __global__ __launch_bounds__(CAND_THREADS) void k_candidates(
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_features_batch: the 192 features + the integer record of every candidate of a LIST, one WAVEFRONT per candidate (the list scorer's
-// front end: kernels_svr_gemm.hip).  Same values as k_candidates (SVMipv4.cpp:60-113, mipgen.cpp:606-760) - the mer counts come from an LDS
-// histogram filled by one pass over the oriented sequences (a lane per start position, three atomic increments) instead of one lane per
-// mer walking the whole sequence, the record's counts from wave ballots over the arms' bytes.
+// k_features_batch: the 192 features + the integer record of every entry of a LIST (the list scorer's front end: kernels_svr_gemm.hip).  Same
+// values as k_candidates (SVMipv4.cpp:60-113, mipgen.cpp:606-760), through the same staging front and the same histogram.
+//
+// Mapping: ONE WAVEFRONT PER ENTRY, four entries per workgroup, nothing wider than a wave barrier.
+//   * The work of an entry is its insert (tens to thousands of bases; the arms are 16-30): a 64-lane wavefront covers a 150-base insert in three
+//     strides and a 1,200-base one in nineteen, with no idle waves - a 256-thread workgroup per entry would leave three of its four waves without
+//     a base to count on a typical insert and pay four workgroup barriers per entry.
+//   * Any insert length: the insert passes through LDS in pieces of MAX_INSERT bases + two of look-ahead (one piece for every realistic capture size).
+//   * Wavefronts of a workgroup finish at different times only as far as their inserts differ.  Probes come with any mix of lengths, so the host
+//     hands them over sorted by insert length (ProbeSrc::order, a counting sort): the four probes of a workgroup are of one length class and the
+//     long ones start first - the tail of the launch is made of the shortest probes.
+// Memory: an entry's bytes are read once, coalesced (lane i reads byte i); 1.5 KB of features are written per entry - for a 150-base insert the
+// stores are 8x the loads, the kernel is bound by its feature stores.
 // ---------------------------------------------------------------------------------------------------------
 #define FB_WAVES 4
 
-__global__ __launch_bounds__(FB_WAVES * 64) void k_features_batch(
-    int n, const DevParams* __restrict__ P, const DevRegion* __restrict__ regions, const mipgen_candidate* __restrict__ cands,
-    const uint8_t* __restrict__ bases, const int32_t* __restrict__ copy, const uint8_t* __restrict__ unmap, const HostConsts* __restrict__ HC,
-    uint64_t* __restrict__ records, double* __restrict__ features)
+template <class Src>
+__global__ __launch_bounds__(FB_WAVES * 64) void k_features_batch(int n, const Src S, const HostConsts* __restrict__ HC, uint64_t* __restrict__ records,
+                                                                   double* __restrict__ features)
 {
     __shared__ uint8_t s_ext_a[FB_WAVES][MIPGEN_MAX_OLIGO + 2], s_lig_a[FB_WAVES][MIPGEN_MAX_OLIGO + 2], s_ins_a[FB_WAVES][MAX_INSERT + 2];
     __shared__ int s_cnt_a[FB_WAVES][128];          // 0..83 insert mers, 84..103 ext mers, 104..123 lig mers
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ci = blockIdx.x * FB_WAVES + wave;
-    if (ci >= n) return;
+    const int wi = blockIdx.x * FB_WAVES + wave;
+    if (wi >= n) return;
     uint8_t* s_ext = s_ext_a[wave]; uint8_t* s_lig = s_lig_a[wave]; uint8_t* s_ins = s_ins_a[wave];
     int* s_cnt = s_cnt_a[wave];
-    const mipgen_candidate c = cands[ci];
-    const DevRegion& R = regions[c.region];
-    const int p = c.scan_start, C = c.capture_size, e = c.ext_len, l = c.lig_len;
-    const bool minus = c.strand != 0;
-    const int ss = C - e - l;
-    const bool valid = constructed(R, p, C, e, l) && e <= MIPGEN_MAX_OLIGO && l <= MIPGEN_MAX_OLIGO && e >= 2 && l >= 2;
-    double* fo = features + (int64_t)ci * MIPGEN_N_FEATURES;
-    if (!valid) {
-        if (lane == 0) records[ci] = 0;
+    const auto en = list_entry(S, wi);
+    const int e = en.e, l = en.l, ss = en.ss;
+    double* fo = features + en.out * MIPGEN_N_FEATURES;
+    if (!en.valid) {
+        if (lane == 0) records[en.out] = 0;
         for (int j = lane; j < MIPGEN_N_FEATURES; j += 64) fo[j] = 0.0;
         return;
     }
-    const ArmStarts st = arm_starts(p, ss, e, l, minus);
-    const int ext_start = st.ext, lig_start = st.lig;
-    auto base_at = [&](int pos) -> uint8_t {
-        const int ri = pos - R.seq_start;
-        return (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
-    };
     s_cnt[lane] = 0; s_cnt[lane + 64] = 0;
-    // arms: lane i holds byte i of the arm in genome order; oriented codes go to LDS
-    const uint8_t raw_e = lane < e ? base_at(ext_start + lane) : (uint8_t)0, raw_l = lane < l ? base_at(lig_start + lane) : (uint8_t)0;
-    if (lane < e) { const int b = raw_e & BASE_CODE_MASK; s_ext[minus ? e - 1 - lane : lane] = (uint8_t)(minus ? comp_code(b) : b); }
-    if (lane < l) { const int b = raw_l & BASE_CODE_MASK; s_lig[minus ? l - 1 - lane : lane] = (uint8_t)(minus ? comp_code(b) : b); }
-    // integer record fields (design_mip, mipgen.cpp:606-760): counts over the arms' bytes by wave ballots
-    const bool in_e = lane < e, in_l = lane < l;
-    auto cnt2 = [&](bool pe, bool pl) -> int { return __builtin_popcountll(__ballot(in_e && pe)) + __builtin_popcountll(__ballot(in_l && pl)); };
-    const int snp_e = (raw_e >> BASE_SNP_SHIFT) & 3, snp_l = (raw_l >> BASE_SNP_SHIFT) & 3;
-    const int code_e = raw_e & BASE_CODE_MASK, code_l = raw_l & BASE_CODE_MASK;
-    const int masked_n = cnt2((raw_e & BASE_MASKED_BIT) != 0, (raw_l & BASE_MASKED_BIT) != 0);
-    const int snp_any = cnt2(snp_e != 0, snp_l != 0), snp_bad = cnt2(snp_e == 2, snp_l == 2), snp_ok = cnt2(snp_e == 1, snp_l == 1);
-    const int bad = cnt2(code_e == BASE_N || code_e == BASE_DASH, code_l == BASE_N || code_l == BASE_DASH);
-    const int ext_copy = oligo_copy(P, R, copy, ext_start, e), lig_copy = oligo_copy(P, R, copy, lig_start, l);
-    const int k = (P->max_capture - C) / P->inc;
-    const bool mapping = k >= 0 && k < P->n_sizes_all && unmapped(P, R, unmap, k, minus, ext_start, lig_start);
-    int snp_count;
-    const uint32_t flags = record_flags(mapping, masked_n, l + e, P->masked_arm_threshold, snp_any, snp_bad, snp_ok, bad != 0, snp_count);
-    const bool guard = bad != 0;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int j0 = s_lig[0], j1 = s_lig[1];
-    const int jc = (int)junction_code(j0, j1);
-    if (lane == 0) {
-        records[ci] = pack_record(ext_copy, lig_copy, masked_n, snp_count, flags, (uint32_t)jc);
-    }
-    // mer histogram: a lane per window start; windows touching a non-ACGT code count nowhere (count_mer compares codes 0..3).  The oriented insert
-    // passes through LDS in pieces of MAX_INSERT bases + two of look-ahead (one piece for every realistic capture size)
+    const ArmInts a = en.stage_arms(s_ext, s_lig, lane);
+    if (lane == 0) records[en.out] = pack_record(a.ext_copy, a.lig_copy, a.masked_n, a.snp_count, (uint32_t)a.flags, (uint32_t)a.jc);
     for (int c0 = 0; c0 < ss; c0 += MAX_INSERT) {
         const int len = min(MAX_INSERT, ss - c0), lenx = min(len + 2, ss - c0);
-        if (c0) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-        for (int i = lane; i < lenx; i += 64) {
-            const int b = base_at(minus ? p + ss - 1 - (c0 + i) : p + c0 + i) & BASE_CODE_MASK;
-            s_ins[i] = (uint8_t)(minus ? comp_code(b) : b);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        if (c0) wave_lds_sync();
+        en.stage_insert(s_ins, c0, lenx, lane, 64);
+        wave_lds_sync();
         hist_insert_piece(s_ins, len, lenx, s_cnt, lane, 64);
     }
     hist_arm(s_ext, e, s_cnt + 84, lane);
     hist_arm(s_lig, l, s_cnt + 104, lane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     // 192 features, SVMipv4.cpp:72-112 (the arithmetic of k_candidates, three features per lane)
     for (int f = lane; f < MIPGEN_N_FEATURES; f += 64)
-        fo[f] = mip_feature(f, s_cnt, e, l, ss, R.lrc, jc, ext_copy, lig_copy, guard, HC);
+        fo[f] = mip_feature(f, s_cnt, e, l, ss, en.lrc, a.jc, a.ext_copy, a.lig_copy, a.guard != 0, HC);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -448,33 +313,26 @@ extern "C" hipError_t mipgen_launch_dense_list_fix(hipStream_t stream, int n, co
     return hipGetLastError();
 }
 
-extern "C" hipError_t mipgen_launch_features_batch(hipStream_t stream, int n, const DevParams* P, const DevRegion* regions, const mipgen_candidate* cands,
-                                                   const uint8_t* bases, const int32_t* copy, const uint8_t* unmap, const HostConsts* HC, uint64_t* records,
-                                                   double* features)
+// the list kernels over either source of S
+extern "C" hipError_t mipgen_launch_features_batch(hipStream_t stream, int n, const ListSrc& S, const HostConsts* HC, uint64_t* records, double* features)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_features_batch, dim3((n + FB_WAVES - 1) / FB_WAVES), dim3(FB_WAVES * 64), 0, stream, n, P, regions, cands, bases, copy, unmap, HC, records,
-                       features);
+    const dim3 grid((n + FB_WAVES - 1) / FB_WAVES), block(FB_WAVES * 64);
+    if (S.kind == LIST_PROBES) hipLaunchKernelGGL(k_features_batch<ProbeSrc>, grid, block, 0, stream, n, S.probes, HC, records, features);
+    else hipLaunchKernelGGL(k_features_batch<BatchSrc>, grid, block, 0, stream, n, S.batch, HC, records, features);
     return hipGetLastError();
 }
-
-extern "C" hipError_t mipgen_launch_candidates(
-    hipStream_t stream, int n, const DevParams* P, const DevRegion* regions, const mipgen_candidate* cands, const uint8_t* bases,
-    const int32_t* copy, const uint8_t* unmap, const HostConsts* HC, const double* model, int n_sv, double gamma, double rho,
-    int method, double* scores, uint64_t* records, double* features, mipgen_candidate_ints* ints, int literal, const unsigned int* n_dev)
+extern "C" hipError_t mipgen_launch_candidates(hipStream_t stream, int n, const ListSrc& S, const HostConsts* HC, const double* model, int n_sv, double gamma, double rho,
+                                               int method, double* scores, uint64_t* records, double* features, mipgen_candidate_ints* ints, int literal,
+                                               const unsigned int* n_dev)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_candidates<false>, dim3(n), dim3(CAND_THREADS), 0, stream, P, regions, cands, bases, copy, unmap, ProbeSrc{}, HC, model,
-                       n_sv, gamma, rho, method, scores, records, features, ints, literal, n_dev);
-    return hipGetLastError();
-}
-extern "C" hipError_t mipgen_launch_candidates_probes(hipStream_t stream, int n, const ProbeSrc* S, const HostConsts* HC, const double* model, int n_sv, double gamma,
-                                                      double rho, int method, double* scores, uint64_t* records, double* features, mipgen_candidate_ints* ints,
-                                                      int literal, const unsigned int* n_dev)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_candidates<true>, dim3(n), dim3(CAND_THREADS), 0, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, *S, HC, model,
-                       n_sv, gamma, rho, method, scores, records, features, ints, literal, n_dev);
+    if (S.kind == LIST_PROBES)
+        hipLaunchKernelGGL(k_candidates<ProbeSrc>, dim3(n), dim3(CAND_THREADS), 0, stream, S.probes, HC, model, n_sv, gamma, rho, method, scores, records, features, ints,
+                           literal, n_dev);
+    else
+        hipLaunchKernelGGL(k_candidates<BatchSrc>, dim3(n), dim3(CAND_THREADS), 0, stream, S.batch, HC, model, n_sv, gamma, rho, method, scores, records, features, ints,
+                           literal, n_dev);
     return hipGetLastError();
 }
 

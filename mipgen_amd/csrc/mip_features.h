@@ -1,6 +1,6 @@
 // mip_features.h — SVMipv4::get_parameters (SVMipv4.cpp:60-113) as the list kernels restate it: one definition each of the mer histogram over
-// an oriented sequence in LDS and of the 192 feature values formed from it.  k_candidates, k_features_batch (kernels_misc.hip: candidates
-// addressed by coordinates in a resident batch) and k_probe_features (kernels_probe.hip: probes given by their sequences) all go through these.
+// an oriented sequence in LDS and of the 192 feature values formed from it.  Both list kernels (kernels_misc.hip: k_candidates, a workgroup per
+// entry, and k_features_batch, a wavefront per entry) go through these, whichever source staged the sequence (list_stage.h).
 //
 // Count layout (int[128]): 0..83 the insert mers in the reference's lexicographic list (x: 21 x, xy: 21 x + 1 + 5 y, xyz: 21 x + 1 + 5 y + 1 + z),
 // 84..103 the extension arm's mers (x: 5 x, xy: 5 x + 1 + y), 104..123 the ligation arm's.

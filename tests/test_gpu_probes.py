@@ -114,7 +114,7 @@ def is_guarded(pr):
 
 @need_ref
 def test_features_bit_for_bit_against_the_reference():
-    """Every one of the 192 doubles of 3,000 random probes equals SVMipv4::get_parameters' as a bit pattern - through k_probe_features (the
+    """Every one of the 192 doubles of 3,000 random probes equals SVMipv4::get_parameters' as a bit pattern - through k_features_batch (the
     >= 256 SVR route) and through k_candidates (features asked with a logistic score, and a list below 256).
 
     The extension arm's GC entry (SVMipv4.cpp:76) divides by `extension_arm_length - arm_mers[i].length() + 1`, an unsigned integer expression,
@@ -134,12 +134,12 @@ def test_features_bit_for_bit_against_the_reference():
     assert sum(len(pr["ins"]) > 1200 for pr in probes) >= 100 and sum(len(pr["ext"]) == 1 for pr in probes) >= 5
     acc = _accel(model=MODEL)
     try:
-        s_svr, f_batch, _ = acc.score_probes(tup, capi.SCORE_SVR, lrc=lrc_rows, want_features=True)               # k_probe_features
+        s_svr, f_batch, _ = acc.score_probes(tup, capi.SCORE_SVR, lrc=lrc_rows, want_features=True)               # k_features_batch
         s_log, f_cand, ints = acc.score_probes(tup, capi.SCORE_LOGISTIC, lrc=lrc_rows, want_features=True, want_ints=True)   # k_candidates
         _, f_short, _ = acc.score_probes(tup[:200], capi.SCORE_SVR, lrc=lrc_rows, want_features=True)             # < 256
     finally:
         acc.close()
-    for name, got in (("k_probe_features", f_batch), ("k_candidates", f_cand)):
+    for name, got in (("k_features_batch", f_batch), ("k_candidates", f_cand)):
         bad = np.nonzero((got.view(np.int64) != want.view(np.int64)).any(axis=1))[0]
         assert bad.size == 0, (name, bad[:5], [np.nonzero(got[b].view(np.int64) != want[b].view(np.int64))[0][:6] for b in bad[:3]])
     assert np.array_equal(f_short.view(np.int64), want[:200].view(np.int64))
@@ -162,7 +162,7 @@ def test_scores_against_the_reference():
     SVR scores within **1e-5**" - for the literal kernel it adds the measurement "91 % ... bit-identical to the reference's, the rest within 2 ulp".
     The logistic route here IS the literal kernel (k_candidates: logistic_exponent_exact + pow_base_cr), so it is held to that kernel's figure,
     2 ulp of the reference's double, on top of the 1e-5; SVR against ref_predict_text (libsvm-written model) is held to the 1e-5, on the >= 256
-    route (k_probe_features + k_svr_gemm + print-exact re-score) and on the < 256 route (k_candidates); the largest differences are printed."""
+    route (k_features_batch + k_svr_gemm + print-exact re-score) and on the < 256 route (k_candidates); the largest differences are printed."""
     R = po.refdrv()
     probes = [pr for pr in random_probes(2400, 23)]
     rng = np.random.default_rng(6)
