@@ -58,6 +58,9 @@ struct SvtPred {
     double gamma, rho;
 };
 
+// tests/svt_driver.py mirrors the three structs with ctypes and asserts the same sizes
+static_assert(sizeof(SvtCtl) == 56 && sizeof(SvtProb) == 144 && sizeof(SvtPred) == 56, "SvtCtl / SvtProb / SvtPred: the layout the ctypes mirrors restate");
+
 // Every launcher takes the device array of descriptors and a device list of `count` indices into it: workgroup b works on probs[list[b]].
 extern "C" {
 hipError_t mipgen_svt_launch_gram(hipStream_t, int n, double gamma, const double* x, double* xsq, double* qd, float* K);

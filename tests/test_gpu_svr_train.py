@@ -83,6 +83,13 @@ CASES = {
     "n4000_wide": dict(n=4000, seed=11, gamma=0.05, C=32.0, p=0.05),
     "duplicated_rows": dict(n=1200, seed=13, gamma=0.01, C=4.0, p=0.05, dup_frac=0.1),
     "zero_rows": dict(n=800, seed=17, gamma=0.02, C=2.0, p=0.1, zero_rows=12),
+    # the edges: fewer rows than a wavefront or a Gram tile, no support vector at all, every support vector at the bound, K = 1 everywhere
+    "n1": dict(n=1, seed=31, gamma=0.01, C=4.0, p=0.05),
+    "n2": dict(n=2, seed=32, gamma=0.01, C=4.0, p=0.001),
+    "n17": dict(n=17, seed=33, gamma=0.01, C=4.0, p=0.05),
+    "no_sv": dict(n=300, seed=37, gamma=0.01, C=4.0, p=10.0),              # p above the spread of the labels
+    "all_bounded": dict(n=300, seed=41, gamma=0.01, C=1e-3, p=0.05),
+    "gamma0": dict(n=300, seed=43, gamma=0.0, C=4.0, p=0.05),
 }
 
 
@@ -98,6 +105,10 @@ def test_model_file_is_libsvms_byte_for_byte(name, tmp_path):
     assert got == want, f"{name}: {first_diff(got, want)}; info {info}"
     n_sv, gamma, _ = acc.model_info()
     assert n_sv == info["n_sv"] == int(want.split(b"total_sv ")[1].split(b"\n")[0]) and gamma == float("%g" % c["gamma"])
+    if name == "no_sv":
+        assert info["n_sv"] == 0 and b"total_sv 0\n" in want
+    if name == "all_bounded":
+        assert info["n_bsv"] == info["n_sv"] > 0, info
     if name == "n4000_wide":                                 # the shrinking path: do_shrinking, its unshrink and the final reconstruct_gradient
         assert info["n_shrink"] > 0 and info["n_reconstruct"] > 0, info
     acc.close()
@@ -155,6 +166,60 @@ def test_trained_handle_scores_as_the_loaded_file(tmp_path):
             assert (np.isnan(s) and np.isnan(want)) or abs(s - want) <= 1e-5, (s, want)
     finally:
         R.ref_svm_free_model(m)
+    acc.close(); fresh.close()
+
+
+def outcome(call):
+    """what a call gives: its result, or the text of its refusal"""
+    try:
+        return "ok", call()
+    except capi.AccelError as e:
+        return "refused", str(e)
+
+
+def same_outcome(a, b):
+    if a[0] != b[0]:
+        return False
+    if a[0] == "refused":
+        return a[1] == b[1]
+    return all((u is None and v is None) or np.array_equal(u, v, equal_nan=u.dtype.kind == "f") for u, v in zip(a[1], b[1]))
+
+
+@need_ref
+def test_trained_handle_without_support_vectors_behaves_as_the_loaded_file(tmp_path):
+    """The no_sv case leaves a model of zero support vectors: the handle that trained it and a fresh handle that loads the file give the same scores, or
+    the same refusal, for the regions and for a list of 200 candidates."""
+    c = CASES["no_sv"]
+    X, Y = training_set(c["n"], c["seed"])
+    path = str(tmp_path / "m.model")
+    acc, P = new_accel()
+    info = acc.train_svr(X, Y, c["gamma"], c["C"], c["p"], model_path=path)
+    assert info["n_sv"] == 0 and b"total_sv 0\n" in open(path, "rb").read()
+    fresh, _ = new_accel()
+    fresh.load_model_file(path)
+    assert acc.model_info() == fresh.model_info() and acc.model_info()[0] == 0
+    genome = synth.random_genome(12000, 5, n_run_frac=0.002, n_run_len=6)
+    regions = [capi.build_region(genome, "1", 5000, 5055, P, bwa_mode="hashed", label="s1", lrc=np.linspace(0.01, 0.3, 44)),
+               capi.build_region(genome, "1", 7000, 7090, P, bwa_mode="hashed", label="s2", lrc=np.linspace(0.3, 0.01, 44))]
+    ra = outcome(lambda: acc.score_regions(regions, capi.SCORE_SVR)[1:])
+    rb = outcome(lambda: fresh.score_regions(regions, capi.SCORE_SVR)[1:])
+    assert same_outcome(ra, rb), (ra, rb)
+    # 200 valid candidates, found by the logistic pass (it needs no model)
+    grids, _, rec = acc.score_regions(regions, capi.SCORE_LOGISTIC)
+    rng = np.random.default_rng(3)
+    cands = []
+    for ri, g in enumerate(grids):
+        valid = np.nonzero((capi.rec_flags(rec[g.offset:g.offset + g.count]) & capi.FLAG_VALID) != 0)[0]
+        for idx in rng.choice(valid, size=min(100, len(valid)), replace=False):
+            A = P.n_arm_pairs
+            a = int(idx % A); row = int(idx // A); st = row & 1; rest = row >> 1
+            ki, pi = rest % g.n_sizes, rest // g.n_sizes
+            cands.append((ri, g.first_pos + pi, P.max_capture_size - (g.first_size_index + ki) * P.capture_increment, P.arm_ext[a], P.arm_lig[a], st))
+    assert len(cands) == 200
+    acc.upload(regions); fresh.upload(regions)
+    ca = outcome(lambda: acc.score_candidates(cands, capi.SCORE_SVR)[:2])
+    cb = outcome(lambda: fresh.score_candidates(cands, capi.SCORE_SVR)[:2])
+    assert same_outcome(ca, cb), (ca, cb)
     acc.close(); fresh.close()
 
 

@@ -7,6 +7,7 @@ import subprocess
 import pytest
 
 from mipgen_amd import capi
+from tests import svt_driver
 
 TRAIN_BIN = os.path.join(os.path.dirname(capi.LIB_PATH), "mipgen_svr_train")
 GOOD = "1.5 1:0.25 3:-1 192:4\n0.5 2:1e-3 5:0.5\n2.25 1:1 2:2 3:3\n"
@@ -24,6 +25,12 @@ def test_struct_mirrors_match_the_header():
     assert capi.SvrTrainInfo.rho.offset == 16 and capi.SvrTrainInfo.n_shrink.offset == 32 and capi.SvrTrainInfo.solve_ms.offset == 48
     assert "mipgen_accel_train_svr" in capi.EXPORTED_SYMBOLS
     assert hasattr(capi.Accel, "train_svr")
+
+
+def test_kernel_struct_mirrors_match_the_header():
+    """svr_train.h static_asserts the same three sizes"""
+    assert C.sizeof(svt_driver.SvtCtl) == 56 and C.sizeof(svt_driver.SvtProb) == 144 and C.sizeof(svt_driver.SvtPred) == 56
+    assert svt_driver.SvtCtl.gmax1.offset == 40 and svt_driver.SvtProb.C.offset == 128 and svt_driver.SvtPred.gamma.offset == 40
 
 
 @pytest.mark.parametrize("args,needle", [
