@@ -229,7 +229,7 @@ static int replay_window_impl(mipgen_accel* h, bool want_mask)
     // the per-candidate emitted flags are only materialised for callers that fetch them (the all_mips file); the fold itself keeps
     // them as lane masks in LDS
     if (want_mask && W.n_cand) HIP_TRY(hipMemsetAsync(h->emitted.p, 0, (size_t)W.n_cand, h->stream));
-    HIP_TRY(mipgen_launch_replay_condense(h->stream, h->n_regions, (int)W.n_pos, h->dp, h->hp.n_pairs, h->hp.n_sizes_all, h->regions.p, h->pos_region.p + W.pos0,
+    HIP_TRY(mipgen_launch_replay_condense(h->stream, (int)W.n_pos, h->dp, h->hp.n_pairs, h->hp.n_sizes_all, h->regions.p, h->pos_region.p + W.pos0,
                                           h->pos_local.p + W.pos0, h->scores.p, h->records.p, h->copy.p, W.cand0, want_mask ? h->emitted.p : nullptr,
                                           h->survivors.p + 2 * W.pos0, h->emitted_per_region.p));
     if (h->timing && h->ev.size() >= 4 * ((size_t)w + 1)) { HIP_TRY(hipEventRecord(h->ev[4 * (size_t)w + 3], h->stream)); h->ev_used[(size_t)w] |= 2; }

@@ -75,47 +75,9 @@ __device__ __forceinline__ int xcd_remap(int b, int n)
 // exact n / d for n < 2^32 / d using a precomputed M = floor(2^32 / d) + 1
 __device__ __forceinline__ uint32_t fastdiv(uint32_t n, uint32_t M) { return __umulhi(n, M); }
 
-// Block-wide exclusive prefix sum, in place, of data[0..n-1] (LDS); data[n] receives the total.
-// Packed 16-bit fields in a u64 scan independently as long as no field reaches 65536.
-// scratch: at least 8 u64 in LDS.  All threads of the block must call.
-__device__ inline void block_exclusive_scan_u64(uint64_t* data, int n, uint64_t* scratch)
-{
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int chunk = (n + nt - 1) / nt;
-    const int lo = tid * chunk;
-    const int hi = min(lo + chunk, n);
-    uint64_t total = 0;
-    for (int i = lo; i < hi; i++) total += data[i];
-    // inclusive scan of per-thread totals within the wave
-    uint64_t inc = total;
-    const int lane = tid & (WAVE - 1), wid = tid / WAVE;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        uint64_t t = shfl_up_u64(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == WAVE - 1) scratch[wid] = inc;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wid; w++) woff += scratch[w];
-    uint64_t run = woff + inc - total;
-    for (int i = lo; i < hi; i++) {
-        uint64_t v = data[i];
-        data[i] = run;
-        run += v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t t = 0;
-        const int nw = (nt + WAVE - 1) / WAVE;
-        for (int w = 0; w < nw; w++) t += scratch[w];
-        data[n] = t;
-    }
-    __syncthreads();
-}
-
-// The same for three arrays of equal length at once: one pass, three barriers instead of nine, the three wave scans interleaved.
-// scratch: at least 3 * 16 u64 in LDS.
+// Block-wide exclusive prefix sum, in place, of three LDS arrays of equal length at once: d*[0..n-1] are scanned, d*[n] receives the total.  One pass,
+// three barriers, the three wave scans interleaved.  Packed 16-bit fields in a u64 scan independently as long as no field reaches 65536.
+// scratch: at least 3 * 16 u64 in LDS.  All threads of the block must call.
 __device__ inline void block_exclusive_scan3_u64(uint64_t* d0, uint64_t* d1, uint64_t* d2, int n, uint64_t* scratch)
 {
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -134,6 +96,7 @@ __device__ inline void block_exclusive_scan3_u64(uint64_t* d0, uint64_t* d1, uin
     if (lane == WAVE - 1) { scratch[wid] = i0; scratch[16 + wid] = i1; scratch[32 + wid] = i2; }
     __syncthreads();
     uint64_t w0 = 0, w1 = 0, w2 = 0;
+#pragma unroll 4                                                         // (eight at a time hold 48 registers here: k_records_logistic<false> went from 38 to 72)
     for (int w = 0; w < wid; w++) { w0 += scratch[w]; w1 += scratch[16 + w]; w2 += scratch[32 + w]; }
     uint64_t r0 = w0 + i0 - t0, r1 = w1 + i1 - t1, r2 = w2 + i2 - t2;
     for (int i = lo; i < hi; i++) {

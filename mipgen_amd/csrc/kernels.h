@@ -65,11 +65,13 @@ struct CallCounters { unsigned long long tested, too_deep, candidates, calls; };
 struct LocusCounters { unsigned long long covered, bases, discordant, deletions, insertions, ins_discordant; };
 
 extern "C" {
-// kernels_logistic.hip
+// kernels_logistic.hip, kernels_logistic_dense.hip: the two producers of the dense grid's records, bit-identical - both stage the tile's bases and take
+// every window count from prefix_words.h, the record rules from mip_record.h and the bounds skips from mip_bounds.h.  k_records_logistic (one candidate per
+// lane; span = bases a tile can touch) scores where the window tables of k_logistic_dense do not fit, and writes the records alone for the SVR kernels
 size_t mipgen_logistic_lds_bytes(int span);
 hipError_t mipgen_launch_records_logistic(hipStream_t, int score, int n_tiles, int span_max, const DevParams*, const DevRegion*, const LogTile*, const uint8_t*, const int32_t*,
                                           const uint8_t*, const HostConsts*, double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
-// kernels_logistic_dense.hip
+// k_logistic_dense (tables per arm / insert window, a (position, size) row per wavefront pass); lds_bytes: the host's tile sizing
 size_t mipgen_logistic_dense_lds_bytes(int np_all, int np, int ssr, int ssmax, int Lmax, int n_up, int n_dn);
 hipError_t mipgen_launch_logistic_dense(hipStream_t, int n_tiles, size_t lds_bytes, const DevParams*, const DevRegion*, const SvrTile*, const uint8_t*, const int32_t*,
                                         const uint8_t*, const HostConsts*, double*, uint64_t*, int64_t* sat_idx, unsigned int* sat_count, unsigned int sat_cap);
@@ -106,8 +108,9 @@ hipError_t mipgen_launch_surv_keep(hipStream_t, const mipgen_survivor* surv, int
 hipError_t mipgen_launch_surv_candidates(hipStream_t, const DevParams*, const DevRegion*, int r0, int r1, const mipgen_survivor* surv, int64_t n, int64_t cand0,
                                          const int64_t* offs, mipgen_candidate* out, int64_t* out_idx);
 hipError_t mipgen_launch_long_range(hipStream_t, int n, const char* seqs, const int64_t* offs, const int32_t* lens, const int32_t* denoms, const LrcMers*, double* out);
-// kernels_replay.hip
-hipError_t mipgen_launch_replay_condense(hipStream_t, int n_regions, int total_pos, const DevParams*, int n_pairs, int n_sizes_max, const DevRegion*, const int32_t* pos_region,
+// kernels_replay.hip: the consumers of the dense grid.  Replay + condense fold, one wavefront per scan position of the window's position map; the launcher picks
+// k_replay_condense_carry<3|5|8> (<= 64 pairs, <= 8 sizes), _narrow<wide> (<= 64 pairs) or the chunked k_replay_condense from n_pairs and n_sizes_max
+hipError_t mipgen_launch_replay_condense(hipStream_t, int total_pos, const DevParams*, int n_pairs, int n_sizes_max, const DevRegion*, const int32_t* pos_region,
                                          const int32_t* pos_local, const double* scores, const uint64_t* records, const int32_t* copy, int64_t cand_base, uint8_t* emitted,
                                          mipgen_survivor* survivors, unsigned long long* emitted_per_region);
 hipError_t mipgen_launch_collapse(hipStream_t, int n_tiles, const CollapseTile* tiles, const DevParams*, const DevRegion*, const int64_t* region_pos0,

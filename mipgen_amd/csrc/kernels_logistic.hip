@@ -7,9 +7,10 @@
 //   SVMipv4::get_score                   /root/reference/SVMipv4.cpp:114-248
 //
 // Mapping to the hardware: one workgroup per run of scan-start positions of one region.  The region bytes the
-// tile can touch are staged in LDS once and turned into packed 16-bit prefix counts (three u64 words per base),
-// so every window statistic of a candidate (A/C/G counts, N guard, masked N, SNP counts, GC/AT class switches)
-// is two ds_read_b64 and a subtract - no per-base loop, no std::string.  One candidate per lane; consecutive
+// tile can touch are staged in LDS once and turned into packed 16-bit prefix counts (three u64 words per base:
+// prefix_words.h, the front this kernel shares with k_logistic_dense), so every window statistic of a candidate
+// (A/C/G counts, N guard, masked N, SNP counts, GC/AT class switches) is two ds_read_b64 and a subtract - no
+// per-base loop, no std::string.  One candidate per lane; consecutive
 // lanes own consecutive dense-grid indices, so the 8-byte score and 8-byte record stores of a wave are two
 // contiguous 512-byte segments (coalesced, the only compulsory HBM traffic of this kernel: 16 B/candidate).
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 
 #include "logistic_device.h"
 #include "mip_record.h"
+#include "prefix_words.h"
 
 // grid = number of tiles; block = LOG_THREADS; dynamic LDS = lds_bytes(span_max)
 #define LOG_RINV 512
@@ -41,43 +43,12 @@ __global__ __launch_bounds__(LOG_THREADS) void k_records_logistic(
     const int lo = p_first - Lmax;                             // chromosome coordinate of tile-local base 0
     const int span = tile.np + Cmax + Lmax;                    // bases [lo, lo+span)
 
-    uint64_t* W0 = (uint64_t*)smem;                            // span+1 each
-    uint64_t* W1 = W0 + (span + 1);
-    uint64_t* W2 = W1 + (span + 1);
-    uint64_t* scratch = W2 + (span + 1);                       // 8
-    double* rinv = (double*)(scratch + 8);                     // LOG_RINV entries: 1.0 / i by true division
-    uint8_t* sb = (uint8_t*)(rinv + LOG_RINV);                 // span
+    PrefixWords W = prefix_words_carve(smem, span);
+    double* rinv = (double*)(W.scratch + PW_SCRATCH);          // LOG_RINV entries: 1.0 / i by true division
+    W.sb = (uint8_t*)(rinv + LOG_RINV);                        // span
 
     for (int i = tid; i < LOG_RINV; i += LOG_THREADS) rinv[i] = i > 0 ? 1.0 / (double)i : 0.0;
-    // ---- stage bases, per-base indicator words ---------------------------------------------------
-    for (int i = tid; i < span; i += LOG_THREADS) {
-        int pos = lo + i;
-        int ri = pos - R.seq_start;
-        uint8_t b = (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
-        sb[i] = b;
-    }
-    __syncthreads();
-    for (int i = tid; i < span; i += LOG_THREADS) {
-        uint8_t b = sb[i];
-        int c = b & BASE_CODE_MASK;
-        int snp = (b >> BASE_SNP_SHIFT) & 3;
-        uint64_t w0 = (uint64_t)(c == BASE_A) | ((uint64_t)(c == BASE_C) << 16) | ((uint64_t)(c == BASE_G) << 32) |
-                      ((uint64_t)(c == BASE_N || c == BASE_DASH) << 48);
-        uint64_t w1 = (uint64_t)((b & BASE_MASKED_BIT) != 0) | ((uint64_t)(snp != 0) << 16) |
-                      ((uint64_t)(snp == 2) << 32) | ((uint64_t)(snp == 1) << 48);
-        int sw = 0;
-        if (i > 0) {
-            int cp = sb[i - 1] & BASE_CODE_MASK;
-            bool gc = (c == BASE_G || c == BASE_C), gcp = (cp == BASE_G || cp == BASE_C);
-            sw = gc != gcp;
-        }
-        uint64_t w2 = (uint64_t)sw | ((uint64_t)(c >= 4) << 16);
-        W0[i] = w0; W1[i] = w1; W2[i] = w2;
-    }
-    __syncthreads();
-    block_exclusive_scan_u64(W0, span, scratch);
-    block_exclusive_scan_u64(W1, span, scratch);
-    block_exclusive_scan_u64(W2, span, scratch);
+    prefix_words_build<LOG_THREADS>(W, R, bases, lo, span);
 
     // ---- one candidate per lane --------------------------------------------------------------------
     const uint32_t row = (uint32_t)(2 * A);                    // candidates per (p, C)
@@ -99,54 +70,36 @@ __global__ __launch_bounds__(LOG_THREADS) void k_records_logistic(
         const int ss = C - e - l;
         const int p = p_first + (int)pl;
 
-        const bool valid = !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) && ss > 0;   // :443-444
         uint64_t rec = 0;
         double score = 0.0;
-        if (valid) {
+        if (constructed(R, p, C, e, l)) {                      // :443-444
             const ArmStarts st = arm_starts(p, ss, e, l, minus);
             const int ext_start = st.ext, lig_start = st.lig;
             const int be = ext_start - lo, bl = lig_start - lo, bi = p - lo;    // tile-local
-            const uint64_t e0 = W0[be + e] - W0[be], l0 = W0[bl + l] - W0[bl];
-            const uint64_t e1 = W1[be + e] - W1[be], l1 = W1[bl + l] - W1[bl];
-            const bool guard = (f16(e0, 3) + f16(l0, 3)) != 0;                  // SVMipv4.cpp:63,116
+            const ArmCounts ce = arm_window(W, be, e), cl = arm_window(W, bl, l);
+            const bool guard = (ce.bad + cl.bad) != 0;                          // SVMipv4.cpp:63,116
             const int ext_copy = oligo_copy(P, R, copy, ext_start, e), lig_copy = oligo_copy(P, R, copy, lig_start, l);
             const bool mapping = unmapped(P, R, unmap, R.k0 + (int)ki, minus, ext_start, lig_start);
-            const uint32_t masked_n = f16(e1, 0) + f16(l1, 0);
+            const uint32_t masked_n = ce.masked + cl.masked;
             int snp_count;
-            const uint32_t flags = record_flags(mapping, (int)masked_n, l + e, thr, (int)(f16(e1, 1) + f16(l1, 1)), (int)(f16(e1, 2) + f16(l1, 2)),
-                                                (int)(f16(e1, 3) + f16(l1, 3)), guard, snp_count);
-            // ligation junction = first two bases of the oriented ligation arm
-            int j0, j1;
-            if (!minus) { j0 = sb[bl] & BASE_CODE_MASK; j1 = sb[bl + 1] & BASE_CODE_MASK; }
-            else { j0 = comp_code(sb[bl + l - 1] & BASE_CODE_MASK); j1 = comp_code(sb[bl + l - 2] & BASE_CODE_MASK); }
-            const uint32_t jc = junction_code(j0, j1);
+            const uint32_t flags = record_flags(mapping, (int)masked_n, l + e, thr, (int)(ce.snp_any + cl.snp_any), (int)(ce.snp_bad + cl.snp_bad),
+                                                (int)(ce.snp_ok + cl.snp_ok), guard, snp_count);
+            const uint32_t jc = lig_junction(W.sb, bl, l, minus);
             rec = pack_record(ext_copy, lig_copy, (int)masked_n, snp_count, flags, jc);
 
             if (SCORE) {
                 if (guard) score = -1000.0;
                 else {
-                    const uint64_t t0 = W0[bi + ss] - W0[bi];
-                    const uint64_t t2 = W2[bi + ss] - W2[bi];
-                    const uint32_t t_other = f16(t2, 1);
-                    int run;
-                    if (t_other == 0) run = 1 + (int)(f16(W2[bi + ss], 0) - f16(W2[bi + 1], 0));
-                    else run = run_count_slow(sb, bi, ss, minus);
-                    // counts on the oriented strand: revcomp swaps G<->C and A<->T
-                    const uint32_t eA = f16(e0, 0), eC = f16(e0, 1), eG = f16(e0, 2);
-                    const uint32_t lA = f16(l0, 0), lC = f16(l0, 1), lG = f16(l0, 2);
-                    const uint32_t tA = f16(t0, 0), tC = f16(t0, 1), tG = f16(t0, 2);
-                    // T = length - A - C - G - (non-ACGT characters, e.g. IUPAC codes, which count as nothing)
-                    const uint32_t e_other = f16(W2[be + e] - W2[be], 1), l_other = f16(W2[bl + l] - W2[bl], 1);
-                    const uint32_t eT = (uint32_t)e - eA - eC - eG - e_other;
-                    const uint32_t lT = (uint32_t)l - lA - lC - lG - l_other;
-                    const uint32_t tT = (uint32_t)ss - tA - tC - tG - t_other;
+                    const InsertCounts t = insert_window(W, bi, ss, minus);
+                    const int run = t.run;
                     Vars x;
                     const double dl = (double)e, ll = (double)l, dn = (double)ss;
-                    const double e_g = minus ? (double)eC : (double)eG, l_g = minus ? (double)lC : (double)lG,
-                                 t_g = minus ? (double)tC : (double)tG;
-                    const double e_a = minus ? (double)eT : (double)eA, l_a = minus ? (double)lT : (double)lA,
-                                 t_a = minus ? (double)tT : (double)tA;
-                    const double e_gc = (double)(eC + eG), l_gc = (double)(lC + lG), t_gc = (double)(tC + tG);
+                    // counts on the oriented strand: revcomp swaps G<->C and A<->T
+                    const double e_g = minus ? (double)ce.nC : (double)ce.nG, l_g = minus ? (double)cl.nC : (double)cl.nG,
+                                 t_g = minus ? (double)t.nC : (double)t.nG;
+                    const double e_a = minus ? (double)ce.nT : (double)ce.nA, l_a = minus ? (double)cl.nT : (double)cl.nA,
+                                 t_a = minus ? (double)t.nT : (double)t.nA;
+                    const double e_gc = (double)(ce.nC + ce.nG), l_gc = (double)(cl.nC + cl.nG), t_gc = (double)(t.nC + t.nG);
                     // contents = count * (1/len) with 1/len from the table (the reference divides; the quotients agree to 1 ulp)
                     const double re = rinv[e], rl = rinv[l], rn = ss < LOG_RINV ? rinv[ss] : 1.0 / dn;
                     x.v[MLV_BPS] = run < LOG_RINV ? dn * rinv[run] : dn / (double)run;
@@ -174,7 +127,7 @@ __global__ __launch_bounds__(LOG_THREADS) void k_records_logistic(
 
 extern "C" size_t mipgen_logistic_lds_bytes(int span)
 {
-    return (size_t)(3 * (span + 1) + 8 + LOG_RINV) * sizeof(uint64_t) + (size_t)span + 16;
+    return (prefix_words_u64(span) + LOG_RINV) * sizeof(uint64_t) + (size_t)span + 16;
 }
 
 extern "C" hipError_t mipgen_launch_records_logistic(

@@ -19,6 +19,8 @@
 #include "logistic_device.h"
 #include "logistic_groups.h"
 #include "exp2_tab.h"
+#include "mip_record.h"
+#include "prefix_words.h"
 
 #define LD_THREADS 512
 #define LD_ARM_STRIDE 9              // doubles per arm-window entry: 8 values + one packed 64-bit word
@@ -33,7 +35,7 @@ extern "C" size_t mipgen_logistic_dense_lds_bytes(int np_all, int np, int ssr, i
     const int nq = np + ssr - 1;
     const int span = np_all + ssmax + 2 * Lmax + 2;
     size_t b = 0;
-    b += (size_t)3 * (span + 1) * 8 + 48 * 8;                   // W0..W2 prefix words + scan scratch
+    b += prefix_words_u64(span) * 8;                             // W0..W2 prefix words + scan scratch
     b += 102 * 8;                                                // log10 of the copy numbers 0..100 (101 = "more than 100")
     b += 256 * 8;                                                // 2^(j/256) table of the exponential
     b += (size_t)span + 16 + 16;                                 // bases (+ alignment of what follows)
@@ -61,7 +63,7 @@ __device__ __forceinline__ uint64_t pack_word(bool lig_role, int copy, uint32_t 
     const uint32_t c16 = (uint32_t)min(max(copy, 0), 65535);
     const uint32_t fl = (guard ? MIPGEN_FLAG_GUARD : 0u) | (snp_ok ? MIPGEN_FLAG_HAS_SNP_MIP : 0u) | (snp_bad != 0 ? MIPGEN_FLAG_SNP : 0u) | (copy <= 0 ? LD_COPY0 : 0u);
     const uint32_t lo = lig_role ? c16 << 16 : c16;
-    const uint32_t hi = min(masked, 255u) | (min(snp_any, 255u) << 8) | (fl << 16) | (lig_role ? (jc < 16 ? jc : 255u) << 24 : 0u);
+    const uint32_t hi = min(masked, 255u) | (min(snp_any, 255u) << 8) | (fl << 16) | (lig_role ? jc << 24 : 0u);
     return (uint64_t)lo | ((uint64_t)hi << 32);
 }
 
@@ -103,37 +105,16 @@ __global__ __launch_bounds__(LD_THREADS, 2) void k_logistic_dense(
     const int lo = p_first - Lmax;                                     // chromosome coordinate of local base 0
     const int span = np_all + (P->max_capture - (R.k0 + tile.ki0) * inc - P->min_sum) + 2 * Lmax + 2;
 
-    uint64_t* W0 = (uint64_t*)smem;
-    uint64_t* W1 = W0 + (span + 1);
-    uint64_t* W2 = W1 + (span + 1);
-    uint64_t* scratch = W2 + (span + 1);                               // 48
-    double* LG = (double*)(scratch + 48);                              // log10(copy), as log_copy_dev gives it
+    PrefixWords W = prefix_words_carve(smem, span);
+    double* LG = (double*)(W.scratch + PW_SCRATCH);                    // log10(0..100), HostConsts::log10_tab (102 slots)
     double* XT = LG + 102;                                             // 2^(j/256)
-    uint8_t* sb = (uint8_t*)(XT + 256);
-    double* const tables = (double*)(smem + ((((size_t)(sb - smem) + span + 16 + 15) & ~(size_t)15)));   // the run's tables, carved per run
+    W.sb = (uint8_t*)(XT + 256);
+    double* const tables = (double*)(smem + ((((size_t)(W.sb - smem) + span + 16 + 15) & ~(size_t)15)));   // the run's tables, carved per run
     for (int i = tid; i < 256; i += LD_THREADS) XT[i] = EXP2_TAB[i];
+    for (int i = tid; i < 102; i += LD_THREADS) LG[i] = i <= 100 ? HC->log10_tab[i] : 2.0;
 
-    // ---- stage bases and the packed prefix words (as k_records_logistic) ---------------------------------------------------------
-    for (int i = tid; i < span; i += LD_THREADS) {
-        const int ri = lo + i - R.seq_start;
-        sb[i] = (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
-    }
-    for (int i = tid; i < 102; i += LD_THREADS) LG[i] = i <= 100 ? HC->log10_tab[i] : 2.0;      // SVMipv4.cpp:173-174: copy > 100 ? 2 : log10(copy)
-    __syncthreads();
-    for (int i = tid; i < span; i += LD_THREADS) {
-        const uint8_t b = sb[i];
-        const int c = b & BASE_CODE_MASK, snp = (b >> BASE_SNP_SHIFT) & 3;
-        int sw = 0;
-        if (i > 0) {
-            const int cp = sb[i - 1] & BASE_CODE_MASK;
-            sw = ((c == BASE_G || c == BASE_C) != (cp == BASE_G || cp == BASE_C));
-        }
-        W0[i] = (uint64_t)(c == BASE_A) | ((uint64_t)(c == BASE_C) << 16) | ((uint64_t)(c == BASE_G) << 32) | ((uint64_t)(c == BASE_N || c == BASE_DASH) << 48);
-        W1[i] = (uint64_t)((b & BASE_MASKED_BIT) != 0) | ((uint64_t)(snp != 0) << 16) | ((uint64_t)(snp == 2) << 32) | ((uint64_t)(snp == 1) << 48);
-        W2[i] = (uint64_t)sw | ((uint64_t)(c >= 4) << 16);
-    }
-    __syncthreads();
-    block_exclusive_scan3_u64(W0, W1, W2, span, scratch);
+    // ---- stage bases and the packed prefix words ------------------------------------------------------------------------------------
+    prefix_words_build<LD_THREADS>(W, R, bases, lo, span);
     LD_STAMP(0)
 
     for (int run = 0; run < n_runs; run++) {
@@ -184,28 +165,15 @@ __global__ __launch_bounds__(LD_THREADS, 2) void k_logistic_dense(
         if (up) { wl = w / n_up; li = w - wl * n_up; len = up_min + li; s = Lmax + pb + wl - len; }
         else { const int w2 = w - nU; wl = w2 / n_dn; li = w2 - wl * n_dn; wl += wl_new; len = dn_min + li; s = Lmax + ssmin + pb + wl; }
         const bool lig_role = up ? minus : !minus;
-        const uint64_t d0 = W0[s + len] - W0[s], d1 = W1[s + len] - W1[s], d2 = W2[s + len] - W2[s];
-        const uint32_t nA = f16(d0, 0), nC = f16(d0, 1), nG = f16(d0, 2), nBad = f16(d0, 3), nOther = f16(d2, 1);
-        const uint32_t nT = (uint32_t)len - nA - nC - nG - nOther;
-        // copy number of the oligo, mipgen.cpp:612-613 (absent key -> 0)
-        int cp = 1;
+        const ArmCounts c = arm_window(W, s, len);
         const int start_chr = lo + s;                                  // chromosome coordinate of the window start
-        if (R.copy_off >= 0) {
-            const int slot = P->len_slot[len], ri = start_chr - R.seq_start;
-            cp = (slot >= 0 && ri >= 0 && ri < R.seq_len) ? copy[R.copy_off + (int64_t)slot * R.seq_len + ri] : 0;
-        }
-        uint32_t jc = 16;
-        if (lig_role) {
-            int j0, j1;
-            if (!minus) { j0 = sb[s] & BASE_CODE_MASK; j1 = sb[s + 1] & BASE_CODE_MASK; }
-            else { j0 = comp_code(sb[s + len - 1] & BASE_CODE_MASK); j1 = comp_code(sb[s + len - 2] & BASE_CODE_MASK); }
-            if (j0 < 4 && j1 < 4) jc = (uint32_t)(4 * j0 + j1);
-        }
+        const int cp = oligo_copy(P, R, copy, start_chr, len);
+        const uint32_t jc = lig_role ? lig_junction(W.sb, s, len, minus) : 255u;
         double* e = (up ? TU : TD) + (size_t)(up ? wl * n_up + li : wl * n_dn + li) * LD_ARM_STRIDE;
         // oriented base contents: the reverse complement swaps A<->T and C<->G
         const double rl = 1.0 / (double)len, dl = (double)len;
-        const double a_c = (double)(minus ? nT : nA) * rl, g_c = (double)(minus ? nC : nG) * rl, gc_c = (double)(nC + nG) * rl;
-        const double lcopy = cp > 100 ? 2.0 : (cp >= 0 ? LG[cp] : __longlong_as_double(0x7FF8000000000000LL));   // as log_copy_dev
+        const double a_c = (double)(minus ? c.nT : c.nA) * rl, g_c = (double)(minus ? c.nC : c.nG) * rl, gc_c = (double)(c.nC + c.nG) * rl;
+        const double lcopy = log_copy_tab(LG, cp);
         if (!lig_role) {
             e[0] = (MIPGEN_LOGISTIC_C0 - MIPGEN_LOGISTIC_C1) + MLG_FE(a_c, g_c, gc_c, dl, lcopy);     // the constant term rides on the extension-arm entry
             e[1] = MLG_G_LG(a_c, g_c, gc_c, dl, lcopy); e[2] = MLG_G_LLC(a_c, g_c, gc_c, dl, lcopy); e[3] = MLG_G_LLEN(a_c, g_c, gc_c, dl, lcopy);
@@ -217,14 +185,14 @@ __global__ __launch_bounds__(LD_THREADS, 2) void k_logistic_dense(
             e[1] = g_c; e[2] = lcopy; e[3] = js; e[4] = a_c;
             e[5] = MLG_HL_BPS(gc_c, g_c, js, a_c, dl, lcopy); e[6] = MLG_HL_TA(gc_c, g_c, js, a_c, dl, lcopy); e[7] = MLG_HL_TGC(gc_c, g_c, js, a_c, dl, lcopy);
         }
-        ((uint64_t*)e)[8] = pack_word(lig_role, cp, f16(d1, 0), f16(d1, 1), f16(d1, 2), f16(d1, 3) != 0, nBad != 0, jc);
+        ((uint64_t*)e)[8] = pack_word(lig_role, cp, c.masked, c.snp_any, c.snp_bad, c.snp_ok != 0, c.bad != 0, jc);
         if (up) {
             // mapping flag, mipgen.cpp:615-625: the MIP starts at its upstream arm on either strand; one bit per capture size of the tile
             uint32_t mask = 0;
-            if (R.unmap_off >= 0 && P->check_copy_number) {
+            if (mapping_tested(P, R)) {
                 const int ms = start_chr - R.seq_start;
                 if (ms >= 0 && ms < R.seq_len)
-                    for (int k = 0; k < rkc; k++) mask |= (uint32_t)(unmap[R.unmap_off + (int64_t)(R.k0 + rk0 + k) * R.seq_len + ms] != 0) << k;
+                    for (int k = 0; k < rkc; k++) mask |= (uint32_t)unmapped_at(R, unmap, R.k0 + rk0 + k, ms) << k;
             }
             UM[wl * n_up + li] = (uint16_t)mask;
         }
@@ -235,15 +203,10 @@ __global__ __launch_bounds__(LD_THREADS, 2) void k_logistic_dense(
         const int pl = w / ssr, ssi = w - pl * ssr, ss = ssmin + ssi, bi = Lmax + pb + pl;
         double* t = TT + (size_t)w * LD_INS_STRIDE;
         if (ss <= 0) { t[0] = 0.0; t[1] = 0.0; t[2] = 0.0; t[3] = 0.0; continue; }
-        const uint64_t t0 = W0[bi + ss] - W0[bi], t2 = W2[bi + ss] - W2[bi];
-        const uint32_t tA = f16(t0, 0), tC = f16(t0, 1), tG = f16(t0, 2), t_other = f16(t2, 1);
-        const uint32_t tT = (uint32_t)ss - tA - tC - tG - t_other;
-        int run;
-        if (t_other == 0) run = 1 + (int)(f16(W2[bi + ss], 0) - f16(W2[bi + 1], 0));        // GC/AT class switches inside the window, SVMipv4.cpp:118-142
-        else run = run_count_slow(sb, bi, ss, minus);
+        const InsertCounts c = insert_window(W, bi, ss, minus);
         const double dn = (double)ss, rn = 1.0 / dn;
-        const double bps = dn / (double)run, tlen = ss > 250 ? 250.0 : dn;
-        const double ta = (double)(minus ? tT : tA) * rn, tg = (double)(minus ? tC : tG) * rn, tgc = (double)(tC + tG) * rn;
+        const double bps = dn / (double)c.run, tlen = ss > 250 ? 250.0 : dn;
+        const double ta = (double)(minus ? c.nT : c.nA) * rn, tg = (double)(minus ? c.nC : c.nG) * rn, tgc = (double)(c.nC + c.nG) * rn;
         t[0] = MLG_FT(bps, tlen, ta, tgc, tg); t[1] = bps; t[2] = tgc; t[3] = ta;
     }
     LD_STAMP(2)
@@ -304,8 +267,9 @@ __global__ __launch_bounds__(LD_THREADS, 2) void k_logistic_dense(
             const int64_t out_row = R.out_off + ((((int64_t)(tile.p0 + pb + pl) * nK + (rk0 + kci)) * 2 + (minus ? 1 : 0)) * A);
             char* const rrow = (char*)(records + out_row);
             char* const srow = (char*)(scores + out_row);
-            // bounds skips, mipgen.cpp:443-444: no lane can fail them in a row this far inside the region (scalar test); otherwise three compares per lane
-            const int over = p + C - 1 - R.seq_stop;                              // the arms must be longer than this
+            // bounds skips, mipgen.cpp:443-444 in their row form (mip_bounds.h: row_all_constructed / row_lane_constructed, written out - see there): no lane can
+            // fail them in a row this far inside the region (scalar test); otherwise three compares per lane
+            const int over = row_over(R.seq_stop, p, C);
             bool valid = have;
             if (!(p > arm_hi && over <= arm_lo && C > P->max_sum)) valid = have && p > arm_mx && over <= arm_mn && C > S;
             lds_cd* T = (lds_cd*)(unsigned long)(s_ins + c_ins);

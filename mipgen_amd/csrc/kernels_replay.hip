@@ -160,6 +160,36 @@ __device__ __forceinline__ Lists row_lists(bool in, int e, int l, int gend, int 
     return L;
 }
 
+// my pair of a row of at most 64 pairs (lane a of the single-wavefront kernels), and the lanes of my arm-sum list
+struct RowPair { bool in; int e, l; Lists L; };
+__device__ __forceinline__ RowPair row_pair(const DevParams* P, int lane)
+{
+    RowPair W;
+    W.in = lane < P->n_pairs;
+    W.e = W.in ? P->arm_ext[lane] : 1; W.l = W.in ? P->arm_lig[lane] : 1;
+    W.L = row_lists(W.in, W.e, W.l, W.in ? P->group_end[lane] : 0, P->key_min_sum);
+    return W;
+}
+
+// The scan position gp of the batch's position map, which one wavefront replays: its region ri / R, its index pi inside the region, the row geometry
+// (A pairs, nK capture sizes, base = the dense-grid index of the position's first candidate) and the two parameters every row of the replay tests.
+struct ReplayPos {
+    int ri, pi;
+    const DevRegion& R;
+    int A, nK;
+    int64_t base;
+    double upper;
+    bool heuristic;
+};
+__device__ __forceinline__ ReplayPos replay_pos(int gp, const DevParams* P, const DevRegion* regions, const int32_t* pos_region, const int32_t* pos_local)
+{
+    const int ri = pos_region[gp], pi = pos_local[gp];
+    const DevRegion& R = regions[ri];
+    const int A = P->n_pairs, nK = R.n_sizes;
+    const int64_t per_pos = (int64_t)nK * A * 2;
+    return ReplayPos{ri, pi, R, A, nK, R.out_off + (int64_t)pi * per_pos, P->upper, P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic};
+}
+
 // One row of the replay, mipgen.cpp:430-434,494-497, all lists of the row at once (see k_replay_condense_narrow): the lanes it emits.  pbs is
 // previous_best_score, carried through the lists and rows.
 __device__ __forceinline__ uint64_t replay_row(double& pbs, double plus, double minus, bool valid, bool heuristic, double upper, const Lists& L)
@@ -215,13 +245,7 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense(
     const int gp = blockIdx.x * REPLAY_WAVES + wave;
     if (gp >= total_pos) return;
     uint64_t* emask = s_masks + (size_t)wave * lds_pitch;
-    const int ri = pos_region[gp], pi = pos_local[gp];
-    const DevRegion& R = regions[ri];
-    const int A = P->n_pairs, nK = R.n_sizes;
-    const int64_t per_pos = (int64_t)nK * A * 2;
-    const int64_t base = R.out_off + (int64_t)pi * per_pos;
-    const double upper = P->upper;
-    const bool heuristic = P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic;
+    const auto [ri, pi, R, A, nK, base, upper, heuristic] = replay_pos(gp, P, regions, pos_region, pos_local);
     const int min_sum = P->key_min_sum;
     const uint64_t lane_bit = 1ull << lane, below_me = lane_bit - 1;
 
@@ -333,29 +357,15 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_narrow(
     const int gp = blockIdx.x * REPLAY_WAVES + wave;
     if (gp >= total_pos) return;
     uint64_t* emask = s_masks + (size_t)wave * lds_pitch;
-    const int ri = pos_region[gp], pi = pos_local[gp];
-    const DevRegion& R = regions[ri];
-    const int A = P->n_pairs, nK = R.n_sizes;
-    const int64_t per_pos = (int64_t)nK * A * 2;
-    const int64_t base = R.out_off + (int64_t)pi * per_pos;
-    const double upper = P->upper;
-    const bool heuristic = P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic;
+    const auto [ri, pi, R, A, nK, base, upper, heuristic] = replay_pos(gp, P, regions, pos_region, pos_local);
     const uint64_t lane_bit = 1ull << lane;
-
-    // my pair, and the lanes of my arm-sum list
-    const bool in = lane < A;
-    const int e = in ? P->arm_ext[lane] : 1, l = in ? P->arm_lig[lane] : 1;
-    const Lists L = row_lists(in, e, l, in ? P->group_end[lane] : 0, P->key_min_sum);
-    // :443-444, the bounds skips, from the geometry alone: a pair is constructed at scan start p and capture size C iff p > max(e, l),
-    // p + C - 1 - min(e, l) <= seq_stop and the scan target is not empty (C > e + l) - exactly the VALID bit of the candidate's record
-    // (kernels_logistic_dense.hip, kernels_logistic.hip: `ss > 0`; mipgen_accel_create refuses parameter sets with min_capture <= max arm sum, the
-    // test keeps this kernel in step with the other two replay kernels should that ever change), which the replay therefore does not fetch: 16 instead of
-    // 24 bytes per pair and row.  One unsigned compare per row: e + l < C <= c_lim  <=>  (unsigned)(C - e - l - 1) <= (unsigned)(c_lim - e - l - 1).
-    const int p_scan = R.first_pos + pi;
-    const int c_lim = R.seq_stop - p_scan + 1 + min(e, l);                   // largest capture size that still fits
-    const int c_span = c_lim - (e + l) - 1;
-    const bool ok_lo = in && p_scan > max(e, l) && c_span >= 0;
-    const int c_top = P->max_capture - R.k0 * P->inc - (e + l) - 1, c_inc = P->inc;   // (capture size of row ki) - e - l - 1 = c_top - ki * c_inc
+    const auto [in, e, l, L] = row_pair(P, lane);
+    // :443-444 from the geometry alone, in the span form of mip_bounds.h - exactly the VALID bit of the candidate's record, which the replay therefore
+    // does not fetch: 16 instead of 24 bytes per pair and row, one unsigned compare per row
+    const BoundsSpan span = bounds_span(R.seq_stop, R.first_pos + pi, e, l);
+    const bool ok_lo = in && span.ok_lo;
+    const int c_span = span.c_span;
+    const int c_top = span_top(P->max_capture - R.k0 * P->inc, e, l), c_inc = P->inc;   // the row of size index ki: c_top - ki * c_inc
 
     // ---- replay, mipgen.cpp:426-497 ---------------------------------------------------------------------
     unsigned long long n_emitted = 0;
@@ -401,7 +411,7 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_narrow(
             if (ki >= nK) break;
             uint64_t emit_all = 0;
             if (!(pbs > upper)) {                                            // :430
-                const bool valid = ok_lo && (unsigned)(c_top - ki * c_inc) <= (unsigned)c_span;  // :443-444 (false outside the row)
+                const bool valid = span_constructed(ok_lo, c_span, c_top - ki * c_inc);         // :443-444 (false outside the row)
                 emit_all = replay_row(pbs, bp[q], bm[q], valid, heuristic, upper, L);
                 n_emitted += 2ull * (unsigned)__builtin_popcountll(emit_all);
                 if (emitted && (emit_all & lane_bit)) {
@@ -483,20 +493,10 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_carry(
     mipgen_survivor* __restrict__ survivors, unsigned long long* __restrict__ emitted_per_region)
 {
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int gp = blockIdx.x * REPLAY_WAVES + wave;
+    const int gp = blockIdx.x * REPLAY_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (gp >= total_pos) return;
-    const int ri = pos_region[gp], pi = pos_local[gp];
-    const DevRegion& R = regions[ri];
-    const int A = P->n_pairs, nK = R.n_sizes;                               // nK <= CR (the launcher checks the parameter set)
-    const int64_t per_pos = (int64_t)nK * A * 2;
-    const int64_t base = R.out_off + (int64_t)pi * per_pos;
-    const double upper = P->upper;
-    const bool heuristic = P->score_method == MIPGEN_SCORE_LOGISTIC && P->logistic_heuristic;
-
-    const bool in = lane < A;
-    const int e = in ? P->arm_ext[lane] : 1, l = in ? P->arm_lig[lane] : 1;
-    const Lists L = row_lists(in, e, l, in ? P->group_end[lane] : 0, P->key_min_sum);
+    const auto [ri, pi, R, A, nK, base, upper, heuristic] = replay_pos(gp, P, regions, pos_region, pos_local);   // nK <= CR (the launcher checks the parameter set)
+    const auto [in, e, l, L] = row_pair(P, lane);
 
     // ---- the position's rows: scores and records of both strands, one round trip ----
     double bp[CR], bm[CR];
@@ -544,11 +544,10 @@ __global__ __launch_bounds__(REPLAY_WAVES * 64) void k_replay_condense_carry(
 }
 
 extern "C" hipError_t mipgen_launch_replay_condense(
-    hipStream_t stream, int n_regions, int total_pos, const DevParams* P, int n_pairs, int n_sizes_max, const DevRegion* regions,
+    hipStream_t stream, int total_pos, const DevParams* P, int n_pairs, int n_sizes_max, const DevRegion* regions,
     const int32_t* pos_region, const int32_t* pos_local, const double* scores, const uint64_t* records, const int32_t* copy, int64_t cand_base,
     uint8_t* emitted, mipgen_survivor* survivors, unsigned long long* emitted_per_region)
 {
-    (void)n_regions;
     if (total_pos <= 0) return hipSuccess;
     const int n_chunks = (n_pairs + 63) / 64;
     const int pitch = n_sizes_max * n_chunks;

@@ -34,11 +34,7 @@ struct BatchEntry {
     int64_t out;                   // where the entry's results go
     const double* lrc;
 
-    __device__ __forceinline__ uint8_t base_at(int pos) const
-    {
-        const int ri = pos - R->seq_start;
-        return (ri >= 0 && ri < R->seq_len) ? S.bases[R->seq_off + ri] : (uint8_t)BASE_OTHER;
-    }
+    __device__ __forceinline__ uint8_t base_at(int pos) const { return region_base(*R, S.bases, pos); }
     // lane i holds byte i of each arm in genome order; oriented codes (complement + reverse on '-') go to LDS, the record's counts over the arms'
     // bytes come from wave ballots
     __device__ __forceinline__ ArmInts stage_arms(uint8_t* s_ext, uint8_t* s_lig, int lane) const

@@ -25,13 +25,14 @@ __constant__ double c_junction_scores[16] = MIPGEN_JUNCTION_SCORES;
 //  W2: class switch | nonACGT<<16
 __device__ __forceinline__ uint32_t f16(uint64_t w, int k) { return (uint32_t)(w >> (16 * k)) & 0xFFFFu; }
 
-__device__ __forceinline__ double log_copy_dev(const HostConsts* HC, int copy)
+// SVMipv4.cpp:173-174: copy > 100 ? 2 : log10(copy), from a table of log10(0..100) (HostConsts::log10_tab or a copy of it in LDS)
+__device__ __forceinline__ double log_copy_tab(const double* tab, int copy)
 {
-    // SVMipv4.cpp:173-174: copy > 100 ? 2 : log10(copy)
     if (copy > 100) return 2.0;
-    if (copy >= 0) return HC->log10_tab[copy];
+    if (copy >= 0) return tab[copy];
     return __longlong_as_double(0x7FF8000000000000LL);   // log10 of a negative int: NaN
 }
+__device__ __forceinline__ double log_copy_dev(const HostConsts* HC, int copy) { return log_copy_tab(HC->log10_tab, copy); }
 
 // SVMipv4.cpp:118-142 on the strand-oriented insert, for windows containing non-ACGT characters.
 // sb: base bytes; window [b0, b0+n) in forward coordinates; minus = walk it reversed (classes are

@@ -1,11 +1,15 @@
 // mip_record.h — the integer record of design_mip and the bounds skips, as the device kernels restate them: one definition each.
 //
 // The record layout is the one the MIPGEN_REC_* accessors of include/mipgen_accel.h read; every builder packs it with pack_record, and every
-// kernel that looks an oligo's copy number up, tests the mapping flag, places a candidate's arms or applies the record's constant SVR scores
-// does so through the functions below.
+// kernel that reads a region's base, looks an oligo's copy number up, tests the mapping flag, places a candidate's arms, orients the ligation
+// junction, decides the bounds skips (mip_bounds.h: the rule and the forms the dense-grid kernels use) or applies the record's constant SVR
+// scores does so through the functions below.  The one exception is k_svr_dense (kernels_svr.hip): its arm_entry keeps a copy lookup and a
+// junction orientation of its own - the kernel sits at its register budget, and a call there changes its generated code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "device_utils.h"
+#include "mip_bounds.h"
 
 struct ArmStarts { int ext, lig; };
 
@@ -16,10 +20,13 @@ __device__ __forceinline__ ArmStarts arm_starts(int p, int ss, int e, int l, boo
 }
 
 // the bounds skips of mipgen.cpp:443-444, and a non-empty scan target: the candidate is constructed (MIPGEN_FLAG_VALID)
-__device__ __forceinline__ bool constructed(const DevRegion& R, int p, int C, int e, int l)
+__device__ __forceinline__ bool constructed(const DevRegion& R, int p, int C, int e, int l) { return constructed(R.seq_stop, p, C, e, l); }
+
+// the byte of the region's sequence at chromosome coordinate pos (common.h: code, masked bit, SNP class); BASE_OTHER outside it
+__device__ __forceinline__ uint8_t region_base(const DevRegion& R, const uint8_t* bases, int pos)
 {
-    const int ss = C - e - l;
-    return !(p - e <= 0 || p - l <= 0) && !(p + C - e - 1 > R.seq_stop || p + C - l - 1 > R.seq_stop) && ss > 0;
+    const int ri = pos - R.seq_start;
+    return (ri >= 0 && ri < R.seq_len) ? bases[R.seq_off + ri] : (uint8_t)BASE_OTHER;
 }
 
 // copy number of the oligo [start, start + len), mipgen.cpp:612-613: absent key -> 0, no table -> 1
@@ -38,12 +45,15 @@ __device__ __forceinline__ int true_arm_copy(const DevParams* P, const DevRegion
     return oligo_copy(P, R, copy, start, len);
 }
 
-// mapping flag, mipgen.cpp:615-625: the unmappable-position table of capture size index k at the MIP's upstream arm
+// mapping flag, mipgen.cpp:615-625: the unmappable-position table of capture size index k at the MIP's upstream arm.  mapping_tested: there is a
+// table and the parameters consult it; unmapped_at: its entry for size index k at ms = start - seq_start, 0 <= ms < seq_len
+__device__ __forceinline__ bool mapping_tested(const DevParams* P, const DevRegion& R) { return R.unmap_off >= 0 && P->check_copy_number; }
+__device__ __forceinline__ bool unmapped_at(const DevRegion& R, const uint8_t* unmap, int k, int ms) { return unmap[R.unmap_off + (int64_t)k * R.seq_len + ms] != 0; }
 __device__ __forceinline__ bool unmapped(const DevParams* P, const DevRegion& R, const uint8_t* unmap, int k, bool minus, int ext_start, int lig_start)
 {
-    if (R.unmap_off < 0 || !P->check_copy_number) return false;
+    if (!mapping_tested(P, R)) return false;
     const int ms = (minus ? lig_start : ext_start) - R.seq_start;
-    return ms >= 0 && ms < R.seq_len && unmap[R.unmap_off + (int64_t)k * R.seq_len + ms] != 0;
+    return ms >= 0 && ms < R.seq_len && unmapped_at(R, unmap, k, ms);
 }
 
 // the record's flags, mipgen.cpp:610,626,690-693,759-760; snp_count is 0 where the mapping flag returns early (the masking and SNP fields keep
@@ -63,6 +73,15 @@ __device__ __forceinline__ uint32_t record_flags(bool mapping, int masked_n, int
 
 // ligation junction = the first two bases of the oriented ligation arm, 4 * code + code (A < C < G < T); 255 if either is not ACGT
 __device__ __forceinline__ uint32_t junction_code(int j0, int j1) { return (j0 < 4 && j1 < 4) ? (uint32_t)(4 * j0 + j1) : 255u; }
+
+// ... of the ligation arm [start, start + len) of genome-order base bytes sb: on '-' the oriented arm is the reverse complement
+__device__ __forceinline__ uint32_t lig_junction(const uint8_t* sb, int start, int len, bool minus)
+{
+    int j0, j1;
+    if (!minus) { j0 = sb[start] & BASE_CODE_MASK; j1 = sb[start + 1] & BASE_CODE_MASK; }
+    else { j0 = comp_code(sb[start + len - 1] & BASE_CODE_MASK); j1 = comp_code(sb[start + len - 2] & BASE_CODE_MASK); }
+    return junction_code(j0, j1);
+}
 
 // the 64-bit record, fields as MIPGEN_REC_*: copy numbers saturate at 65535, the masked-base and SNP counts at 255
 __device__ __forceinline__ uint64_t pack_record(int ext_copy, int lig_copy, int masked_n, int snp_count, uint32_t flags, uint32_t jc)
