@@ -222,3 +222,38 @@ def plant_scores(acc, scores: np.ndarray, window: Optional[int] = None) -> None:
         assert rc == 0, f"hipMemcpy failed: hipError_t {rc}"
     back, _ = acc.download(wi["first_candidate"], wi["n_candidates"])
     assert np.array_equal(back.view(np.uint64), scores.view(np.uint64)), "the downloaded scores are not the planted bits"
+
+
+REC_VALID_BIT = np.uint64(capi.FLAG_VALID << 48)
+REC_COPY_BITS = np.uint64(0xFFFFFFFF)
+
+
+def plant_records(acc, records: np.ndarray, window: Optional[int] = None) -> None:
+    """The twin of plant_scores for the records (uint64, one per dense candidate of the window scored last, in dense order): the second pointer of
+    mipgen_accel_result_device_ptrs, the same hipMemcpy through the library's own handle, the same read-back of the planted bits.
+
+    A planted record MAY change the SNP count, the masked-base count and the MAPPING flag: the condense fold reads all three from the record on
+    the device and in the oracle alike.  It must NOT change
+      the VALID bit       the single-wavefront replay kernels for more than 8 capture sizes derive it from the geometry (mip_bounds.h) while the
+                          oracle reads it from the record: a planted bit would compare two definitions of "constructed";
+      the copy fields     the device takes an arm's copy number from the record's two 16-bit fields unless one is saturated, the oracle from
+                          the region's copy table: drive copy numbers through capi.RegionData(copy=...) instead.
+    Both are asserted here against the records about to be overwritten."""
+    import ctypes as C
+    records = np.ascontiguousarray(records, dtype=np.uint64)
+    wi = acc.window_info(0 if window is None else window)
+    assert records.shape == (wi["n_candidates"],), (records.shape, wi)
+    acc.synchronize()
+    _, scored = acc.download(wi["first_candidate"], wi["n_candidates"])
+    assert np.array_equal(records & REC_VALID_BIT, scored & REC_VALID_BIT), "a planted record must keep the VALID bit as scored"
+    assert np.array_equal(records & REC_COPY_BITS, scored & REC_COPY_BITS), "a planted record must keep both copy fields as scored"
+    _, ptr = acc.result_device_ptrs()
+    if records.size:
+        assert ptr != 0
+        memcpy = acc.lib.hipMemcpy
+        memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        memcpy.restype = C.c_int
+        rc = memcpy(C.c_void_p(ptr), records.ctypes.data_as(C.c_void_p), records.nbytes, HIP_MEMCPY_HOST_TO_DEVICE)
+        assert rc == 0, f"hipMemcpy failed: hipError_t {rc}"
+    _, back = acc.download(wi["first_candidate"], wi["n_candidates"])
+    assert np.array_equal(back, records), "the downloaded records are not the planted bits"
