@@ -547,6 +547,46 @@ int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq
                                             int32_t max_indel, int32_t* counts, int32_t* anchors, mipgen_insertion_totals* totals);
 int mipgen_accel_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* records, int64_t n);
 
+/* ---- insertion alleles called against a background of the other samples (new entry points only: the ABI number does not change) ----
+ * Everything up to a row's allele records and its anchor table is the insertions call above, unchanged.  A record is TESTED material iff it is not ambiguous (so
+ * 1 <= length <= 15); ambiguous records are never tested and never pooled as an alt, but their molecules stay in `span`, so in every denominator.  For a tested
+ * record k = count and n = span of its anchor (n >= k >= 1).  Sample rows, qualification, leave-one-out, the filters, the score and the totals are those of the
+ * variant calls above with (k, n) so defined: sample row s' qualifies at allele a = (pos, length, bases) iff n' > 0 and k' 10^6 <= bg_max_ppm n', k' its count of
+ * exactly that allele (0 without such a record), n' its span at pos.  The POOL is sparse: S[pos] = the span summed over ALL sample rows, and per distinct
+ * non-ambiguous allele of any sample row one record with bg_alt = K = the k' of the qualifying rows and bg_excluded = X = the n' of the rows whose record does not
+ * qualify; N = S - X, and an allele no sample row carries has K = 0, N = S.  totals: tested = non-ambiguous records with min_depth <= n <= MIPGEN_CALL_MAX_DEPTH;
+ * too_deep = those above the cap; candidates; calls.  Call records come in ascending order of the allele key, the same bytes from call to call; bg_alt, bg_depth =
+ * K_o, N_o, the background without the row; reserved = 0.
+ *   insertion_call_tables:     from host arrays, no read session needed: records[n_records] as insertions_fetch returns them (strictly ascending key order; ambiguous
+ *                              ones are skipped), span[n_pos] the row's span per anchor, pool_records[n_pool] in strictly ascending key order, pool_span[n_pos] = S.
+ *   consensus_insertion_pool:  the insertions route of every sample row of the session, appended, sorted and reduced on the device.  The pool stays with the consensus
+ *                              reads and remembers these arguments; totals (may be NULL): rows = the sample rows, entries = their non-ambiguous records, alleles = the
+ *                              distinct ones.  The allele records the insertions call left on the handle are gone afterwards.
+ *   insertion_pool_fetch:      the distinct pool records (n must equal totals.alleles) and S (n_pos int32; either may be NULL).
+ *   consensus_insertion_call:  recomputes the insertions of `row` (any row, undetermined included) with the pool's arguments - counts, anchors, ins_totals (each may
+ *                              be NULL) are what mipgen_accel_reads_consensus_insertions returns for them, and mipgen_accel_insertions_fetch finds the row's
+ *                              records - then flags, scores, orders and joins its calls.
+ *   insertion_call_fetch:      the records of the last insertion call of either kind; n must equal its totals.calls.
+ * MIPGEN_E_INVALID: every refusal of the insertions call and of the call parameters; n_pos outside 1..2^29 - 1; n_records or n_pool negative or above 2^29 - 1; a
+ * record or pool position outside 0..n_pos - 1; records or pool not strictly ascending; a pool record with length outside 1..15; NULL arrays; a row of more than
+ * 2^29 - 1 allele records; a fetch with another n.  MIPGEN_E_STATE: no consensus reads; pool_fetch or consensus_insertion_call without a pool, or with
+ * params.bg_max_ppm different from the pool's; call_fetch before any insertion call.  MIPGEN_E_NOMEM: the bytes of the insertions call, 20 bytes per entry twice over and
+ * the sort's scratch, 4 bytes per position, and the candidate list of a call (one per record) against free device memory; each check comes before the allocations it
+ * covers.  The pileup, call, locus and insertions entry points, their records and timing indices 11-15 are untouched by these calls, except that the pool and the
+ * call count into the scratch of mipgen_accel_reads_consensus_insertions. */
+typedef struct mipgen_insertion_pool_record { int64_t pos; int32_t length; uint32_t bases; int32_t bg_alt, bg_excluded; } mipgen_insertion_pool_record;
+typedef struct mipgen_insertion_call_record { int64_t pos; int32_t length; uint32_t bases; int32_t depth, alt, bg_alt, bg_depth, q, reserved; } mipgen_insertion_call_record;
+typedef struct mipgen_insertion_pool_totals { int64_t rows, entries, alleles; } mipgen_insertion_pool_totals;
+int mipgen_accel_insertion_call_tables(mipgen_accel* h, const mipgen_insertion_record* records, int64_t n_records, const int32_t* span, int64_t n_pos,
+                                       const mipgen_insertion_pool_record* pool_records, int64_t n_pool, const int32_t* pool_span, int32_t own_row_is_sample,
+                                       const mipgen_call_params* params, mipgen_call_totals* totals);
+int mipgen_accel_reads_consensus_insertion_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                                int32_t max_indel, int32_t bg_max_ppm, mipgen_insertion_pool_totals* totals);
+int mipgen_accel_insertion_pool_fetch(mipgen_accel* h, mipgen_insertion_pool_record* pool_records, int64_t n, int32_t* pool_span);
+int mipgen_accel_reads_consensus_insertion_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, int32_t* anchors,
+                                                mipgen_insertion_totals* ins_totals, mipgen_call_totals* call_totals);
+int mipgen_accel_insertion_call_fetch(mipgen_accel* h, mipgen_insertion_call_record* records, int64_t n);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -763,7 +803,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * mipgen_accel_reads_consensus_pileup_gapped (timing enabled); 13 = the kernels of the last mipgen_accel_call_tables, mipgen_accel_reads_consensus_call (its pileup
  * included) or mipgen_accel_reads_consensus_call_pool (timing enabled); 14 = the kernels of the last locus call of any kind (mipgen_accel_locus_tables,
  * mipgen_accel_reads_consensus_locus_*), its pileup included (timing enabled); 15 = the kernels of the last mipgen_accel_reads_consensus_insertions, its
- * placement and count included (timing enabled). */
+ * placement and count included (timing enabled); 16 = the kernels of the last insertion pool or insertion call of either kind (mipgen_accel_insertion_call_tables,
+ * mipgen_accel_reads_consensus_insertion_pool, mipgen_accel_reads_consensus_insertion_call), the insertions route of its rows included (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -106,11 +106,18 @@ class LocusTotals(C.Structure):    # mipgen_locus_totals
     _fields_ = [(n, C.c_int64) for n in ("covered", "bases", "discordant", "deletions", "insertions", "ins_discordant")]
 
 
+class InsertionPoolTotals(C.Structure):    # mipgen_insertion_pool_totals
+    _fields_ = [(n, C.c_int64) for n in ("rows", "entries", "alleles")]
+
+
 class InsertionTotals(C.Structure):    # mipgen_insertion_totals
     _fields_ = [(n, C.c_int64) for n in ("groups", "used", "span", "insertions", "ins_discordant", "ambiguous", "alleles", "gapped_sides")]
 
 
 INSERTION_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("count", "<i4"), ("bases", "<u4"), ("ambiguous", "<i4")])   # mipgen_insertion_record, 24 bytes
+INSERTION_POOL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("bases", "<u4"), ("bg_alt", "<i4"), ("bg_excluded", "<i4")])   # mipgen_insertion_pool_record, 24 bytes
+INSERTION_CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("bases", "<u4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4"),
+                                        ("reserved", "<i4")])   # mipgen_insertion_call_record, 40 bytes
 CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("allele", "<i4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4")])   # mipgen_call_record
 CALL_MAX_DEPTH = 1 << 20
 
@@ -408,6 +415,16 @@ def load_library(path: Optional[str] = None):
                                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(InsertionTotals)]
     lib.mipgen_accel_insertions_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
     lib.mipgen_accel_insertions_fetch.restype = C.c_int
+    lib.mipgen_accel_insertion_call_tables.argtypes = [vp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32,
+                                                       C.POINTER(CallParams), C.POINTER(CallTotals)]
+    lib.mipgen_accel_reads_consensus_insertion_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                C.POINTER(InsertionPoolTotals)]
+    lib.mipgen_accel_insertion_pool_fetch.argtypes = [vp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    lib.mipgen_accel_reads_consensus_insertion_call.argtypes = [vp, C.c_int32, C.POINTER(CallParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(InsertionTotals),
+                                                                C.POINTER(CallTotals)]
+    lib.mipgen_accel_insertion_call_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
+    for name in ("insertion_call_tables", "reads_consensus_insertion_pool", "insertion_pool_fetch", "reads_consensus_insertion_call", "insertion_call_fetch"):
+        getattr(lib, "mipgen_accel_" + name).restype = C.c_int
     lib.mipgen_accel_call_tables.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CallParams),
                                              C.POINTER(CallTotals)]
     lib.mipgen_accel_reads_consensus_call_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -513,6 +530,8 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_locus_tables", "mipgen_accel_reads_consensus_locus_plan", "mipgen_accel_reads_consensus_locus_pileup",
     "mipgen_accel_reads_consensus_locus_call_pool", "mipgen_accel_reads_consensus_locus_call", "mipgen_accel_reads_consensus_locus_call_pileup_totals",
     "mipgen_accel_reads_consensus_insertions", "mipgen_accel_insertions_fetch",
+    "mipgen_accel_insertion_call_tables", "mipgen_accel_reads_consensus_insertion_pool", "mipgen_accel_insertion_pool_fetch",
+    "mipgen_accel_reads_consensus_insertion_call", "mipgen_accel_insertion_call_fetch",
 ]
 
 
@@ -1090,6 +1109,62 @@ class Accel:
         records = np.zeros(n, dtype=INSERTION_RECORD_DTYPE)
         self._check(self.lib.mipgen_accel_insertions_fetch(self.h, records.ctypes.data if n else None, n))
         return records
+
+    # insertion calls
+    def insertion_call_fetch(self, n: int) -> np.ndarray:
+        """mipgen_accel_insertion_call_fetch: the n records of the last insertion call of either kind as an array of INSERTION_CALL_RECORD_DTYPE, in ascending allele-key
+        order."""
+        records = np.zeros(n, dtype=INSERTION_CALL_RECORD_DTYPE)
+        self._check(self.lib.mipgen_accel_insertion_call_fetch(self.h, records.ctypes.data if n else None, n))
+        return records
+
+    def insertion_call_tables(self, records, span, pool_records, pool_span, own_row_is_sample: bool, params: "CallParams"):
+        """mipgen_accel_insertion_call_tables: insertion calls from host arrays, no read session needed.  records: INSERTION_RECORD_DTYPE in strictly
+        ascending key order, as insertions_fetch returns them; span: int32 [n_pos], the row's span per anchor; pool_records: INSERTION_POOL_RECORD_DTYPE in strictly
+        ascending key order; pool_span: int32 [n_pos], the span summed over the sample rows.  Returns (call records, totals dict: tested, too_deep, candidates, calls)."""
+        records = np.ascontiguousarray(records, dtype=INSERTION_RECORD_DTYPE)
+        pool_records = np.ascontiguousarray(pool_records, dtype=INSERTION_POOL_RECORD_DTYPE)
+        span = np.ascontiguousarray(span, dtype=np.int32)
+        pool_span = np.ascontiguousarray(pool_span, dtype=np.int32)
+        if span.ndim != 1 or span.shape != pool_span.shape:
+            raise ValueError(f"span {span.shape} and pool_span {pool_span.shape} do not match")
+        tot = CallTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_insertion_call_tables(self.h, records.ctypes.data if len(records) else None, len(records), span.ctypes.data_as(i32p), len(span),
+                                                                pool_records.ctypes.data if len(pool_records) else None, len(pool_records), pool_span.ctypes.data_as(i32p),
+                                                                int(bool(own_row_is_sample)), C.byref(params), C.byref(tot)))
+        return self.insertion_call_fetch(int(tot.calls)), self._totals(tot)
+
+    def consensus_insertion_pool(self, mol_seq, mol_len: Sequence[int], min_family: int = 1, min_quality: int = 0, max_indel: int = 8, bg_max_ppm: int = 200000) -> dict:
+        """mipgen_accel_reads_consensus_insertion_pool, callable after consensus_reads: the sparse background pool of insertion alleles over the sample rows of the
+        session.  Arguments as consensus_insertions takes them.  Returns the totals dict: rows, entries, alleles."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        tot = InsertionPoolTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_insertion_pool(self.h, seq, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), min_family, min_quality, max_indel,
+                                                                         bg_max_ppm, C.byref(tot)))
+        self._ins_call_positions = total
+        return self._totals(tot)
+
+    def insertion_pool_fetch(self, n: int):
+        """mipgen_accel_insertion_pool_fetch: (the n distinct records of the insertion pool as an array of INSERTION_POOL_RECORD_DTYPE in ascending key order, S - the
+        span per position summed over the sample rows - as int32 [n_pos])."""
+        records = np.zeros(n, dtype=INSERTION_POOL_RECORD_DTYPE)
+        span = np.zeros(getattr(self, "_ins_call_positions", 0), dtype=np.int32)
+        self._check(self.lib.mipgen_accel_insertion_pool_fetch(self.h, records.ctypes.data if n else None, n, span.ctypes.data_as(C.POINTER(C.c_int32)) if len(span) else None))
+        return records, span
+
+    def consensus_insertion_call(self, row: int, params: "CallParams"):
+        """mipgen_accel_reads_consensus_insertion_call, callable after consensus_insertion_pool: the insertion calls of one row against the pool.  Returns (counts,
+        anchors, insertion totals dict - what consensus_insertions returns for the pool's arguments -, call records, call totals dict); insertions_fetch finds the
+        row's allele records afterwards."""
+        total = getattr(self, "_ins_call_positions", 0)
+        counts = np.empty((total, 8), dtype=np.int32)
+        anchors = np.empty((total, 4), dtype=np.int32)
+        it, ct = InsertionTotals(), CallTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_reads_consensus_insertion_call(self.h, row, C.byref(params), counts.ctypes.data_as(i32p), anchors.ctypes.data_as(i32p), C.byref(it),
+                                                                         C.byref(ct)))
+        return counts, anchors, self._totals(it), self.insertion_call_fetch(int(ct.calls)), self._totals(ct)
 
     def call_fetch(self, n: int) -> np.ndarray:
         """mipgen_accel_call_fetch: the n records of the last call of either kind as an array of CALL_RECORD_DTYPE, in ascending (pos, allele)."""

@@ -249,6 +249,41 @@ struct InsScratch {
     void release() { count.release(); anchors.release(); ctr.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release();
                      records.release(); n_alleles = -1; }
 };
+// mipgen_accel_reads_consensus_insertion_pool: the sparse pool over the sample rows - S per position, keys and sums per distinct allele - and the
+// arguments it was built with (`args`: a PoolState whose dense pool stays unreserved); the entries and what orders them are held only while the pool is built.
+// Released with the reads.
+struct InsPool {
+    PoolState args;
+    DevBuf<int32_t> S;                                       // positions
+    DevBuf<uint64_t> pool_keys;                              // distinct alleles, ascending
+    DevBuf<InsPoolSums> pool_sums;
+    DevBuf<InsPoolCounters> ctr;
+    DevBuf<uint64_t> keys, keys_sorted;                      // entries (transient, as everything below)
+    DevBuf<InsPoolSums> sums;
+    DevBuf<uint32_t> ids, ids_sorted, run_start;
+    DevBuf<int32_t> run_counts;
+    DevBuf<char> temp;
+    int64_t n_pos = 0, rows = 0, n_entries = 0, n_alleles = 0;
+    size_t entry_held() const { return (keys.cap + keys_sorted.cap + pool_keys.cap) * 8 + (sums.cap + pool_sums.cap) * sizeof(InsPoolSums) +
+                                       (ids.cap + ids_sorted.cap + run_start.cap + run_counts.cap) * 4 + temp.cap; }
+    size_t table_held() const { return S.cap * 4 + ctr.cap * sizeof(InsPoolCounters); }
+    void release_transient() { keys.release(); keys_sorted.release(); sums.release(); ids.release(); ids_sorted.release(); run_start.release(); run_counts.release(); temp.release(); }
+    void release() { args.release(); release_transient(); S.release(); pool_keys.release(); pool_sums.release(); ctr.release(); n_pos = rows = n_entries = n_alleles = 0; }
+};
+// what an insertion call of either kind (mipgen_accel_insertion_call_tables too) leaves on the HANDLE: a CallRun of its own - mipgen_accel_call_fetch keeps finding the
+// last variant call -, the joined records, and the uploaded arrays of the tables call
+struct InsCallRun {
+    CallRun run;
+    DevBuf<mipgen_insertion_call_record> out;
+    DevBuf<mipgen_insertion_record> records;
+    DevBuf<int32_t> span, pool_span;
+    DevBuf<uint64_t> pool_keys;
+    DevBuf<InsPoolSums> pool_sums;
+    int64_t n_calls = -1;                                    // the records of the last insertion call (-1: none yet)
+    size_t held() const { return run.held() + out.cap * sizeof(mipgen_insertion_call_record) + records.cap * sizeof(mipgen_insertion_record) + (span.cap + pool_span.cap) * 4 +
+                                 pool_keys.cap * 8 + pool_sums.cap * sizeof(InsPoolSums); }
+    void release() { run.release(); out.release(); records.release(); span.release(); pool_span.release(); pool_keys.release(); pool_sums.release(); n_calls = -1; }
+};
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
     int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
@@ -256,12 +291,13 @@ struct ConsensusResult {
     CallScratch call;
     LocusScratch locus;
     InsScratch ins;
+    InsPool ins_pool;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); }
 };
 
 struct mipgen_accel {
@@ -390,6 +426,8 @@ struct mipgen_accel {
     LocusRun locus_run;              // the plan and tables of the last mipgen_accel_locus_tables (accel_pileup.hip)
     double locus_ms = -1.0;          // the kernels of the last locus call of any kind, its pileup included (timing enabled)
     double insertions_ms = -1.0;     // the kernels of the last mipgen_accel_reads_consensus_insertions (timing enabled)
+    InsCallRun ins_call;             // the last insertion call's candidates and records (accel_pileup.hip)
+    double ins_call_ms = -1.0;       // the kernels of the last insertion pool or insertion call of either kind (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -1,7 +1,8 @@
 // accel_pileup.hip — the two pileups read off the consensus reads a session left on the handle: allele counts per template position of one row (DESIGN 4.12:
 // mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped), the variant calls made from them (4.14: mipgen_accel_call_tables,
 // _reads_consensus_call_pool, _reads_consensus_call, _call_fetch) and the same per genome locus (4.15: mipgen_accel_locus_tables, _reads_consensus_locus_plan /
-// _locus_pileup / _locus_call_pool / _locus_call), and the insertion alleles of a row (4.16: mipgen_accel_reads_consensus_insertions, mipgen_accel_insertions_fetch).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
+// _locus_pileup / _locus_call_pool / _locus_call), and the insertion alleles of a row (4.16: mipgen_accel_reads_consensus_insertions, mipgen_accel_insertions_fetch) and their calls against a sparse pool over the sample rows (4.17: mipgen_accel_insertion_call_tables,
+// _reads_consensus_insertion_pool, _insertion_pool_fetch, _reads_consensus_insertion_call, _insertion_call_fetch).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
 // count_row is the ONE count: the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches of the plain
 // or the gapped table, download and totals of one row into the CountScratch it is given.  Every entry point gives a scratch of its own - `pile` / `gapped` of the
 // ConsensusResult, of its CallScratch, of its LocusScratch, of its InsScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
@@ -214,29 +215,27 @@ static size_t call_run_bytes(int64_t n_pos)
     return 2 * padded(c, sizeof(mipgen_call_record)) + 2 * padded(c, 8) + 2 * padded(c, 4) + padded(c * 6, 1) + padded(1, sizeof(CallCounters));
 }
 
-// The calls of one finished table on the device against pool and ref there: flag, one read of the candidate count, tail, sort, gather.  The stream is idle and
-// h->call_run.n_calls set on success.
-static int run_call(mipgen_accel* h, const int32_t* counts, int columns, const int32_t* pool, const uint8_t* ref, int64_t n_pos, bool own_row_is_sample,
-                    const mipgen_call_params& prm, SpanTimer& timer, mipgen_call_totals* totals)
+// What every call shares from its flag kernel to its ordered records, in the CallRun U it is given: `flag` lists the candidates (at most max_cand; their pos below
+// n_keys) into U.cand and counts them in U.ctr, then one read of the candidate count, tail, sort, gather.  The stream is idle and U.n_calls set on success.
+template <typename Flag>
+static int run_flagged(mipgen_accel* h, CallRun& U, int64_t n_keys, int64_t max_cand, const CallModel& M, SpanTimer& timer, mipgen_call_totals* totals, Flag flag)
 {
-    CallRun& U = h->call_run;
     U.n_calls = -1;
-    const CallModel M{prm.min_depth, prm.min_alt, prm.min_ppm, prm.min_q, prm.a0, prm.n0, prm.bg_max_ppm};
-    if (U.cand.reserve(4 * (size_t)n_pos) || U.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    if (U.cand.reserve((size_t)max_cand) || U.ctr.reserve(1)) return MIPGEN_E_NOMEM;
     hipStream_t st = h->stream;
     IdleOnExit idle{st};
     CallCounters cc;
     HIP_TRY(hipMemsetAsync(U.ctr.p, 0, sizeof cc, st));
     timer.mark();
-    HIP_TRY(mipgen_launch_call_flag(st, counts, columns, pool, ref, n_pos, own_row_is_sample ? 1 : 0, M, U.cand.p, U.ctr.p));
+    HIP_TRY(flag(U.cand.p, U.ctr.p));
     timer.mark();
     HIP_TRY(hipMemcpyAsync(&cc, U.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t n_cand = (int64_t)cc.candidates;
-    if (n_cand < 0 || n_cand > 4 * n_pos) return fail(MIPGEN_E_STATE, "call: %lld candidates listed of %lld positions", (long long)n_cand, (long long)n_pos);
+    if (n_cand < 0 || n_cand > max_cand) return fail(MIPGEN_E_STATE, "call: %lld candidates listed of %lld positions", (long long)n_cand, (long long)n_keys);
     if (n_cand > 0) {
-        int end_bit = 4;                                                 // the bits of the sentinel n_pos << 3, the largest key
-        while (end_bit < 64 && (((uint64_t)n_pos << 3) >> end_bit)) end_bit++;
+        int end_bit = 4;                                                 // the bits of the sentinel n_keys << 3, the largest key
+        while (end_bit < 64 && (((uint64_t)n_keys << 3) >> end_bit)) end_bit++;
         size_t temp_bytes = 0;
         HIP_TRY(mipgen_consensus_sort(st, nullptr, &temp_bytes, nullptr, nullptr, nullptr, nullptr, n_cand, end_bit));
         if (U.keys.reserve((size_t)n_cand) || U.keys_sorted.reserve((size_t)n_cand) || U.ids.reserve((size_t)n_cand) || U.ids_sorted.reserve((size_t)n_cand) ||
@@ -244,7 +243,7 @@ static int run_call(mipgen_accel* h, const int32_t* counts, int columns, const i
             return MIPGEN_E_NOMEM;
         temp_bytes = U.temp.cap;
         timer.mark();
-        HIP_TRY(mipgen_launch_call_tail(st, U.cand.p, n_cand, n_pos, M, U.keys.p, U.ids.p, U.ctr.p));
+        HIP_TRY(mipgen_launch_call_tail(st, U.cand.p, n_cand, n_keys, M, U.keys.p, U.ids.p, U.ctr.p));
         HIP_TRY(mipgen_consensus_sort(st, U.temp.p, &temp_bytes, U.keys.p, U.keys_sorted.p, U.ids.p, U.ids_sorted.p, n_cand, end_bit));
         HIP_TRY(mipgen_launch_call_gather(st, U.cand.p, U.ids_sorted.p, n_cand, U.ctr.p, U.records.p));
         timer.mark();
@@ -255,6 +254,19 @@ static int run_call(mipgen_accel* h, const int32_t* counts, int columns, const i
     U.n_calls = (int64_t)cc.calls;
     if (totals) *totals = {(int64_t)cc.tested, (int64_t)cc.too_deep, n_cand, (int64_t)cc.calls};
     return MIPGEN_OK;
+}
+
+static CallModel model_of(const mipgen_call_params& prm) { return {prm.min_depth, prm.min_alt, prm.min_ppm, prm.min_q, prm.a0, prm.n0, prm.bg_max_ppm}; }
+
+// The calls of one finished table on the device against pool and ref there, into h->call_run: k_call_flag, then the shared tail.
+static int run_call(mipgen_accel* h, const int32_t* counts, int columns, const int32_t* pool, const uint8_t* ref, int64_t n_pos, bool own_row_is_sample,
+                    const mipgen_call_params& prm, SpanTimer& timer, mipgen_call_totals* totals)
+{
+    const CallModel M = model_of(prm);
+    hipStream_t st = h->stream;
+    return run_flagged(h, h->call_run, n_pos, 4 * n_pos, M, timer, totals, [&](mipgen_call_record* cand, CallCounters* ctr) {
+        return mipgen_launch_call_flag(st, counts, columns, pool, ref, n_pos, own_row_is_sample ? 1 : 0, M, cand, ctr);
+    });
 }
 
 // the sample rows of a session: all but the last (undetermined) when it had barcodes, the one row otherwise
@@ -437,53 +449,25 @@ static int last_pileup_totals(mipgen_accel* h, bool locus, const char* none, mip
 }
 
 
-extern "C" {
-
-// Allele counts per template position of one row from the consensus reads the handle holds (DESIGN 4.12).  Reads R's groups and reads; writes R->pile only.
-int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, int32_t* counts,
-                                        mipgen_pileup_totals* totals)
+// ---- insertion alleles and their calls (4.17) ---------------------------------------------------------------------------------------------------
+// every refusal of a row whose insertions are asked for: A has need_seq, must_place and runs set
+static int plan_insertions(mipgen_accel* h, const RowArgs& A, int32_t row, RowPlan* P)
 {
-    RowPlan P;
-    const RowArgs A{nullptr, mol_len, n, min_family, min_quality, 0};
-    if (int rc = plan_row(h, A, row, &P)) return rc;
-    h->pileup_ms = -1.0;
-    SpanTimer pile_time{h->timing, h->stream};
-    mipgen_gapped_totals t;
-    Counted counted;
-    if (int rc = count_row(h, P, P.R->pile, Budget{"pileup"}, A, row, pile_time, counts, &t, &counted)) return rc;
-    if (totals) *totals = {t.groups, t.used, t.bases, t.discordant};
-    return booked(pile_time, &h->pileup_ms);
+    if (int rc = plan_row(h, A, row, P)) return rc;
+    if (P->n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: the insertion alleles take 2^29 - 1 at most", (long long)P->n_pos);
+    return MIPGEN_OK;
 }
 
-// The pileup with indels of one row (DESIGN 4.13).  Reads R's groups and reads; writes R->gapped only.
-int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
-                                               int32_t max_indel, int32_t* counts, mipgen_gapped_totals* totals)
+// The insertion alleles of one planned row into R->ins, the kernels spans of `timer`: the gapped count with five-plane projections, then - the events being its
+// `insertions` total - the anchor table and the events in one pass of the count frame, the keys sorted, their runs, and a record per run.  The anchor table and the
+// S.n_alleles records stay on the device (a session without groups leaves neither, and 0 records).  Reads R's groups and reads; writes R->ins only.
+static int insertions_row(mipgen_accel* h, const RowPlan& P, const RowArgs& A, int32_t row, SpanTimer& timer, int32_t* counts, int32_t* anchors,
+                          mipgen_insertion_totals* totals)
 {
-    RowPlan P;
-    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true};
-    if (int rc = plan_row(h, A, row, &P)) return rc;
-    h->gapped_ms = -1.0;
-    SpanTimer gap_time{h->timing, h->stream};
-    Counted counted;
-    if (int rc = count_row(h, P, P.R->gapped, Budget{"gapped pileup"}, A, row, gap_time, counts, totals, &counted)) return rc;
-    return booked(gap_time, &h->gapped_ms);
-}
-
-// Insertion alleles of one row: the gapped count with five-plane projections, then - the events being its `insertions` total - the anchor table and the
-// events in one pass of the count frame, the keys sorted, their runs, and a record per run.  Reads R's groups and reads; writes R->ins only.
-int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
-                                            int32_t max_indel, int32_t* counts, int32_t* anchors, mipgen_insertion_totals* totals)
-{
-    RowPlan P;
-    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
-    if (int rc = plan_row(h, A, row, &P)) return rc;
-    if (P.n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: the insertion alleles take 2^29 - 1 at most", (long long)P.n_pos);
     InsScratch& S = P.R->ins;
     S.n_alleles = -1;
-    h->insertions_ms = -1.0;
     const size_t np = (size_t)P.n_pos, cells = np * INSERTION_COLUMNS;
     hipStream_t st = h->stream;
-    SpanTimer timer{h->timing, st};
     mipgen_gapped_totals gt;
     Counted counted;
     const Budget B{"insertions", padded(cells, 4) + padded(1, sizeof(InsCounters)), S.table_held()};
@@ -492,7 +476,7 @@ int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq
         if (anchors) memset(anchors, 0, cells * sizeof(int32_t));
         if (totals) *totals = mipgen_insertion_totals{};
         S.n_alleles = 0;
-        return booked(timer, &h->insertions_ms);
+        return MIPGEN_OK;
     }
     const int64_t events = gt.insertions;
     if (events < 0 || events > 0x7fffffff) return fail(MIPGEN_E_INVALID, "insertions: %lld events in row %d: 2^31 - 1 at most", (long long)events, row);
@@ -540,6 +524,194 @@ int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq
     if ((int64_t)ic.alleles > events || (events > 0 && ic.alleles == 0)) return fail(MIPGEN_E_STATE, "insertions: %llu alleles of %lld events", ic.alleles, (long long)events);
     S.n_alleles = (int64_t)ic.alleles;
     if (totals) *totals = {gt.groups, gt.used, (int64_t)ic.span, events, (int64_t)ic.ins_discordant, (int64_t)ic.ambiguous, S.n_alleles, gt.gapped_sides};
+    return MIPGEN_OK;
+}
+
+// the first `used` elements of b kept while it grows to `want` (DevBuf::reserve lets go of what it held)
+template <typename T>
+static int grow_keeping(DevBuf<T>& b, size_t used, size_t want, hipStream_t st)
+{
+    if (want <= b.cap) return MIPGEN_OK;
+    DevBuf<T> bigger;
+    bigger.pool = b.pool;
+    if (bigger.reserve(want)) return MIPGEN_E_NOMEM;
+    if (used) {
+        const hipError_t e = hipMemcpyAsync(bigger.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
+        const hipError_t w = hipStreamSynchronize(st);
+        if (e != hipSuccess || w != hipSuccess) { bigger.release(); return fail(MIPGEN_E_HIP, "hipMemcpyAsync of %zu pool entries: %s", used, hipGetErrorString(e != hipSuccess ? e : w)); }
+    }
+    b.release();
+    b = bigger;
+    return MIPGEN_OK;
+}
+
+// what one entry of the pool takes while the pool is built: key and sorted key, sums, index and sorted index, and of its run the key, the sums, the length and the start
+static const size_t INS_POOL_ENTRY_BYTES = 3 * 8 + 2 * sizeof(InsPoolSums) + 4 * 4;
+
+// The sparse pool over the sample rows: the insertions route of every sample row, its spans added into S and its non-ambiguous records appended as entries;
+// then the entries sorted by key, their runs - the distinct alleles - and the sums of every run.  The caller has made its refusals and dropped the pool that was held.
+static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, int32_t bg_max_ppm, SpanTimer& timer)
+{
+    InsPool& Q = P.R->ins_pool;
+    InsScratch& I = P.R->ins;
+    hipStream_t st = h->stream;
+    const size_t np = (size_t)P.n_pos;
+    size_t room = 0;
+    if (int rc = room_beside(Q.table_held(), &room)) return rc;
+    if (padded(np, 4) + padded(1, sizeof(InsPoolCounters)) > room)
+        return fail(MIPGEN_E_NOMEM, "insertion pool: %lld template positions need %zu MiB of device memory beside the insertions', %zu MiB are free", (long long)P.n_pos,
+                    (padded(np, 4) + padded(1, sizeof(InsPoolCounters))) >> 20, room >> 20);
+    if (Q.S.reserve(np) || Q.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{st};
+    HIP_TRY(hipMemsetAsync(Q.S.p, 0, np * 4, st));
+    HIP_TRY(hipMemsetAsync(Q.ctr.p, 0, sizeof(InsPoolCounters), st));
+    InsPoolCounters pc{0, 0};
+    int64_t used = 0;
+    const int64_t rows = sample_rows(P.R);
+    for (int64_t r = 0; r < rows; r++) {
+        if (int rc = insertions_row(h, P, A, (int32_t)r, timer, nullptr, nullptr, nullptr)) return rc;
+        if (P.R->n_groups == 0) continue;                                // (nothing is on the device: S stays zero and there is no entry)
+        const int64_t n_rec = I.n_alleles;
+        if (used + n_rec > 0x7fffffff) return fail(MIPGEN_E_INVALID, "insertion pool: more than 2^31 - 1 allele records over the sample rows");
+        const size_t want = (size_t)(used + n_rec);
+        if (want > Q.keys.cap) {                                         // the entries' bytes, known only now: checked before they are allocated
+            const size_t need = padded(want, 8) + padded(want, sizeof(InsPoolSums)) + padded(want, 4);
+            if (int rc = room_beside(0, &room)) return rc;
+            if (need > room)
+                return fail(MIPGEN_E_NOMEM, "insertion pool: %zu entries need %zu MiB of device memory, %zu MiB are free", want, need >> 20, room >> 20);
+            if (int rc = grow_keeping(Q.keys, (size_t)used, want, st)) return rc;
+            if (int rc = grow_keeping(Q.sums, (size_t)used, want, st)) return rc;
+            if (int rc = grow_keeping(Q.ids, (size_t)used, want, st)) return rc;
+        }
+        timer.mark();
+        HIP_TRY(mipgen_launch_ins_pool_append(st, I.anchors.p, P.n_pos, I.records.p, n_rec, bg_max_ppm, Q.S.p, Q.keys.p, Q.sums.p, Q.ids.p, (int64_t)want, Q.ctr.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&pc, Q.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((int64_t)pc.entries < used || (int64_t)pc.entries > used + n_rec)
+            return fail(MIPGEN_E_STATE, "insertion pool: %llu entries after row %lld, %lld before it and %lld records", pc.entries, (long long)r, (long long)used, (long long)n_rec);
+        used = (int64_t)pc.entries;
+    }
+    I.n_alleles = -1;                                                    // (the records of the last sample row are no call's result)
+    if (used > 0) {
+        const size_t ne = (size_t)used;
+        size_t t_sort = 0, t_runs = 0, t_scan = 0;
+        HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, nullptr, nullptr, nullptr, nullptr, used, 64));
+        HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, nullptr, used, nullptr, nullptr, nullptr));
+        HIP_TRY(mipgen_consensus_scan_u32(st, nullptr, &t_scan, nullptr, nullptr, used));
+        size_t temp_bytes = std::max<size_t>(std::max(t_sort, std::max(t_runs, t_scan)), 1);
+        const size_t need = padded(ne, INS_POOL_ENTRY_BYTES) + padded(temp_bytes, 1);
+        if (int rc = room_beside(Q.entry_held(), &room)) return rc;
+        if (need > room)
+            return fail(MIPGEN_E_NOMEM, "insertion pool: %lld entries need %zu MiB of device memory, %zu MiB are free", (long long)used, need >> 20, room >> 20);
+        if (Q.keys_sorted.reserve(ne) || Q.ids_sorted.reserve(ne) || Q.pool_keys.reserve(ne) || Q.pool_sums.reserve(ne) || Q.run_counts.reserve(ne) || Q.run_start.reserve(ne) ||
+            Q.temp.reserve(temp_bytes))
+            return MIPGEN_E_NOMEM;
+        temp_bytes = Q.temp.cap;
+        timer.mark();
+        HIP_TRY(mipgen_consensus_sort(st, Q.temp.p, &temp_bytes, Q.keys.p, Q.keys_sorted.p, Q.ids.p, Q.ids_sorted.p, used, 64));
+        HIP_TRY(mipgen_consensus_runs(st, Q.temp.p, &temp_bytes, Q.keys_sorted.p, used, Q.pool_keys.p, Q.run_counts.p, &Q.ctr.p->alleles));
+        HIP_TRY(mipgen_consensus_scan_u32(st, Q.temp.p, &temp_bytes, Q.run_counts.p, Q.run_start.p, used));   // (beyond the runs the lengths are unwritten and the starts unread)
+        HIP_TRY(mipgen_launch_ins_pool_reduce(st, Q.run_counts.p, Q.run_start.p, &Q.ctr.p->alleles, used, Q.ids_sorted.p, Q.sums.p, Q.pool_sums.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&pc, Q.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(idle.wait());
+    if ((int64_t)pc.alleles > used || (used > 0 && pc.alleles == 0)) return fail(MIPGEN_E_STATE, "insertion pool: %llu alleles of %lld entries", pc.alleles, (long long)used);
+    Q.release_transient();
+    Q.n_pos = P.n_pos; Q.rows = rows; Q.n_entries = used; Q.n_alleles = (int64_t)pc.alleles;
+    PoolState& G = Q.args;
+    G.mol_len.assign(A.mol_len, A.mol_len + A.n);
+    G.mol_seq.assign(A.mol_seq, (size_t)P.n_pos);
+    G.min_family = A.min_family; G.min_quality = A.min_quality; G.max_indel = A.max_indel; G.bg_max_ppm = bg_max_ppm;
+    G.have = true;
+    return MIPGEN_OK;
+}
+
+// The insertion calls of n_rec allele records on the device (ascending; span[x * span_stride] the row's span of anchor x) against a sparse pool there, into
+// h->ins_call: k_ins_call_flag, the tail every call shares, and the join of the calls with their allele records.  The stream is idle and h->ins_call.n_calls set on
+// success.
+static int run_ins_call(mipgen_accel* h, const mipgen_insertion_record* records, int64_t n_rec, const int32_t* span, int span_stride, int64_t n_pos, const uint64_t* pool_keys,
+                        const InsPoolSums* pool_sums, int64_t n_pool, const int32_t* pool_span, bool own_row_is_sample, const mipgen_call_params& prm, SpanTimer& timer,
+                        mipgen_call_totals* totals)
+{
+    InsCallRun& V = h->ins_call;
+    V.n_calls = -1;
+    if (n_rec > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "insertion call: %lld allele records in the row: 2^29 - 1 at most", (long long)n_rec);
+    if (n_rec == 0) {
+        if (totals) *totals = mipgen_call_totals{};
+        V.n_calls = 0;
+        return MIPGEN_OK;
+    }
+    // flag, tail, sort, gather and join at the worst (every record a call): the list and the ordered records, two (key, slot) pairs per candidate, the sort's scratch
+    // (taken as call_run_bytes takes it) and the joined records
+    const size_t c = (size_t)n_rec;
+    const size_t need = 2 * padded(c, sizeof(mipgen_call_record)) + 2 * padded(c, 8) + 2 * padded(c, 4) + padded(c * 6, 1) + padded(1, sizeof(CallCounters)) +
+                        padded(c, sizeof(mipgen_insertion_call_record));
+    size_t room = 0;
+    if (int rc = room_beside(V.run.held() + V.out.cap * sizeof(mipgen_insertion_call_record), &room)) return rc;
+    if (need > room)
+        return fail(MIPGEN_E_NOMEM, "insertion call: %lld allele records need up to %zu MiB of device memory, %zu MiB are free", (long long)n_rec, need >> 20, room >> 20);
+    const CallModel M = model_of(prm);
+    hipStream_t st = h->stream;
+    if (int rc = run_flagged(h, V.run, n_rec, n_rec, M, timer, totals, [&](mipgen_call_record* cand, CallCounters* ctr) {
+            return mipgen_launch_ins_call_flag(st, records, n_rec, span, span_stride, n_pos, pool_keys, pool_sums, n_pool, pool_span, own_row_is_sample ? 1 : 0, M, cand, ctr);
+        })) return rc;
+    const int64_t n_calls = V.run.n_calls;
+    if (n_calls > 0) {
+        if (V.out.reserve((size_t)n_calls)) return MIPGEN_E_NOMEM;
+        IdleOnExit idle{st};
+        timer.mark();
+        HIP_TRY(mipgen_launch_ins_call_records(st, V.run.records.p, n_calls, records, n_rec, V.out.p));
+        timer.mark();
+        HIP_TRY(idle.wait());
+    }
+    V.n_calls = n_calls;
+    return MIPGEN_OK;
+}
+
+extern "C" {
+
+// Allele counts per template position of one row from the consensus reads the handle holds (DESIGN 4.12).  Reads R's groups and reads; writes R->pile only.
+int mipgen_accel_reads_consensus_pileup(mipgen_accel* h, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality, int32_t* counts,
+                                        mipgen_pileup_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{nullptr, mol_len, n, min_family, min_quality, 0};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
+    h->pileup_ms = -1.0;
+    SpanTimer pile_time{h->timing, h->stream};
+    mipgen_gapped_totals t;
+    Counted counted;
+    if (int rc = count_row(h, P, P.R->pile, Budget{"pileup"}, A, row, pile_time, counts, &t, &counted)) return rc;
+    if (totals) *totals = {t.groups, t.used, t.bases, t.discordant};
+    return booked(pile_time, &h->pileup_ms);
+}
+
+// The pileup with indels of one row (DESIGN 4.13).  Reads R's groups and reads; writes R->gapped only.
+int mipgen_accel_reads_consensus_pileup_gapped(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                               int32_t max_indel, int32_t* counts, mipgen_gapped_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
+    h->gapped_ms = -1.0;
+    SpanTimer gap_time{h->timing, h->stream};
+    Counted counted;
+    if (int rc = count_row(h, P, P.R->gapped, Budget{"gapped pileup"}, A, row, gap_time, counts, totals, &counted)) return rc;
+    return booked(gap_time, &h->gapped_ms);
+}
+
+// Insertion alleles of one row: insertions_row with a timer of its own.  Reads R's groups and reads; writes R->ins only.
+int mipgen_accel_reads_consensus_insertions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                            int32_t max_indel, int32_t* counts, int32_t* anchors, mipgen_insertion_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
+    if (int rc = plan_insertions(h, A, row, &P)) return rc;
+    h->insertions_ms = -1.0;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = insertions_row(h, P, A, row, timer, counts, anchors, totals)) return rc;
     return booked(timer, &h->insertions_ms);
 }
 
@@ -554,6 +726,146 @@ int mipgen_accel_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* reco
     if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemcpyAsync(records, S.records.p, (size_t)n * sizeof(mipgen_insertion_record), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MIPGEN_OK;
+}
+
+// Insertion calls from host arrays: no read session is needed; the arrays are uploaded into the handle's InsCallRun, the pool records as keys and sums.
+int mipgen_accel_insertion_call_tables(mipgen_accel* h, const mipgen_insertion_record* records, int64_t n_records, const int32_t* span, int64_t n_pos,
+                                       const mipgen_insertion_pool_record* pool_records, int64_t n_pool, const int32_t* pool_span, int32_t own_row_is_sample,
+                                       const mipgen_call_params* params, mipgen_call_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (int rc = check_call_params(params)) return rc;
+    if (n_pos < 1 || n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld positions: 1 to 2^29 - 1", (long long)n_pos);
+    if (n_records < 0 || n_records > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld allele records: 0 to 2^29 - 1", (long long)n_records);
+    if (n_pool < 0 || n_pool > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld pool records: 0 to 2^29 - 1", (long long)n_pool);
+    if (!span || !pool_span || (n_records && !records) || (n_pool && !pool_records)) return fail(MIPGEN_E_INVALID, "bad arguments: no records, no span, no pool records or no pool span");
+    uint64_t before = 0;
+    for (int64_t i = 0; i < n_records; i++) {
+        const mipgen_insertion_record& r = records[i];
+        if (r.pos < 0 || r.pos >= n_pos) return fail(MIPGEN_E_INVALID, "allele record %lld: position %lld of %lld", (long long)i, (long long)r.pos, (long long)n_pos);
+        if (r.length < 1 || (!r.ambiguous && r.length > GAP_ALLELE_MAX_LEN))
+            return fail(MIPGEN_E_INVALID, "allele record %lld: length %d (1 to %d bases are spelt out; a longer allele is ambiguous)", (long long)i, r.length, GAP_ALLELE_MAX_LEN);
+        const uint64_t key = gap_allele_key(r.pos, r.length, r.ambiguous != 0, r.bases);
+        if (i && key <= before) return fail(MIPGEN_E_INVALID, "allele record %lld: the records are not in strictly ascending key order", (long long)i);
+        before = key;
+    }
+    std::vector<uint64_t> keys((size_t)n_pool);
+    std::vector<InsPoolSums> sums((size_t)n_pool);
+    for (int64_t i = 0; i < n_pool; i++) {
+        const mipgen_insertion_pool_record& r = pool_records[i];
+        if (r.pos < 0 || r.pos >= n_pos) return fail(MIPGEN_E_INVALID, "pool record %lld: position %lld of %lld", (long long)i, (long long)r.pos, (long long)n_pos);
+        if (r.length < 1 || r.length > GAP_ALLELE_MAX_LEN) return fail(MIPGEN_E_INVALID, "pool record %lld: length %d: 1 to %d", (long long)i, r.length, GAP_ALLELE_MAX_LEN);
+        keys[(size_t)i] = ins_call_key(r.pos, r.length, r.bases);
+        if (i && keys[(size_t)i] <= keys[(size_t)i - 1]) return fail(MIPGEN_E_INVALID, "pool record %lld: the pool is not in strictly ascending key order", (long long)i);
+        sums[(size_t)i] = {r.bg_alt, r.bg_excluded};
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    InsCallRun& V = h->ins_call;
+    V.n_calls = -1;
+    h->ins_call_ms = -1.0;
+    const size_t np = (size_t)n_pos, nr = (size_t)n_records, nq = (size_t)n_pool;
+    const size_t need = 2 * padded(np, 4) + padded(nr, sizeof(mipgen_insertion_record)) + padded(nq, 8) + padded(nq, sizeof(InsPoolSums));
+    size_t room = 0;
+    if (int rc = room_beside(V.held() - V.run.held() - V.out.cap * sizeof(mipgen_insertion_call_record), &room)) return rc;
+    if (need > room)
+        return fail(MIPGEN_E_NOMEM, "insertion call: %lld positions, %lld allele records and %lld pool records need %zu MiB of device memory, %zu MiB are free", (long long)n_pos,
+                    (long long)n_records, (long long)n_pool, need >> 20, room >> 20);
+    if (V.span.reserve(np) || V.pool_span.reserve(np) || V.records.reserve(std::max<size_t>(nr, 1)) || V.pool_keys.reserve(std::max<size_t>(nq, 1)) ||
+        V.pool_sums.reserve(std::max<size_t>(nq, 1)))
+        return MIPGEN_E_NOMEM;
+    hipStream_t st = h->stream;
+    IdleOnExit idle{st};                                                 // (keys and sums outlive their copies)
+    HIP_TRY(hipMemcpyAsync(V.span.p, span, np * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(V.pool_span.p, pool_span, np * 4, hipMemcpyHostToDevice, st));
+    if (nr) HIP_TRY(hipMemcpyAsync(V.records.p, records, nr * sizeof(mipgen_insertion_record), hipMemcpyHostToDevice, st));
+    if (nq) HIP_TRY(hipMemcpyAsync(V.pool_keys.p, keys.data(), nq * 8, hipMemcpyHostToDevice, st));
+    if (nq) HIP_TRY(hipMemcpyAsync(V.pool_sums.p, sums.data(), nq * sizeof(InsPoolSums), hipMemcpyHostToDevice, st));
+    SpanTimer timer{h->timing, st};
+    if (int rc = run_ins_call(h, V.records.p, n_records, V.span.p, 1, n_pos, V.pool_keys.p, V.pool_sums.p, n_pool, V.pool_span.p, own_row_is_sample != 0, *params, timer, totals))
+        return rc;
+    return booked(timer, &h->ins_call_ms);
+}
+
+// The sparse pool over the sample rows of the session.  Writes R->ins_pool and, through the insertions route of every row, R->ins.
+int mipgen_accel_reads_consensus_insertion_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                                int32_t max_indel, int32_t bg_max_ppm, mipgen_insertion_pool_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
+    if (int rc = plan_insertions(h, A, 0, &P)) return rc;
+    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    InsPool& Q = P.R->ins_pool;
+    Q.args.drop();                                                       // (a pool that fails leaves none)
+    h->ins_call_ms = -1.0;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = build_ins_pool(h, P, A, bg_max_ppm, timer)) return rc;
+    if (totals) *totals = {Q.rows, Q.n_entries, Q.n_alleles};
+    return booked(timer, &h->ins_call_ms);
+}
+
+// The distinct records of the pool, in ascending key order, and S.
+int mipgen_accel_insertion_pool_fetch(mipgen_accel* h, mipgen_insertion_pool_record* pool_records, int64_t n, int32_t* pool_span)
+{
+    if (int rc = check_reads(h)) return rc;
+    const InsPool& Q = h->consensus->ins_pool;
+    if (!Q.args.have) return fail(MIPGEN_E_STATE, "the consensus reads have no insertion pool: mipgen_accel_reads_consensus_insertion_pool builds it");
+    if (n != Q.n_alleles) return fail(MIPGEN_E_INVALID, "%lld pool records asked: the insertion pool holds %lld", (long long)n, (long long)Q.n_alleles);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    std::vector<uint64_t> keys((size_t)n);
+    std::vector<InsPoolSums> sums((size_t)n);
+    {
+        IdleOnExit idle{st};
+        if (n && pool_records) {
+            HIP_TRY(hipMemcpyAsync(keys.data(), Q.pool_keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(sums.data(), Q.pool_sums.p, (size_t)n * sizeof(InsPoolSums), hipMemcpyDeviceToHost, st));
+        }
+        if (pool_span) HIP_TRY(hipMemcpyAsync(pool_span, Q.S.p, (size_t)Q.n_pos * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(idle.wait());
+    }
+    for (int64_t i = 0; pool_records && i < n; i++) {
+        const uint64_t key = keys[(size_t)i];
+        pool_records[i] = {gap_allele_pos(key), gap_allele_length(key), gap_allele_bases(key), sums[(size_t)i].K, sums[(size_t)i].X};
+    }
+    return MIPGEN_OK;
+}
+
+// The insertion calls of one row against the sparse pool: the row's insertions recomputed with the pool's arguments into R->ins, where
+// mipgen_accel_insertions_fetch finds its records, then flag, tail, order and join.
+int mipgen_accel_reads_consensus_insertion_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, int32_t* anchors,
+                                                mipgen_insertion_totals* ins_totals, mipgen_call_totals* call_totals)
+{
+    if (int rc = check_reads(h)) return rc;
+    const InsPool& Q = h->consensus->ins_pool;
+    if (!Q.args.have) return fail(MIPGEN_E_STATE, "the consensus reads have no insertion pool: mipgen_accel_reads_consensus_insertion_pool builds it");
+    RowPlan P;
+    RowArgs A;
+    if (int rc = plan_call(h, Q.args, row, params, "insertion pool", &A, &P)) return rc;
+    A.need_seq = A.must_place = A.runs = true;
+    h->ins_call_ms = -1.0;
+    h->ins_call.n_calls = -1;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = insertions_row(h, P, A, row, timer, counts, anchors, ins_totals)) return rc;
+    const InsScratch& I = P.R->ins;
+    if (int rc = run_ins_call(h, I.records.p, I.n_alleles, I.anchors.p, INSERTION_COLUMNS, P.n_pos, Q.pool_keys.p, Q.pool_sums.p, Q.n_alleles, Q.S.p,
+                              (int64_t)row < sample_rows(P.R), *params, timer, call_totals)) return rc;
+    return booked(timer, &h->ins_call_ms);
+}
+
+// The records of the last insertion call of either kind, in ascending allele-key order.
+int mipgen_accel_insertion_call_fetch(mipgen_accel* h, mipgen_insertion_call_record* records, int64_t n)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    const InsCallRun& V = h->ins_call;
+    if (V.n_calls < 0)
+        return fail(MIPGEN_E_STATE, "the handle holds no insertion calls: mipgen_accel_insertion_call_tables or mipgen_accel_reads_consensus_insertion_call leaves them");
+    if (n != V.n_calls) return fail(MIPGEN_E_INVALID, "%lld records asked: the last insertion call left %lld", (long long)n, (long long)V.n_calls);
+    if (n == 0) return MIPGEN_OK;
+    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(records, V.out.p, (size_t)n * sizeof(mipgen_insertion_call_record), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MIPGEN_OK;
 }

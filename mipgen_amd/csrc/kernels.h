@@ -6,6 +6,7 @@
 #include "common.h"
 #include "reads_common.h"
 #include "call_model.h"
+#include "insertion_call_model.h"
 
 struct HostConsts;                   // logistic_device.h: crosses the boundary by pointer only
 struct LrcMers { int8_t k[MIPGEN_N_LRC], code[MIPGEN_N_LRC], rc[MIPGEN_N_LRC]; };   // per mer: length, base-4 code, code of its reverse complement (-1: palindrome)
@@ -60,6 +61,9 @@ struct PileRow {
 // variant calls: what k_call_flag and k_call_tail count; the positions one call takes: 4 candidates per position stay below the 2^31 - 1 pairs of the sort
 struct CallCounters { unsigned long long tested, too_deep, candidates, calls; };
 #define MIPGEN_CALL_MAX_POSITIONS (((int64_t)1 << 29) - 1)
+
+// insertion calls: the entries appended to the sparse pool so far, its distinct alleles
+struct InsPoolCounters { unsigned long long entries, alleles; };
 
 // loci: the totals of a merged table, as k_locus_sum counts them
 struct LocusCounters { unsigned long long covered, bases, discordant, deletions, insertions, ins_discordant; };
@@ -189,6 +193,18 @@ hipError_t mipgen_launch_call_flag(hipStream_t, const int32_t* counts, int colum
                                    const CallModel& P, mipgen_call_record* cand, CallCounters* ctr);
 hipError_t mipgen_launch_call_tail(hipStream_t, mipgen_call_record* cand, int64_t n_cand, int64_t n_pos, const CallModel& P, uint64_t* keys, uint32_t* ids, CallCounters* ctr);
 hipError_t mipgen_launch_call_gather(hipStream_t, const mipgen_call_record* cand, const uint32_t* ids, int64_t n_cand, const CallCounters* ctr, mipgen_call_record* records);
+// kernels_insertion_call.hip: one sample row's spans and non-ambiguous alleles into the sparse pool (S zero before the first row, ctr zero on entry; at most
+// cap entries are written); the sums of the runs of the sorted entries; the candidates of a row's allele records against the pool (cand: n_records records, ctr zero
+// on entry; a candidate's pos is its record's index); the calls joined with their allele records
+hipError_t mipgen_launch_ins_pool_append(hipStream_t, const int32_t* anchors, int64_t n_pos, const mipgen_insertion_record* records, int64_t n_records, int32_t bg_max_ppm,
+                                         int32_t* S, uint64_t* keys, InsPoolSums* sums, uint32_t* ids, int64_t cap, InsPoolCounters* ctr);
+hipError_t mipgen_launch_ins_pool_reduce(hipStream_t, const int32_t* run_counts, const uint32_t* run_start, const unsigned long long* n_runs, int64_t n_entries,
+                                         const uint32_t* ids_sorted, const InsPoolSums* entry_sums, InsPoolSums* pool_sums);
+hipError_t mipgen_launch_ins_call_flag(hipStream_t, const mipgen_insertion_record* records, int64_t n_records, const int32_t* span, int span_stride, int64_t n_pos,
+                                       const uint64_t* pool_keys, const InsPoolSums* pool_sums, int64_t n_pool, const int32_t* pool_span, int own_row_is_sample,
+                                       const CallModel& P, mipgen_call_record* cand, CallCounters* ctr);
+hipError_t mipgen_launch_ins_call_records(hipStream_t, const mipgen_call_record* calls, int64_t n_calls, const mipgen_insertion_record* records, int64_t n_records,
+                                          mipgen_insertion_call_record* out);
 // kernels_locus.hip: the (locus, x) pairs of a plan for the sort; src[n_pos] and first[n_loci + 1] from the sorted pairs; a count table folded into
 // merged[n_loci][columns] and its totals (ctr zero on entry)
 hipError_t mipgen_launch_locus_keys(hipStream_t, const int64_t* plan, int64_t n_pos, int64_t n_loci, uint64_t* keys, uint32_t* ids);

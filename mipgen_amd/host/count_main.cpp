@@ -51,6 +51,12 @@
 //                           `length` times N for the molecules whose inserted bases could not be told; span = the molecules that cover the anchor with one agreed
 //                           length, 0 included; ppm = floor(count 10^6 / span)
 //   stderr     a last line: "mipgen_count: insertion alleles A events I ambiguous B span S"
+//   -call_insertions ICALLS needs -pileup_insertions: the insertion alleles of every row called against a background of the other samples, under the
+//                           -call_* options.  One pool call, then one insertion call per row (undetermined too) that takes the place of the insertions call: FILE
+//                           and INS are byte for byte what they are without the option.  Header ">sample <tab> mip_key <tab> chr <tab> position <tab> strand <tab>
+//                           length <tab> inserted <tab> depth <tab> alt_count <tab> alt_ppm <tab> bg_alt <tab> bg_depth <tab> q"; one line per call in row, table and
+//                           record order; position, strand and inserted as in INS; depth = the span of the anchor; alt_ppm = floor(alt_count 10^6 / depth)
+//   stderr     a last line: "mipgen_count: insertion calls C candidates K tested P too_deep D"
 // Variant calls from the pileup against a background of the other samples (without -call every byte written is what it was):
 //   -call CALLS             needs -pileup and uses -pileup_min_family, -pileup_min_quality and -pileup_indels as given: one pool over the sample rows, then one call per
 //                           row (undetermined too) that feeds BOTH files - FILE is byte for byte what it is without -call.  Header
@@ -105,6 +111,7 @@ static int usage(const std::string& msg)
             "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n"
             "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n"
             "-pileup_insertions file : with -pileup_indels, the inserted bases per anchor: length, bases, molecules, spanning molecules and ppm per allele\n"
+            "-call_insertions file : with -pileup_insertions, the insertion alleles of every sample called against the background of the others, under the -call_* options\n"
             "-call file : with -pileup, variant calls of every sample against the background of the others; -call_min_depth n (default 20), -call_min_alt k (3), -call_min_ppm p (0),\n"
             "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n"
             "-pileup_loci file : with -pileup, the counts per genome base, summed over the probes that cover it; -loci_parts target|all : what of a probe counts (default target)\n"
@@ -210,7 +217,7 @@ int main(int argc, char** argv)
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
     long min_family = 1, pile_family = 1, pile_quality = 0, pile_indels = 0;
     bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
-    std::string consensus_prefix, pileup_path, call_path, ins_path;
+    std::string consensus_prefix, pileup_path, call_path, ins_path, call_ins_path;
     mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
     bool call_option_given = false, loci_parts_given = false, loci_all = false;
     std::string loci_path, call_loci_path;
@@ -249,6 +256,7 @@ int main(int argc, char** argv)
         else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
         else if (a == "-pileup_indels") { if (!svr_parse_int(v.c_str(), &pile_indels) || pile_indels < 1 || pile_indels > 15) return usage("-pileup_indels must be 1 to 15"); }
         else if (a == "-pileup_insertions") { if (v.empty()) return usage("-pileup_insertions takes a file"); ins_path = v; }
+        else if (a == "-call_insertions") { if (v.empty()) return usage("-call_insertions takes a file"); call_ins_path = v; }
         else if (a == "-call") { if (v.empty()) return usage("-call takes a file"); call_path = v; }
         else if (a == "-pileup_loci") { if (v.empty()) return usage("-pileup_loci takes a file"); loci_path = v; }
         else if (a == "-call_loci") { if (v.empty()) return usage("-call_loci takes a file"); call_loci_path = v; }
@@ -291,7 +299,9 @@ int main(int argc, char** argv)
     const bool loci = !loci_path.empty(), call_loci = !call_loci_path.empty();
     if (loci && !pileup) return usage("-pileup_loci needs -pileup file");
     if ((call_loci || loci_parts_given) && !loci) return usage("-call_loci and -loci_parts need -pileup_loci file");
-    if (call_option_given && !call && !call_loci) return usage("the -call_* options need -call file or -call_loci file");
+    const bool call_ins = !call_ins_path.empty();
+    if (call_ins && !insertions) return usage("-call_insertions needs -pileup_insertions file");
+    if (call_option_given && !call && !call_loci && !call_ins) return usage("the -call_* options need -call file or -call_loci file");
     if (pileup && te + tl == 0) return usage("-pileup needs tag bases: with -tag_sizes 0,0 there are no molecules to count");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
@@ -411,6 +421,8 @@ int main(int argc, char** argv)
     if (pileup && !(pile_out = fopen(pileup_path.c_str(), "w"))) return usage("-pileup " + pileup_path + ": can't write " + pileup_path);
     FILE* ins_out = nullptr;
     if (insertions && !(ins_out = fopen(ins_path.c_str(), "w"))) return usage("-pileup_insertions " + ins_path + ": can't write " + ins_path);
+    FILE* call_ins_out = nullptr;
+    if (call_ins && !(call_ins_out = fopen(call_ins_path.c_str(), "w"))) return usage("-call_insertions " + call_ins_path + ": can't write " + call_ins_path);
     FILE* call_out = nullptr;
     if (call && !(call_out = fopen(call_path.c_str(), "w"))) return usage("-call " + call_path + ": can't write " + call_path);
     FILE *loci_out = nullptr, *call_loci_out = nullptr;
@@ -510,6 +522,7 @@ int main(int argc, char** argv)
     long long call_calls = 0, call_cands = 0, call_tested = 0, call_deep = 0;
     long long loci_lines = 0, loci_bases = 0, loci_nonref = 0, loci_disc = 0, lcall_calls = 0, lcall_cands = 0, lcall_tested = 0, lcall_deep = 0;
     long long ins_alleles = 0, ins_events = 0, ins_amb = 0, ins_span = 0;
+    long long icall_calls = 0, icall_cands = 0, icall_tested = 0, icall_deep = 0;
     const size_t pile_cols = pile_indels ? 8 : 5;
     if (pileup) {
         int64_t n_pos = 0;
@@ -560,28 +573,61 @@ int main(int argc, char** argv)
         // -pileup_insertions: the records of a row (ascending anchor, so table order) as lines; span comes from the anchor table of the row
         std::vector<int32_t> ianch[2] = {std::vector<int32_t>(insertions ? (size_t)n_pos * 4 : 0), std::vector<int32_t>(insertions && n_rows > 1 ? (size_t)n_pos * 4 : 0)};
         std::vector<mipgen_insertion_record> irecs[2];
+        // what a line of INS and a line of ICALLS share of an allele: sample, mip_key, chr, position, strand, length and the inserted bases, appended to *text
+        auto append_allele = [&](const char* sample, int64_t pos, int32_t length, uint32_t bases, bool ambiguous, std::string* text) {
+            const size_t i = (size_t)(std::upper_bound(pos_off.begin(), pos_off.end(), pos) - pos_off.begin()) - 1;
+            const std::vector<std::string>& f = *rows[i];
+            const RowCoords& c = coords[i];
+            const long t = (long)(pos - pos_off[i]);
+            std::string inserted((size_t)length, 'N');
+            if (!ambiguous)
+                for (int j = 0; j < length; j++) {                                       // base j of the molecule; on a '-' probe the plus strand reads it from the far end, complemented
+                    const unsigned code = (bases >> (2 * (length - 1 - j))) & 3u;
+                    if (c.minus) inserted[(size_t)(length - 1 - j)] = "TGCA"[code]; else inserted[(size_t)j] = "ACGT"[code];
+                }
+            char buf[120];
+            snprintf(buf, sizeof buf, "\t%ld\t%c\t%d\t", c.minus ? c.ext_stop - (t + 1) : c.ext_start + t, c.minus ? '-' : '+', length);
+            text->append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf).append(inserted);
+        };
         auto write_insertions = [&](size_t r, const std::vector<int32_t>& anch, const std::vector<mipgen_insertion_record>& rec) {
             const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
-            std::string text, inserted;
+            std::string text;
             char buf[120];
             for (const mipgen_insertion_record& q : rec) {
-                const size_t i = (size_t)(std::upper_bound(pos_off.begin(), pos_off.end(), q.pos) - pos_off.begin()) - 1;
-                const std::vector<std::string>& f = *rows[i];
-                const RowCoords& c = coords[i];
-                const long t = (long)(q.pos - pos_off[i]);
-                inserted.assign((size_t)q.length, 'N');
-                if (!q.ambiguous)
-                    for (int j = 0; j < q.length; j++) {                                 // base j of the molecule; on a '-' probe the plus strand reads it from the far end, complemented
-                        const unsigned code = (q.bases >> (2 * (q.length - 1 - j))) & 3u;
-                        if (c.minus) inserted[(size_t)(q.length - 1 - j)] = "TGCA"[code]; else inserted[(size_t)j] = "ACGT"[code];
-                    }
+                append_allele(sample, q.pos, q.length, q.bases, q.ambiguous != 0, &text);
                 const int32_t span = anch[(size_t)q.pos * 4];
-                snprintf(buf, sizeof buf, "\t%ld\t%c\t%d\t", c.minus ? c.ext_stop - (t + 1) : c.ext_start + t, c.minus ? '-' : '+', q.length);
-                text.append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf).append(inserted);
                 snprintf(buf, sizeof buf, "\t%d\t%d\t%lld\n", q.count, span, (long long)q.count * 1000000ll / span);
                 text.append(buf);
             }
             fwrite(text.data(), 1, text.size(), ins_out);
+        };
+        // -call_insertions: the call records of a row (ascending allele key, so table order) as lines
+        std::vector<mipgen_insertion_call_record> icrecs[2];
+        auto write_insertion_calls = [&](size_t r, const std::vector<mipgen_insertion_call_record>& rec) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text;
+            char buf[160];
+            for (const mipgen_insertion_call_record& q : rec) {
+                append_allele(sample, q.pos, q.length, q.bases, false, &text);
+                snprintf(buf, sizeof buf, "\t%d\t%d\t%lld\t%d\t%d\t%d\n", q.depth, q.alt, (long long)q.alt * 1000000ll / q.depth, q.bg_alt, q.bg_depth, q.q);
+                text.append(buf);
+            }
+            fwrite(text.data(), 1, text.size(), call_ins_out);
+        };
+        // the insertions of a row, for INS (and FILE, when counts is not NULL): the insertions call, or under -call_insertions the insertion call, which returns the same
+        auto row_insertions = [&](size_t r, int32_t* counts, mipgen_insertion_totals* it) {
+            int prc;
+            if (call_ins) {
+                mipgen_call_totals ict{0, 0, 0, 0};
+                prc = mipgen_accel_reads_consensus_insertion_call(h, (int32_t)r, &call_prm, counts, ianch[r & 1].data(), it, &ict);
+                if (prc == MIPGEN_OK) { icrecs[r & 1].resize((size_t)ict.calls); prc = mipgen_accel_insertion_call_fetch(h, icrecs[r & 1].data(), ict.calls); }
+                if (prc == MIPGEN_OK) { icall_calls += ict.calls; icall_cands += ict.candidates; icall_tested += ict.tested; icall_deep += ict.too_deep; }
+            } else
+                prc = mipgen_accel_reads_consensus_insertions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
+                                                              (int32_t)pile_indels, counts, ianch[r & 1].data(), it);
+            if (prc == MIPGEN_OK) { irecs[r & 1].resize((size_t)it->alleles); prc = mipgen_accel_insertions_fetch(h, irecs[r & 1].data(), it->alleles); }
+            if (prc == MIPGEN_OK) { ins_alleles += it->alleles; ins_events += it->insertions; ins_amb += it->ambiguous; ins_span += it->span; }
+            return prc;
         };
         // -call: the records of a row (ascending position, then allele class) as lines; within a position the printed alts go A C G T -, which on a '-' probe is
         // the reverse of the class order of the four bases
@@ -665,6 +711,11 @@ int main(int argc, char** argv)
                                                        call_prm.bg_max_ppm) != MIPGEN_OK) return die();
         }
         if (insertions) fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tinserted\tcount\tspan\tppm\n", ins_out);
+        if (call_ins) {
+            fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tinserted\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\n", call_ins_out);
+            if (mipgen_accel_reads_consensus_insertion_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
+                                                            call_prm.bg_max_ppm, nullptr) != MIPGEN_OK) return die();
+        }
         fputs(pile_indels ? ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n"
                           : ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
         std::thread writer;
@@ -702,13 +753,8 @@ int main(int argc, char** argv)
                 lcall_calls += lct.calls; lcall_cands += lct.candidates; lcall_tested += lct.tested; lcall_deep += lct.too_deep;
             } else if (insertions) {                                                     // one insertions call per row feeds FILE and INS: its counts are the gapped pileup's
                 mipgen_insertion_totals it;
-                prc = mipgen_accel_reads_consensus_insertions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
-                                                              (int32_t)pile_indels, table[r & 1].data(), ianch[r & 1].data(), &it);
-                if (prc == MIPGEN_OK) { irecs[r & 1].resize((size_t)it.alleles); prc = mipgen_accel_insertions_fetch(h, irecs[r & 1].data(), it.alleles); }
-                if (prc == MIPGEN_OK) {
-                    gt.used = it.used; gt.gapped_sides = it.gapped_sides;
-                    ins_alleles += it.alleles; ins_events += it.insertions; ins_amb += it.ambiguous; ins_span += it.span;
-                }
+                prc = row_insertions(r, table[r & 1].data(), &it);
+                if (prc == MIPGEN_OK) { gt.used = it.used; gt.gapped_sides = it.gapped_sides; }
             } else
             prc = pile_indels ? mipgen_accel_reads_consensus_pileup_gapped(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
                                                                                      (int32_t)pile_quality, (int32_t)pile_indels, table[r & 1].data(), &gt)
@@ -716,10 +762,7 @@ int main(int argc, char** argv)
                                                                               table[r & 1].data(), &pt);
             if (insertions && (call || loci) && prc == MIPGEN_OK) {                      // beside -call or -pileup_loci: the insertions call of the row feeds INS only
                 mipgen_insertion_totals it;
-                prc = mipgen_accel_reads_consensus_insertions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
-                                                              (int32_t)pile_indels, nullptr, ianch[r & 1].data(), &it);
-                if (prc == MIPGEN_OK) { irecs[r & 1].resize((size_t)it.alleles); prc = mipgen_accel_insertions_fetch(h, irecs[r & 1].data(), it.alleles); }
-                if (prc == MIPGEN_OK) { ins_alleles += it.alleles; ins_events += it.insertions; ins_amb += it.ambiguous; ins_span += it.span; }
+                prc = row_insertions(r, nullptr, &it);
             }
             if (pile_indels) { pt.used = gt.used; pile_gapped += gt.gapped_sides; }
             if (writer.joinable()) writer.join();
@@ -730,11 +773,13 @@ int main(int argc, char** argv)
                 if (call) write_calls(r, recs[r & 1]);
                 if (loci) write_loci(r, ltable[r & 1], lrecs[r & 1]);
                 if (insertions) write_insertions(r, ianch[r & 1], irecs[r & 1]);
+                if (call_ins) write_insertion_calls(r, icrecs[r & 1]);
             });
         }
         if (writer.joinable()) writer.join();
         if (fclose(pile_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, pileup_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (insertions && fclose(ins_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, ins_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (call_ins && fclose(call_ins_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_ins_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call && fclose(call_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (loci && fclose(loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call_loci && fclose(call_loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
@@ -821,5 +866,6 @@ int main(int argc, char** argv)
     if (loci) fprintf(stderr, "%s: loci %zu lines %lld bases %lld nonref %lld discordant %lld\n", PROG, lplan.locus_pos.size(), loci_lines, loci_bases, loci_nonref, loci_disc);
     if (call_loci) fprintf(stderr, "%s: locus calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, lcall_calls, lcall_cands, lcall_tested, lcall_deep);
     if (insertions) fprintf(stderr, "%s: insertion alleles %lld events %lld ambiguous %lld span %lld\n", PROG, ins_alleles, ins_events, ins_amb, ins_span);
+    if (call_ins) fprintf(stderr, "%s: insertion calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, icall_calls, icall_cands, icall_tested, icall_deep);
     return 0;
 }
