@@ -101,6 +101,35 @@ struct DevBuf {
         p = nullptr; cap = 0;
     }
 };
+static inline size_t padded(size_t count, size_t size) { return (count + count / 8 + 64) * size; }      // (what DevBuf::reserve asks for at most)
+
+// (key, id) pairs and their sorted copies, with the ONE scratch of mipgen_consensus_sort and of the runs and scans that follow it on the same pairs (kernels_consensus.hip).
+// Whoever orders something on the device holds one of these: a budget takes bytes(), and every use is told the whole scratch, so no caller sees a temp_bytes.
+struct SortedPairs {
+    DevBuf<uint64_t> keys, keys_sorted;
+    DevBuf<uint32_t> ids, ids_sorted;
+    DevBuf<char> temp;
+    size_t held() const { return (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap) * 4 + temp.cap; }
+    void release() { keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release(); }
+    static size_t bytes(size_t n, size_t scratch) { return 2 * padded(n, 8) + 2 * padded(n, 4) + padded(scratch, 1); }     // what reserve(n, scratch) asks for at most
+    // *scratch: what a sort of n pairs over end_bit key bits takes and, on the same scratch, the runs of n_runs keys and a u32 scan over n_scan (0: not asked for); 1 at least
+    static hipError_t scratch_bytes(hipStream_t st, int64_t n, int end_bit, int64_t n_runs, int64_t n_scan, size_t* scratch)
+    {
+        size_t t_sort = 0, t_runs = 0, t_scan = 0;
+        hipError_t e = mipgen_consensus_sort(st, nullptr, &t_sort, nullptr, nullptr, nullptr, nullptr, n, end_bit);
+        if (e == hipSuccess && n_runs) e = mipgen_consensus_runs(st, nullptr, &t_runs, nullptr, n_runs, nullptr, nullptr, nullptr);
+        if (e == hipSuccess && n_scan) e = mipgen_consensus_scan_u32(st, nullptr, &t_scan, nullptr, nullptr, n_scan);
+        *scratch = std::max<size_t>(std::max(t_sort, std::max(t_runs, t_scan)), 1);
+        return e;
+    }
+    int reserve(size_t n, size_t scratch) { return keys.reserve(n) || keys_sorted.reserve(n) || ids.reserve(n) || ids_sorted.reserve(n) || temp.reserve(scratch) ? MIPGEN_E_NOMEM : MIPGEN_OK; }
+    // keys / ids [0, n) into keys_sorted / ids_sorted, ascending by the low end_bit bits of the key; the runs of keys_sorted[0, n): the key and the length of each and their
+    // number (keys and ids are free once sorted, and may take the first two); exclusive sums.  Each is told the whole scratch.
+    hipError_t sort(hipStream_t st, int64_t n, int end_bit) { size_t all = temp.cap; return mipgen_consensus_sort(st, temp.p, &all, keys.p, keys_sorted.p, ids.p, ids_sorted.p, n, end_bit); }
+    hipError_t runs(hipStream_t st, int64_t n, uint64_t* run_keys, int32_t* run_counts, unsigned long long* n_runs) { size_t all = temp.cap; return mipgen_consensus_runs(st, temp.p, &all, keys_sorted.p, n, run_keys, run_counts, n_runs); }
+    hipError_t scan_u32(hipStream_t st, const int32_t* in, uint32_t* out, int64_t n) { size_t all = temp.cap; return mipgen_consensus_scan_u32(st, temp.p, &all, in, out, n); }
+    hipError_t scan_i64(hipStream_t st, const int64_t* in, int64_t* out, int64_t n) { size_t all = temp.cap; return mipgen_consensus_scan_i64(st, temp.p, &all, in, out, n); }
+};
 
 // two pinned host chunks + their "copy finished" events: large tables cross PCIe as they are packed / unpacked, chunk by chunk
 template <typename T>
@@ -163,14 +192,18 @@ struct CountScratch {
     size_t held() const { return row.held() + counts.cap * 4 + proj_off.cap * 8 + list.cap * 4 + mol_seq.cap + need.cap + proj.cap + ctr.cap * sizeof(GappedCounters); }
     void release() { row.release(); counts.release(); proj_off.release(); list.release(); mol_seq.release(); need.release(); proj.release(); ctr.release(); }
 };
-// A background pool over the sample rows, the arguments it was built with - a call recomputes its row with them - and the pileup totals of the
-// row called last
-struct PoolState {
+// The arguments a pool over the sample rows was built with: a call recomputes its row with them.  remember() is what a builder ends with (accel_pileup.hip, beside RowArgs)
+struct RowArgs;
+struct PoolArgs {
     bool have = false;                                       // a pool is held
-    DevBuf<int32_t> pool;                                    // positions or loci x (K[5], N[5])
     std::vector<int32_t> mol_len;
     std::string mol_seq;                                     // (empty: the pool was built without template bases)
     int32_t min_family = 1, min_quality = 0, max_indel = 0, bg_max_ppm = 0;
+    void remember(const RowArgs& A, int64_t n_pos, int32_t bg_max_ppm_);
+};
+// A dense background pool, its arguments and the pileup totals of the row called last
+struct PoolState : PoolArgs {
+    DevBuf<int32_t> pool;                                    // positions or loci x (K[5], N[5])
     mipgen_gapped_totals last{0, 0, 0, 0, 0, 0, 0, 0};        // the pileup totals of the row called last
     bool have_last = false;
     void drop() { have = have_last = false; }
@@ -188,29 +221,23 @@ struct CallScratch {
 // what a call of either kind (mipgen_accel_call_tables too) leaves on the HANDLE: the candidate list, the sort's buffers and the ordered records of the last call
 struct CallRun {
     DevBuf<mipgen_call_record> cand, records;                // 4 per position at most; the candidates of the call
-    DevBuf<uint64_t> keys, keys_sorted;
-    DevBuf<uint32_t> ids, ids_sorted;
-    DevBuf<char> temp;
+    SortedPairs pairs;                                       // (key, slot) of every candidate
     DevBuf<CallCounters> ctr;
     DevBuf<int32_t> counts, pool;                            // the uploaded arrays of mipgen_accel_call_tables
     DevBuf<uint8_t> ref;
     int64_t n_calls = -1;                                    // the records of the last call (-1: none yet)
-    size_t held() const { return (cand.cap + records.cap) * sizeof(mipgen_call_record) + (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap) * 4 + temp.cap +
-                                 ctr.cap * sizeof(CallCounters) + (counts.cap + pool.cap) * 4 + ref.cap; }
-    void release() { cand.release(); records.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release(); ctr.release();
-                     counts.release(); pool.release(); ref.release(); n_calls = -1; }
+    size_t held() const { return (cand.cap + records.cap) * sizeof(mipgen_call_record) + pairs.held() + ctr.cap * sizeof(CallCounters) + (counts.cap + pool.cap) * 4 + ref.cap; }
+    void release() { cand.release(); records.release(); pairs.release(); ctr.release(); counts.release(); pool.release(); ref.release(); n_calls = -1; }
 };
 // loci.  A plan on the device: src and first are what a merge reads; the rest is held only while the plan is built
 struct LocusPlan {
     DevBuf<int64_t> plan;                                    // positions (transient)
-    DevBuf<uint64_t> keys, keys_sorted;                      // positions (transient)
-    DevBuf<uint32_t> ids, ids_sorted;                        // positions (transient)
-    DevBuf<char> temp;                                       // the sort's scratch (transient)
+    SortedPairs pairs;                                       // (locus, position) of every position (transient)
     DevBuf<uint32_t> src, first;                             // positions: x << 2 | flags in locus order; loci + 1
     int64_t n_pos = 0, n_loci = 0;
     bool have = false;
-    size_t held() const { return plan.cap * 8 + (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap + src.cap + first.cap) * 4 + temp.cap; }
-    void release_transient() { plan.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release(); }
+    size_t held() const { return plan.cap * 8 + pairs.held() + (src.cap + first.cap) * 4; }
+    void release_transient() { plan.release(); pairs.release(); }
     void release() { release_transient(); src.release(); first.release(); have = false; n_pos = n_loci = 0; }
 };
 // what mipgen_accel_locus_tables leaves on the HANDLE: its plan and the uploaded and merged tables
@@ -234,41 +261,35 @@ struct LocusScratch {
     void release() { plan.release(); ref.release(); pile.release(); gapped.release(); merged.release(); ctr.release(); state.release(); }
 };
 // mipgen_accel_reads_consensus_insertions: a count scratch of its own - its projections have five planes -, the anchor table, the events and what
-// orders them; released with the reads.  run keys and run counts take the place of keys and ids once the sort has read them.
+// orders them; released with the reads.  run keys and run counts take the place of pairs.keys and pairs.ids once the sort has read them.
 struct InsScratch {
     CountScratch count;
     DevBuf<int32_t> anchors;                                 // positions x INSERTION_COLUMNS
     DevBuf<InsCounters> ctr;
-    DevBuf<uint64_t> keys, keys_sorted;                      // events
-    DevBuf<uint32_t> ids, ids_sorted;                        // events (the sort moves pairs; nothing reads them)
-    DevBuf<char> temp;
+    SortedPairs pairs;                                       // events (the sort moves pairs; nothing reads the ids)
     DevBuf<mipgen_insertion_record> records;                 // events at most
     int64_t n_alleles = -1;                                  // the records of the last call (-1: none, or it failed)
-    size_t event_held() const { return (keys.cap + keys_sorted.cap) * 8 + (ids.cap + ids_sorted.cap) * 4 + temp.cap + records.cap * sizeof(mipgen_insertion_record); }
+    size_t event_held() const { return pairs.held() + records.cap * sizeof(mipgen_insertion_record); }
     size_t table_held() const { return anchors.cap * 4 + ctr.cap * sizeof(InsCounters); }
-    void release() { count.release(); anchors.release(); ctr.release(); keys.release(); keys_sorted.release(); ids.release(); ids_sorted.release(); temp.release();
-                     records.release(); n_alleles = -1; }
+    void release() { count.release(); anchors.release(); ctr.release(); pairs.release(); records.release(); n_alleles = -1; }
 };
 // mipgen_accel_reads_consensus_insertion_pool: the sparse pool over the sample rows - S per position, keys and sums per distinct allele - and the
-// arguments it was built with (`args`: a PoolState whose dense pool stays unreserved); the entries and what orders them are held only while the pool is built.
-// Released with the reads.
+// arguments it was built with; the entries and what orders them are held only while the pool is built.  Released with the reads.
 struct InsPool {
-    PoolState args;
+    PoolArgs args;
     DevBuf<int32_t> S;                                       // positions
     DevBuf<uint64_t> pool_keys;                              // distinct alleles, ascending
     DevBuf<InsPoolSums> pool_sums;
     DevBuf<InsPoolCounters> ctr;
-    DevBuf<uint64_t> keys, keys_sorted;                      // entries (transient, as everything below)
+    SortedPairs pairs;                                       // (key, index) of every entry (transient, as everything below)
     DevBuf<InsPoolSums> sums;
-    DevBuf<uint32_t> ids, ids_sorted, run_start;
+    DevBuf<uint32_t> run_start;
     DevBuf<int32_t> run_counts;
-    DevBuf<char> temp;
     int64_t n_pos = 0, rows = 0, n_entries = 0, n_alleles = 0;
-    size_t entry_held() const { return (keys.cap + keys_sorted.cap + pool_keys.cap) * 8 + (sums.cap + pool_sums.cap) * sizeof(InsPoolSums) +
-                                       (ids.cap + ids_sorted.cap + run_start.cap + run_counts.cap) * 4 + temp.cap; }
+    size_t entry_held() const { return pairs.held() + pool_keys.cap * 8 + (sums.cap + pool_sums.cap) * sizeof(InsPoolSums) + (run_start.cap + run_counts.cap) * 4; }
     size_t table_held() const { return S.cap * 4 + ctr.cap * sizeof(InsPoolCounters); }
-    void release_transient() { keys.release(); keys_sorted.release(); sums.release(); ids.release(); ids_sorted.release(); run_start.release(); run_counts.release(); temp.release(); }
-    void release() { args.release(); release_transient(); S.release(); pool_keys.release(); pool_sums.release(); ctr.release(); n_pos = rows = n_entries = n_alleles = 0; }
+    void release_transient() { pairs.release(); sums.release(); run_start.release(); run_counts.release(); }
+    void release() { args.have = false; release_transient(); S.release(); pool_keys.release(); pool_sums.release(); ctr.release(); n_pos = rows = n_entries = n_alleles = 0; }
 };
 // what an insertion call of either kind (mipgen_accel_insertion_call_tables too) leaves on the HANDLE: a CallRun of its own - mipgen_accel_call_fetch keeps finding the
 // last variant call -, the joined records, and the uploaded arrays of the tables call
@@ -280,8 +301,8 @@ struct InsCallRun {
     DevBuf<uint64_t> pool_keys;
     DevBuf<InsPoolSums> pool_sums;
     int64_t n_calls = -1;                                    // the records of the last insertion call (-1: none yet)
-    size_t held() const { return run.held() + out.cap * sizeof(mipgen_insertion_call_record) + records.cap * sizeof(mipgen_insertion_record) + (span.cap + pool_span.cap) * 4 +
-                                 pool_keys.cap * 8 + pool_sums.cap * sizeof(InsPoolSums); }
+    size_t call_held() const { return run.held() + out.cap * sizeof(mipgen_insertion_call_record); }          // what run_ins_call fills
+    size_t upload_held() const { return records.cap * sizeof(mipgen_insertion_record) + (span.cap + pool_span.cap) * 4 + pool_keys.cap * 8 + pool_sums.cap * sizeof(InsPoolSums); }
     void release() { run.release(); out.release(); records.release(); span.release(); pool_span.release(); pool_keys.release(); pool_sums.release(); n_calls = -1; }
 };
 struct ConsensusResult {

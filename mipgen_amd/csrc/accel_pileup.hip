@@ -7,7 +7,8 @@
 // or the gapped table, download and totals of one row into the CountScratch it is given.  Every entry point gives a scratch of its own - `pile` / `gapped` of the
 // ConsensusResult, of its CallScratch, of its LocusScratch, of its InsScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
 // a Target: per template position, or per locus, where count_target folds the row's table by the installed plan (kernels_locus.hip) between the count and the pool
-// or run_call.  An entry point is its own refusals, its budget and one call of the shared route.
+// or run_call.  An entry point is its own refusals, its budget and one call of the shared route.  Whatever is ordered on the device - candidates, plan positions, insertion
+// events, pool entries - lies in the SortedPairs of its struct, and what a pool was built with in a PoolArgs (both accel_internal.h).
 #include "accel_internal.h"
 #include "gapped_align.h"
 
@@ -21,14 +22,20 @@ struct RowArgs {
     int planes() const { return runs ? 5 : 3; }
 };
 
+void PoolArgs::remember(const RowArgs& A, int64_t n_pos, int32_t bg_max_ppm_)
+{
+    mol_len.assign(A.mol_len, A.mol_len + A.n);
+    if (A.mol_seq) mol_seq.assign(A.mol_seq, (size_t)n_pos); else mol_seq.clear();     // (the dense pool without indels may be built without template bases)
+    min_family = A.min_family; min_quality = A.min_quality; max_indel = A.max_indel; bg_max_ppm = bg_max_ppm_;
+    have = true;
+}
+
 struct RowPlan {
     ConsensusResult* R = nullptr;
     int64_t n_pos = 0, n_units = 0;                                      // template positions; rounds of 64 of them
     int32_t max_len = 0;
     size_t bytes = 0;                                                    // the device memory RowScratch takes at most
 };
-
-static size_t padded(size_t count, size_t size) { return (count + count / 8 + 64) * size; }      // (what DevBuf::reserve asks for at most)
 
 // what a call may take: the bytes it holds already and the free ones
 static int room_beside(size_t held, size_t* room)
@@ -195,6 +202,12 @@ static int count_row(mipgen_accel* h, const RowPlan& P, CountScratch& W, const B
 }
 
 // ---- variant calls ---------------------------------------------------------------------------------------------------------------------------
+static int check_bg_max_ppm(int32_t bg_max_ppm)
+{
+    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    return MIPGEN_OK;
+}
+
 static int check_call_params(const mipgen_call_params* p)
 {
     if (!p) return fail(MIPGEN_E_INVALID, "bad arguments: no call parameters");
@@ -203,16 +216,15 @@ static int check_call_params(const mipgen_call_params* p)
     if (p->min_ppm < 0 || p->min_ppm > 1000000) return fail(MIPGEN_E_INVALID, "min_ppm %d: 0 to 1000000", p->min_ppm);
     if (p->min_q < 0 || p->min_q > CALL_Q_CAP) return fail(MIPGEN_E_INVALID, "min_q %d: 0 to %d", p->min_q, CALL_Q_CAP);
     if (!(p->a0 > 0 && p->a0 < p->n0 && p->n0 <= (1 << 30))) return fail(MIPGEN_E_INVALID, "prior %d / %d: 0 < a0 < n0 <= 2^30", p->a0, p->n0);
-    if (p->bg_max_ppm < 0 || p->bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", p->bg_max_ppm);
-    return MIPGEN_OK;
+    return check_bg_max_ppm(p->bg_max_ppm);
 }
 
-// what flag, tail, sort and gather of n_pos positions take at the worst (4 candidates per position): the list, the ordered records, two (key, slot) pairs per candidate
-// and the sort's own scratch (measured at 1/16 of the sort's bytes, taken at 1/4)
-static size_t call_run_bytes(int64_t n_pos)
+// what flag, tail, sort and gather of at most max_cand candidates (4 per position; every record of an insertion call) take at the worst: the list, the ordered
+// records, two (key, slot) pairs per candidate and the sort's own scratch (measured at 1/16 of the sort's bytes, taken at 1/4)
+static size_t call_run_bytes(int64_t max_cand)
 {
-    const size_t c = 4 * (size_t)n_pos;
-    return 2 * padded(c, sizeof(mipgen_call_record)) + 2 * padded(c, 8) + 2 * padded(c, 4) + padded(c * 6, 1) + padded(1, sizeof(CallCounters));
+    const size_t c = (size_t)max_cand;
+    return 2 * padded(c, sizeof(mipgen_call_record)) + SortedPairs::bytes(c, c * 6) + padded(1, sizeof(CallCounters));
 }
 
 // What every call shares from its flag kernel to its ordered records, in the CallRun U it is given: `flag` lists the candidates (at most max_cand; their pos below
@@ -236,16 +248,13 @@ static int run_flagged(mipgen_accel* h, CallRun& U, int64_t n_keys, int64_t max_
     if (n_cand > 0) {
         int end_bit = 4;                                                 // the bits of the sentinel n_keys << 3, the largest key
         while (end_bit < 64 && (((uint64_t)n_keys << 3) >> end_bit)) end_bit++;
-        size_t temp_bytes = 0;
-        HIP_TRY(mipgen_consensus_sort(st, nullptr, &temp_bytes, nullptr, nullptr, nullptr, nullptr, n_cand, end_bit));
-        if (U.keys.reserve((size_t)n_cand) || U.keys_sorted.reserve((size_t)n_cand) || U.ids.reserve((size_t)n_cand) || U.ids_sorted.reserve((size_t)n_cand) ||
-            U.records.reserve((size_t)n_cand) || U.temp.reserve(std::max<size_t>(temp_bytes, 1)))
-            return MIPGEN_E_NOMEM;
-        temp_bytes = U.temp.cap;
+        size_t scratch = 0;
+        HIP_TRY(SortedPairs::scratch_bytes(st, n_cand, end_bit, 0, 0, &scratch));
+        if (U.pairs.reserve((size_t)n_cand, scratch) || U.records.reserve((size_t)n_cand)) return MIPGEN_E_NOMEM;
         timer.mark();
-        HIP_TRY(mipgen_launch_call_tail(st, U.cand.p, n_cand, n_keys, M, U.keys.p, U.ids.p, U.ctr.p));
-        HIP_TRY(mipgen_consensus_sort(st, U.temp.p, &temp_bytes, U.keys.p, U.keys_sorted.p, U.ids.p, U.ids_sorted.p, n_cand, end_bit));
-        HIP_TRY(mipgen_launch_call_gather(st, U.cand.p, U.ids_sorted.p, n_cand, U.ctr.p, U.records.p));
+        HIP_TRY(mipgen_launch_call_tail(st, U.cand.p, n_cand, n_keys, M, U.pairs.keys.p, U.pairs.ids.p, U.ctr.p));
+        HIP_TRY(U.pairs.sort(st, n_cand, end_bit));
+        HIP_TRY(mipgen_launch_call_gather(st, U.cand.p, U.pairs.ids_sorted.p, n_cand, U.ctr.p, U.records.p));
         timer.mark();
         HIP_TRY(hipMemcpyAsync(&cc, U.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
     }
@@ -295,7 +304,7 @@ static int locus_end_bit(int64_t n_loci)                                 // the 
     return end_bit;
 }
 
-// A checked plan onto the device (timed as one span of `timer`): the budget - the plan, the pairs and the sorted pairs, the sort's scratch, src and first, and
+// A checked plan onto the device (timed as one span of `timer`): the budget - the plan, the pairs with the sort's scratch, src and first, and
 // `more_need` bytes the caller allocates next, against what is held and free - before anything is allocated; then keys, sort, sources and first.  The stream is idle
 // and only src and first are still held on success.  what: the call's name.
 static int build_locus_plan(mipgen_accel* h, LocusPlan& L, const int64_t* plan, int64_t n_pos, int64_t n_loci, size_t more_need, size_t more_held, const char* what,
@@ -304,25 +313,21 @@ static int build_locus_plan(mipgen_accel* h, LocusPlan& L, const int64_t* plan, 
     hipStream_t st = h->stream;
     const size_t np = (size_t)n_pos, nl = (size_t)n_loci;
     const int end_bit = locus_end_bit(n_loci);
-    size_t temp_bytes = 0;
-    HIP_TRY(mipgen_consensus_sort(st, nullptr, &temp_bytes, nullptr, nullptr, nullptr, nullptr, n_pos, end_bit));
-    const size_t need = 3 * padded(np, 8) + 3 * padded(np, 4) + padded(std::max<size_t>(temp_bytes, 1), 1) + padded(nl + 1, 4) + more_need;
-    size_t room = 0;
+    size_t scratch = 0, room = 0;
+    HIP_TRY(SortedPairs::scratch_bytes(st, n_pos, end_bit, 0, 0, &scratch));
+    const size_t need = padded(np, 8) + SortedPairs::bytes(np, scratch) + padded(np, 4) + padded(nl + 1, 4) + more_need;
     if (int rc = room_beside(L.held() + more_held, &room)) return rc;
     if (need > room)
         return fail(MIPGEN_E_NOMEM, "%s: a plan of %lld positions and %lld loci needs up to %zu MiB of device memory, %zu MiB are free", what, (long long)n_pos,
                     (long long)n_loci, need >> 20, room >> 20);
     L.have = false;
-    if (L.plan.reserve(np) || L.keys.reserve(np) || L.keys_sorted.reserve(np) || L.ids.reserve(np) || L.ids_sorted.reserve(np) || L.src.reserve(np) ||
-        L.first.reserve(nl + 1) || L.temp.reserve(std::max<size_t>(temp_bytes, 1)))
-        return MIPGEN_E_NOMEM;
-    temp_bytes = L.temp.cap;
+    if (L.plan.reserve(np) || L.pairs.reserve(np, scratch) || L.src.reserve(np) || L.first.reserve(nl + 1)) return MIPGEN_E_NOMEM;
     IdleOnExit idle{st};                                                 // (the caller's plan outlives its copy)
     HIP_TRY(hipMemcpyAsync(L.plan.p, plan, np * 8, hipMemcpyHostToDevice, st));
     timer.mark();
-    HIP_TRY(mipgen_launch_locus_keys(st, L.plan.p, n_pos, n_loci, L.keys.p, L.ids.p));
-    HIP_TRY(mipgen_consensus_sort(st, L.temp.p, &temp_bytes, L.keys.p, L.keys_sorted.p, L.ids.p, L.ids_sorted.p, n_pos, end_bit));
-    HIP_TRY(mipgen_launch_locus_index(st, L.keys_sorted.p, L.ids_sorted.p, L.plan.p, n_pos, n_loci, L.src.p, L.first.p));
+    HIP_TRY(mipgen_launch_locus_keys(st, L.plan.p, n_pos, n_loci, L.pairs.keys.p, L.pairs.ids.p));
+    HIP_TRY(L.pairs.sort(st, n_pos, end_bit));
+    HIP_TRY(mipgen_launch_locus_index(st, L.pairs.keys_sorted.p, L.pairs.ids_sorted.p, L.plan.p, n_pos, n_loci, L.src.p, L.first.p));
     timer.mark();
     HIP_TRY(idle.wait());
     L.release_transient();
@@ -402,16 +407,13 @@ static int build_pool(mipgen_accel* h, const RowPlan& P, const Target& T, const 
         timer.mark();
     }
     HIP_TRY(idle.wait());
-    S.mol_len.assign(A.mol_len, A.mol_len + A.n);
-    if (A.mol_seq) S.mol_seq.assign(A.mol_seq, (size_t)P.n_pos); else S.mol_seq.clear();
-    S.min_family = A.min_family; S.min_quality = A.min_quality; S.max_indel = A.max_indel; S.bg_max_ppm = bg_max_ppm;
-    S.have = true;
+    S.remember(A, P.n_pos, bg_max_ppm);
     return booked(timer, T.ms);
 }
 
 // What a call of one row against the pool of a target shares up to its refusals of the row and the parameters: the row planned with the pool's arguments.
 // pool_name: "pool" or "locus pool", as the message names it.
-static int plan_call(mipgen_accel* h, const PoolState& S, int32_t row, const mipgen_call_params* params, const char* pool_name, RowArgs* A, RowPlan* P)
+static int plan_call(mipgen_accel* h, const PoolArgs& S, int32_t row, const mipgen_call_params* params, const char* pool_name, RowArgs* A, RowPlan* P)
 {
     *A = {S.mol_seq.data(), S.mol_len.data(), (int32_t)S.mol_len.size(), S.min_family, S.min_quality, S.max_indel};
     if (int rc = plan_row(h, *A, row, P)) return rc;
@@ -428,7 +430,7 @@ static int call_row(mipgen_accel* h, const RowPlan& P, const Target& T, const Ro
     const int64_t n_out = T.n_out(P);
     *T.ms = -1.0;
     h->call_run.n_calls = -1;
-    const Budget B{what, call_run_bytes(n_out), h->call_run.held(), true};
+    const Budget B{what, call_run_bytes(4 * n_out), h->call_run.held(), true};
     SpanTimer timer{h->timing, h->stream};
     S.have_last = false;
     Counted counted;
@@ -482,29 +484,23 @@ static int insertions_row(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
     if (events < 0 || events > 0x7fffffff) return fail(MIPGEN_E_INVALID, "insertions: %lld events in row %d: 2^31 - 1 at most", (long long)events, row);
     // the events' bytes, known only now: checked before they are allocated
     const size_t ne = (size_t)events;
-    size_t temp_bytes = 0;
     if (events > 0) {
-        size_t t_sort = 0, t_runs = 0;
-        HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, nullptr, nullptr, nullptr, nullptr, events, 64));
-        HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, nullptr, events, nullptr, nullptr, nullptr));
-        temp_bytes = std::max<size_t>(std::max(t_sort, t_runs), 1);
-        const size_t need = 2 * padded(ne, 8) + 2 * padded(ne, 4) + padded(temp_bytes, 1) + padded(ne, sizeof(mipgen_insertion_record));
-        size_t room = 0;
+        size_t scratch = 0, room = 0;
+        HIP_TRY(SortedPairs::scratch_bytes(st, events, 64, events, 0, &scratch));
+        const size_t need = SortedPairs::bytes(ne, scratch) + padded(ne, sizeof(mipgen_insertion_record));
         if (int rc = room_beside(S.event_held(), &room)) return rc;
         if (need > room)
             return fail(MIPGEN_E_NOMEM, "insertions: %lld events need %zu MiB of device memory, %zu MiB are free", (long long)events, need >> 20, room >> 20);
-        if (S.keys.reserve(ne) || S.keys_sorted.reserve(ne) || S.ids.reserve(ne) || S.ids_sorted.reserve(ne) || S.temp.reserve(temp_bytes) || S.records.reserve(ne))
-            return MIPGEN_E_NOMEM;
-        temp_bytes = S.temp.cap;
+        if (S.pairs.reserve(ne, scratch) || S.records.reserve(ne)) return MIPGEN_E_NOMEM;
     }
     if (S.anchors.reserve(cells) || S.ctr.reserve(1)) return MIPGEN_E_NOMEM;
     IdleOnExit idle{st};
     InsCounters ic;
     HIP_TRY(hipMemsetAsync(S.ctr.p, 0, sizeof ic, st));
-    if (events > 0) HIP_TRY(hipMemsetAsync(S.ids.p, 0, ne * 4, st));
+    if (events > 0) HIP_TRY(hipMemsetAsync(S.pairs.ids.p, 0, ne * 4, st));
     const CountScratch& W = S.count;
     timer.mark();
-    HIP_TRY(mipgen_launch_insertions(st, P.R->view(), counted.row, P.n_units, counted.g_first, W.proj_off.p, W.proj.p, S.anchors.p, S.keys.p, events, S.ctr.p));
+    HIP_TRY(mipgen_launch_insertions(st, P.R->view(), counted.row, P.n_units, counted.g_first, W.proj_off.p, W.proj.p, S.anchors.p, S.pairs.keys.p, events, S.ctr.p));
     timer.mark();
     HIP_TRY(hipMemcpyAsync(&ic, S.ctr.p, sizeof ic, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -513,9 +509,10 @@ static int insertions_row(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
                     ic.ins_discordant, (long long)gt.ins_discordant);
     if (events > 0) {
         timer.mark();
-        HIP_TRY(mipgen_consensus_sort(st, S.temp.p, &temp_bytes, S.keys.p, S.keys_sorted.p, S.ids.p, S.ids_sorted.p, events, 64));
-        HIP_TRY(mipgen_consensus_runs(st, S.temp.p, &temp_bytes, S.keys_sorted.p, events, S.keys.p, reinterpret_cast<int32_t*>(S.ids.p), &S.ctr.p->alleles));
-        HIP_TRY(mipgen_launch_insertion_records(st, S.keys.p, reinterpret_cast<const int32_t*>(S.ids.p), &S.ctr.p->alleles, events, S.records.p));
+        int32_t* run_counts = reinterpret_cast<int32_t*>(S.pairs.ids.p);
+        HIP_TRY(S.pairs.sort(st, events, 64));
+        HIP_TRY(S.pairs.runs(st, events, S.pairs.keys.p, run_counts, &S.ctr.p->alleles));
+        HIP_TRY(mipgen_launch_insertion_records(st, S.pairs.keys.p, run_counts, &S.ctr.p->alleles, events, S.records.p));
         timer.mark();
         HIP_TRY(hipMemcpyAsync(&ic, S.ctr.p, sizeof ic, hipMemcpyDeviceToHost, st));
     }
@@ -545,8 +542,8 @@ static int grow_keeping(DevBuf<T>& b, size_t used, size_t want, hipStream_t st)
     return MIPGEN_OK;
 }
 
-// what one entry of the pool takes while the pool is built: key and sorted key, sums, index and sorted index, and of its run the key, the sums, the length and the start
-static const size_t INS_POOL_ENTRY_BYTES = 3 * 8 + 2 * sizeof(InsPoolSums) + 4 * 4;
+// what one entry of the pool takes while the pool is built beside its sorted pairs: its sums, and of its run the key, the sums, the length and the start
+static const size_t INS_POOL_ENTRY_BYTES = 8 + 2 * sizeof(InsPoolSums) + 2 * 4;
 
 // The sparse pool over the sample rows: the insertions route of every sample row, its spans added into S and its non-ambiguous records appended as entries;
 // then the entries sorted by key, their runs - the distinct alleles - and the sums of every run.  The caller has made its refusals and dropped the pool that was held.
@@ -574,17 +571,17 @@ static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
         const int64_t n_rec = I.n_alleles;
         if (used + n_rec > 0x7fffffff) return fail(MIPGEN_E_INVALID, "insertion pool: more than 2^31 - 1 allele records over the sample rows");
         const size_t want = (size_t)(used + n_rec);
-        if (want > Q.keys.cap) {                                         // the entries' bytes, known only now: checked before they are allocated
+        if (want > Q.pairs.keys.cap) {                                         // the entries' bytes, known only now: checked before they are allocated
             const size_t need = padded(want, 8) + padded(want, sizeof(InsPoolSums)) + padded(want, 4);
             if (int rc = room_beside(0, &room)) return rc;
             if (need > room)
                 return fail(MIPGEN_E_NOMEM, "insertion pool: %zu entries need %zu MiB of device memory, %zu MiB are free", want, need >> 20, room >> 20);
-            if (int rc = grow_keeping(Q.keys, (size_t)used, want, st)) return rc;
+            if (int rc = grow_keeping(Q.pairs.keys, (size_t)used, want, st)) return rc;
             if (int rc = grow_keeping(Q.sums, (size_t)used, want, st)) return rc;
-            if (int rc = grow_keeping(Q.ids, (size_t)used, want, st)) return rc;
+            if (int rc = grow_keeping(Q.pairs.ids, (size_t)used, want, st)) return rc;
         }
         timer.mark();
-        HIP_TRY(mipgen_launch_ins_pool_append(st, I.anchors.p, P.n_pos, I.records.p, n_rec, bg_max_ppm, Q.S.p, Q.keys.p, Q.sums.p, Q.ids.p, (int64_t)want, Q.ctr.p));
+        HIP_TRY(mipgen_launch_ins_pool_append(st, I.anchors.p, P.n_pos, I.records.p, n_rec, bg_max_ppm, Q.S.p, Q.pairs.keys.p, Q.sums.p, Q.pairs.ids.p, (int64_t)want, Q.ctr.p));
         timer.mark();
         HIP_TRY(hipMemcpyAsync(&pc, Q.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -595,24 +592,19 @@ static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
     I.n_alleles = -1;                                                    // (the records of the last sample row are no call's result)
     if (used > 0) {
         const size_t ne = (size_t)used;
-        size_t t_sort = 0, t_runs = 0, t_scan = 0;
-        HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, nullptr, nullptr, nullptr, nullptr, used, 64));
-        HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, nullptr, used, nullptr, nullptr, nullptr));
-        HIP_TRY(mipgen_consensus_scan_u32(st, nullptr, &t_scan, nullptr, nullptr, used));
-        size_t temp_bytes = std::max<size_t>(std::max(t_sort, std::max(t_runs, t_scan)), 1);
-        const size_t need = padded(ne, INS_POOL_ENTRY_BYTES) + padded(temp_bytes, 1);
+        size_t scratch = 0;
+        HIP_TRY(SortedPairs::scratch_bytes(st, used, 64, used, used, &scratch));
+        const size_t need = SortedPairs::bytes(ne, scratch) + padded(ne, INS_POOL_ENTRY_BYTES);
         if (int rc = room_beside(Q.entry_held(), &room)) return rc;
         if (need > room)
             return fail(MIPGEN_E_NOMEM, "insertion pool: %lld entries need %zu MiB of device memory, %zu MiB are free", (long long)used, need >> 20, room >> 20);
-        if (Q.keys_sorted.reserve(ne) || Q.ids_sorted.reserve(ne) || Q.pool_keys.reserve(ne) || Q.pool_sums.reserve(ne) || Q.run_counts.reserve(ne) || Q.run_start.reserve(ne) ||
-            Q.temp.reserve(temp_bytes))
-            return MIPGEN_E_NOMEM;
-        temp_bytes = Q.temp.cap;
+        // (keys and ids hold the entries and are large enough: the reserve adds their sorted copies and the scratch)
+        if (Q.pairs.reserve(ne, scratch) || Q.pool_keys.reserve(ne) || Q.pool_sums.reserve(ne) || Q.run_counts.reserve(ne) || Q.run_start.reserve(ne)) return MIPGEN_E_NOMEM;
         timer.mark();
-        HIP_TRY(mipgen_consensus_sort(st, Q.temp.p, &temp_bytes, Q.keys.p, Q.keys_sorted.p, Q.ids.p, Q.ids_sorted.p, used, 64));
-        HIP_TRY(mipgen_consensus_runs(st, Q.temp.p, &temp_bytes, Q.keys_sorted.p, used, Q.pool_keys.p, Q.run_counts.p, &Q.ctr.p->alleles));
-        HIP_TRY(mipgen_consensus_scan_u32(st, Q.temp.p, &temp_bytes, Q.run_counts.p, Q.run_start.p, used));   // (beyond the runs the lengths are unwritten and the starts unread)
-        HIP_TRY(mipgen_launch_ins_pool_reduce(st, Q.run_counts.p, Q.run_start.p, &Q.ctr.p->alleles, used, Q.ids_sorted.p, Q.sums.p, Q.pool_sums.p));
+        HIP_TRY(Q.pairs.sort(st, used, 64));
+        HIP_TRY(Q.pairs.runs(st, used, Q.pool_keys.p, Q.run_counts.p, &Q.ctr.p->alleles));
+        HIP_TRY(Q.pairs.scan_u32(st, Q.run_counts.p, Q.run_start.p, used));      // (beyond the runs the lengths are unwritten and the starts unread)
+        HIP_TRY(mipgen_launch_ins_pool_reduce(st, Q.run_counts.p, Q.run_start.p, &Q.ctr.p->alleles, used, Q.pairs.ids_sorted.p, Q.sums.p, Q.pool_sums.p));
         timer.mark();
         HIP_TRY(hipMemcpyAsync(&pc, Q.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
     }
@@ -620,11 +612,7 @@ static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
     if ((int64_t)pc.alleles > used || (used > 0 && pc.alleles == 0)) return fail(MIPGEN_E_STATE, "insertion pool: %llu alleles of %lld entries", pc.alleles, (long long)used);
     Q.release_transient();
     Q.n_pos = P.n_pos; Q.rows = rows; Q.n_entries = used; Q.n_alleles = (int64_t)pc.alleles;
-    PoolState& G = Q.args;
-    G.mol_len.assign(A.mol_len, A.mol_len + A.n);
-    G.mol_seq.assign(A.mol_seq, (size_t)P.n_pos);
-    G.min_family = A.min_family; G.min_quality = A.min_quality; G.max_indel = A.max_indel; G.bg_max_ppm = bg_max_ppm;
-    G.have = true;
+    Q.args.remember(A, P.n_pos, bg_max_ppm);
     return MIPGEN_OK;
 }
 
@@ -643,13 +631,10 @@ static int run_ins_call(mipgen_accel* h, const mipgen_insertion_record* records,
         V.n_calls = 0;
         return MIPGEN_OK;
     }
-    // flag, tail, sort, gather and join at the worst (every record a call): the list and the ordered records, two (key, slot) pairs per candidate, the sort's scratch
-    // (taken as call_run_bytes takes it) and the joined records
-    const size_t c = (size_t)n_rec;
-    const size_t need = 2 * padded(c, sizeof(mipgen_call_record)) + 2 * padded(c, 8) + 2 * padded(c, 4) + padded(c * 6, 1) + padded(1, sizeof(CallCounters)) +
-                        padded(c, sizeof(mipgen_insertion_call_record));
+    // flag, tail, sort, gather and join at the worst (every record a call): the shared tail over n_rec candidates and the joined records
+    const size_t need = call_run_bytes(n_rec) + padded((size_t)n_rec, sizeof(mipgen_insertion_call_record));
     size_t room = 0;
-    if (int rc = room_beside(V.run.held() + V.out.cap * sizeof(mipgen_insertion_call_record), &room)) return rc;
+    if (int rc = room_beside(V.call_held(), &room)) return rc;
     if (need > room)
         return fail(MIPGEN_E_NOMEM, "insertion call: %lld allele records need up to %zu MiB of device memory, %zu MiB are free", (long long)n_rec, need >> 20, room >> 20);
     const CallModel M = model_of(prm);
@@ -667,6 +652,21 @@ static int run_ins_call(mipgen_accel* h, const mipgen_insertion_record* records,
         HIP_TRY(idle.wait());
     }
     V.n_calls = n_calls;
+    return MIPGEN_OK;
+}
+
+// What the three fetch calls share once the handle is there: the `held` records of the last call (below 0: none, `none` is the refusal's text) from `from` on the device
+// into records[0, n); what: the call as the message of a wrong n names it.
+template <typename Record>
+static int fetch_records(mipgen_accel* h, const DevBuf<Record>& from, int64_t held, const char* none, const char* what, Record* records, int64_t n)
+{
+    if (held < 0) return fail(MIPGEN_E_STATE, "%s", none);
+    if (n != held) return fail(MIPGEN_E_INVALID, "%lld records asked: the last %s left %lld", (long long)n, what, (long long)held);
+    if (n == 0) return MIPGEN_OK;
+    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(records, from.p, (size_t)n * sizeof(Record), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MIPGEN_OK;
 }
 
@@ -720,14 +720,8 @@ int mipgen_accel_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* reco
 {
     if (int rc = check_reads(h)) return rc;
     const InsScratch& S = h->consensus->ins;
-    if (S.n_alleles < 0) return fail(MIPGEN_E_STATE, "the consensus reads hold no insertion alleles: mipgen_accel_reads_consensus_insertions leaves them");
-    if (n != S.n_alleles) return fail(MIPGEN_E_INVALID, "%lld records asked: the last insertions call left %lld", (long long)n, (long long)S.n_alleles);
-    if (n == 0) return MIPGEN_OK;
-    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(records, S.records.p, (size_t)n * sizeof(mipgen_insertion_record), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MIPGEN_OK;
+    return fetch_records(h, S.records, S.n_alleles, "the consensus reads hold no insertion alleles: mipgen_accel_reads_consensus_insertions leaves them", "insertions call",
+                         records, n);
 }
 
 // Insertion calls from host arrays: no read session is needed; the arrays are uploaded into the handle's InsCallRun, the pool records as keys and sums.
@@ -768,7 +762,7 @@ int mipgen_accel_insertion_call_tables(mipgen_accel* h, const mipgen_insertion_r
     const size_t np = (size_t)n_pos, nr = (size_t)n_records, nq = (size_t)n_pool;
     const size_t need = 2 * padded(np, 4) + padded(nr, sizeof(mipgen_insertion_record)) + padded(nq, 8) + padded(nq, sizeof(InsPoolSums));
     size_t room = 0;
-    if (int rc = room_beside(V.held() - V.run.held() - V.out.cap * sizeof(mipgen_insertion_call_record), &room)) return rc;
+    if (int rc = room_beside(V.upload_held(), &room)) return rc;
     if (need > room)
         return fail(MIPGEN_E_NOMEM, "insertion call: %lld positions, %lld allele records and %lld pool records need %zu MiB of device memory, %zu MiB are free", (long long)n_pos,
                     (long long)n_records, (long long)n_pool, need >> 20, room >> 20);
@@ -795,9 +789,9 @@ int mipgen_accel_reads_consensus_insertion_pool(mipgen_accel* h, const char* mol
     RowPlan P;
     const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
     if (int rc = plan_insertions(h, A, 0, &P)) return rc;
-    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    if (int rc = check_bg_max_ppm(bg_max_ppm)) return rc;
     InsPool& Q = P.R->ins_pool;
-    Q.args.drop();                                                       // (a pool that fails leaves none)
+    Q.args.have = false;                                                 // (a pool that fails leaves none)
     h->ins_call_ms = -1.0;
     SpanTimer timer{h->timing, h->stream};
     if (int rc = build_ins_pool(h, P, A, bg_max_ppm, timer)) return rc;
@@ -858,16 +852,9 @@ int mipgen_accel_reads_consensus_insertion_call(mipgen_accel* h, int32_t row, co
 int mipgen_accel_insertion_call_fetch(mipgen_accel* h, mipgen_insertion_call_record* records, int64_t n)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    const InsCallRun& V = h->ins_call;
-    if (V.n_calls < 0)
-        return fail(MIPGEN_E_STATE, "the handle holds no insertion calls: mipgen_accel_insertion_call_tables or mipgen_accel_reads_consensus_insertion_call leaves them");
-    if (n != V.n_calls) return fail(MIPGEN_E_INVALID, "%lld records asked: the last insertion call left %lld", (long long)n, (long long)V.n_calls);
-    if (n == 0) return MIPGEN_OK;
-    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(records, V.out.p, (size_t)n * sizeof(mipgen_insertion_call_record), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MIPGEN_OK;
+    return fetch_records(h, h->ins_call.out, h->ins_call.n_calls,
+                         "the handle holds no insertion calls: mipgen_accel_insertion_call_tables or mipgen_accel_reads_consensus_insertion_call leaves them", "insertion call",
+                         records, n);
 }
 
 // Calls from host arrays: no read session is needed; the arrays are uploaded into the handle's CallRun.
@@ -882,7 +869,7 @@ int mipgen_accel_call_tables(mipgen_accel* h, const int32_t* counts, int32_t col
     HIP_TRY(hipSetDevice(h->device));
     CallRun& U = h->call_run;
     h->call_ms = -1.0;
-    const size_t np = (size_t)n_pos, need = padded(np * (size_t)columns, 4) + padded(np * 10, 4) + padded(np, 1) + call_run_bytes(n_pos);
+    const size_t np = (size_t)n_pos, need = padded(np * (size_t)columns, 4) + padded(np * 10, 4) + padded(np, 1) + call_run_bytes(4 * n_pos);
     size_t room = 0;
     if (int rc = room_beside(U.held(), &room)) return rc;
     if (need > room) return fail(MIPGEN_E_NOMEM, "call: %lld positions need up to %zu MiB of device memory, %zu MiB are free", (long long)n_pos, need >> 20, room >> 20);
@@ -904,14 +891,14 @@ int mipgen_accel_reads_consensus_call_pool(mipgen_accel* h, const char* mol_seq,
     RowPlan P;
     const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true};      // the template bases are the ref bytes: needed without indels too
     if (int rc = plan_row(h, A, 0, &P)) return rc;
-    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    if (int rc = check_bg_max_ppm(bg_max_ppm)) return rc;
     if (P.n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: a call takes 2^29 - 1 at most", (long long)P.n_pos);
     CallScratch& C = P.R->call;
     C.state.drop();                                                      // (a pool that fails leaves none)
     h->call_ms = -1.0;
     const size_t np = (size_t)P.n_pos;
     // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_row's
-    const size_t more = padded(np * 10, 4) + padded(np, 1) + call_run_bytes(P.n_pos), held = C.state.pool.cap * 4 + C.ref.cap + h->call_run.held();
+    const size_t more = padded(np * 10, 4) + padded(np, 1) + call_run_bytes(4 * P.n_pos), held = C.state.pool.cap * 4 + C.ref.cap + h->call_run.held();
     size_t room = 0;
     if (int rc = room_beside(held, &room)) return rc;
     if (more > room)
@@ -1018,7 +1005,7 @@ int mipgen_accel_reads_consensus_locus_call_pool(mipgen_accel* h, const char* mo
     RowPlan P;
     const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, max_indel != 0};      // (the ref bytes came with the plan, which also bounded the loci)
     if (int rc = plan_row(h, A, 0, &P)) return rc;
-    if (bg_max_ppm < 0 || bg_max_ppm > 1000000) return fail(MIPGEN_E_INVALID, "bg_max_ppm %d: 0 to 1000000", bg_max_ppm);
+    if (int rc = check_bg_max_ppm(bg_max_ppm)) return rc;
     LocusScratch& L = P.R->locus;
     if (int rc = check_locus_session(L, P)) return rc;
     L.state.drop();                                                      // (a pool that fails leaves none)
@@ -1026,7 +1013,7 @@ int mipgen_accel_reads_consensus_locus_call_pool(mipgen_accel* h, const char* mo
     const int64_t n_loci = L.plan.n_loci;
     const size_t nl = (size_t)n_loci, cols = max_indel ? GAPPED_COLUMNS : PILEUP_COLUMNS;
     // the budget of the pool AND of the calls that follow, before anything is allocated; the row's own terms are count_row's
-    const size_t more = padded(nl * cols, 4) + padded(nl * 10, 4) + padded(1, sizeof(LocusCounters)) + call_run_bytes(n_loci);
+    const size_t more = padded(nl * cols, 4) + padded(nl * 10, 4) + padded(1, sizeof(LocusCounters)) + call_run_bytes(4 * n_loci);
     const auto held = [&] { return (L.merged.cap + L.state.pool.cap) * 4 + L.ctr.cap * sizeof(LocusCounters) + h->call_run.held(); };
     size_t room = 0;
     if (int rc = room_beside(held(), &room)) return rc;
@@ -1061,15 +1048,8 @@ int mipgen_accel_reads_consensus_locus_call_pileup_totals(mipgen_accel* h, mipge
 int mipgen_accel_call_fetch(mipgen_accel* h, mipgen_call_record* records, int64_t n)
 {
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
-    const CallRun& U = h->call_run;
-    if (U.n_calls < 0) return fail(MIPGEN_E_STATE, "the handle holds no calls: mipgen_accel_call_tables or mipgen_accel_reads_consensus_call leaves them");
-    if (n != U.n_calls) return fail(MIPGEN_E_INVALID, "%lld records asked: the last call left %lld", (long long)n, (long long)U.n_calls);
-    if (n == 0) return MIPGEN_OK;
-    if (!records) return fail(MIPGEN_E_INVALID, "bad arguments: no records array");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(records, U.records.p, (size_t)n * sizeof(mipgen_call_record), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MIPGEN_OK;
+    return fetch_records(h, h->call_run.records, h->call_run.n_calls, "the handle holds no calls: mipgen_accel_call_tables or mipgen_accel_reads_consensus_call leaves them", "call",
+                         records, n);
 }
 
 }  // extern "C"

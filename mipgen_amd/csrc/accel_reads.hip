@@ -126,7 +126,7 @@ static void build_sample_table(const char* const* barcodes, int n_samples, int J
 struct FreeOnExit { void* p; ~FreeOnExit() { if (p) (void)hipFree(p); } };
 
 // The (cell, tag) keys of a plain or samples session, sorted and duplicate-free between feed calls.  A consensus session keeps no list: its `keys` is the scratch
-// k_read_assign writes a chunk's keys to (cap stays 0), and `sort_temp` and `end_bit` serve the sort of its finish.
+// k_read_assign writes a chunk's keys to (cap stays 0), and `end_bit` serves the sort of its finish; `sort_temp` stays unreserved, as sort_unique is never reached.
 struct KeyList {
     DevBuf<uint64_t> keys, keys_alt;
     DevBuf<char> sort_temp;
@@ -197,15 +197,15 @@ struct ConsensusPart {
     std::vector<ArenaChunk> chunks;
     size_t arena_cap = 0, arena_used = 0; int64_t total_pairs = 0;
     DevBuf<ConsensusCounters> ctr;
-    DevBuf<uint64_t> c_keys_in, c_keys_out;                  // the (key, pair id) of every pair, as fed and sorted
-    DevBuf<uint32_t> c_ids_in, c_ids_out, c_start, c_order;
+    SortedPairs pairs;                                       // the (key, pair id) of every pair, as fed and sorted; its scratch serves every scan of finish too
+    DevBuf<uint32_t> c_start, c_order;
     DevBuf<ConsensusPair> c_recs;
     DevBuf<int64_t> c_ext_len, c_lig_len;
     void release()
     {
         for (const ArenaChunk& c : chunks) (void)hipFree(c.block);
         chunks.clear();
-        ctr.release(); c_keys_in.release(); c_keys_out.release(); c_ids_in.release(); c_ids_out.release(); c_start.release(); c_order.release(); c_recs.release();
+        ctr.release(); pairs.release(); c_start.release(); c_order.release(); c_recs.release();
         c_ext_len.release(); c_lig_len.release();
     }
 };
@@ -544,7 +544,7 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
 {
     hipStream_t st = h->stream;
     ConsensusPart& C = S->cons;
-    DevBuf<char>& temp = S->keys.sort_temp;
+    SortedPairs& Q = C.pairs;
     const int64_t N = C.total_pairs;
     h->consensus_vote_ms = h->consensus_sort_ms = -1.0;
     ConsensusCounters cc;
@@ -552,32 +552,26 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t M = (int64_t)cc.members;                                   // pairs in a group: the keys below the sentinel
     if (M == 0) return MIPGEN_OK;
+    // one scratch buffer for the sort, the run boundaries and the three scans (sized for the most entries any of them sees)
+    size_t scratch = 0, t_i64 = 0;
+    const int sort_bits = S->keys.end_bit + 1;                               // the cell and tag bits that can be set, and the sentinel's
+    HIP_TRY(SortedPairs::scratch_bytes(st, N, sort_bits, M, M + 1, &scratch));
+    HIP_TRY(mipgen_consensus_scan_i64(st, nullptr, &t_i64, nullptr, nullptr, M + 1));
     // every pair's (key, id) and record, chunk after chunk, in feed order
-    if (C.c_keys_in.reserve((size_t)N) || C.c_keys_out.reserve((size_t)N) || C.c_ids_in.reserve((size_t)N) || C.c_ids_out.reserve((size_t)N) || C.c_recs.reserve((size_t)N))
-        return MIPGEN_E_NOMEM;
+    if (Q.reserve((size_t)N, std::max(scratch, t_i64) + 16) || C.c_recs.reserve((size_t)N)) return MIPGEN_E_NOMEM;
     for (const ArenaChunk& c : C.chunks) {
         const ChunkLayout L(c.n, 0, 0);                                      // (the per-pair parts lie in front of the bytes)
         HIP_TRY(hipMemcpyAsync(C.c_recs.p + c.pair0, c.block + L.recs, (size_t)c.n * sizeof(ConsensusPair), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(C.c_keys_in.p + c.pair0, c.block + L.keys, (size_t)c.n * 8, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(C.c_ids_in.p + c.pair0, c.block + L.ids, (size_t)c.n * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(Q.keys.p + c.pair0, c.block + L.keys, (size_t)c.n * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(Q.ids.p + c.pair0, c.block + L.ids, (size_t)c.n * 4, hipMemcpyDeviceToDevice, st));
     }
-    // one scratch buffer for the sort, the run boundaries and the three scans (sized for the most entries any of them sees)
-    size_t t_sort = 0, t_runs = 0, t_u32 = 0, t_i64 = 0;
-    const int sort_bits = S->keys.end_bit + 1;                               // the cell and tag bits that can be set, and the sentinel's
-    HIP_TRY(mipgen_consensus_sort(st, nullptr, &t_sort, C.c_keys_in.p, C.c_keys_out.p, C.c_ids_in.p, C.c_ids_out.p, N, sort_bits));
-    HIP_TRY(mipgen_consensus_runs(st, nullptr, &t_runs, C.c_keys_out.p, M, C.c_keys_in.p, reinterpret_cast<int32_t*>(C.c_ids_in.p), &C.ctr.p->groups));
-    HIP_TRY(mipgen_consensus_scan_u32(st, nullptr, &t_u32, reinterpret_cast<int32_t*>(C.c_ids_in.p), C.c_ids_in.p, M + 1));
-    HIP_TRY(mipgen_consensus_scan_i64(st, nullptr, &t_i64, nullptr, nullptr, M + 1));
-    if (temp.reserve(std::max(std::max(t_sort, t_runs), std::max(t_u32, t_i64)) + 16)) return MIPGEN_E_NOMEM;
-    size_t tb = 0;
-    auto temp_bytes = [&]() { tb = temp.cap; return &tb; };                  // (every user of the scratch is told its whole size)
     SpanTimer sort_time{h->timing, st}, vote_time{h->timing, st};
     // sort; the runs of the member keys: group key and family size (the fed arrays are free once sorted, and take them)
     sort_time.mark();
-    HIP_TRY(mipgen_consensus_sort(st, temp.p, temp_bytes(), C.c_keys_in.p, C.c_keys_out.p, C.c_ids_in.p, C.c_ids_out.p, N, sort_bits));
-    uint64_t* group_keys = C.c_keys_in.p;
-    int32_t* family = reinterpret_cast<int32_t*>(C.c_ids_in.p);
-    HIP_TRY(mipgen_consensus_runs(st, temp.p, temp_bytes(), C.c_keys_out.p, M, group_keys, family, &C.ctr.p->groups));
+    HIP_TRY(Q.sort(st, N, sort_bits));
+    uint64_t* group_keys = Q.keys.p;
+    int32_t* family = reinterpret_cast<int32_t*>(Q.ids.p);
+    HIP_TRY(Q.runs(st, M, group_keys, family, &C.ctr.p->groups));
     sort_time.mark();
     HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -588,7 +582,7 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
         return MIPGEN_E_NOMEM;
     HIP_TRY(hipMemcpyAsync(R->keys.p, group_keys, (size_t)G * 8, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(R->family.p, family, (size_t)G * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(mipgen_consensus_scan_u32(st, temp.p, temp_bytes(), R->family.p, C.c_start.p, G));
+    HIP_TRY(Q.scan_u32(st, R->family.p, C.c_start.p, G));
     HIP_TRY(mipgen_launch_consensus_partition(st, R->family.p, G, C.c_order.p, C.ctr.p));
     HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -597,9 +591,9 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
     // the length of every group's two consensus reads (entry G stays 0), and from their exclusive sums where each is written
     HIP_TRY(hipMemsetAsync(C.c_ext_len.p, 0, (size_t)(G + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(C.c_lig_len.p, 0, (size_t)(G + 1) * 8, st));
-    HIP_TRY(mipgen_launch_consensus_len(st, S->P.te, S->P.tl, G, C.c_order.p, n_big, C.c_start.p, R->family.p, C.c_ids_out.p, C.c_recs.p, C.c_ext_len.p, C.c_lig_len.p));
-    HIP_TRY(mipgen_consensus_scan_i64(st, temp.p, temp_bytes(), C.c_ext_len.p, R->ext_off.p, G + 1));
-    HIP_TRY(mipgen_consensus_scan_i64(st, temp.p, temp_bytes(), C.c_lig_len.p, R->lig_off.p, G + 1));
+    HIP_TRY(mipgen_launch_consensus_len(st, S->P.te, S->P.tl, G, C.c_order.p, n_big, C.c_start.p, R->family.p, Q.ids_sorted.p, C.c_recs.p, C.c_ext_len.p, C.c_lig_len.p));
+    HIP_TRY(Q.scan_i64(st, C.c_ext_len.p, R->ext_off.p, G + 1));
+    HIP_TRY(Q.scan_i64(st, C.c_lig_len.p, R->lig_off.p, G + 1));
     int64_t totals[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&totals[0], R->ext_off.p + G, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&totals[1], R->lig_off.p + G, 8, hipMemcpyDeviceToHost, st));
@@ -608,7 +602,7 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
         R->lig_qual.reserve((size_t)totals[1] + 1))
         return MIPGEN_E_NOMEM;
     vote_time.mark();
-    HIP_TRY(mipgen_launch_consensus_vote(st, S->P.te, S->P.tl, G, C.c_order.p, n_small, n_big, C.c_start.p, R->family.p, C.c_ids_out.p, C.c_recs.p, R->ext_off.p,
+    HIP_TRY(mipgen_launch_consensus_vote(st, S->P.te, S->P.tl, G, C.c_order.p, n_small, n_big, C.c_start.p, R->family.p, Q.ids_sorted.p, C.c_recs.p, R->ext_off.p,
                                          R->lig_off.p, R->ext_seq.p, R->ext_qual.p, R->lig_seq.p, R->lig_qual.p));
     vote_time.mark();
     // unique tags of a cell = its groups: the group keys ARE the sorted, duplicate-free key list of a plain session
