@@ -587,6 +587,47 @@ int mipgen_accel_reads_consensus_insertion_call(mipgen_accel* h, int32_t row, co
                                                 mipgen_insertion_totals* ins_totals, mipgen_call_totals* call_totals);
 int mipgen_accel_insertion_call_fetch(mipgen_accel* h, mipgen_insertion_call_record* records, int64_t n);
 
+/* ---- insertion alleles per genome locus: folded over the probes that cover it, pooled and called (new entry points only: the ABI number does not change) ----
+ * Inputs of one row: its allele records (4.16: ascending key, pos = template position x, bases in the orientation of M), its anchor table anchors[n_pos][4] (span, ins,
+ * ins_discordant, ambiguous) and a locus plan (4.15).  A source (x, flags) of locus l PULLS one anchor row: row x - 1 under bit 1, row x with flags 0, none on a minus
+ * source without bit 1 - the rule by which the merged table takes its columns 6 and 7; the plan is obeyed as given, so an anchor row is pulled by at most two sources.
+ * locus_anchors[n_loci][4] is the sum of the pulled rows, all four columns together.  Every record of a pulled row becomes a locus allele: pos = l; length and
+ * ambiguous unchanged; bases unchanged on a source with bit 0 clear, and under bit 0 the reverse complement of a non-ambiguous record (base j becomes
+ * 3 - base(length - 1 - j), base 0 still in the most significant used bits); an ambiguous record - a run above 15 bases included - stays bit for bit what it is.
+ * Records of equal key add their counts; the locus records come as mipgen_insertion_record in ascending key order, distinct, the same bytes from call to call.
+ * locus_anchors[:, 1] and [:, 2] equal columns 6 and 7 of the merged 8-column table of the same row; per locus the record counts add up to locus_anchors[:, 1], those
+ * of the ambiguous ones to [:, 3].  totals: loci = loci with a non-zero anchor row; span, insertions, ins_discordant, ambiguous = the column sums; alleles = the locus
+ * records; folded = the (record, source) pairs; dropped = the records no source pulls.  Pool and calls are those of 4.17 with x := l, span := locus_anchors[:, 0] and
+ * n_pos := n_loci on the locus records of every row; a plus and a minus probe place an insertion inside a repeat at opposite ends of it, and those stay two alleles.
+ *   locus_insertion_tables:            from host arrays, no read session needed; locus_anchors and totals may be NULL.
+ *   locus_insertions_fetch:            the locus records of the last fold of the handle (tables, locus_insertions or locus_insertion_call); n must equal totals.alleles.
+ *   consensus_locus_insertions:        the insertions call of `row` - counts, anchors, ins_totals and mipgen_accel_insertions_fetch are its results - folded under the
+ *                                      installed plan.
+ *   consensus_locus_insertion_pool:    4.17's pool over the sample rows with the fold between every row's insertions and the append; it stays with the consensus
+ *                                      reads until the next locus plan.  locus_insertion_pool_fetch: its records and S[n_loci].
+ *   consensus_locus_insertion_call:    recomputes and folds `row` with the pool's arguments, then flags, scores, orders and joins its calls into a run of its own:
+ *                                      mipgen_accel_insertion_call_fetch and mipgen_accel_call_fetch keep finding what they found.  locus_insertion_call_fetch: the
+ *                                      records, pos = the locus; n must equal call_totals.calls.
+ * MIPGEN_E_INVALID: every refusal of the insertions call, of the call parameters and of the plan check; records not strictly ascending; a record position outside
+ * 0..n_pos - 1; a sum of mol_len different from the plan's n_pos; more than 2^29 - 1 locus records in a row; a fetch with another n.  MIPGEN_E_STATE: no consensus
+ * reads; no plan; a call without a locus insertion pool or with another bg_max_ppm than the pool's; a fetch before any call.  MIPGEN_E_NOMEM: the anchor map (8 bytes
+ * per position), the 2 n_records pairs with their sorted copies, scratch and runs, the locus records and locus_anchors against held + free device memory, each before
+ * the allocations it covers.  Timing index 17; indices 11-16 and every other entry point's records are untouched, except that the session calls count into the scratch
+ * of mipgen_accel_reads_consensus_insertions. */
+typedef struct mipgen_locus_insertion_totals { int64_t loci, span, insertions, ins_discordant, ambiguous, alleles, folded, dropped; } mipgen_locus_insertion_totals;
+int mipgen_accel_locus_insertion_tables(mipgen_accel* h, const mipgen_insertion_record* records, int64_t n_records, const int32_t* anchors, const int64_t* plan, int64_t n_pos,
+                                        int64_t n_loci, int32_t* locus_anchors, mipgen_locus_insertion_totals* totals);
+int mipgen_accel_locus_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* records, int64_t n);
+int mipgen_accel_reads_consensus_locus_insertions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                                  int32_t max_indel, int32_t* counts, int32_t* anchors, int32_t* locus_anchors, mipgen_insertion_totals* ins_totals,
+                                                  mipgen_locus_insertion_totals* totals);
+int mipgen_accel_reads_consensus_locus_insertion_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                                      int32_t max_indel, int32_t bg_max_ppm, mipgen_insertion_pool_totals* totals);
+int mipgen_accel_locus_insertion_pool_fetch(mipgen_accel* h, mipgen_insertion_pool_record* pool_records, int64_t n, int32_t* pool_span);
+int mipgen_accel_reads_consensus_locus_insertion_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, int32_t* anchors, int32_t* locus_anchors,
+                                                      mipgen_insertion_totals* ins_totals, mipgen_locus_insertion_totals* locus_totals, mipgen_call_totals* call_totals);
+int mipgen_accel_locus_insertion_call_fetch(mipgen_accel* h, mipgen_insertion_call_record* records, int64_t n);
+
 /* Featurev5::get_long_range_content on the device: extended_seq covers the region +/- 1000 bases
  * (mipgen.cpp:1125-1128,1225); denominator = chrom_seq_stop - chrom_seq_start + 2001 (Featurev5.cpp:49,53). */
 int mipgen_accel_long_range_content(mipgen_accel* h, const char* extended_seq, int32_t len,
@@ -804,7 +845,9 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * included) or mipgen_accel_reads_consensus_call_pool (timing enabled); 14 = the kernels of the last locus call of any kind (mipgen_accel_locus_tables,
  * mipgen_accel_reads_consensus_locus_*), its pileup included (timing enabled); 15 = the kernels of the last mipgen_accel_reads_consensus_insertions, its
  * placement and count included (timing enabled); 16 = the kernels of the last insertion pool or insertion call of either kind (mipgen_accel_insertion_call_tables,
- * mipgen_accel_reads_consensus_insertion_pool, mipgen_accel_reads_consensus_insertion_call), the insertions route of its rows included (timing enabled). */
+ * mipgen_accel_reads_consensus_insertion_pool, mipgen_accel_reads_consensus_insertion_call), the insertions route of its rows included (timing enabled);
+ * 17 = the kernels of the last locus insertions call of any kind (mipgen_accel_locus_insertion_tables, mipgen_accel_reads_consensus_locus_insertions, _locus_insertion_pool,
+ * _locus_insertion_call), the insertions route of its rows included (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -114,6 +114,10 @@ class InsertionTotals(C.Structure):    # mipgen_insertion_totals
     _fields_ = [(n, C.c_int64) for n in ("groups", "used", "span", "insertions", "ins_discordant", "ambiguous", "alleles", "gapped_sides")]
 
 
+class LocusInsertionTotals(C.Structure):    # mipgen_locus_insertion_totals
+    _fields_ = [(n, C.c_int64) for n in ("loci", "span", "insertions", "ins_discordant", "ambiguous", "alleles", "folded", "dropped")]
+
+
 INSERTION_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("count", "<i4"), ("bases", "<u4"), ("ambiguous", "<i4")])   # mipgen_insertion_record, 24 bytes
 INSERTION_POOL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("bases", "<u4"), ("bg_alt", "<i4"), ("bg_excluded", "<i4")])   # mipgen_insertion_pool_record, 24 bytes
 INSERTION_CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("bases", "<u4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4"),
@@ -425,6 +429,21 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_insertion_call_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
     for name in ("insertion_call_tables", "reads_consensus_insertion_pool", "insertion_pool_fetch", "reads_consensus_insertion_call", "insertion_call_fetch"):
         getattr(lib, "mipgen_accel_" + name).restype = C.c_int
+    lib.mipgen_accel_locus_insertion_tables.argtypes = [vp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), i64p_, C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                                        C.POINTER(LocusInsertionTotals)]
+    lib.mipgen_accel_locus_insertions_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
+    lib.mipgen_accel_reads_consensus_locus_insertions.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(InsertionTotals),
+                                                                  C.POINTER(LocusInsertionTotals)]
+    lib.mipgen_accel_reads_consensus_locus_insertion_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                      C.POINTER(InsertionPoolTotals)]
+    lib.mipgen_accel_locus_insertion_pool_fetch.argtypes = [vp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+    lib.mipgen_accel_reads_consensus_locus_insertion_call.argtypes = [vp, C.c_int32, C.POINTER(CallParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                                      C.POINTER(InsertionTotals), C.POINTER(LocusInsertionTotals), C.POINTER(CallTotals)]
+    lib.mipgen_accel_locus_insertion_call_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
+    for name in ("locus_insertion_tables", "locus_insertions_fetch", "reads_consensus_locus_insertions", "reads_consensus_locus_insertion_pool", "locus_insertion_pool_fetch",
+                 "reads_consensus_locus_insertion_call", "locus_insertion_call_fetch"):
+        getattr(lib, "mipgen_accel_" + name).restype = C.c_int
     lib.mipgen_accel_call_tables.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CallParams),
                                              C.POINTER(CallTotals)]
     lib.mipgen_accel_reads_consensus_call_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -532,6 +551,9 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_consensus_insertions", "mipgen_accel_insertions_fetch",
     "mipgen_accel_insertion_call_tables", "mipgen_accel_reads_consensus_insertion_pool", "mipgen_accel_insertion_pool_fetch",
     "mipgen_accel_reads_consensus_insertion_call", "mipgen_accel_insertion_call_fetch",
+    "mipgen_accel_locus_insertion_tables", "mipgen_accel_locus_insertions_fetch", "mipgen_accel_reads_consensus_locus_insertions",
+    "mipgen_accel_reads_consensus_locus_insertion_pool", "mipgen_accel_locus_insertion_pool_fetch", "mipgen_accel_reads_consensus_locus_insertion_call",
+    "mipgen_accel_locus_insertion_call_fetch",
 ]
 
 
@@ -1232,6 +1254,7 @@ class Accel:
         ref = np.frombuffer(bytes(locus_ref), dtype=np.uint8) if isinstance(locus_ref, (bytes, bytearray)) else np.ascontiguousarray(locus_ref, dtype=np.uint8)
         self._check(self.lib.mipgen_accel_reads_consensus_locus_plan(self.h, plan.ctypes.data_as(C.POINTER(C.c_int64)), len(plan), ref.ctypes.data, len(ref)))
         self._locus_shape, self._locus_call_cols = (len(plan), len(ref)), None
+        self._locus_ins_positions = None                                 # (the locus insertion pool goes with the plan it was built under)
 
     def _locus_out(self, rows, cols):
         """An output table of a locus call and its pointer; (None, None) where no wrapper has installed what gives its shape: the library refuses such a call
@@ -1276,6 +1299,77 @@ class Accel:
         tot = GappedTotals()
         self._check(self.lib.mipgen_accel_reads_consensus_locus_call_pileup_totals(self.h, C.byref(tot)))
         return self._totals(tot)
+
+    # insertion alleles per locus
+    def locus_insertions_fetch(self, n: int) -> np.ndarray:
+        """mipgen_accel_locus_insertions_fetch: the n locus records of the last fold as an array of INSERTION_RECORD_DTYPE, pos = the locus, in ascending key order."""
+        records = np.zeros(n, dtype=INSERTION_RECORD_DTYPE)
+        self._check(self.lib.mipgen_accel_locus_insertions_fetch(self.h, records.ctypes.data if n else None, n))
+        return records
+
+    def locus_insertion_tables(self, records, anchors, plan, n_loci: int):
+        """mipgen_accel_locus_insertion_tables: allele records and an anchor table from host arrays folded per locus, no read session needed.  records:
+        INSERTION_RECORD_DTYPE in strictly ascending key order; anchors: int32 [n_pos][4]; plan: int64 [n_pos] as locus_tables takes it.  Returns (locus records,
+        locus_anchors int32 [n_loci][4], the totals dict: loci, span, insertions, ins_discordant, ambiguous, alleles, folded, dropped)."""
+        records = np.ascontiguousarray(records, dtype=INSERTION_RECORD_DTYPE)
+        anchors = np.ascontiguousarray(anchors, dtype=np.int32)
+        plan = np.ascontiguousarray(plan, dtype=np.int64)
+        if anchors.ndim != 2 or anchors.shape != (len(plan), 4):
+            raise ValueError(f"anchors {anchors.shape} do not match a plan of {len(plan)} positions")
+        out = np.empty((max(int(n_loci), 0), 4), dtype=np.int32)
+        tot = LocusInsertionTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_locus_insertion_tables(self.h, records.ctypes.data if len(records) else None, len(records), anchors.ctypes.data_as(i32p),
+                                                                 plan.ctypes.data_as(C.POINTER(C.c_int64)), len(plan), n_loci, out.ctypes.data_as(i32p), C.byref(tot)))
+        return self.locus_insertions_fetch(int(tot.alleles)), out, self._totals(tot)
+
+    def consensus_locus_insertions(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 8):
+        """mipgen_accel_reads_consensus_locus_insertions, callable after consensus_locus_plan: the insertion alleles of one row folded per locus.  Returns (counts,
+        anchors, insertion totals dict - what consensus_insertions returns, and insertions_fetch finds its records -, locus records, locus_anchors [n_loci][4], locus
+        insertion totals dict)."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        counts, counts_p = self._locus_out(total, 8)
+        anchors, anchors_p = self._locus_out(total, 4)
+        loci, loci_p = self._locus_out(self._locus_shape[1] if getattr(self, "_locus_shape", None) else None, 4)
+        it, lt = InsertionTotals(), LocusInsertionTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_insertions(self.h, seq, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), row, min_family, min_quality,
+                                                                           max_indel, counts_p, anchors_p, loci_p, C.byref(it), C.byref(lt)))
+        return counts, anchors, self._totals(it), self.locus_insertions_fetch(int(lt.alleles)), loci, self._totals(lt)
+
+    def consensus_locus_insertion_pool(self, mol_seq, mol_len: Sequence[int], min_family: int = 1, min_quality: int = 0, max_indel: int = 8, bg_max_ppm: int = 200000) -> dict:
+        """mipgen_accel_reads_consensus_locus_insertion_pool, callable after consensus_locus_plan: the sparse pool of locus insertion alleles over the sample rows.
+        Returns the totals dict: rows, entries, alleles."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        tot = InsertionPoolTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_insertion_pool(self.h, seq, lens.ctypes.data_as(C.POINTER(C.c_int32)), len(lens), min_family, min_quality,
+                                                                               max_indel, bg_max_ppm, C.byref(tot)))
+        self._locus_ins_positions = total
+        return self._totals(tot)
+
+    def locus_insertion_pool_fetch(self, n: int):
+        """mipgen_accel_locus_insertion_pool_fetch: (the n distinct records of the locus insertion pool, S per locus as int32 [n_loci])."""
+        records = np.zeros(n, dtype=INSERTION_POOL_RECORD_DTYPE)
+        span = np.zeros(self._locus_shape[1] if getattr(self, "_locus_shape", None) else 0, dtype=np.int32)
+        self._check(self.lib.mipgen_accel_locus_insertion_pool_fetch(self.h, records.ctypes.data if n else None, n, span.ctypes.data_as(C.POINTER(C.c_int32)) if len(span) else None))
+        return records, span
+
+    def locus_insertion_call_fetch(self, n: int) -> np.ndarray:
+        """mipgen_accel_locus_insertion_call_fetch: the n records of the last insertion call per locus as an array of INSERTION_CALL_RECORD_DTYPE, pos = the locus."""
+        records = np.zeros(n, dtype=INSERTION_CALL_RECORD_DTYPE)
+        self._check(self.lib.mipgen_accel_locus_insertion_call_fetch(self.h, records.ctypes.data if n else None, n))
+        return records
+
+    def consensus_locus_insertion_call(self, row: int, params: "CallParams"):
+        """mipgen_accel_reads_consensus_locus_insertion_call, callable after consensus_locus_insertion_pool: the insertion calls of one row per locus.  Returns (counts,
+        anchors, insertion totals dict, locus records, locus_anchors, locus insertion totals dict, call records - pos is the locus -, call totals dict)."""
+        total = getattr(self, "_locus_ins_positions", None)
+        counts, counts_p = self._locus_out(total, 8)
+        anchors, anchors_p = self._locus_out(total, 4)
+        loci, loci_p = self._locus_out(self._locus_shape[1] if getattr(self, "_locus_shape", None) and total is not None else None, 4)
+        it, lt, ct = InsertionTotals(), LocusInsertionTotals(), CallTotals()
+        self._check(self.lib.mipgen_accel_reads_consensus_locus_insertion_call(self.h, row, C.byref(params), counts_p, anchors_p, loci_p, C.byref(it), C.byref(lt), C.byref(ct)))
+        return (counts, anchors, self._totals(it), self.locus_insertions_fetch(int(lt.alleles)), loci, self._totals(lt), self.locus_insertion_call_fetch(int(ct.calls)),
+                self._totals(ct))
 
     def score_candidate_array(self, arr, n: int, method: int) -> np.ndarray:
         """score_candidates() for a ready-made ctypes array of Candidate: scores only."""

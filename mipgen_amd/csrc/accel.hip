@@ -147,6 +147,8 @@ void mipgen_accel_destroy(mipgen_accel* h)
     h->call_run.release();
     h->locus_run.release();
     h->ins_call.release();
+    h->locus_ins.release();
+    h->locus_ins_call.release();
     h->model.release(); h->model_t.release(); h->sv_norm.release(); h->sv_coef.release(); h->sv_center.release(); h->regions.release(); h->bases.release(); h->unmap.release(); h->copy.release();
     h->log_tiles.release(); h->svr_tiles.release(); h->ld_tiles.release(); h->scores.release(); h->records.release();
     h->emitted.release(); h->survivors.release(); h->emitted_per_region.release(); h->pos_region.release(); h->pos_local.release();
@@ -591,6 +593,7 @@ double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which)
     if (h && which == 14) return h->locus_ms;
     if (h && which == 15) return h->insertions_ms;
     if (h && which == 16) return h->ins_call_ms;
+    if (h && which == 17) return h->locus_ins_ms;
     if (!h || !h->timing) return -1.0;
     if (hipSetDevice(h->device) != hipSuccess) return -1.0;
     double total = 0.0;

@@ -305,6 +305,43 @@ struct InsCallRun {
     size_t upload_held() const { return records.cap * sizeof(mipgen_insertion_record) + (span.cap + pool_span.cap) * 4 + pool_keys.cap * 8 + pool_sums.cap * sizeof(InsPoolSums); }
     void release() { run.release(); out.release(); records.release(); span.release(); pool_span.release(); pool_keys.release(); pool_sums.release(); n_calls = -1; }
 };
+// insertion alleles per locus.  What k_locus_anchor_map leaves of a plan: built on the first fold under it, dropped with it
+struct LocusInsMap {
+    DevBuf<uint32_t> own, prev;                              // positions each: locus << 2 | flags of the source that pulls the anchor row, or GAP_LOCUS_NONE
+    bool have = false;
+    size_t held() const { return (own.cap + prev.cap) * 4; }
+    void release() { own.release(); prev.release(); have = false; }
+};
+// One folded row, on the HANDLE (the tables call and the session calls share it, as the calls share a CallRun): the (locus key, record index) pairs and what orders
+// them - run keys and run counts take the place of pairs.keys and pairs.ids once the sort has read them -, the locus records and the locus anchor table
+struct LocusInsFold {
+    SortedPairs pairs;                                       // 2 x the row's records at most
+    DevBuf<uint32_t> run_start;
+    DevBuf<mipgen_insertion_record> records;                 // the locus records of the last fold
+    DevBuf<int32_t> anchors;                                 // loci x INSERTION_COLUMNS
+    DevBuf<LocusInsCounters> ctr;
+    int64_t n_alleles = -1;                                  // the locus records of the last fold (-1: none, or it failed)
+    size_t pair_held() const { return pairs.held() + run_start.cap * 4 + records.cap * sizeof(mipgen_insertion_record); }
+    size_t table_held() const { return anchors.cap * 4 + ctr.cap * sizeof(LocusInsCounters); }
+    void release() { pairs.release(); run_start.release(); records.release(); anchors.release(); ctr.release(); n_alleles = -1; }
+};
+// what mipgen_accel_locus_insertion_tables leaves on the HANDLE beside the fold: its plan, its map and the uploaded arrays
+struct LocusInsRun {
+    LocusPlan plan;
+    LocusInsMap map;
+    DevBuf<mipgen_insertion_record> records;
+    DevBuf<int32_t> anchors;
+    LocusInsFold fold;
+    size_t upload_held() const { return records.cap * sizeof(mipgen_insertion_record) + anchors.cap * 4; }
+    void release() { plan.release(); map.release(); records.release(); anchors.release(); fold.release(); }
+};
+// mipgen_accel_reads_consensus_locus_insertion*: the map of the installed plan and the sparse pool over the loci; released with the reads, dropped with the plan
+struct LocusInsScratch {
+    LocusInsMap map;
+    InsPool pool;
+    void drop() { map.have = false; pool.args.have = false; }
+    void release() { map.release(); pool.release(); }
+};
 struct ConsensusResult {
     int64_t n_groups = 0, ext_bytes = 0, lig_bytes = 0;
     int64_t n = 0, rows = 0;                                 // probes and rows of the session that left the reads: a cell is row * n + probe
@@ -313,12 +350,13 @@ struct ConsensusResult {
     LocusScratch locus;
     InsScratch ins;
     InsPool ins_pool;
+    LocusInsScratch locus_ins;
     DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); locus_ins.release(); }
 };
 
 struct mipgen_accel {
@@ -449,6 +487,9 @@ struct mipgen_accel {
     double insertions_ms = -1.0;     // the kernels of the last mipgen_accel_reads_consensus_insertions (timing enabled)
     InsCallRun ins_call;             // the last insertion call's candidates and records (accel_pileup.hip)
     double ins_call_ms = -1.0;       // the kernels of the last insertion pool or insertion call of either kind (timing enabled)
+    LocusInsRun locus_ins;           // the last fold of insertion alleles to loci, its records and locus anchor table (accel_pileup.hip)
+    InsCallRun locus_ins_call;       // the last insertion call per locus: a run of its own, so that mipgen_accel_insertion_call_fetch keeps finding the last call per probe
+    double locus_ins_ms = -1.0;      // the kernels of the last locus insertions call of any kind, the insertions route of its rows included (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

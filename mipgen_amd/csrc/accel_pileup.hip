@@ -2,7 +2,9 @@
 // mipgen_accel_reads_consensus_pileup) and the same with indels (4.13: _consensus_pileup_gapped), the variant calls made from them (4.14: mipgen_accel_call_tables,
 // _reads_consensus_call_pool, _reads_consensus_call, _call_fetch) and the same per genome locus (4.15: mipgen_accel_locus_tables, _reads_consensus_locus_plan /
 // _locus_pileup / _locus_call_pool / _locus_call), and the insertion alleles of a row (4.16: mipgen_accel_reads_consensus_insertions, mipgen_accel_insertions_fetch) and their calls against a sparse pool over the sample rows (4.17: mipgen_accel_insertion_call_tables,
-// _reads_consensus_insertion_pool, _insertion_pool_fetch, _reads_consensus_insertion_call, _insertion_call_fetch).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
+// _reads_consensus_insertion_pool, _insertion_pool_fetch, _reads_consensus_insertion_call, _insertion_call_fetch) and, folded to genome loci by the installed plan between
+// the insertions of a row and its pool or call (4.19: mipgen_accel_locus_insertion_tables, _locus_insertions_fetch, _reads_consensus_locus_insertions / _locus_insertion_pool /
+// _locus_insertion_call, _locus_insertion_pool_fetch, _locus_insertion_call_fetch: fold_insertions is the one fold).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
 // count_row is the ONE count: the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches of the plain
 // or the gapped table, download and totals of one row into the CountScratch it is given.  Every entry point gives a scratch of its own - `pile` / `gapped` of the
 // ConsensusResult, of its CallScratch, of its LocusScratch, of its InsScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
@@ -547,16 +549,18 @@ static const size_t INS_POOL_ENTRY_BYTES = 8 + 2 * sizeof(InsPoolSums) + 2 * 4;
 
 // The sparse pool over the sample rows: the insertions route of every sample row, its spans added into S and its non-ambiguous records appended as entries;
 // then the entries sorted by key, their runs - the distinct alleles - and the sums of every run.  The caller has made its refusals and dropped the pool that was held.
-static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, int32_t bg_max_ppm, SpanTimer& timer)
+// The pool Q is over n_out anchor rows: the template positions, or the loci, where row_of - which runs the insertions route of sample row r and says
+// where its anchor table and its n_rec records lie on the device - folds the row too.  what: the pool as a message names it.
+template <typename RowOf>
+static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, int32_t bg_max_ppm, SpanTimer& timer, InsPool& Q, int64_t n_out, const char* what, RowOf row_of)
 {
-    InsPool& Q = P.R->ins_pool;
     InsScratch& I = P.R->ins;
     hipStream_t st = h->stream;
-    const size_t np = (size_t)P.n_pos;
+    const size_t np = (size_t)n_out;
     size_t room = 0;
     if (int rc = room_beside(Q.table_held(), &room)) return rc;
     if (padded(np, 4) + padded(1, sizeof(InsPoolCounters)) > room)
-        return fail(MIPGEN_E_NOMEM, "insertion pool: %lld template positions need %zu MiB of device memory beside the insertions', %zu MiB are free", (long long)P.n_pos,
+        return fail(MIPGEN_E_NOMEM, "%s: %lld template positions need %zu MiB of device memory beside the insertions', %zu MiB are free", what, (long long)n_out,
                     (padded(np, 4) + padded(1, sizeof(InsPoolCounters))) >> 20, room >> 20);
     if (Q.S.reserve(np) || Q.ctr.reserve(1)) return MIPGEN_E_NOMEM;
     IdleOnExit idle{st};
@@ -566,27 +570,29 @@ static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
     int64_t used = 0;
     const int64_t rows = sample_rows(P.R);
     for (int64_t r = 0; r < rows; r++) {
-        if (int rc = insertions_row(h, P, A, (int32_t)r, timer, nullptr, nullptr, nullptr)) return rc;
+        const int32_t* row_anchors = nullptr;
+        const mipgen_insertion_record* row_records = nullptr;
+        int64_t n_rec = 0;
+        if (int rc = row_of((int32_t)r, &row_anchors, &row_records, &n_rec)) return rc;
         if (P.R->n_groups == 0) continue;                                // (nothing is on the device: S stays zero and there is no entry)
-        const int64_t n_rec = I.n_alleles;
-        if (used + n_rec > 0x7fffffff) return fail(MIPGEN_E_INVALID, "insertion pool: more than 2^31 - 1 allele records over the sample rows");
+        if (used + n_rec > 0x7fffffff) return fail(MIPGEN_E_INVALID, "%s: more than 2^31 - 1 allele records over the sample rows", what);
         const size_t want = (size_t)(used + n_rec);
         if (want > Q.pairs.keys.cap) {                                         // the entries' bytes, known only now: checked before they are allocated
             const size_t need = padded(want, 8) + padded(want, sizeof(InsPoolSums)) + padded(want, 4);
             if (int rc = room_beside(0, &room)) return rc;
             if (need > room)
-                return fail(MIPGEN_E_NOMEM, "insertion pool: %zu entries need %zu MiB of device memory, %zu MiB are free", want, need >> 20, room >> 20);
+                return fail(MIPGEN_E_NOMEM, "%s: %zu entries need %zu MiB of device memory, %zu MiB are free", what, want, need >> 20, room >> 20);
             if (int rc = grow_keeping(Q.pairs.keys, (size_t)used, want, st)) return rc;
             if (int rc = grow_keeping(Q.sums, (size_t)used, want, st)) return rc;
             if (int rc = grow_keeping(Q.pairs.ids, (size_t)used, want, st)) return rc;
         }
         timer.mark();
-        HIP_TRY(mipgen_launch_ins_pool_append(st, I.anchors.p, P.n_pos, I.records.p, n_rec, bg_max_ppm, Q.S.p, Q.pairs.keys.p, Q.sums.p, Q.pairs.ids.p, (int64_t)want, Q.ctr.p));
+        HIP_TRY(mipgen_launch_ins_pool_append(st, row_anchors, n_out, row_records, n_rec, bg_max_ppm, Q.S.p, Q.pairs.keys.p, Q.sums.p, Q.pairs.ids.p, (int64_t)want, Q.ctr.p));
         timer.mark();
         HIP_TRY(hipMemcpyAsync(&pc, Q.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if ((int64_t)pc.entries < used || (int64_t)pc.entries > used + n_rec)
-            return fail(MIPGEN_E_STATE, "insertion pool: %llu entries after row %lld, %lld before it and %lld records", pc.entries, (long long)r, (long long)used, (long long)n_rec);
+            return fail(MIPGEN_E_STATE, "%s: %llu entries after row %lld, %lld before it and %lld records", what, pc.entries, (long long)r, (long long)used, (long long)n_rec);
         used = (int64_t)pc.entries;
     }
     I.n_alleles = -1;                                                    // (the records of the last sample row are no call's result)
@@ -597,7 +603,7 @@ static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
         const size_t need = SortedPairs::bytes(ne, scratch) + padded(ne, INS_POOL_ENTRY_BYTES);
         if (int rc = room_beside(Q.entry_held(), &room)) return rc;
         if (need > room)
-            return fail(MIPGEN_E_NOMEM, "insertion pool: %lld entries need %zu MiB of device memory, %zu MiB are free", (long long)used, need >> 20, room >> 20);
+            return fail(MIPGEN_E_NOMEM, "%s: %lld entries need %zu MiB of device memory, %zu MiB are free", what, (long long)used, need >> 20, room >> 20);
         // (keys and ids hold the entries and are large enough: the reserve adds their sorted copies and the scratch)
         if (Q.pairs.reserve(ne, scratch) || Q.pool_keys.reserve(ne) || Q.pool_sums.reserve(ne) || Q.run_counts.reserve(ne) || Q.run_start.reserve(ne)) return MIPGEN_E_NOMEM;
         timer.mark();
@@ -609,21 +615,20 @@ static int build_ins_pool(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
         HIP_TRY(hipMemcpyAsync(&pc, Q.ctr.p, sizeof pc, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(idle.wait());
-    if ((int64_t)pc.alleles > used || (used > 0 && pc.alleles == 0)) return fail(MIPGEN_E_STATE, "insertion pool: %llu alleles of %lld entries", pc.alleles, (long long)used);
+    if ((int64_t)pc.alleles > used || (used > 0 && pc.alleles == 0)) return fail(MIPGEN_E_STATE, "%s: %llu alleles of %lld entries", what, pc.alleles, (long long)used);
     Q.release_transient();
-    Q.n_pos = P.n_pos; Q.rows = rows; Q.n_entries = used; Q.n_alleles = (int64_t)pc.alleles;
+    Q.n_pos = n_out; Q.rows = rows; Q.n_entries = used; Q.n_alleles = (int64_t)pc.alleles;
     Q.args.remember(A, P.n_pos, bg_max_ppm);
     return MIPGEN_OK;
 }
 
 // The insertion calls of n_rec allele records on the device (ascending; span[x * span_stride] the row's span of anchor x) against a sparse pool there, into
-// h->ins_call: k_ins_call_flag, the tail every call shares, and the join of the calls with their allele records.  The stream is idle and h->ins_call.n_calls set on
-// success.
-static int run_ins_call(mipgen_accel* h, const mipgen_insertion_record* records, int64_t n_rec, const int32_t* span, int span_stride, int64_t n_pos, const uint64_t* pool_keys,
+// V (h->ins_call; h->locus_ins_call for the calls per locus of DESIGN 4.19): k_ins_call_flag, the tail every call shares, and the join of the calls with their allele
+// records.  The stream is idle and V.n_calls set on success.
+static int run_ins_call(mipgen_accel* h, InsCallRun& V, const mipgen_insertion_record* records, int64_t n_rec, const int32_t* span, int span_stride, int64_t n_pos, const uint64_t* pool_keys,
                         const InsPoolSums* pool_sums, int64_t n_pool, const int32_t* pool_span, bool own_row_is_sample, const mipgen_call_params& prm, SpanTimer& timer,
                         mipgen_call_totals* totals)
 {
-    InsCallRun& V = h->ins_call;
     V.n_calls = -1;
     if (n_rec > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "insertion call: %lld allele records in the row: 2^29 - 1 at most", (long long)n_rec);
     if (n_rec == 0) {
@@ -655,8 +660,30 @@ static int run_ins_call(mipgen_accel* h, const mipgen_insertion_record* records,
     return MIPGEN_OK;
 }
 
-// What the three fetch calls share once the handle is there: the `held` records of the last call (below 0: none, `none` is the refusal's text) from `from` on the device
-// into records[0, n); what: the call as the message of a wrong n names it.
+// the distinct records of a sparse pool that is held, in ascending key order, and S over its anchor rows
+static int fetch_ins_pool(mipgen_accel* h, const InsPool& Q, mipgen_insertion_pool_record* pool_records, int64_t n, int32_t* pool_span)
+{
+    if (n != Q.n_alleles) return fail(MIPGEN_E_INVALID, "%lld pool records asked: the insertion pool holds %lld", (long long)n, (long long)Q.n_alleles);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    std::vector<uint64_t> keys((size_t)n);
+    std::vector<InsPoolSums> sums((size_t)n);
+    {
+        IdleOnExit idle{st};
+        if (n && pool_records) {
+            HIP_TRY(hipMemcpyAsync(keys.data(), Q.pool_keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(sums.data(), Q.pool_sums.p, (size_t)n * sizeof(InsPoolSums), hipMemcpyDeviceToHost, st));
+        }
+        if (pool_span) HIP_TRY(hipMemcpyAsync(pool_span, Q.S.p, (size_t)Q.n_pos * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(idle.wait());
+    }
+    for (int64_t i = 0; pool_records && i < n; i++) {
+        const uint64_t key = keys[(size_t)i];
+        pool_records[i] = {gap_allele_pos(key), gap_allele_length(key), gap_allele_bases(key), sums[(size_t)i].K, sums[(size_t)i].X};
+    }
+    return MIPGEN_OK;
+}
+
 template <typename Record>
 static int fetch_records(mipgen_accel* h, const DevBuf<Record>& from, int64_t held, const char* none, const char* what, Record* records, int64_t n)
 {
@@ -668,6 +695,110 @@ static int fetch_records(mipgen_accel* h, const DevBuf<Record>& from, int64_t he
     HIP_TRY(hipMemcpyAsync(records, from.p, (size_t)n * sizeof(Record), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MIPGEN_OK;
+}
+
+// ---- insertion alleles per locus -----------------------------------------------------------------------------------------------------------------
+// every refusal of allele records given from the host: positions inside the table, lengths that a key can hold, strictly ascending keys
+static int check_insertion_records(const mipgen_insertion_record* records, int64_t n_records, int64_t n_pos)
+{
+    uint64_t before = 0;
+    for (int64_t i = 0; i < n_records; i++) {
+        const mipgen_insertion_record& r = records[i];
+        if (r.pos < 0 || r.pos >= n_pos) return fail(MIPGEN_E_INVALID, "allele record %lld: position %lld of %lld", (long long)i, (long long)r.pos, (long long)n_pos);
+        if (r.length < 1 || (!r.ambiguous && r.length > GAP_ALLELE_MAX_LEN))
+            return fail(MIPGEN_E_INVALID, "allele record %lld: length %d (1 to %d bases are spelt out; a longer allele is ambiguous)", (long long)i, r.length, GAP_ALLELE_MAX_LEN);
+        const uint64_t key = gap_allele_key(r.pos, r.length, r.ambiguous != 0, r.bases);
+        if (i && key <= before) return fail(MIPGEN_E_INVALID, "allele record %lld: the records are not in strictly ascending key order", (long long)i);
+        before = key;
+    }
+    return MIPGEN_OK;
+}
+
+// The allele records of one row on the device (ascending; n_rec of them, 0 with records NULL) and its anchor table there (NULL: a session without groups left none,
+// and the row is all zero) folded under the plan L into F: the map of the plan built first when M does not hold it; then the (locus key, record index) pairs, their
+// sort, runs and scan, a locus record per run, and the locus anchor table with its totals - spans of `timer`.  Each budget is checked before the allocations it
+// covers.  F.n_alleles locus records and F.anchors stay on the device; locus_anchors (may be NULL) a copy, totals (may be NULL) the sums.  The stream is idle on return.
+static int fold_insertions(mipgen_accel* h, const LocusPlan& L, LocusInsMap& M, LocusInsFold& F, const mipgen_insertion_record* records, int64_t n_rec, const int32_t* anchors,
+                           SpanTimer& timer, int32_t* locus_anchors, mipgen_locus_insertion_totals* totals)
+{
+    F.n_alleles = -1;
+    hipStream_t st = h->stream;
+    const size_t np = (size_t)L.n_pos, nl = (size_t)L.n_loci, cells = nl * INSERTION_COLUMNS;
+    if (n_rec > 0x3fffffff) return fail(MIPGEN_E_INVALID, "locus insertions: %lld allele records in the row: twice as many pairs do not fit the sort", (long long)n_rec);
+    size_t room = 0;
+    if (!M.have) {
+        if (int rc = room_beside(M.held(), &room)) return rc;
+        if (2 * padded(np, 4) > room)
+            return fail(MIPGEN_E_NOMEM, "locus insertions: the anchor map of %lld positions needs %zu MiB of device memory, %zu MiB are free", (long long)L.n_pos,
+                        (2 * padded(np, 4)) >> 20, room >> 20);
+        if (M.own.reserve(np) || M.prev.reserve(np)) return MIPGEN_E_NOMEM;
+    }
+    if (int rc = room_beside(F.table_held(), &room)) return rc;
+    if (padded(cells, 4) + padded(1, sizeof(LocusInsCounters)) > room)
+        return fail(MIPGEN_E_NOMEM, "locus insertions: %lld loci need %zu MiB of device memory, %zu MiB are free", (long long)L.n_loci,
+                    (padded(cells, 4) + padded(1, sizeof(LocusInsCounters))) >> 20, room >> 20);
+    if (F.anchors.reserve(cells) || F.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    const int64_t cap = 2 * n_rec;
+    if (n_rec > 0) {
+        size_t scratch = 0;
+        HIP_TRY(SortedPairs::scratch_bytes(st, cap, 64, cap, cap, &scratch));
+        const size_t need = SortedPairs::bytes((size_t)cap, scratch) + padded((size_t)cap, 4) + padded((size_t)cap, sizeof(mipgen_insertion_record));
+        if (int rc = room_beside(F.pair_held(), &room)) return rc;
+        if (need > room)
+            return fail(MIPGEN_E_NOMEM, "locus insertions: %lld allele records need up to %zu MiB of device memory, %zu MiB are free", (long long)n_rec, need >> 20, room >> 20);
+        if (F.pairs.reserve((size_t)cap, scratch) || F.run_start.reserve((size_t)cap) || F.records.reserve((size_t)cap)) return MIPGEN_E_NOMEM;
+    }
+    IdleOnExit idle{st};
+    LocusInsCounters lc;
+    memset(&lc, 0, sizeof lc);
+    HIP_TRY(hipMemsetAsync(F.ctr.p, 0, sizeof lc, st));
+    timer.mark();
+    if (!M.have) {
+        HIP_TRY(hipMemsetAsync(M.own.p, 0xff, np * 4, st));
+        HIP_TRY(hipMemsetAsync(M.prev.p, 0xff, np * 4, st));
+        HIP_TRY(mipgen_launch_locus_anchor_map(st, L.src.p, L.first.p, L.n_pos, L.n_loci, M.own.p, M.prev.p));
+        M.have = true;
+    }
+    if (anchors) HIP_TRY(mipgen_launch_locus_anchor_merge(st, anchors, L.src.p, L.first.p, L.n_pos, L.n_loci, F.anchors.p, F.ctr.p));
+    else HIP_TRY(hipMemsetAsync(F.anchors.p, 0, cells * sizeof(int32_t), st));
+    if (n_rec > 0) HIP_TRY(mipgen_launch_locus_ins_fold(st, records, n_rec, M.own.p, M.prev.p, L.n_pos, F.pairs.keys.p, F.pairs.ids.p, cap, F.ctr.p));
+    timer.mark();
+    HIP_TRY(hipMemcpyAsync(&lc, F.ctr.p, sizeof lc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t folded = (int64_t)lc.folded;
+    if (folded < 0 || folded > cap || (int64_t)lc.dropped > n_rec)
+        return fail(MIPGEN_E_STATE, "locus insertions: %llu pairs and %llu records without a source of %lld records", lc.folded, lc.dropped, (long long)n_rec);
+    if (folded > 0) {
+        timer.mark();
+        int32_t* run_counts = reinterpret_cast<int32_t*>(F.pairs.ids.p);
+        HIP_TRY(F.pairs.sort(st, folded, 64));
+        HIP_TRY(F.pairs.runs(st, folded, F.pairs.keys.p, run_counts, &F.ctr.p->alleles));
+        HIP_TRY(F.pairs.scan_u32(st, run_counts, F.run_start.p, folded));          // (beyond the runs the lengths are stale and the starts unread)
+        HIP_TRY(mipgen_launch_locus_ins_reduce(st, F.pairs.keys.p, run_counts, F.run_start.p, &F.ctr.p->alleles, folded, F.pairs.ids_sorted.p, records, n_rec, F.records.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&lc, F.ctr.p, sizeof lc, hipMemcpyDeviceToHost, st));
+    }
+    if (locus_anchors) HIP_TRY(hipMemcpyAsync(locus_anchors, F.anchors.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    if ((int64_t)lc.alleles > folded || (folded > 0 && lc.alleles == 0)) return fail(MIPGEN_E_STATE, "locus insertions: %llu locus records of %lld pairs", lc.alleles, (long long)folded);
+    if ((int64_t)lc.alleles > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "locus insertions: %llu locus records in the row: 2^29 - 1 at most", lc.alleles);
+    F.n_alleles = (int64_t)lc.alleles;
+    if (totals)
+        *totals = {(int64_t)lc.loci, (int64_t)lc.span, (int64_t)lc.insertions, (int64_t)lc.ins_discordant, (int64_t)lc.ambiguous, F.n_alleles, folded, (int64_t)lc.dropped};
+    return MIPGEN_OK;
+}
+
+// One planned row of the session through the insertions route (into R->ins, as the insertion pool and call of 4.17 count) and folded under the installed plan into
+// the handle's fold.  counts, anchors, ins_totals: what the plain insertions call returns (each may be NULL).
+static int locus_insertions_row(mipgen_accel* h, const RowPlan& P, const RowArgs& A, int32_t row, SpanTimer& timer, int32_t* counts, int32_t* anchors, int32_t* locus_anchors,
+                                mipgen_insertion_totals* ins_totals, mipgen_locus_insertion_totals* totals)
+{
+    h->locus_ins.fold.n_alleles = -1;
+    if (int rc = insertions_row(h, P, A, row, timer, counts, anchors, ins_totals)) return rc;
+    const InsScratch& I = P.R->ins;
+    const bool on_device = P.R->n_groups != 0;
+    return fold_insertions(h, P.R->locus.plan, P.R->locus_ins.map, h->locus_ins.fold, on_device ? I.records.p : nullptr, on_device ? I.n_alleles : 0,
+                           on_device ? I.anchors.p : nullptr, timer, locus_anchors, totals);
 }
 
 extern "C" {
@@ -777,7 +908,7 @@ int mipgen_accel_insertion_call_tables(mipgen_accel* h, const mipgen_insertion_r
     if (nq) HIP_TRY(hipMemcpyAsync(V.pool_keys.p, keys.data(), nq * 8, hipMemcpyHostToDevice, st));
     if (nq) HIP_TRY(hipMemcpyAsync(V.pool_sums.p, sums.data(), nq * sizeof(InsPoolSums), hipMemcpyHostToDevice, st));
     SpanTimer timer{h->timing, st};
-    if (int rc = run_ins_call(h, V.records.p, n_records, V.span.p, 1, n_pos, V.pool_keys.p, V.pool_sums.p, n_pool, V.pool_span.p, own_row_is_sample != 0, *params, timer, totals))
+    if (int rc = run_ins_call(h, V, V.records.p, n_records, V.span.p, 1, n_pos, V.pool_keys.p, V.pool_sums.p, n_pool, V.pool_span.p, own_row_is_sample != 0, *params, timer, totals))
         return rc;
     return booked(timer, &h->ins_call_ms);
 }
@@ -794,7 +925,12 @@ int mipgen_accel_reads_consensus_insertion_pool(mipgen_accel* h, const char* mol
     Q.args.have = false;                                                 // (a pool that fails leaves none)
     h->ins_call_ms = -1.0;
     SpanTimer timer{h->timing, h->stream};
-    if (int rc = build_ins_pool(h, P, A, bg_max_ppm, timer)) return rc;
+    const InsScratch& I = P.R->ins;
+    if (int rc = build_ins_pool(h, P, A, bg_max_ppm, timer, Q, P.n_pos, "insertion pool", [&](int32_t r, const int32_t** anchors, const mipgen_insertion_record** records, int64_t* n_rec) {
+            if (int rc = insertions_row(h, P, A, r, timer, nullptr, nullptr, nullptr)) return rc;
+            *anchors = I.anchors.p; *records = I.records.p; *n_rec = I.n_alleles;
+            return (int)MIPGEN_OK;
+        })) return rc;
     if (totals) *totals = {Q.rows, Q.n_entries, Q.n_alleles};
     return booked(timer, &h->ins_call_ms);
 }
@@ -805,25 +941,7 @@ int mipgen_accel_insertion_pool_fetch(mipgen_accel* h, mipgen_insertion_pool_rec
     if (int rc = check_reads(h)) return rc;
     const InsPool& Q = h->consensus->ins_pool;
     if (!Q.args.have) return fail(MIPGEN_E_STATE, "the consensus reads have no insertion pool: mipgen_accel_reads_consensus_insertion_pool builds it");
-    if (n != Q.n_alleles) return fail(MIPGEN_E_INVALID, "%lld pool records asked: the insertion pool holds %lld", (long long)n, (long long)Q.n_alleles);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    std::vector<uint64_t> keys((size_t)n);
-    std::vector<InsPoolSums> sums((size_t)n);
-    {
-        IdleOnExit idle{st};
-        if (n && pool_records) {
-            HIP_TRY(hipMemcpyAsync(keys.data(), Q.pool_keys.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(sums.data(), Q.pool_sums.p, (size_t)n * sizeof(InsPoolSums), hipMemcpyDeviceToHost, st));
-        }
-        if (pool_span) HIP_TRY(hipMemcpyAsync(pool_span, Q.S.p, (size_t)Q.n_pos * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(idle.wait());
-    }
-    for (int64_t i = 0; pool_records && i < n; i++) {
-        const uint64_t key = keys[(size_t)i];
-        pool_records[i] = {gap_allele_pos(key), gap_allele_length(key), gap_allele_bases(key), sums[(size_t)i].K, sums[(size_t)i].X};
-    }
-    return MIPGEN_OK;
+    return fetch_ins_pool(h, Q, pool_records, n, pool_span);
 }
 
 // The insertion calls of one row against the sparse pool: the row's insertions recomputed with the pool's arguments into R->ins, where
@@ -843,7 +961,7 @@ int mipgen_accel_reads_consensus_insertion_call(mipgen_accel* h, int32_t row, co
     SpanTimer timer{h->timing, h->stream};
     if (int rc = insertions_row(h, P, A, row, timer, counts, anchors, ins_totals)) return rc;
     const InsScratch& I = P.R->ins;
-    if (int rc = run_ins_call(h, I.records.p, I.n_alleles, I.anchors.p, INSERTION_COLUMNS, P.n_pos, Q.pool_keys.p, Q.pool_sums.p, Q.n_alleles, Q.S.p,
+    if (int rc = run_ins_call(h, h->ins_call, I.records.p, I.n_alleles, I.anchors.p, INSERTION_COLUMNS, P.n_pos, Q.pool_keys.p, Q.pool_sums.p, Q.n_alleles, Q.S.p,
                               (int64_t)row < sample_rows(P.R), *params, timer, call_totals)) return rc;
     return booked(timer, &h->ins_call_ms);
 }
@@ -962,7 +1080,7 @@ int mipgen_accel_reads_consensus_locus_plan(mipgen_accel* h, const int64_t* plan
     h->locus_ms = -1.0;
     SpanTimer timer{h->timing, h->stream};
     const int built = build_locus_plan(h, L.plan, plan, n_pos, n_loci, padded((size_t)n_loci, 1), L.ref.cap, "locus plan", timer);
-    if (!L.plan.have || built == MIPGEN_OK) L.state.drop();                      // the pool goes with its plan: a plan refused for its budget leaves both as they were
+    if (!L.plan.have || built == MIPGEN_OK) { L.state.drop(); h->consensus->locus_ins.drop(); }      // the pools and the anchor map go with their plan: a plan refused for its budget leaves them as they were
     if (built) return built;
     L.plan.have = false;                                                 // (until the ref bytes are there too)
     if (L.ref.reserve((size_t)n_loci)) return MIPGEN_E_NOMEM;
@@ -1050,6 +1168,127 @@ int mipgen_accel_call_fetch(mipgen_accel* h, mipgen_call_record* records, int64_
     if (!h) return fail(MIPGEN_E_INVALID, "null handle");
     return fetch_records(h, h->call_run.records, h->call_run.n_calls, "the handle holds no calls: mipgen_accel_call_tables or mipgen_accel_reads_consensus_call leaves them", "call",
                          records, n);
+}
+
+// ---- insertion alleles per locus ----
+// Allele records and an anchor table from host arrays folded by a plan from host arrays: no read session is needed; everything is uploaded into the handle's LocusInsRun.
+int mipgen_accel_locus_insertion_tables(mipgen_accel* h, const mipgen_insertion_record* records, int64_t n_records, const int32_t* anchors, const int64_t* plan, int64_t n_pos,
+                                        int64_t n_loci, int32_t* locus_anchors, mipgen_locus_insertion_totals* totals)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!anchors || (n_records && !records)) return fail(MIPGEN_E_INVALID, "bad arguments: no anchor table or no allele records");
+    if (int rc = check_locus_plan(plan, n_pos, n_loci)) return rc;
+    if (n_records < 0 || n_records > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld allele records: 0 to 2^29 - 1", (long long)n_records);
+    if (int rc = check_insertion_records(records, n_records, n_pos)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    LocusInsRun& U = h->locus_ins;
+    U.fold.n_alleles = -1;
+    U.map.have = false;                                                  // (the map is of the plan of this call)
+    h->locus_ins_ms = -1.0;
+    const size_t np = (size_t)n_pos, nr = (size_t)n_records;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = build_locus_plan(h, U.plan, plan, n_pos, n_loci, padded(np * INSERTION_COLUMNS, 4) + padded(nr, sizeof(mipgen_insertion_record)), U.upload_held(),
+                                  "locus insertion tables", timer)) return rc;
+    if (U.anchors.reserve(np * INSERTION_COLUMNS) || U.records.reserve(std::max<size_t>(nr, 1))) return MIPGEN_E_NOMEM;
+    {
+        IdleOnExit idle{h->stream};
+        HIP_TRY(hipMemcpyAsync(U.anchors.p, anchors, np * INSERTION_COLUMNS * 4, hipMemcpyHostToDevice, h->stream));
+        if (nr) HIP_TRY(hipMemcpyAsync(U.records.p, records, nr * sizeof(mipgen_insertion_record), hipMemcpyHostToDevice, h->stream));
+    }
+    if (int rc = fold_insertions(h, U.plan, U.map, U.fold, U.records.p, n_records, U.anchors.p, timer, locus_anchors, totals)) return rc;
+    return booked(timer, &h->locus_ins_ms);
+}
+
+// The locus records of the last fold the handle made - the tables call, the locus insertions call or the locus insertion call -, in ascending key order.
+int mipgen_accel_locus_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* records, int64_t n)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    return fetch_records(h, h->locus_ins.fold.records, h->locus_ins.fold.n_alleles,
+                         "the handle holds no locus insertion alleles: mipgen_accel_locus_insertion_tables or mipgen_accel_reads_consensus_locus_insertions leaves them",
+                         "locus insertions call", records, n);
+}
+
+// The insertion alleles of one row (4.16, into R->ins) folded under the installed plan.  Writes R->ins, R->locus_ins.map and the handle's fold.
+int mipgen_accel_reads_consensus_locus_insertions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                                  int32_t max_indel, int32_t* counts, int32_t* anchors, int32_t* locus_anchors, mipgen_insertion_totals* ins_totals,
+                                                  mipgen_locus_insertion_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
+    if (int rc = plan_insertions(h, A, row, &P)) return rc;
+    if (int rc = check_locus_session(P.R->locus, P)) return rc;
+    h->locus_ins_ms = -1.0;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = locus_insertions_row(h, P, A, row, timer, counts, anchors, locus_anchors, ins_totals, totals)) return rc;
+    return booked(timer, &h->locus_ins_ms);
+}
+
+// The sparse pool over the sample rows, per locus: 4.17's pool with every row folded between its insertions and the append.  Writes R->locus_ins and, through the
+// insertions route of every row, R->ins.
+int mipgen_accel_reads_consensus_locus_insertion_pool(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t min_family, int32_t min_quality,
+                                                      int32_t max_indel, int32_t bg_max_ppm, mipgen_insertion_pool_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true, true};
+    if (int rc = plan_insertions(h, A, 0, &P)) return rc;
+    if (int rc = check_bg_max_ppm(bg_max_ppm)) return rc;
+    if (int rc = check_locus_session(P.R->locus, P)) return rc;
+    InsPool& Q = P.R->locus_ins.pool;
+    Q.args.have = false;                                                 // (a pool that fails leaves none)
+    h->locus_ins_ms = -1.0;
+    LocusInsFold& F = h->locus_ins.fold;
+    SpanTimer timer{h->timing, h->stream};
+    const int built = build_ins_pool(h, P, A, bg_max_ppm, timer, Q, P.R->locus.plan.n_loci, "locus insertion pool",
+                                     [&](int32_t r, const int32_t** anchors, const mipgen_insertion_record** records, int64_t* n_rec) {
+            if (int rc = locus_insertions_row(h, P, A, r, timer, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+            *anchors = F.anchors.p; *records = F.records.p; *n_rec = F.n_alleles;
+            return (int)MIPGEN_OK;
+        });
+    F.n_alleles = -1;                                                    // (the locus records of the last sample row are no call's result)
+    if (built) return built;
+    if (totals) *totals = {Q.rows, Q.n_entries, Q.n_alleles};
+    return booked(timer, &h->locus_ins_ms);
+}
+
+// The distinct records of the locus insertion pool, in ascending key order, and S over the loci.
+int mipgen_accel_locus_insertion_pool_fetch(mipgen_accel* h, mipgen_insertion_pool_record* pool_records, int64_t n, int32_t* pool_span)
+{
+    if (int rc = check_reads(h)) return rc;
+    const InsPool& Q = h->consensus->locus_ins.pool;
+    if (!Q.args.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus insertion pool: mipgen_accel_reads_consensus_locus_insertion_pool builds it");
+    return fetch_ins_pool(h, Q, pool_records, n, pool_span);
+}
+
+// The insertion calls of one row per locus against the locus insertion pool: the row's insertions recomputed with the pool's arguments and folded, then 4.17's
+// flag, tail, order and join over the locus records and the locus anchor table, into a run of its own.
+int mipgen_accel_reads_consensus_locus_insertion_call(mipgen_accel* h, int32_t row, const mipgen_call_params* params, int32_t* counts, int32_t* anchors, int32_t* locus_anchors,
+                                                      mipgen_insertion_totals* ins_totals, mipgen_locus_insertion_totals* locus_totals, mipgen_call_totals* call_totals)
+{
+    if (int rc = check_reads(h)) return rc;
+    const LocusScratch& L = h->consensus->locus;
+    const InsPool& Q = h->consensus->locus_ins.pool;
+    if (!L.plan.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus plan: mipgen_accel_reads_consensus_locus_plan installs it");
+    if (!Q.args.have) return fail(MIPGEN_E_STATE, "the consensus reads have no locus insertion pool: mipgen_accel_reads_consensus_locus_insertion_pool builds it");
+    RowPlan P;
+    RowArgs A;
+    if (int rc = plan_call(h, Q.args, row, params, "locus insertion pool", &A, &P)) return rc;
+    A.need_seq = A.must_place = A.runs = true;
+    h->locus_ins_ms = -1.0;
+    h->locus_ins_call.n_calls = -1;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = locus_insertions_row(h, P, A, row, timer, counts, anchors, locus_anchors, ins_totals, locus_totals)) return rc;
+    const LocusInsFold& F = h->locus_ins.fold;
+    if (int rc = run_ins_call(h, h->locus_ins_call, F.records.p, F.n_alleles, F.anchors.p, INSERTION_COLUMNS, L.plan.n_loci, Q.pool_keys.p, Q.pool_sums.p, Q.n_alleles, Q.S.p,
+                              (int64_t)row < sample_rows(P.R), *params, timer, call_totals)) return rc;
+    return booked(timer, &h->locus_ins_ms);
+}
+
+// The records of the last insertion call per locus, in ascending allele-key order; pos is the locus.
+int mipgen_accel_locus_insertion_call_fetch(mipgen_accel* h, mipgen_insertion_call_record* records, int64_t n)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    return fetch_records(h, h->locus_ins_call.out, h->locus_ins_call.n_calls,
+                         "the handle holds no locus insertion calls: mipgen_accel_reads_consensus_locus_insertion_call leaves them", "locus insertion call", records, n);
 }
 
 }  // extern "C"

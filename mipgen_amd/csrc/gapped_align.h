@@ -178,6 +178,28 @@ GAP_HD bool gap_allele_ambiguous(uint64_t key) { return ((key >> 30) & 1u) != 0;
 GAP_HD int gap_allele_length(uint64_t key) { const int l = (int)((key >> 31) & 15u); return l ? l : (int)(key & 0x3fffffffu); }
 GAP_HD uint32_t gap_allele_bases(uint64_t key) { return ((key >> 31) & 15u) ? (uint32_t)(key & 0x3fffffffu) : 0u; }
 
+// ---- insertion alleles per genome locus -----------------------------------------------------------------------------------------------------
+// The reverse complement of the l bases (1..GAP_ALLELE_MAX_LEN) of an allele over the 2-bit codes: base j becomes 3 - base(l - 1 - j), base 0 still in the most
+// significant of the 2 l used bits.  Complement = every used bit flipped; the reverse = the sixteen 2-bit groups of the word swapped end for end, then shifted down.
+GAP_HD uint32_t gap_allele_revcomp(uint32_t bases, int l)
+{
+    uint32_t v = ~bases & ((1u << (2 * l)) - 1u);
+    v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
+    v = ((v >> 4) & 0x0f0f0f0fu) | ((v & 0x0f0f0f0fu) << 4);
+    v = ((v >> 8) & 0x00ff00ffu) | ((v & 0x00ff00ffu) << 8);
+    v = (v >> 16) | (v << 16);
+    return v >> (32 - 2 * l);
+}
+
+// The key of the locus allele a record (length l, ambiguous, bases) becomes under the plan word `word` = locus << 2 | flags of the source that pulls it: the
+// position is the locus; a non-ambiguous record turns under bit 0; an ambiguous one - a run above GAP_ALLELE_MAX_LEN included - stays bit for bit what it is.
+GAP_HD uint64_t gap_locus_allele_key(uint32_t word, int l, bool ambiguous, uint32_t bases)
+{
+    const bool turn = (word & 1u) && !ambiguous && l >= 1 && l <= GAP_ALLELE_MAX_LEN;
+    return gap_allele_key((int64_t)(word >> 2), l, ambiguous, turn ? gap_allele_revcomp(bases, l) : bases);
+}
+#define GAP_LOCUS_NONE 0xFFFFFFFFu   // own[a] / prev[a] of an anchor row no source pulls
+
 // ---- the serial row: what k_gap_align's lanes do for row i >= 1, one lane after the other (host only) ----------------------------------------------------
 // h_prev / h: the GAP_LANES values of row i - 1 / i (GAP_NEG outside the band); q_byte = q[i - 1]; two words of directions go to dirs2.
 static inline void gap_row_serial(int i, int W, int L, int side, int q_byte, const uint8_t* M, const int* h_prev, int* h, uint32_t* dirs2)

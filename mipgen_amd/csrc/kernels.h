@@ -68,6 +68,9 @@ struct InsPoolCounters { unsigned long long entries, alleles; };
 // loci: the totals of a merged table, as k_locus_sum counts them
 struct LocusCounters { unsigned long long covered, bases, discordant, deletions, insertions, ins_discordant; };
 
+// insertion alleles per locus: the totals of a locus anchor table, the runs of the sorted pairs, the (record, source) pairs and the records no source pulls
+struct LocusInsCounters { unsigned long long loci, span, insertions, ins_discordant, ambiguous, alleles, folded, dropped; };
+
 extern "C" {
 // kernels_logistic.hip, kernels_logistic_dense.hip: the two producers of the dense grid's records, bit-identical - both stage the tile's bases and take
 // every window count from prefix_words.h, the record rules from mip_record.h and the bounds skips from mip_bounds.h.  k_records_logistic (one candidate per
@@ -212,4 +215,14 @@ hipError_t mipgen_launch_locus_index(hipStream_t, const uint64_t* keys_sorted, c
                                      uint32_t* first);
 hipError_t mipgen_launch_locus_merge(hipStream_t, const int32_t* counts, int columns, const uint32_t* src, const uint32_t* first, int64_t n_pos, int64_t n_loci,
                                      int32_t* merged, LocusCounters* ctr);
+// kernels_locus_insertions.hip: own / prev of every anchor row from the sources of a plan (both GAP_LOCUS_NONE on entry); the (locus key, record index)
+// pairs of a row's allele records (at most cap = 2 n_records; ctr zero on entry); the locus records of the runs of the sorted pairs; the anchor table folded into
+// locus_anchors[n_loci][4] and its totals
+hipError_t mipgen_launch_locus_anchor_map(hipStream_t, const uint32_t* src, const uint32_t* first, int64_t n_pos, int64_t n_loci, uint32_t* own, uint32_t* prev);
+hipError_t mipgen_launch_locus_ins_fold(hipStream_t, const mipgen_insertion_record* records, int64_t n_records, const uint32_t* own, const uint32_t* prev, int64_t n_pos,
+                                        uint64_t* keys, uint32_t* ids, int64_t cap, LocusInsCounters* ctr);
+hipError_t mipgen_launch_locus_ins_reduce(hipStream_t, const uint64_t* run_keys, const int32_t* run_counts, const uint32_t* run_start, const unsigned long long* n_runs,
+                                          int64_t n_pairs, const uint32_t* ids_sorted, const mipgen_insertion_record* records, int64_t n_records, mipgen_insertion_record* out);
+hipError_t mipgen_launch_locus_anchor_merge(hipStream_t, const int32_t* anchors, const uint32_t* src, const uint32_t* first, int64_t n_pos, int64_t n_loci,
+                                            int32_t* locus_anchors, LocusInsCounters* ctr);
 }

@@ -78,6 +78,21 @@
 //                           <tab> alt_count <tab> alt_ppm <tab> bg_alt <tab> bg_depth <tab> q <tab> probes"; a deleted base prints alt "-"
 //   stderr     after the lines above: "mipgen_count: loci L lines P bases B nonref R discordant D" and, with -call_loci, "mipgen_count: locus calls C candidates K
 //              tested P too_deep D"
+// Insertion alleles per genome locus, folded over the probes that cover it (without these options every byte written is what it was):
+//   -insertion_loci ILOCI   needs -pileup_insertions and -pileup_loci: the allele records of INS folded under the plan of LOCI - minus-strand probes turned into plus
+//                           orientation, equal alleles of one locus added up, span the spanning molecules of every probe whose anchor lands there.  ONE more call per
+//                           row (undetermined too), the locus insertions call, feeds ILOCI only: FILE, INS, ICALLS, LOCI and CALLS are byte for byte what they are
+//                           without the option.  Header ">sample <tab> chr <tab> position <tab> length <tab> inserted <tab> count <tab> span <tab> ppm <tab> probes"; one
+//                           line per locus allele in row order, then record order (locus, then allele key); chr, position and probes as LOCI prints them for the locus,
+//                           which is the lower genome coordinate of the two bases the insertion lies between; inserted is in plus orientation, `length` times N for an
+//                           ambiguous record; ppm = floor(count 10^6 / span).  A plus and a minus probe place an insertion inside a repeat at opposite ends of it: those
+//                           stay two lines
+//   -call_insertion_loci ILCALLS   needs -insertion_loci: the locus alleles of every row called against a background of the other samples, under the -call_* options.  One
+//                           pool call, then the locus insertion call takes the place of the locus insertions call of every row and feeds ILOCI and ILCALLS.  Header
+//                           ">sample <tab> chr <tab> position <tab> length <tab> inserted <tab> depth <tab> alt_count <tab> alt_ppm <tab> bg_alt <tab> bg_depth <tab> q
+//                           <tab> probes"; the numbers as -call_insertions prints them
+//   stderr     last lines: "mipgen_count: insertion loci L alleles A events I ambiguous B span S" (L: the loci of the plan) and, with -call_insertion_loci,
+//              "mipgen_count: insertion locus calls C candidates K tested P too_deep D"
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -115,7 +130,9 @@ static int usage(const std::string& msg)
             "-call file : with -pileup, variant calls of every sample against the background of the others; -call_min_depth n (default 20), -call_min_alt k (3), -call_min_ppm p (0),\n"
             "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n"
             "-pileup_loci file : with -pileup, the counts per genome base, summed over the probes that cover it; -loci_parts target|all : what of a probe counts (default target)\n"
-            "-call_loci file : with -pileup_loci, the variant calls per genome base on the merged counts, under the -call_* options\n");
+            "-call_loci file : with -pileup_loci, the variant calls per genome base on the merged counts, under the -call_* options\n"
+            "-insertion_loci file : with -pileup_insertions and -pileup_loci, the insertion alleles per genome base, folded over the probes that cover it\n"
+            "-call_insertion_loci file : with -insertion_loci, the insertion alleles per genome base called against the background of the other samples, under the -call_* options\n");
     return 1;
 }
 
@@ -220,7 +237,7 @@ int main(int argc, char** argv)
     std::string consensus_prefix, pileup_path, call_path, ins_path, call_ins_path;
     mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
     bool call_option_given = false, loci_parts_given = false, loci_all = false;
-    std::string loci_path, call_loci_path;
+    std::string loci_path, call_loci_path, ins_loci_path, call_ins_loci_path;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
@@ -260,6 +277,8 @@ int main(int argc, char** argv)
         else if (a == "-call") { if (v.empty()) return usage("-call takes a file"); call_path = v; }
         else if (a == "-pileup_loci") { if (v.empty()) return usage("-pileup_loci takes a file"); loci_path = v; }
         else if (a == "-call_loci") { if (v.empty()) return usage("-call_loci takes a file"); call_loci_path = v; }
+        else if (a == "-insertion_loci") { if (v.empty()) return usage("-insertion_loci takes a file"); ins_loci_path = v; }
+        else if (a == "-call_insertion_loci") { if (v.empty()) return usage("-call_insertion_loci takes a file"); call_ins_loci_path = v; }
         else if (a == "-loci_parts") { if (v != "target" && v != "all") return usage("-loci_parts must be target or all"); loci_all = v == "all"; loci_parts_given = true; }
         else if (a == "-call_min_depth") { if (!svr_parse_int(v.c_str(), &iv) || iv < 1 || iv > INT32_MAX) return usage("-call_min_depth must be 1 or more"); call_prm.min_depth = (int32_t)iv; call_option_given = true; }
         else if (a == "-call_min_alt") { if (!svr_parse_int(v.c_str(), &iv) || iv < 1 || iv > INT32_MAX) return usage("-call_min_alt must be 1 or more"); call_prm.min_alt = (int32_t)iv; call_option_given = true; }
@@ -301,7 +320,10 @@ int main(int argc, char** argv)
     if ((call_loci || loci_parts_given) && !loci) return usage("-call_loci and -loci_parts need -pileup_loci file");
     const bool call_ins = !call_ins_path.empty();
     if (call_ins && !insertions) return usage("-call_insertions needs -pileup_insertions file");
-    if (call_option_given && !call && !call_loci && !call_ins) return usage("the -call_* options need -call file or -call_loci file");
+    const bool ins_loci = !ins_loci_path.empty(), call_ins_loci = !call_ins_loci_path.empty();
+    if (ins_loci && (!insertions || !loci)) return usage("-insertion_loci needs -pileup_insertions file and -pileup_loci file");
+    if (call_ins_loci && !ins_loci) return usage("-call_insertion_loci needs -insertion_loci file");
+    if (call_option_given && !call && !call_loci && !call_ins && !call_ins_loci) return usage("the -call_* options need -call file or -call_loci file");
     if (pileup && te + tl == 0) return usage("-pileup needs tag bases: with -tag_sizes 0,0 there are no molecules to count");
     std::vector<std::string> index_paths;
     std::vector<long> index_len;
@@ -428,6 +450,10 @@ int main(int argc, char** argv)
     FILE *loci_out = nullptr, *call_loci_out = nullptr;
     if (loci && !(loci_out = fopen(loci_path.c_str(), "w"))) return usage("-pileup_loci " + loci_path + ": can't write " + loci_path);
     if (call_loci && !(call_loci_out = fopen(call_loci_path.c_str(), "w"))) return usage("-call_loci " + call_loci_path + ": can't write " + call_loci_path);
+    FILE *ins_loci_out = nullptr, *call_ins_loci_out = nullptr;
+    if (ins_loci && !(ins_loci_out = fopen(ins_loci_path.c_str(), "w"))) return usage("-insertion_loci " + ins_loci_path + ": can't write " + ins_loci_path);
+    if (call_ins_loci && !(call_ins_loci_out = fopen(call_ins_loci_path.c_str(), "w")))
+        return usage("-call_insertion_loci " + call_ins_loci_path + ": can't write " + call_ins_loci_path);
 
     // ---- the device ----
     mipgen_accel* h = nullptr;
@@ -523,6 +549,7 @@ int main(int argc, char** argv)
     long long loci_lines = 0, loci_bases = 0, loci_nonref = 0, loci_disc = 0, lcall_calls = 0, lcall_cands = 0, lcall_tested = 0, lcall_deep = 0;
     long long ins_alleles = 0, ins_events = 0, ins_amb = 0, ins_span = 0;
     long long icall_calls = 0, icall_cands = 0, icall_tested = 0, icall_deep = 0;
+    long long iloci_alleles = 0, iloci_events = 0, iloci_amb = 0, iloci_span = 0, ilcall_calls = 0, ilcall_cands = 0, ilcall_tested = 0, ilcall_deep = 0;
     const size_t pile_cols = pile_indels ? 8 : 5;
     if (pileup) {
         int64_t n_pos = 0;
@@ -694,6 +721,54 @@ int main(int argc, char** argv)
             }
             fwrite(text.data(), 1, text.size(), call_loci_out);
         };
+        // -insertion_loci: the locus records of a row (ascending locus, then allele key) as lines - the fold has turned the bases into plus orientation already -;
+        // span comes from the locus anchor table of the row; -call_insertion_loci: the call records of a row likewise
+        std::vector<int32_t> lanch[2] = {std::vector<int32_t>(ins_loci ? n_loci * 4 : 0), std::vector<int32_t>(ins_loci && n_rows > 1 ? n_loci * 4 : 0)};
+        std::vector<mipgen_insertion_record> lirecs[2];
+        std::vector<mipgen_insertion_call_record> licrecs[2];
+        auto append_locus_allele = [&](const char* sample, int64_t l, int32_t length, uint32_t bases, bool ambiguous, std::string* text) {
+            std::string inserted((size_t)length, 'N');
+            for (int j = 0; !ambiguous && j < length; j++) inserted[(size_t)j] = "ACGT"[(bases >> (2 * (length - 1 - j))) & 3u];
+            char buf[80];
+            snprintf(buf, sizeof buf, "\t%ld\t%d\t", lplan.locus_pos[(size_t)l], length);
+            text->append(sample).append("\t").append(lplan.chroms[(size_t)lplan.locus_chr[(size_t)l]]).append(buf).append(inserted);
+        };
+        auto write_insertion_loci = [&](size_t r, const std::vector<int32_t>& anch, const std::vector<mipgen_insertion_record>& rec, const std::vector<mipgen_insertion_call_record>& crec) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text;
+            char buf[160];
+            for (const mipgen_insertion_record& q : rec) {
+                append_locus_allele(sample, q.pos, q.length, q.bases, q.ambiguous != 0, &text);
+                const int32_t span = anch[(size_t)q.pos * 4];
+                snprintf(buf, sizeof buf, "\t%d\t%d\t%lld\t%d\n", q.count, span, (long long)q.count * 1000000ll / span, lplan.sources[(size_t)q.pos]);
+                text.append(buf);
+            }
+            fwrite(text.data(), 1, text.size(), ins_loci_out);
+            if (!call_ins_loci) return;
+            text.clear();
+            for (const mipgen_insertion_call_record& q : crec) {
+                append_locus_allele(sample, q.pos, q.length, q.bases, false, &text);
+                snprintf(buf, sizeof buf, "\t%d\t%d\t%lld\t%d\t%d\t%d\t%d\n", q.depth, q.alt, (long long)q.alt * 1000000ll / q.depth, q.bg_alt, q.bg_depth, q.q,
+                         lplan.sources[(size_t)q.pos]);
+                text.append(buf);
+            }
+            fwrite(text.data(), 1, text.size(), call_ins_loci_out);
+        };
+        // the ONE more call of a row under -insertion_loci: the locus insertions call, or under -call_insertion_loci the locus insertion call, which folds the same
+        auto row_insertion_loci = [&](size_t r) {
+            mipgen_locus_insertion_totals lit{0, 0, 0, 0, 0, 0, 0, 0};
+            mipgen_call_totals ict{0, 0, 0, 0};
+            int prc = call_ins_loci ? mipgen_accel_reads_consensus_locus_insertion_call(h, (int32_t)r, &call_prm, nullptr, nullptr, lanch[r & 1].data(), nullptr, &lit, &ict)
+                                    : mipgen_accel_reads_consensus_locus_insertions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family,
+                                                                                    (int32_t)pile_quality, (int32_t)pile_indels, nullptr, nullptr, lanch[r & 1].data(), nullptr, &lit);
+            if (prc == MIPGEN_OK) { lirecs[r & 1].resize((size_t)lit.alleles); prc = mipgen_accel_locus_insertions_fetch(h, lirecs[r & 1].data(), lit.alleles); }
+            if (prc == MIPGEN_OK && call_ins_loci) { licrecs[r & 1].resize((size_t)ict.calls); prc = mipgen_accel_locus_insertion_call_fetch(h, licrecs[r & 1].data(), ict.calls); }
+            if (prc == MIPGEN_OK) {
+                iloci_alleles += lit.alleles; iloci_events += lit.insertions; iloci_amb += lit.ambiguous; iloci_span += lit.span;
+                ilcall_calls += ict.calls; ilcall_cands += ict.candidates; ilcall_tested += ict.tested; ilcall_deep += ict.too_deep;
+            }
+            return prc;
+        };
         if (loci) {
             fputs(pile_indels ? ">sample\tchr\tposition\tref\tprobes\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n" : ">sample\tchr\tposition\tref\tprobes\tA\tC\tG\tT\tdiscordant\n",
                   loci_out);
@@ -715,6 +790,12 @@ int main(int argc, char** argv)
             fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tinserted\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\n", call_ins_out);
             if (mipgen_accel_reads_consensus_insertion_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
                                                             call_prm.bg_max_ppm, nullptr) != MIPGEN_OK) return die();
+        }
+        if (ins_loci) fputs(">sample\tchr\tposition\tlength\tinserted\tcount\tspan\tppm\tprobes\n", ins_loci_out);
+        if (call_ins_loci) {
+            fputs(">sample\tchr\tposition\tlength\tinserted\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\tprobes\n", call_ins_loci_out);
+            if (mipgen_accel_reads_consensus_locus_insertion_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
+                                                                  call_prm.bg_max_ppm, nullptr) != MIPGEN_OK) return die();
         }
         fputs(pile_indels ? ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\tdel\tins\tins_discordant\n"
                           : ">sample\tmip_key\tchr\tposition\tstrand\tpart\tref\tA\tC\tG\tT\tdiscordant\n", pile_out);
@@ -764,6 +845,7 @@ int main(int argc, char** argv)
                 mipgen_insertion_totals it;
                 prc = row_insertions(r, nullptr, &it);
             }
+            if (ins_loci && prc == MIPGEN_OK) prc = row_insertion_loci(r);              // one more call per row: it feeds ILOCI (and ILCALLS) only
             if (pile_indels) { pt.used = gt.used; pile_gapped += gt.gapped_sides; }
             if (writer.joinable()) writer.join();
             if (prc != MIPGEN_OK) return die();
@@ -774,6 +856,7 @@ int main(int argc, char** argv)
                 if (loci) write_loci(r, ltable[r & 1], lrecs[r & 1]);
                 if (insertions) write_insertions(r, ianch[r & 1], irecs[r & 1]);
                 if (call_ins) write_insertion_calls(r, icrecs[r & 1]);
+                if (ins_loci) write_insertion_loci(r, lanch[r & 1], lirecs[r & 1], licrecs[r & 1]);
             });
         }
         if (writer.joinable()) writer.join();
@@ -783,6 +866,8 @@ int main(int argc, char** argv)
         if (call && fclose(call_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (loci && fclose(loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call_loci && fclose(call_loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (ins_loci && fclose(ins_loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, ins_loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (call_ins_loci && fclose(call_ins_loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_ins_loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
     }
     mipgen_accel_destroy(h);
 
@@ -867,5 +952,7 @@ int main(int argc, char** argv)
     if (call_loci) fprintf(stderr, "%s: locus calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, lcall_calls, lcall_cands, lcall_tested, lcall_deep);
     if (insertions) fprintf(stderr, "%s: insertion alleles %lld events %lld ambiguous %lld span %lld\n", PROG, ins_alleles, ins_events, ins_amb, ins_span);
     if (call_ins) fprintf(stderr, "%s: insertion calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, icall_calls, icall_cands, icall_tested, icall_deep);
+    if (ins_loci) fprintf(stderr, "%s: insertion loci %zu alleles %lld events %lld ambiguous %lld span %lld\n", PROG, lplan.locus_pos.size(), iloci_alleles, iloci_events, iloci_amb, iloci_span);
+    if (call_ins_loci) fprintf(stderr, "%s: insertion locus calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, ilcall_calls, ilcall_cands, ilcall_tested, ilcall_deep);
     return 0;
 }
