@@ -404,6 +404,26 @@ int mipgen_accel_reads_finish_consensus(mipgen_accel* h, int64_t* reads, int64_t
 int mipgen_accel_reads_consensus_fetch(mipgen_accel* h, int32_t* cell, uint32_t* tag, int32_t* family, int64_t* ext_off, char* ext_seq, char* ext_qual, int64_t* lig_off,
                                        char* lig_seq, char* lig_qual);
 
+/* ---- sequencing errors in molecular tags, corrected before the consensus (new entry points only: the ABI number does not change) ----
+ * The tag merge model.  A RAW group is a group of the model above; its count c is its family size.  A NEIGHBOUR of a raw group is another raw group of the SAME cell
+ * whose tag code differs in exactly one base (one 2-bit field).  Neighbour a is an ELIGIBLE PARENT of b when c_a >= 2 c_b - 1 and c_a > c_b; the PARENT of b is its
+ * eligible parent of the largest count, of the smaller tag code among equals; a group without one is a root.  A CORRECTED group is a root with all its descendants:
+ * its tag is the root's, its family the sum of the raw families, its consensus the vote of the model above over all those members.  reads, the totals, row_pairs and
+ * the per-pair indices are unchanged; unique_tags counts corrected groups.  Dirty tags join nothing, and tags of different cells never meet.
+ *   set_tag_mismatches: d = 0 (the default of every open: tags are compared exactly, and the session allocates and launches what it always did) or 1 (the merge
+ *                       above at finish_consensus); valid on an open consensus session at any time before its finish.  MIPGEN_E_STATE with no session open or
+ *                       with a session that keeps no reads (it stays usable); MIPGEN_E_INVALID for any other d.
+ *   last_tag_merge:     the totals of the last finish_consensus: raw_groups, groups (corrected), absorbed = raw_groups - groups, moved_pairs (the pairs of the
+ *                       absorbed groups) and max_depth (the parent links of the longest chain).  At d = 0: raw_groups = groups, the rest 0.
+ *   tag_map_fetch:      one entry per RAW group in raw group order (ascending cell, raw tag code): cell, raw tag, raw family and the tag of the corrected group
+ *                       it went to (at d = 0: the identity map).  Every pointer may be NULL.
+ * last_tag_merge and tag_map_fetch: MIPGEN_E_STATE when the handle holds no consensus reads (before a finish_consensus, after the next open).  A parent walk that
+ * does not end within 31 links - a state the rule cannot build - fails the finish with MIPGEN_E_STATE. */
+typedef struct mipgen_tag_merge_totals { int64_t raw_groups, groups, absorbed, moved_pairs, max_depth; } mipgen_tag_merge_totals;
+int mipgen_accel_reads_set_tag_mismatches(mipgen_accel* h, int32_t d);
+int mipgen_accel_reads_last_tag_merge(mipgen_accel* h, mipgen_tag_merge_totals* totals);
+int mipgen_accel_reads_tag_map_fetch(mipgen_accel* h, int32_t* cell, uint32_t* raw_tag, int32_t* raw_family, uint32_t* tag);
+
 /* ---- allele counts per captured base from the consensus reads (new entry point only: the ABI number does not change) ----
  * The pileup model.  The call reads the consensus reads the handle holds since the last finish_consensus and nothing else.  Probe p has a molecule
  * length mol_len[p] >= 1: the bytes of M = ext arm + scan target + lig arm.  Every read of a probe starts at the same template base, so position t of the extension
@@ -847,7 +867,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * placement and count included (timing enabled); 16 = the kernels of the last insertion pool or insertion call of either kind (mipgen_accel_insertion_call_tables,
  * mipgen_accel_reads_consensus_insertion_pool, mipgen_accel_reads_consensus_insertion_call), the insertions route of its rows included (timing enabled);
  * 17 = the kernels of the last locus insertions call of any kind (mipgen_accel_locus_insertion_tables, mipgen_accel_reads_consensus_locus_insertions, _locus_insertion_pool,
- * _locus_insertion_call), the insertions route of its rows included (timing enabled). */
+ * _locus_insertion_call), the insertions route of its rows included (timing enabled); 18 = k_tag_parent, k_tag_root and k_tag_rewrite of the last
+ * mipgen_accel_reads_finish_consensus of a session with tag mismatches 1 (timing enabled; its second sort and run boundaries are part of 10). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

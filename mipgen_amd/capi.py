@@ -83,6 +83,10 @@ class ConsensusSizes(C.Structure):   # mipgen_consensus_sizes
     _fields_ = [(n, C.c_int64) for n in ("n_groups", "ext_bytes", "lig_bytes")]
 
 
+class TagMergeTotals(C.Structure):   # mipgen_tag_merge_totals
+    _fields_ = [(n, C.c_int64) for n in ("raw_groups", "groups", "absorbed", "moved_pairs", "max_depth")]
+
+
 class PileupTotals(C.Structure):    # mipgen_pileup_totals
     _fields_ = [(n, C.c_int64) for n in ("groups", "used", "bases", "discordant")]
 
@@ -412,6 +416,9 @@ def load_library(path: Optional[str] = None):
     lib.mipgen_accel_reads_finish_consensus.argtypes = [vp, i64p_, i64p_, C.POINTER(ReadTotals), C.POINTER(SampleTotals), i64p_, C.POINTER(ConsensusSizes)]
     lib.mipgen_accel_reads_consensus_fetch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), i64p_, C.c_void_p, C.c_void_p, i64p_, C.c_void_p,
                                                        C.c_void_p]
+    lib.mipgen_accel_reads_set_tag_mismatches.argtypes = [vp, C.c_int32]
+    lib.mipgen_accel_reads_last_tag_merge.argtypes = [vp, C.POINTER(TagMergeTotals)]
+    lib.mipgen_accel_reads_tag_map_fetch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.mipgen_accel_reads_consensus_pileup.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(PileupTotals)]
     lib.mipgen_accel_reads_consensus_pileup_gapped.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                                C.POINTER(C.c_int32), C.POINTER(GappedTotals)]
@@ -462,7 +469,7 @@ def load_library(path: Optional[str] = None):
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
                  "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped", "consensus_call_pool", "consensus_call",
                  "consensus_locus_plan", "consensus_locus_pileup", "consensus_locus_call_pool", "consensus_locus_call", "consensus_locus_call_pileup_totals",
-                 "consensus_insertions"):
+                 "consensus_insertions", "set_tag_mismatches", "last_tag_merge", "tag_map_fetch"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -542,6 +549,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_reads_last_assignment",
     "mipgen_accel_reads_open_samples", "mipgen_accel_reads_feed_samples", "mipgen_accel_reads_finish_samples", "mipgen_accel_reads_last_samples",
     "mipgen_accel_reads_open_consensus", "mipgen_accel_reads_feed_consensus", "mipgen_accel_reads_finish_consensus", "mipgen_accel_reads_consensus_fetch",
+    "mipgen_accel_reads_set_tag_mismatches", "mipgen_accel_reads_last_tag_merge", "mipgen_accel_reads_tag_map_fetch",
     "mipgen_accel_reads_consensus_pileup",
     "mipgen_accel_reads_consensus_pileup_gapped",
     "mipgen_accel_call_tables", "mipgen_accel_reads_consensus_call_pool", "mipgen_accel_reads_consensus_call", "mipgen_accel_call_fetch",
@@ -945,10 +953,12 @@ class Accel:
         return scores, feats, ints
 
     def _read_session(self, arms, ext_reads, lig_reads, quals=None, index_reads=None, barcodes=None, barcode_mismatches=0, tag_sizes=(5, 0), mismatches=0,
-                      swap_reads=False, chunks=1, key_buffer=0, arena_bytes=0, want_assignment=False):
+                      swap_reads=False, chunks=1, key_buffer=0, arena_bytes=0, want_assignment=False, tag_mismatches=0, after_open=None):
         """One read session of any kind through its own entry points - with samples when `barcodes` is given, a consensus session when `quals` = (ext_quals,
         lig_quals) is: open, feed in `chunks` cuts (with the per-pair downloads if want_assignment), finish, and the groups of a consensus session.  An error
-        while feeding closes the session through its finish with null outputs.  Returns (reads[rows][n], unique_tags[rows][n], totals dict, row_pairs[rows] or
+        while feeding closes the session through its finish with null outputs.  tag_mismatches other than 0: mipgen_accel_reads_set_tag_mismatches right after
+        the open (0 leaves the session as the open made it: the setter is not called); after_open: called with no arguments once the session is open - an error it
+        raises closes the session like one while feeding.  Returns (reads[rows][n], unique_tags[rows][n], totals dict, row_pairs[rows] or
         None, groups or None, sample index per pair or None, probe index per pair)."""
         lib, h = self.lib, self.h
         samples, consensus = barcodes is not None, quals is not None
@@ -994,6 +1004,10 @@ class Accel:
         sample = np.empty(n_pairs, dtype=np.int32) if samples else None
         probe = np.empty(n_pairs, dtype=np.int32)
         try:
+            if tag_mismatches != 0:
+                self._check(lib.mipgen_accel_reads_set_tag_mismatches(h, tag_mismatches))
+            if after_open is not None:
+                after_open()
             cuts = [n_pairs * k // max(chunks, 1) for k in range(max(chunks, 1) + 1)]
             for a, b in zip(cuts[:-1], cuts[1:]):
                 e, eo = cut("ext", a, b)
@@ -1060,14 +1074,34 @@ class Accel:
     def consensus_reads(self, arms: Sequence[tuple], ext_reads: Sequence[bytes], lig_reads: Sequence[bytes], ext_quals: Sequence[bytes], lig_quals: Sequence[bytes],
                         index_reads: Optional[Sequence[bytes]] = None, barcodes: Optional[Sequence[bytes]] = None, barcode_mismatches: int = 0,
                         tag_sizes: Tuple[int, int] = (5, 0), mismatches: int = 0, swap_reads: bool = False, chunks: int = 1, arena_bytes: int = 0,
-                        want_assignment: bool = False):
+                        want_assignment: bool = False, tag_mismatches: int = 0, after_open=None):
         """mipgen_accel_reads_open_consensus / _feed_consensus / _finish_consensus / _consensus_fetch: the counts of count_reads (barcodes None: reads and
         unique_tags have one row) or count_reads_samples, and one consensus read pair per (row, probe, tag) group.  ext_quals / lig_quals: the quality string
         of every read, as long as the read.  Returns (reads[rows][n], unique_tags[rows][n], totals dict, row_pairs[rows] or None, groups[, sample index per
-        pair or None, probe index per pair]); groups as consensus_fetch gives them."""
+        pair or None, probe index per pair]); groups as consensus_fetch gives them.  tag_mismatches 1: tags one substitution apart are merged by the count rule
+        of DESIGN 4.20 first - the groups are the corrected ones; last_tag_merge and tag_map_fetch tell what was merged."""
         out = self._read_session(arms, ext_reads, lig_reads, (ext_quals, lig_quals), index_reads, barcodes, barcode_mismatches, tag_sizes, mismatches, swap_reads, chunks,
-                                 arena_bytes=arena_bytes, want_assignment=want_assignment)
+                                 arena_bytes=arena_bytes, want_assignment=want_assignment, tag_mismatches=tag_mismatches, after_open=after_open)
         return out if want_assignment else out[:5]
+
+    def set_tag_mismatches(self, d: int) -> None:
+        """mipgen_accel_reads_set_tag_mismatches on the open consensus session: 0 or 1."""
+        self._check(self.lib.mipgen_accel_reads_set_tag_mismatches(self.h, d))
+
+    def last_tag_merge(self) -> dict:
+        """mipgen_accel_reads_last_tag_merge: raw_groups, groups, absorbed, moved_pairs and max_depth of the last consensus_reads."""
+        tot = TagMergeTotals()
+        self._check(self.lib.mipgen_accel_reads_last_tag_merge(self.h, C.byref(tot)))
+        return {f[0]: int(getattr(tot, f[0])) for f in TagMergeTotals._fields_}
+
+    def tag_map_fetch(self):
+        """mipgen_accel_reads_tag_map_fetch: one (cell, raw tag code, raw family, corrected tag code) per RAW group of the last consensus_reads, in raw group order."""
+        G = self.last_tag_merge()["raw_groups"]
+        i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        cell = np.empty(G, dtype=np.int32); raw_tag = np.empty(G, dtype=np.uint32); raw_family = np.empty(G, dtype=np.int32); tag = np.empty(G, dtype=np.uint32)
+        self._check(self.lib.mipgen_accel_reads_tag_map_fetch(self.h, cell.ctypes.data_as(i32p), raw_tag.ctypes.data_as(u32p), raw_family.ctypes.data_as(i32p),
+                                                              tag.ctypes.data_as(u32p)))
+        return [(int(cell[g]), int(raw_tag[g]), int(raw_family[g]), int(tag[g])) for g in range(G)]
 
     # ---- pileups, calls and loci off the consensus reads (DESIGN 4.12-4.15) ----
     @staticmethod

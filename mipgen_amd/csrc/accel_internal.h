@@ -355,8 +355,14 @@ struct ConsensusResult {
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
+    // the tag merge of the session that left the reads.  merged: the raw groups and the root of each are held; otherwise the map is the identity on `keys`
+    // and `family` and nothing below is reserved
+    mipgen_tag_merge_totals tag_totals{0, 0, 0, 0, 0};
+    bool merged = false;
+    DevBuf<uint64_t> raw_keys;                               // raw_groups
+    DevBuf<int32_t> raw_family, raw_root;                    // ... the family of each and the raw group that is its root
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); locus_ins.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); raw_keys.release(); raw_family.release(); raw_root.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); locus_ins.release(); }
 };
 
 struct mipgen_accel {
@@ -477,7 +483,8 @@ struct mipgen_accel {
     double sample_assign_ms = -1.0;  // k_sample_assign over the feed calls of the last samples session (timing enabled)
     ConsensusResult* consensus = nullptr;   // held from mipgen_accel_reads_finish_consensus until the next mipgen_accel_reads_open* or mipgen_accel_destroy
     double consensus_vote_ms = -1.0; // k_consensus_vote_wave + k_consensus_vote_wg of the last mipgen_accel_reads_finish_consensus (timing enabled)
-    double consensus_sort_ms = -1.0; // ... its radix sort of (key, pair id) and the run boundaries
+    double consensus_sort_ms = -1.0; // ... its radix sort of (key, pair id) and the run boundaries (both sorts of a session that merges tags)
+    double tag_merge_ms = -1.0;      // ... its k_tag_parent, k_tag_root and k_tag_rewrite (a session with tag mismatches 1, timing enabled)
     double pileup_ms = -1.0;         // the kernels_pileup.hip kernels of the last mipgen_accel_reads_consensus_pileup (timing enabled)
     double gapped_ms = -1.0;         // the kernels of the last mipgen_accel_reads_consensus_pileup_gapped (timing enabled)
     CallRun call_run;                // the last call's candidates and records (accel_pileup.hip)

@@ -3,9 +3,11 @@
 // _finish_consensus / _consensus_fetch; the pileups read off the ConsensusResult a finish leaves on the handle are accel_pileup.hip's).  The three families of entry points name ONE path.  ReadsSession is what every session has plus a KeyList, a SamplesPart and a
 // ConsensusPart; its flags `samples` and `consensus` say which parts are set up, and session_for() alone matches a call to the open session.  open_impl: check_open
 // (probe table, then barcodes), build_host_tables, the budget, upload_tables.  feed_impl: eleven stages, the kinds differing in data only - where the bases of the call live and where
-// k_read_assign's keys go.  finish_session: consensus_finish where reads were kept, finish_impl, release.  Errors are HIP_TRY returns; IdleOnExit and FreeOnExit put the
+// k_read_assign's keys go.  finish_session: consensus_finish where reads were kept - with merge_tags between its runs and its partition when the session was told to correct its
+// tags (4.20: mipgen_accel_reads_set_tag_mismatches / _last_tag_merge / _tag_map_fetch) -, finish_impl, release.  Errors are HIP_TRY returns; IdleOnExit and FreeOnExit put the
 // stream and a chunk's block right on every way out, SpanTimer books HIP-event times.  A session owns every buffer it uses; of the handle it takes the device and the stream.
 #include "accel_internal.h"
+#include "tag_merge.h"
 
 struct SeedTableBufs {
     DevBuf<uint32_t> slots, start;
@@ -201,12 +203,15 @@ struct ConsensusPart {
     DevBuf<uint32_t> c_start, c_order;
     DevBuf<ConsensusPair> c_recs;
     DevBuf<int64_t> c_ext_len, c_lig_len;
+    int32_t tag_mismatches = 0;                              // mipgen_accel_reads_set_tag_mismatches; at 0 nothing below is reserved
+    DevBuf<int32_t> t_parent;                                // the parent of every raw group
+    DevBuf<TagMergeCounters> t_ctr;
     void release()
     {
         for (const ArenaChunk& c : chunks) (void)hipFree(c.block);
         chunks.clear();
         ctr.release(); pairs.release(); c_start.release(); c_order.release(); c_recs.release();
-        c_ext_len.release(); c_lig_len.release();
+        c_ext_len.release(); c_lig_len.release(); t_parent.release(); t_ctr.release();
     }
 };
 
@@ -539,6 +544,56 @@ static int download_last(mipgen_accel* h, bool sample, int32_t* out, int64_t cap
     return MIPGEN_OK;
 }
 
+// The tag merge of a session with tag mismatches 1, between the runs of the sorted member keys and the partition.  On entry the *G raw groups lie in
+// Q.keys / Q.ids (group key, family); they are copied to R, every raw group gets its parent and its root, and - when a group was absorbed at all - every member key is
+// rewritten to its root's key, back into the unsorted arrays, which are sorted and run-length encoded once more: Q.keys / Q.ids then hold the *G corrected groups.
+// The G-sized arrays are checked against free device memory before the first launch.
+static int merge_tags(mipgen_accel* h, ReadsSession* S, ConsensusResult* R, int64_t N, int64_t M, int sort_bits, int64_t* G, SpanTimer& sort_time, SpanTimer& merge_time)
+{
+    hipStream_t st = h->stream;
+    ConsensusPart& C = S->cons;
+    SortedPairs& Q = C.pairs;
+    const int64_t G0 = *G;
+    size_t free_b = 0;
+    if (int rc = free_device_bytes(&free_b)) return rc;
+    const size_t need = padded((size_t)G0, 8) + 3 * padded((size_t)G0, 4) + padded(1, sizeof(TagMergeCounters));      // raw keys; raw families, roots, parents
+    if (need + ((size_t)64 << 20) > free_b)
+        return fail(MIPGEN_E_NOMEM, "tag merge: the parent, root and raw copy of %lld groups need %zu MiB of device memory, %zu MiB are free", (long long)G0, need >> 20, free_b >> 20);
+    if (R->raw_keys.reserve((size_t)G0) || R->raw_family.reserve((size_t)G0) || R->raw_root.reserve((size_t)G0) || C.t_parent.reserve((size_t)G0) || C.t_ctr.reserve(1))
+        return MIPGEN_E_NOMEM;
+    HIP_TRY(hipMemcpyAsync(R->raw_keys.p, Q.keys.p, (size_t)G0 * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R->raw_family.p, Q.ids.p, (size_t)G0 * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(C.t_ctr.p, 0, sizeof(TagMergeCounters), st));
+    merge_time.mark();
+    HIP_TRY(mipgen_launch_tag_parent(st, R->raw_keys.p, R->raw_family.p, G0, S->P.te + S->P.tl, C.t_parent.p));
+    HIP_TRY(mipgen_launch_tag_root(st, C.t_parent.p, R->raw_family.p, G0, R->raw_root.p, C.t_ctr.p));
+    merge_time.mark();
+    TagMergeCounters tc;
+    HIP_TRY(hipMemcpyAsync(&tc, C.t_ctr.p, sizeof tc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (tc.unended) return fail(MIPGEN_E_STATE, "tag merge: the parent walk of %llu groups did not end within %d links", tc.unended, TAG_MERGE_MAX_LINKS);
+    if ((int64_t)tc.absorbed >= G0 || (int64_t)tc.moved_pairs >= M)
+        return fail(MIPGEN_E_STATE, "tag merge: %llu groups of %lld absorbed, %llu pairs of %lld moved", tc.absorbed, (long long)G0, tc.moved_pairs, (long long)M);
+    R->merged = true;
+    if (tc.absorbed) {                                                       // (nothing absorbed: the raw groups are the corrected ones, and the second sort is skipped)
+        merge_time.mark();
+        HIP_TRY(mipgen_launch_tag_rewrite(st, Q.keys_sorted.p, Q.ids_sorted.p, N, M, R->raw_keys.p, G0, R->raw_root.p, Q.keys.p, Q.ids.p));
+        merge_time.mark();
+        sort_time.mark();
+        HIP_TRY(Q.sort(st, N, sort_bits));
+        HIP_TRY(Q.runs(st, M, Q.keys.p, reinterpret_cast<int32_t*>(Q.ids.p), &C.ctr.p->groups));
+        sort_time.mark();
+        ConsensusCounters cc;
+        HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((int64_t)cc.groups != G0 - (int64_t)tc.absorbed)
+            return fail(MIPGEN_E_STATE, "tag merge: %llu groups after %llu of %lld were absorbed", cc.groups, tc.absorbed, (long long)G0);
+        *G = (int64_t)cc.groups;
+    }
+    R->tag_totals = {G0, *G, (int64_t)tc.absorbed, (int64_t)tc.moved_pairs, (int64_t)tc.max_depth};
+    return MIPGEN_OK;
+}
+
 // The groups of a consensus session and their consensus reads into R; unique tags per cell - the groups of the cell - into S->unique.
 static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R)
 {
@@ -546,7 +601,7 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
     ConsensusPart& C = S->cons;
     SortedPairs& Q = C.pairs;
     const int64_t N = C.total_pairs;
-    h->consensus_vote_ms = h->consensus_sort_ms = -1.0;
+    h->consensus_vote_ms = h->consensus_sort_ms = h->tag_merge_ms = -1.0;
     ConsensusCounters cc;
     HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -565,7 +620,7 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
         HIP_TRY(hipMemcpyAsync(Q.keys.p + c.pair0, c.block + L.keys, (size_t)c.n * 8, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(Q.ids.p + c.pair0, c.block + L.ids, (size_t)c.n * 4, hipMemcpyDeviceToDevice, st));
     }
-    SpanTimer sort_time{h->timing, st}, vote_time{h->timing, st};
+    SpanTimer sort_time{h->timing, st}, vote_time{h->timing, st}, merge_time{h->timing, st};
     // sort; the runs of the member keys: group key and family size (the fed arrays are free once sorted, and take them)
     sort_time.mark();
     HIP_TRY(Q.sort(st, N, sort_bits));
@@ -575,8 +630,11 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
     sort_time.mark();
     HIP_TRY(hipMemcpyAsync(&cc, C.ctr.p, sizeof cc, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const int64_t G = (int64_t)cc.groups;
+    int64_t G = (int64_t)cc.groups;
     if (G < 1 || G > M) return fail(MIPGEN_E_STATE, "consensus reads: %lld groups of %lld members", (long long)G, (long long)M);
+    R->tag_totals = {G, G, 0, 0, 0};
+    if (C.tag_mismatches)                                                    // (group_keys and family then hold the corrected groups)
+        if (int rc = merge_tags(h, S, R, N, M, sort_bits, &G, sort_time, merge_time)) return rc;
     if (R->keys.reserve((size_t)G) || R->family.reserve((size_t)G) || R->ext_off.reserve((size_t)G + 1) || R->lig_off.reserve((size_t)G + 1) || C.c_start.reserve((size_t)G) ||
         C.c_order.reserve((size_t)G) || C.c_ext_len.reserve((size_t)G + 1) || C.c_lig_len.reserve((size_t)G + 1))
         return MIPGEN_E_NOMEM;
@@ -608,7 +666,8 @@ static int consensus_finish(mipgen_accel* h, ReadsSession* S, ConsensusResult* R
     // unique tags of a cell = its groups: the group keys ARE the sorted, duplicate-free key list of a plain session
     HIP_TRY(mipgen_launch_reads_histogram(st, R->keys.p, G, S->unique.p));
     HIP_TRY(hipStreamSynchronize(st));
-    double sort_ms = 0.0, vote_ms = 0.0;
+    double sort_ms = 0.0, vote_ms = 0.0, merge_ms = 0.0;
+    if (merge_time.add_to(&merge_ms)) h->tag_merge_ms = merge_ms;
     if (sort_time.add_to(&sort_ms)) h->consensus_sort_ms = sort_ms;
     if (vote_time.add_to(&vote_ms)) h->consensus_vote_ms = vote_ms;
     R->n_groups = G; R->ext_bytes = totals[0]; R->lig_bytes = totals[1];
@@ -701,6 +760,58 @@ int mipgen_accel_reads_feed_consensus(mipgen_accel* h, int64_t n_pairs, const ch
                                       const char* lig_qual, const int64_t* lig_offsets, const char* index_bytes, const int64_t* index_offsets)
 {
     return feed_impl(h, KIND_CONSENSUS, n_pairs, ext_bytes, ext_qual, ext_offsets, lig_bytes, lig_qual, lig_offsets, index_bytes, index_offsets);
+}
+
+int mipgen_accel_reads_set_tag_mismatches(mipgen_accel* h, int32_t d)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    ReadsSession* S = h->reads;
+    if (!S) return fail(MIPGEN_E_STATE, "no read-counting session is open");
+    if (!S->consensus) return fail(MIPGEN_E_STATE, "the open session keeps no reads: tags are merged by family size, in a session opened by mipgen_accel_reads_open_consensus");
+    if (d != 0 && d != 1) return fail(MIPGEN_E_INVALID, "tag_mismatches %d outside 0..1", d);
+    S->cons.tag_mismatches = d;
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_last_tag_merge(mipgen_accel* h, mipgen_tag_merge_totals* totals)
+{
+    if (!h || !totals) return fail(MIPGEN_E_INVALID, "bad arguments");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    *totals = h->consensus->tag_totals;
+    return MIPGEN_OK;
+}
+
+int mipgen_accel_reads_tag_map_fetch(mipgen_accel* h, int32_t* cell, uint32_t* raw_tag, int32_t* raw_family, uint32_t* tag)
+{
+    if (!h) return fail(MIPGEN_E_INVALID, "null handle");
+    if (!h->consensus) return fail(MIPGEN_E_STATE, "the handle holds no consensus reads: mipgen_accel_reads_finish_consensus leaves them, the next mipgen_accel_reads_open* drops them");
+    HIP_TRY(hipSetDevice(h->device));
+    const ConsensusResult* R = h->consensus;
+    const size_t G0 = (size_t)R->tag_totals.raw_groups;
+    if (G0 == 0) return MIPGEN_OK;
+    hipStream_t st = h->stream;
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> root;
+    if (cell || raw_tag || tag) {
+        keys.resize(G0);
+        HIP_TRY(hipMemcpyAsync(keys.data(), R->merged ? R->raw_keys.p : R->keys.p, G0 * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (tag && R->merged) {
+        root.resize(G0);
+        HIP_TRY(hipMemcpyAsync(root.data(), R->raw_root.p, G0 * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (raw_family) HIP_TRY(hipMemcpyAsync(raw_family, R->merged ? R->raw_family.p : R->family.p, G0 * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t g = 0; g < keys.size(); g++) {
+        if (cell) cell[g] = (int32_t)(keys[g] >> 32);
+        if (raw_tag) raw_tag[g] = (uint32_t)keys[g];
+        if (tag) {
+            const size_t r = R->merged ? (size_t)root[g] : g;
+            if (r >= G0) return fail(MIPGEN_E_STATE, "tag merge: raw group %zu has root %zu of %zu", g, r, G0);
+            tag[g] = (uint32_t)keys[r];
+        }
+    }
+    return MIPGEN_OK;
 }
 
 int mipgen_accel_reads_last_samples(mipgen_accel* h, int32_t* sample_index, int64_t capacity) { return download_last(h, true, sample_index, capacity); }

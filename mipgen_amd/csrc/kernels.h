@@ -173,6 +173,13 @@ hipError_t mipgen_launch_consensus_len(hipStream_t, int te, int tl, int64_t n_gr
 hipError_t mipgen_launch_consensus_vote(hipStream_t, int te, int tl, int64_t n_groups, const uint32_t* order, int64_t n_small, int64_t n_big, const uint32_t* group_start,
                                         const int32_t* family, const uint32_t* ids, const ConsensusPair* recs, const int64_t* ext_off, const int64_t* lig_off, uint8_t* ext_seq,
                                         uint8_t* ext_qual, uint8_t* lig_seq, uint8_t* lig_qual);
+// kernels_tag_merge.hip (the rule and TagMergeCounters: tag_merge.h): the parent of every raw group, its root and the totals (ctr zero on entry), and the
+// sorted pairs back into the unsorted arrays with every member key replaced by its root's
+struct TagMergeCounters;
+hipError_t mipgen_launch_tag_parent(hipStream_t, const uint64_t* keys, const int32_t* family, int64_t n_groups, int tag_bases, int32_t* parent);
+hipError_t mipgen_launch_tag_root(hipStream_t, const int32_t* parent, const int32_t* family, int64_t n_groups, int32_t* root, TagMergeCounters* ctr);
+hipError_t mipgen_launch_tag_rewrite(hipStream_t, const uint64_t* keys_sorted, const uint32_t* ids_sorted, int64_t n_pairs, int64_t n_members, const uint64_t* group_keys,
+                                     int64_t n_groups, const int32_t* root, uint64_t* keys, uint32_t* ids);
 // kernels_pileup.hip: the cell boundaries of one row, its (cell, round) units and its used groups (R: cell0, n, mol_len and min_family are read; start, units
 // and ctr are written, ctr zero on entry); then the counts and their sums
 hipError_t mipgen_launch_pileup_prepare(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, uint32_t* start, uint2* units, PileupCounters* ctr);

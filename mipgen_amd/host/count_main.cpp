@@ -93,6 +93,15 @@
 //                           <tab> probes"; the numbers as -call_insertions prints them
 //   stderr     last lines: "mipgen_count: insertion loci L alleles A events I ambiguous B span S" (L: the loci of the plan) and, with -call_insertion_loci,
 //              "mipgen_count: insertion locus calls C candidates K tested P too_deep D"
+// Sequencing errors in molecular tags, corrected before the consensus (without -tag_mismatches 1 every byte written is what it was):
+//   -tag_mismatches 0|1     1: the (sample, probe, tag) groups whose tags differ in one base are merged by the count rule - a group joins its neighbour of the largest
+//                           family when that family is at least twice its own minus one, and larger - before anything is counted or voted.  The session then keeps its
+//                           reads even without -consensus or -pileup (the rule needs family sizes), which costs the arena of DESIGN 4.11.  Every output carries the
+//                           corrected groups: unique_tags in -o, -samples and -labels, the consensus FASTQ (the tag of the header is the corrected one, the family the
+//                           merged one) and every pileup, call, locus and insertion file
+//   -tag_map FILE           needs -tag_mismatches 1: "sample <tab> mip_key <tab> raw_tag <tab> raw_family <tab> tag" under a header line of those words, one line per RAW
+//                           group in group order (sample, probe, raw tag), tags as bases, the sample as the consensus header writes it
+//   stderr     after the lines above: "mipgen_count: tag_mismatches 1 raw R groups G absorbed A moved_pairs P max_depth D"
 // Arguments are checked, the tables are parsed and both FASTQ files are read through once (record structure, equal record counts) before the
 // device is opened: a malformed row or record names its file and line.  Then the reads stream to the device in chunks of at most 2^19 pairs, and a
 // second thread reads and packs the next chunk while the device works on the current one.  Any error ends with a message and exit status 1.
@@ -132,7 +141,9 @@ static int usage(const std::string& msg)
             "-pileup_loci file : with -pileup, the counts per genome base, summed over the probes that cover it; -loci_parts target|all : what of a probe counts (default target)\n"
             "-call_loci file : with -pileup_loci, the variant calls per genome base on the merged counts, under the -call_* options\n"
             "-insertion_loci file : with -pileup_insertions and -pileup_loci, the insertion alleles per genome base, folded over the probes that cover it\n"
-            "-call_insertion_loci file : with -insertion_loci, the insertion alleles per genome base called against the background of the other samples, under the -call_* options\n");
+            "-call_insertion_loci file : with -insertion_loci, the insertion alleles per genome base called against the background of the other samples, under the -call_* options\n"
+            "-tag_mismatches 0|1 : 1 merges tags one base apart by family size before anything is counted (default 0); the reads are then kept on the device as for -consensus\n"
+            "-tag_map file : with -tag_mismatches 1, sample, mip_key, raw_tag, raw_family and corrected tag per uncorrected group\n");
     return 1;
 }
 
@@ -237,7 +248,8 @@ int main(int argc, char** argv)
     std::string consensus_prefix, pileup_path, call_path, ins_path, call_ins_path;
     mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
     bool call_option_given = false, loci_parts_given = false, loci_all = false;
-    std::string loci_path, call_loci_path, ins_loci_path, call_ins_loci_path;
+    std::string loci_path, call_loci_path, ins_loci_path, call_ins_loci_path, tag_map_path;
+    int tag_mism = 0;
     std::string out_path, label_path, label_kind = "tags", reads_a, reads_b, barcode_path, samples_path, index_arg, index_len_arg;
     std::vector<std::string> inputs;
     for (int i = 1; i < argc; i++) {
@@ -290,6 +302,8 @@ int main(int argc, char** argv)
             if (!parse_int_list(v, pr) || pr.size() != 2 || !(pr[0] > 0 && pr[0] < pr[1] && pr[1] <= (1L << 30))) return usage("-call_prior takes a,n with 0 < a < n <= 2^30");
             call_prm.a0 = (int32_t)pr[0]; call_prm.n0 = (int32_t)pr[1]; call_option_given = true;
         }
+        else if (a == "-tag_mismatches") { if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-tag_mismatches must be 0 or 1"); tag_mism = (int)iv; }
+        else if (a == "-tag_map") { if (v.empty()) return usage("-tag_map takes a file"); tag_map_path = v; }
         else if (a == "-barcode_mismatches") {
             if (!svr_parse_int(v.c_str(), &iv) || iv < 0 || iv > 1) return usage("-barcode_mismatches must be 0 or 1");
             bc_mism = (int)iv; bc_mism_given = true;
@@ -308,7 +322,11 @@ int main(int argc, char** argv)
     const bool consensus = !consensus_prefix.empty();
     if (min_family_given && !consensus) return usage("-min_family needs -consensus prefix");
     if (consensus && te + tl == 0) return usage("-consensus needs tag bases: with -tag_sizes 0,0 there are no molecules to collapse");
-    const bool pileup = !pileup_path.empty(), keep_reads = consensus || pileup;      // (-pileup reads the consensus reads: its session keeps the reads too)
+    if (tag_mism && te + tl == 0) return usage("-tag_mismatches 1 needs tag bases: with -tag_sizes 0,0 there are no tags to correct");
+    const bool tag_map = !tag_map_path.empty();
+    if (tag_map && !tag_mism) return usage("-tag_map needs -tag_mismatches 1");
+    // (-pileup reads the consensus reads: its session keeps the reads too; -tag_mismatches 1 merges by family size, which only such a session has)
+    const bool pileup = !pileup_path.empty(), keep_reads = consensus || pileup || tag_mism;
     if (pile_option_given && !pileup) return usage("-pileup_min_family and -pileup_min_quality need -pileup file");
     if (pile_indels && !pileup) return usage("-pileup_indels needs -pileup file");
     const bool insertions = !ins_path.empty();
@@ -455,6 +473,9 @@ int main(int argc, char** argv)
     if (call_ins_loci && !(call_ins_loci_out = fopen(call_ins_loci_path.c_str(), "w")))
         return usage("-call_insertion_loci " + call_ins_loci_path + ": can't write " + call_ins_loci_path);
 
+    FILE* tag_map_out = nullptr;
+    if (tag_map && !(tag_map_out = fopen(tag_map_path.c_str(), "w"))) return usage("-tag_map " + tag_map_path + ": can't write " + tag_map_path);
+
     // ---- the device ----
     mipgen_accel* h = nullptr;
     if (svr_tool_handle(&h) != MIPGEN_OK) { fprintf(stderr, "%s: %s\n", PROG, mipgen_accel_last_error()); return 1; }
@@ -480,6 +501,7 @@ int main(int argc, char** argv)
                            : mipgen_accel_reads_finish(h, reads, unique, tot);
     };
     if (open_session() != MIPGEN_OK) return die();
+    if (tag_mism && mipgen_accel_reads_set_tag_mismatches(h, tag_mism) != MIPGEN_OK) return die();
 
     // two chunks: the reader thread fills one while the device works on the other
     Chunk chunks[2];
@@ -536,6 +558,26 @@ int main(int argc, char** argv)
     mipgen_sample_totals stot{0, 0};
     mipgen_consensus_sizes csz{0, 0, 0};
     if (finish_session(reads.data(), unique.data(), &tot, &stot, row_pairs.data(), &csz) != MIPGEN_OK) return die();
+    // -tag_mismatches 1: what was merged, and the map of the raw groups
+    mipgen_tag_merge_totals tmt{0, 0, 0, 0, 0};
+    if (tag_mism && mipgen_accel_reads_last_tag_merge(h, &tmt) != MIPGEN_OK) return die();
+    if (tag_map) {
+        const size_t G0 = (size_t)tmt.raw_groups;
+        std::vector<int32_t> m_cell(G0), m_family(G0);
+        std::vector<uint32_t> m_raw(G0), m_tag(G0);
+        if (mipgen_accel_reads_tag_map_fetch(h, m_cell.data(), m_raw.data(), m_family.data(), m_tag.data()) != MIPGEN_OK) return die();
+        const int T = te + tl;
+        const size_t n_p = probes.size(), n_r = by_sample ? barcodes.size() + 1 : 1;
+        fprintf(tag_map_out, "sample\tmip_key\traw_tag\traw_family\ttag\n");
+        for (size_t g = 0; g < G0; g++) {
+            const size_t r = (size_t)m_cell[g] / n_p, i = (size_t)m_cell[g] % n_p;
+            char raw[17], cor[17];
+            for (int j = 0; j < T; j++) { raw[j] = "ACGT"[(m_raw[g] >> (2 * (T - 1 - j))) & 3u]; cor[j] = "ACGT"[(m_tag[g] >> (2 * (T - 1 - j))) & 3u]; }
+            raw[T] = cor[T] = 0;
+            fprintf(tag_map_out, "%s\t%s\t%s\t%d\t%s\n", !by_sample ? "*" : r + 1 < n_r ? sample_labels[r].c_str() : "undetermined", (*rows[i])[COL_KEY].c_str(), raw, m_family[g], cor);
+        }
+        if (fclose(tag_map_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, tag_map_path.c_str()); mipgen_accel_destroy(h); return 1; }
+    }
     const mipgen_consensus_sizes fsz = consensus ? csz : mipgen_consensus_sizes{0, 0, 0};      // (-pileup alone downloads no consensus read)
     std::vector<int32_t> g_cell((size_t)fsz.n_groups), g_family((size_t)fsz.n_groups);
     std::vector<uint32_t> g_tag((size_t)fsz.n_groups);
@@ -954,5 +996,8 @@ int main(int argc, char** argv)
     if (call_ins) fprintf(stderr, "%s: insertion calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, icall_calls, icall_cands, icall_tested, icall_deep);
     if (ins_loci) fprintf(stderr, "%s: insertion loci %zu alleles %lld events %lld ambiguous %lld span %lld\n", PROG, lplan.locus_pos.size(), iloci_alleles, iloci_events, iloci_amb, iloci_span);
     if (call_ins_loci) fprintf(stderr, "%s: insertion locus calls %lld candidates %lld tested %lld too_deep %lld\n", PROG, ilcall_calls, ilcall_cands, ilcall_tested, ilcall_deep);
+    if (tag_mism)
+        fprintf(stderr, "%s: tag_mismatches 1 raw %lld groups %lld absorbed %lld moved_pairs %lld max_depth %lld\n", PROG, (long long)tmt.raw_groups, (long long)tmt.groups,
+                (long long)tmt.absorbed, (long long)tmt.moved_pairs, (long long)tmt.max_depth);
     return 0;
 }
