@@ -852,6 +852,32 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
                                     int32_t n_points, const mipgen_svr_cv_point* points, double* target, mipgen_svr_cv_result* results,
                                     const char* fold_model_prefix);
 
+/* ---- deletion alleles: start and length per molecule, counted per sample --------------- */
+/* Everything up to the vote of a molecule at a template position is the gapped pileup's (4.13), `del` as fifth class.  Let c[t], 0 <= t < L, be the voted class of a
+ * used molecule of probe p at position t: A C G T, discordant, del, or nothing.  A deletion EVENT of the molecule is a maximal run [a, a + l) of positions with
+ * c[t] == del, so every del the gapped pileup counts belongs to exactly one event; l is bounded by L, not by max_indel.  The event is RAGGED when the molecule is
+ * discordant at a - 1 or at a + l with one of its two usable observations there a del: the two sides disagree on its extent (a flank outside [0, L) is never ragged).
+ * An ALLELE is (pos = pos_off[p] + a, length, ragged); records come in ascending order of the key pos << 35 | length << 1 | ragged, distinct, the same bytes from
+ * call to call.  The depth of a record is the depth at its FIRST deleted base: the used molecules whose class there is one of A C G T del - what the per-base caller
+ * of 4.14 takes as depth there -, so count <= depth and depth >= 1.
+ *   consensus_deletions: counts (n_pos x 8, may be NULL) is what mipgen_accel_reads_consensus_pileup_gapped returns for the same arguments; sites (n_pos x 4 int32, may
+ *                        be NULL): depth, starts (events whose first base is here), ragged (those of them that are ragged), del (molecules that vote del here) per
+ *                        position.  sites[:, 3] == counts[:, 5]; sites[:, 0] == counts[:, 0:4].sum(1) + counts[:, 5]; per position the counts of the records add up to
+ *                        sites[:, 1], those of the ragged ones to sites[:, 2]; for every position t the counts of the records with pos <= t < pos + length add up to
+ *                        counts[t][5].  totals (may be NULL): groups, used, gapped_sides as the gapped pileup's; depth = the sum of sites[:, 0]; deleted_bases = the sum
+ *                        of length x count = the gapped pileup's deletions; events, ragged = the sums of sites[:, 1] and [:, 2]; alleles = the records left on the handle.
+ *   deletions_fetch:     the records of the last consensus_deletions; n must equal its totals.alleles.
+ * MIPGEN_E_INVALID: every refusal of the gapped pileup; more than 2^29 - 1 template positions; more than 2^31 - 1 deleted bases (the bound of the events) in the row;
+ * fetch with another n.  MIPGEN_E_STATE: no consensus reads; fetch before any call (or after one that failed behind its refusals).  MIPGEN_E_NOMEM: the gapped pileup's
+ * bytes, 16 bytes per position of sites, and - once the count has given the deleted bases - 48 bytes per possible event and the sort's scratch, against held + free
+ * device memory; each check comes before the allocations it covers.  The call counts into scratch of its own (released with the reads): every other entry point, its
+ * scratch, its records and timing indices 0-18 are untouched by it; it may be repeated, for any row in any order.  A handle with zero groups gives zeros. */
+typedef struct mipgen_deletion_record { int64_t pos; int32_t length, count, ragged, depth; } mipgen_deletion_record;
+typedef struct mipgen_deletion_totals { int64_t groups, used, depth, deleted_bases, events, ragged, alleles, gapped_sides; } mipgen_deletion_totals;
+int mipgen_accel_reads_consensus_deletions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                           int32_t max_indel, int32_t* counts, int32_t* sites, mipgen_deletion_totals* totals);
+int mipgen_accel_deletions_fetch(mipgen_accel* h, mipgen_deletion_record* records, int64_t n);
+
 /* ---- instrumentation ------------------------------------------------------------------------------ */
 /* HIP-event time (ms) of the kernels of the last scoring call (summed over its windows), measured on the handle's stream;
  * negative if unavailable.  which: 0 = dense SVR kernel, 1 = records + scoring kernels, 2 = records / logistic kernel,
@@ -868,7 +894,8 @@ int mipgen_accel_cross_validate_svr(mipgen_accel* h, int32_t n, const double* x,
  * mipgen_accel_reads_consensus_insertion_pool, mipgen_accel_reads_consensus_insertion_call), the insertions route of its rows included (timing enabled);
  * 17 = the kernels of the last locus insertions call of any kind (mipgen_accel_locus_insertion_tables, mipgen_accel_reads_consensus_locus_insertions, _locus_insertion_pool,
  * _locus_insertion_call), the insertions route of its rows included (timing enabled); 18 = k_tag_parent, k_tag_root and k_tag_rewrite of the last
- * mipgen_accel_reads_finish_consensus of a session with tag mismatches 1 (timing enabled; its second sort and run boundaries are part of 10). */
+ * mipgen_accel_reads_finish_consensus of a session with tag mismatches 1 (timing enabled; its second sort and run boundaries are part of 10); 19 = the kernels of
+ * the last mipgen_accel_reads_consensus_deletions, its placement and count included (timing enabled). */
 double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which);
 /* enable/disable per-call event timing (it inserts two hipEventRecord per call) */
 int mipgen_accel_set_timing(mipgen_accel* h, int32_t enabled);

@@ -122,6 +122,11 @@ class LocusInsertionTotals(C.Structure):    # mipgen_locus_insertion_totals (DES
     _fields_ = [(n, C.c_int64) for n in ("loci", "span", "insertions", "ins_discordant", "ambiguous", "alleles", "folded", "dropped")]
 
 
+class DeletionTotals(C.Structure):    # mipgen_deletion_totals
+    _fields_ = [(n, C.c_int64) for n in ("groups", "used", "depth", "deleted_bases", "events", "ragged", "alleles", "gapped_sides")]
+
+
+DELETION_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("count", "<i4"), ("ragged", "<i4"), ("depth", "<i4")])   # mipgen_deletion_record, 24 bytes
 INSERTION_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("count", "<i4"), ("bases", "<u4"), ("ambiguous", "<i4")])   # mipgen_insertion_record, 24 bytes
 INSERTION_POOL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("bases", "<u4"), ("bg_alt", "<i4"), ("bg_excluded", "<i4")])   # mipgen_insertion_pool_record, 24 bytes
 INSERTION_CALL_RECORD_DTYPE = np.dtype([("pos", "<i8"), ("length", "<i4"), ("bases", "<u4"), ("depth", "<i4"), ("alt", "<i4"), ("bg_alt", "<i4"), ("bg_depth", "<i4"), ("q", "<i4"),
@@ -426,6 +431,10 @@ def load_library(path: Optional[str] = None):
                                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(InsertionTotals)]
     lib.mipgen_accel_insertions_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
     lib.mipgen_accel_insertions_fetch.restype = C.c_int
+    lib.mipgen_accel_reads_consensus_deletions.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(DeletionTotals)]
+    lib.mipgen_accel_deletions_fetch.argtypes = [vp, C.c_void_p, C.c_int64]
+    lib.mipgen_accel_deletions_fetch.restype = C.c_int
     lib.mipgen_accel_insertion_call_tables.argtypes = [vp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32,
                                                        C.POINTER(CallParams), C.POINTER(CallTotals)]
     lib.mipgen_accel_reads_consensus_insertion_pool.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -469,7 +478,7 @@ def load_library(path: Optional[str] = None):
     for name in ("open", "feed", "finish", "set_key_buffer", "last_assignment", "open_samples", "feed_samples", "finish_samples", "last_samples", "open_consensus",
                  "feed_consensus", "finish_consensus", "consensus_fetch", "consensus_pileup", "consensus_pileup_gapped", "consensus_call_pool", "consensus_call",
                  "consensus_locus_plan", "consensus_locus_pileup", "consensus_locus_call_pool", "consensus_locus_call", "consensus_locus_call_pileup_totals",
-                 "consensus_insertions", "set_tag_mismatches", "last_tag_merge", "tag_map_fetch"):
+                 "consensus_insertions", "consensus_deletions", "set_tag_mismatches", "last_tag_merge", "tag_map_fetch"):
         getattr(lib, "mipgen_accel_reads_" + name).restype = C.c_int
     lib.mipgen_accel_long_range_content.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.mipgen_accel_replay_condense.argtypes = [vp]
@@ -562,6 +571,7 @@ EXPORTED_SYMBOLS = [
     "mipgen_accel_locus_insertion_tables", "mipgen_accel_locus_insertions_fetch", "mipgen_accel_reads_consensus_locus_insertions",
     "mipgen_accel_reads_consensus_locus_insertion_pool", "mipgen_accel_locus_insertion_pool_fetch", "mipgen_accel_reads_consensus_locus_insertion_call",
     "mipgen_accel_locus_insertion_call_fetch",
+    "mipgen_accel_reads_consensus_deletions", "mipgen_accel_deletions_fetch",
 ]
 
 
@@ -1164,6 +1174,27 @@ class Accel:
         """mipgen_accel_insertions_fetch: the n records of the last consensus_insertions as an array of INSERTION_RECORD_DTYPE."""
         records = np.zeros(n, dtype=INSERTION_RECORD_DTYPE)
         self._check(self.lib.mipgen_accel_insertions_fetch(self.h, records.ctypes.data if n else None, n))
+        return records
+
+    # deletion alleles (DESIGN 4.21)
+    def consensus_deletions(self, mol_seq, mol_len: Sequence[int], row: int = 0, min_family: int = 1, min_quality: int = 0, max_indel: int = 8):
+        """mipgen_accel_reads_consensus_deletions, callable after consensus_reads: the deletion alleles of one row.  Arguments as consensus_pileup_gapped
+        takes them.  Returns (counts[sum(mol_len)][8] - the gapped pileup's table -, sites[sum(mol_len)][4] int32 - depth, starts, ragged, del per position -, the
+        records as an array of DELETION_RECORD_DTYPE in ascending key order, and the totals dict: groups, used, depth, deleted_bases, events, ragged, alleles,
+        gapped_sides)."""
+        lens, total, seq = self._templates(mol_seq, mol_len)
+        counts = np.empty((total, 8), dtype=np.int32)
+        sites = np.empty((total, 4), dtype=np.int32)
+        tot = DeletionTotals()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mipgen_accel_reads_consensus_deletions(self.h, seq, lens.ctypes.data_as(i32p), len(lens), row, min_family, min_quality, max_indel,
+                                                                    counts.ctypes.data_as(i32p), sites.ctypes.data_as(i32p), C.byref(tot)))
+        return counts, sites, self.deletions_fetch(int(tot.alleles)), self._totals(tot)
+
+    def deletions_fetch(self, n: int) -> np.ndarray:
+        """mipgen_accel_deletions_fetch: the n records of the last consensus_deletions as an array of DELETION_RECORD_DTYPE."""
+        records = np.zeros(n, dtype=DELETION_RECORD_DTYPE)
+        self._check(self.lib.mipgen_accel_deletions_fetch(self.h, records.ctypes.data if n else None, n))
         return records
 
     # insertion calls (DESIGN 4.17)

@@ -595,6 +595,7 @@ double mipgen_accel_last_kernel_ms(mipgen_accel* h, int32_t which)
     if (h && which == 16) return h->ins_call_ms;
     if (h && which == 17) return h->locus_ins_ms;
     if (h && which == 18) return h->tag_merge_ms;
+    if (h && which == 19) return h->deletions_ms;
     if (!h || !h->timing) return -1.0;
     if (hipSetDevice(h->device) != hipSuccess) return -1.0;
     double total = 0.0;

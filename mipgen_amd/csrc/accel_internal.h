@@ -273,6 +273,19 @@ struct InsScratch {
     size_t table_held() const { return anchors.cap * 4 + ctr.cap * sizeof(InsCounters); }
     void release() { count.release(); anchors.release(); ctr.release(); pairs.release(); records.release(); n_alleles = -1; }
 };
+// mipgen_accel_reads_consensus_deletions: a count scratch of its own, the sites table, the events and what orders them; released with the reads.
+// run keys and run counts take the place of pairs.keys and pairs.ids once the sort has read them.
+struct DelScratch {
+    CountScratch count;
+    DevBuf<int32_t> sites;                                   // positions x DELETION_COLUMNS
+    DevBuf<DelCounters> ctr;
+    SortedPairs pairs;                                       // the deleted bases of the row: the events at most (the sort moves pairs; nothing reads the ids)
+    DevBuf<mipgen_deletion_record> records;
+    int64_t n_alleles = -1;                                  // the records of the last call (-1: none, or it failed)
+    size_t event_held() const { return pairs.held() + records.cap * sizeof(mipgen_deletion_record); }
+    size_t table_held() const { return sites.cap * 4 + ctr.cap * sizeof(DelCounters); }
+    void release() { count.release(); sites.release(); ctr.release(); pairs.release(); records.release(); n_alleles = -1; }
+};
 // mipgen_accel_reads_consensus_insertion_pool: the sparse pool over the sample rows - S per position, keys and sums per distinct allele - and the
 // arguments it was built with; the entries and what orders them are held only while the pool is built.  Released with the reads.
 struct InsPool {
@@ -351,7 +364,8 @@ struct ConsensusResult {
     InsScratch ins;
     InsPool ins_pool;
     LocusInsScratch locus_ins;
-    DevBuf<uint64_t> keys;                                   // (cell << 32) | tag of every group, ascending
+    DelScratch del;
+    DevBuf<uint64_t> keys;                              // (cell << 32) | tag of every group, ascending
     DevBuf<int32_t> family;
     DevBuf<int64_t> ext_off, lig_off;                        // n_groups + 1
     DevBuf<uint8_t> ext_seq, ext_qual, lig_seq, lig_qual;
@@ -362,7 +376,7 @@ struct ConsensusResult {
     DevBuf<uint64_t> raw_keys;                               // raw_groups
     DevBuf<int32_t> raw_family, raw_root;                    // ... the family of each and the raw group that is its root
     ConsensusView view() const { return {keys.p, family.p, ext_off.p, lig_off.p, ext_seq.p, ext_qual.p, lig_seq.p, lig_qual.p, n_groups}; }
-    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); raw_keys.release(); raw_family.release(); raw_root.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); locus_ins.release(); }
+    void release() { keys.release(); family.release(); ext_off.release(); lig_off.release(); ext_seq.release(); ext_qual.release(); lig_seq.release(); lig_qual.release(); raw_keys.release(); raw_family.release(); raw_root.release(); pile.release(); gapped.release(); call.release(); locus.release(); ins.release(); ins_pool.release(); locus_ins.release(); del.release(); }
 };
 
 struct mipgen_accel {
@@ -497,6 +511,7 @@ struct mipgen_accel {
     LocusInsRun locus_ins;           // the last fold of insertion alleles to loci, its records and locus anchor table (accel_pileup.hip)
     InsCallRun locus_ins_call;       // the last insertion call per locus: a run of its own, so that mipgen_accel_insertion_call_fetch keeps finding the last call per probe
     double locus_ins_ms = -1.0;      // the kernels of the last locus insertions call of any kind, the insertions route of its rows included (timing enabled)
+    double deletions_ms = -1.0;      // the kernels of the last mipgen_accel_reads_consensus_deletions (timing enabled)
     // timing: four events per window (records | svr | replay), summed over the windows of the last call
     bool timing = false;
     std::vector<hipEvent_t> ev;

@@ -4,7 +4,8 @@
 // _locus_pileup / _locus_call_pool / _locus_call), and the insertion alleles of a row (4.16: mipgen_accel_reads_consensus_insertions, mipgen_accel_insertions_fetch) and their calls against a sparse pool over the sample rows (4.17: mipgen_accel_insertion_call_tables,
 // _reads_consensus_insertion_pool, _insertion_pool_fetch, _reads_consensus_insertion_call, _insertion_call_fetch) and, folded to genome loci by the installed plan between
 // the insertions of a row and its pool or call (4.19: mipgen_accel_locus_insertion_tables, _locus_insertions_fetch, _reads_consensus_locus_insertions / _locus_insertion_pool /
-// _locus_insertion_call, _locus_insertion_pool_fetch, _locus_insertion_call_fetch: fold_insertions is the one fold).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
+// _locus_insertion_call, _locus_insertion_pool_fetch, _locus_insertion_call_fetch: fold_insertions is the one fold), and the deletion alleles of a row (4.21:
+// mipgen_accel_reads_consensus_deletions, mipgen_accel_deletions_fetch, counting into the DelScratch of the ConsensusResult).  The arguments of a row travel as one RowArgs.  plan_row makes every check of them (nothing allocated or launched);
 // count_row is the ONE count: the budget, prepare_row (the row's buffers, the cell boundaries and the (cell, round) units: a filled PileRow), the launches of the plain
 // or the gapped table, download and totals of one row into the CountScratch it is given.  Every entry point gives a scratch of its own - `pile` / `gapped` of the
 // ConsensusResult, of its CallScratch, of its LocusScratch, of its InsScratch - so no call touches what another holds.  A pool and a call are one route each (build_pool, call_row) over
@@ -526,6 +527,71 @@ static int insertions_row(mipgen_accel* h, const RowPlan& P, const RowArgs& A, i
     return MIPGEN_OK;
 }
 
+// ---- deletion alleles ------------------------------------------------------------------------------------------------------------------------------
+// The deletion alleles of one planned row into R->del, the kernels spans of `timer`: the gapped count with three-plane projections, then - the events being bounded by
+// its `deletions` total, the deleted bases - the sites table and the events in one pass of the count frame, the keys sorted, their runs, and a record per run.  The
+// sites table and the S.n_alleles records stay on the device (a session without groups leaves neither, and 0 records).  Reads R's groups and reads; writes R->del only.
+static int deletions_row(mipgen_accel* h, const RowPlan& P, const RowArgs& A, int32_t row, SpanTimer& timer, int32_t* counts, int32_t* sites, mipgen_deletion_totals* totals)
+{
+    DelScratch& S = P.R->del;
+    S.n_alleles = -1;
+    const size_t np = (size_t)P.n_pos, cells = np * DELETION_COLUMNS;
+    hipStream_t st = h->stream;
+    mipgen_gapped_totals gt;
+    Counted counted;
+    const Budget B{"deletions", padded(cells, 4) + padded(1, sizeof(DelCounters)), S.table_held()};
+    if (int rc = count_row(h, P, S.count, B, A, row, timer, counts, &gt, &counted)) return rc;
+    if (!counted.have_row) {                                             // (a session without groups: nothing was launched)
+        if (sites) memset(sites, 0, cells * sizeof(int32_t));
+        if (totals) *totals = mipgen_deletion_totals{};
+        S.n_alleles = 0;
+        return MIPGEN_OK;
+    }
+    const int64_t cap = gt.deletions;                                    // every event holds one deleted base at least
+    if (cap < 0 || cap > 0x7fffffff) return fail(MIPGEN_E_INVALID, "deletions: %lld deleted bases in row %d bound its events: 2^31 - 1 at most", (long long)cap, row);
+    // the events' bytes, known only now: checked before they are allocated
+    const size_t ne = (size_t)cap;
+    if (cap > 0) {
+        size_t scratch = 0, room = 0;
+        HIP_TRY(SortedPairs::scratch_bytes(st, cap, 64, cap, 0, &scratch));
+        const size_t need = SortedPairs::bytes(ne, scratch) + padded(ne, sizeof(mipgen_deletion_record));
+        if (int rc = room_beside(S.event_held(), &room)) return rc;
+        if (need > room)
+            return fail(MIPGEN_E_NOMEM, "deletions: up to %lld events need %zu MiB of device memory, %zu MiB are free", (long long)cap, need >> 20, room >> 20);
+        if (S.pairs.reserve(ne, scratch) || S.records.reserve(ne)) return MIPGEN_E_NOMEM;
+    }
+    if (S.sites.reserve(cells) || S.ctr.reserve(1)) return MIPGEN_E_NOMEM;
+    IdleOnExit idle{st};
+    DelCounters dc;
+    HIP_TRY(hipMemsetAsync(S.ctr.p, 0, sizeof dc, st));
+    if (cap > 0) HIP_TRY(hipMemsetAsync(S.pairs.ids.p, 0, ne * 4, st));
+    const CountScratch& W = S.count;
+    timer.mark();
+    HIP_TRY(mipgen_launch_deletions(st, P.R->view(), counted.row, P.n_units, counted.g_first, W.proj_off.p, W.proj.p, S.sites.p, S.pairs.keys.p, cap, S.ctr.p));
+    timer.mark();
+    HIP_TRY(hipMemcpyAsync(&dc, S.ctr.p, sizeof dc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t events = (int64_t)dc.events;
+    if (dc.events > (unsigned long long)cap || (int64_t)dc.length_sum != cap || (int64_t)dc.deleted != cap || dc.starts != dc.events)
+        return fail(MIPGEN_E_STATE, "deletions: %llu events emitted and %llu counted, %llu bases in them and %llu counted of %lld", dc.events, dc.starts, dc.length_sum,
+                    dc.deleted, (long long)cap);
+    if (events > 0) {
+        timer.mark();
+        int32_t* run_counts = reinterpret_cast<int32_t*>(S.pairs.ids.p);
+        HIP_TRY(S.pairs.sort(st, events, 64));
+        HIP_TRY(S.pairs.runs(st, events, S.pairs.keys.p, run_counts, &S.ctr.p->alleles));
+        HIP_TRY(mipgen_launch_deletion_records(st, S.pairs.keys.p, run_counts, &S.ctr.p->alleles, events, S.sites.p, P.n_pos, S.records.p));
+        timer.mark();
+        HIP_TRY(hipMemcpyAsync(&dc, S.ctr.p, sizeof dc, hipMemcpyDeviceToHost, st));
+    }
+    if (sites) HIP_TRY(hipMemcpyAsync(sites, S.sites.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(idle.wait());
+    if ((int64_t)dc.alleles > events || (events > 0 && dc.alleles == 0)) return fail(MIPGEN_E_STATE, "deletions: %llu alleles of %lld events", dc.alleles, (long long)events);
+    S.n_alleles = (int64_t)dc.alleles;
+    if (totals) *totals = {gt.groups, gt.used, (int64_t)dc.depth, cap, events, (int64_t)dc.ragged, S.n_alleles, gt.gapped_sides};
+    return MIPGEN_OK;
+}
+
 // the first `used` elements of b kept while it grows to `want` (DevBuf::reserve lets go of what it held)
 template <typename T>
 static int grow_keeping(DevBuf<T>& b, size_t used, size_t want, hipStream_t st)
@@ -852,6 +918,29 @@ int mipgen_accel_insertions_fetch(mipgen_accel* h, mipgen_insertion_record* reco
     if (int rc = check_reads(h)) return rc;
     const InsScratch& S = h->consensus->ins;
     return fetch_records(h, S.records, S.n_alleles, "the consensus reads hold no insertion alleles: mipgen_accel_reads_consensus_insertions leaves them", "insertions call",
+                         records, n);
+}
+
+// Deletion alleles of one row: deletions_row with a timer of its own.  Reads R's groups and reads; writes R->del only.
+int mipgen_accel_reads_consensus_deletions(mipgen_accel* h, const char* mol_seq, const int32_t* mol_len, int32_t n, int32_t row, int32_t min_family, int32_t min_quality,
+                                           int32_t max_indel, int32_t* counts, int32_t* sites, mipgen_deletion_totals* totals)
+{
+    RowPlan P;
+    const RowArgs A{mol_seq, mol_len, n, min_family, min_quality, max_indel, true, true};
+    if (int rc = plan_row(h, A, row, &P)) return rc;
+    if (P.n_pos > MIPGEN_CALL_MAX_POSITIONS) return fail(MIPGEN_E_INVALID, "%lld template positions: the deletion alleles take 2^29 - 1 at most", (long long)P.n_pos);
+    h->deletions_ms = -1.0;
+    SpanTimer timer{h->timing, h->stream};
+    if (int rc = deletions_row(h, P, A, row, timer, counts, sites, totals)) return rc;
+    return booked(timer, &h->deletions_ms);
+}
+
+// The records of the last deletions call, in ascending key order.
+int mipgen_accel_deletions_fetch(mipgen_accel* h, mipgen_deletion_record* records, int64_t n)
+{
+    if (int rc = check_reads(h)) return rc;
+    const DelScratch& S = h->consensus->del;
+    return fetch_records(h, S.records, S.n_alleles, "the consensus reads hold no deletion alleles: mipgen_accel_reads_consensus_deletions leaves them", "deletions call",
                          records, n);
 }
 

@@ -200,6 +200,37 @@ GAP_HD uint64_t gap_locus_allele_key(uint32_t word, int l, bool ambiguous, uint3
 }
 #define GAP_LOCUS_NONE 0xFFFFFFFFu   // own[a] / prev[a] of an anchor row no source pulls
 
+// ---- deletion alleles -----------------------------------------------------------------------------------------------------------------------
+// the class of one observation, and of a molecule at a position: 0..3 = A C G T
+#define GAP_CLASS_DEL 4u
+#define GAP_CLASS_NONE 5u
+#define GAP_CLASS_DISC 6u
+
+// The vote of one molecule at one position from its two usable observations (each 0..3, GAP_CLASS_DEL or GAP_CLASS_NONE; a molecule that is not used brings
+// GAP_CLASS_NONE twice): nothing, the one class, the shared class, or discordant.
+GAP_HD uint32_t gap_molecule_class(uint32_t ce, uint32_t cl)
+{
+    const bool ue = ce < GAP_CLASS_NONE, ul = cl < GAP_CLASS_NONE;
+    return ue && ul && ce != cl ? GAP_CLASS_DISC : ue ? ce : ul ? cl : GAP_CLASS_NONE;
+}
+
+// The molecule is discordant here and one of its two usable observations is a deletion: next to a run of deletions, the two sides disagree on its extent.
+GAP_HD bool gap_ragged_flank(uint32_t ce, uint32_t cl) { return gap_molecule_class(ce, cl) == GAP_CLASS_DISC && (ce == GAP_CLASS_DEL || cl == GAP_CLASS_DEL); }
+
+// The consecutive set bits of mask from bit `lane` upwards (0 if that bit is clear, 64 - lane at most): the part of a run of deletions that lies in the 64
+// positions of one round.
+GAP_HD int gap_mask_run(uint64_t mask, int lane)
+{
+    const uint64_t clear = ~(mask >> lane);                                     // (the shift brings zeros in from above: set bits here, unless lane is 0)
+    return clear == 0 ? 64 : __builtin_ctzll(clear);
+}
+
+// The 64-bit key of a deletion allele: x << 35 | l << 1 | ragged, x < 2^29, l <= GAP_MAX_MOL < 2^12.  Ascending: position, then length, then clean before ragged.
+GAP_HD uint64_t gap_deletion_key(int64_t x, int l, bool ragged) { return ((uint64_t)x << 35) | ((uint64_t)(uint32_t)l << 1) | (uint64_t)(ragged ? 1u : 0u); }
+GAP_HD int64_t gap_deletion_pos(uint64_t key) { return (int64_t)(key >> 35); }
+GAP_HD int gap_deletion_length(uint64_t key) { return (int)((key >> 1) & 0xfffu); }
+GAP_HD bool gap_deletion_ragged(uint64_t key) { return (key & 1u) != 0; }
+
 // ---- the serial row: what k_gap_align's lanes do for row i >= 1, one lane after the other (host only) ----------------------------------------------------
 // h_prev / h: the GAP_LANES values of row i - 1 / i (GAP_NEG outside the band); q_byte = q[i - 1]; two words of directions go to dirs2.
 static inline void gap_row_serial(int i, int W, int L, int side, int q_byte, const uint8_t* M, const int* h_prev, int* h, uint32_t* dirs2)

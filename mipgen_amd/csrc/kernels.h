@@ -196,6 +196,11 @@ hipError_t mipgen_launch_insertions(hipStream_t, const ConsensusView& C, const P
                                     int32_t* anchors, uint64_t* keys, int64_t cap, InsCounters* ctr);
 hipError_t mipgen_launch_insertion_records(hipStream_t, const uint64_t* run_keys, const int32_t* run_counts, const unsigned long long* n_runs, int64_t cap,
                                            mipgen_insertion_record* records);
+// deletion alleles: the sites table and the events of a row from its three-plane projections; the runs of the sorted keys as records
+hipError_t mipgen_launch_deletions(hipStream_t, const ConsensusView& C, const PileRow& R, int64_t n_units, uint32_t g_first, const int64_t* proj_off, const uint8_t* proj,
+                                   int32_t* sites, uint64_t* keys, int64_t cap, DelCounters* ctr);
+hipError_t mipgen_launch_deletion_records(hipStream_t, const uint64_t* run_keys, const int32_t* run_counts, const unsigned long long* n_runs, int64_t cap, const int32_t* sites,
+                                          int64_t n_pos, mipgen_deletion_record* records);
 // kernels_call.hip: one row's table added into the pool (K[5], N[5] per position); the candidates of a table against the pool (cand: 4 n_pos records, ctr
 // zero on entry); their scores, sort keys and ctr->calls; the calls in key order
 hipError_t mipgen_launch_call_pool(hipStream_t, const int32_t* counts, int columns, int64_t n_pos, int32_t bg_max_ppm, int32_t* pool);

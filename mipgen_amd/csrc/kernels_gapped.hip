@@ -29,6 +29,13 @@
 //                 consensus reads through the run indices, votes per base, packs the key (gap_allele_key) and writes it with one 8-byte store.  The group loop is
 //                 wave-uniform, so the ballot sees the whole wavefront.  The slots are exact beforehand: the `insertions` total of the GapPile count.
 //  k_ins_records  a lane per run of the sorted keys (mipgen_consensus_sort, mipgen_consensus_runs): key and count decoded into a 24-byte record.
+//
+// Deletion alleles, over the three-plane projections of 4.13.
+//  DelPile        a third policy of the count frame, k_del_wave / k_del_wg: four counters per position (depth, starts, ragged, del; one 16-byte store) from the voted
+//                 class of every molecule, and the maximal runs of `del` along a molecule as events: a start lane is one that votes del while the lane below does
+//                 not (a shuffle; lane 0 of a later round observes t - 1 itself), the length the consecutive set bits of the ballot of del lanes and, past lane 63,
+//                 direct observations.  The slots are bounded beforehand by the `deletions` total of the GapPile count.
+//  k_del_records  a lane per run of the sorted keys: key and count decoded into a 24-byte record, its depth read from the sites table.
 #include "pileup_frame.h"
 #include "gapped_align.h"
 
@@ -181,10 +188,7 @@ __global__ __launch_bounds__(64) void k_gap_align(const uint32_t* __restrict__ l
 }
 
 // ---- the count ------------------------------------------------------------------------------------------------------------------------------------------
-#define GAP_CLASS_DEL 4u
-#define GAP_CLASS_NONE 5u
-#define GAP_CLASS_DISC 6u
-
+// (the classes GAP_CLASS_DEL, GAP_CLASS_NONE and GAP_CLASS_DISC are gapped_align.h's)
 // where the count finds the projections: proj_off[2 (g - g_first) + side] into proj, or -1
 struct GapProj { uint32_t g_first; const int64_t* __restrict__ off; const uint8_t* __restrict__ bytes; };
 
@@ -346,6 +350,114 @@ __global__ __launch_bounds__(256) void k_ins_records(const uint64_t* __restrict_
     records[i] = r;
 }
 
+// ---- deletion alleles -------------------------------------------------------------------------------------------------------------------------
+// where the events go: keys[0, cap), the slots reserved through ctr->events
+struct DelEmit { uint64_t* __restrict__ keys; unsigned long long cap; DelCounters* __restrict__ ctr; };
+
+// one group's reads and projections, as the observations of a position need them
+struct DelMolecule { int64_t eo, lo, pe, pl; int el, ll; bool ok; };
+
+// The class of the molecule at template position t (t <= L; L itself for a clamped lane, whose value is discarded) and whether a run of deletions that borders on
+// t is ragged there.  A molecule that is not used has no class.
+__device__ static inline uint32_t del_class(const ConsensusView& I, const PileRow& R, const GapProj& P, const DelMolecule& m, int t, int L, uint32_t& ce, uint32_t& cl)
+{
+    uint32_t ne, nl;
+    bool ve, vl;
+    gap_observe(P.bytes, m.pe, I.ext_seq, I.ext_qual, m.eo, m.el, t, t, L, false, R.min_quality, ce, ve, ne);
+    gap_observe(P.bytes, m.pl, I.lig_seq, I.lig_qual, m.lo, m.ll, L - 1 - t, t, L, true, R.min_quality, cl, vl, nl);
+    if (!m.ok) ce = cl = GAP_CLASS_NONE;
+    return gap_molecule_class(ce, cl);
+}
+
+// A third policy of the count frame, k_del_wave / k_del_wg: four counters per position (depth, starts, ragged, del; one 16-byte store) and THE EVENTS as a side
+// effect.  A lane whose molecule votes del while the lane below does not is the start of a maximal run; its length is the consecutive set bits of the ballot of the
+// del lanes from its own position and, only where that run reaches lane 63 and the template goes on, the positions of the rounds behind observed directly.  The
+// next round's wavefront sees that tail as "not a start" by the same rule.  Everything the wavefront decides on - the ballots, lane 0's neighbour, the
+// continuation - is wave-uniform, so no lane waits for another.
+struct DelPile {
+    static constexpr int COLUMNS = DELETION_COLUMNS;
+    using Counters = DelCounters;
+    static constexpr ColumnSum<DelCounters> SUMS[4] = {{0, 1, &DelCounters::depth}, {1, 2, &DelCounters::starts}, {2, 3, &DelCounters::ragged}, {3, 4, &DelCounters::deleted}};
+    int n[COLUMNS] = {0, 0, 0, 0};                                                          // depth, starts, ragged, del
+    __device__ static inline void groups(DelPile& S, const ConsensusView& I, const PileRow& R, uint32_t g0, uint32_t g1, uint32_t stride, int t, int L, const GapProj& P,
+                                         const DelEmit& E)
+    {
+        const int lane = threadIdx.x & 63;
+        const int t0 = __builtin_amdgcn_readfirstlane(t);                                   // the round's first position (lane 0 is never clamped)
+        const bool live = t < L;
+        for (uint32_t g = g0; g < g1; g += stride) {                                        // (wave-uniform: every lane of the wavefront is here)
+            DelMolecule m;
+            m.eo = I.ext_off[g]; m.lo = I.lig_off[g];
+            m.el = (int)(I.ext_off[g + 1] - m.eo); m.ll = (int)(I.lig_off[g + 1] - m.lo);
+            m.pe = P.off[2 * (size_t)(g - P.g_first)]; m.pl = P.off[2 * (size_t)(g - P.g_first) + 1];
+            m.ok = I.family[g] >= R.min_family;
+            uint32_t ce, cl;
+            const uint32_t c = del_class(I, R, P, m, t, L, ce, cl);
+            const bool del = live && c == GAP_CLASS_DEL;                                    // (a lane clamped at or beyond the template's end is no part of any run)
+            const bool rag = live && gap_ragged_flank(ce, cl);
+            S.n[0] += c < GAP_CLASS_NONE; S.n[3] += c == GAP_CLASS_DEL;
+            const unsigned long long dels = __ballot(del);
+            if (dels == 0ull) continue;                                                     // (the wavefront's: the common case ends here)
+            // the class of the position below: the lane below, or for lane 0 of a later round one more observation; nothing at t = 0
+            bool below_del = __shfl_up((int)del, 1) != 0, below_rag = __shfl_up((int)rag, 1) != 0;
+            if ((dels & 1ull) && t0 > 0) {                                                  // (wave-uniform)
+                uint32_t be, bl;
+                const uint32_t b = del_class(I, R, P, m, t0 - 1, L, be, bl);
+                if (lane == 0) { below_del = b == GAP_CLASS_DEL; below_rag = gap_ragged_flank(be, bl); }
+            } else if (lane == 0) {
+                below_del = false; below_rag = false;
+            }
+            const bool start = del && !below_del;
+            const unsigned long long starts = __ballot(start);
+            if (starts == 0ull) continue;                                                   // (the wavefront's: every del lane continues a run of the round before)
+            const unsigned long long rags = __ballot(rag);
+            int l = start ? gap_mask_run(dels, lane) : 0;
+            const int after = lane + l;                                                     // the lane behind the run, 64 if the run reaches the round's end
+            bool above_rag = start && after < 64 && ((rags >> (after & 63)) & 1ull);
+            // the one run that reaches lane 63, where the template goes on: wave-uniform direct observations behind the round
+            const bool reaches = start && after == 64;
+            if (__ballot(reaches) != 0ull && t0 + 64 < L) {
+                int more = 0;
+                bool end_rag = false;
+                for (int tt = t0 + 64; tt < L; tt++) {
+                    uint32_t xe, xl;
+                    if (del_class(I, R, P, m, tt, L, xe, xl) != GAP_CLASS_DEL) { end_rag = gap_ragged_flank(xe, xl); break; }
+                    more++;
+                }
+                if (reaches) { l += more; above_rag = end_rag; }
+            }
+            const bool ragged = start && (below_rag || above_rag);
+            S.n[1] += start; S.n[2] += ragged;
+            const long long sum = wave_sum_i64((long long)l);
+            unsigned long long first = 0;
+            if (lane == 0) {
+                first = atomicAdd(&E.ctr->events, (unsigned long long)__popcll(starts));
+                atomicAdd(&E.ctr->length_sum, (unsigned long long)sum);
+            }
+            first = __shfl(first, 0);
+            if (start) {
+                const unsigned long long slot = first + (unsigned long long)__popcll(starts & ((1ull << lane) - 1ull));
+                const uint32_t p = (uint32_t)(I.keys[g] >> 32) - R.cell0;
+                if (slot < E.cap) E.keys[slot] = gap_deletion_key(R.pos_off[p] + t, l, ragged);
+            }
+        }
+    }
+    __device__ inline void store(int32_t* __restrict__ o) const { *reinterpret_cast<int4*>(o) = make_int4(n[0], n[1], n[2], n[3]); }      // (16 bytes per position, the table 256-byte aligned)
+};
+
+// a lane per run of the sorted keys: the record's depth is the sites table's at the run's first base
+__global__ __launch_bounds__(256) void k_del_records(const uint64_t* __restrict__ run_keys, const int32_t* __restrict__ run_counts, const unsigned long long* __restrict__ n_runs,
+                                                     int64_t cap, const int32_t* __restrict__ sites, int64_t n_pos, mipgen_deletion_record* __restrict__ records)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap || (unsigned long long)i >= *n_runs) return;
+    const uint64_t key = run_keys[i];
+    mipgen_deletion_record r;
+    r.pos = gap_deletion_pos(key); r.length = gap_deletion_length(key); r.count = run_counts[i]; r.ragged = gap_deletion_ragged(key) ? 1 : 0;
+    r.depth = r.pos < n_pos ? sites[r.pos * DELETION_COLUMNS] : 0;                          // (a key is a position of the table: the guard costs nothing)
+    records[i] = r;
+}
+
 extern "C" {
 
 size_t mipgen_gap_align_lds_bytes(int max_len, int W) { return (size_t)2 * (size_t)(max_len + W) * 2 * sizeof(uint32_t); }
@@ -396,6 +508,25 @@ hipError_t mipgen_launch_insertion_records(hipStream_t st, const uint64_t* run_k
 {
     if (cap < 1 || cap > 0x7fffffff) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_ins_records, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, run_keys, run_counts, n_runs, cap, records);
+    return hipGetLastError();
+}
+
+// sites[R.n_pos][4] written whole and summed into ctr, the deletion events of the row into keys[0, cap) in no defined order, ctr->events their number and
+// ctr->length_sum the sum of their lengths (ctr zero on entry); proj_off / proj: the three-plane projections of the row
+hipError_t mipgen_launch_deletions(hipStream_t st, const ConsensusView& C, const PileRow& R, int64_t n_units, uint32_t g_first, const int64_t* proj_off, const uint8_t* proj,
+                                   int32_t* sites, uint64_t* keys, int64_t cap, DelCounters* ctr)
+{
+    if (R.n_small < 0 || R.n_big < 0 || R.n_small + R.n_big != n_units || n_units > 0x7fffffff || R.n_pos < 1 || R.n_pos > MIPGEN_CALL_MAX_POSITIONS || cap < 0 || cap > 0x7fffffff)
+        return hipErrorInvalidValue;
+    return pile_launch<DelPile>(st, C, R, sites, ctr, GapProj{g_first, proj_off, proj}, DelEmit{keys, (unsigned long long)cap, ctr});
+}
+
+// the first min(*n_runs, cap) runs decoded into records, their depth read from sites[n_pos][4]
+hipError_t mipgen_launch_deletion_records(hipStream_t st, const uint64_t* run_keys, const int32_t* run_counts, const unsigned long long* n_runs, int64_t cap, const int32_t* sites,
+                                          int64_t n_pos, mipgen_deletion_record* records)
+{
+    if (cap < 1 || cap > 0x7fffffff || n_pos < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_del_records, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, run_keys, run_counts, n_runs, cap, sites, n_pos, records);
     return hipGetLastError();
 }
 

@@ -122,3 +122,6 @@ struct GappedCounters { unsigned long long n_sides, proj_bytes, gapped_sides, ba
 // insertion alleles: the columns of the anchor table; what InsPile sums and emits, and the runs of the sorted keys
 #define INSERTION_COLUMNS 4          // span, ins, ins_discordant, ambiguous
 struct InsCounters { unsigned long long span, insertions, ins_discordant, ambiguous, events, alleles; };
+// deletion alleles: the columns of the sites table; what DelPile sums and emits - the events and the sum of their lengths -, and the runs of the sorted keys
+#define DELETION_COLUMNS 4           // depth, starts, ragged, del
+struct DelCounters { unsigned long long depth, starts, ragged, deleted, events, length_sum, alleles; };

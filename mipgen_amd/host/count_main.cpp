@@ -51,6 +51,14 @@
 //                           `length` times N for the molecules whose inserted bases could not be told; span = the molecules that cover the anchor with one agreed
 //                           length, 0 included; ppm = floor(count 10^6 / span)
 //   stderr     a last line: "mipgen_count: insertion alleles A events I ambiguous B span S"
+//   -pileup_deletions DEL   needs -pileup_indels: the deletions as events, start and length per molecule.  One deletions call per row (undetermined too)
+//                           feeds DEL only - a second count of the row beside whatever feeds FILE; FILE and every other file are byte for byte what they are without
+//                           the option.  Header ">sample <tab> mip_key <tab> chr <tab> position <tab> strand <tab> length <tab> deleted <tab> ragged <tab> count <tab>
+//                           depth <tab> ppm"; one line per allele in row order, then table order, then the order of the records.  position is the LOWEST genome
+//                           coordinate of the deleted bases, on both strands; deleted is the template's bytes in genome plus orientation (reverse-complemented on a
+//                           '-' probe); ragged = 1 where the two reads of the molecules disagree on the extent; depth = the molecules that vote A C G T or del at
+//                           the first deleted base; ppm = floor(count 10^6 / depth)
+//   stderr     a last line: "mipgen_count: deletion alleles A events E ragged R deleted_bases B"
 //   -call_insertions ICALLS needs -pileup_insertions: the insertion alleles of every row called against a background of the other samples, under the
 //                           -call_* options.  One pool call, then one insertion call per row (undetermined too) that takes the place of the insertions call: FILE
 //                           and INS are byte for byte what they are without the option.  Header ">sample <tab> mip_key <tab> chr <tab> position <tab> strand <tab>
@@ -135,6 +143,7 @@ static int usage(const std::string& msg)
             "-pileup file : A, C, G, T and discordant molecules per captured base, in genome plus orientation; -pileup_min_family k (default 1), -pileup_min_quality q, 0..40 (default 0)\n"
             "-pileup_indels W : with -pileup, place the reads with up to W (1..15) inserted or deleted bases first; adds the columns del, ins, ins_discordant\n"
             "-pileup_insertions file : with -pileup_indels, the inserted bases per anchor: length, bases, molecules, spanning molecules and ppm per allele\n"
+            "-pileup_deletions file : with -pileup_indels, the deletions as events: start, length, deleted bases, ragged, molecules, depth at the first base and ppm per allele\n"
             "-call_insertions file : with -pileup_insertions, the insertion alleles of every sample called against the background of the others, under the -call_* options\n"
             "-call file : with -pileup, variant calls of every sample against the background of the others; -call_min_depth n (default 20), -call_min_alt k (3), -call_min_ppm p (0),\n"
             "    -call_min_q q, 0..9999 (30), -call_prior a,n : error prior a/n, 0 < a < n <= 2^30 (1,1000), -call_background_max_ppm p, 0..1000000 (200000)\n"
@@ -245,7 +254,7 @@ int main(int argc, char** argv)
     int te = 5, tl = 0, mism = 0, bc_mism = 0;
     long min_family = 1, pile_family = 1, pile_quality = 0, pile_indels = 0;
     bool swap = false, bc_mism_given = false, min_family_given = false, pile_option_given = false;
-    std::string consensus_prefix, pileup_path, call_path, ins_path, call_ins_path;
+    std::string consensus_prefix, pileup_path, call_path, ins_path, call_ins_path, del_path;
     mipgen_call_params call_prm{20, 3, 0, 30, 1, 1000, 200000};
     bool call_option_given = false, loci_parts_given = false, loci_all = false;
     std::string loci_path, call_loci_path, ins_loci_path, call_ins_loci_path, tag_map_path;
@@ -285,6 +294,7 @@ int main(int argc, char** argv)
         else if (a == "-pileup_min_quality") { if (!svr_parse_int(v.c_str(), &pile_quality) || pile_quality < 0 || pile_quality > 40) return usage("-pileup_min_quality must be 0 to 40"); pile_option_given = true; }
         else if (a == "-pileup_indels") { if (!svr_parse_int(v.c_str(), &pile_indels) || pile_indels < 1 || pile_indels > 15) return usage("-pileup_indels must be 1 to 15"); }
         else if (a == "-pileup_insertions") { if (v.empty()) return usage("-pileup_insertions takes a file"); ins_path = v; }
+        else if (a == "-pileup_deletions") { if (v.empty()) return usage("-pileup_deletions takes a file"); del_path = v; }
         else if (a == "-call_insertions") { if (v.empty()) return usage("-call_insertions takes a file"); call_ins_path = v; }
         else if (a == "-call") { if (v.empty()) return usage("-call takes a file"); call_path = v; }
         else if (a == "-pileup_loci") { if (v.empty()) return usage("-pileup_loci takes a file"); loci_path = v; }
@@ -331,6 +341,8 @@ int main(int argc, char** argv)
     if (pile_indels && !pileup) return usage("-pileup_indels needs -pileup file");
     const bool insertions = !ins_path.empty();
     if (insertions && !pile_indels) return usage("-pileup_insertions needs -pileup file -pileup_indels W");
+    const bool deletions = !del_path.empty();
+    if (deletions && !pile_indels) return usage("-pileup_deletions needs -pileup file -pileup_indels W");
     const bool call = !call_path.empty();
     if (call && !pileup) return usage("-call needs -pileup file");
     const bool loci = !loci_path.empty(), call_loci = !call_loci_path.empty();
@@ -461,6 +473,8 @@ int main(int argc, char** argv)
     if (pileup && !(pile_out = fopen(pileup_path.c_str(), "w"))) return usage("-pileup " + pileup_path + ": can't write " + pileup_path);
     FILE* ins_out = nullptr;
     if (insertions && !(ins_out = fopen(ins_path.c_str(), "w"))) return usage("-pileup_insertions " + ins_path + ": can't write " + ins_path);
+    FILE* del_out = nullptr;
+    if (deletions && !(del_out = fopen(del_path.c_str(), "w"))) return usage("-pileup_deletions " + del_path + ": can't write " + del_path);
     FILE* call_ins_out = nullptr;
     if (call_ins && !(call_ins_out = fopen(call_ins_path.c_str(), "w"))) return usage("-call_insertions " + call_ins_path + ": can't write " + call_ins_path);
     FILE* call_out = nullptr;
@@ -590,6 +604,7 @@ int main(int argc, char** argv)
     long long call_calls = 0, call_cands = 0, call_tested = 0, call_deep = 0;
     long long loci_lines = 0, loci_bases = 0, loci_nonref = 0, loci_disc = 0, lcall_calls = 0, lcall_cands = 0, lcall_tested = 0, lcall_deep = 0;
     long long ins_alleles = 0, ins_events = 0, ins_amb = 0, ins_span = 0;
+    long long del_alleles = 0, del_events = 0, del_ragged = 0, del_bases = 0;
     long long icall_calls = 0, icall_cands = 0, icall_tested = 0, icall_deep = 0;
     long long iloci_alleles = 0, iloci_events = 0, iloci_amb = 0, iloci_span = 0, ilcall_calls = 0, ilcall_cands = 0, ilcall_tested = 0, ilcall_deep = 0;
     const size_t pile_cols = pile_indels ? 8 : 5;
@@ -697,6 +712,38 @@ int main(int argc, char** argv)
             if (prc == MIPGEN_OK) { irecs[r & 1].resize((size_t)it->alleles); prc = mipgen_accel_insertions_fetch(h, irecs[r & 1].data(), it->alleles); }
             if (prc == MIPGEN_OK) { ins_alleles += it->alleles; ins_events += it->insertions; ins_amb += it->ambiguous; ins_span += it->span; }
             return prc;
+        };
+        // -pileup_deletions: one more call per row, the deletions call, feeds DEL only; its records (ascending position, so table order) as lines.  The deleted bytes
+        // are the template's, reverse-complemented on a '-' probe (only A C G T complement)
+        std::vector<mipgen_deletion_record> drecs[2];
+        auto row_deletions = [&](size_t r) {
+            mipgen_deletion_totals dt{0, 0, 0, 0, 0, 0, 0, 0};
+            int prc = mipgen_accel_reads_consensus_deletions(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)r, (int32_t)pile_family, (int32_t)pile_quality,
+                                                             (int32_t)pile_indels, nullptr, nullptr, &dt);
+            if (prc == MIPGEN_OK) { drecs[r & 1].resize((size_t)dt.alleles); prc = mipgen_accel_deletions_fetch(h, drecs[r & 1].data(), dt.alleles); }
+            if (prc == MIPGEN_OK) { del_alleles += dt.alleles; del_events += dt.events; del_ragged += dt.ragged; del_bases += dt.deleted_bases; }
+            return prc;
+        };
+        auto write_deletions = [&](size_t r, const std::vector<mipgen_deletion_record>& rec) {
+            const char* sample = !by_sample ? "*" : r + 1 < n_rows ? sample_labels[r].c_str() : "undetermined";
+            std::string text;
+            char buf[160];
+            for (const mipgen_deletion_record& q : rec) {
+                const size_t i = (size_t)(std::upper_bound(pos_off.begin(), pos_off.end(), q.pos) - pos_off.begin()) - 1;
+                const std::vector<std::string>& f = *rows[i];
+                const RowCoords& c = coords[i];
+                const long a = (long)(q.pos - pos_off[i]);
+                std::string deleted = mol_seq.substr((size_t)q.pos, (size_t)q.length);
+                if (c.minus) {
+                    std::reverse(deleted.begin(), deleted.end());
+                    for (char& ch : deleted) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
+                }
+                snprintf(buf, sizeof buf, "\t%ld\t%c\t%d\t", c.minus ? c.ext_stop - (a + q.length - 1) : c.ext_start + a, c.minus ? '-' : '+', q.length);
+                text.append(sample).append("\t").append(f[COL_KEY]).append("\t").append(f[COL_CHR]).append(buf).append(deleted);
+                snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%lld\n", q.ragged, q.count, q.depth, (long long)q.count * 1000000ll / q.depth);
+                text.append(buf);
+            }
+            fwrite(text.data(), 1, text.size(), del_out);
         };
         // -call: the records of a row (ascending position, then allele class) as lines; within a position the printed alts go A C G T -, which on a '-' probe is
         // the reverse of the class order of the four bases
@@ -828,6 +875,7 @@ int main(int argc, char** argv)
                                                        call_prm.bg_max_ppm) != MIPGEN_OK) return die();
         }
         if (insertions) fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tinserted\tcount\tspan\tppm\n", ins_out);
+        if (deletions) fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tdeleted\tragged\tcount\tdepth\tppm\n", del_out);
         if (call_ins) {
             fputs(">sample\tmip_key\tchr\tposition\tstrand\tlength\tinserted\tdepth\talt_count\talt_ppm\tbg_alt\tbg_depth\tq\n", call_ins_out);
             if (mipgen_accel_reads_consensus_insertion_pool(h, mol_seq.data(), mol_len.data(), n_probes32, (int32_t)pile_family, (int32_t)pile_quality, (int32_t)pile_indels,
@@ -888,6 +936,7 @@ int main(int argc, char** argv)
                 prc = row_insertions(r, nullptr, &it);
             }
             if (ins_loci && prc == MIPGEN_OK) prc = row_insertion_loci(r);              // one more call per row: it feeds ILOCI (and ILCALLS) only
+            if (deletions && prc == MIPGEN_OK) prc = row_deletions(r);                  // one more call per row: it feeds DEL only
             if (pile_indels) { pt.used = gt.used; pile_gapped += gt.gapped_sides; }
             if (writer.joinable()) writer.join();
             if (prc != MIPGEN_OK) return die();
@@ -898,12 +947,14 @@ int main(int argc, char** argv)
                 if (loci) write_loci(r, ltable[r & 1], lrecs[r & 1]);
                 if (insertions) write_insertions(r, ianch[r & 1], irecs[r & 1]);
                 if (call_ins) write_insertion_calls(r, icrecs[r & 1]);
+                if (deletions) write_deletions(r, drecs[r & 1]);
                 if (ins_loci) write_insertion_loci(r, lanch[r & 1], lirecs[r & 1], licrecs[r & 1]);
             });
         }
         if (writer.joinable()) writer.join();
         if (fclose(pile_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, pileup_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (insertions && fclose(ins_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, ins_path.c_str()); mipgen_accel_destroy(h); return 1; }
+        if (deletions && fclose(del_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, del_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call_ins && fclose(call_ins_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_ins_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (call && fclose(call_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, call_path.c_str()); mipgen_accel_destroy(h); return 1; }
         if (loci && fclose(loci_out) != 0) { fprintf(stderr, "%s: error writing %s\n", PROG, loci_path.c_str()); mipgen_accel_destroy(h); return 1; }
@@ -999,5 +1050,6 @@ int main(int argc, char** argv)
     if (tag_mism)
         fprintf(stderr, "%s: tag_mismatches 1 raw %lld groups %lld absorbed %lld moved_pairs %lld max_depth %lld\n", PROG, (long long)tmt.raw_groups, (long long)tmt.groups,
                 (long long)tmt.absorbed, (long long)tmt.moved_pairs, (long long)tmt.max_depth);
+    if (deletions) fprintf(stderr, "%s: deletion alleles %lld events %lld ragged %lld deleted_bases %lld\n", PROG, del_alleles, del_events, del_ragged, del_bases);
     return 0;
 }
